@@ -2,7 +2,7 @@
 """bench.py — BASELINE.json's metric (Mrays/s + ms/frame at 1080p / 64 spp; RMSE vs the CPU reference) for the wavefront
 path tracer on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]    (N > 1: launched by torch.distributed.run, one rank per GPU)
 
 A "step" is one full frame of the headline workload: the 1M-triangle Cornell scene (BASELINE.md §3, C5's scene),
 1920x1080, 64 spp, max depth 8 — scene, BVH and all path state resident in HBM before the timed region.
@@ -29,6 +29,10 @@ Extra objects on the JSON line (rank 0; all measured outside the timed region):
                  timed the same way with the same roofline object for its dominant kernel.
   ranks        : (N > 1) every rank's wall time, rays, kernel time per frame (max / mean), and the HBM-side bandwidth its share
                  stands for (bytes per ray of the single-GPU counter pass x its rays / its kernel time) against both peaks.
+
+--dump-outputs DIR (rank 0) writes what the last timed step computed: DIR/frame.npy, the float32 framebuffer (H, W, 4), and
+DIR/rays.npy, the rays traced for that frame (float64). A frame larger than 64 MB is replaced by a fixed seeded sample of its
+pixels, DIR/frame.npy (n, 4) with their row-major indices in DIR/pixel_index.npy. Inputs are seeded: same arguments, same inputs.
 """
 import argparse
 import hashlib
@@ -41,10 +45,11 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0          # MI355X spec, /opt/skills/guides/MI355X_MICROARCH.md "HBM3E peak BW"
-HBM_ACHIEVABLE_GBS = 6290.0    # measured achievable, same guide ("8 TB/s peak (spec); ~6.3 TB/s achievable"; SURVEY 8d quotes 6.29)
+HBM_PEAK_GBS = 8000.0          # MI355X spec, HBM3E peak bandwidth
+HBM_ACHIEVABLE_GBS = 6290.0    # measured achievable ("8 TB/s peak (spec); ~6.3 TB/s achievable"; SURVEY 8d quotes 6.29)
 VALU_PEAK_GINST = 1024 * 2.4 / 2.0  # G wave64 VALU instructions per second: 256 CUs x 4 SIMD-32, 2 cycles per instruction, 2.4 GHz max clock
 KERNEL_NAMES = {0: "unprobed", 1: "k_extend", 2: "k_extend_packed", 3: "k_extend_pool"}
+DUMP_LIMIT_BYTES = 64_000_000
 
 
 def main():
@@ -68,6 +73,7 @@ def main():
     ap.add_argument("--kernel", default="auto", choices=["auto", "simple", "packed", "pool"],
                     help="extend kernel: auto = probed per scene in the first frame (the default), else forced (profiling passes force it so that "
                          "no probe iteration sits inside the one profiled frame)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed frame and its ray count as DIR/<name>.npy (rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the oracle legs (cpu_baseline and parity)")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-configs", action="store_true", help="skip the other BASELINE configs")
@@ -79,6 +85,8 @@ def main():
     ap.add_argument("--rehearse-gloo", action="store_true",
                     help="N>1 ranks on ONE GPU over gloo (CPU-staged gather): rehearsal of the N>1 code path, not a measurement")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import numpy as np
     import torch
@@ -179,6 +187,8 @@ def main():
         elapsed, rays_all = max(t[0] for t in per_rank), sum(t[1] for t in per_rank)
     else:
         rays_all = float(rays)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, frame, rays_all / args.steps)  # every timed frame is the same frame: its rays are the mean
 
     if exchange and (args.rehearse_gloo or args.force_exchange) and rank == 0:
         # the rehearsal also proves the partition: the assembled frame must equal a single-rank frame bit for bit
@@ -265,6 +275,19 @@ def main():
     if exchange:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(path, frame, rays):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "rays.npy"), np.array([rays], np.float64))
+    if frame.nbytes > DUMP_LIMIT_BYTES:
+        px = frame.reshape(-1, frame.shape[-1])
+        n = DUMP_LIMIT_BYTES // (px.itemsize * px.shape[1] + 8)
+        idx = np.sort(np.random.default_rng(0x5EED0001).choice(len(px), n, replace=False))
+        np.save(os.path.join(path, "pixel_index.npy"), idx.astype(np.float64))
+        frame = px[idx]
+    np.save(os.path.join(path, "frame.npy"), np.ascontiguousarray(frame, np.float32))
 
 
 def source_hash():

@@ -8,7 +8,10 @@ tests/test_spirv_pin.py holds the oracle's claimed operation order against. It i
 fixes the arithmetic of SURVEY.md §8a rows a1-a3 (reciprocal multiply for /1080, FMA-contracted discriminant and
 numerator, one divide, two normalisations, strict `> 0`).
 
-Run in the build container (the reference tree does not travel to the GPU box):  python tests/golden/make_spirv_ops.py
+Run with the reference checkout at hand:
+    python tests/golden/make_spirv_ops.py <reference>/RayTracing/Assets/Shaders/Compiled/Ray/Test.spirv
+encode() is decode()'s inverse: tests/test_spirv_pin.py rebuilds the module's bytes from the committed table and checks their
+digest, so the tests need only the table.
 """
 import hashlib
 import json
@@ -17,7 +20,6 @@ import struct
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SPIRV = "/root/reference/RayTracing/Assets/Shaders/Compiled/Ray/Test.spirv"
 
 # the opcodes that occur in this module (SPIR-V 1.0 numbering) and the GLSL.std.450 extended instructions it uses
 OPCODES = {3: "OpSource", 5: "OpName", 11: "OpExtInstImport", 12: "OpExtInst", 14: "OpMemoryModel", 15: "OpEntryPoint", 16: "OpExecutionMode",
@@ -34,7 +36,7 @@ HAS_RESULT = {12, 43, 44, 54, 59, 61, 79, 80, 81, 112, 127, 129, 131, 133, 136, 
 LITERAL_TAIL = {81: 1, 79: None}  # OpCompositeExtract: composite id, then literal indices; OpVectorShuffle: two ids, then literal components
 
 
-def decode(path=SPIRV):
+def decode(path):
     raw = open(path, "rb").read()
     assert len(raw) % 4 == 0
     w = struct.unpack("<%dI" % (len(raw) // 4), raw)
@@ -68,9 +70,27 @@ def decode(path=SPIRV):
     return out
 
 
+def encode(out):
+    """The module's bytes from decode()'s table (header word 4, the schema, is 0 in every module)."""
+    ops = {v: k for k, v in OPCODES.items()}
+    ext = {v: k for k, v in GLSL450.items()}
+    major, minor = (int(x) for x in out["version"].split("."))
+    w = [0x07230203, major << 16 | minor << 8, int(out["generator"], 16), out["bound"], 0]
+    for rec in out["instructions"]:
+        op = ops.get(rec["op"]) or int(rec["op"][2:])
+        a = [rec[k] for k in ("type", "id") if k in rec]
+        if op == 12:
+            a += [rec["set"], ext.get(rec["inst"], rec["inst"])]
+        if op == 43:
+            a.append(int(rec["bits"], 16))
+        a += [int(x, 16) if isinstance(x, str) else x for x in rec["operands"]]
+        w += [(len(a) + 1) << 16 | op] + a
+    return struct.pack("<%dI" % len(w), *w)
+
+
 if __name__ == "__main__":
-    if not os.path.exists(SPIRV):
-        sys.exit(f"{SPIRV} not found: this script runs in the build container only")
+    if len(sys.argv) != 2 or not os.path.exists(sys.argv[1]):
+        sys.exit("usage: make_spirv_ops.py <reference>/RayTracing/Assets/Shaders/Compiled/Ray/Test.spirv")
     with open(os.path.join(HERE, "test_spirv_ops.json"), "w") as f:
-        json.dump(decode(), f, indent=0)
+        json.dump(decode(sys.argv[1]), f, indent=0)
     print("wrote tests/golden/test_spirv_ops.json")

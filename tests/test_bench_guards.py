@@ -44,3 +44,24 @@ def test_counter_profiles_are_dropped_when_anything_differs(monkeypatch):
     monkeypatch.setattr(b, "source_hash", lambda: "0" * 64)  # the kernels changed since the counters were taken
     pmc, why = b.load_pmc("tess", key, kern)
     assert pmc is None and "stale" in why
+
+
+def test_dump_outputs_is_complete_or_a_fixed_sample(tmp_path):
+    """--dump-outputs: the whole frame while it fits 64 MB, else the same seeded pixel sample every run, within the limit."""
+    import numpy as np
+    b = _bench()
+    frame = np.random.default_rng(1).random((360, 640, 4), dtype=np.float32)
+    b.dump_outputs(str(tmp_path / "small"), frame, 1234.0)
+    assert np.array_equal(np.load(tmp_path / "small" / "frame.npy"), frame)
+    assert np.load(tmp_path / "small" / "rays.npy").tolist() == [1234.0]
+    assert not (tmp_path / "small" / "pixel_index.npy").exists()
+    big = np.zeros((2160, 3840, 4), np.float32)
+    big.reshape(-1, 4)[:, 0] = np.arange(2160 * 3840)
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), big, 1.0)
+    got = {d: {n: np.load(tmp_path / d / f"{n}.npy") for n in ("frame", "pixel_index", "rays")} for d in ("a", "b")}
+    assert all(np.array_equal(got["a"][n], got["b"][n]) for n in got["a"])
+    idx, px = got["a"]["pixel_index"], got["a"]["frame"]
+    assert idx.dtype == np.float64 and px.dtype == np.float32 and px.shape == (len(idx), 4)
+    assert np.array_equal(px[:, 0], idx) and len(np.unique(idx)) == len(idx)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64_000_000 + 1024

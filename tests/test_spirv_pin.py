@@ -9,12 +9,12 @@ import json
 import os
 
 import numpy as np
-import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 OPS = json.load(open(os.path.join(HERE, "golden", "test_spirv_ops.json")))
 INS = OPS["instructions"]
 BY_ID = {i["id"]: i for i in INS if "id" in i}
+TEST_SPIRV_SHA256 = "051e3943762e15c4331937cf14d8bcb8bb281fc8ba744d7a116d3593419c9f0f"  # RayTracing/Assets/Shaders/Compiled/Ray/Test.spirv
 
 
 def const(i):
@@ -32,16 +32,19 @@ def only(op, **kw):
     return hits[0]
 
 
-def test_fixture_is_the_reference_file():
-    """In the build container the fixture is re-derived from the reference's file; on the GPU box (no /root/reference) it is data."""
+def test_fixture_is_the_reference_file(tmp_path):
+    """The fixture is the reference's Test.spirv decoded without loss: the words it holds rebuild a 1,524-byte module with that
+    file's sha256, and decoding those bytes gives the fixture back."""
+    import hashlib
     import importlib.util
     spec = importlib.util.spec_from_file_location("make_spirv_ops", os.path.join(HERE, "golden", "make_spirv_ops.py"))
     m = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(m)
-    if not os.path.exists(m.SPIRV):
-        pytest.skip("reference tree not present (GPU box): the committed fixture stands")
-    assert m.decode() == OPS
-    assert OPS["bytes"] == 1524
+    raw = m.encode(OPS)
+    assert len(raw) == OPS["bytes"] == 1524
+    assert hashlib.sha256(raw).hexdigest() == OPS["sha256"] == TEST_SPIRV_SHA256
+    (tmp_path / "Test.spirv").write_bytes(raw)
+    assert m.decode(str(tmp_path / "Test.spirv")) == OPS
 
 
 def test_dispatch_shape_and_store():
