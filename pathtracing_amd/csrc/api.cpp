@@ -51,6 +51,62 @@ template <typename T> struct DevBuf {
     void adopt(void *q, size_t count) { release(); p = (T *)q; n = count; } // take over a hipMalloc-ed array
 };
 
+// Which extend kernel a frame runs. A frame's PT_FLAG_EXTEND_* beats pt_tuning.extend_kernel, which beats the scene's own choice, measured:
+//   inside a frame : iteration 2 of group 0 runs the one-ray-per-lane kernel, iteration 3 the lane-packing one (bit-identical results), each
+//                    bracketed by events; accepted only if both traced a real share of the frame's slots;
+//   across frames  : a frame too short for that (few samples per stream: it is over in two iterations) runs whole on one kernel — the first
+//                    on the one-ray-per-lane kernel, the next on the lane-packing one — and the rays per millisecond of the two frames decide.
+// The faster per ray wins (packed needs +10 %). Deep incoherent traversals (1M-triangle soup) gain ~2.5x from packing, shallow ones (walls of
+// a box) lose ~35 %, and no static property of the tree tells them apart. Counting / profiling frames neither probe nor feed
+// the decision: their kernels are instrumented builds. A probing frame runs one loop and no finish mode, so that its timed iterations compare.
+uint32_t faster(double rate_simple, double rate_packed) { return rate_packed > 1.10 * rate_simple ? EXT_PACKED : EXT_SIMPLE; }
+struct ExtendChoice {           // what a scene remembers
+    uint32_t kernel = 0;        // the ExtendKernel an earlier frame picked (0 = none yet)
+    double rate_simple = 0.0, rate_packed = 0.0; // rays per ms of whole frames run on one kernel (frames too short to probe inside)
+    uint32_t misses = 0;        // warm frames too small to time: after three the scene settles on the one-ray-per-lane kernel for good
+};
+struct ExtendFrame {            // the choice during one frame
+    ExtendChoice &mem;
+    bool undecided;             // nothing forces a kernel and the scene has not picked one: this frame measures (whole, on frame_kernel)
+    uint32_t frame_kernel, kernel; // kernel: 0 = probing inside this frame, else the ExtendKernel every iteration uses
+    bool mixed = false;         // this frame ran probe iterations on both kernels: its overall rate says nothing about either
+    uint64_t probe_n[2] = { 0, 0 }; // rays traced by probe iterations 2 and 3
+    ExtendFrame(ExtendChoice &m, uint32_t forced, bool instrumented) : mem(m),
+        undecided(forced == 0u && m.kernel == 0u && !instrumented),
+        frame_kernel((undecided && m.rate_simple > 0.0 && m.rate_packed == 0.0) ? EXT_PACKED : EXT_SIMPLE), // first the default, then the other
+        kernel(forced ? forced : m.kernel ? m.kernel : (undecided && frame_kernel == EXT_SIMPLE) ? 0u : frame_kernel) {}
+    bool probing(uint32_t g, uint32_t it) const { return g == 0u && kernel == 0u && (it == 2u || it == 3u); }
+    int launch_kernel(uint32_t g, uint32_t it, bool split) const { return (kernel == EXT_PACKED || (probing(g, it) && it == 3u)) ? EXT_PACKED : (kernel == EXT_POOL && !split) ? EXT_POOL : EXT_SIMPLE; }
+    // default path vertices per launch. Lane-packing: a lane pulls a new entry whenever its budget ends, so a long budget costs nothing and saves
+    // launches (ms per frame with 8 / 16 / 32 / 64 vertices, tools/exp_packed.py: 1M soup 72.2 / 71.5 / 70.5 / 67.4, at 256 spp 277.6 / 271.8 /
+    // 268.3 / 266.1, 5k soup 7.99 / 7.43 / 7.35 / 7.39); the probe iteration keeps 8 so that it stays comparable with the one before it
+    uint32_t bounces(uint32_t g, uint32_t it, int k, uint32_t simple) const { return k != EXT_PACKED ? simple : probing(g, it) ? 8u : 64u; }
+    // loop g's readback of iteration `it`, which traced `traced` rays; by iteration 3's, both probe iterations and their events `ev` (start and
+    // end of each, pt_context::ev_probe) are complete
+    hipError_t observe(uint32_t g, uint32_t it, uint64_t traced, uint32_t loop_slots, const hipEvent_t *ev)
+    {
+        if (!probing(g, it)) return hipSuccess;
+        probe_n[it - 2u] = traced;
+        if (it == 2u) return hipSuccess;
+        float ms_simple = 0.f, ms_packed = 0.f; hipError_t e = hipEventElapsedTime(&ms_simple, ev[0], ev[1]);
+        if (e != hipSuccess || (e = hipEventElapsedTime(&ms_packed, ev[2], ev[3])) != hipSuccess) return e;
+        const uint64_t enough = (uint64_t)loop_slots / 8u; // each probe iteration must have traced a real share of the slots
+        if (probe_n[0] < enough || probe_n[1] < enough) { // inconclusive (the frame was all but over): finish on the default, whole frames decide
+            kernel = EXT_SIMPLE; mixed = probe_n[1] >= enough / 8u; // did the lane-packing iteration trace enough to colour this frame's rate?
+        } else kernel = mem.kernel = faster(probe_n[0] / std::max((double)ms_simple, 1e-6), probe_n[1] / std::max((double)ms_packed, 1e-6));
+        return hipSuccess;
+    }
+    // the whole frame: a warm one (cold = it had to allocate: first touch of fresh memory is 30 % slower, not a measurement) on one
+    // kernel of at least 2^20 rays gives that kernel's rate
+    void frame_done(uint64_t rays, double gpu_ms, bool cold)
+    {
+        if (!undecided || mem.kernel != 0u || cold) return;
+        if (mixed || rays < (1u << 20) || !(gpu_ms > 0.0)) { if (++mem.misses >= 3u) mem.kernel = EXT_SIMPLE; return; }
+        (frame_kernel == EXT_PACKED ? mem.rate_packed : mem.rate_simple) = (double)rays / gpu_ms;
+        if (mem.rate_simple > 0.0 && mem.rate_packed > 0.0) mem.kernel = faster(mem.rate_simple, mem.rate_packed);
+    }
+};
+
 } // namespace
 
 struct pt_context {
@@ -63,13 +119,17 @@ struct pt_context {
     // what the partial sums in `acc` currently hold (PT_FLAG_ACCUMULATE continues them): frame geometry and samples so far
     uint32_t acc_w = 0, acc_h = 0, acc_rank = 0, acc_nranks = 0, acc_streams = 0, acc_seed = 0;
     uint64_t acc_spp = 0;
-    DevBuf<float2> hit;
-    DevBuf<uint32_t> sd, q_ext0, q_ext1, q_b[B_COUNT], counters, fb8;
+    DevBuf<float2> hit;             // split frames only (k_shade reads what the extend kernel found), like the two specular buckets
+    DevBuf<uint32_t> sd, q_ext0, q_ext1, q_metal, q_dielectric, counters, fb8;
     DevBuf<int32_t> stack_ovf;
     // What k_generate would write at the start of every frame of a fused pipeline, kept from the first frame of its kind: the first
     // extend queue (every shard's slots in slot order, holes for off-image pixels and sample-less streams) and the counter block
     // that goes with it. A frame then starts with one 2.4 KB device copy instead of a kernel over every slot; the first extend
     // launch reads q_init in place of q_ext[0] and zeroes the radiance sums of the slots it starts (kernels.hip, it == 0).
+    // Invariant: a template may start a non-accumulate frame only if every `acc` slot its first queue does not start holds zero. A template in
+    // which every stream has a sample starts every in-image slot (off-image slots are never written). A dense one (first_spp < streams) leaves
+    // whole streams out: the non-accumulate frame that builds it zeroes them, and start_frame drops it after any other kind of frame, since
+    // accumulate frames keep those streams' sums and full-state frames start every stream.
     DevBuf<uint32_t> q_init, cnt_init;
     struct InitKey { uint32_t w, h, rank, nranks, streams, first_spp, offset, n_slots, shard_cap; const void *q, *acc;
                      bool operator==(const InitKey &o) const { return std::memcmp(this, &o, sizeof *this) == 0; } } init_key{};
@@ -78,33 +138,28 @@ struct pt_context {
     uint32_t *h_counts = nullptr; // pinned: kLag readbacks of the per-shard queue sizes (pt_tuning.readback = 1) + one copy of all counters
     uint4 *h_ring = nullptr, *d_ring = nullptr; // mapped pinned memory the extend kernels report their queue sizes to, kLag x kShards lines
                                                 // (host address, device address); PathState::host_ring
-    uint32_t readback = 0;                      // pt_tuning.readback: 0 = the kernels store the sizes to h_ring, 1 = one 2-4 KB copy per launch
-    uint32_t extend_kernel = 0;                 // pt_tuning.extend_kernel: 0 = probed per scene, else the ExtendKernel every scene uses
     hipEvent_t ev_lag[kMaxGroups][kLag] = {};
     hipStream_t group_stream[kMaxGroups] = {}; // group 0 runs on `stream` when there is one group only
     hipEvent_t ev_fork = nullptr, ev_join[kMaxGroups] = {};
-    uint32_t groups = 0;                        // pt_tuning.loops (1, 2, 4) overrides; 0 = two loops, whose launch tails overlap. Measured
-                                                // (tools/exp_loops.py, ms per frame with 1 / 2 / 4 loops): 1M-tri Cornell 1080p/64spp 18.42 /
-                                                // 18.08 / 18.77, a rank's 1/8 of it 4.11 / 3.81 / -, soup 76.2 / 73.3 / 72.3, glass 256 spp
-                                                // 37.8 / 37.0 / 36.6, 4K/1024 spp 1062 / 1051 / 1046. Frames that time single kernels
-                                                // (PT_FLAG_PROFILE_KERNELS, visit counting, the extend-kernel probe) run one loop, so that
-                                                // a timed launch has the GPU to itself.
-    uint32_t bounces = 0;                       // pt_tuning.bounces (1..64): path vertices per launch of the fused kernel (state in registers);
-                                                // 0 = 3/4 max_depth - 2 clamped to [4, 12]: depth 8 -> 4, depth 16 -> 10 (ms per frame with 2 / 3 /
-                                                // 4 / 6 / 8 / 12 vertices: 1M-triangle Cornell, depth 8: 18.57 / 17.80 / 17.52 / 17.50 / 17.68 / 17.87;
-                                                // Cornell+glass+metal, depth 16: 47.5 / 41.0 / 38.3 / 35.3 / 34.3 / 33.5)
-    double compact_below = 0.9;                // pt_tuning.compact_below: a shard re-packs its queue in a launch that would leave alive/length
-                                                // below this (>1 = every launch, 0 = never); else carried in place (want_compact, kernels.hip).
-    uint32_t lag = 0;                           // pt_tuning.lag (2..4; 0 = by frame length, see render_frame)
-    uint32_t sticky_samples = 32;               // pt_tuning.sticky_samples. Measured, 1M-tri Cornell 1080p, ms per frame by spp (8 streams),
-                                                // start-of-launch ratio (round 1) / predicted ratio / sticky / every launch:
-                                                //   8: 4.13/4.20/4.07/3.01  32: 10.95/10.93/9.70/9.61  64: 19.28/18.82/18.45/18.36
-                                                //   128: 38.15/36.12/36.04/36.06  256: 73.06/71.95/71.99/72.15  512: 142.8/141.5/143.0/143.7
-                                                //   1024: 284.5/283.7/289.9/292.5; 4K/1024: 1067.7/1064.1/1097.0/1108 (tools/exp_compact.py)
-    double sparse_below = 0.0;                  // pt_tuning.sparse_below (0 = off, the default: measured ±0): see PathState::sparse_below
-    uint32_t finish_below = 4096;             // pt_tuning.finish_below: a shard with no more alive paths than this runs them to
-                                                // their end in one launch of the fused kernel (0 = never)
-    uint32_t packed_chunk = 0;                  // pt_tuning.packed_chunk: queue entries per wavefront of the lane-packing kernel (0 = by stream count)
+    pt_tuning tuning = { // the scheduling knobs (include/ptrt.h): defaults and the measurements behind them
+        0,    // bounces (1..64): path vertices per launch of the fused kernel (state in registers); 0 = 3/4 max_depth - 2 clamped to
+              // [4, 12]: depth 8 -> 4, depth 16 -> 10 (ms per frame with 2 / 3 / 4 / 6 / 8 / 12 vertices: 1M-triangle Cornell, depth 8:
+              // 18.57 / 17.80 / 17.52 / 17.50 / 17.68 / 17.87; Cornell+glass+metal, depth 16: 47.5 / 41.0 / 38.3 / 35.3 / 34.3 / 33.5)
+        0,    // loops (1, 2, 4) overrides; 0 = two loops, whose launch tails overlap. Measured (tools/exp_loops.py, ms per frame with
+              // 1 / 2 / 4 loops): 1M-tri Cornell 1080p/64spp 18.42 / 18.08 / 18.77, a rank's 1/8 of it 4.11 / 3.81 / -, soup 76.2 / 73.3 /
+              // 72.3, glass 256 spp 37.8 / 37.0 / 36.6, 4K/1024 spp 1062 / 1051 / 1046. Frames that time single kernels
+              // (PT_FLAG_PROFILE_KERNELS, visit counting, the extend-kernel probe) run one loop, so that a timed launch has the GPU to itself.
+        4096, // finish_below: a shard with no more alive paths than this runs them to their end in one launch of the fused kernel (0 = never)
+        0,    // packed_chunk: queue entries per wavefront of the lane-packing kernel (0 = by stream count)
+        0.9f, // compact_below: a shard re-packs its queue in a launch that would leave alive/length below this (>1 = every launch, 0 = never); else carried in place (want_compact)
+        0.f,  // sparse_below (0 = off, the default: measured ±0): see PathState::sparse_below
+        32,   // sticky_samples. Measured, 1M-tri Cornell 1080p, ms per frame by spp (8 streams), start-of-launch ratio (round 1) / predicted ratio / sticky / every launch:
+              //   8: 4.13/4.20/4.07/3.01  32: 10.95/10.93/9.70/9.61  64: 19.28/18.82/18.45/18.36  128: 38.15/36.12/36.04/36.06
+              //   256: 73.06/71.95/71.99/72.15  512: 142.8/141.5/143.0/143.7  1024: 284.5/283.7/289.9/292.5; 4K/1024: 1067.7/1064.1/1097.0/1108 (tools/exp_compact.py)
+        0,    // lag (2..5; 0 = by frame length, see plan_frame)
+        0,    // extend_kernel: 0 = probed per scene (ExtendChoice), else the ExtendKernel every scene uses
+        0,    // readback: 0 = the kernels store the sizes to h_ring, 1 = one 2-4 KB copy per launch (pt_context_create falls back to it)
+    };
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
     hipEvent_t ev_probe[4] = {}; // brackets of the two probe iterations that pick the extend kernel
     std::vector<hipEvent_t> ev_pool;
@@ -132,10 +187,7 @@ struct pt_scene {
     uint64_t n_blob_tris() const { return device_packed ? tri_mat.size() : bvh.tris.size(); }
     DevBuf<float4> d_nodes, d_tris, d_spheres, d_mats;
     bool has_specular = false;
-    mutable uint32_t ext_choice = 0;     // cache, not scene content: the extend kernel an earlier frame's probe picked (0 = none yet, ExtendKernel otherwise)
-    mutable double rate_simple = 0.0, rate_packed = 0.0; // rays per ms of whole frames run on one kernel (frames too short to probe inside)
-    mutable uint32_t probe_misses = 0;   // warm frames that neither decided nor fed the decision (too few rays to time): after three the scene
-                                         // settles on the one-ray-per-lane kernel instead of staying in probe mode (one loop, no finish mode) for good
+    mutable ExtendChoice ext;            // cache, not scene content: what earlier frames measured
     DevBuf<uint2> d_sph_mat;
     DeviceScene ds{};
 };
@@ -186,6 +238,22 @@ hipEvent_t pool_event(pt_context *c, size_t i)
     return c->ev_pool[i];
 }
 
+void drain(pt_context *c) // nothing of the context's may still run: on its loop streams or its own
+{
+    for (auto &gs : c->group_stream) if (gs) (void)hipStreamSynchronize(gs);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+}
+
+struct Frame {                  // a path-traced frame as plan_frame lays it out, and what its loops leave for finish_frame
+    uint32_t nranks, streams, pixel_slots, n_slots, shard_cap, samples_per_stream, lag, n_loops, packed_chunk, default_bounces;
+    uint32_t forced;            // ExtendKernel a frame flag or pt_tuning.extend_kernel forces (0 = none)
+    bool profile, count, split, bucket, full_state, accumulate, mapped, compact;
+    size_t q_entries; uint64_t total_spp, allocs_before;
+    PathState ps; FrameParams fp;
+    uint32_t iters; uint64_t slot_launches; size_t n_events; // launches of the longest loop, paths alive at launch starts, profile events
+    std::vector<uint64_t> trace_alive, trace_rays;
+};
+
 } // namespace
 
 namespace ptrt {
@@ -232,7 +300,7 @@ pt_status pt_context_create(const pt_device_desc *desc, pt_context **out)
             std::memset(c->h_ring, 0, sizeof(uint4) * kLag * kShards);
         else {
             if (c->h_ring) (void)hipHostFree(c->h_ring);
-            c->h_ring = c->d_ring = nullptr; c->readback = 1u;
+            c->h_ring = c->d_ring = nullptr; c->tuning.readback = 1u;
             (void)hipGetLastError();
         }
     }
@@ -254,10 +322,7 @@ pt_status pt_context_create(const pt_device_desc *desc, pt_context **out)
 pt_status pt_context_get_tuning(const pt_context *c, pt_tuning *o)
 {
     if (!c || !o) return fail(nullptr, PT_ERR_INVALID_ARGUMENT, "pt_context_get_tuning: NULL argument");
-    std::memset(o, 0, sizeof *o);
-    o->bounces = c->bounces; o->loops = c->groups; o->finish_below = c->finish_below; o->packed_chunk = c->packed_chunk;
-    o->compact_below = (float)c->compact_below; o->sparse_below = (float)c->sparse_below; o->sticky_samples = c->sticky_samples; o->lag = c->lag;
-    o->extend_kernel = c->extend_kernel; o->readback = c->readback;
+    *o = c->tuning;
     return PT_OK;
 }
 
@@ -270,12 +335,10 @@ pt_status pt_context_set_tuning(pt_context *c, const pt_tuning *t)
     if (t->lag != 0 && (t->lag < 2 || t->lag > kLag)) return fail(c, PT_ERR_INVALID_ARGUMENT, "tuning: lag must be 0 (default) or 2..%u", kLag);
     if (!(t->compact_below >= 0.f && t->compact_below <= 2.f) || !(t->sparse_below >= 0.f && t->sparse_below <= 1.f))
         return fail(c, PT_ERR_INVALID_ARGUMENT, "tuning: compact_below must be in [0,2], sparse_below in [0,1]");
-    c->bounces = t->bounces; c->groups = t->loops; c->finish_below = t->finish_below; c->packed_chunk = t->packed_chunk;
     if (t->extend_kernel > (uint32_t)EXT_POOL) return fail(c, PT_ERR_INVALID_ARGUMENT, "tuning: extend_kernel must be 0 (probed), 1 (one ray per lane), 2 (lane-packing) or 3 (pooled)");
     if (t->readback > 1) return fail(c, PT_ERR_INVALID_ARGUMENT, "tuning: readback must be 0 (mapped store) or 1 (copy per launch)");
     if (t->readback == 0 && !c->d_ring) return fail(c, PT_ERR_UNSUPPORTED, "tuning: readback 0 needs host-mapped pinned memory, which this platform did not provide");
-    c->compact_below = t->compact_below; c->sparse_below = t->sparse_below; c->sticky_samples = t->sticky_samples; c->lag = t->lag;
-    c->extend_kernel = t->extend_kernel; c->readback = t->readback;
+    c->tuning = *t; // all or nothing: a refused call changes no field
     return PT_OK;
 }
 
@@ -283,18 +346,16 @@ void pt_context_destroy(pt_context *c)
 {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    for (auto &gs : c->group_stream) if (gs) (void)hipStreamSynchronize(gs); // nothing may still run on the buffers released below
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    drain(c); // nothing may still run on the buffers released below
     c->ray_o.release(); c->ray_d.release(); c->thr.release(); c->acc.release(); c->tiles.release(); c->fb.release(); c->hit.release();
     c->sd.release(); c->q_ext0.release(); c->q_ext1.release(); c->counters.release(); c->fb8.release(); c->stack_ovf.release();
-    c->q_init.release(); c->cnt_init.release();
-    for (auto &q : c->q_b) q.release();
+    c->q_init.release(); c->cnt_init.release(); c->q_metal.release(); c->q_dielectric.release();
     if (c->h_counts) (void)hipHostFree(c->h_counts);
     if (c->h_ring) (void)hipHostFree(c->h_ring);
     for (auto &row : c->ev_lag) for (auto &e : row) if (e) (void)hipEventDestroy(e);
     for (auto &e : c->ev_join) if (e) (void)hipEventDestroy(e);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    for (auto &gs : c->group_stream) if (gs) { (void)hipStreamSynchronize(gs); (void)hipStreamDestroy(gs); }
+    for (auto &gs : c->group_stream) if (gs) (void)hipStreamDestroy(gs);
     for (auto &e : c->ev_probe) if (e) (void)hipEventDestroy(e);
     if (c->ev_start) (void)hipEventDestroy(c->ev_start);
     if (c->ev_stop) (void)hipEventDestroy(c->ev_stop);
@@ -526,7 +587,7 @@ pt_status pt_scene_commit(pt_scene *s, uint32_t bvh_width)
     for (int k = 0; k < 3; ++k) d.sky[k] = s->sky[k];
     d.bvh_width = bvh_width;
     d.cam = s->cam;
-    s->ext_choice = 0; s->rate_simple = s->rate_packed = 0.0; s->probe_misses = 0;
+    s->ext = ExtendChoice{};
     s->has_specular = false;
     for (const pt_material &m : s->mats) if (m.kind != PT_LAMBERT) s->has_specular = true;
     s->committed = true;
@@ -588,139 +649,105 @@ static pt_status ensure_frame(pt_context *c, uint32_t w, uint32_t h)
     return PT_OK;
 }
 
-static pt_status render_frame(pt_context *c, const pt_scene *s, const pt_render_params *p, pt_stats *stats);
-
-pt_status pt_render(pt_context *c, const pt_scene *s, const pt_render_params *p, pt_stats *stats)
+// Plan: validate, derive the frame's geometry and decoded flags, allocate what the frame uses, fill PathState and FrameParams
+static pt_status plan_frame(pt_context *c, const pt_scene *s, const pt_render_params *p, const pt_tile_layout &lay, Frame &f)
 {
-    const pt_status st = render_frame(c, s, p, stats);
-    if (st != PT_OK && c) { // an error exit may leave kernels in flight on the loop streams: nothing of this frame survives the call
-        (void)hipSetDevice(c->device);
-        for (auto &gs : c->group_stream) if (gs) (void)hipStreamSynchronize(gs);
-        if (c->stream) (void)hipStreamSynchronize(c->stream);
-        c->acc_spp = 0; c->fb_valid = false;
-    }
-    return st;
-}
-
-static pt_status render_frame(pt_context *c, const pt_scene *s, const pt_render_params *p, pt_stats *stats)
-{
-    if (!c || !p) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_render: NULL argument");
-    pt_tile_layout lay;
-    pt_status st = layout_of(p, &lay);
-    if (st != PT_OK) return fail(c, st, "pt_render: bad width/height/rank/nranks/tile_size");
-    HIP_TRY(c, hipSetDevice(c->device));
-    pt_stats out; std::memset(&out, 0, sizeof out);
-    c->fb_valid = false;
-    const bool profile = (p->flags & PT_FLAG_PROFILE_KERNELS) != 0, count = (p->flags & PT_FLAG_COUNT_VISITS) != 0;
-    // rays per wavefront of the lane-packing kernel: 256 once several sample streams keep the queues long, else 128 (measured)
-    const uint32_t packed_chunk = c->packed_chunk >= 64u ? c->packed_chunk : ((p->streams >= 4u) ? 256u : 128u);
-    const bool bucket_specular = (p->flags & PT_FLAG_BUCKET_SPECULAR) != 0;
-    const bool split_kernels = bucket_specular || (p->flags & PT_FLAG_SPLIT_KERNELS) != 0;
-    const uint32_t forced_choice = (p->flags & PT_FLAG_EXTEND_POOL) ? (uint32_t)EXT_POOL : (p->flags & PT_FLAG_EXTEND_PACKED) ? (uint32_t)EXT_PACKED
-                                   : (p->flags & PT_FLAG_EXTEND_SIMPLE) ? (uint32_t)EXT_SIMPLE : c->extend_kernel; // a flag beats pt_tuning.extend_kernel
-
-    if (p->mode == PT_REFERENCE_SPHERE) {
-        // Renderer.ComputeFrame: one dispatch, then the host blocks on the fence (Renderer.cs:1020,1036,972)
-        if ((st = ensure_frame(c, p->width, p->height)) != PT_OK) return st;
-        HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
-        HIP_TRY(c, launch_reference_sphere(c->stream, p->width, p->height, c->fb.p, c->fb8.p));
-        HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        float ms = 0.f; HIP_TRY(c, hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
-        out.gpu_ms = ms; out.other_ms = ms;
-        out.rays = out.paths = (uint64_t)p->width * p->height;
-        out.iterations = 1;
-        c->fb_valid = true;
-        if (stats) *stats = out;
-        return PT_OK;
-    }
-    if (p->mode != PT_PATH_TRACE) return fail(c, PT_ERR_INVALID_ARGUMENT, "unknown mode %u", p->mode);
     if (!s) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_render: scene is NULL");
     if (s->ctx != c) return fail(c, PT_ERR_INVALID_ARGUMENT, "scene belongs to another context");
     if (!s->committed) return fail(c, PT_ERR_NOT_COMMITTED, "scene not committed");
     if (p->spp == 0 || p->spp >= (1u << 24)) return fail(c, PT_ERR_INVALID_ARGUMENT, "spp must be in [1, 2^24)");
     if (p->max_depth == 0 || p->max_depth > 255) return fail(c, PT_ERR_INVALID_ARGUMENT, "max_depth must be in [1,255]");
     if (!std::isfinite(p->ray_eps) || p->ray_eps < 0.f) return fail(c, PT_ERR_INVALID_ARGUMENT, "ray_eps must be finite and >= 0");
-
     if (p->streams > 64) return fail(c, PT_ERR_INVALID_ARGUMENT, "streams must be in [0,64]");
-    const uint32_t nranks = p->nranks ? p->nranks : 1u;
-    const uint32_t streams = p->streams ? p->streams : 1u;
-    const uint32_t pixel_slots = lay.tiles_per_rank * kTilePixels;              // one slot per owned pixel ...
-    const uint64_t slots64 = (uint64_t)pixel_slots * streams;                   // ... per sample stream
+    const pt_tuning &t = c->tuning;
+    f.nranks = p->nranks ? p->nranks : 1u; f.streams = p->streams ? p->streams : 1u;
+    f.pixel_slots = lay.tiles_per_rank * kTilePixels;                  // one slot per owned pixel ...
+    const uint64_t slots64 = (uint64_t)f.pixel_slots * f.streams;      // ... per sample stream
     if (slots64 >= (1ull << 28)) return fail(c, PT_ERR_UNSUPPORTED, "frame too large: %llu slots (pixels of this rank x streams), limit 2^28", (unsigned long long)slots64); // kernels.hip at(): 32-bit byte offsets
-    const uint32_t n_slots = (uint32_t)slots64;
-
-    const uint64_t allocs_before = g_device_allocs;
-    HIP_TRY(c, c->ray_o.ensure(n_slots)); HIP_TRY(c, c->ray_d.ensure(n_slots)); HIP_TRY(c, c->thr.ensure(n_slots));
-    HIP_TRY(c, c->acc.ensure(n_slots)); HIP_TRY(c, c->tiles.ensure(pixel_slots)); HIP_TRY(c, c->hit.ensure(n_slots)); HIP_TRY(c, c->sd.ensure(n_slots));
-    // every queue = kShards regions of shard_cap entries; shard s owns the 2^kShardGroupShift-slot groups g with g % kShards == s
-    const uint32_t groups = (n_slots + (1u << kShardGroupShift) - 1u) >> kShardGroupShift, shard_cap = ((groups + kShards - 1) / kShards) << kShardGroupShift;
-    const size_t q_entries = (size_t)kShards * shard_cap;
-    HIP_TRY(c, c->q_ext0.ensure(q_entries)); HIP_TRY(c, c->q_ext1.ensure(q_entries));
-    for (auto &q : c->q_b) HIP_TRY(c, q.ensure(q_entries));
-    const uint32_t ovf = s->bvh.stack_need > kStackLds ? s->bvh.stack_need - kStackLds : 0u;
-    if (ovf) HIP_TRY(c, c->stack_ovf.ensure((size_t)ovf * q_entries));
-    if (nranks == 1) { if ((st = ensure_frame(c, p->width, p->height)) != PT_OK) return st; }
-
-    PathState ps{};
-    ps.ray_o = c->ray_o.p; ps.ray_d = c->ray_d.p; ps.hit = c->hit.p; ps.thr = c->thr.p; ps.sd = c->sd.p; ps.acc = c->acc.p;
-    ps.q_ext[0] = c->q_ext0.p; ps.q_ext[1] = c->q_ext1.p;
-    for (uint32_t b = 0; b < B_COUNT; ++b) ps.q_bucket[b] = c->q_b[b].p;
-    ps.counters = c->counters.p; ps.stack_ovf = c->stack_ovf.p; ps.stack_ovf_entries = ovf; ps.n_slots = n_slots; ps.shard_cap = shard_cap;
-    ps.shard_base = 0; ps.shard_count = kShards;
-    ps.compact_below = (float)c->compact_below; ps.finish_below = c->finish_below; ps.sparse_below = (float)c->sparse_below;
-    const uint32_t samples_per_stream = (p->spp + (p->streams ? p->streams : 1u) - 1u) / (p->streams ? p->streams : 1u);
-    ps.repack_sticky = (samples_per_stream <= c->sticky_samples && c->compact_below > 0.0) ? 1u : 0u;
-    const bool mapped = c->readback == 0u; // queue sizes reach the host by the kernels' own stores (fold_traced) instead of a copy per launch
-    ps.host_ring = mapped ? c->d_ring : nullptr; ps.ring_slots = kLag;
-    const bool repack_always = ps.repack_sticky && samples_per_stream <= 2u; // nothing (or next to nothing) regenerates: every launch leaves holes
-
-    FrameParams fp{};
-    fp.width = p->width; fp.height = p->height; fp.spp = p->spp; fp.max_depth = p->max_depth; fp.rr_start = p->rr_start;
-    fp.seed_hashed = host_pcg(p->seed); fp.sample_offset = p->sample_offset; fp.ray_eps = p->ray_eps;
-    fp.rank = p->rank; fp.nranks = nranks; fp.tiles_x = lay.tiles_x; fp.n_tiles = lay.n_tiles;
-    fp.streams = streams; fp.slots_per_stream = pixel_slots;
-    div_magic(streams, fp.streams_magic, fp.streams_shift); div_magic(lay.tiles_x, fp.tiles_x_magic, fp.tiles_x_shift);
-    fp.offset_mod = p->sample_offset % streams;
+    f.n_slots = (uint32_t)slots64;
+    // every queue = kShards regions of shard_cap entries, one per shard. k_generate deals the 2^kShardGroupShift-slot groups out in
+    // rotation: entry group t of shard s starts as slot group t * kShards + (s - t) mod kShards, so a shard owns ceil(groups / kShards)
+    const uint32_t groups = (f.n_slots + (1u << kShardGroupShift) - 1u) >> kShardGroupShift, shard_cap = ((groups + kShards - 1) / kShards) << kShardGroupShift;
+    f.shard_cap = shard_cap; f.q_entries = (size_t)kShards * shard_cap;
+    f.samples_per_stream = (p->spp + f.streams - 1u) / f.streams;
+    f.profile = (p->flags & PT_FLAG_PROFILE_KERNELS) != 0; f.count = (p->flags & PT_FLAG_COUNT_VISITS) != 0;
+    f.bucket = (p->flags & PT_FLAG_BUCKET_SPECULAR) != 0; f.split = f.bucket || (p->flags & PT_FLAG_SPLIT_KERNELS) != 0;
+    f.forced = (p->flags & PT_FLAG_EXTEND_POOL) ? (uint32_t)EXT_POOL : (p->flags & PT_FLAG_EXTEND_PACKED) ? (uint32_t)EXT_PACKED
+               : (p->flags & PT_FLAG_EXTEND_SIMPLE) ? (uint32_t)EXT_SIMPLE : t.extend_kernel;
+    // the fused one-ray-per-lane and lane-packing kernels build a slot's initial state in registers in their first launch; k_shade
+    // (split pipelines) and the pooled kernel read it from memory
+    f.full_state = f.split || f.forced == (uint32_t)EXT_POOL;
+    f.mapped = t.readback == 0u; // queue sizes reach the host by the kernels' own stores (fold_traced) instead of a copy per launch
+    // rays per wavefront of the lane-packing kernel: 256 once several sample streams keep the queues long, else 128 (measured)
+    f.packed_chunk = t.packed_chunk >= 64u ? t.packed_chunk : (f.streams >= 4u ? 256u : 128u);
+    // path vertices per launch of the one-ray-per-lane kernel: 3/4 max_depth - 2 (saturating), clamped to [4, 12]
+    const uint32_t v34 = p->max_depth * 3u / 4u; f.default_bounces = std::min(12u, std::max(4u, v34 > 2u ? v34 - 2u : 0u));
+    // Iterations the host runs ahead of the queue sizes it reads back (pt_tuning.lag). The frame ends `lag` launches after its last path, on
+    // grids sized `lag` iterations ago: short frames feel that (ms per 1080p frame with lag 4 / 3 / 2, tools/exp_lag.py: 1 spp 0.567 / 0.537 /
+    // 0.529, 8 spp 2.79 / 2.73 / 2.70, glass 8 spp 1.57 / 1.52 / 1.48), long ones not (64 spp 17.73 / 17.68 / 17.73; a rank's 1/8 2.63 / 2.59 /
+    // 2.61), and the lane-packing kernel's short tail launches want the host further ahead (soup 72.3 / 72.4 / 73.1). At least 2: the launch
+    // after the last one that had paths clears that one's counter line. With the sizes stored by the kernels themselves (pt_tuning.readback =
+    // 0) iteration j's line is written by launch j + 1, so the same run-ahead of the GPU takes one more iteration of lag than with a copy.
+    f.lag = t.lag ? t.lag : (f.samples_per_stream <= 2u ? 2u : 3u) + (f.mapped ? 1u : 0u);
     // progressive accumulation (the reference re-renders every frame, App.cs:39-42; this is its converging analogue):
     // keep the stream partials of the previous call(s) and divide by the total number of samples at the end
-    const bool accumulate = (p->flags & PT_FLAG_ACCUMULATE) != 0;
-    if (accumulate) {
-        if (c->acc_spp == 0 || c->acc_w != p->width || c->acc_h != p->height || c->acc_rank != p->rank || c->acc_nranks != nranks ||
-            c->acc_streams != streams || c->acc_seed != p->seed)
+    f.accumulate = (p->flags & PT_FLAG_ACCUMULATE) != 0;
+    if (f.accumulate) {
+        if (c->acc_spp == 0 || c->acc_w != p->width || c->acc_h != p->height || c->acc_rank != p->rank || c->acc_nranks != f.nranks ||
+            c->acc_streams != f.streams || c->acc_seed != p->seed)
             return fail(c, PT_ERR_INVALID_ARGUMENT, "PT_FLAG_ACCUMULATE needs a previous frame with the same size, rank, nranks, streams and seed");
         if (p->sample_offset != c->acc_spp) return fail(c, PT_ERR_INVALID_ARGUMENT, "PT_FLAG_ACCUMULATE: sample_offset must be %llu (samples so far)", (unsigned long long)c->acc_spp);
     }
-    fp.accumulate = accumulate ? 1u : 0u;
-    const uint64_t total_spp = (accumulate ? c->acc_spp : 0u) + p->spp;
-    c->acc_spp = 0; // invalid until this frame completes
+    f.total_spp = (f.accumulate ? c->acc_spp : 0u) + p->spp; c->acc_spp = 0; // acc_spp: invalid until this frame completes
+    f.allocs_before = g_device_allocs;
+    HIP_TRY(c, c->ray_o.ensure(f.n_slots)); HIP_TRY(c, c->ray_d.ensure(f.n_slots)); HIP_TRY(c, c->thr.ensure(f.n_slots));
+    HIP_TRY(c, c->acc.ensure(f.n_slots)); HIP_TRY(c, c->tiles.ensure(f.pixel_slots)); HIP_TRY(c, c->sd.ensure(f.n_slots));
+    HIP_TRY(c, c->q_ext0.ensure(f.q_entries)); HIP_TRY(c, c->q_ext1.ensure(f.q_entries));
+    // hit records and the metal / dielectric buckets are k_shade's (no kernel indexes the miss and Lambert buckets)
+    if (f.split) { HIP_TRY(c, c->hit.ensure(f.n_slots)); HIP_TRY(c, c->q_metal.ensure(f.q_entries)); HIP_TRY(c, c->q_dielectric.ensure(f.q_entries)); }
+    if (!f.full_state) { HIP_TRY(c, c->q_init.ensure(f.q_entries)); HIP_TRY(c, c->cnt_init.ensure(kCntTotalWords)); }
+    const uint32_t ovf = s->bvh.stack_need > kStackLds ? s->bvh.stack_need - kStackLds : 0u;
+    if (ovf) HIP_TRY(c, c->stack_ovf.ensure((size_t)ovf * f.q_entries));
+    if (f.nranks == 1) { const pt_status st = ensure_frame(c, p->width, p->height); if (st != PT_OK) return st; }
+    PathState &ps = f.ps;
+    ps.ray_o = c->ray_o.p; ps.ray_d = c->ray_d.p; ps.thr = c->thr.p; ps.sd = c->sd.p; ps.acc = c->acc.p; ps.q_ext[0] = c->q_ext0.p; ps.q_ext[1] = c->q_ext1.p;
+    if (f.split) { ps.hit = c->hit.p; ps.q_bucket[B_METAL] = c->q_metal.p; ps.q_bucket[B_DIELECTRIC] = c->q_dielectric.p; }
+    ps.counters = c->counters.p; ps.stack_ovf = c->stack_ovf.p; ps.stack_ovf_entries = ovf; ps.n_slots = f.n_slots; ps.shard_cap = f.shard_cap;
+    ps.shard_base = 0; ps.shard_count = kShards; ps.compact_below = t.compact_below; ps.finish_below = t.finish_below; ps.sparse_below = t.sparse_below;
+    ps.repack_sticky = (f.samples_per_stream <= t.sticky_samples && t.compact_below > 0.f) ? 1u : 0u;
+    ps.host_ring = f.mapped ? c->d_ring : nullptr; ps.ring_slots = kLag;
+    // re-packing forced: buckets re-append (no fixed positions), or next to nothing regenerates (every launch leaves holes)
+    f.compact = f.bucket || (ps.repack_sticky && f.samples_per_stream <= 2u);
+    FrameParams &fp = f.fp;
+    fp.width = p->width; fp.height = p->height; fp.spp = p->spp; fp.max_depth = p->max_depth; fp.rr_start = p->rr_start;
+    fp.seed_hashed = host_pcg(p->seed); fp.sample_offset = p->sample_offset; fp.ray_eps = p->ray_eps;
+    fp.rank = p->rank; fp.nranks = f.nranks; fp.tiles_x = lay.tiles_x; fp.n_tiles = lay.n_tiles; fp.streams = f.streams; fp.slots_per_stream = f.pixel_slots;
+    div_magic(f.streams, fp.streams_magic, fp.streams_shift); div_magic(lay.tiles_x, fp.tiles_x_magic, fp.tiles_x_shift);
+    fp.offset_mod = p->sample_offset % f.streams; fp.accumulate = f.accumulate ? 1u : 0u;
+    return PT_OK;
+}
 
-    const DeviceScene &sc = s->ds;
+// Start: the first extend queue and counter block, after ev_start. A full-state frame runs k_generate over every slot; a fused one copies the
+// template of its geometry (pt_context::q_init: k_generate's output depends on which slots exist and on whether every stream has a sample).
+static pt_status start_frame(pt_context *c, const pt_scene *s, const pt_render_params *p, const Frame &f)
+{
     hipStream_t q = c->stream;
-    // the fused one-ray-per-lane and lane-packing kernels build a slot's initial state in registers in their first launch; k_shade
-    // (split pipelines) and the pooled kernel read it from memory
-    const bool full_state = split_kernels || forced_choice == (uint32_t)EXT_POOL;
-    if (full_state) {
+    if (f.full_state) {
         HIP_TRY(c, hipMemsetAsync(c->counters.p, 0, sizeof(uint32_t) * kCntTotalWords, q));
         HIP_TRY(c, hipEventRecord(c->ev_start, q));
-        HIP_TRY(c, launch_generate(q, sc, ps, fp, 1u));
+        HIP_TRY(c, launch_generate(q, s->ds, f.ps, f.fp, 1u));
     } else {
-        // k_generate's output depends on the frame's geometry only (which slots exist: size, rank, streams, whether every stream has
-        // a sample): made once per geometry, then a frame starts with a copy of the counter block (pt_context::q_init)
-        HIP_TRY(c, c->q_init.ensure(q_entries)); HIP_TRY(c, c->cnt_init.ensure(kCntTotalWords));
-        pt_context::InitKey key;
-        std::memset(&key, 0, sizeof key);
-        key.w = p->width; key.h = p->height; key.rank = p->rank; key.nranks = nranks; key.streams = streams; key.first_spp = std::min(p->spp, streams);
-        key.offset = p->sample_offset % streams; key.n_slots = n_slots; key.shard_cap = shard_cap; key.q = c->q_init.p; key.acc = c->acc.p;
+        HIP_TRY(c, hipEventRecord(c->ev_start, q));
+        pt_context::InitKey key; std::memset(&key, 0, sizeof key); // (compared bytewise: padding included)
+        key.w = p->width; key.h = p->height; key.rank = p->rank; key.nranks = f.nranks; key.streams = f.streams; key.first_spp = std::min(p->spp, f.streams);
+        key.offset = f.fp.offset_mod; key.n_slots = f.n_slots; key.shard_cap = f.shard_cap; key.q = c->q_init.p; key.acc = c->acc.p;
         if (!c->init_valid || !(key == c->init_key)) {
-            c->init_valid = false;
-            HIP_TRY(c, hipMemsetAsync(c->cnt_init.p, 0, sizeof(uint32_t) * kCntTotalWords, q));
-            PathState pt = ps;
-            pt.counters = c->cnt_init.p; pt.q_ext[0] = c->q_init.p;
+            c->init_valid = false; HIP_TRY(c, hipMemsetAsync(c->cnt_init.p, 0, sizeof(uint32_t) * kCntTotalWords, q));
+            PathState pt = f.ps; pt.counters = c->cnt_init.p; pt.q_ext[0] = c->q_init.p;
             // whole streams without a sample (spp < streams): the first queue holds the live slots only, and the first launch is sized by it
-            const bool dense = key.first_spp < streams;
-            HIP_TRY(c, launch_generate(q, sc, pt, fp, dense ? 2u : 0u)); // also zeroes every slot's sum (slots that never hold a path stay zero from here on)
-            c->init_bound = shard_cap;
+            const bool dense = key.first_spp < f.streams;
+            HIP_TRY(c, launch_generate(q, s->ds, pt, f.fp, dense ? 2u : 0u)); // also zeroes every slot's sum unless the frame accumulates
+            c->init_bound = f.shard_cap;
             if (dense) {
                 HIP_TRY(c, hipMemcpyAsync(c->h_counts + kFinalOffset, c->cnt_init.p, sizeof(uint32_t) * kShards * kCounterStride, hipMemcpyDeviceToHost, q));
                 HIP_TRY(c, hipStreamSynchronize(q));
@@ -729,219 +756,192 @@ static pt_status render_frame(pt_context *c, const pt_scene *s, const pt_render_
             }
             c->init_key = key; c->init_valid = true;
         }
-        HIP_TRY(c, hipEventRecord(c->ev_start, q));
         HIP_TRY(c, hipMemcpyAsync(c->counters.p, c->cnt_init.p, sizeof(uint32_t) * kCntTotalWords, hipMemcpyDeviceToDevice, q));
     }
+    // the template invariant (pt_context::q_init): this frame writes the streams a dense template leaves out
+    if ((f.accumulate || f.full_state) && c->init_key.first_spp < c->init_key.streams) c->init_valid = false;
+    return PT_OK;
+}
 
-    // Wavefront loops. Shards never exchange slots, so the 64 shards are split into `n_loops` independent loops, each on
-    // its own HIP stream: the tail of one group's launch (its last wavefronts draining) is filled by the other's launch
-    // (pt_context::groups has the measurements). Inside a loop a shard's queue can only shrink (slots die, none are born),
-    // so the queue sizes read back `lag` iterations ago are valid launch bounds: the host never stalls the GPU to size a grid.
-    // Per-kernel timing, visit counting and the extend-kernel probe (events around single iterations) want kernels alone on
-    // the GPU: one loop.
-    // Which extend kernel (when no flag forces one): measured, per scene, and remembered in the scene.
-    //   inside a frame : iteration 2 of group 0 runs the one-ray-per-lane kernel, iteration 3 the lane-packing one (bit-identical
-    //                    results), each bracketed by events; accepted only if both traced a real share of the frame's slots;
-    //   across frames  : a frame too short for that (few samples per stream: it is over in two iterations) runs whole on one
-    //                    kernel — the first on the one-ray-per-lane kernel, the next on the lane-packing one — and the rays per
-    //                    millisecond of the two frames decide.
-    // The faster per ray wins (packed needs +10 %). Deep incoherent traversals (1M-triangle soup) gain ~2.5x from packing, shallow
-    // ones (walls of a box) lose ~35 %, and no static property of the tree tells them apart. Counting / profiling
-    // frames neither probe nor feed the decision: their kernels are instrumented builds.
-    const bool undecided = forced_choice == 0u && s->ext_choice == 0u && !count && !profile;
-    const uint32_t frame_kernel = (undecided && s->rate_simple > 0.0 && s->rate_packed == 0.0) ? (uint32_t)EXT_PACKED : (uint32_t)EXT_SIMPLE;
-    const bool will_probe = undecided && frame_kernel == (uint32_t)EXT_SIMPLE;
-    const uint32_t n_loops = (profile || count || will_probe) ? 1u : c->groups ? c->groups : 2u;
-    const uint32_t per_group = kShards / n_loops;
-    //
-    // Queues are carried over IN PLACE from one iteration to the next: a lane writes its own queue position, dead paths
-    // leave holes, and lane <-> slot stays the generation order, so the slot-indexed state keeps its coalescing and no
-    // returning atomic is needed. A shard re-packs its survivors (ballot + atomic append) in the iteration in which its
-    // alive/length ratio is below `compact_below`, and runs its last `finish_below` paths to their end in one launch;
-    // both are decided by the kernels from the shard's counters, the host only sizes grids and notices the end.
-    struct Loop { hipStream_t stream; uint32_t base, bound, iters; bool done; };
-    Loop loops[kMaxGroups];
+// Loops. Shards never exchange slots, so the 64 shards are split into `n_loops` independent loops, each on its own HIP stream: the tail of one
+// group's launch (its last wavefronts draining) is filled by the other's launch (pt_tuning.loops has the measurements). Inside a loop a shard's
+// queue can only shrink (slots die, none are born), so the queue sizes read back `lag` iterations ago are valid launch bounds: the host never
+// stalls the GPU to size a grid. Queues are carried over IN PLACE from one iteration to the next: a lane writes its own queue position, dead
+// paths leave holes, and lane <-> slot stays the generation order, so the slot-indexed state keeps its coalescing and no returning atomic is
+// needed. A shard re-packs its survivors (ballot + atomic append) in the iteration in which its alive/length ratio is below `compact_below`,
+// and runs its last `finish_below` paths to their end in one launch; both are decided by the kernels from the shard's counters, the host only
+// sizes grids and notices the end.
+static pt_status run_loops(pt_context *c, const pt_scene *s, const pt_render_params *p, Frame &f, ExtendFrame &x)
+{
+    hipStream_t q = c->stream; const uint32_t n_loops = f.n_loops, per_group = kShards / n_loops;
+    struct Loop { hipStream_t stream; uint32_t base, bound, iters; bool done; } loops[kMaxGroups];
     HIP_TRY(c, hipEventRecord(c->ev_fork, q));
     for (uint32_t g = 0; g < n_loops; ++g) {
-        loops[g] = Loop{ n_loops == 1 ? q : c->group_stream[g], g * per_group, full_state ? shard_cap : c->init_bound, 0u, false }; // no shard's queue can outgrow its first one
+        loops[g] = Loop{ n_loops == 1 ? q : c->group_stream[g], g * per_group, f.full_state ? f.shard_cap : c->init_bound, 0u, false }; // no shard's queue can outgrow its first one
         if (loops[g].stream != q) HIP_TRY(c, hipStreamWaitEvent(loops[g].stream, c->ev_fork, 0));
     }
     const uint64_t max_iters = (uint64_t)p->spp * p->max_depth + kLag + 2;
-    // Iterations the host runs ahead of the queue sizes it reads back (pt_tuning.lag). The frame ends `lag` launches after its last
-    // path, on grids sized `lag` iterations ago: short frames feel that (ms per 1080p frame with lag 4 / 3 / 2, tools/exp_lag.py:
-    // 1 spp 0.567 / 0.537 / 0.529, 8 spp 2.79 / 2.73 / 2.70, glass 8 spp 1.57 / 1.52 / 1.48), long ones not (64 spp 17.73 / 17.68 /
-    // 17.73; a rank's 1/8 2.63 / 2.59 / 2.61), and the lane-packing kernel's short tail launches want the host further ahead (soup
-    // 72.3 / 72.4 / 73.1). At least 2: the launch after the last one that had paths clears that one's counter line.
-    // With the sizes stored by the kernels themselves (pt_tuning.readback = 0) iteration j's line is written by launch j + 1, so the
-    // same run-ahead of the GPU takes one more iteration of lag than with a copy behind every launch.
-    const uint32_t lag = c->lag ? c->lag : (samples_per_stream <= 2u ? 2u : 3u) + (mapped ? 1u : 0u);
-    size_t nev = 0;
-    uint32_t iters_max = 0;
-    // path vertices per launch of the one-ray-per-lane kernel: 3/4 max_depth - 2 (saturating), clamped to [4, 12]
-    const uint32_t v34 = p->max_depth * 3u / 4u, default_bounces = std::min(12u, std::max(4u, v34 > 2u ? v34 - 2u : 0u));
-    // 0 = probing inside this frame, else the ExtendKernel every iteration uses
-    uint32_t ext_choice = forced_choice ? forced_choice : s->ext_choice ? s->ext_choice : will_probe ? 0u : frame_kernel;
-    bool mixed = false; // this frame ran probe iterations on both kernels: its overall rate says nothing about either
-    uint64_t probe_n[2] = { 0, 0 }, slot_launches = 0;
-    const bool trace = profile && getenv("PTRT_TRACE") != nullptr; // developer aid: per-iteration table on stderr
-    std::vector<uint64_t> trace_alive, trace_rays;
+    const bool trace = f.profile && getenv("PTRT_TRACE") != nullptr; // developer aid: per-iteration table on stderr
+    // One kernel per iteration by default: every extend kernel (one ray per lane, lane-packing, pooled) shades its own hits (mode 0:
+    // Lambert-only scene, lean code; 2: all kinds). PT_FLAG_SPLIT_KERNELS / _BUCKET_SPECULAR run k_shade as a second kernel.
+    const int shade_mode = s->has_specular ? 2 : 0;
     for (uint32_t live = n_loops; live > 0;) {
         for (uint32_t g = 0; g < n_loops; ++g) {
             Loop &L = loops[g];
             if (L.done) continue;
             if (L.iters >= max_iters) return fail(c, PT_ERR_INTERNAL, "wavefront loop did not drain after %u iterations", L.iters);
-            const uint32_t it = L.iters;
-            PathState pg = ps;
-            pg.shard_base = L.base; pg.shard_count = per_group;
-            if (it == 0u && !full_state) pg.q_ext[0] = c->q_init.p; // the frame's first queue is the same every frame: read, never written
-            if (ext_choice == 0u) pg.finish_below = 0u; // while the extend kernel is still being probed, iterations stay comparable
+            const uint32_t it = L.iters; PathState pg = f.ps; pg.shard_base = L.base; pg.shard_count = per_group;
+            if (it == 0u && !f.full_state) pg.q_ext[0] = c->q_init.p; // the frame's first queue is the template: read, never written
+            if (x.kernel == 0u) pg.finish_below = 0u; // probing: no finish mode
             hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
-            if (profile) {
-                e0 = pool_event(c, nev++); e1 = pool_event(c, nev++); e2 = pool_event(c, nev++);
+            if (f.profile) {
+                e0 = pool_event(c, f.n_events++); e1 = pool_event(c, f.n_events++); e2 = pool_event(c, f.n_events++);
                 if (!e0 || !e1 || !e2) return fail(c, PT_ERR_HIP, "hipEventCreate failed");
                 HIP_TRY(c, hipEventRecord(e0, L.stream));
             }
-            const bool probing = g == 0u && ext_choice == 0u && (L.iters == 2u || L.iters == 3u);
-            const bool use_packed = ext_choice == (uint32_t)EXT_PACKED || (probing && L.iters == 3u);
-            const int kernel = use_packed ? EXT_PACKED : (ext_choice == (uint32_t)EXT_POOL && !split_kernels) ? EXT_POOL : EXT_SIMPLE;
-            const bool compact = bucket_specular || repack_always; // forced: buckets re-append, there are no fixed positions
-            // One kernel per iteration by default: every extend kernel (one ray per lane, lane-packing, pooled) shades its own hits
-            // (mode 0: Lambert-only scene, lean code; 2: all kinds). PT_FLAG_SPLIT_KERNELS / _BUCKET_SPECULAR run k_shade as a second kernel.
-            const int shade_mode = s->has_specular ? 2 : 0;
-            const bool fused = !split_kernels;
-            if (probing) HIP_TRY(c, hipEventRecord(c->ev_probe[(L.iters - 2u) * 2u], L.stream));
-            HIP_TRY(c, launch_extend(L.stream, sc, pg, fp, it, L.bound, count, kernel, packed_chunk, fused ? shade_mode : -1, compact,
-                                     c->bounces ? c->bounces : use_packed ? (probing ? 8u : 64u) : default_bounces));
-                                     // lane-packing: a lane pulls a new entry whenever its budget ends, so a long budget costs nothing and
-                                     // saves launches (ms per frame with 8 / 16 / 32 / 64 vertices, tools/exp_packed.py: 1M soup 72.2 / 71.5 /
-                                     // 70.5 / 67.4, at 256 spp 277.6 / 271.8 / 268.3 / 266.1, 5k soup 7.99 / 7.43 / 7.35 / 7.39); the probe
-                                     // iteration keeps 8 so that it stays comparable with the one before it
-            if (profile) HIP_TRY(c, hipEventRecord(e1, L.stream));
-            if (!fused && !bucket_specular) HIP_TRY(c, launch_shade(L.stream, sc, pg, fp, it, L.bound, shade_mode, compact));
-            else if (!fused) {
-                HIP_TRY(c, launch_shade(L.stream, sc, pg, fp, it, L.bound, 0, true));
-                HIP_TRY(c, launch_shade(L.stream, sc, pg, fp, it, L.bound, 1, true)); // metal + dielectric buckets
-            }
-            if (probing) HIP_TRY(c, hipEventRecord(c->ev_probe[(L.iters - 2u) * 2u + 1u], L.stream)); // the whole iteration, either way
-            if (profile) HIP_TRY(c, hipEventRecord(e2, L.stream));
+            const bool probing = x.probing(g, it); const int kernel = x.launch_kernel(g, it, f.split);
+            if (probing) HIP_TRY(c, hipEventRecord(c->ev_probe[(it - 2u) * 2u], L.stream));
+            HIP_TRY(c, launch_extend(L.stream, s->ds, pg, f.fp, it, L.bound, f.count, kernel, f.packed_chunk, f.split ? -1 : shade_mode, f.compact,
+                                     c->tuning.bounces ? c->tuning.bounces : x.bounces(g, it, kernel, f.default_bounces)));
+            if (f.profile) HIP_TRY(c, hipEventRecord(e1, L.stream));
+            if (f.bucket) {
+                HIP_TRY(c, launch_shade(L.stream, s->ds, pg, f.fp, it, L.bound, 0, true));
+                HIP_TRY(c, launch_shade(L.stream, s->ds, pg, f.fp, it, L.bound, 1, true)); // metal + dielectric buckets
+            } else if (f.split) HIP_TRY(c, launch_shade(L.stream, s->ds, pg, f.fp, it, L.bound, shade_mode, f.compact));
+            if (probing) HIP_TRY(c, hipEventRecord(c->ev_probe[(it - 2u) * 2u + 1u], L.stream)); // the whole iteration, either way
+            if (f.profile) HIP_TRY(c, hipEventRecord(e2, L.stream));
             const uint32_t ring = L.iters % kLag;
-            if (!mapped) {
+            if (!f.mapped) {
                 uint32_t *h_ring = c->h_counts + ((size_t)g * kLag + ring) * kRingWords;
                 HIP_TRY(c, hipMemcpyAsync(h_ring, c->counters.p + cnt_ext_index((it + 1u) % 3u, L.base), sizeof(uint32_t) * per_group * kCounterStride,
                                           hipMemcpyDeviceToHost, L.stream));
             }
             HIP_TRY(c, hipEventRecord(c->ev_lag[g][ring], L.stream));
-            ++L.iters;
-            iters_max = std::max(iters_max, L.iters);
-            if (L.iters >= lag) {
-                const uint32_t old_iter = L.iters - lag; // iteration old_iter traced `traced` rays and left `total` paths alive: its survivors bound every later queue
-                // mapped: launch old_iter + 1 stored old_iter's lines (fold_traced); it is at most the launch just enqueued since lag >= 2
-                HIP_TRY(c, hipEventSynchronize(c->ev_lag[g][(mapped ? old_iter + 1u : old_iter) % kLag]));
-                const volatile uint32_t *h_old = mapped ? (const volatile uint32_t *)(c->h_ring + (size_t)(old_iter % kLag) * kShards + L.base)
-                                               : c->h_counts + ((size_t)g * kLag + old_iter % kLag) * kRingWords;
-                const uint32_t line = mapped ? 4u : kCounterStride;
-                uint32_t mx = 0;
-                // a shard's line: word 0 = queue length (holes included), word 1 = alive entries, words 2-3 = rays the iteration traced
-                uint64_t total = 0, traced = 0;
-                for (uint32_t sh = 0; sh < per_group; ++sh) {
-                    mx = std::max(mx, (uint32_t)h_old[sh * line]);
-                    total += h_old[sh * line + 1];
-                    traced += (uint64_t)h_old[sh * line + 2] | ((uint64_t)h_old[sh * line + 3] << 32);
-                }
-                L.bound = mx;
-                if (trace) {
-                    trace_alive.resize(std::max<size_t>(trace_alive.size(), old_iter + 1), 0); trace_rays.resize(trace_alive.size(), 0);
-                    trace_alive[old_iter] += total; trace_rays[old_iter] += traced;
-                }
-                slot_launches += total; // = paths alive at the start of iteration old_iter + 1 (those read after the loop ended are all 0)
-                if (total == 0) { L.done = true; --live; }
-                if (g == 0u && ext_choice == 0u && (old_iter == 2u || old_iter == 3u)) probe_n[old_iter - 2u] = traced;
-                if (g == 0u && ext_choice == 0u && old_iter == 3u) { // iterations 2 and 3 (and their events) are complete by now
-                    float ms_simple = 0.f, ms_packed = 0.f;
-                    HIP_TRY(c, hipEventElapsedTime(&ms_simple, c->ev_probe[0], c->ev_probe[1]));
-                    HIP_TRY(c, hipEventElapsedTime(&ms_packed, c->ev_probe[2], c->ev_probe[3]));
-                    const double r_simple = probe_n[0] / std::max((double)ms_simple, 1e-6), r_packed = probe_n[1] / std::max((double)ms_packed, 1e-6);
-                    const uint64_t enough = (uint64_t)(n_slots / n_loops) / 8u; // each probe iteration must have traced a real share of the slots
-                    if (probe_n[0] >= enough && probe_n[1] >= enough) {
-                        ext_choice = r_packed > 1.10 * r_simple ? (uint32_t)EXT_PACKED : (uint32_t)EXT_SIMPLE;
-                        s->ext_choice = ext_choice;
-                    } else { // inconclusive (the frame was all but over): finish on the default and let whole frames decide
-                        ext_choice = (uint32_t)EXT_SIMPLE;
-                        mixed = probe_n[1] >= enough / 8u; // did the lane-packing iteration trace enough to colour this frame's rate?
-                    }
-                }
+            f.iters = std::max(f.iters, ++L.iters);
+            if (L.iters < f.lag) continue;
+            const uint32_t old_iter = L.iters - f.lag; // iteration old_iter traced `traced` rays and left `total` paths alive: its survivors bound every later queue
+            // mapped: launch old_iter + 1 stored old_iter's lines (fold_traced); it is at most the launch just enqueued since lag >= 2
+            HIP_TRY(c, hipEventSynchronize(c->ev_lag[g][(f.mapped ? old_iter + 1u : old_iter) % kLag]));
+            const volatile uint32_t *h_old = f.mapped ? (const volatile uint32_t *)(c->h_ring + (size_t)(old_iter % kLag) * kShards + L.base)
+                                                      : c->h_counts + ((size_t)g * kLag + old_iter % kLag) * kRingWords;
+            // a shard's line: word 0 = queue length (holes included), word 1 = alive entries, words 2-3 = rays the iteration traced
+            const uint32_t line = f.mapped ? 4u : kCounterStride;
+            uint32_t mx = 0; uint64_t total = 0, traced = 0;
+            for (uint32_t sh = 0; sh < per_group; ++sh) {
+                mx = std::max(mx, (uint32_t)h_old[sh * line]);
+                total += h_old[sh * line + 1];
+                traced += (uint64_t)h_old[sh * line + 2] | ((uint64_t)h_old[sh * line + 3] << 32);
             }
+            L.bound = mx;
+            if (trace) {
+                f.trace_alive.resize(std::max<size_t>(f.trace_alive.size(), old_iter + 1), 0); f.trace_rays.resize(f.trace_alive.size(), 0);
+                f.trace_alive[old_iter] += total; f.trace_rays[old_iter] += traced;
+            }
+            f.slot_launches += total; // = paths alive at the start of iteration old_iter + 1 (those read after the loop ended are all 0)
+            if (total == 0) { L.done = true; --live; }
+            HIP_TRY(c, x.observe(g, old_iter, traced, f.n_slots / n_loops, c->ev_probe));
         }
     }
     for (uint32_t g = 0; g < n_loops; ++g) // join: the main stream continues after every group's last kernel
-        if (loops[g].stream != q) {
-            HIP_TRY(c, hipEventRecord(c->ev_join[g], loops[g].stream));
-            HIP_TRY(c, hipStreamWaitEvent(q, c->ev_join[g], 0));
-        }
-    const uint32_t iters = iters_max;
-    HIP_TRY(c, launch_reduce_streams(q, c->acc.p, c->tiles.p, pixel_slots, streams)); // tiles = the pixel sums = the gather payload
-    if (nranks == 1)
-        HIP_TRY(c, launch_assemble(q, c->tiles.p, 1, pixel_slots, p->width, p->height, lay.tiles_x, lay.n_tiles, 1.0f / (float)total_spp, c->fb.p, c->fb8.p));
+        if (loops[g].stream != q) { HIP_TRY(c, hipEventRecord(c->ev_join[g], loops[g].stream)); HIP_TRY(c, hipStreamWaitEvent(q, c->ev_join[g], 0)); }
+    return PT_OK;
+}
+
+// Finish: reduce the streams and assemble, read every counter back, check that the frame ended clean, fill pt_stats
+static pt_status finish_frame(pt_context *c, const pt_render_params *p, const Frame &f, ExtendFrame &x, pt_stats *stats)
+{
+    hipStream_t q = c->stream; const FrameParams &fp = f.fp;
+    HIP_TRY(c, launch_reduce_streams(q, c->acc.p, c->tiles.p, f.pixel_slots, f.streams)); // tiles = the pixel sums = the gather payload
+    if (f.nranks == 1)
+        HIP_TRY(c, launch_assemble(q, c->tiles.p, 1, f.pixel_slots, p->width, p->height, fp.tiles_x, fp.n_tiles, 1.0f / (float)f.total_spp, c->fb.p, c->fb8.p));
     HIP_TRY(c, hipEventRecord(c->ev_stop, q));
     HIP_TRY(c, hipMemcpyAsync(c->h_counts + kFinalOffset, c->counters.p, sizeof(uint32_t) * kCntTotalWords, hipMemcpyDeviceToHost, q));
     HIP_TRY(c, hipStreamSynchronize(q));
-
-    const uint32_t *hc = c->h_counts + kFinalOffset;
+    pt_stats out; std::memset(&out, 0, sizeof out); const uint32_t *hc = c->h_counts + kFinalOffset;
     if (hc[kCntError]) return fail(c, PT_ERR_INTERNAL, "device error flag 0x%x (1 = traversal stack overflow, 2 = step limit)", hc[kCntError]);
     auto u64_at = [&](uint32_t w) { return (uint64_t)hc[w] | ((uint64_t)hc[w + 1] << 32); };
     for (uint32_t sh = 0; sh < kShards; ++sh) {
         if (hc[cnt_alive_index(0, sh)] || hc[cnt_alive_index(1, sh)] || hc[cnt_alive_index(2, sh)]) return fail(c, PT_ERR_INTERNAL, "extend queue of shard %u not empty at frame end", sh);
         out.rays += u64_at(cnt_rays_index(sh));
     }
-    float ms = 0.f; HIP_TRY(c, hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
-    out.gpu_ms = ms;
+    float ms = 0.f; HIP_TRY(c, hipEventElapsedTime(&ms, c->ev_start, c->ev_stop)); out.gpu_ms = ms;
     out.node_visits = u64_at(kCntNodes); out.tri_tests = u64_at(kCntTris); out.sphere_tests = u64_at(kCntSph);
     // PT_FLAG_COUNT_VISITS + one-ray-per-lane kernel: wave-level node-loop iterations (bits 0-39) and, from bit 40 up, how many
     // of them came after the wave's first leaf phase of the ray (diagnostic for tools/exp_util.py)
     out.reserved[3] = (u64_at(kCntWaveNodeIters) & 0xFFFFFFFFFFull) | (u64_at(kCntWaveNodeIters + 2) << 40);
-    if (count && getenv("PTRT_TRACE")) { // developer aid: where the node loop's lane-slots go (one-ray-per-lane kernel)
+    if (f.count && getenv("PTRT_TRACE")) { // developer aid: where the node loop's lane-slots go (one-ray-per-lane kernel)
         const double slots = 64.0 * (double)u64_at(kCntWaveNodeIters), v = (double)out.node_visits, lf = (double)u64_at(kCntIdleLeaf), dn = (double)u64_at(kCntIdleDone);
         if (slots > 0) fprintf(stderr, "ptrt: node-loop lane-slots %.3g: visiting %.1f %%, waiting at a leaf %.1f %%, ray finished %.1f %%, no ray %.1f %%\n", slots,
                                100 * v / slots, 100 * lf / slots, 100 * dn / slots, 100 * (slots - v - lf - dn) / slots);
     }
-    out.iterations = iters; out.extend_launches = iters;
-    const bool cold_frame = g_device_allocs != allocs_before; // first touch of fresh allocations: 30 % slower, not a measurement
-    if (undecided && s->ext_choice == 0u && !mixed && !cold_frame && out.rays >= (1u << 20) && out.gpu_ms > 0.0) { // a whole frame on one kernel: remember its rate
-        (frame_kernel == (uint32_t)EXT_PACKED ? s->rate_packed : s->rate_simple) = (double)out.rays / out.gpu_ms;
-        if (s->rate_simple > 0.0 && s->rate_packed > 0.0) s->ext_choice = s->rate_packed > 1.10 * s->rate_simple ? (uint32_t)EXT_PACKED : (uint32_t)EXT_SIMPLE;
-    } else if (undecided && s->ext_choice == 0u && !cold_frame && ++s->probe_misses >= 3u) s->ext_choice = (uint32_t)EXT_SIMPLE; // frames too small to time
-    out.reserved[0] = ext_choice ? ext_choice : (uint32_t)EXT_SIMPLE; // extend kernel in use at frame end (ExtendKernel)
+    out.iterations = f.iters; out.extend_launches = f.iters;
+    x.frame_done(out.rays, out.gpu_ms, g_device_allocs != f.allocs_before);
+    out.reserved[0] = x.kernel ? x.kernel : (uint32_t)EXT_SIMPLE; // extend kernel in use at frame end (ExtendKernel)
     out.reserved[1] = hc[kCntCompactions]; // (shard, iteration) pairs that re-packed their queue (the others carried it over in place)
-    {   // paths = owned in-image pixels x spp
-        uint64_t px = 0;
-        for (uint32_t t = p->rank; t < lay.n_tiles; t += nranks) {
-            const uint32_t tx = t % lay.tiles_x, ty = t / lay.tiles_x;
-            const uint32_t w = std::min(kTile, p->width - tx * kTile), h = std::min(kTile, p->height - ty * kTile);
-            px += (uint64_t)w * h;
-        }
-        out.paths = px * p->spp;
-        // path states read + written by the wavefront loop = sum over launches of the paths alive at launch start
-        // (iteration 0 starts every (pixel, stream) pair that has a sample)
-        out.reserved[2] = slot_launches + px * std::min(streams, p->spp);
+    uint64_t px = 0; // paths = owned in-image pixels x spp
+    for (uint32_t t = p->rank; t < fp.n_tiles; t += f.nranks) {
+        const uint32_t tx = t % fp.tiles_x, ty = t / fp.tiles_x;
+        px += (uint64_t)std::min(kTile, p->width - tx * kTile) * std::min(kTile, p->height - ty * kTile);
     }
-    if (profile) {
-        for (size_t i = 0; i + 2 < nev; i += 3) { // three events per iteration: before extend, between, after shade
-            float a = 0.f, b = 0.f;
-            HIP_TRY(c, hipEventElapsedTime(&a, c->ev_pool[i], c->ev_pool[i + 1]));
+    out.paths = px * p->spp;
+    // path states read + written by the wavefront loop = sum over launches of the paths alive at launch start
+    // (iteration 0 starts every (pixel, stream) pair that has a sample)
+    out.reserved[2] = f.slot_launches + px * std::min(f.streams, p->spp);
+    if (f.profile) {
+        const bool trace = getenv("PTRT_TRACE") != nullptr;
+        for (size_t i = 0; i + 2 < f.n_events; i += 3) { // three events per iteration: before extend, between, after shade
+            float a = 0.f, b = 0.f; HIP_TRY(c, hipEventElapsedTime(&a, c->ev_pool[i], c->ev_pool[i + 1]));
             HIP_TRY(c, hipEventElapsedTime(&b, c->ev_pool[i + 1], c->ev_pool[i + 2]));
             out.extend_ms += a; out.shade_ms += b;
             if (trace) fprintf(stderr, "ptrt: iteration %3zu  rays %10llu  alive after %10llu  extend %8.3f ms  shade %8.3f ms\n", i / 3,
-                               (unsigned long long)(i / 3 < trace_rays.size() ? trace_rays[i / 3] : 0),
-                               (unsigned long long)(i / 3 < trace_alive.size() ? trace_alive[i / 3] : 0), a, b);
+                               (unsigned long long)(i / 3 < f.trace_rays.size() ? f.trace_rays[i / 3] : 0),
+                               (unsigned long long)(i / 3 < f.trace_alive.size() ? f.trace_alive[i / 3] : 0), a, b);
         }
         out.other_ms = out.gpu_ms - out.extend_ms - out.shade_ms;
     }
-    c->n_slots = pixel_slots;
-    c->acc_w = p->width; c->acc_h = p->height; c->acc_rank = p->rank; c->acc_nranks = nranks; c->acc_streams = streams; c->acc_seed = p->seed;
-    c->acc_spp = total_spp;
-    c->fb_valid = (nranks == 1);
+    c->n_slots = f.pixel_slots; c->acc_w = p->width; c->acc_h = p->height; c->acc_rank = p->rank; c->acc_nranks = f.nranks; c->acc_streams = f.streams; c->acc_seed = p->seed;
+    c->acc_spp = f.total_spp; c->fb_valid = (f.nranks == 1);
     if (stats) *stats = out;
     return PT_OK;
+}
+
+static pt_status render_frame(pt_context *c, const pt_scene *s, const pt_render_params *p, pt_stats *stats)
+{
+    if (!c || !p) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_render: NULL argument");
+    pt_tile_layout lay; pt_status st = layout_of(p, &lay);
+    if (st != PT_OK) return fail(c, st, "pt_render: bad width/height/rank/nranks/tile_size");
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->fb_valid = false;
+    if (p->mode == PT_REFERENCE_SPHERE) { // Renderer.ComputeFrame: one dispatch, then the host blocks on the fence (Renderer.cs:1020,1036,972)
+        if ((st = ensure_frame(c, p->width, p->height)) != PT_OK) return st;
+        HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
+        HIP_TRY(c, launch_reference_sphere(c->stream, p->width, p->height, c->fb.p, c->fb8.p));
+        HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        float ms = 0.f; HIP_TRY(c, hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
+        pt_stats out; std::memset(&out, 0, sizeof out);
+        out.gpu_ms = ms; out.other_ms = ms; out.rays = out.paths = (uint64_t)p->width * p->height; out.iterations = 1;
+        c->fb_valid = true; if (stats) *stats = out;
+        return PT_OK;
+    }
+    if (p->mode != PT_PATH_TRACE) return fail(c, PT_ERR_INVALID_ARGUMENT, "unknown mode %u", p->mode);
+    Frame f{};
+    if ((st = plan_frame(c, s, p, lay, f)) != PT_OK) return st;
+    ExtendFrame x(s->ext, f.forced, f.count || f.profile);
+    f.n_loops = (f.profile || f.count || x.kernel == 0u) ? 1u : c->tuning.loops ? c->tuning.loops : 2u; // timed kernels run alone
+    if ((st = start_frame(c, s, p, f)) != PT_OK || (st = run_loops(c, s, p, f, x)) != PT_OK) return st;
+    return finish_frame(c, p, f, x, stats);
+}
+
+pt_status pt_render(pt_context *c, const pt_scene *s, const pt_render_params *p, pt_stats *stats)
+{
+    const pt_status st = render_frame(c, s, p, stats);
+    if (st != PT_OK && c) { // an error exit may leave kernels in flight on the loop streams: nothing of this frame survives the call
+        (void)hipSetDevice(c->device);
+        drain(c);
+        c->acc_spp = 0; c->fb_valid = false;
+    }
+    return st;
 }
 
 pt_status pt_framebuffer_read(pt_context *c, float *rgba, uint64_t n_floats)

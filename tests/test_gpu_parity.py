@@ -735,6 +735,11 @@ def test_host_readback_and_kernel_pin(P, pto):
         for bad in (dict(extend_kernel=4), dict(readback=2), dict(lag=1), dict(lag=6)):
             with pytest.raises(P.PtException):
                 r.SetTuning(**bad)
+        r.SetTuning(bounces=5)
+        with pytest.raises(P.PtException):
+            r.SetTuning(bounces=7, extend_kernel=4)
+        assert r.GetTuning().bounces == 5  # a refused call changes no field
+        r.SetTuning(bounces=0)
         # frames too small to time settle on the one-ray-per-lane kernel instead of probing for ever (one loop, no finish mode)
         r.SetTuning(extend_kernel=0)
         r.SetScene(sd, 0)
@@ -775,6 +780,17 @@ def test_frame_start_template_follows_the_geometry(P, pto, renderer):
         renderer.Render(0.0)
         done += n
     assert np.array_equal(renderer.ReadFramebuffer(), ref)
+    # a dense template (spp < streams) must not be reused after frames that wrote the streams it leaves out: progressive frames (A: offsets
+    # 0, 4, 8, then a restart at 0) and full-state frames (B: split kernels, or the pooled kernel); the restart equals the oracle's frame
+    osc = pto.Scene(sdw, (renderer.BvhInfo().width,) + renderer.BvhRead())
+    acc, split, pool = N.PT_FLAG_ACCUMULATE, N.PT_FLAG_SPLIT_KERNELS, N.PT_FLAG_EXTEND_POOL
+    for seq in ([(4, 8, 0, 0), (4, 8, 4, acc), (4, 8, 8, acc)], [(2, 4, 0, 0), (4, 4, 0, split)], [(2, 4, 0, 0), (4, 4, 0, pool)]):
+        for spp, streams, offset, flags in seq + seq[:1]:
+            p = P.make_params(200, 120, spp=spp, max_depth=7, streams=streams, sample_offset=offset, flags=flags)
+            renderer.Params = p
+            st = renderer.Render(0.0)
+        ref, ost = pto.render(osc, p)
+        assert st.rays == ost.rays and np.array_equal(renderer.ReadFramebuffer(), ref), seq
     del osc
 
 
