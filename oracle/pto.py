@@ -134,6 +134,16 @@ class Scene:
         return rc, d.value
 
 
+def camera_ray(cam, x, y, key=0):
+    """(origin, direction) of the camera ray of pixel (x, y) (SPEC §3) as float32 arrays. `cam`: any ctypes struct with the
+    pt_camera layout; `key` only matters with cam.jitter set."""
+    c = pto_camera()
+    C.memmove(C.byref(c), C.byref(cam), C.sizeof(pto_camera))
+    o, d = (C.c_float * 3)(), (C.c_float * 3)()
+    lib.pto_camera_ray(C.byref(c), x, y, key, o, d)
+    return np.array(o[:], np.float32), np.array(d[:], np.float32)
+
+
 def render(scene, params, threads=0):
     """params: any ctypes struct with the pt_render_params layout. Returns (rgba float32 HxWx4, pto_stats)."""
     p = pto_params()

@@ -1,0 +1,189 @@
+"""The oracle's closest hit against a float64 ray caster (tests/ray_caster64.py) on adversarial scenes, and the properties of
+those scenes the GPU tests rely on. The oracle restates the f32 spec; the caster answers the geometric question, so these
+pin the spec's geometry itself. A disagreement must be explained by an edge (within EDGE_BAND, a miss there is a crack) or by
+two surfaces at the same distance; anything else fails."""
+import numpy as np
+import pytest
+
+import adversarial_scenes as S
+import ray_caster64 as rc
+
+W, H = 65, 49           # odd: the axis camera's centre row and column
+CRACK_RAYS = 300        # rays aimed at interior points of shared edges of the tessellated Cornell box
+PINNED_CRACKS = 44      # of them, the rays SPEC §4's Möller–Trumbore lets through (brute force and BVH alike)
+ALLOWED = 0.01          # the edge and coincident classes together stay below this fraction of a frame's pixels
+
+
+def build_bvh_detached(scene, layout=0):
+    """The product's host builder on a detached scene. Imported late: libptrt.so exists only once the build fixture has run,
+    after collection."""
+    from pathtracing_amd.host import build_bvh_detached as build
+    return build(scene, layout)
+
+
+def oracle_ids(pto, sd, layout, w, h):
+    sd = S.id_scene(sd)
+    info, nodes, tris = build_bvh_detached(sd, layout)
+    img, _ = pto.render(pto.Scene(sd, (info.width, nodes, tris)), S.params_id(w, h))
+    return S.ids_of(img)
+
+
+def scenes(P, w=W, h=H):
+    N = P.native
+    c1 = P.make_scene(N.PT_SCENE_CORNELL, 0, 1, w, h)
+    return {
+        "tess": P.make_scene(N.PT_SCENE_CORNELL_TESS, 2000, 5, w + 1, h + 1),
+        "c4": P.make_scene(N.PT_SCENE_CORNELL_GLASS, 0, 5, w, h),
+        "layers": S.stacked_layers(w, h),
+        "duplicates": S.duplicates(w, h)[0],
+        "axis": S.axis_camera(c1, w, h),
+        "floor": S.floor_camera(c1, w, h),
+        "spheres64": S.sphere_list(64, w, h),
+        "inside_sphere": S.sphere_list(31, w, h, camera_inside=True),
+    }
+
+
+def check_classes(sd, o, d, ids, name, cast_result=None):
+    """Assert the classification of `ids` against the caster; returns the classes."""
+    c = rc.classify(sd.verts, sd.spheres, o, d, ids, cast_result)
+    n = {k: len(v) for k, v in c.items() if k != "want"}
+    assert n["wrong"] == 0, (name, n, c["wrong"][:10], ids[c["wrong"][:10]], c["want"][c["wrong"][:10]])
+    assert n["edge"] + n["coincident"] <= ALLOWED * len(o), (name, n)
+    return c
+
+
+# the frame size the tessellated scene is checked at: its regular grid lines up with every 4th pixel column of a 65-wide frame
+def _size(name):
+    return (W + 1, H + 1) if name == "tess" else (W, H)
+
+
+@pytest.mark.parametrize("layout", [2, 4, 68, 72, 73])
+def test_oracle_closest_hit_matches_float64(P, pto, layout):
+    """Every adversarial scene: the oracle's primary-hit id image (pto_render of an id_scene) classified against the caster.
+    The floor camera's centre row lies in the floor's plane; those rays are the only ones left out."""
+    for name, sd in scenes(P).items():
+        w, h = _size(name)
+        o, d = rc.camera_rays(pto, S.id_scene(sd).cam, w, h)
+        c = check_classes(sd, o, d, oracle_ids(pto, sd, layout, w, h), name)
+        if name == "floor":
+            assert list(c["in_plane"]) == [(h // 2) * w + x for x in range(w)]
+        else:
+            assert len(c["in_plane"]) == 0, name
+        if name in ("duplicates", "layers", "inside_sphere"):
+            assert len(c["edge"]) + len(c["coincident"]) <= 8, name
+
+
+def test_pto_closest_matches_float64(P, pto):
+    """pto.closest on single rays (brute force and the product's blob) agrees with the caster on the duplicates scene: the lowest
+    id of a tie wins, whichever leaf it sits in."""
+    sd, src = S.duplicates(W, H)
+    o, d = rc.camera_rays(pto, S.id_scene(sd).cam, W, H)
+    sel = np.arange(0, len(o), 7)
+    info, nodes, tris = build_bvh_detached(sd, 68)
+    for sc in (pto.Scene(sd), pto.Scene(sd, (info.width, nodes, tris))):
+        ids = np.array([sc.closest(o[i], d[i])[0] for i in sel], np.uint64)
+        c = check_classes(sd, o[sel], d[sel], ids, "duplicates")
+        hit = ids != rc.MISS
+        assert hit.sum() > 0.6 * len(sel)
+        # the winner is the lowest id among the copies of its source triangle
+        for i in np.nonzero(hit & (ids < len(src)))[0]:
+            assert ids[i] == np.nonzero(src == src[ids[i]])[0].min()
+        assert np.array_equal(ids[hit], c["want"][hit])
+
+
+def test_camera_ray_binding(P, pto):
+    """pto.camera_ray is SPEC §3: the axis camera's centre row and column have direction components of exactly zero."""
+    sd = S.axis_camera(P.make_scene(0, 0, 1, W, H), W, H)
+    o, d = pto.camera_ray(sd.cam, W // 2, H // 2)
+    assert o.dtype == np.float32 and list(d) == [0.0, 0.0, -1.0]
+    assert pto.camera_ray(sd.cam, 3, H // 2)[1][1] == 0.0 and pto.camera_ray(sd.cam, W // 2, 5)[1][0] == 0.0
+    _, d = pto.camera_ray(S.ray_camera(sd, (0, 0, 0), (3, 0, -4)).cam, 0, 0)
+    assert np.allclose(d, [0.6, 0, -0.8], atol=1e-7)
+
+
+def test_caster_in_plane_rule():
+    """A ray is left out as in-plane only if it touches a triangle whose plane it lies in: not for a coplanar triangle off to
+    the side, nor for one behind its origin."""
+    verts = np.float32([[0, 0, -1, 1, 0, -1, 0, 0, -2],        # all in the plane y = 0
+                        [5, 0, -1, 6, 0, -1, 5, 0, -2],
+                        [0, 0, 1, 1, 0, 1, 0, 0, 2]])
+    o = np.float32([[0.2, 0, 0], [0.2, 0, -1.2], [0.2, 0, 0], [0.2, 0, 3]])
+    d = np.float32([[0, 0, -1], [1, 0, 0], [0, 0, 1], [0, 0, 1]])
+    # ray 0 runs across triangle 0; ray 1 starts inside triangle 0 and crosses triangle 1; ray 2 crosses triangle 2;
+    # ray 3 has every triangle behind it
+    no_spheres = np.zeros((0, 4), np.float32)
+    assert list(rc.cast(verts, no_spheres, o, d)[3]) == [True, True, True, False]
+    for tri, want in ((0, [True, True, False, False]), (1, [False, True, False, False]), (2, [False, False, True, False])):
+        assert list(rc.cast(verts[tri:tri + 1], no_spheres, o, d)[3]) == want, tri
+
+
+@pytest.mark.parametrize("layout", [2, 4, 68, 72, 73])
+def test_stacked_layers_overflow_the_lds_stack(P, pto, layout):
+    """Walking the product's blob (SPEC §4 push order, float64 boxes shrunk by a margin) shows that every sampled camera ray of
+    the stacked-layers scene holds more than 12 + 4 stack entries, and never more than pt_bvh_info.stack_need."""
+    sd = S.stacked_layers(W, H)
+    info, nodes, tris = build_bvh_detached(sd, layout)
+    o, d = rc.camera_rays(pto, sd.cam, W, H)
+    depth = [rc.stack_depth(layout, nodes, tris, o[i], d[i]) for i in range(0, len(o), 53)]
+    assert min(depth) > 12 + 4, (layout, min(depth))
+    assert max(depth) <= info.stack_need, (layout, max(depth), info.stack_need)
+
+
+def test_sphere_list_limit(P):
+    """64 spheres are accepted, 65 are refused at the API (kMaxSpheres: they are a flat list)."""
+    build_bvh_detached(S.sphere_list(64, 16, 16))
+    with pytest.raises(P.PtException):
+        build_bvh_detached(S.sphere_list(65, 16, 16))
+
+
+@pytest.mark.parametrize("k", [-30, -8, 8, 30])
+def test_power_of_two_scale_is_invisible_in_the_oracle(P, pto, k):
+    """Scaling every length by 2**k scales every step of SPEC §4-§5 by an exact power of two (only the leaf padding breaks the
+    symmetry, which cannot change a hit), so the path-traced frame is bit-identical for every layout of the product's host
+    builder. Catches what does not scale with the scene: an absolute distance constant in the oracle, or a quantiser exponent
+    saturating at its clamp. A scale-invariant rounding error of the quantiser shifts with k in both frames; a box that no
+    longer encloses its triangles is caught by test_oracle_closest_hit_matches_float64 instead."""
+    N = P.native
+    for sd in (P.make_scene(N.PT_SCENE_CORNELL, 0, 5, 48, 36), P.make_scene(N.PT_SCENE_CORNELL_GLASS, 0, 5, 48, 36),
+               P.make_scene(N.PT_SCENE_CORNELL_TESS, 2000, 5, 48, 36)):
+        p = P.make_params(48, 36, spp=2, max_depth=6)
+        info, nodes, tris = build_bvh_detached(sd, 2)
+        ref, ost = pto.render(pto.Scene(sd, (info.width, nodes, tris)), p)
+        s2 = S.scaled(sd, k)
+        p2 = P.make_params(48, 36, spp=2, max_depth=6, ray_eps=1e-4 * 2.0 ** k)
+        for layout in (2, 4, 68, 72, 73):
+            info, nodes, tris = build_bvh_detached(s2, layout)
+            img, st = pto.render(pto.Scene(s2, (info.width, nodes, tris)), p2)
+            assert st.rays == ost.rays and np.array_equal(img, ref), (k, layout)
+
+
+def crack_rays(P, pto):
+    """The tessellated Cornell box (30,000 triangles, 160x120 camera) and CRACK_RAYS rays from its camera to shared-edge points,
+    each as the only pixel of a 1x1 camera (so the device can trace exactly these rays)."""
+    sd = P.make_scene(P.native.PT_SCENE_CORNELL_TESS, 30000, 0x5EED0001, 160, 120)
+    org = np.array(sd.cam.origin[:], np.float32)
+    cams = [S.ray_camera(sd, org, p - org) for p in S.shared_edge_targets(sd, CRACK_RAYS)]
+    rays = [pto.camera_ray(c.cam, 0, 0) for c in cams]
+    return sd, cams, np.array([r[0] for r in rays]), np.array([r[1] for r in rays])
+
+
+def test_shared_edge_leak_is_pinned(P, pto):
+    """SPEC §4's Möller–Trumbore is not watertight: rays aimed at edges shared by two triangles of a closed mesh slip through.
+    The count is pinned (brute force and the product's blob agree on every ray), so a watertight test shows up here."""
+    sd, _, o, d = crack_rays(P, pto)
+    info, nodes, tris = build_bvh_detached(sd, 0)
+    bf, bvh = pto.Scene(sd), pto.Scene(sd, (info.width, nodes, tris))
+    ids = np.array([bf.closest(o[i], d[i])[0] for i in range(len(o))], np.uint64)
+    assert np.array_equal(ids, [bvh.closest(o[i], d[i])[0] for i in range(len(o))])
+    c = rc.classify(sd.verts, sd.spheres, o, d, ids)
+    assert len(c["wrong"]) == 0 and len(c["coincident"]) == 0
+    assert (c["want"] != rc.MISS).all()  # in float64 every one of these rays hits the box
+    assert len(c["crack"]) == int((ids == rc.MISS).sum()) == PINNED_CRACKS
+
+
+@pytest.mark.xfail(strict=True, reason="SPEC §4's Möller–Trumbore test is not watertight: rays through shared edges of a closed "
+                                       "mesh can miss both triangles (test_shared_edge_leak_is_pinned)")
+def test_shared_edges_are_watertight(P, pto):
+    sd, _, o, d = crack_rays(P, pto)
+    bf = pto.Scene(sd)
+    assert all(bf.closest(o[i], d[i])[0] != rc.MISS for i in range(len(o)))

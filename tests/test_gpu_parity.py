@@ -854,16 +854,20 @@ def test_randomised_configurations_against_the_oracle(P, pto, renderer):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("flags", [8, 4])  # one ray per lane, lane-packing
+@pytest.mark.parametrize("flags", [8, 4, 128])  # one ray per lane, lane-packing, pooled
 def test_sphere_lists_of_any_length(P, pto, renderer, flags):
     """The kernels read the sphere list four spheres per scalar load (device arrays padded to a multiple of four): lists of
-    0, 1, 2, 3, 5, 6 and 9 spheres must give the oracle's frame, ray count and sphere-test count."""
+    0, 1, 2, 3, 5, 6, 9, 10, 31, 63 and 64 (the limit) spheres must give the oracle's frame, ray count and sphere-test count."""
     base = P.make_scene(P.native.PT_SCENE_CORNELL_GLASS, 0, 3, 160, 120)
     rng = np.random.default_rng(5)
     pool = np.concatenate([base.spheres] + [base.spheres * np.float32([1, 1, 1, 0.6]) + np.float32([dx, 0.35 * (k + 1), dz, 0]) for k, (dx, dz) in
                                             enumerate(rng.uniform(-0.15, 0.15, (2, 2)))])[:9].astype(np.float32)
     pool_mat = np.concatenate([base.sph_mat] * 3)[:9].astype(np.uint32)
-    for n in (0, 1, 2, 3, 5, 6, 9):
+    # spheres 9..63: small balls scattered through the box, materials cycling over the scene's four
+    extra = np.concatenate([rng.uniform(-0.8, 0.8, (55, 3)), rng.uniform(0.03, 0.12, (55, 1))], axis=1).astype(np.float32)
+    pool = np.concatenate([pool, extra])
+    pool_mat = np.concatenate([pool_mat, base.sph_mat[np.arange(55) % len(base.sph_mat)]]).astype(np.uint32)
+    for n in (0, 1, 2, 3, 5, 6, 9, 10, 31, 63, 64):
         sd = P.make_scene(P.native.PT_SCENE_CORNELL_GLASS, 0, 3, 160, 120)
         sd.spheres, sd.sph_mat = pool[:n].copy(), pool_mat[:n].copy()
         p = P.make_params(160, 120, spp=6, max_depth=10, streams=2, flags=flags)
