@@ -30,7 +30,9 @@ using namespace ptd;
 
 namespace ptrt {
 
-PT_DEV uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
+// Number of lanes below this one whose bit is set in the wave mask `m` (the position of this lane among them).
+PT_DEV uint32_t lane_prefix(uint64_t m) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); }
+PT_DEV uint32_t lane_id() { return lane_prefix(~0ull); }
 
 // Scene data that no kernel writes, read at a wave-uniform address: through the constant address space the load is a scalar
 // load (s_load_dwordx4 into SGPRs, scalar cache) instead of a vector load whose 64 lanes fetch the same 16 bytes — for the sphere
@@ -60,7 +62,7 @@ PT_DEV void wave_push(uint32_t *counter, uint32_t *queue, bool pred, uint32_t va
 {
     const uint64_t m = __ballot(pred);
     if (m == 0) return;
-    const uint32_t prefix = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    const uint32_t prefix = lane_prefix(m);
     const int leader = __ffsll((long long)m) - 1;
     uint32_t base = 0;
     if ((int)lane_id() == leader) base = atomicAdd(counter, (uint32_t)__popcll(m));
@@ -91,45 +93,33 @@ PT_DEV const ExtArgs &cold()
 }
 
 // Slot order. A slot is one (pixel slot, stream) pair; 64 consecutive slots are one 8x8 pixel block of one stream (a
-// wavefront). PT_STREAM_INNER: the K streams of a block are K consecutive 64-slot groups, so that wavefronts that run
-// at the same time work on the same few tiles of the image (their primary rays want the same corner of the scene,
-// which then fits the XCDs' 4 MB L2s). Otherwise stream-major: all blocks of stream 0, then stream 1, ...
-#ifndef PT_STREAM_INNER
-#define PT_STREAM_INNER 1
-#endif
+// wavefront). The K streams of a block are K consecutive 64-slot groups, so that wavefronts that run at the same time
+// work on the same few tiles of the image (their primary rays want the same corner of the scene, which then fits the
+// XCDs' 4 MB L2s).
 PT_DEV uint32_t slot_stream(uint32_t slot, const FrameParams &fp)
 {
-    if (!PT_STREAM_INNER) return slot / fp.slots_per_stream;
     const uint32_t g = slot >> 6;
     return g - div_by(g, fp.streams_magic, fp.streams_shift) * fp.streams;
 }
 PT_DEV uint32_t slot_pixel_slot(uint32_t slot, const FrameParams &fp)
 {
-    return PT_STREAM_INNER ? ((div_by(slot >> 6, fp.streams_magic, fp.streams_shift) << 6) | (slot & 63u)) : slot % fp.slots_per_stream;
+    return (div_by(slot >> 6, fp.streams_magic, fp.streams_shift) << 6) | (slot & 63u);
 }
-PT_DEV size_t slot_of(uint32_t pixel_slot, uint32_t stream, uint32_t streams, uint32_t slots_per_stream)
+PT_DEV size_t slot_of(uint32_t pixel_slot, uint32_t stream, uint32_t streams)
 {
-    return PT_STREAM_INNER ? (((size_t)(pixel_slot >> 6) * streams + stream) << 6) | (pixel_slot & 63u)
-                           : (size_t)stream * slots_per_stream + pixel_slot;
+    return (((size_t)(pixel_slot >> 6) * streams + stream) << 6) | (pixel_slot & 63u);
 }
 
-// Which shard and which block of that shard's queue a workgroup is. PT_SHARD_FASTEST: a 1-D grid with the shard as the
-// fastest index, so that workgroups are dispatched in slot order (shard s holds every 64th group of 2^kShardGroupShift slots) and, with the
+// Which shard and which block of that shard's queue a workgroup is: a 1-D grid with the shard as the fastest index, so
+// that workgroups are dispatched in slot order (shard s holds every 64th group of 2^kShardGroupShift slots) and, with the
 // dispatcher dealing workgroups round-robin to the 8 XCDs, a shard's workgroups always land on the same XCD.
-#ifndef PT_SHARD_FASTEST
-#define PT_SHARD_FASTEST 1
-#endif
 PT_DEV void block_pos(const PathState &ps, uint32_t &shard, uint32_t &bx, uint32_t &nbx)
 {
     // shard_count is a power of two (kShards / loops): mask and shift, not a division per wave
     const uint32_t sh = 31u - (uint32_t)__builtin_clz(ps.shard_count);
-    if (PT_SHARD_FASTEST) { shard = (blockIdx.x & (ps.shard_count - 1u)) + ps.shard_base; bx = blockIdx.x >> sh; nbx = gridDim.x >> sh; }
-    else { shard = blockIdx.y + ps.shard_base; bx = blockIdx.x; nbx = gridDim.x; }
+    shard = (blockIdx.x & (ps.shard_count - 1u)) + ps.shard_base; bx = blockIdx.x >> sh; nbx = gridDim.x >> sh;
 }
-static inline dim3 shard_grid(uint32_t blocks, uint32_t shard_count)
-{
-    return PT_SHARD_FASTEST ? dim3(blocks * shard_count) : dim3(blocks, shard_count);
-}
+static inline dim3 shard_grid(uint32_t blocks, uint32_t shard_count) { return dim3(blocks * shard_count); }
 
 PT_DEV bool slot_pixel(uint32_t slot_all, const FrameParams &fp, uint32_t &x, uint32_t &y)
 {
@@ -426,10 +416,7 @@ __global__ void __launch_bounds__(kBlock) k_generate(DeviceScene sc, PathState p
     uint32_t shard, bx, nbx;
     block_pos(ps, shard, bx, nbx);
     const uint32_t j = bx * kBlock + threadIdx.x;
-#ifndef PT_DEAL_ROT
-#define PT_DEAL_ROT 1
-#endif
-    const uint32_t t = j >> kShardGroupShift, rot = (shard + kShards - (t * PT_DEAL_ROT) % kShards) % kShards;
+    const uint32_t t = j >> kShardGroupShift, rot = (shard + kShards - t % kShards) % kShards;
     const uint32_t slot = ((t * kShards + rot) << kShardGroupShift) | (j & ((1u << kShardGroupShift) - 1u));
     uint32_t x = 0, y = 0;
     const bool in_range = j < ps.shard_cap && slot < ps.n_slots;
@@ -467,11 +454,7 @@ PT_DEV bool shade_one(const DeviceScene &sc, const PathState &ps, const FramePar
     // The slot's radiance sum | path count comes from HBM: it is requested up front, whether or not this vertex will touch it, so that
     // its latency runs under the hit-record and material loads below instead of behind them (Cornell 7.04 -> 6.83 ms, Cornell + glass
     // + metal 31.9 -> 31.7, soup 68.2 -> 67.6, 1M-triangle Cornell +-0); written back only if touched.
-#ifdef PT_EXP_NOACC // timing probe only (wrong pictures): what the radiance-sum load costs where it stands
-    float4 A = make_float4(0.f, 0.f, 0.f, 0.f);
-#else
     float4 A = at(ps.acc, slot);
-#endif
     bool touched = false, term = false, alive = false;
     auto add = [&](V3 L) {
         touched = true;
@@ -502,11 +485,9 @@ PT_DEV bool shade_one(const DeviceScene &sc, const PathState &ps, const FramePar
         const V3 n = front ? ng : neg(ng);
         float4 m0 = sc.mats[(size_t)mat * 3], m1 = sc.mats[(size_t)mat * 3 + 1];
         const float4 m2 = sc.mats[(size_t)mat * 3 + 2];
-#ifndef PT_EXP_NO_MATPAIR
         // Both rows are requested before either is looked at: left alone, the compiler sinks the second load behind the test of the
         // first row's kind — one more dependent round trip in a step that already chains hit record -> material
         asm volatile("" : "+v"(m0.x), "+v"(m1.x));
-#endif
         const V3 alb = v3(m0.y, m0.z, m0.w), emi = xyz(m1);
         const uint32_t kind = __float_as_uint(m0.x);
         if (MODE == SHADE_QUEUE && kind != (uint32_t)PT_LAMBERT) { defer = 1u + kind; return false; } // shaded by k_shade<SHADE_BUCKETS>
@@ -589,43 +570,10 @@ PT_DEV bool want_compact(const PathState &ps, uint32_t len, uint32_t n_alive, ui
     return forced || (sticky && len < ps.shard_cap) || (float)predicted < ps.compact_below * (float)len;
 }
 
-// EXPERIMENT (-DPT_REPACK_SORT=1; DESIGN.md §4 "coherence-ordered re-packing"): at a re-pack a wave appends its survivors ordered by a
-// 6-bit key — octant of the ray direction, octant of the origin about the scene's centre — instead of by lane. Rank of a lane among
-// the wave's survivors by (key, lane), from ballots alone: walking the key bits from the top, `eq` keeps the lanes that agree with
-// mine so far and `lt` collects those that have a 0 where I have a 1.
-#ifndef PT_REPACK_SORT
-#define PT_REPACK_SORT 0
-#endif
-PT_DEV uint32_t wave_rank_by_key(bool pred, uint32_t key)
-{
-    uint64_t eq = __ballot(pred), lt = 0;
-#pragma unroll
-    for (int b = 5; b >= 0; --b) {
-        const bool one = (key >> b) & 1u;
-        const uint64_t bal = __ballot(pred && one);
-        if (one) lt |= eq & ~bal;
-        eq &= one ? bal : ~bal;
-    }
-    const uint64_t below = (1ull << lane_id()) - 1ull;
-    return (uint32_t)__popcll(lt) + (uint32_t)__popcll(eq & below);
-}
-PT_DEV void wave_push_sorted(uint32_t *counter, uint32_t *queue, bool pred, uint32_t value, uint32_t key)
-{
-    const uint64_t m = __ballot(pred);
-    if (m == 0) return;
-    const uint32_t rank = wave_rank_by_key(pred, key);
-    const int leader = __ffsll((long long)m) - 1;
-    uint32_t base = 0;
-    if ((int)lane_id() == leader) base = atomicAdd(counter, (uint32_t)__popcll(m));
-    base = __shfl(base, leader, 64);
-    if (pred) queue[base + rank] = value;
-}
-
 PT_DEV void queue_next(const PathState &ps, uint32_t shard, uint32_t cnext, uint32_t *q_next, uint32_t gid, uint32_t total, bool alive,
-                       uint32_t slot, bool compact, uint32_t sort_key = 0u)
+                       uint32_t slot, bool compact)
 {
-    if (compact && PT_REPACK_SORT) wave_push_sorted(&ps.counters[cnt_ext_index(cnext, shard)], q_next, alive, slot, sort_key);
-    else if (compact) wave_push(&ps.counters[cnt_ext_index(cnext, shard)], q_next, alive, slot);
+    if (compact) wave_push(&ps.counters[cnt_ext_index(cnext, shard)], q_next, alive, slot);
     else {
         if (gid < total) at(q_next, gid) = alive ? slot : kInvalidSlot;
         if (gid == 0) ps.counters[cnt_ext_index(cnext, shard)] = total;
@@ -678,6 +626,19 @@ PT_DEV int32_t pop_slow(const StackCtx &k, uint32_t &sp)
     const PathState &ps = cold().ps;
     return ps.stack_ovf[(size_t)(sp - kStackLds) * ((size_t)kShards * ps.shard_cap) + k.col];
 }
+// Pop when the caller knows the top entry is in LDS (sp <= kStackLds).
+PT_DEV int32_t pop_lds(const StackCtx &k, uint32_t &sp)
+{
+    if (sp == 0) return PT_BVH_EMPTY;
+    --sp;
+    return k.lds[sp * k.stride + k.tid];
+}
+// Pop after a leaf: the LDS-only path unless some lane of the calling ones has entries in the overflow area.
+PT_DEV int32_t pop_after_leaf(const StackCtx &k, uint32_t &sp)
+{
+    const bool deep = __any((int)(sp > kStackLds)) != 0;
+    return deep ? pop_slow(k, sp) : pop_lds(k, sp);
+}
 
 // One inner-node visit of the lanes that call it: fetch, slab tests, children pushed farthest first, nearest (or the popped
 // stack top) becomes `cur`. Stack fast path: while every calling lane still has room for a whole node's pushes in its LDS column
@@ -712,9 +673,7 @@ PT_DEV void node_visit_rows(const float4 *__restrict__ base, float4 r0, float4 r
                 sp += (h && prev != PT_BVH_EMPTY) ? 1u : 0u;
                 prev = h ? ref[p] : prev;
             }
-            if (prev != PT_BVH_EMPTY) cur = prev;
-            else if (sp) { --sp; cur = k.lds[sp * k.stride + k.tid]; }
-            else cur = PT_BVH_EMPTY;
+            cur = prev != PT_BVH_EMPTY ? prev : pop_lds(k, sp);
         } else {
 #pragma unroll
             for (int p = N - 1; p >= 0; --p)
@@ -732,9 +691,7 @@ PT_DEV void node_visit_rows(const float4 *__restrict__ base, float4 r0, float4 r
             k.lds[sp * k.stride + k.tid] = ref[i];
             sp += key[i] != 0xFFFFFFFFu ? 1u : 0u;
         }
-        if (key[0] != 0xFFFFFFFFu) cur = ref[0];
-        else if (sp) { --sp; cur = k.lds[sp * k.stride + k.tid]; }
-        else cur = PT_BVH_EMPTY;
+        cur = key[0] != 0xFFFFFFFFu ? ref[0] : pop_lds(k, sp);
     } else {
 #pragma unroll
         for (int i = N - 1; i >= 1; --i)
@@ -756,15 +713,83 @@ PT_DEV uint32_t leaf_step(const float4 *__restrict__ tris, const StackCtx &k, V3
         if (more == 0u) break;
         ++first; --more;
     }
-    const bool deep = __any((int)(sp > kStackLds)) != 0;
-    if (!deep) { if (sp) { --sp; cur = k.lds[sp * k.stride + k.tid]; } else cur = PT_BVH_EMPTY; }
-    else cur = pop_slow(k, sp);
+    cur = pop_after_leaf(k, sp);
     return n;
 }
 
 // Finish mode (n_alive <= finish_below): a launch keeps going until its paths end, but never for more than this many
 // vertices per lane, so that a launch stays bounded whatever spp and max_depth are; the host loop simply goes on.
 constexpr uint32_t kFinishVertices = 256;
+
+// The launch prologue of the extend kernels: which shard and queue block the workgroup is, the shard's queue as the previous launch
+// left it, and the queue policy. The shard's first thread rotates the triple-buffered counters (cnext gets this launch's alive count
+// as the next one's prev_alive; the line after next is cleared), folds the previous launch's ray count and counts a re-pack.
+//   predicted : want_compact with the death prediction and the sticky rule (k_extend, k_extend_pool); else the plain ratio
+//   carry_len : a carried-in-place queue keeps its length, written here (else queue_next writes it at the end)
+// SHADE_NONE: one ray per alive entry, counted here. `idle`: the workgroup has nothing to do and returns. `ps` is the caller's cold().ps,
+// so that the prologue's scalar loads and the caller's go through one kernarg pointer. The caller derives the shard's first queue
+// entry, qbase = shard * shard_cap, after its early return: computed before it, it tips k_extend's register allocation into spills.
+struct ExtHead {
+    uint32_t shard, bx, parity, cnext, n, n_alive;
+    bool do_compact, idle;
+};
+template <int FUSE>
+PT_DEV ExtHead extend_head(const ExtArgs &a, const PathState &ps, uint32_t per_block, uint32_t tid, bool predicted, bool carry_len)
+{
+    ExtHead e;
+    const uint32_t it = a.it, ccur = it % 3u, czero = (it + 2u) % 3u;
+    e.parity = it & 1u; e.cnext = (it + 1u) % 3u;
+    uint32_t nbx;
+    block_pos(a.ps, e.shard, e.bx, nbx);
+    e.n = ps.counters[cnt_ext_index(ccur, e.shard)]; e.n_alive = ps.counters[cnt_alive_index(ccur, e.shard)];
+    e.do_compact = FUSE != SHADE_NONE &&
+                   (predicted ? want_compact(ps, e.n, e.n_alive, ps.counters[cnt_prev_alive_index(ccur, e.shard)], ps.repack_sticky != 0u, a.compact != 0u)
+                              : want_compact(ps, e.n, e.n_alive, 0u, false, a.compact != 0u));
+    if (e.bx * per_block + tid == 0u) {
+        ps.counters[cnt_prev_alive_index(e.cnext, e.shard)] = e.n_alive;
+        ps.counters[cnt_ext_index(czero, e.shard)] = 0u; // the queue after next
+        ps.counters[cnt_alive_index(czero, e.shard)] = 0u;
+        fold_traced(ps, e.shard, it, e.n, e.n_alive);
+        if (FUSE == SHADE_NONE) *traced_counter(ps, e.cnext, e.shard) = e.n_alive; // the fused kernels count what they trace, per wavefront
+        else if (carry_len && !e.do_compact) ps.counters[cnt_ext_index(e.cnext, e.shard)] = e.n;
+        if (e.do_compact && e.n_alive) atomicAdd(&ps.counters[kCntCompactions], 1u);
+    }
+    e.idle = e.bx * per_block >= e.n || e.n_alive == 0u;
+    return e;
+}
+
+// Park what traversal does not need in LDS (column `tid` of five rows of `stride` words): 5 VGPRs less while the wave gathers nodes.
+PT_DEV void stash_park(uint32_t *stash, uint32_t stride, uint32_t tid, const PathRegs &r)
+{
+    stash[0 * stride + tid] = __float_as_uint(r.T.x); stash[1 * stride + tid] = __float_as_uint(r.T.y);
+    stash[2 * stride + tid] = __float_as_uint(r.T.z); stash[3 * stride + tid] = r.key;
+    stash[4 * stride + tid] = (r.sample << 8) | r.depth;
+    asm volatile("" ::: "memory"); // the values must really leave the registers: no store-to-load forwarding across the traversal
+}
+PT_DEV void stash_restore(const uint32_t *stash, uint32_t stride, uint32_t tid, PathRegs &r)
+{
+    r.T = v3(__uint_as_float(stash[0 * stride + tid]), __uint_as_float(stash[1 * stride + tid]), __uint_as_float(stash[2 * stride + tid]));
+    r.key = stash[3 * stride + tid];
+    const uint32_t sdv = stash[4 * stride + tid];
+    r.sample = sdv >> 8; r.depth = sdv & 255u;
+}
+
+// PT_FLAG_COUNT_VISITS tallies of one lane, flushed once per lane at the end of the launch.
+struct VisitCounts {
+    unsigned long long nodes = 0, tris = 0, sph = 0;
+    unsigned long long wave_iters = 0, wave_iters_late = 0, idle_leaf = 0, idle_done = 0; // k_extend / k_extend_pool diagnostics
+};
+PT_DEV void flush_visit_counters(const PathState &ps, const VisitCounts &v)
+{
+    auto add = [&](uint32_t i, unsigned long long x) { atomicAdd(reinterpret_cast<unsigned long long *>(ps.counters + i), x); };
+    if (v.wave_iters) add(kCntWaveNodeIters, v.wave_iters);
+    if (v.wave_iters_late) add(kCntWaveNodeIters + 2, v.wave_iters_late);
+    if (v.idle_leaf) add(kCntIdleLeaf, v.idle_leaf);
+    if (v.idle_done) add(kCntIdleDone, v.idle_done);
+    add(kCntNodes, v.nodes);
+    add(kCntTris, v.tris);
+    add(kCntSph, v.sph);
+}
 
 template <int L, bool COUNT, int FUSE>
 __global__ void __launch_bounds__(kExtBlock) __attribute__((amdgpu_waves_per_eu(PT_EXT_WAVES(L, FUSE), PT_EXT_WAVES(L, FUSE)))) k_extend(ExtArgs a)
@@ -773,33 +798,18 @@ __global__ void __launch_bounds__(kExtBlock) __attribute__((amdgpu_waves_per_eu(
     const float4 *__restrict__ nodes = a.sc.nodes, *__restrict__ tris = a.sc.tris, *__restrict__ spheres = a.sc.spheres;
     const uint32_t n_spheres = a.sc.n_spheres, n_tris = a.sc.n_tris, n_nodes = a.sc.n_nodes;
     const uint32_t it = a.it;
-    const uint32_t parity = it & 1u, ccur = it % 3u, cnext = (it + 1u) % 3u, czero = (it + 2u) % 3u;
     __shared__ int32_t s_stack[kStackLds * kExtBlock];
     __shared__ uint32_t s_stash[(FUSE != SHADE_NONE ? 5 : 1) * kExtBlock];
-    uint32_t *stash = s_stash;
-    uint32_t shard, bx, nbx;
-    block_pos(a.ps, shard, bx, nbx);
     const uint32_t tid = threadIdx.x;
-    const uint32_t gid = bx * kExtBlock + tid;                  // index inside the shard's queue
-    uint32_t n, n_alive, slot = kInvalidSlot, n_bounces;
-    bool do_compact;
-    uint32_t qbase; // first entry of this shard's region of the queues (entries: 32-bit offsets like the slot arrays, see at())
+    ExtHead hd;
+    uint32_t gid, qbase, slot = kInvalidSlot, n_bounces; // qbase: first entry of this shard's region of the queues (see at())
     {
         const PathState &ps = cold().ps;
-        n = ps.counters[cnt_ext_index(ccur, shard)]; n_alive = ps.counters[cnt_alive_index(ccur, shard)];
-        do_compact = FUSE != SHADE_NONE && want_compact(ps, n, n_alive, ps.counters[cnt_prev_alive_index(ccur, shard)], ps.repack_sticky != 0u, a.compact != 0u);
-        if (gid == 0) {
-            ps.counters[cnt_prev_alive_index(cnext, shard)] = n_alive;
-            ps.counters[cnt_ext_index(czero, shard)] = 0u;         // the queue after next
-            ps.counters[cnt_alive_index(czero, shard)] = 0u;
-            fold_traced(ps, shard, it, n, n_alive);
-            if (FUSE == SHADE_NONE) *traced_counter(ps, cnext, shard) = n_alive; // one ray per alive entry; the fused kernel
-                                                                                 // counts what it traces, per wavefront
-            if (do_compact && n_alive) atomicAdd(&ps.counters[kCntCompactions], 1u);
-        }
-        if (bx * kExtBlock >= n || n_alive == 0u) return;
-        qbase = shard * ps.shard_cap;
-        if (gid < n) slot = at(ps.q_ext[parity], qbase + gid);
+        hd = extend_head<FUSE>(a, ps, kExtBlock, tid, true, false);
+        gid = hd.bx * kExtBlock + tid;                         // index inside the shard's queue
+        if (hd.idle) return;
+        qbase = hd.shard * ps.shard_cap;
+        if (gid < hd.n) slot = at(ps.q_ext[hd.parity], qbase + gid);
         // FUSE: up to `bounces` path vertices per launch with the path state in registers (a terminated path continues with
         // its stream's next camera ray, so most lanes stay busy); the state goes back to memory once, at the end.
         // Once few paths are left in the shard (the frame's tail) the launch runs them to their end instead (bounded by
@@ -807,13 +817,14 @@ __global__ void __launch_bounds__(kExtBlock) __attribute__((amdgpu_waves_per_eu(
         // behind a wave's longest path. A launch that STARTS sparse (many paths ended during the previous one) runs every
         // wavefront at the cost of its few live lanes; it advances one vertex only, re-packs, and the dense launch after
         // it does the real work.
-        const bool sparse = do_compact && (float)n_alive < ps.sparse_below * (float)n;
-        n_bounces = FUSE == SHADE_NONE ? 1u : (n_alive <= ps.finish_below ? kFinishVertices : sparse ? 1u : a.bounces);
+        const bool sparse = hd.do_compact && (float)hd.n_alive < ps.sparse_below * (float)hd.n;
+        n_bounces = FUSE == SHADE_NONE ? 1u : (hd.n_alive <= ps.finish_below ? kFinishVertices : sparse ? 1u : a.bounces);
     }
+    const uint32_t shard = hd.shard, parity = hd.parity, n = hd.n;
     const bool active = slot != kInvalidSlot;                  // holes: paths that ended since the queue was last compacted
     const StackCtx stk{ s_stack, kExtBlock, tid, qbase + gid };
 
-    unsigned long long c_nodes = 0, c_tris = 0, c_sph = 0, c_wave_iters = 0, c_wave_iters_late = 0, c_idle_leaf = 0, c_idle_done = 0;
+    VisitCounts vc;
     __shared__ int32_t s_state[COUNT ? 64 : 1]; // COUNT diagnostics: every lane's `cur` (1 = no ray), readable by the lane that counts
     PathRegs r;
     r.o = v3(0.f, 0.f, 0.f); r.d = v3(0.f, 0.f, 1.f); r.T = v3(0.f, 0.f, 0.f); r.key = r.sample = r.depth = 0u;
@@ -836,14 +847,9 @@ __global__ void __launch_bounds__(kExtBlock) __attribute__((amdgpu_waves_per_eu(
     if (alive) {
         const V3 o = r.o, d = r.d;
         Hit h{ __builtin_inff(), PT_MISS, PT_MISS };
-        if (FUSE != SHADE_NONE) { // park what traversal does not need in LDS: 5 VGPRs less while the wave gathers nodes
-            stash[0 * kExtBlock + tid] = __float_as_uint(r.T.x); stash[1 * kExtBlock + tid] = __float_as_uint(r.T.y);
-            stash[2 * kExtBlock + tid] = __float_as_uint(r.T.z); stash[3 * kExtBlock + tid] = r.key;
-            stash[4 * kExtBlock + tid] = (r.sample << 8) | r.depth;
-            asm volatile("" ::: "memory"); // the values must really leave the registers: no store-to-load forwarding across the traversal
-        }
+        if (FUSE != SHADE_NONE) stash_park(s_stash, kExtBlock, tid, r);
 
-        { const uint32_t ns = spheres_test(spheres, n_spheres, n_tris, o, d, h); if (COUNT) c_sph += ns; }
+        { const uint32_t ns = spheres_test(spheres, n_spheres, n_tris, o, d, h); if (COUNT) vc.sph += ns; }
 
         const RaySetup rs = ray_setup(o, d);
         int32_t cur = n_nodes ? 0 : PT_BVH_EMPTY;
@@ -853,7 +859,7 @@ __global__ void __launch_bounds__(kExtBlock) __attribute__((amdgpu_waves_per_eu(
         // 7.31 -> 7.02, Cornell+glass+metal 32.6 -> 31.9).
         if (n_nodes) {
             ++steps;
-            if (COUNT) { c_nodes++; if (lane_id() == (uint32_t)(__ffsll((long long)__ballot(1)) - 1)) c_wave_iters++; }
+            if (COUNT) { vc.nodes++; if (lane_id() == (uint32_t)(__ffsll((long long)__ballot(1)) - 1)) vc.wave_iters++; }
             const uniform_f4 root = as_uniform(nodes);
             node_visit_rows<L>(nodes, uniform_load(root, 0), uniform_load(root, 1), uniform_load(root, 2), uniform_load(root, 3), stk, rs, h.t, cur, sp);
             if (COUNT) s_state[tid & 63u] = cur;
@@ -870,13 +876,13 @@ __global__ void __launch_bounds__(kExtBlock) __attribute__((amdgpu_waves_per_eu(
             while ((uint32_t)cur < (uint32_t)PT_BVH_EMPTY) { // ---- node phase: inner-node refs are 0 .. 0x7ffffffe (EMPTY = 0x7fffffff)
                 if (++steps > (1u << 22)) { atomicOr(&cold().ps.counters[kCntError], 2u); cur = PT_BVH_EMPTY; break; }
                 if (COUNT) { // one lane per wave-iteration counts it; [1]: iterations after the wave's first leaf phase of this ray
-                    c_nodes++;
+                    vc.nodes++;
                     if (lane_id() == (uint32_t)(__ffsll((long long)__ballot(1)) - 1)) {
-                        c_wave_iters++; if (late_cycle) c_wave_iters_late++;
+                        vc.wave_iters++; if (late_cycle) vc.wave_iters_late++;
                         // why the other lanes of this iteration are idle (their state sits in LDS: they are masked off here)
                         uint32_t n_leaf = 0, n_done = 0;
                         for (uint32_t l = 0; l < 64u; ++l) { const int32_t c2 = s_state[l]; n_leaf += c2 < 0 ? 1u : 0u; n_done += c2 == PT_BVH_EMPTY ? 1u : 0u; }
-                        c_idle_leaf += n_leaf; c_idle_done += n_done;
+                        vc.idle_leaf += n_leaf; vc.idle_done += n_done;
                     }
                 }
                 node_step<L>(nodes, stk, rs, h.t, cur, sp);
@@ -885,15 +891,12 @@ __global__ void __launch_bounds__(kExtBlock) __attribute__((amdgpu_waves_per_eu(
             if (cur == PT_BVH_EMPTY) break;
             if (COUNT) late_cycle = true;
             const uint32_t nt = leaf_step(tris, stk, o, d, h, cur, sp); // ---- leaf phase
-            if (COUNT) { c_tris += nt; s_state[tid & 63u] = cur; }
+            if (COUNT) { vc.tris += nt; s_state[tid & 63u] = cur; }
         }
 
         if (FUSE == SHADE_NONE) at(cold().ps.hit, slot) = make_float2(h.t, __uint_as_float(h.ref)); // k_shade walks the same queue in the same order
         else {
-            r.T = v3(__uint_as_float(stash[0 * kExtBlock + tid]), __uint_as_float(stash[1 * kExtBlock + tid]), __uint_as_float(stash[2 * kExtBlock + tid]));
-            r.key = stash[3 * kExtBlock + tid];
-            const uint32_t sdv = stash[4 * kExtBlock + tid];
-            r.sample = sdv >> 8; r.depth = sdv & 255u;
+            stash_restore(s_stash, kExtBlock, tid, r);
             uint32_t defer = 0u;
             const ExtArgs &c = cold();
             alive = shade_one<FUSE>(c.sc, c.ps, c.fp, slot, r, h.t, h.ref, B_LAMBERT, defer);
@@ -901,22 +904,11 @@ __global__ void __launch_bounds__(kExtBlock) __attribute__((amdgpu_waves_per_eu(
     }
     }
     const PathState &ps = cold().ps;
-    if (COUNT && active) {
-        if (c_wave_iters) atomicAdd(reinterpret_cast<unsigned long long *>(ps.counters + kCntWaveNodeIters), c_wave_iters);
-        if (c_wave_iters_late) atomicAdd(reinterpret_cast<unsigned long long *>(ps.counters + kCntWaveNodeIters + 2), c_wave_iters_late);
-        if (c_idle_leaf) atomicAdd(reinterpret_cast<unsigned long long *>(ps.counters + kCntIdleLeaf), c_idle_leaf);
-        if (c_idle_done) atomicAdd(reinterpret_cast<unsigned long long *>(ps.counters + kCntIdleDone), c_idle_done);
-        atomicAdd(reinterpret_cast<unsigned long long *>(ps.counters + kCntNodes), c_nodes);
-        atomicAdd(reinterpret_cast<unsigned long long *>(ps.counters + kCntTris), c_tris);
-        atomicAdd(reinterpret_cast<unsigned long long *>(ps.counters + kCntSph), c_sph);
-    }
+    if (COUNT && active) flush_visit_counters(ps, vc);
     if (FUSE != SHADE_NONE) {
         if (alive) path_store(ps, slot, r);
-        uint32_t sort_key = 0u;
-        if (PT_REPACK_SORT) sort_key = (r.d.x < 0.f ? 32u : 0u) | (r.d.y < 0.f ? 16u : 0u) | (r.d.z < 0.f ? 8u : 0u) |
-                                       (r.o.x < 0.f ? 4u : 0u) | (r.o.y < 0.f ? 2u : 0u) | (r.o.z < 0.f ? 1u : 0u);
-        queue_next(ps, shard, cnext, &at(ps.q_ext[parity ^ 1u], qbase), gid, n, alive, slot, do_compact, sort_key);
-        if (wave_rays && lane_id() == 0u) atomicAdd(traced_counter(ps, cnext, shard), (unsigned long long)wave_rays);
+        queue_next(ps, shard, hd.cnext, &at(ps.q_ext[parity ^ 1u], qbase), gid, n, alive, slot, hd.do_compact);
+        if (wave_rays && lane_id() == 0u) atomicAdd(traced_counter(ps, hd.cnext, shard), (unsigned long long)wave_rays);
     }
 }
 
@@ -947,34 +939,22 @@ k_extend_packed(ExtArgs a)
     // hot arguments stay in SGPRs; everything else is read through cold() where it is used (see ExtArgs)
     const float4 *__restrict__ nodes = a.sc.nodes, *__restrict__ tris = a.sc.tris, *__restrict__ spheres = a.sc.spheres;
     const uint32_t n_spheres = a.sc.n_spheres, n_tris = a.sc.n_tris, n_nodes = a.sc.n_nodes;
-    const uint32_t it = a.it, chunk = a.chunk, compact = a.compact, bounces = a.bounces;
-    constexpr int N = fanout<L>();
+    const uint32_t it = a.it, chunk = a.chunk, bounces = a.bounces;
     __shared__ int32_t s_stack[kStackLds * 64];
     __shared__ uint32_t s_stash[(FUSE != SHADE_NONE ? 5 : 1) * 64];
-    uint32_t *stash = s_stash;
-    const uint32_t parity = it & 1u, ccur = it % 3u, cnext = (it + 1u) % 3u, czero = (it + 2u) % 3u;
-    uint32_t shard, bx, nbx;
-    block_pos(a.ps, shard, bx, nbx);
-    const uint32_t n = cold().ps.counters[cnt_ext_index(ccur, shard)], n_alive = cold().ps.counters[cnt_alive_index(ccur, shard)];
     const uint32_t lane = threadIdx.x;
-    const bool do_compact = FUSE != SHADE_NONE && want_compact(cold().ps, n, n_alive, 0u, false, compact != 0u); // holes cost this kernel one skipped pull: plain ratio
-    if (bx == 0 && lane == 0) {
-        cold().ps.counters[cnt_prev_alive_index(cnext, shard)] = n_alive; // for a one-ray-per-lane launch that may follow (probe frames)
-        cold().ps.counters[cnt_ext_index(czero, shard)] = 0u;
-        cold().ps.counters[cnt_alive_index(czero, shard)] = 0u;
-        fold_traced(cold().ps, shard, it, n, n_alive);
-        if (FUSE == SHADE_NONE) *traced_counter(cold().ps, cnext, shard) = n_alive; // one ray per alive entry
-        else if (!do_compact) cold().ps.counters[cnt_ext_index(cnext, shard)] = n;  // carried in place: the length stays
-        if (do_compact && n_alive) atomicAdd(&cold().ps.counters[kCntCompactions], 1u);
-    }
-    uint32_t next = bx * chunk;                               // wave-uniform cursor into the shard's queue
-    if (next >= n || n_alive == 0u) return;
-    const uint32_t end = min(n, next + chunk);
-    const size_t qbase = (size_t)shard * cold().ps.shard_cap;
-    const uint32_t *queue = cold().ps.q_ext[parity] + qbase;
-    uint32_t *q_next = cold().ps.q_ext[parity ^ 1u] + qbase;
-    const size_t uid = qbase + (size_t)bx * 64u + lane;        // unique per thread of this launch (chunk >= 64)
-    const size_t ovf_stride = (size_t)kShards * cold().ps.shard_cap;
+    // holes cost this kernel one skipped pull: plain-ratio re-pack; prev_alive is still written for a one-ray-per-lane launch that
+    // may follow (probe frames)
+    const ExtHead hd = extend_head<FUSE>(a, cold().ps, chunk, lane, false, true);
+    if (hd.idle) return;
+    const uint32_t shard = hd.shard, n_alive = hd.n_alive;
+    const bool do_compact = hd.do_compact;
+    uint32_t next = hd.bx * chunk;                            // wave-uniform cursor into the shard's queue
+    const uint32_t end = min(hd.n, next + chunk);
+    const uint32_t qbase = hd.shard * cold().ps.shard_cap;
+    const uint32_t *queue = cold().ps.q_ext[hd.parity] + (size_t)qbase;
+    uint32_t *q_next = cold().ps.q_ext[hd.parity ^ 1u] + (size_t)qbase;
+    const StackCtx stk{ s_stack, 64u, lane, qbase + hd.bx * 64u + lane }; // overflow column unique per thread of the launch (chunk >= 64)
     const uint32_t budget0 = FUSE == SHADE_NONE ? 1u : (n_alive <= cold().ps.finish_below ? kFinishVertices : bounces);
 
     bool has = false;                                          // lane holds a ray
@@ -985,33 +965,13 @@ k_extend_packed(ExtArgs a)
     V3 &o = r.o, &d = r.d;
     RaySetup rs = ray_setup(o, d);
     Hit h{ __builtin_inff(), PT_MISS, PT_MISS };
-    unsigned long long c_nodes = 0, c_tris = 0, c_sph = 0;
+    VisitCounts vc;
     uint32_t wave_rays = 0, wave_alive = 0;
 
-    auto push = [&](int32_t v) {
-        if (sp < kStackLds) s_stack[sp * 64u + lane] = v;
-        else {
-            const uint32_t e = sp - kStackLds;
-            if (e < cold().ps.stack_ovf_entries) cold().ps.stack_ovf[(size_t)e * ovf_stride + uid] = v;
-            else { atomicOr(&cold().ps.counters[kCntError], 1u); return; }
-        }
-        ++sp;
-    };
-    auto pop = [&]() -> int32_t {
-        if (sp == 0) return PT_BVH_EMPTY;
-        --sp;
-        return sp < kStackLds ? s_stack[sp * 64u + lane] : cold().ps.stack_ovf[(size_t)(sp - kStackLds) * ovf_stride + uid];
-    };
-
     auto start_ray = [&]() { // the lane's ray is in r.o, r.d
-        if (FUSE != SHADE_NONE) { // park what traversal does not need (as in k_extend)
-            stash[0 * 64u + lane] = __float_as_uint(r.T.x); stash[1 * 64u + lane] = __float_as_uint(r.T.y);
-            stash[2 * 64u + lane] = __float_as_uint(r.T.z); stash[3 * 64u + lane] = r.key;
-            stash[4 * 64u + lane] = (r.sample << 8) | r.depth;
-            asm volatile("" ::: "memory"); // no store-to-load forwarding: the values leave the registers
-        }
+        if (FUSE != SHADE_NONE) stash_park(s_stash, 64u, lane, r); // as in k_extend
         h = Hit{ __builtin_inff(), PT_MISS, PT_MISS };
-        { const uint32_t ns = spheres_test(spheres, n_spheres, n_tris, o, d, h); if (COUNT) c_sph += ns; }
+        { const uint32_t ns = spheres_test(spheres, n_spheres, n_tris, o, d, h); if (COUNT) vc.sph += ns; }
         rs = ray_setup(o, d);
         cur = n_nodes ? 0 : PT_BVH_EMPTY;
         sp = 0; steps = 0;
@@ -1026,10 +986,7 @@ k_extend_packed(ExtArgs a)
                 at(cold().ps.hit, slot) = make_float2(h.t, __uint_as_float(h.ref));
                 has = false;
             } else {
-                r.T = v3(__uint_as_float(stash[0 * 64u + lane]), __uint_as_float(stash[1 * 64u + lane]), __uint_as_float(stash[2 * 64u + lane]));
-                r.key = stash[3 * 64u + lane];
-                const uint32_t sdv = stash[4 * 64u + lane];
-                r.sample = sdv >> 8; r.depth = sdv & 255u;
+                stash_restore(s_stash, 64u, lane, r);
                 uint32_t defer = 0u;
                 const bool alive = shade_one<FUSE>(cold().sc, cold().ps, cold().fp, slot, r, h.t, h.ref, B_LAMBERT, defer);
                 --budget;
@@ -1043,14 +1000,14 @@ k_extend_packed(ExtArgs a)
         if (FUSE != SHADE_NONE) {
             wave_rays += (uint32_t)__popcll(__ballot(fin && has));
             wave_alive += (uint32_t)__popcll(__ballot(retire_alive));
-            if (do_compact) wave_push(&cold().ps.counters[cnt_ext_index(cnext, shard)], q_next, retire_alive, slot);
+            if (do_compact) wave_push(&cold().ps.counters[cnt_ext_index(hd.cnext, shard)], q_next, retire_alive, slot);
             else if (retired) q_next[pos] = retire_alive ? slot : kInvalidSlot; // the entry keeps its queue position
         }
         // ---- refill idle lanes from the wave's chunk
         const uint64_t idle = __ballot(!has);
         const uint32_t avail = end - next;
         if (idle && avail) {
-            const uint32_t prefix = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+            const uint32_t prefix = lane_prefix(idle);
             const bool pull = !has && prefix < avail;
             if (pull) { pos = next + prefix; slot = queue[pos]; }
             if (pull && slot == kInvalidSlot) { // a hole leaves the lane idle until the next refill
@@ -1081,56 +1038,14 @@ k_extend_packed(ExtArgs a)
                 const uint32_t enc = (uint32_t)~cur, first = enc >> 3, more = enc & 7u;
                 const float4 *base = inner ? nodes + (size_t)cur * node_rows<L>() : tris + (size_t)first * 4;
                 const float4 r0 = base[0], r1 = base[1], r2 = base[2], r3 = base[3];
-                const bool deep = __any((int)(sp + (uint32_t)(N - 1) > kStackLds)) != 0; // stack fast path as in k_extend
-                auto pop_fast = [&]() -> int32_t {
-                    if (sp == 0) return PT_BVH_EMPTY;
-                    --sp;
-                    return s_stack[sp * 64u + lane];
-                };
                 if (++steps > (1u << 22)) { atomicOr(&cold().ps.counters[kCntError], 2u); cur = PT_BVH_EMPTY; }
-                else if (inner && L == PT_BVH_WIDTH_8O) { // octant order: see node_visit_rows
-                    uint32_t hits;
-                    int32_t ref[N];
-                    if constexpr (L == PT_BVH_WIDTH_8O) visit_node_oct8(base, r0, r1, r2, r3, rs, h.t, hits, ref);
-                    if (COUNT) c_nodes++;
-                    int32_t prev = PT_BVH_EMPTY;
-                    if (!deep) {
-#pragma unroll
-                        for (int p = N - 1; p >= 0; --p) {
-                            const bool hp = (hits >> p) & 1u;
-                            s_stack[sp * 64u + lane] = prev;
-                            sp += (hp && prev != PT_BVH_EMPTY) ? 1u : 0u;
-                            prev = hp ? ref[p] : prev;
-                        }
-                        cur = prev != PT_BVH_EMPTY ? prev : pop_fast();
-                    } else {
-#pragma unroll
-                        for (int p = N - 1; p >= 0; --p)
-                            if ((hits >> p) & 1u) { if (prev != PT_BVH_EMPTY) push(prev); prev = ref[p]; }
-                        cur = prev != PT_BVH_EMPTY ? prev : pop();
-                    }
-                } else if (inner) {
-                    uint32_t key[N];
-                    int32_t ref[N];
-                    visit_node<L>(base, r0, r1, r2, r3, rs, h.t, key, ref);
-                    if (COUNT) c_nodes++;
-                    if (!deep) {
-#pragma unroll
-                        for (int i = N - 1; i >= 1; --i) {
-                            s_stack[sp * 64u + lane] = ref[i];
-                            sp += key[i] != 0xFFFFFFFFu ? 1u : 0u;
-                        }
-                        cur = (key[0] != 0xFFFFFFFFu) ? ref[0] : pop_fast();
-                    } else {
-#pragma unroll
-                        for (int i = N - 1; i >= 1; --i)
-                            if (key[i] != 0xFFFFFFFFu) push(ref[i]);
-                        cur = (key[0] != 0xFFFFFFFFu) ? ref[0] : pop();
-                    }
-                } else {
+                else if (inner) {
+                    node_visit_rows<L>(base, r0, r1, r2, r3, stk, rs, h.t, cur, sp);
+                    if (COUNT) vc.nodes++;
+                } else { // one triangle per step: the wave may refill between the triangles of a leaf
                     tri_test(r0, r1, r2, first, o, d, h);
-                    if (COUNT) c_tris++;
-                    cur = more ? (int32_t)~(((first + 1u) << 3) | (more - 1u)) : (deep ? pop() : pop_fast());
+                    if (COUNT) vc.tris++;
+                    cur = more ? (int32_t)~(((first + 1u) << 3) | (more - 1u)) : pop_after_leaf(stk, sp);
                 }
             }
             const uint32_t busy = (uint32_t)__popcll(__ballot(has && cur != PT_BVH_EMPTY));
@@ -1142,14 +1057,10 @@ k_extend_packed(ExtArgs a)
             }
         }
     }
-    if (COUNT) {
-        atomicAdd(reinterpret_cast<unsigned long long *>(cold().ps.counters + kCntNodes), c_nodes);
-        atomicAdd(reinterpret_cast<unsigned long long *>(cold().ps.counters + kCntTris), c_tris);
-        atomicAdd(reinterpret_cast<unsigned long long *>(cold().ps.counters + kCntSph), c_sph);
-    }
+    if (COUNT) flush_visit_counters(cold().ps, vc);
     if (FUSE != SHADE_NONE && lane == 0u) {
-        if (wave_rays) atomicAdd(traced_counter(cold().ps, cnext, shard), (unsigned long long)wave_rays);
-        if (wave_alive) atomicAdd(&cold().ps.counters[cnt_alive_index(cnext, shard)], wave_alive);
+        if (wave_rays) atomicAdd(traced_counter(cold().ps, hd.cnext, shard), (unsigned long long)wave_rays);
+        if (wave_alive) atomicAdd(&cold().ps.counters[cnt_alive_index(hd.cnext, shard)], wave_alive);
     }
 }
 
@@ -1186,37 +1097,26 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT_POOL
     static_assert(E % 64u == 0 && E >= 64u && E <= 256u, "kPool: 64, 128, 192 or 256 (live list holds byte indices)");
     const float4 *__restrict__ nodes = a.sc.nodes, *__restrict__ tris = a.sc.tris, *__restrict__ spheres = a.sc.spheres;
     const uint32_t n_spheres = a.sc.n_spheres, n_tris = a.sc.n_tris, n_nodes = a.sc.n_nodes;
-    const uint32_t it = a.it;
-    const uint32_t parity = it & 1u, ccur = it % 3u, cnext = (it + 1u) % 3u, czero = (it + 2u) % 3u;
     __shared__ int32_t s_stack[kStackLds * 64];
     __shared__ float s_ht[E];       // per pool entry: closest hit so far (before traversal: of the sphere list), t
     __shared__ uint32_t s_href[E];  //                 ... and its primitive ref
     __shared__ uint32_t s_slot[E];  // slot of the entry, kInvalidSlot once its path and stream have ended
     __shared__ uint8_t s_live[E];   // entries that hold a ray for the coming traversal, densely
-    uint32_t shard, bx, nbx;
-    block_pos(a.ps, shard, bx, nbx);
     const uint32_t lane = threadIdx.x;
-    uint32_t n, n_alive, n_bounces;
-    bool do_compact;
+    ExtHead hd;
+    uint32_t n_bounces;
     size_t qbase;
     {
         const PathState &ps = cold().ps;
-        n = ps.counters[cnt_ext_index(ccur, shard)]; n_alive = ps.counters[cnt_alive_index(ccur, shard)];
-        do_compact = want_compact(ps, n, n_alive, ps.counters[cnt_prev_alive_index(ccur, shard)], ps.repack_sticky != 0u, a.compact != 0u);
-        if (bx == 0 && lane == 0) {
-            ps.counters[cnt_prev_alive_index(cnext, shard)] = n_alive;
-            ps.counters[cnt_ext_index(czero, shard)] = 0u;
-            ps.counters[cnt_alive_index(czero, shard)] = 0u;
-            fold_traced(ps, shard, it, n, n_alive);
-            if (!do_compact) ps.counters[cnt_ext_index(cnext, shard)] = n; // carried in place: the length stays
-            if (do_compact && n_alive) atomicAdd(&ps.counters[kCntCompactions], 1u);
-        }
-        if (bx * E >= n || n_alive == 0u) return;
-        qbase = (size_t)shard * ps.shard_cap;
-        n_bounces = n_alive <= ps.finish_below ? kFinishVertices : a.bounces;
+        hd = extend_head<FUSE>(a, ps, E, lane, true, true);
+        if (hd.idle) return;
+        qbase = (size_t)hd.shard * ps.shard_cap;
+        n_bounces = hd.n_alive <= ps.finish_below ? kFinishVertices : a.bounces;
     }
+    const uint32_t shard = hd.shard, bx = hd.bx, parity = hd.parity, n = hd.n;
+    const bool do_compact = hd.do_compact;
     const StackCtx stk{ s_stack, 64u, lane, (uint32_t)qbase + bx * 64u + lane };
-    unsigned long long c_nodes = 0, c_tris = 0, c_sph = 0, c_wave_iters = 0;
+    VisitCounts vc;
 
     auto spheres_of = [&](V3 o, V3 d, uint32_t e) { // the sphere list is tested when a ray is made (full width); traversal starts from its result
         Hit h{ __builtin_inff(), PT_MISS, PT_MISS };
@@ -1225,7 +1125,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT_POOL
     };
     auto live_append = [&](bool pred, uint32_t e, uint32_t &count) {
         const uint64_t m = __ballot(pred);
-        if (pred) s_live[count + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = (uint8_t)e;
+        if (pred) s_live[count + lane_prefix(m)] = (uint8_t)e;
         count += (uint32_t)__popcll(m);
     };
 
@@ -1260,7 +1160,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT_POOL
             const uint64_t idle = __ballot(!has);
             const uint32_t avail = n_live - next;
             if (idle && avail) {
-                const uint32_t prefix = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+                const uint32_t prefix = lane_prefix(idle);
                 if (!has && prefix < avail) {
                     const PathState &ps = cold().ps;
                     e = s_live[next + prefix];
@@ -1271,7 +1171,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT_POOL
                     cur = n_nodes ? 0 : PT_BVH_EMPTY;
                     rs = ray_setup(o, d);
                     sp = 0; steps = 0; has = true;
-                    if (COUNT) c_sph += n_spheres;
+                    if (COUNT) vc.sph += n_spheres;
                 }
                 next += min((uint32_t)__popcll(idle), avail);
             }
@@ -1283,11 +1183,11 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT_POOL
                 const uint32_t n_l = (uint32_t)__popcll(m_l), busy = (uint32_t)__popcll(m_n) + n_l;
                 if (next < n_live && 64u - busy >= kPoolRefill) break; // enough lanes can take a new ray
                 if (m_l && (!m_n || n_l >= kPoolLeafWait)) {
-                    if (is_l) { const uint32_t nt = leaf_step(tris, stk, o, d, h, cur, sp); if (COUNT) c_tris += nt; }
+                    if (is_l) { const uint32_t nt = leaf_step(tris, stk, o, d, h, cur, sp); if (COUNT) vc.tris += nt; }
                 } else if (is_n) {
                     if (++steps > (1u << 22)) { atomicOr(&cold().ps.counters[kCntError], 2u); cur = PT_BVH_EMPTY; }
                     else {
-                        if (COUNT) { c_nodes++; if (lane == (uint32_t)(__ffsll((long long)m_n) - 1)) c_wave_iters++; }
+                        if (COUNT) { vc.nodes++; if (lane == (uint32_t)(__ffsll((long long)m_n) - 1)) vc.wave_iters++; }
                         node_step<L>(nodes, stk, rs, h.t, cur, sp);
                     }
                 }
@@ -1329,19 +1229,14 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT_POOL
         const uint32_t e2 = hh * 64u + lane, g = bx * E + e2;
         const uint32_t slot = s_slot[e2];
         const bool alive = slot != kInvalidSlot;
-        if (do_compact) wave_push(&ps.counters[cnt_ext_index(cnext, shard)], q_next, alive, slot);
+        if (do_compact) wave_push(&ps.counters[cnt_ext_index(hd.cnext, shard)], q_next, alive, slot);
         else if (g < n) q_next[g] = slot;
         n_left += (uint32_t)__popcll(__ballot(alive));
     }
-    if (COUNT) {
-        if (c_wave_iters) atomicAdd(reinterpret_cast<unsigned long long *>(ps.counters + kCntWaveNodeIters), c_wave_iters);
-        atomicAdd(reinterpret_cast<unsigned long long *>(ps.counters + kCntNodes), c_nodes);
-        atomicAdd(reinterpret_cast<unsigned long long *>(ps.counters + kCntTris), c_tris);
-        atomicAdd(reinterpret_cast<unsigned long long *>(ps.counters + kCntSph), c_sph);
-    }
+    if (COUNT) flush_visit_counters(ps, vc);
     if (lane == 0u) {
-        if (wave_rays) atomicAdd(traced_counter(ps, cnext, shard), (unsigned long long)wave_rays);
-        if (n_left) atomicAdd(&ps.counters[cnt_alive_index(cnext, shard)], n_left);
+        if (wave_rays) atomicAdd(traced_counter(ps, hd.cnext, shard), (unsigned long long)wave_rays);
+        if (n_left) atomicAdd(&ps.counters[cnt_alive_index(hd.cnext, shard)], n_left);
     }
 }
 
@@ -1411,9 +1306,9 @@ __global__ void __launch_bounds__(kBlock) k_reduce_streams(const float4 *__restr
 {
     const uint32_t slot = blockIdx.x * kBlock + threadIdx.x; // pixel slot
     if (slot >= slots_per_stream) return;
-    float4 t = acc[slot_of(slot, 0u, streams, slots_per_stream)];
+    float4 t = acc[slot_of(slot, 0u, streams)];
     for (uint32_t k = 1; k < streams; ++k) {
-        const float4 a = acc[slot_of(slot, k, streams, slots_per_stream)];
+        const float4 a = acc[slot_of(slot, k, streams)];
         t.x = t.x + a.x; t.y = t.y + a.y; t.z = t.z + a.z; t.w = t.w + a.w;
     }
     tiles[slot] = t;
