@@ -90,6 +90,19 @@ public unsafe class HipRenderer : IDisposable
         set { Ptrt.Check(Ptrt.pt_context_set_tuning(_ctx, &value), _ctx); }
     }
 
+    // Ray queries on the current scene (docs/SPEC.md §4.2). rays: 8 floats per ray {o.xyz, tmax, d.xyz, 0} (|d| = 1 for spheres);
+    // returns 4 floats per ray {t, prim id bits, u, v}, a miss = {+inf, 0xFFFFFFFF bits, 0, 0}. Host arrays: the library stages them.
+    public float[] TraceRays(float[] rays, bool occlusion = false)
+    {
+        if (rays.Length % 8 != 0) throw new ArgumentException("rays: 8 floats per ray");
+        var hits = new float[rays.Length / 2];
+        uint flags = (uint)PtTraceFlags.HostMemory | (occlusion ? (uint)PtTraceFlags.Occlusion : 0u);
+        PtStats st;
+        fixed (float* r = rays) fixed (float* h = hits)
+            Ptrt.Check(Ptrt.pt_trace_rays(_ctx, _scene, r, h, (ulong)(rays.Length / 8), flags, &st), _ctx);
+        return hits;
+    }
+
     internal void* Context => _ctx;
     internal void* Scene => _scene;
 

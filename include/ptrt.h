@@ -29,7 +29,8 @@ extern "C" {
 #endif
 
 /* 2: pt_tuning grew to 40 bytes (extend_kernel, readback); pt_comm_*, pt_framebuffer_read_srgb8, PT_FLAG_EXTEND_POOL, pt_bvh_info.stack_need and
- * the BVH2 default for small scenes had arrived under version 1. Hosts compare pt_abi_version() with the header they were built against. */
+ * the BVH2 default for small scenes had arrived under version 1. pt_trace_rays and PT_TRACE_* arrived later under version 2 (additions
+ * only: no struct or existing signature changed). Hosts compare pt_abi_version() with the header they were built against. */
 #define PTRT_ABI_VERSION 2
 
 typedef int32_t pt_status;
@@ -201,6 +202,26 @@ pt_status pt_scene_bvh_read(const pt_scene *s, void *nodes, uint64_t node_bytes,
 
 /* ---- frame: replaces Renderer.ComputeFrame (Renderer.cs:1006-1040) + the fence wait (Renderer.cs:970-972) */
 pt_status pt_render(pt_context *ctx, const pt_scene *scene, const pt_render_params *params, pt_stats *stats);
+
+/* ---- ray queries (docs/SPEC.md §4.2): the closest-hit traversal of pt_render on caller rays, without a path — what a host uses
+ *      for picking, visibility tests or baking. */
+/* pt_trace_rays flags */
+enum {
+    PT_TRACE_OCCLUSION = 1u,    /* any hit with t <= tmax ends the ray (shadow / visibility query); default: closest hit */
+    PT_TRACE_COUNT_VISITS = 2u, /* closest-hit only: count node visits / triangle / sphere tests into stats (slower kernel) */
+    PT_TRACE_HOST_MEMORY = 4u   /* rays / hits are host pointers; the library stages them. Default: device pointers on ctx's device */
+};
+/* Trace n_rays caller rays against a committed scene. Synchronous on the context's stream, like pt_render.
+ * rays: n_rays records of 32 B  {o.x, o.y, o.z, tmax, d.x, d.y, d.z, 0}        (f32, 16-B aligned; 4-B with PT_TRACE_HOST_MEMORY)
+ * hits: n_rays records of 16 B  {t, prim_id (u32 bits), u, v}                  (f32, 16-B aligned; 4-B with PT_TRACE_HOST_MEMORY)
+ * Closest hit: the smallest (t, prim_id) with t <= tmax; a miss is {+inf, 0xFFFFFFFF, 0, 0}. prim_id counts triangles 0..NT-1, then
+ * spheres NT + j; (u, v) are a triangle hit's barycentrics, 0 for spheres. tmax = +inf: unbounded; tmax <= 0 or NaN: a miss. Spheres
+ * need |d| = 1 (the library does not normalise); a triangle's t is in units of |d|. Device arrays must lie on ctx's device inside one
+ * allocation. stats (may be NULL): rays = n_rays, gpu_ms (the query kernels, staging copies excluded), and with PT_TRACE_COUNT_VISITS
+ * node_visits / tri_tests / sphere_tests. PT_TRACE_OCCLUSION | PT_TRACE_COUNT_VISITS is PT_ERR_INVALID_ARGUMENT. A query touches no
+ * state of pt_render (accumulated sums, framebuffer, queues). */
+pt_status pt_trace_rays(pt_context *ctx, const pt_scene *scene, const void *rays, void *hits, uint64_t n_rays,
+                        uint32_t flags, pt_stats *stats);
 
 /* ---- results: the reference never reads its image back (it is sampled by the display pass,
  *      Renderer.cs:1042-1121); these replace that consumer. float4 linear radiance, row-major. */

@@ -166,6 +166,12 @@ struct pt_context {
     uint32_t fb_w = 0, fb_h = 0;
     uint32_t n_slots = 0; // slots of the last path-traced frame (acc layout)
     bool fb_valid = false;
+    // pt_trace_rays: its own counter block, overflow stack, staging buffers (PT_TRACE_HOST_MEMORY) and events, so that a query touches
+    // nothing a frame reads (the frame-start template, the partial sums, the queues and their counters)
+    DevBuf<uint32_t> trace_cnt;
+    DevBuf<int32_t> trace_ovf;
+    DevBuf<float4> trace_rays, trace_hits;
+    hipEvent_t ev_trace[2] = {};
 };
 
 struct pt_scene {
@@ -313,6 +319,7 @@ pt_status pt_context_create(const pt_device_desc *desc, pt_context **out)
     for (uint32_t g = 0; g < kMaxGroups; ++g)
         for (uint32_t i = 0; ok && i < kLag; ++i) ok = hipEventCreateWithFlags(&c->ev_lag[g][i], hipEventDisableTiming) == hipSuccess;
     for (uint32_t i = 0; ok && i < 4; ++i) ok = hipEventCreate(&c->ev_probe[i]) == hipSuccess;
+    for (uint32_t i = 0; ok && i < 2; ++i) ok = hipEventCreate(&c->ev_trace[i]) == hipSuccess;
     ok = ok && c->counters.ensure(kCntTotalWords) == hipSuccess;
     if (!ok) { pt_context_destroy(c); return fail(nullptr, PT_ERR_HIP, "context resource creation failed"); }
     *out = c;
@@ -350,6 +357,7 @@ void pt_context_destroy(pt_context *c)
     c->ray_o.release(); c->ray_d.release(); c->thr.release(); c->acc.release(); c->tiles.release(); c->fb.release(); c->hit.release();
     c->sd.release(); c->q_ext0.release(); c->q_ext1.release(); c->counters.release(); c->fb8.release(); c->stack_ovf.release();
     c->q_init.release(); c->cnt_init.release(); c->q_metal.release(); c->q_dielectric.release();
+    c->trace_cnt.release(); c->trace_ovf.release(); c->trace_rays.release(); c->trace_hits.release();
     if (c->h_counts) (void)hipHostFree(c->h_counts);
     if (c->h_ring) (void)hipHostFree(c->h_ring);
     for (auto &row : c->ev_lag) for (auto &e : row) if (e) (void)hipEventDestroy(e);
@@ -357,6 +365,7 @@ void pt_context_destroy(pt_context *c)
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     for (auto &gs : c->group_stream) if (gs) (void)hipStreamDestroy(gs);
     for (auto &e : c->ev_probe) if (e) (void)hipEventDestroy(e);
+    for (auto &e : c->ev_trace) if (e) (void)hipEventDestroy(e);
     if (c->ev_start) (void)hipEventDestroy(c->ev_start);
     if (c->ev_stop) (void)hipEventDestroy(c->ev_stop);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
@@ -941,6 +950,88 @@ pt_status pt_render(pt_context *c, const pt_scene *s, const pt_render_params *p,
         drain(c);
         c->acc_spp = 0; c->fb_valid = false;
     }
+    return st;
+}
+
+// ------------------------------------------------------------------------------------------------ ray queries (docs/SPEC.md §4.2)
+
+namespace {
+// A caller's device array must lie inside one allocation on the context's device: the kernel reads / writes `bytes` from `p` unchecked.
+pt_status check_device_array(pt_context *c, const void *p, uint64_t bytes, const char *what)
+{
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess || (at.type != hipMemoryTypeDevice && !at.isManaged) || at.device != c->device) {
+        (void)hipGetLastError();
+        return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_trace_rays: %s is not device memory of the context's device %d (host arrays: PT_TRACE_HOST_MEMORY)", what, c->device);
+    }
+    hipDeviceptr_t base = nullptr; size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return PT_OK; } // (range unknown: trust the caller)
+    if ((const char *)p + bytes > (const char *)base + size)
+        return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_trace_rays: %s holds %llu bytes from the pointer on, the batch needs %llu", what,
+                    (unsigned long long)((const char *)base + size - (const char *)p), (unsigned long long)bytes);
+    return PT_OK;
+}
+} // namespace
+
+static pt_status trace_rays(pt_context *c, const pt_scene *s, const void *rays, void *hits, uint64_t n_rays, uint32_t flags, pt_stats *stats)
+{
+    constexpr uint32_t known = PT_TRACE_OCCLUSION | PT_TRACE_COUNT_VISITS | PT_TRACE_HOST_MEMORY;
+    if (flags & ~known) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_trace_rays: unknown flag bits 0x%x", flags & ~known);
+    const bool occlusion = (flags & PT_TRACE_OCCLUSION) != 0, count = (flags & PT_TRACE_COUNT_VISITS) != 0, host = (flags & PT_TRACE_HOST_MEMORY) != 0;
+    if (occlusion && count) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_trace_rays: PT_TRACE_COUNT_VISITS counts closest-hit queries only (occlusion promises no visit order)");
+    if (!c || !s || !rays || !hits) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_trace_rays: NULL argument");
+    const uintptr_t align = host ? 3u : 15u; // the kernel loads and stores 16-byte rows; staged host arrays only need float alignment
+    if (((uintptr_t)rays & align) || ((uintptr_t)hits & align))
+        return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_trace_rays: rays and hits must be %u-byte aligned", (unsigned)align + 1u);
+    if (s->ctx != c) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_trace_rays: scene belongs to another context");
+    if (!s->committed) return fail(c, PT_ERR_NOT_COMMITTED, "scene not committed");
+    if (n_rays >> 40) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_trace_rays: n_rays %llu is not a batch size", (unsigned long long)n_rays);
+    pt_stats out; std::memset(&out, 0, sizeof out);
+    out.rays = n_rays;
+    if (n_rays == 0) { if (stats) *stats = out; return PT_OK; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    pt_status st;
+    if (!host && ((st = check_device_array(c, rays, n_rays * 32u, "rays")) != PT_OK || (st = check_device_array(c, hits, n_rays * 16u, "hits")) != PT_OK)) return st;
+    hipStream_t q = c->stream;
+    const uint64_t chunk = 1ull << 31; // rays per launch (k_trace indexes with 32 bits)
+    const uint32_t blocks = trace_blocks((uint32_t)std::min<uint64_t>(n_rays, chunk)), lanes = blocks * kExtBlock;
+    PathState ps{};
+    ps.shard_cap = (lanes + kShards - 1u) / kShards; // one overflow column per lane of the grid, reused by its every ray
+    ps.stack_ovf_entries = s->bvh.stack_need > kStackLds ? s->bvh.stack_need - kStackLds : 0u;
+    if (ps.stack_ovf_entries) HIP_TRY(c, c->trace_ovf.ensure((size_t)ps.stack_ovf_entries * kShards * ps.shard_cap));
+    ps.stack_ovf = c->trace_ovf.p;
+    HIP_TRY(c, c->trace_cnt.ensure(kCntTotalWords)); // the kernels use the global words only: error flag and visit counters
+    ps.counters = c->trace_cnt.p;
+    const float4 *d_rays = (const float4 *)rays;
+    float4 *d_hits = (float4 *)hits;
+    if (host) { // staged through the context's own buffers
+        HIP_TRY(c, c->trace_rays.ensure((size_t)n_rays * 2u)); HIP_TRY(c, c->trace_hits.ensure((size_t)n_rays));
+        HIP_TRY(c, hipMemcpyAsync(c->trace_rays.p, rays, n_rays * 32u, hipMemcpyHostToDevice, q));
+        d_rays = c->trace_rays.p; d_hits = c->trace_hits.p;
+    }
+    constexpr uint32_t words = kCntTotalWords - kCntGlobals;
+    HIP_TRY(c, hipMemsetAsync(c->trace_cnt.p + kCntGlobals, 0, sizeof(uint32_t) * words, q));
+    HIP_TRY(c, hipEventRecord(c->ev_trace[0], q));
+    for (uint64_t first = 0; first < n_rays; first += chunk)
+        HIP_TRY(c, launch_trace(q, s->ds, ps, d_rays + 2u * first, d_hits + first, (uint32_t)std::min(chunk, n_rays - first), occlusion, count));
+    HIP_TRY(c, hipEventRecord(c->ev_trace[1], q));
+    if (host) HIP_TRY(c, hipMemcpyAsync(hits, d_hits, n_rays * 16u, hipMemcpyDeviceToHost, q));
+    uint32_t hc[words];
+    HIP_TRY(c, hipMemcpyAsync(hc, c->trace_cnt.p + kCntGlobals, sizeof hc, hipMemcpyDeviceToHost, q));
+    HIP_TRY(c, hipStreamSynchronize(q));
+    if (hc[kCntError - kCntGlobals])
+        return fail(c, PT_ERR_INTERNAL, "pt_trace_rays: device error flag 0x%x (1 = traversal stack overflow, 2 = step limit)", hc[kCntError - kCntGlobals]);
+    auto u64_at = [&](uint32_t w) { return (uint64_t)hc[w - kCntGlobals] | ((uint64_t)hc[w - kCntGlobals + 1] << 32); };
+    float ms = 0.f; HIP_TRY(c, hipEventElapsedTime(&ms, c->ev_trace[0], c->ev_trace[1])); out.gpu_ms = ms;
+    if (count) { out.node_visits = u64_at(kCntNodes); out.tri_tests = u64_at(kCntTris); out.sphere_tests = u64_at(kCntSph); }
+    if (stats) *stats = out;
+    return PT_OK;
+}
+
+pt_status pt_trace_rays(pt_context *c, const pt_scene *s, const void *rays, void *hits, uint64_t n_rays, uint32_t flags, pt_stats *stats)
+{
+    const pt_status st = trace_rays(c, s, rays, hits, n_rays, flags, stats);
+    if (st != PT_OK && c) { (void)hipSetDevice(c->device); drain(c); } // nothing of a failed query (e.g. a copy into `hits`) runs on after the call
     return st;
 }
 

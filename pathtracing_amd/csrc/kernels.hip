@@ -11,6 +11,8 @@
 //   k_shade<MODE>      : the split pipeline's second kernel (PT_FLAG_SPLIT_KERNELS / PT_FLAG_BUCKET_SPECULAR): walks
 //                        the queue k_extend<.., SHADE_NONE> just walked; QUEUE/INLINE shade in queue order, BUCKETS
 //                        shades the metal / dielectric hits that QUEUE deferred to per-kind bucket queues
+//   k_trace<L,MODE>    : pt_trace_rays: caller rays -> closest hit (or any hit: occlusion), one ray per lane on k_extend's
+//                        traversal core, no path state
 //   k_reduce_streams   : fixed-order sum of a pixel's stream partials
 //   k_assemble         : tile-major slots (of 1..R ranks) -> row-major float4 + RGBA8 frame
 //
@@ -1241,6 +1243,89 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT_POOL
 }
 
 // ------------------------------------------------------------------------------------------------
+// k_trace<L, MODE>: pt_trace_rays (docs/SPEC.md §4.2). Caller rays {o.xyz | tmax, d.xyz | 0} -> hit records {t, prim id, u, v}, one
+// ray per lane on k_extend's while-while traversal (sphere list, root visit from one scalar load, node_step / leaf_step phases), the
+// closest hit started from (tmax, MISS) instead of (+inf, MISS). Grid-stride: a grid of at most kTraceBlocks one-wave workgroups walks
+// the batch and every lane keeps its overflow-stack column (blockIdx.x * 64 + lane) for all of its rays, so the overflow area is
+// bounded by the grid, not by the batch.
+//   TRACE_CLOSEST   : closest hit; a triangle's u, v are recomputed from the winning record after traversal (tri_uv), so tri_test
+//                     carries nothing more through the loop
+//   TRACE_COUNT     : the same, counting node visits / triangle / sphere tests (SPEC §4.1) into the trace's own counter block
+//   TRACE_OCCLUSION : any hit with t <= tmax ends the ray: a sphere hit skips the traversal, the first accepted triangle ends the leaf
+//                     and the node loop of its lane (no visit order is promised, so there is no counting variant)
+// The kernel arguments begin with an ExtArgs of which only ps.counters / stack_ovf / stack_ovf_entries / shard_cap are set: cold()
+// and the stack helpers reach the overflow area and the error word exactly as they do from the extend kernels.
+enum TraceMode { TRACE_CLOSEST = 0, TRACE_COUNT = 1, TRACE_OCCLUSION = 2 };
+struct TraceArgs : ExtArgs {
+    const float4 *rays; // two rows per ray
+    float4 *hits;       // one row per ray
+    uint32_t n;
+};
+
+// Occlusion leaf: its triangles in array order until one is accepted, which ends the ray (cur = PT_BVH_EMPTY); else the next stack entry.
+PT_DEV void leaf_step_any(const float4 *__restrict__ tris, const StackCtx &k, V3 o, V3 d, Hit &h, int32_t &cur, uint32_t &sp)
+{
+    const uint32_t enc = (uint32_t)~cur;
+    uint32_t first = enc >> 3, more = enc & 7u;
+    for (;;) {
+        const float4 *base = tris + (size_t)first * 4;
+        tri_test(base[0], base[1], base[2], first, o, d, h);
+        if (h.id != PT_MISS) { cur = PT_BVH_EMPTY; return; }
+        if (more == 0u) break;
+        ++first; --more;
+    }
+    cur = pop_after_leaf(k, sp);
+}
+
+template <int L, int MODE>
+__global__ void __launch_bounds__(kExtBlock) __attribute__((amdgpu_waves_per_eu(PT_EXT_WAVES(L, SHADE_NONE), PT_EXT_WAVES(L, SHADE_NONE))))
+k_trace(TraceArgs a)
+{
+    constexpr bool COUNT = MODE == TRACE_COUNT, ANY = MODE == TRACE_OCCLUSION;
+    const float4 *__restrict__ nodes = a.sc.nodes, *__restrict__ tris = a.sc.tris, *__restrict__ spheres = a.sc.spheres;
+    const uint32_t n_spheres = a.sc.n_spheres, n_tris = a.sc.n_tris, n_nodes = a.sc.n_nodes, n = a.n;
+    const float4 *__restrict__ rays = a.rays;
+    float4 *__restrict__ hits = a.hits;
+    __shared__ int32_t s_stack[kStackLds * kExtBlock];
+    const uint32_t tid = threadIdx.x;
+    const StackCtx stk{ s_stack, kExtBlock, tid, blockIdx.x * kExtBlock + tid };
+    VisitCounts vc;
+    for (uint32_t base = blockIdx.x * kExtBlock; base < n; base += gridDim.x * kExtBlock) { // wave-uniform; n <= 2^31 (api.cpp): no wrap
+        const uint32_t i = base + tid;
+        if (i >= n) continue;
+        const float4 ro = rays[2u * (size_t)i], rd = rays[2u * (size_t)i + 1u];
+        const V3 o = xyz(ro), d = xyz(rd);
+        Hit h{ ro.w, PT_MISS, PT_MISS };
+        if (ro.w > 0.0f) { // tmax <= 0 or NaN: nothing can be accepted (docs/SPEC.md §4.2)
+            { const uint32_t ns = spheres_test(spheres, n_spheres, n_tris, o, d, h); if (COUNT) vc.sph += ns; }
+            const RaySetup rs = ray_setup(o, d);
+            int32_t cur = PT_BVH_EMPTY;
+            uint32_t sp = 0, steps = 0;
+            if (n_nodes && !(ANY && h.id != PT_MISS)) { // root visit: one scalar load of node 0's rows, as in k_extend
+                ++steps;
+                if (COUNT) vc.nodes++;
+                const uniform_f4 root = as_uniform(nodes);
+                node_visit_rows<L>(nodes, uniform_load(root, 0), uniform_load(root, 1), uniform_load(root, 2), uniform_load(root, 3), stk, rs, h.t, cur, sp);
+            }
+            for (;;) { // while-while, as in k_extend
+                while ((uint32_t)cur < (uint32_t)PT_BVH_EMPTY) {
+                    if (++steps > (1u << 22)) { atomicOr(&cold().ps.counters[kCntError], 2u); cur = PT_BVH_EMPTY; break; }
+                    if (COUNT) vc.nodes++;
+                    node_step<L>(nodes, stk, rs, h.t, cur, sp);
+                }
+                if (cur == PT_BVH_EMPTY) break;
+                if (ANY) leaf_step_any(tris, stk, o, d, h, cur, sp);
+                else { const uint32_t nt = leaf_step(tris, stk, o, d, h, cur, sp); if (COUNT) vc.tris += nt; }
+            }
+        }
+        float u = 0.0f, v = 0.0f;
+        if (!ANY && h.ref < n_tris) { const float4 *t = tris + (size_t)h.ref * 4; tri_uv(t[0], t[1], t[2], o, d, u, v); }
+        hits[i] = h.id == PT_MISS ? make_float4(__builtin_inff(), __uint_as_float(PT_MISS), 0.0f, 0.0f) : make_float4(h.t, __uint_as_float(h.id), u, v);
+    }
+    if (COUNT) flush_visit_counters(cold().ps, vc);
+}
+
+// ------------------------------------------------------------------------------------------------
 // k_shade<SHADE_QUEUE>   : walks the extend queue of this iteration in the SAME order k_extend did, so ray/throughput/hit
 //                          reads are the coalesced, L2-warm lines k_extend just touched. Misses and Lambert hits are shaded
 //                          in place; specular kinds (metal, dielectric) are deferred to per-kind bucket queues.
@@ -1382,6 +1467,33 @@ hipError_t launch_extend(hipStream_t s, const DeviceScene &sc, const PathState &
     case PT_BVH_WIDTH_4Q: count ? extend_lc<PT_BVH_WIDTH_4Q, true>(s, grid, a, kernel, fuse) : extend_lc<PT_BVH_WIDTH_4Q, false>(s, grid, a, kernel, fuse); break;
     case PT_BVH_WIDTH_8Q: count ? extend_lc<PT_BVH_WIDTH_8Q, true>(s, grid, a, kernel, fuse) : extend_lc<PT_BVH_WIDTH_8Q, false>(s, grid, a, kernel, fuse); break;
     case PT_BVH_WIDTH_8O: count ? extend_lc<PT_BVH_WIDTH_8O, true>(s, grid, a, kernel, fuse) : extend_lc<PT_BVH_WIDTH_8O, false>(s, grid, a, kernel, fuse); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+template <int L>
+static void trace_l(hipStream_t s, dim3 grid, const TraceArgs &a, int mode)
+{
+    if (mode == TRACE_OCCLUSION) hipLaunchKernelGGL((k_trace<L, TRACE_OCCLUSION>), grid, dim3(kExtBlock), 0, s, a);
+    else if (mode == TRACE_COUNT) hipLaunchKernelGGL((k_trace<L, TRACE_COUNT>), grid, dim3(kExtBlock), 0, s, a);
+    else hipLaunchKernelGGL((k_trace<L, TRACE_CLOSEST>), grid, dim3(kExtBlock), 0, s, a);
+}
+
+uint32_t trace_blocks(uint32_t n) { return std::max(1u, std::min(kTraceBlocks, (n + kExtBlock - 1u) / kExtBlock)); }
+
+hipError_t launch_trace(hipStream_t s, const DeviceScene &sc, const PathState &ps, const float4 *rays, float4 *hits, uint32_t n, bool occlusion, bool count)
+{
+    TraceArgs a{};
+    a.sc = sc; a.ps = ps; a.rays = rays; a.hits = hits; a.n = n;
+    const dim3 grid(trace_blocks(n));
+    const int mode = occlusion ? TRACE_OCCLUSION : count ? TRACE_COUNT : TRACE_CLOSEST;
+    switch (sc.bvh_width) {
+    case PT_BVH_WIDTH_2: trace_l<PT_BVH_WIDTH_2>(s, grid, a, mode); break;
+    case PT_BVH_WIDTH_4: trace_l<PT_BVH_WIDTH_4>(s, grid, a, mode); break;
+    case PT_BVH_WIDTH_4Q: trace_l<PT_BVH_WIDTH_4Q>(s, grid, a, mode); break;
+    case PT_BVH_WIDTH_8Q: trace_l<PT_BVH_WIDTH_8Q>(s, grid, a, mode); break;
+    case PT_BVH_WIDTH_8O: trace_l<PT_BVH_WIDTH_8O>(s, grid, a, mode); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -95,6 +95,17 @@ PT_DEV void tri_test(float4 r0, float4 r1, float4 r2, uint32_t blob_index, V3 o,
               && (t < h.t || (t == h.t && id < h.id));
     if (ok) { h.t = t; h.id = id; h.ref = blob_index; }
 }
+// The barycentrics of an accepted triangle, recomputed from its record with tri_test's own expressions (the same bits tri_test
+// compared): the ray queries report them without carrying them through the traversal.
+PT_DEV void tri_uv(float4 r0, float4 r1, float4 r2, V3 o, V3 d, float &u, float &v)
+{
+    const V3 v0 = xyz(r0), e1 = xyz(r1), e2 = xyz(r2);
+    const V3 p = cross(d, e2);
+    const float inv_det = 1.0f / dot(e1, p);
+    const V3 tv = o - v0;
+    u = dot(tv, p) * inv_det;
+    v = dot(d, cross(tv, e1)) * inv_det;
+}
 
 PT_DEV void sphere_test(float4 s, uint32_t id, V3 o, V3 d, Hit &h)
 {

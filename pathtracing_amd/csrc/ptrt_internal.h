@@ -27,6 +27,9 @@ constexpr uint32_t kShardGroupShift = PT_SHARD_GROUP_SHIFT;
 constexpr uint32_t kStackLds = PT_STACK_LDS;       // traversal-stack entries kept in LDS per lane
 constexpr uint32_t kExtBlock = PT_EXT_BLOCK;       // workgroup size of k_extend (a wave retires on its own when it is 64)
 constexpr uint32_t kMaxSpheres = 64;
+// Largest grid of k_trace (pt_trace_rays), in one-wave workgroups: 2^20 lanes = two rounds of the 8192 waves an MI355X holds at 8 waves
+// per SIMD. Every lane keeps one overflow-stack column for the whole batch, so this bounds the overflow area of a query.
+constexpr uint32_t kTraceBlocks = 16384;
 #ifndef PT_POOL
 #define PT_POOL 128
 #endif
@@ -158,6 +161,11 @@ hipError_t launch_extend(hipStream_t s, const DeviceScene &sc, const PathState &
 //          0 = every lane writes its own position of the next queue (slot or kInvalidSlot): no returning atomics, and the
 //              queue keeps its slot order, which is what keeps the slot-indexed path state coalesced (modes 0 and 2 only)
 hipError_t launch_shade(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp, uint32_t it, uint32_t shard_bound, int mode, bool compact);
+// pt_trace_rays: n <= 2^31 caller rays (2 float4 rows each) -> hit records (1 float4 row each), on a grid of trace_blocks(n) workgroups of
+// kExtBlock lanes. ps: only counters (error word and visit counters at kCntGlobals), stack_ovf, stack_ovf_entries and shard_cap are read;
+// shard_cap * kShards must cover trace_blocks(n) * kExtBlock lanes. occlusion and count are exclusive.
+uint32_t trace_blocks(uint32_t n);
+hipError_t launch_trace(hipStream_t s, const DeviceScene &sc, const PathState &ps, const float4 *rays, float4 *hits, uint32_t n, bool occlusion, bool count);
 hipError_t launch_reduce_streams(hipStream_t s, const float4 *acc, float4 *tiles, uint32_t slots_per_stream, uint32_t streams);
 hipError_t launch_assemble(hipStream_t s, const float4 *gathered, uint32_t nranks, uint32_t slots_per_rank,
                            uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t n_tiles, float inv_spp,

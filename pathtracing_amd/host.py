@@ -187,6 +187,53 @@ class Renderer:
         _check(N.lib.pt_scene_bvh_read(self._scene, _ptr(nodes), info.node_bytes, _ptr(tris), info.tri_bytes), self._ctx)
         return nodes[: int(info.node_bytes)], tris[: int(info.tri_bytes)]
 
+    def TraceRays(self, rays, tmax=None, occlusion=False, count_visits=False):
+        """Ray queries on the current scene (include/ptrt.h pt_trace_rays, docs/SPEC.md §4.2); returns (hits, pt_stats).
+
+        rays: an (N, 8) float32 array of {o.xyz, tmax, d.xyz, 0} records, or a pair (origins, directions) of (N, 3) arrays (|d| = 1
+        for spheres). tmax: None keeps the records' own column (+inf for a pair), else a scalar or (N,) array that replaces it.
+        torch tensors on the renderer's device are passed as device pointers (an (N, 8) contiguous float32 tensor without tmax is
+        used in place); numpy arrays take the staged host path. hits: (N, 4) float32 of the same kind, {t, prim id bits, u, v}; a miss
+        is {+inf, 0xFFFFFFFF, 0, 0} — `hits[:, 1].view(np.uint32)` (torch: `.view(torch.int32)`) gives the ids."""
+        pair = isinstance(rays, (tuple, list))
+        first = rays[0] if pair else rays
+        flags = (N.PT_TRACE_OCCLUSION if occlusion else 0) | (N.PT_TRACE_COUNT_VISITS if count_visits else 0)
+        stats = N.pt_stats()
+        if N.torch is not None and isinstance(first, N.torch.Tensor):
+            torch = N.torch
+            dev = first.device
+            if dev.type != "cuda" or (dev.index if dev.index is not None else torch.cuda.current_device()) != self._device:
+                raise ValueError(f"rays are on {dev}, the renderer on cuda:{self._device}")
+            if pair:
+                o, d = (torch.as_tensor(a, dtype=torch.float32, device=dev).reshape(-1, 3) for a in rays)
+                rec = torch.cat([o, torch.full_like(o[:, :1], float("inf")), d, torch.zeros_like(o[:, :1])], dim=1)
+            else:
+                rec = rays if rays.dtype == torch.float32 and rays.is_contiguous() and rays.dim() == 2 and rays.shape[1] == 8 else \
+                    rays.to(torch.float32).reshape(-1, 8).contiguous()
+            if tmax is not None:
+                rec = rec if pair else rec.clone()  # never write into the caller's tensor
+                rec[:, 3] = torch.as_tensor(tmax, dtype=torch.float32, device=dev)
+            hits = torch.empty((rec.shape[0], 4), dtype=torch.float32, device=dev)
+            if rec.shape[0] == 0:  # (an empty tensor has no storage to point at)
+                return hits, stats
+            torch.cuda.current_stream(dev).synchronize()  # the library runs on its own stream: the records must be complete
+            _check(N.lib.pt_trace_rays(self._ctx, self._scene, C.c_void_p(rec.data_ptr()), C.c_void_p(hits.data_ptr()),
+                                       rec.shape[0], flags, C.byref(stats)), self._ctx)
+            return hits, stats
+        if pair:
+            o, d = (np.asarray(a, np.float32).reshape(-1, 3) for a in rays)
+            rec = np.zeros((len(o), 8), np.float32)
+            rec[:, 0:3], rec[:, 3], rec[:, 4:7] = o, np.inf, d
+        else:
+            rec = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        if tmax is not None:
+            rec = rec if pair else rec.copy()  # never write into the caller's array
+            rec[:, 3] = tmax
+        hits = np.empty((len(rec), 4), np.float32)
+        _check(N.lib.pt_trace_rays(self._ctx, self._scene, _ptr(rec), _ptr(hits), len(rec), flags | N.PT_TRACE_HOST_MEMORY,
+                                   C.byref(stats)), self._ctx)
+        return hits, stats
+
     # Renderer.Update (Renderer.cs:86-89) is empty in the reference
     def Update(self, deltaTime):
         pass
