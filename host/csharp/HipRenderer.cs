@@ -103,6 +103,27 @@ public unsafe class HipRenderer : IDisposable
         return hits;
     }
 
+    // Move the current scene's geometry without a new commit (docs/SPEC.md §4.3), e.g. from an application's Update(deltaTime):
+    // verts = 9 floats per triangle (the committed count and order), spheres = 4 floats per sphere {centre, radius}; either may be null.
+    // The tree keeps its topology, the picture is exactly a fresh commit's; pt_bvh_info.sah_cost says when a new commit would pay again.
+    // Returns the triangle update's stats (gpu_ms).
+    public PtStats UpdateGeometry(float[] verts, float[] spheres = null)
+    {
+        PtStats st = default;
+        if (verts != null)
+        {
+            if (verts.Length % 9 != 0) throw new ArgumentException("verts: 9 floats per triangle");
+            fixed (float* v = verts)
+                Ptrt.Check(Ptrt.pt_scene_update_triangles(_scene, v, (ulong)(verts.Length / 9), (uint)PtUpdateFlags.HostMemory, &st), _ctx);
+        }
+        if (spheres != null)
+        {
+            if (spheres.Length % 4 != 0) throw new ArgumentException("spheres: 4 floats per sphere");
+            fixed (float* p = spheres) Ptrt.Check(Ptrt.pt_scene_update_spheres(_scene, p, (ulong)(spheres.Length / 4)), _ctx);
+        }
+        return st;
+    }
+
     internal void* Context => _ctx;
     internal void* Scene => _scene;
 

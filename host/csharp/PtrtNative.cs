@@ -14,6 +14,7 @@ public enum PtSceneKind : uint { Cornell = 0, CornellGlass = 1, TriangleSoup = 2
 [Flags] public enum PtFlags : uint { ProfileKernels = 1, CountVisits = 2, ExtendPacked = 4, ExtendSimple = 8, Accumulate = 16, BucketSpecular = 32, SplitKernels = 64, ExtendPool = 128 }
 [Flags] public enum PtCommFlags : uint { ForceRccl = 1, CopyExchange = 2 }
 [Flags] public enum PtTraceFlags : uint { Occlusion = 1, CountVisits = 2, HostMemory = 4 }
+[Flags] public enum PtUpdateFlags : uint { HostMemory = 1 }
 public enum PtBvhWidth : uint { Default = 0, W2 = 2, W4 = 4, W4Q = 68, W8Q = 72, W8O = 73, BuildLbvh = 0x100 }
 
 [StructLayout(LayoutKind.Sequential)] public unsafe struct PtDeviceDesc { public int device_ordinal; public void* stream; public uint flags; public uint reserved; }
@@ -60,6 +61,8 @@ public static unsafe class Ptrt
     [DllImport(Lib)] public static extern PtStatus pt_scene_bvh_read(void* s, void* nodes, ulong node_bytes, void* tris48, ulong tri_bytes);
     [DllImport(Lib)] public static extern PtStatus pt_render(void* ctx, void* scene, PtRenderParams* p, PtStats* stats);
     [DllImport(Lib)] public static extern PtStatus pt_trace_rays(void* ctx, void* scene, void* rays, void* hits, ulong n_rays, uint flags, PtStats* stats);
+    [DllImport(Lib)] public static extern PtStatus pt_scene_update_triangles(void* s, void* verts9, ulong count, uint flags, PtStats* stats);
+    [DllImport(Lib)] public static extern PtStatus pt_scene_update_spheres(void* s, float* cxyzr, ulong count);
     [DllImport(Lib)] public static extern PtStatus pt_framebuffer_read(void* ctx, float* rgba, ulong n_floats);
     [DllImport(Lib)] public static extern PtStatus pt_framebuffer_read_rgba8(void* ctx, byte* rgba8, ulong n_bytes);
     [DllImport(Lib)] public static extern PtStatus pt_framebuffer_read_srgb8(void* ctx, byte* rgba8, ulong n_bytes);

@@ -29,8 +29,8 @@ extern "C" {
 #endif
 
 /* 2: pt_tuning grew to 40 bytes (extend_kernel, readback); pt_comm_*, pt_framebuffer_read_srgb8, PT_FLAG_EXTEND_POOL, pt_bvh_info.stack_need and
- * the BVH2 default for small scenes had arrived under version 1. pt_trace_rays and PT_TRACE_* arrived later under version 2 (additions
- * only: no struct or existing signature changed). Hosts compare pt_abi_version() with the header they were built against. */
+ * the BVH2 default for small scenes had arrived under version 1. pt_trace_rays and PT_TRACE_* arrived later under version 2, and after them
+ * pt_scene_update_triangles / pt_scene_update_spheres and PT_UPDATE_HOST_MEMORY (additions only: no struct or existing signature changed). Hosts compare pt_abi_version() with the header they were built against. */
 #define PTRT_ABI_VERSION 2
 
 typedef int32_t pt_status;
@@ -222,6 +222,29 @@ enum {
  * state of pt_render (accumulated sums, framebuffer, queues). */
 pt_status pt_trace_rays(pt_context *ctx, const pt_scene *scene, const void *rays, void *hits, uint64_t n_rays,
                         uint32_t flags, pt_stats *stats);
+
+/* ---- geometry updates (docs/SPEC.md §4.3): move a committed scene's triangles or spheres without a new commit — what a host's
+ *      per-frame Update hook (Renderer.Update, Renderer.cs:86-89) uses to animate. The BVH keeps its topology and leaf assignment;
+ *      the triangle records and every box are recomputed on the GPU from the new vertices, so the scene renders and traces exactly as
+ *      a fresh commit of these vertices would. Traversal speed degrades as motion stretches the old tree: pt_bvh_info.sah_cost is
+ *      recomputed by every update and is the caller's signal to commit again. n_nodes, max_depth, stack_need and the layout stay;
+ *      build_ms keeps describing the commit. pt_scene_bvh_read returns the refitted blob. A later pt_scene_commit builds from the
+ *      updated geometry. An update leaves the context's accumulated sums alone: a PT_FLAG_ACCUMULATE frame after it continues the old
+ *      sums (the mean then mixes both geometries). Both calls are synchronous on the context's stream; a refused call leaves the scene
+ *      as it was. Checked in this order: flags, committed (PT_ERR_NOT_COMMITTED), count (must equal the committed count), NULL,
+ *      the values (host arrays), then detached scenes and scenes committed under the PTRT_UNIFIED experiment (PT_ERR_UNSUPPORTED). */
+/* pt_scene_update_triangles flags */
+enum {
+    PT_UPDATE_HOST_MEMORY = 1u  /* verts9 is a host pointer (staged by the library); default: a device pointer on the scene's context's device */
+};
+/* New positions for the committed triangles: 9 floats each, same count and order as pt_scene_set_triangles; the materials stay.
+ * Non-finite coordinates are PT_ERR_INVALID_ARGUMENT (a device array is checked by a reduction before anything is written). A device
+ * array must lie inside one allocation on the context's device, 4-byte aligned. stats (may be NULL): gpu_ms of the update's kernels
+ * (staging copies excluded), everything else 0. */
+pt_status pt_scene_update_triangles(pt_scene *s, const void *verts9, uint64_t count, uint32_t flags, pt_stats *stats);
+/* New centres and radii for the committed spheres (host memory, 4 floats each, same count); materials stay. Bad spheres as
+ * pt_scene_set_spheres defines them are PT_ERR_INVALID_ARGUMENT. */
+pt_status pt_scene_update_spheres(pt_scene *s, const float *cxyzr, uint64_t count);
 
 /* ---- results: the reference never reads its image back (it is sampled by the display pass,
  *      Renderer.cs:1042-1121); these replace that consumer. float4 linear radiance, row-major. */

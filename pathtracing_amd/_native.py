@@ -40,6 +40,7 @@ PT_SCENE_CORNELL, PT_SCENE_CORNELL_GLASS, PT_SCENE_TRIANGLE_SOUP, PT_SCENE_CORNE
 PT_BVH_WIDTH_2, PT_BVH_WIDTH_4, PT_BVH_WIDTH_4Q, PT_BVH_WIDTH_8Q, PT_BVH_WIDTH_8O, PT_BVH_BUILD_LBVH = 2, 4, 68, 72, 73, 0x100
 PT_COMM_FORCE_RCCL, PT_COMM_COPY_EXCHANGE = 1, 2
 PT_TRACE_OCCLUSION, PT_TRACE_COUNT_VISITS, PT_TRACE_HOST_MEMORY = 1, 2, 4
+PT_UPDATE_HOST_MEMORY = 1
 
 
 class pt_device_desc(C.Structure):
@@ -116,6 +117,8 @@ SYMBOLS = {
     "pt_scene_bvh_read": (_st, [_vp, _vp, _u64, _vp, _u64]),
     "pt_render": (_st, [_vp, _vp, _P(pt_render_params), _P(pt_stats)]),
     "pt_trace_rays": (_st, [_vp, _vp, _vp, _vp, _u64, _u32, _P(pt_stats)]),
+    "pt_scene_update_triangles": (_st, [_vp, _vp, _u64, _u32, _P(pt_stats)]),
+    "pt_scene_update_spheres": (_st, [_vp, _vp, _u64]),
     "pt_framebuffer_read": (_st, [_vp, _vp, _u64]),
     "pt_framebuffer_read_rgba8": (_st, [_vp, _vp, _u64]),
     "pt_framebuffer_read_srgb8": (_st, [_vp, _vp, _u64]),

@@ -4,6 +4,7 @@
 // HIP only: there is no CPU fallback anywhere in this library.
 #include "ptrt_internal.h"
 #include "bvh_build.h"
+#include "refit.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
@@ -186,7 +187,9 @@ struct pt_scene {
     uint32_t layout = 0;                 // PT_BVH_WIDTH_* the scene was committed with
     mutable std::vector<uint8_t> packed_nodes; // layouts PT_BVH_WIDTH_4Q / _8Q: the 64- / 128-byte nodes that are uploaded / read back
     bool device_packed = false;          // the blob was packed on the device (lbvh.hip build_lbvh_blob4q_device): the host copies below
-    mutable bool host_mirror = true;     // (packed_nodes, bvh.tris) are fetched from the device the first time pt_scene_bvh_read wants them
+    mutable bool host_mirror = true;     // false: the host copies of the blob (packed_nodes or bvh.slots, and bvh.tris) are stale — packed on the
+                                         // device, or refitted since — and pt_scene_bvh_read fetches them from the device first
+    bool unified = false;                // committed under the PTRT_UNIFIED experiment (one array of nodes and triangles): no updates
     bool quantised() const { return layout == PT_BVH_WIDTH_4Q || layout == PT_BVH_WIDTH_8Q || layout == PT_BVH_WIDTH_8O; }
     const void *node_data() const { return quantised() ? (const void *)packed_nodes.data() : (const void *)bvh.slots.data(); }
     uint64_t node_bytes() const { return device_packed ? (uint64_t)bvh.n_nodes * 64u : quantised() ? packed_nodes.size() : bvh.slots.size() * sizeof(BvhSlot); }
@@ -196,6 +199,18 @@ struct pt_scene {
     mutable ExtendChoice ext;            // cache, not scene content: what earlier frames measured
     DevBuf<uint2> d_sph_mat;
     DeviceScene ds{};
+    // pt_scene_update_triangles (refit.hip, docs/SPEC.md §4.3): scratch made by the first update after a commit, kept until the next one
+    struct Refit {
+        bool ready = false;                  // level lists built for the committed tree
+        std::vector<uint32_t> level_off;     // level l (deepest first) = list[level_off[l] .. level_off[l + 1])
+        DevBuf<uint32_t> list, flag;
+        DevBuf<float> tbox, nbox, carea;     // per blob triangle / per node / per child slot
+        DevBuf<float> verts[2];              // verts[cur]: the scene's current vertices once an update has run; the other one takes the next
+        DevBuf<double> sah;                  // per-block partial sums, then the total
+        uint32_t cur = 0;
+        hipEvent_t ev[4] = {};
+    } refit;
+    bool verts_on_device = false;        // `verts` is stale: the current vertices are refit.verts[refit.cur] (fetched when a commit needs them)
 };
 
 namespace {
@@ -392,6 +407,9 @@ void pt_scene_destroy(pt_scene *s)
     if (!s) return;
     if (s->ctx) { (void)hipSetDevice(s->ctx->device); (void)hipStreamSynchronize(s->ctx->stream); }
     s->d_nodes.release(); s->d_tris.release();s->d_spheres.release(); s->d_mats.release(); s->d_sph_mat.release();
+    auto &R = s->refit;
+    R.list.release(); R.flag.release(); R.tbox.release(); R.nbox.release(); R.carea.release(); R.verts[0].release(); R.verts[1].release(); R.sah.release();
+    for (auto &e : R.ev) if (e) (void)hipEventDestroy(e);
     delete s;
 }
 
@@ -403,6 +421,7 @@ pt_status pt_scene_set_triangles(pt_scene *s, const float *verts9, const uint32_
     for (uint64_t i = 0; i < count * 9; ++i)
         if (!std::isfinite(verts9[i])) return fail(s->ctx, PT_ERR_INVALID_ARGUMENT, "non-finite vertex coordinate at float %llu", (unsigned long long)i);
     s->verts.assign(verts9, verts9 + count * 9);
+    s->verts_on_device = false;
     if (material_ids) s->tri_mat.assign(material_ids, material_ids + count); else s->tri_mat.assign(count, 0u);
     s->committed = false;
     return PT_OK;
@@ -478,6 +497,13 @@ pt_status pt_scene_commit(pt_scene *s, uint32_t bvh_width)
     if ((nt || ns) && nm == 0) return fail(c, PT_ERR_INVALID_ARGUMENT, "primitives but no materials");
     for (uint32_t i = 0; i < nt; ++i) if (s->tri_mat[i] >= nm) return fail(c, PT_ERR_INVALID_ARGUMENT, "triangle %u: material id %u >= %u", i, s->tri_mat[i], nm);
     for (uint32_t i = 0; i < ns; ++i) if (s->sph_mat[i] >= nm) return fail(c, PT_ERR_INVALID_ARGUMENT, "sphere %u: material id %u >= %u", i, s->sph_mat[i], nm);
+
+    if (s->verts_on_device) { // updated since the last commit: build from the current vertices
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipMemcpy(s->verts.data(), s->refit.verts[s->refit.cur].p, s->verts.size() * sizeof(float), hipMemcpyDeviceToHost));
+        s->verts_on_device = false;
+    }
+    s->refit.ready = false;
 
     const bool oct = bvh_width == PT_BVH_WIDTH_8O;
     const uint32_t fan = bvh_width == PT_BVH_WIDTH_2 ? 2u : (bvh_width == PT_BVH_WIDTH_8Q || oct) ? 8u : 4u;
@@ -599,6 +625,7 @@ pt_status pt_scene_commit(pt_scene *s, uint32_t bvh_width)
     s->ext = ExtendChoice{};
     s->has_specular = false;
     for (const pt_material &m : s->mats) if (m.kind != PT_LAMBERT) s->has_specular = true;
+    s->unified = unified_units != 0;
     s->committed = true;
     return PT_OK;
 }
@@ -621,15 +648,18 @@ pt_status pt_scene_bvh_read(const pt_scene *s, void *nodes, uint64_t node_bytes,
 {
     if (!s) return fail(nullptr, PT_ERR_INVALID_ARGUMENT, "scene is NULL");
     if (!s->committed) return fail(s->ctx, PT_ERR_NOT_COMMITTED, "scene not committed");
-    if (!s->host_mirror) { // packed on the device: fetch the blob now (nodes as they are, triangles = rows 0-2 of the 64-byte records)
+    if (!s->host_mirror) { // packed on the device or refitted: fetch the blob now (nodes as they are, triangles = rows 0-2 of the 64-byte records)
         const pt_scene *m = s; // fills the (mutable) host copies the scene owns; device data and results are untouched
         pt_context *c = s->ctx;
         HIP_TRY(c, hipSetDevice(c->device));
-        m->packed_nodes.resize((size_t)s->bvh.n_nodes * 64);
-        std::vector<float> rec(s->tri_mat.size() * 16);
-        if (!m->packed_nodes.empty()) HIP_TRY(c, hipMemcpy(m->packed_nodes.data(), s->d_nodes.p, m->packed_nodes.size(), hipMemcpyDeviceToHost));
+        const size_t nn = s->bvh.n_nodes;
+        void *host_nodes = nullptr; size_t bytes = 0;
+        if (s->quantised()) { m->packed_nodes.resize(nn * (s->layout == PT_BVH_WIDTH_4Q ? 64 : 128)); host_nodes = m->packed_nodes.data(); bytes = m->packed_nodes.size(); }
+        else { m->bvh.slots.resize(nn * s->bvh.width); host_nodes = m->bvh.slots.data(); bytes = m->bvh.slots.size() * sizeof(BvhSlot); }
+        std::vector<float> rec(s->n_blob_tris() * 16);
+        if (bytes) HIP_TRY(c, hipMemcpy(host_nodes, s->d_nodes.p, bytes, hipMemcpyDeviceToHost));
         if (!rec.empty()) HIP_TRY(c, hipMemcpy(rec.data(), s->d_tris.p, rec.size() * sizeof(float), hipMemcpyDeviceToHost));
-        m->bvh.tris.resize(s->tri_mat.size());
+        m->bvh.tris.resize(s->n_blob_tris());
         for (size_t i = 0; i < m->bvh.tris.size(); ++i) std::memcpy(&m->bvh.tris[i], &rec[i * 16], sizeof(BvhTri));
         s->host_mirror = true;
     }
@@ -957,17 +987,18 @@ pt_status pt_render(pt_context *c, const pt_scene *s, const pt_render_params *p,
 
 namespace {
 // A caller's device array must lie inside one allocation on the context's device: the kernel reads / writes `bytes` from `p` unchecked.
-pt_status check_device_array(pt_context *c, const void *p, uint64_t bytes, const char *what)
+pt_status check_device_array(pt_context *c, const void *p, uint64_t bytes, const char *what, const char *who = "pt_trace_rays",
+                             const char *host_flag = "PT_TRACE_HOST_MEMORY")
 {
     hipPointerAttribute_t at;
     if (hipPointerGetAttributes(&at, p) != hipSuccess || (at.type != hipMemoryTypeDevice && !at.isManaged) || at.device != c->device) {
         (void)hipGetLastError();
-        return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_trace_rays: %s is not device memory of the context's device %d (host arrays: PT_TRACE_HOST_MEMORY)", what, c->device);
+        return fail(c, PT_ERR_INVALID_ARGUMENT, "%s: %s is not device memory of the context's device %d (host arrays: %s)", who, what, c->device, host_flag);
     }
     hipDeviceptr_t base = nullptr; size_t size = 0;
     if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return PT_OK; } // (range unknown: trust the caller)
     if ((const char *)p + bytes > (const char *)base + size)
-        return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_trace_rays: %s holds %llu bytes from the pointer on, the batch needs %llu", what,
+        return fail(c, PT_ERR_INVALID_ARGUMENT, "%s: %s holds %llu bytes from the pointer on, the call needs %llu", who, what,
                     (unsigned long long)((const char *)base + size - (const char *)p), (unsigned long long)bytes);
     return PT_OK;
 }
@@ -1032,6 +1063,137 @@ pt_status pt_trace_rays(pt_context *c, const pt_scene *s, const void *rays, void
 {
     const pt_status st = trace_rays(c, s, rays, hits, n_rays, flags, stats);
     if (st != PT_OK && c) { (void)hipSetDevice(c->device); drain(c); } // nothing of a failed query (e.g. a copy into `hits`) runs on after the call
+    return st;
+}
+
+// ------------------------------------------------------------------------------------------------ geometry updates (docs/SPEC.md §4.3)
+
+// The first update after a commit: level lists from the tree's refs (in device node order, whatever PTRT_NODE_ORDER made of it) and the
+// scratch the passes use. Sizes are those of the committed tree, which an update never changes.
+static pt_status prepare_refit(pt_scene *s)
+{
+    pt_context *c = s->ctx;
+    auto &R = s->refit;
+    const uint32_t nn = s->bvh.n_nodes, fan = s->bvh.width, nbt = (uint32_t)s->n_blob_tris(), nt = (uint32_t)s->tri_mat.size();
+    for (auto &e : R.ev) if (!e) HIP_TRY(c, hipEventCreate(&e));
+    std::vector<int32_t> refs((size_t)nn * fan);
+    if (s->device_packed) { // BVH4Q nodes that never visited the host: their four refs (bytes 16-31 of every 64-byte node)
+        if (nn) HIP_TRY(c, hipMemcpy2D(refs.data(), 16, (const uint8_t *)s->d_nodes.p + 16, 64, 16, nn, hipMemcpyDeviceToHost));
+    } else for (size_t k = 0; k < refs.size(); ++k) refs[k] = s->bvh.slots[k].ref; // the host blob the device nodes were packed from
+    std::vector<uint32_t> list;
+    if (!refit_levels(refs.data(), nn, fan, nbt, list, R.level_off)) return fail(c, PT_ERR_INTERNAL, "pt_scene_update_triangles: the committed tree's refs do not form a tree");
+    HIP_TRY(c, R.list.ensure(list.size()));
+    if (!list.empty()) HIP_TRY(c, hipMemcpy(R.list.p, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(c, R.tbox.ensure((size_t)nbt * 6)); HIP_TRY(c, R.nbox.ensure((size_t)nn * 6)); HIP_TRY(c, R.carea.ensure((size_t)nn * fan));
+    HIP_TRY(c, R.verts[0].ensure((size_t)nt * 9)); HIP_TRY(c, R.verts[1].ensure((size_t)nt * 9));
+    HIP_TRY(c, R.sah.ensure(refit_sah_blocks(nn) + 1u)); HIP_TRY(c, R.flag.ensure(1));
+    R.ready = true;
+    return PT_OK;
+}
+
+static pt_status update_triangles(pt_scene *s, const void *verts9, uint64_t count, uint32_t flags, pt_stats *stats)
+{
+    if (!s) return fail(nullptr, PT_ERR_INVALID_ARGUMENT, "pt_scene_update_triangles: scene is NULL");
+    pt_context *c = s->ctx;
+    if (flags & ~(uint32_t)PT_UPDATE_HOST_MEMORY) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_scene_update_triangles: unknown flag bits 0x%x", flags & ~(uint32_t)PT_UPDATE_HOST_MEMORY);
+    if (!s->committed) return fail(c, PT_ERR_NOT_COMMITTED, "pt_scene_update_triangles: scene not committed");
+    const uint64_t nt = s->tri_mat.size();
+    if (count != nt) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_scene_update_triangles: count %llu, the scene was committed with %llu triangles", (unsigned long long)count, (unsigned long long)nt);
+    if (count && !verts9) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_scene_update_triangles: verts9 is NULL");
+    const bool host = (flags & PT_UPDATE_HOST_MEMORY) != 0;
+    if (host) {
+        const float *v = (const float *)verts9;
+        for (uint64_t i = 0; i < count * 9; ++i)
+            if (!std::isfinite(v[i])) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_scene_update_triangles: non-finite vertex coordinate at float %llu", (unsigned long long)i);
+    }
+    if (!c) return fail(c, PT_ERR_UNSUPPORTED, "pt_scene_update_triangles: a detached scene has no device tree to refit (set the triangles and commit)");
+    if (s->unified) return fail(c, PT_ERR_UNSUPPORTED, "pt_scene_update_triangles: not for a scene committed under PTRT_UNIFIED");
+    pt_stats out; std::memset(&out, 0, sizeof out);
+    if (count == 0) { if (stats) *stats = out; return PT_OK; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    pt_status st;
+    if (!host) {
+        if ((uintptr_t)verts9 & 3u) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_scene_update_triangles: verts9 must be 4-byte aligned");
+        if ((st = check_device_array(c, verts9, count * 36u, "verts9", "pt_scene_update_triangles", "PT_UPDATE_HOST_MEMORY")) != PT_OK) return st;
+    }
+    auto &R = s->refit;
+    if (!R.ready && (st = prepare_refit(s)) != PT_OK) return st;
+    hipStream_t q = c->stream;
+    const uint32_t nxt = s->verts_on_device ? R.cur ^ 1u : R.cur; // the buffer that does not hold the scene's current vertices
+    float *v = R.verts[nxt].p;
+    if (host) HIP_TRY(c, hipMemcpyAsync(v, verts9, count * 36u, hipMemcpyHostToDevice, q));
+    HIP_TRY(c, hipEventRecord(R.ev[0], q));
+    float ms_check = 0.f;
+    if (!host) { // the non-finite reduction runs (and copies the batch aside) before anything of the scene is written
+        HIP_TRY(c, hipMemsetAsync(R.flag.p, 0, sizeof(uint32_t), q));
+        HIP_TRY(c, launch_refit_stage(q, (const float *)verts9, v, count * 9u, R.flag.p));
+        HIP_TRY(c, hipEventRecord(R.ev[1], q));
+        uint32_t bad = 0;
+        HIP_TRY(c, hipMemcpyAsync(&bad, R.flag.p, sizeof bad, hipMemcpyDeviceToHost, q));
+        HIP_TRY(c, hipStreamSynchronize(q));
+        if (bad) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_scene_update_triangles: non-finite vertex coordinate in the device array");
+        HIP_TRY(c, hipEventElapsedTime(&ms_check, R.ev[0], R.ev[1]));
+        HIP_TRY(c, hipEventRecord(R.ev[0], q));
+    }
+    const uint32_t layout = s->layout;
+    HIP_TRY(c, launch_refit_tris(q, v, s->d_tris.p, (uint32_t)s->n_blob_tris(), R.tbox.p));
+    for (size_t l = 0; l + 1 < R.level_off.size(); ++l)
+        HIP_TRY(c, launch_refit_level(q, layout, s->d_nodes.p, R.list.p + R.level_off[l], R.level_off[l + 1] - R.level_off[l], R.tbox.p, R.nbox.p, R.carea.p));
+    const uint32_t nb = refit_sah_blocks(s->bvh.n_nodes);
+    HIP_TRY(c, launch_refit_sah(q, layout, s->d_nodes.p, s->bvh.n_nodes, R.carea.p, R.nbox.p, R.sah.p, R.sah.p + nb));
+    HIP_TRY(c, hipEventRecord(R.ev[2], q));
+    double sah = 0.0;
+    HIP_TRY(c, hipMemcpyAsync(&sah, R.sah.p + nb, sizeof sah, hipMemcpyDeviceToHost, q));
+    HIP_TRY(c, hipStreamSynchronize(q));
+    float ms = 0.f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, R.ev[0], R.ev[2]));
+    out.gpu_ms = (double)ms + ms_check;
+    R.cur = nxt; s->verts_on_device = true;
+    s->bvh.sah_cost = (float)sah;
+    s->host_mirror = false;
+    if (stats) *stats = out;
+    return PT_OK;
+}
+
+static pt_status update_spheres(pt_scene *s, const float *cxyzr, uint64_t count)
+{
+    if (!s) return fail(nullptr, PT_ERR_INVALID_ARGUMENT, "pt_scene_update_spheres: scene is NULL");
+    pt_context *c = s->ctx;
+    if (!s->committed) return fail(c, PT_ERR_NOT_COMMITTED, "pt_scene_update_spheres: scene not committed");
+    const uint64_t ns = s->sph_mat.size();
+    if (count != ns) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_scene_update_spheres: count %llu, the scene was committed with %llu spheres", (unsigned long long)count, (unsigned long long)ns);
+    if (count && !cxyzr) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_scene_update_spheres: cxyzr is NULL");
+    for (uint64_t i = 0; i < count; ++i) // the rule of pt_scene_set_spheres
+        if (!finite3(cxyzr + i * 4) || !(cxyzr[i * 4 + 3] > 0.f) || !std::isfinite(cxyzr[i * 4 + 3]))
+            return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_scene_update_spheres: sphere %llu: non-finite centre or radius <= 0", (unsigned long long)i);
+    if (!c) return fail(c, PT_ERR_UNSUPPORTED, "pt_scene_update_spheres: a detached scene has no device copy to update (set the spheres and commit)");
+    if (s->unified) return fail(c, PT_ERR_UNSUPPORTED, "pt_scene_update_spheres: not for a scene committed under PTRT_UNIFIED");
+    if (count == 0) return PT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    std::vector<uint2> mi(count);
+    for (uint64_t i = 0; i < count; ++i) { // material id + 1.0f / r, as pt_scene_commit makes them
+        const float inv_r = 1.0f / cxyzr[i * 4 + 3];
+        mi[i].x = s->sph_mat[i]; std::memcpy(&mi[i].y, &inv_r, 4);
+    }
+    hipStream_t q = c->stream;
+    HIP_TRY(c, hipMemcpyAsync(s->d_spheres.p, cxyzr, count * 16u, hipMemcpyHostToDevice, q));
+    HIP_TRY(c, hipMemcpyAsync(s->d_sph_mat.p, mi.data(), count * sizeof(uint2), hipMemcpyHostToDevice, q));
+    HIP_TRY(c, hipStreamSynchronize(q));
+    s->spheres.assign(cxyzr, cxyzr + count * 4);
+    return PT_OK;
+}
+
+pt_status pt_scene_update_triangles(pt_scene *s, const void *verts9, uint64_t count, uint32_t flags, pt_stats *stats)
+{
+    const pt_status st = update_triangles(s, verts9, count, flags, stats);
+    if (st != PT_OK && s && s->ctx) { (void)hipSetDevice(s->ctx->device); drain(s->ctx); } // nothing of a failed update runs on after the call
+    return st;
+}
+
+pt_status pt_scene_update_spheres(pt_scene *s, const float *cxyzr, uint64_t count)
+{
+    const pt_status st = update_spheres(s, cxyzr, count);
+    if (st != PT_OK && s && s->ctx) { (void)hipSetDevice(s->ctx->device); drain(s->ctx); }
     return st;
 }
 

@@ -15,6 +15,7 @@
 #include <chrono>
 #include <vector>
 #include "bvh_build.h"
+#include "quantize_node.h"
 
 namespace ptrt {
 namespace {
@@ -273,8 +274,6 @@ __global__ void __launch_bounds__(256) k_expand(TreeView t, const int32_t *__res
     inner_count[q] = ni;
 }
 
-__device__ __forceinline__ float scale_of(uint32_t e) { return __uint_as_float(e << 23); }
-
 // one level, second half: number the inner children breadth-first (they are the next level's queue), quantise, write the node
 __global__ void __launch_bounds__(256) k_finalize(TreeView t, uint32_t n_cur, uint32_t base, const int32_t *__restrict__ kids, const uint32_t *__restrict__ offs,
                                                   int32_t *__restrict__ queue_next, uint8_t *__restrict__ nodes, float *__restrict__ cost, float inv_root_area)
@@ -302,46 +301,12 @@ __global__ void __launch_bounds__(256) k_finalize(TreeView t, uint32_t n_cur, ui
         }
     }
     cost[node] = my_cost;
-    // ---- docs/SPEC.md §4.1 BVH4Q: per axis a power-of-two grid from the children's union; every decoded box must enclose its float box,
-    // checked with the traversal's own expression fma((float)q, scale, origin) (bvh_build.cpp quantize_nodes is the host twin)
-    uint8_t *nd = nodes + (size_t)node * 64;
-    float org[3]; uint32_t ex[3];
-    uint32_t qlo[3] = { 0, 0, 0 }, qhi[3] = { 0, 0, 0 }; // 4 bytes each, child c in byte c
-    for (int a = 0; a < 3; ++a) {
-        float lo = __builtin_inff(), hi = -__builtin_inff();
-        for (int c = 0; c < 4; ++c) if (ref[c] != kNoKid) { lo = fminf(lo, box[c].lo[a]); hi = fmaxf(hi, box[c].hi[a]); }
-        if (!(lo <= hi)) lo = hi = 0.f;
-        org[a] = lo;
-        int e = 1;
-        {
-            const float ext = hi - lo;
-            int ee; const float m = frexpf(ext / 255.0f, &ee);
-            e = (ext > 0.f) ? ee + 127 - (m == 0.5f ? 1 : 0) : 1;
-            e = min(max(e, 1), 254);
-        }
-        for (;;) {
-            const float sc = scale_of((uint32_t)e);
-            bool ok = true;
-            uint32_t pl = 0, ph = 0;
-            for (int c = 0; c < 4 && ok; ++c) {
-                if (ref[c] == kNoKid) continue;
-                int ql = (int)floorf((box[c].lo[a] - lo) / sc), qh = (int)ceilf((box[c].hi[a] - lo) / sc);
-                ql = min(max(ql, 0), 255); qh = min(max(qh, 0), 255);
-                while (ql > 0 && !(__builtin_fmaf((float)ql, sc, lo) <= box[c].lo[a])) --ql;
-                while (qh < 255 && !(__builtin_fmaf((float)qh, sc, lo) >= box[c].hi[a])) ++qh;
-                if (!(__builtin_fmaf((float)ql, sc, lo) <= box[c].lo[a]) || !(__builtin_fmaf((float)qh, sc, lo) >= box[c].hi[a])) { ok = false; break; }
-                pl |= (uint32_t)ql << (8 * c); ph |= (uint32_t)qh << (8 * c);
-            }
-            if (ok || e >= 254) { qlo[a] = pl; qhi[a] = ph; break; }
-            ++e;
-        }
-        ex[a] = (uint32_t)e;
-    }
-    uint32_t *w = reinterpret_cast<uint32_t *>(nd);
-    w[0] = __float_as_uint(org[0]); w[1] = __float_as_uint(org[1]); w[2] = __float_as_uint(org[2]);
-    w[3] = ex[0] | (ex[1] << 8) | (ex[2] << 16);
+    // ---- docs/SPEC.md §4.1 BVH4Q: quantise the children's boxes (quantize_node.h, shared with refit.hip), then the refs
+    bool used[4];
+    for (int c = 0; c < 4; ++c) used[c] = ref[c] != kNoKid;
+    uint32_t *w = reinterpret_cast<uint32_t *>(nodes + (size_t)node * 64);
+    quantize_node<4>(box, used, w);
     for (int c = 0; c < 4; ++c) w[4 + c] = (uint32_t)ref[c];
-    w[8] = qlo[0]; w[9] = qlo[1]; w[10] = qlo[2]; w[11] = qhi[0]; w[12] = qhi[1]; w[13] = qhi[2]; w[14] = 0u; w[15] = 0u;
 }
 
 // depth and worst-case traversal-stack need, one level at a time from the bottom (children live in the next level)

@@ -234,6 +234,36 @@ class Renderer:
                                    C.byref(stats)), self._ctx)
         return hits, stats
 
+    def UpdateGeometry(self, verts=None, spheres=None):
+        """Move the current scene's triangles and/or spheres without a new commit (include/ptrt.h pt_scene_update_triangles /
+        pt_scene_update_spheres, docs/SPEC.md §4.3); returns the triangle update's pt_stats (gpu_ms), zeros without one.
+
+        verts: (N, 9) or (N, 3, 3) float32, the committed count and order; a float32 torch tensor on the renderer's device goes in as a
+        device pointer (the current stream is synchronised first), numpy arrays take the staged host path. spheres: (S, 4) centres
+        and radii, the committed count (host memory). The tree keeps its topology, so the picture is exactly that of a fresh SetScene
+        of the moved geometry; BvhInfo().sah_cost tells how much the old tree has degraded. Each of the two is one library call:
+        the triangles are updated first, and a refused sphere update leaves the triangle update in place."""
+        stats = N.pt_stats()
+        if verts is not None:
+            if N.torch is not None and isinstance(verts, N.torch.Tensor):
+                torch = N.torch
+                dev = verts.device
+                if dev.type != "cuda" or (dev.index if dev.index is not None else torch.cuda.current_device()) != self._device:
+                    raise ValueError(f"verts are on {dev}, the renderer on cuda:{self._device}")
+                v = verts.to(torch.float32).reshape(-1, 9).contiguous()
+                torch.cuda.current_stream(dev).synchronize()  # the library runs on its own stream: the vertices must be complete
+                _check(N.lib.pt_scene_update_triangles(self._scene, C.c_void_p(v.data_ptr() if v.shape[0] else None), v.shape[0], 0,
+                                                       C.byref(stats)), self._ctx)
+            else:
+                v = np.ascontiguousarray(verts, np.float32).reshape(-1, 9)
+                _check(N.lib.pt_scene_update_triangles(self._scene, _ptr(v), len(v), N.PT_UPDATE_HOST_MEMORY, C.byref(stats)), self._ctx)
+        if spheres is not None:
+            if N.torch is not None and isinstance(spheres, N.torch.Tensor):
+                spheres = spheres.detach().cpu().numpy()
+            sph = np.ascontiguousarray(spheres, np.float32).reshape(-1, 4)
+            _check(N.lib.pt_scene_update_spheres(self._scene, _ptr(sph), len(sph)), self._ctx)
+        return stats
+
     # Renderer.Update (Renderer.cs:86-89) is empty in the reference
     def Update(self, deltaTime):
         pass

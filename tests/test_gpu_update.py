@@ -1,0 +1,293 @@
+"""-m gpu: pt_scene_update_triangles / pt_scene_update_spheres (docs/SPEC.md §4.3) against the oracle, on every layout and both builders.
+
+A refit keeps the committed tree's topology and recomputes the triangle records and every box from the new vertices, so the blob it
+leaves must pass the oracle's structural check against the new vertices, render the oracle's frame bit for bit, answer ray queries as
+the oracle does, and give the frame of a fresh commit of the moved geometry. Also: a no-op update changes no byte, device and host
+input agree, spheres move, topology and sah_cost behave, long animations and a re-commit work, a refused device update changes
+nothing, progressive rendering is undisturbed, and a 1M-triangle tree refits."""
+import ctypes as C
+import dataclasses
+
+import numpy as np
+import pytest
+
+import ray_caster64 as rc
+from test_gpu_trace import H, LAYOUTS, MISS, W, _scenes, ids_of, oracle, records
+
+pytestmark = pytest.mark.gpu
+
+SCENES = ["cornell", "glass", "tess", "soup", "layers", "duplicates", "spheres64"]
+
+
+def moved(sd, verts=None, spheres=None):
+    return dataclasses.replace(sd, verts=sd.verts if verts is None else np.asarray(verts, np.float32).reshape(-1, 9),
+                               spheres=sd.spheres if spheres is None else np.asarray(spheres, np.float32).reshape(-1, 4))
+
+
+def deform(sd, rng, kind):
+    """'small': every vertex jittered by 1e-3 of the scene's extent; 'large': every triangle carried up to 40 % of the extent across
+    the scene (plus jitter), so that leaves overlap and boxes grow."""
+    v = np.asarray(sd.verts, np.float32).reshape(-1, 3, 3)
+    if len(v) == 0:
+        return np.zeros((0, 9), np.float32)
+    ext = float(np.ptp(v.reshape(-1, 3), axis=0).max())
+    out = v.astype(np.float64) + rng.normal(scale=1e-3 * ext, size=v.shape)
+    if kind == "large":
+        out += rng.uniform(-0.4 * ext, 0.4 * ext, size=(len(v), 1, 3))
+    return out.astype(np.float32).reshape(-1, 9)
+
+
+def blob(r):
+    info = r.BvhInfo()
+    nodes, tris = r.BvhRead()
+    return info, nodes.copy(), tris.copy()
+
+
+def check_against_oracle(P, pto, r, sd, ctx, params=None):
+    """The renderer's current blob validates against sd's vertices, renders the oracle's frame bit for bit (rays and paths too), and
+    its closest-hit queries with visit counters equal pto_closest's."""
+    info, nodes, tris = blob(r)
+    osc = pto.Scene(sd, (info.width, nodes, tris))
+    assert osc.validate_bvh()[0] == 0, ctx
+    params = params or P.make_params(W, H, spp=2, max_depth=8, streams=2)
+    r.Params = params
+    st = r.Render(0.0)
+    ref, ost = pto.render(osc, params)
+    assert np.array_equal(r.ReadFramebuffer(), ref), ctx
+    assert (st.rays, st.paths) == (ost.rays, ost.paths), ctx
+    o, d = rc.camera_rays(pto, sd.cam, W, H)
+    sel = slice(None, None, 3)
+    o, d = o[sel], d[sel]
+    ids, ts, ost = oracle(pto, osc, o, d)
+    hits, qst = r.TraceRays(records(o, d), count_visits=True)
+    assert np.array_equal(ids_of(hits), ids), ctx
+    hit = ids != MISS
+    assert np.array_equal(hits[hit, 0].view(np.uint32), ts[hit].view(np.uint32)), ctx
+    assert (qst.node_visits, qst.tri_tests, qst.sphere_tests) == (ost.node_visits, ost.tri_tests, ost.sphere_tests), ctx
+    return osc
+
+
+@pytest.mark.parametrize("name", SCENES)
+def test_refit_is_exact(P, pto, renderer, name):
+    """Small jitter, then large motion, on every layout and builder: the refitted blob validates against the new vertices and the
+    device equals the oracle on it (frames, rays, paths, closest hits, visit counters)."""
+    N = P.native
+    sd = _scenes(P)[name]
+    for width in LAYOUTS:
+        for build in (0, N.PT_BVH_BUILD_LBVH):
+            rng = np.random.default_rng(width + build)
+            renderer.SetScene(sd, width | build)
+            cur = sd
+            for kind in ("small", "large"):
+                cur = moved(sd, deform(cur, rng, kind))
+                st = renderer.UpdateGeometry(verts=cur.verts)
+                assert st.rays == 0 and st.node_visits == 0 and (st.gpu_ms > 0) == (len(cur.verts) > 0)
+                check_against_oracle(P, pto, renderer, cur, (name, width, build, kind))
+
+
+@pytest.mark.parametrize("name", ["glass", "tess", "soup"])
+def test_same_picture_as_a_rebuild(P, pto, renderer, name):
+    """The frame after an update equals the frame from a fresh SetScene of the deformed geometry, bit for bit."""
+    N = P.native
+    sd = _scenes(P)[name]
+    params = P.make_params(W, H, spp=4, max_depth=8, streams=4)
+    for width in LAYOUTS:
+        for build in (0, N.PT_BVH_BUILD_LBVH):
+            v2 = deform(sd, np.random.default_rng(7), "large")
+            renderer.SetScene(sd, width | build)
+            renderer.UpdateGeometry(verts=v2)
+            renderer.Params = params
+            renderer.Render(0.0)
+            refit = renderer.ReadFramebuffer()
+            renderer.SetScene(moved(sd, v2), width | build)
+            renderer.Render(0.0)
+            assert np.array_equal(refit, renderer.ReadFramebuffer()), (name, width, build)
+
+
+@pytest.mark.parametrize("name", ["glass", "tess", "soup", "duplicates"])
+def test_noop_update_changes_nothing(P, pto, renderer, name):
+    """Every builder puts exact unions of the padded triangle boxes in its blob, and the refit computes the same unions with the same
+    quantiser: updating with the unchanged vertices leaves every byte as the commit made it, and sah_cost within 1e-5."""
+    N = P.native
+    sd = _scenes(P)[name]
+    for width in LAYOUTS:
+        for build in (0, N.PT_BVH_BUILD_LBVH):
+            renderer.SetScene(sd, width | build)
+            info0, nodes0, tris0 = blob(renderer)
+            for _ in range(2):
+                renderer.UpdateGeometry(verts=sd.verts)
+                info1, nodes1, tris1 = blob(renderer)
+                assert np.array_equal(nodes0, nodes1) and np.array_equal(tris0, tris1), (name, width, build)
+                assert abs(info1.sah_cost - info0.sah_cost) <= 1e-5 * info0.sah_cost, (name, width, build, info0.sah_cost, info1.sah_cost)
+                assert info1.build_ms == info0.build_ms
+
+
+def test_device_input_equals_host_input(P, pto, renderer):
+    """A float32 torch tensor on the device and a numpy array give identical blob bytes and sah_cost."""
+    import torch
+    N = P.native
+    sd = _scenes(P)["tess"]
+    v2 = deform(sd, np.random.default_rng(3), "large")
+    for width in (2, 68, 73):
+        for build in (0, N.PT_BVH_BUILD_LBVH):
+            out = []
+            for verts in (v2, torch.from_numpy(v2).cuda(), torch.from_numpy(v2.reshape(-1, 3, 3)).cuda()):
+                renderer.SetScene(sd, width | build)
+                st = renderer.UpdateGeometry(verts=verts)
+                assert st.gpu_ms > 0
+                out.append(blob(renderer))
+            for info, nodes, tris in out[1:]:
+                assert np.array_equal(nodes, out[0][1]) and np.array_equal(tris, out[0][2]), (width, build)
+                assert info.sah_cost == out[0][0].sah_cost
+
+
+def test_spheres_move(P, pto, renderer):
+    """Moved and resized spheres (triangles unchanged, then both at once) give the oracle's frame."""
+    sd = _scenes(P)["spheres64"]
+    rng = np.random.default_rng(5)
+    for width in (2, 68):
+        renderer.SetScene(sd, width)
+        sph = np.asarray(sd.spheres, np.float32).copy()
+        sph[:, :3] += rng.normal(scale=0.05, size=(len(sph), 3)).astype(np.float32)
+        sph[:, 3] *= rng.uniform(0.5, 1.5, size=len(sph)).astype(np.float32)
+        st = renderer.UpdateGeometry(spheres=sph)
+        assert st.gpu_ms == 0
+        check_against_oracle(P, pto, renderer, moved(sd, spheres=sph), ("spheres", width))
+        v2 = deform(sd, rng, "small")
+        sph2 = sph.copy()
+        sph2[:, 1] += np.float32(0.1)
+        renderer.UpdateGeometry(verts=v2, spheres=sph2)
+        check_against_oracle(P, pto, renderer, moved(sd, v2, sph2), ("both", width))
+
+
+def numpy_sah(nodes, width):
+    """bvh_build.cpp emit_blob's cost restated on f32 slots: sum of f32(area / root area) (times the count for a leaf), in float64."""
+    n = width
+    slots = np.frombuffer(nodes.tobytes(), np.float32).reshape(-1, n, 8)
+    refs = slots[:, :, 3].view(np.int32)
+    lo, hi = slots[:, :, 0:3], slots[:, :, 4:7]
+
+    def area(lo, hi):
+        d = (hi - lo).astype(np.float32)
+        a = np.float32(2) * (d[..., 0] * d[..., 1] + d[..., 1] * d[..., 2] + d[..., 2] * d[..., 0])
+        return np.where(d[..., 0] < 0, np.float32(0), a).astype(np.float32)
+
+    used = refs != 0x7FFFFFFF
+    rlo, rhi = lo[0][used[0]].min(0), hi[0][used[0]].max(0)
+    ra = np.maximum(area(rlo, rhi), np.float32(1e-30))
+    cnt = np.where(refs < 0, (~refs & 7) + 1, 1).astype(np.float64)
+    q = (area(lo, hi) / ra).astype(np.float32).astype(np.float64)
+    return float((q * cnt)[used].sum())
+
+
+def test_topology_stable_and_sah(P, pto, renderer):
+    """n_nodes, max_depth, stack_need and the layout stay through updates; sah_cost rises with large motion, and on the f32 layouts
+    equals a numpy recomputation from the read-back boxes within 1e-5."""
+    N = P.native
+    for name in ("tess", "soup", "layers"):
+        sd = _scenes(P)[name]
+        for width in LAYOUTS:
+            for build in (0, N.PT_BVH_BUILD_LBVH):
+                renderer.SetScene(sd, width | build)
+                info0, nodes0, _ = blob(renderer)
+                if width in (2, 4):
+                    assert abs(numpy_sah(nodes0, width) - info0.sah_cost) <= 1e-5 * info0.sah_cost
+                renderer.UpdateGeometry(verts=deform(sd, np.random.default_rng(1), "large"))
+                info1, nodes1, _ = blob(renderer)
+                ctx = (name, width, build)
+                assert (info1.width, info1.n_nodes, info1.max_depth, info1.stack_need, info1.node_bytes, info1.tri_bytes) == \
+                    (info0.width, info0.n_nodes, info0.max_depth, info0.stack_need, info0.node_bytes, info0.tri_bytes), ctx
+                assert info1.sah_cost > info0.sah_cost, ctx
+                if width in (2, 4):
+                    assert abs(numpy_sah(nodes1, width) - info1.sah_cost) <= 1e-5 * info1.sah_cost, ctx
+
+
+def test_long_animation_and_recommit(P, pto, renderer):
+    """Ten consecutive updates (a wave through the mesh) all validate and match the oracle; a pt_scene_commit after them builds from
+    the updated geometry."""
+    N = P.native
+    sd = _scenes(P)["tess"]
+    v = np.asarray(sd.verts, np.float32).reshape(-1, 3, 3)
+    ext = float(np.ptp(v.reshape(-1, 3), axis=0).max())
+    for width, build in ((68, N.PT_BVH_BUILD_LBVH), (73, 0), (4, 0)):
+        renderer.SetScene(sd, width | build)
+        cur = sd
+        for k in range(10):
+            w = v.copy()
+            w[..., 1] += (0.05 * ext * np.sin(w[..., 0] * 7.0 + k * 0.6)).astype(np.float32)
+            cur = moved(sd, w)
+            renderer.UpdateGeometry(verts=cur.verts)
+            if k % 3 == 0 or k == 9:
+                check_against_oracle(P, pto, renderer, cur, (width, build, k))
+            else:
+                info, nodes, tris = blob(renderer)
+                assert pto.Scene(cur, (info.width, nodes, tris)).validate_bvh()[0] == 0
+        assert N.lib.pt_scene_commit(renderer._scene, width | build) == N.PT_OK
+        check_against_oracle(P, pto, renderer, cur, (width, build, "recommit"))
+
+
+def test_refused_device_update_changes_nothing(P, pto, renderer):
+    """A device array with one NaN is PT_ERR_INVALID_ARGUMENT, and the blob and the next frame equal those before the call; so are a
+    device pointer that is not 4-byte aligned, host memory passed as device memory, and a wrong count."""
+    import torch
+    N = P.native
+    sd = _scenes(P)["glass"]
+    for width in (2, 68):
+        renderer.SetScene(sd, width)
+        renderer.UpdateGeometry(verts=deform(sd, np.random.default_rng(2), "small"))
+        info0, nodes0, tris0 = blob(renderer)
+        renderer.Params = P.make_params(W, H, spp=4, max_depth=8, streams=4)
+        renderer.Render(0.0)
+        before = renderer.ReadFramebuffer()
+        bad = torch.from_numpy(deform(sd, np.random.default_rng(4), "large")).cuda()
+        bad[len(bad) // 2, 4] = float("nan")
+        host = np.asarray(sd.verts, np.float32).copy()
+        torch.cuda.synchronize()
+        st = N.pt_stats()
+        call = lambda p, n: N.lib.pt_scene_update_triangles(renderer._scene, C.c_void_p(p), n, 0, C.byref(st))
+        assert call(bad.data_ptr(), len(bad)) == N.PT_ERR_INVALID_ARGUMENT
+        assert b"non-finite" in N.lib.pt_last_error(renderer._ctx)
+        assert call(bad.data_ptr() + 2, len(bad)) == N.PT_ERR_INVALID_ARGUMENT
+        assert call(host.ctypes.data, len(bad)) == N.PT_ERR_INVALID_ARGUMENT
+        assert b"not device memory" in N.lib.pt_last_error(renderer._ctx)
+        assert call(bad.data_ptr(), len(bad) - 1) == N.PT_ERR_INVALID_ARGUMENT
+        with pytest.raises(P.PtException):
+            renderer.UpdateGeometry(verts=bad)
+        info1, nodes1, tris1 = blob(renderer)
+        assert np.array_equal(nodes0, nodes1) and np.array_equal(tris0, tris1) and info1.sah_cost == info0.sah_cost
+        renderer.Render(0.0)
+        assert np.array_equal(renderer.ReadFramebuffer(), before), width
+
+
+def test_progressive_frames_then_update(P, pto, renderer):
+    """Progressive frames (PT_FLAG_ACCUMULATE), an update, then a non-accumulate frame with spp >= streams: the oracle's frame of the
+    new geometry. The update keeps the scene's extend-kernel choice and the context's frame-start template; neither may show."""
+    N = P.native
+    sd = _scenes(P)["glass"]
+    renderer.SetScene(sd, 0)
+    for offset, flags in ((0, 0), (4, N.PT_FLAG_ACCUMULATE), (8, N.PT_FLAG_ACCUMULATE)):
+        renderer.Params = P.make_params(W, H, spp=4, max_depth=8, streams=4, sample_offset=offset, flags=flags)
+        renderer.Render(0.0)
+    v2 = deform(sd, np.random.default_rng(9), "large")
+    renderer.UpdateGeometry(verts=v2)
+    for spp in (4, 8):
+        check_against_oracle(P, pto, renderer, moved(sd, v2), spp, P.make_params(W, H, spp=spp, max_depth=8, streams=4))
+
+
+def test_million_triangle_lbvh_refits(P, pto, renderer):
+    """The 1M-triangle Cornell box committed with the GPU builder (BVH4Q packed on the device), deformed on the device: the blob still
+    validates, the topology stays, and a small frame matches the oracle."""
+    import torch
+    N = P.native
+    sd = P.make_scene(N.PT_SCENE_CORNELL_TESS, 1_000_000, 3, W, H)
+    renderer.SetScene(sd, N.PT_BVH_BUILD_LBVH)
+    info0 = renderer.BvhInfo()
+    assert info0.width == 68 and info0.n_tris >= 900_000
+    v = torch.from_numpy(np.asarray(sd.verts, np.float32)).cuda().reshape(-1, 3, 3)
+    v = v + 0.02 * torch.sin(v[..., 0:1] * 5.0)
+    st = renderer.UpdateGeometry(verts=v)
+    assert st.gpu_ms > 0
+    cur = moved(sd, v.cpu().numpy())
+    info1 = renderer.BvhInfo()
+    assert (info1.n_nodes, info1.max_depth, info1.stack_need) == (info0.n_nodes, info0.max_depth, info0.stack_need)
+    check_against_oracle(P, pto, renderer, cur, "1M", P.make_params(W, H, spp=1, max_depth=4))
