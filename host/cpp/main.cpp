@@ -1,7 +1,8 @@
 // ptrt_cli — headless counterpart of Program.cs / App.Run (RayTracing/Program.cs:1-9, App.cs:15-21):
 // build a renderer, render N frames, write the image the reference would have shown in its window.
 //   ptrt_cli [--scene reference|cornell|glass|soup|tess] [--detail N] [--size WxH] [--spp N] [--depth N]
-//            [--frames N] [--ppm out.ppm] [--pfm out.pfm] [--gpus N] [--virtual 0|1|2]
+//            [--frames N] [--ppm out.ppm] [--pfm out.pfm] [--gpus N] [--virtual 0|1|2] [--nee]
+// --nee: next-event estimation (PT_FLAG_NEXT_EVENT, docs/SPEC.md §7).
 // --gpus N: the frame's tiles over N devices of this node, one RCCL gather per frame (pt_comm); with --virtual 1 the N ranks are
 // rendered one after the other on device 0 (rehearsal of the partition on a single GPU); with --virtual 2 every rank has its own
 // context on device 0, the ranks render concurrently (one host thread each) and exchange their tiles by device copies.
@@ -14,9 +15,11 @@
 int main(int argc, char **argv)
 {
     std::string scene = "reference", ppm = "frame.ppm", pfm;
-    uint32_t w = 1920, h = 1080, detail = 0, spp = 64, depth = 8, frames = 1, gpus = 1, virt = 0;
-    for (int i = 1; i + 1 < argc; i += 2) {
+    uint32_t w = 1920, h = 1080, detail = 0, spp = 64, depth = 8, frames = 1, gpus = 1, virt = 0, flags = 0;
+    for (int i = 1; i < argc; i += 2) {
         const std::string a = argv[i];
+        if (a == "--nee") { flags |= PT_FLAG_NEXT_EVENT; --i; continue; } // a switch: no value
+        if (i + 1 >= argc) { std::fprintf(stderr, "option %s needs a value\n", a.c_str()); return 2; }
         if (a == "--scene") scene = argv[i + 1];
         else if (a == "--detail") detail = (uint32_t)std::strtoul(argv[i + 1], nullptr, 0);
         else if (a == "--size") std::sscanf(argv[i + 1], "%ux%u", &w, &h);
@@ -38,7 +41,7 @@ int main(int argc, char **argv)
             multi.reset(new ptrt_host::MultiRenderer(gpus, w, h, (int)virt));
             multi->Init();
             multi->LoadSyntheticScene(kind, detail);
-            multi->Params.spp = spp; multi->Params.max_depth = depth;
+            multi->Params.spp = spp; multi->Params.max_depth = depth; multi->Params.flags |= flags;
             for (uint32_t f = 0; f < frames; ++f) multi->Render(0.f);
             unsigned long long rays = 0; double ms = 0;
             for (const pt_stats &s : multi->LastStats) { rays += s.rays; ms = s.gpu_ms > ms ? s.gpu_ms : ms; }
@@ -48,7 +51,7 @@ int main(int argc, char **argv)
             single->Init();
             if (scene != "reference") {
                 single->LoadSyntheticScene(kind, detail);
-                single->Params.spp = spp; single->Params.max_depth = depth;
+                single->Params.spp = spp; single->Params.max_depth = depth; single->Params.flags |= flags;
             }
             for (uint32_t f = 0; f < frames; ++f) single->Render(0.f);
             const pt_stats &s = single->LastStats;

@@ -11,7 +11,7 @@ public enum PtStatus : int { Ok = 0, InvalidArgument, NoDevice, Hip, OutOfMemory
 public enum PtMode : uint { ReferenceSphere = 0, PathTrace = 1 }
 public enum PtMaterialKind : uint { Lambert = 0, Metal = 1, Dielectric = 2 }
 public enum PtSceneKind : uint { Cornell = 0, CornellGlass = 1, TriangleSoup = 2, CornellTess = 3 }
-[Flags] public enum PtFlags : uint { ProfileKernels = 1, CountVisits = 2, ExtendPacked = 4, ExtendSimple = 8, Accumulate = 16, BucketSpecular = 32, SplitKernels = 64, ExtendPool = 128 }
+[Flags] public enum PtFlags : uint { ProfileKernels = 1, CountVisits = 2, ExtendPacked = 4, ExtendSimple = 8, Accumulate = 16, BucketSpecular = 32, SplitKernels = 64, ExtendPool = 128, NextEvent = 256 }
 [Flags] public enum PtCommFlags : uint { ForceRccl = 1, CopyExchange = 2 }
 [Flags] public enum PtTraceFlags : uint { Occlusion = 1, CountVisits = 2, HostMemory = 4 }
 [Flags] public enum PtUpdateFlags : uint { HostMemory = 1 }

@@ -30,7 +30,8 @@ extern "C" {
 
 /* 2: pt_tuning grew to 40 bytes (extend_kernel, readback); pt_comm_*, pt_framebuffer_read_srgb8, PT_FLAG_EXTEND_POOL, pt_bvh_info.stack_need and
  * the BVH2 default for small scenes had arrived under version 1. pt_trace_rays and PT_TRACE_* arrived later under version 2, and after them
- * pt_scene_update_triangles / pt_scene_update_spheres and PT_UPDATE_HOST_MEMORY (additions only: no struct or existing signature changed). Hosts compare pt_abi_version() with the header they were built against. */
+ * pt_scene_update_triangles / pt_scene_update_spheres and PT_UPDATE_HOST_MEMORY, then PT_FLAG_NEXT_EVENT (additions only: no struct or existing
+ * signature changed). Hosts compare pt_abi_version() with the header they were built against. */
 #define PTRT_ABI_VERSION 2
 
 typedef int32_t pt_status;
@@ -68,9 +69,15 @@ enum {
                                      inside the extend kernel; same frame, lets PT_FLAG_PROFILE_KERNELS time the two separately */
     PT_FLAG_EXTEND_POOL = 128u,   /* force the pooled extend kernel (a wavefront owns 128 queue entries, refills idle lanes during
                                      traversal and shades the whole pool at full width) */
-    PT_FLAG_ACCUMULATE = 16u     /* progressive rendering: keep the sums of the previous call(s) (same size/rank/streams/seed,
-                                     sample_offset = samples so far) and show the mean over all samples — the converging analogue
-                                     of the reference's render-every-frame loop (App.cs:39-42) */
+    PT_FLAG_ACCUMULATE = 16u,    /* progressive rendering: keep the sums of the previous call(s) (same size/rank/streams/seed and
+                                     PT_FLAG_NEXT_EVENT setting, sample_offset = samples so far) and show the mean over all samples — the
+                                     converging analogue of the reference's render-every-frame loop (App.cs:39-42) */
+    PT_FLAG_NEXT_EVENT = 256u     /* next-event estimation (docs/SPEC.md §7): every Lambert vertex also samples a point on an emissive triangle
+                                     and traces a shadow ray to it, combined with the BSDF-sampled hits by multiple importance sampling. Same
+                                     mean, far less noise in scenes lit by small emitters. The BSDF-sampled paths are those of a plain frame;
+                                     pt_stats.rays then counts their rays plus the shadow rays traced. Runs on the one-ray-per-lane kernel:
+                                     with PT_FLAG_EXTEND_PACKED / _POOL, PT_FLAG_SPLIT_KERNELS / _BUCKET_SPECULAR, pt_tuning.extend_kernel 2 / 3
+                                     or PT_FLAG_COUNT_VISITS the frame is PT_ERR_UNSUPPORTED */
 };
 /* pt_scene_commit options */
 enum {
@@ -119,7 +126,8 @@ typedef struct {
 } pt_render_params; /* 64 B */
 
 typedef struct {
-    uint64_t rays;          /* ray-scene intersection queries = path segments (the benchmark's unit) */
+    uint64_t rays;          /* ray-scene intersection queries = path segments (the benchmark's unit); with PT_FLAG_NEXT_EVENT plus the
+                               shadow rays traced, so that rays(NEE) - rays(plain) of the same frame is the shadow-ray count */
     uint64_t paths;
     uint64_t node_visits, tri_tests, sphere_tests; /* only with PT_FLAG_COUNT_VISITS, else 0 */
     uint32_t iterations;    /* wavefront iterations = launches of the extend kernel; the default (fused one-ray-per-lane) kernel advances
@@ -157,7 +165,8 @@ typedef struct {
  * the same tree another memory order, or collapse it to wide nodes by the old rule, for the builder experiments of DESIGN.md). */
 typedef struct {
     uint32_t bounces;       /* path vertices a lane advances per launch of the fused extend kernels, 1..64; 0 (default) = 3/4 max_depth - 2
-                               clamped to [4, 12] for the one-ray-per-lane kernel, 64 for the lane-packing one */
+                               clamped to [4, 12] for the one-ray-per-lane kernel, 64 for the lane-packing one. PT_FLAG_NEXT_EVENT frames:
+                               rays (shadow or extension) a lane traces per launch; 0 = twice the one-ray-per-lane default */
     uint32_t loops;         /* independent shard-group wavefront loops per frame, each on its own stream: 1, 2 or 4; 0 (default) = two
                                (frames with PT_FLAG_PROFILE_KERNELS / PT_FLAG_COUNT_VISITS always run one: their kernels are timed alone) */
     uint32_t finish_below;  /* a shard with at most this many live paths runs them to their end in one launch (default 4096; 0 = never) */

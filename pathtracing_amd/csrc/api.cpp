@@ -120,6 +120,8 @@ struct pt_context {
     // what the partial sums in `acc` currently hold (PT_FLAG_ACCUMULATE continues them): frame geometry and samples so far
     uint32_t acc_w = 0, acc_h = 0, acc_rank = 0, acc_nranks = 0, acc_streams = 0, acc_seed = 0;
     uint64_t acc_spp = 0;
+    bool acc_nee = false;           // ... and whether they are next-event estimates (PT_FLAG_NEXT_EVENT): the two do not mix
+    DevBuf<float4> nee_ext, nee_rad; // PT_FLAG_NEXT_EVENT frames only: a slot's pending shadow ray (ptrt_internal.h NeeArgs)
     DevBuf<float2> hit;             // split frames only (k_shade reads what the extend kernel found), like the two specular buckets
     DevBuf<uint32_t> sd, q_ext0, q_ext1, q_metal, q_dielectric, counters, fb8;
     DevBuf<int32_t> stack_ovf;
@@ -211,6 +213,14 @@ struct pt_scene {
         hipEvent_t ev[4] = {};
     } refit;
     bool verts_on_device = false;        // `verts` is stale: the current vertices are refit.verts[refit.cur] (fetched when a commit needs them)
+    // The light table of next-event estimation (docs/SPEC.md §7, build_lights): made at every commit and every triangle update from the
+    // candidates — the triangles whose material emits, in triangle order — of which those with area * (e.r + e.g + e.b) > 0 are lights.
+    std::vector<uint32_t> light_cand;    // original ids of the candidates
+    std::vector<uint32_t> cand_blob;     // the blob index of each candidate (where its pa goes in d_pa)
+    std::vector<float> pa_span;          // host image of d_pa[cand_lo .. cand_hi], the only entries that can be non-zero
+    uint32_t cand_lo = 0, n_lights = 0;
+    DevBuf<float4> d_lights;
+    DevBuf<float> d_cdf, d_pa;
 };
 
 namespace {
@@ -231,6 +241,49 @@ pt_status fail(pt_context *ctx, pt_status code, const char *fmt, ...)
     } while (0)
 
 bool finite3(const float *p) { return std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]); }
+
+// docs/SPEC.md §7: the light set, its f32 CDF and the per-light records from the current vertices of the candidates (9 floats each, in
+// candidate order), uploaded to the scene's device arrays. Area, normal and pa in the op order of §0 / §7; the weights in double.
+pt_status build_lights(pt_context *c, pt_scene *s, const float *cand_verts)
+{
+    std::vector<float> rec, cdf; // 16 floats per light: v0|pa, e1|Le.r, e2|Le.g, n_l|Le.b
+    std::vector<double> w;       // area * (e.r + e.g + e.b) per light
+    std::vector<uint32_t> cand;  // which candidate each light is
+    double total = 0.0;
+    for (size_t k = 0; k < s->light_cand.size(); ++k) {
+        const float *v = cand_verts + k * 9;
+        const float e1[3] = { v[3] - v[0], v[4] - v[1], v[5] - v[2] }, e2[3] = { v[6] - v[0], v[7] - v[1], v[8] - v[2] };
+        const float cr[3] = { std::fmaf(e1[1], e2[2], -(e1[2] * e2[1])), std::fmaf(e1[2], e2[0], -(e1[0] * e2[2])), std::fmaf(e1[0], e2[1], -(e1[1] * e2[0])) };
+        const float dd = std::fmaf(cr[2], cr[2], std::fmaf(cr[1], cr[1], cr[0] * cr[0]));
+        const float area = 0.5f * std::sqrt(dd), inv = 1.0f / std::sqrt(dd); // n_l = normalize(cross(e1, e2)): the bits of the shading row
+        const float *e = s->mats[s->tri_mat[s->light_cand[k]]].emission;
+        const double wk = (double)area * ((double)e[0] + (double)e[1] + (double)e[2]);
+        if (!(area > 0.f) || !(wk > 0.0)) continue;
+        total += wk; w.push_back(wk); cand.push_back((uint32_t)k);
+        const float r[16] = { v[0], v[1], v[2], area, e1[0], e1[1], e1[2], e[0], e2[0], e2[1], e2[2], e[1], cr[0] * inv, cr[1] * inv, cr[2] * inv, e[2] };
+        rec.insert(rec.end(), r, r + 16);
+    }
+    const size_t nl = w.size();
+    cdf.resize(nl);
+    std::fill(s->pa_span.begin(), s->pa_span.end(), 0.0f);
+    double run = 0.0;
+    for (size_t i = 0; i < nl; ++i) {
+        run += w[i]; // the same sums in the same order as above
+        cdf[i] = i + 1 == nl ? 1.0f : (float)(run / total);
+        const float pa = (float)(w[i] / total) / rec[i * 16 + 3]; // pmf (as stored, f32) / area
+        rec[i * 16 + 3] = pa;
+        s->pa_span[s->cand_blob[cand[i]] - s->cand_lo] = pa;
+    }
+    s->n_lights = (uint32_t)nl;
+    if (!c) return PT_OK;
+    HIP_TRY(c, s->d_lights.ensure(std::max<size_t>(nl, 1) * 4)); HIP_TRY(c, s->d_cdf.ensure(std::max<size_t>(nl, 1)));
+    if (nl) {
+        HIP_TRY(c, hipMemcpy(s->d_lights.p, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(s->d_cdf.p, cdf.data(), nl * sizeof(float), hipMemcpyHostToDevice));
+    }
+    if (!s->pa_span.empty()) HIP_TRY(c, hipMemcpy(s->d_pa.p + s->cand_lo, s->pa_span.data(), s->pa_span.size() * sizeof(float), hipMemcpyHostToDevice));
+    return PT_OK;
+}
 
 pt_status layout_of(const pt_render_params *p, pt_tile_layout *o)
 {
@@ -269,6 +322,8 @@ struct Frame {                  // a path-traced frame as plan_frame lays it out
     uint32_t nranks, streams, pixel_slots, n_slots, shard_cap, samples_per_stream, lag, n_loops, packed_chunk, default_bounces;
     uint32_t forced;            // ExtendKernel a frame flag or pt_tuning.extend_kernel forces (0 = none)
     bool profile, count, split, bucket, full_state, accumulate, mapped, compact;
+    bool nee;                   // PT_FLAG_NEXT_EVENT (docs/SPEC.md §7): the one-ray-per-lane kernel with light samples
+    NeeArgs nee_args;
     size_t q_entries; uint64_t total_spp, allocs_before;
     PathState ps; FrameParams fp;
     uint32_t iters; uint64_t slot_launches; size_t n_events; // launches of the longest loop, paths alive at launch starts, profile events
@@ -614,6 +669,33 @@ pt_status pt_scene_commit(pt_scene *s, uint32_t bvh_width)
     }
     if (nm) HIP_TRY(c, hipMemcpy(s->d_mats.p, s->mats.data(), (size_t)nm * sizeof(pt_material), hipMemcpyHostToDevice));
     lap("upload nodes + rest");
+    {   // the light table of next-event estimation (docs/SPEC.md §7): candidates, where their pa lives in the blob order, the table
+        const uint32_t nbt = (uint32_t)s->n_blob_tris();
+        s->light_cand.clear(); s->cand_blob.clear(); s->pa_span.clear(); s->cand_lo = 0; s->n_lights = 0;
+        for (uint32_t i = 0; i < nt; ++i) {
+            const float *e = s->mats[s->tri_mat[i]].emission;
+            if (e[0] != 0.f || e[1] != 0.f || e[2] != 0.f) s->light_cand.push_back(i);
+        }
+        HIP_TRY(c, s->d_pa.ensure(std::max<size_t>(nbt, 1)));
+        HIP_TRY(c, hipMemset(s->d_pa.p, 0, std::max<size_t>(nbt, 1) * sizeof(float)));
+        if (!s->light_cand.empty() && !unified_units) {
+            std::vector<uint32_t> blob_of(nt), ids(nbt);
+            if (s->device_packed) HIP_TRY(c, hipMemcpy2D(ids.data(), 4, (const uint8_t *)s->d_tris.p + 12, 64, 4, nbt, hipMemcpyDeviceToHost)); // row 0 .w
+            else for (uint32_t j = 0; j < nbt; ++j) ids[j] = s->bvh.tris[j].id;
+            for (uint32_t j = 0; j < nbt; ++j) blob_of[ids[j]] = j;
+            uint32_t hi = 0; s->cand_lo = nbt;
+            std::vector<float> cv(s->light_cand.size() * 9);
+            for (size_t k = 0; k < s->light_cand.size(); ++k) {
+                const uint32_t b = blob_of[s->light_cand[k]];
+                s->cand_blob.push_back(b); s->cand_lo = std::min(s->cand_lo, b); hi = std::max(hi, b);
+                std::memcpy(&cv[k * 9], &s->verts[(size_t)s->light_cand[k] * 9], 9 * sizeof(float));
+            }
+            s->pa_span.assign(hi - s->cand_lo + 1u, 0.0f);
+            const pt_status st = build_lights(c, s, cv.data());
+            if (st != PT_OK) return st;
+        }
+        lap("light table");
+    }
 
     DeviceScene &d = s->ds;
     d.nodes = s->d_nodes.p; d.tris = s->d_tris.p; d.spheres = s->d_spheres.p; d.sph_mat = s->d_sph_mat.p; d.mats = s->d_mats.p;
@@ -713,6 +795,18 @@ static pt_status plan_frame(pt_context *c, const pt_scene *s, const pt_render_pa
     f.bucket = (p->flags & PT_FLAG_BUCKET_SPECULAR) != 0; f.split = f.bucket || (p->flags & PT_FLAG_SPLIT_KERNELS) != 0;
     f.forced = (p->flags & PT_FLAG_EXTEND_POOL) ? (uint32_t)EXT_POOL : (p->flags & PT_FLAG_EXTEND_PACKED) ? (uint32_t)EXT_PACKED
                : (p->flags & PT_FLAG_EXTEND_SIMPLE) ? (uint32_t)EXT_SIMPLE : t.extend_kernel;
+    // next-event estimation lives in the fused one-ray-per-lane kernel only. Its frames neither probe the extend kernel nor feed the
+    // scene's choice (a forced kernel does neither), and they have no visit counters: a shadow ray's traversal stops at its tmax, which
+    // §4.1's counters do not describe.
+    f.nee = (p->flags & PT_FLAG_NEXT_EVENT) != 0;
+    if (f.nee) {
+        if (f.split || f.forced == (uint32_t)EXT_PACKED || f.forced == (uint32_t)EXT_POOL)
+            return fail(c, PT_ERR_UNSUPPORTED, "PT_FLAG_NEXT_EVENT runs on the one-ray-per-lane kernel only: not with PT_FLAG_EXTEND_PACKED, "
+                                               "PT_FLAG_EXTEND_POOL, PT_FLAG_SPLIT_KERNELS, PT_FLAG_BUCKET_SPECULAR or pt_tuning.extend_kernel 2 / 3");
+        if (f.count) return fail(c, PT_ERR_UNSUPPORTED, "PT_FLAG_NEXT_EVENT does not count visits (PT_FLAG_COUNT_VISITS)");
+        if (s->unified) return fail(c, PT_ERR_UNSUPPORTED, "PT_FLAG_NEXT_EVENT: not for a scene committed under PTRT_UNIFIED");
+        f.forced = EXT_SIMPLE;
+    }
     // the fused one-ray-per-lane and lane-packing kernels build a slot's initial state in registers in their first launch; k_shade
     // (split pipelines) and the pooled kernel read it from memory
     f.full_state = f.split || f.forced == (uint32_t)EXT_POOL;
@@ -721,6 +815,9 @@ static pt_status plan_frame(pt_context *c, const pt_scene *s, const pt_render_pa
     f.packed_chunk = t.packed_chunk >= 64u ? t.packed_chunk : (f.streams >= 4u ? 256u : 128u);
     // path vertices per launch of the one-ray-per-lane kernel: 3/4 max_depth - 2 (saturating), clamped to [4, 12]
     const uint32_t v34 = p->max_depth * 3u / 4u; f.default_bounces = std::min(12u, std::max(4u, v34 > 2u ? v34 - 2u : 0u));
+    // NEE: `bounces` counts rays, and a vertex with a light sample takes two (shadow, then extension): twice the passes for about as many
+    // vertices per launch
+    if (f.nee) f.default_bounces *= 2u;
     // Iterations the host runs ahead of the queue sizes it reads back (pt_tuning.lag). The frame ends `lag` launches after its last path, on
     // grids sized `lag` iterations ago: short frames feel that (ms per 1080p frame with lag 4 / 3 / 2, tools/exp_lag.py: 1 spp 0.567 / 0.537 /
     // 0.529, 8 spp 2.79 / 2.73 / 2.70, glass 8 spp 1.57 / 1.52 / 1.48), long ones not (64 spp 17.73 / 17.68 / 17.73; a rank's 1/8 2.63 / 2.59 /
@@ -735,6 +832,8 @@ static pt_status plan_frame(pt_context *c, const pt_scene *s, const pt_render_pa
         if (c->acc_spp == 0 || c->acc_w != p->width || c->acc_h != p->height || c->acc_rank != p->rank || c->acc_nranks != f.nranks ||
             c->acc_streams != f.streams || c->acc_seed != p->seed)
             return fail(c, PT_ERR_INVALID_ARGUMENT, "PT_FLAG_ACCUMULATE needs a previous frame with the same size, rank, nranks, streams and seed");
+        if (c->acc_nee != f.nee)
+            return fail(c, PT_ERR_INVALID_ARGUMENT, "PT_FLAG_ACCUMULATE: the sums so far were made %s PT_FLAG_NEXT_EVENT", c->acc_nee ? "with" : "without");
         if (p->sample_offset != c->acc_spp) return fail(c, PT_ERR_INVALID_ARGUMENT, "PT_FLAG_ACCUMULATE: sample_offset must be %llu (samples so far)", (unsigned long long)c->acc_spp);
     }
     f.total_spp = (f.accumulate ? c->acc_spp : 0u) + p->spp; c->acc_spp = 0; // acc_spp: invalid until this frame completes
@@ -747,6 +846,10 @@ static pt_status plan_frame(pt_context *c, const pt_scene *s, const pt_render_pa
     if (!f.full_state) { HIP_TRY(c, c->q_init.ensure(f.q_entries)); HIP_TRY(c, c->cnt_init.ensure(kCntTotalWords)); }
     const uint32_t ovf = s->bvh.stack_need > kStackLds ? s->bvh.stack_need - kStackLds : 0u;
     if (ovf) HIP_TRY(c, c->stack_ovf.ensure((size_t)ovf * f.q_entries));
+    if (f.nee) {
+        HIP_TRY(c, c->nee_ext.ensure(f.n_slots)); HIP_TRY(c, c->nee_rad.ensure(f.n_slots));
+        f.nee_args = NeeArgs{ s->d_lights.p, s->d_cdf.p, s->d_pa.p, s->n_lights, c->nee_ext.p, c->nee_rad.p };
+    }
     if (f.nranks == 1) { const pt_status st = ensure_frame(c, p->width, p->height); if (st != PT_OK) return st; }
     PathState &ps = f.ps;
     ps.ray_o = c->ray_o.p; ps.ray_d = c->ray_d.p; ps.thr = c->thr.p; ps.sd = c->sd.p; ps.acc = c->acc.p; ps.q_ext[0] = c->q_ext0.p; ps.q_ext[1] = c->q_ext1.p;
@@ -819,7 +922,7 @@ static pt_status run_loops(pt_context *c, const pt_scene *s, const pt_render_par
         loops[g] = Loop{ n_loops == 1 ? q : c->group_stream[g], g * per_group, f.full_state ? f.shard_cap : c->init_bound, 0u, false }; // no shard's queue can outgrow its first one
         if (loops[g].stream != q) HIP_TRY(c, hipStreamWaitEvent(loops[g].stream, c->ev_fork, 0));
     }
-    const uint64_t max_iters = (uint64_t)p->spp * p->max_depth + kLag + 2;
+    const uint64_t max_iters = (uint64_t)p->spp * p->max_depth * (f.nee ? 2u : 1u) + kLag + 2; // NEE: up to two rays per vertex
     const bool trace = f.profile && getenv("PTRT_TRACE") != nullptr; // developer aid: per-iteration table on stderr
     // One kernel per iteration by default: every extend kernel (one ray per lane, lane-packing, pooled) shades its own hits (mode 0:
     // Lambert-only scene, lean code; 2: all kinds). PT_FLAG_SPLIT_KERNELS / _BUCKET_SPECULAR run k_shade as a second kernel.
@@ -841,7 +944,7 @@ static pt_status run_loops(pt_context *c, const pt_scene *s, const pt_render_par
             const bool probing = x.probing(g, it); const int kernel = x.launch_kernel(g, it, f.split);
             if (probing) HIP_TRY(c, hipEventRecord(c->ev_probe[(it - 2u) * 2u], L.stream));
             HIP_TRY(c, launch_extend(L.stream, s->ds, pg, f.fp, it, L.bound, f.count, kernel, f.packed_chunk, f.split ? -1 : shade_mode, f.compact,
-                                     c->tuning.bounces ? c->tuning.bounces : x.bounces(g, it, kernel, f.default_bounces)));
+                                     c->tuning.bounces ? c->tuning.bounces : x.bounces(g, it, kernel, f.default_bounces), f.nee ? &f.nee_args : nullptr));
             if (f.profile) HIP_TRY(c, hipEventRecord(e1, L.stream));
             if (f.bucket) {
                 HIP_TRY(c, launch_shade(L.stream, s->ds, pg, f.fp, it, L.bound, 0, true));
@@ -939,7 +1042,7 @@ static pt_status finish_frame(pt_context *c, const pt_render_params *p, const Fr
         out.other_ms = out.gpu_ms - out.extend_ms - out.shade_ms;
     }
     c->n_slots = f.pixel_slots; c->acc_w = p->width; c->acc_h = p->height; c->acc_rank = p->rank; c->acc_nranks = f.nranks; c->acc_streams = f.streams; c->acc_seed = p->seed;
-    c->acc_spp = f.total_spp; c->fb_valid = (f.nranks == 1);
+    c->acc_spp = f.total_spp; c->acc_nee = f.nee; c->fb_valid = (f.nranks == 1);
     if (stats) *stats = out;
     return PT_OK;
 }
@@ -1148,6 +1251,14 @@ static pt_status update_triangles(pt_scene *s, const void *verts9, uint64_t coun
     float ms = 0.f;
     HIP_TRY(c, hipEventElapsedTime(&ms, R.ev[0], R.ev[2]));
     out.gpu_ms = (double)ms + ms_check;
+    if (!s->pa_span.empty()) { // the light table from the new vertices of the candidates (same candidates: the materials stay)
+        const uint32_t lo = s->light_cand.front(), hi = s->light_cand.back(); // in triangle order
+        std::vector<float> span((size_t)(hi - lo + 1u) * 9u), cv(s->light_cand.size() * 9u);
+        if (host) std::memcpy(span.data(), (const float *)verts9 + (size_t)lo * 9u, span.size() * sizeof(float));
+        else HIP_TRY(c, hipMemcpy(span.data(), v + (size_t)lo * 9u, span.size() * sizeof(float), hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < s->light_cand.size(); ++k) std::memcpy(&cv[k * 9], &span[(size_t)(s->light_cand[k] - lo) * 9u], 9 * sizeof(float));
+        if ((st = build_lights(c, s, cv.data())) != PT_OK) return st;
+    }
     R.cur = nxt; s->verts_on_device = true;
     s->bvh.sah_cost = (float)sah;
     s->host_mirror = false;

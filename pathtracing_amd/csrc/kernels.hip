@@ -93,6 +93,17 @@ PT_DEV const ExtArgs &cold()
     asm volatile("" : "+s"(p));
     return *(const ExtArgs *)p;
 }
+// The arguments of a PT_FLAG_NEXT_EVENT launch: ExtArgs as every other extend kernel has them, the light table and the pending-shadow-ray
+// state behind them (ptrt_internal.h NeeArgs), read through cold_nee() like the rest of the cold arguments.
+struct ExtArgsNee : ExtArgs { NeeArgs nee; };
+template <bool NEE> struct ExtArgsOf { using type = ExtArgs; };
+template <> struct ExtArgsOf<true> { using type = ExtArgsNee; };
+PT_DEV const NeeArgs &cold_nee()
+{
+    auto p = __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return ((const ExtArgsNee *)p)->nee;
+}
 
 // Slot order. A slot is one (pixel slot, stream) pair; 64 consecutive slots are one 8x8 pixel block of one stream (a
 // wavefront). The K streams of a block are K consecutive 64-slot groups, so that wavefronts that run at the same time
@@ -388,6 +399,38 @@ PT_DEV void path_store(const PathState &ps, uint32_t slot, const PathRegs &r)
     at(ps.sd, slot) = (r.sample << 8) | r.depth;
 }
 
+// ------------------------------------------------------------------------------------------------ next-event estimation (docs/SPEC.md §7)
+// A lane of a PT_FLAG_NEXT_EVENT frame traces one ray per pass of the bounce loop: the extension ray of its path, or — after a Lambert
+// vertex that sampled a light — first the shadow ray toward the light point (r.o = the vertex's continuation origin, r.d = its
+// direction, t_best starts at its tmax) and in the pass after it the extension ray. The extension ray's direction and the radiance the
+// shadow ray brings if it reaches the light wait in NeeArgs::ext / ::rad; only `aux` and `flags` ride along in registers (and in the .w
+// words of ray_o / ray_d between launches).
+enum : uint32_t { NEE_PENDING = 1u, NEE_END = 2u }; // the ray in r.d is a shadow ray; the path ends once it is resolved
+struct NeeRegs {
+    float aux;      // NEE_PENDING: the shadow ray's tmax; else the Lambert pdf (cos / pi) of the extension ray in r.d, 0 = none
+    uint32_t flags;
+};
+constexpr float kInvPi = 0.318309873f; // f32(1 / pi)
+// The MIS weights of §7 are quotients of pdfs that may both underflow or overflow at grazing or point-blank configurations: NaN counts 0.
+PT_DEV float nan_to_zero(float w) { return w >= 0.0f ? w : 0.0f; }
+// The smallest i with u < cdf[i] (cdf non-decreasing, cdf[n - 1] = 1 > u).
+PT_DEV uint32_t pick_light(const float *cdf, uint32_t n, float u)
+{
+    uint32_t lo = 0, hi = n - 1u;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (u < cdf[mid]) hi = mid; else lo = mid + 1u;
+    }
+    return lo;
+}
+PT_DEV void path_store_nee(const PathState &ps, uint32_t slot, const PathRegs &r, const NeeRegs &nr)
+{
+    at(ps.ray_o, slot) = make_float4(r.o.x, r.o.y, r.o.z, __uint_as_float(nr.flags));
+    at(ps.ray_d, slot) = make_float4(r.d.x, r.d.y, r.d.z, nr.aux);
+    at(ps.thr, slot) = make_float4(r.T.x, r.T.y, r.T.z, __uint_as_float(r.key));
+    at(ps.sd, slot) = (r.sample << 8) | r.depth;
+}
+
 // The first sample of a slot's stream: stream k takes the samples s with (sample_offset + s) % K == k, in increasing s (docs/SPEC.md §5).
 PT_DEV uint32_t first_sample(uint32_t slot, const FrameParams &fp)
 {
@@ -446,9 +489,31 @@ __global__ void __launch_bounds__(kBlock) k_generate(DeviceScene sc, PathState p
 }
 
 
-template <int MODE>
+// The end of a path whose last vertex had a light sample (resolve_shadow): its stream's next sample of the pixel, regenerated in place as
+// shade_one does it, if there is one.
+PT_DEV bool next_sample(const DeviceScene &sc, const FrameParams &fp, uint32_t slot, PathRegs &r, uint32_t &depth)
+{
+    uint32_t &key = r.key, &sample = r.sample;
+    bool alive = false;
+    sample += fp.streams;
+    if (sample < fp.spp) {
+        uint32_t x = 0, y = 0;
+        slot_pixel(slot, fp, x, y);
+        key = path_key(fp.seed_hashed, y * fp.width + x, fp.sample_offset + sample);
+        camera_ray_of(sc.cam, x, y, key, r.o, r.d);
+        r.T = v3(1.f, 1.f, 1.f);
+        depth = 0;
+        alive = true;
+    }
+    return alive;
+}
+
+// NEE (k_extend<.., NEE> only): emission hits of light-set triangles after a Lambert vertex are weighted by w_b, and a Lambert vertex
+// below max_depth samples a light (from the T that arrived at it); a traced sample leaves the shadow ray in (r.o, r.d, nr->aux) with
+// NEE_PENDING set (and NEE_END when the path ends at this vertex), so that the caller's next pass resolves it (resolve_shadow).
+template <int MODE, bool NEE = false>
 PT_DEV bool shade_one(const DeviceScene &sc, const PathState &ps, const FrameParams &fp, uint32_t slot, PathRegs &r, float t, uint32_t ref,
-                      uint32_t b, uint32_t &defer)
+                      uint32_t b, uint32_t &defer, NeeRegs *nr = nullptr)
 {
     V3 &o = r.o, &d = r.d, &T = r.T;
     uint32_t &key = r.key, &sample = r.sample;
@@ -493,7 +558,20 @@ PT_DEV bool shade_one(const DeviceScene &sc, const PathState &ps, const FramePar
         const V3 alb = v3(m0.y, m0.z, m0.w), emi = xyz(m1);
         const uint32_t kind = __float_as_uint(m0.x);
         if (MODE == SHADE_QUEUE && kind != (uint32_t)PT_LAMBERT) { defer = 1u + kind; return false; } // shaded by k_shade<SHADE_BUCKETS>
-        if (emi.x != 0.0f || emi.y != 0.0f || emi.z != 0.0f) add(emi);
+        if (emi.x != 0.0f || emi.y != 0.0f || emi.z != 0.0f) {
+            if constexpr (NEE) { // §7 w_b: the ray left a Lambert vertex (aux = its pdf) and hit a light-set triangle (pa > 0)
+                V3 e = emi;
+                if (nr->aux > 0.0f && ref < sc.n_tris) {
+                    const float pa = cold_nee().pa[ref];
+                    if (pa > 0.0f) {
+                        const float pl = (pa * (t * t)) / __builtin_fabsf(dot(ng, d)), q = pl / nr->aux;
+                        const float w = nan_to_zero(1.0f / fma_(q, q, 1.0f));
+                        e = v3(emi.x * w, emi.y * w, emi.z * w);
+                    }
+                }
+                add(e);
+            } else add(emi);
+        }
         if (depth >= fp.max_depth) term = true;
         else {
             const uint32_t bb = depth - 1u;
@@ -504,9 +582,11 @@ PT_DEV bool shade_one(const DeviceScene &sc, const PathState &ps, const FramePar
             else bs = sample_dielectric(alb, m2.x, d, n, front, u01(key, 6u + 4u * bb));
             const V3 wi = bs.wi, W = bs.W;
             const float side = bs.side;
+            V3 ta = T; // NEE: T * albedo of a Lambert vertex (W = albedo), before Russian roulette
             if (!bs.ok) term = true;
             else {
                 T = v3(T.x * W.x, T.y * W.y, T.z * W.z);
+                ta = T;
                 if (!(fmax_(T.x, fmax_(T.y, T.z)) > 0.0f)) term = true;
                 else if (depth >= fp.rr_start) {
                     const float qrr = fmin_(fmax_(T.x, fmax_(T.y, T.z)), 0.95f);
@@ -514,6 +594,35 @@ PT_DEV bool shade_one(const DeviceScene &sc, const PathState &ps, const FramePar
                     else { const float iq = 1.0f / qrr; T = v3(T.x * iq, T.y * iq, T.z * iq); }
                 }
                 if (!term) { o = madd(side * fp.ray_eps, n, P); d = wi; }
+            }
+            if constexpr (NEE) {
+                const NeeArgs &na = cold_nee();
+                // the pdf of the extension ray, for the w_b of the emission it may find (Lambert vertices only)
+                if (!term) nr->aux = (bk == B_LAMBERT && na.n_lights) ? dot(n, wi) * kInvPi : 0.0f;
+                // §7 light sample of a Lambert vertex. Computed after the BSDF sample and Russian roulette to keep it out of their registers;
+                // its random numbers are its own (dimensions 1024 + 3b ..) and it uses only T * albedo of the T that arrived here.
+                if (bk == B_LAMBERT && na.n_lights) {
+                    const float4 *lr = na.lights + (size_t)pick_light(na.cdf, na.n_lights, u01(key, 1024u + 3u * bb)) * 4;
+                    const float4 l0 = lr[0], l1 = lr[1], l2 = lr[2];
+                    const float su = __builtin_sqrtf(u01(key, 1025u + 3u * bb)), b1 = 1.0f - su, b2 = u01(key, 1026u + 3u * bb) * su;
+                    const V3 x = v3(fma_(b2, l2.x, fma_(b1, l1.x, l0.x)), fma_(b2, l2.y, fma_(b1, l1.y, l0.y)), fma_(b2, l2.z, fma_(b1, l1.z, l0.z)));
+                    const V3 so = madd(fp.ray_eps, n, P); // the continuation origin of a Lambert vertex (side +1)
+                    const V3 dl = x - so;
+                    const float dist2 = dot(dl, dl), dist = __builtin_sqrtf(dist2), inv = 1.0f / dist;
+                    const V3 sd = v3(dl.x * inv, dl.y * inv, dl.z * inv);
+                    const float4 l3 = lr[3];
+                    const float cs = dot(n, sd), cl = __builtin_fabsf(dot(xyz(l3), sd));
+                    if (cs > 0.0f && cl > 0.0f) { // the shadow ray goes first; the extension ray (if the path goes on) waits in NeeArgs::ext
+                        const float pl = (l0.w * dist2) / cl, q = (cs * kInvPi) / pl;
+                        const float f = nan_to_zero(q / fma_(q, q, 1.0f)); // w_l * pdf_bsdf / pdf_light
+                        at(na.rad, slot) = make_float4((ta.x * f) * l1.w, (ta.y * f) * l2.w, (ta.z * f) * l3.w, 0.0f);
+                        if (!term) at(na.ext, slot) = make_float4(d.x, d.y, d.z, nr->aux);
+                        nr->flags = NEE_PENDING | (term ? NEE_END : 0u);
+                        nr->aux = dist * 0.9999f;
+                        o = so; d = sd;
+                        term = false;
+                    }
+                }
             }
         }
     }
@@ -531,9 +640,28 @@ PT_DEV bool shade_one(const DeviceScene &sc, const PathState &ps, const FramePar
             depth = 0;
             alive = true;
         }
+        if constexpr (NEE) nr->aux = 0.0f; // a camera ray: its emission hits keep weight 1
     } else alive = true;
     if (touched) at(ps.acc, slot) = A;
     r.depth = depth;
+    return alive;
+}
+
+// NEE: the pass after a light sample. A shadow ray that found nothing with t <= tmax adds its radiance (§7); then the path either
+// ends (NEE_END: the vertex's Russian roulette or max_depth ended it) or continues with the extension ray that waited in NeeArgs::ext.
+PT_DEV bool resolve_shadow(const DeviceScene &sc, const PathState &ps, const FrameParams &fp, const NeeArgs &na, uint32_t slot, PathRegs &r,
+                           NeeRegs &nr, bool visible)
+{
+    const bool end = (nr.flags & NEE_END) != 0u;
+    bool alive = true;
+    if (visible || end) {
+        float4 A = at(ps.acc, slot);
+        if (visible) { const float4 L = at(na.rad, slot); A.x = A.x + L.x; A.y = A.y + L.y; A.z = A.z + L.z; }
+        if (end) { A.w += 1.0f; alive = next_sample(sc, fp, slot, r, r.depth); nr.aux = 0.0f; }
+        at(ps.acc, slot) = A;
+    }
+    if (!end) { const float4 e = at(na.ext, slot); r.d = xyz(e); nr.aux = e.w; }
+    nr.flags = 0u;
     return alive;
 }
 
@@ -606,6 +734,12 @@ PT_DEV void queue_next(const PathState &ps, uint32_t shard, uint32_t cnext, uint
 #ifndef PT_EXT_WAVES
 #define PT_EXT_WAVES(L, FUSE) (((L) == PT_BVH_WIDTH_4Q || (L) == PT_BVH_WIDTH_2) && (FUSE) != SHADE_INLINE ? 8 : 7)
 #endif
+// The NEE instantiations (docs/SPEC.md §7) hold the light sample on top of the path: 80 VGPRs = 6 waves, 72 = 7 for the Lambert-only
+// shading of the 2- and 4-wide layouts (at 7 waves the others spill 6-13 VGPRs to scratch). None of them spills at these budgets.
+#ifndef PT_EXT_WAVES_NEE
+#define PT_EXT_WAVES_NEE(L, FUSE) ((FUSE) == SHADE_QUEUE && (L) != PT_BVH_WIDTH_8Q && (L) != PT_BVH_WIDTH_8O ? 7 : 6)
+#endif
+#define PT_EXT_WAVES_OF(L, FUSE, NEE) ((NEE) ? PT_EXT_WAVES_NEE(L, FUSE) : PT_EXT_WAVES(L, FUSE))
 // A lane's traversal stack: kStackLds entries in its LDS column ([level][lane]: conflict-free), the rest in a global
 // overflow column sized by the builder's exact worst case (pt_bvh_info.stack_need).
 struct StackCtx { int32_t *lds; uint32_t stride, tid, col; }; // col: the lane's column of the overflow area, unique per thread of a launch
@@ -793,15 +927,19 @@ PT_DEV void flush_visit_counters(const PathState &ps, const VisitCounts &v)
     add(kCntSph, v.sph);
 }
 
-template <int L, bool COUNT, int FUSE>
-__global__ void __launch_bounds__(kExtBlock) __attribute__((amdgpu_waves_per_eu(PT_EXT_WAVES(L, FUSE), PT_EXT_WAVES(L, FUSE)))) k_extend(ExtArgs a)
+// NEE (PT_FLAG_NEXT_EVENT; fused, not counting): one ray per lane per pass, a shadow ray or an extension ray (see NeeRegs); `bounces`
+// then counts passes.
+template <int L, bool COUNT, int FUSE, bool NEE = false>
+__global__ void __launch_bounds__(kExtBlock) __attribute__((amdgpu_waves_per_eu(PT_EXT_WAVES_OF(L, FUSE, NEE), PT_EXT_WAVES_OF(L, FUSE, NEE))))
+k_extend(typename ExtArgsOf<NEE>::type a)
 {
+    static_assert(!NEE || (FUSE != SHADE_NONE && !COUNT), "NEE: fused shading, no visit counters");
     // hot arguments (stay in SGPRs across the traversal loop); everything else goes through cold()
     const float4 *__restrict__ nodes = a.sc.nodes, *__restrict__ tris = a.sc.tris, *__restrict__ spheres = a.sc.spheres;
     const uint32_t n_spheres = a.sc.n_spheres, n_tris = a.sc.n_tris, n_nodes = a.sc.n_nodes;
     const uint32_t it = a.it;
     __shared__ int32_t s_stack[kStackLds * kExtBlock];
-    __shared__ uint32_t s_stash[(FUSE != SHADE_NONE ? 5 : 1) * kExtBlock];
+    __shared__ uint32_t s_stash[(FUSE != SHADE_NONE ? (NEE ? 7 : 5) : 1) * kExtBlock];
     const uint32_t tid = threadIdx.x;
     ExtHead hd;
     uint32_t gid, qbase, slot = kInvalidSlot, n_bounces; // qbase: first entry of this shard's region of the queues (see at())
@@ -830,6 +968,7 @@ __global__ void __launch_bounds__(kExtBlock) __attribute__((amdgpu_waves_per_eu(
     __shared__ int32_t s_state[COUNT ? 64 : 1]; // COUNT diagnostics: every lane's `cur` (1 = no ray), readable by the lane that counts
     PathRegs r;
     r.o = v3(0.f, 0.f, 0.f); r.d = v3(0.f, 0.f, 1.f); r.T = v3(0.f, 0.f, 0.f); r.key = r.sample = r.depth = 0u;
+    NeeRegs nr{ 0.0f, 0u };
     if (active) {
         const PathState &ps = cold().ps;
         if (FUSE == SHADE_NONE) { r.o = xyz(at(ps.ray_o, slot)); r.d = xyz(at(ps.ray_d, slot)); }
@@ -837,7 +976,10 @@ __global__ void __launch_bounds__(kExtBlock) __attribute__((amdgpu_waves_per_eu(
             path_init(cold().sc, cold().fp, slot, r);
             if (!cold().fp.accumulate) at(ps.acc, slot) = make_float4(0.f, 0.f, 0.f, 0.f);
         }
-        else path_load(ps, slot, r);
+        else {
+            path_load(ps, slot, r);
+            if constexpr (NEE) { nr.flags = __float_as_uint(at(ps.ray_o, slot).w); nr.aux = at(ps.ray_d, slot).w; }
+        }
     }
     bool alive = active;
     uint32_t wave_rays = 0;
@@ -848,8 +990,12 @@ __global__ void __launch_bounds__(kExtBlock) __attribute__((amdgpu_waves_per_eu(
     if (COUNT && kExtBlock == 64u) { s_state[tid] = alive ? 0 : 1; __syncthreads(); } // 1: neither a node, a leaf nor PT_BVH_EMPTY
     if (alive) {
         const V3 o = r.o, d = r.d;
-        Hit h{ __builtin_inff(), PT_MISS, PT_MISS };
+        Hit h{ (NEE && (nr.flags & NEE_PENDING)) ? nr.aux : __builtin_inff(), PT_MISS, PT_MISS }; // a shadow ray: §4.2 with its tmax
         if (FUSE != SHADE_NONE) stash_park(s_stash, kExtBlock, tid, r);
+        if constexpr (NEE) {
+            s_stash[5 * kExtBlock + tid] = __float_as_uint(nr.aux); s_stash[6 * kExtBlock + tid] = nr.flags;
+            asm volatile("" ::: "memory");
+        }
 
         { const uint32_t ns = spheres_test(spheres, n_spheres, n_tris, o, d, h); if (COUNT) vc.sph += ns; }
 
@@ -901,6 +1047,11 @@ __global__ void __launch_bounds__(kExtBlock) __attribute__((amdgpu_waves_per_eu(
             stash_restore(s_stash, kExtBlock, tid, r);
             uint32_t defer = 0u;
             const ExtArgs &c = cold();
+            if constexpr (NEE) {
+                nr.aux = __uint_as_float(s_stash[5 * kExtBlock + tid]); nr.flags = s_stash[6 * kExtBlock + tid];
+                if (nr.flags & NEE_PENDING) alive = resolve_shadow(c.sc, c.ps, c.fp, cold_nee(), slot, r, nr, h.ref == PT_MISS);
+                else alive = shade_one<FUSE, true>(c.sc, c.ps, c.fp, slot, r, h.t, h.ref, B_LAMBERT, defer, &nr);
+            } else
             alive = shade_one<FUSE>(c.sc, c.ps, c.fp, slot, r, h.t, h.ref, B_LAMBERT, defer);
         }
     }
@@ -908,7 +1059,7 @@ __global__ void __launch_bounds__(kExtBlock) __attribute__((amdgpu_waves_per_eu(
     const PathState &ps = cold().ps;
     if (COUNT && active) flush_visit_counters(ps, vc);
     if (FUSE != SHADE_NONE) {
-        if (alive) path_store(ps, slot, r);
+        if (alive) { if constexpr (NEE) path_store_nee(ps, slot, r, nr); else path_store(ps, slot, r); }
         queue_next(ps, shard, hd.cnext, &at(ps.q_ext[parity ^ 1u], qbase), gid, n, alive, slot, hd.do_compact);
         if (wave_rays && lane_id() == 0u) atomicAdd(traced_counter(ps, hd.cnext, shard), (unsigned long long)wave_rays);
     }
@@ -1449,8 +1600,15 @@ static void extend_lc(hipStream_t s, dim3 grid, const ExtArgs &a, int kernel, in
     else hipLaunchKernelGGL((k_extend<L, C, SHADE_NONE>), grid, dim3(kExtBlock), 0, s, a);
 }
 
+template <int L>
+static void extend_nee(hipStream_t s, dim3 grid, const ExtArgsNee &a, int fuse)
+{
+    if (fuse == SHADE_INLINE) hipLaunchKernelGGL((k_extend<L, false, SHADE_INLINE, true>), grid, dim3(kExtBlock), 0, s, a);
+    else hipLaunchKernelGGL((k_extend<L, false, SHADE_QUEUE, true>), grid, dim3(kExtBlock), 0, s, a);
+}
+
 hipError_t launch_extend(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp, uint32_t it, uint32_t shard_bound, bool count,
-                         int kernel, uint32_t packed_chunk, int fuse, bool compact, uint32_t bounces)
+                         int kernel, uint32_t packed_chunk, int fuse, bool compact, uint32_t bounces, const NeeArgs *nee)
 {
     // kernel: EXT_SIMPLE one ray per lane; EXT_PACKED a wavefront owns `packed_chunk` (>= 64) queue entries and refills idle lanes,
     // shading each finished ray on the spot; EXT_POOL a wavefront owns kPool entries, refills idle lanes during traversal and shades
@@ -1461,6 +1619,20 @@ hipError_t launch_extend(hipStream_t s, const DeviceScene &sc, const PathState &
     const dim3 grid = shard_grid(shard_bound ? (shard_bound + per_block - 1) / per_block : 1u, ps.shard_count);
     ExtArgs a;
     a.sc = sc; a.ps = ps; a.fp = fp; a.it = it; a.compact = compact ? 1u : 0u; a.bounces = bounces ? bounces : 1u; a.chunk = chunk;
+    if (nee) { // the one-ray-per-lane kernel, fused, not counting (api.cpp refuses every other combination before it gets here)
+        if (kernel != EXT_SIMPLE || count || fuse == SHADE_NONE) return hipErrorInvalidValue;
+        ExtArgsNee an;
+        static_cast<ExtArgs &>(an) = a; an.nee = *nee;
+        switch (sc.bvh_width) {
+        case PT_BVH_WIDTH_2: extend_nee<PT_BVH_WIDTH_2>(s, grid, an, fuse); break;
+        case PT_BVH_WIDTH_4: extend_nee<PT_BVH_WIDTH_4>(s, grid, an, fuse); break;
+        case PT_BVH_WIDTH_4Q: extend_nee<PT_BVH_WIDTH_4Q>(s, grid, an, fuse); break;
+        case PT_BVH_WIDTH_8Q: extend_nee<PT_BVH_WIDTH_8Q>(s, grid, an, fuse); break;
+        case PT_BVH_WIDTH_8O: extend_nee<PT_BVH_WIDTH_8O>(s, grid, an, fuse); break;
+        default: return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
+    }
     switch (sc.bvh_width) {
     case PT_BVH_WIDTH_2:  count ? extend_lc<PT_BVH_WIDTH_2, true>(s, grid, a, kernel, fuse) : extend_lc<PT_BVH_WIDTH_2, false>(s, grid, a, kernel, fuse); break;
     case PT_BVH_WIDTH_4:  count ? extend_lc<PT_BVH_WIDTH_4, true>(s, grid, a, kernel, fuse) : extend_lc<PT_BVH_WIDTH_4, false>(s, grid, a, kernel, fuse); break;

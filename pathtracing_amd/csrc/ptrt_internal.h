@@ -118,6 +118,19 @@ struct PathState {           // SoA over slots
     uint32_t ring_slots;
 };
 
+// Next-event estimation (PT_FLAG_NEXT_EVENT, docs/SPEC.md §7): the light table of the committed scene (api.cpp build_lights) and the
+// per-slot state a pending shadow ray leaves behind. A separate block behind ExtArgs (kernels.hip ExtArgsNee) rather than fields of
+// DeviceScene / PathState: those sit in the kernarg segment of every extend kernel, and growing them would move the offsets every other
+// kernel loads its arguments from.
+struct NeeArgs {
+    const float4 *lights;  // 4 rows per light, in light order: v0|pa, e1|Le.r, e2|Le.g, n_l|Le.b (pa = pmf / area, n_l = the shading row)
+    const float *cdf;      // n_lights entries, the last one 1.0f
+    const float *pa;       // per blob triangle: pa of the light it is, 0 for every other triangle (read on emissive hits only)
+    uint32_t n_lights;
+    float4 *ext;           // per slot, while a shadow ray is pending: the extension ray's direction | its Lambert pdf
+    float4 *rad;           // per slot, while a shadow ray is pending: the radiance the shadow ray adds if it reaches the light | -
+};
+
 struct FrameParams {
     uint32_t width, height, spp, max_depth, rr_start, seed_hashed, sample_offset;
     float ray_eps;
@@ -154,8 +167,9 @@ hipError_t launch_generate(hipStream_t s, const DeviceScene &sc, const PathState
 // kernel: ExtendKernel. fuse: -1 = extend only (k_shade follows); 0 / 2 = the kernel also shades (Lambert-only / all kinds) and
 // queues the next iteration, honouring `compact` like launch_shade. packed_chunk: queue entries per wavefront of EXT_PACKED.
 // bounces (fused only): path vertices a lane advances per launch.
+// nee (may be NULL): a PT_FLAG_NEXT_EVENT frame; only the one-ray-per-lane kernel, fused (fuse 0 / 2), without counting, has it.
 hipError_t launch_extend(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp, uint32_t it, uint32_t shard_bound, bool count,
-                         int kernel, uint32_t packed_chunk, int fuse, bool compact, uint32_t bounces);
+                         int kernel, uint32_t packed_chunk, int fuse, bool compact, uint32_t bounces, const NeeArgs *nee = nullptr);
 // mode: 0 = queue order, specular kinds deferred to buckets; 1 = the specular buckets; 2 = queue order, everything shaded in place
 // compact: 1 = survivors are appended densely to the next queue (ballot + one returning atomic per wavefront);
 //          0 = every lane writes its own position of the next queue (slot or kInvalidSlot): no returning atomics, and the

@@ -1,0 +1,134 @@
+"""Next-event estimation (docs/SPEC.md §7) without a GPU: the scalar checker of tests/nee_ref/ against the brute-force path tracer
+of the oracle, the exact structural properties of §7, and the flag's plumbing through the header and the bindings.
+
+The checker writes its own light table, light sampling, MIS and accumulation from the spec; it shares only §7's unchanged pieces
+(closest hit, BSDF sample, camera ray, RNG) with oracle/. The device is held to it bit for bit by tests/test_gpu_nee.py."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+import nee_checker as nc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+S = 32       # image side
+SPP = 2048   # samples per pixel of the statistical tests
+Z = 4.0      # the statistical tests' bound, in standard deviations
+
+
+@pytest.fixture(scope="session", autouse=True)
+def _checker():
+    nc.build()
+
+
+def moments(P, pto, sd, flags, spp=SPP):
+    """(per-pixel mean, per-pixel sample variance of one sample's radiance, stats) of the checker at S x S."""
+    params = P.make_params(S, S, spp=spp, max_depth=8, streams=1, seed=11)
+    img, st, sq = nc.render(pto, pto.Scene(sd), params, flags=flags, with_sq=True)
+    m = img[..., :3].astype(np.float64)
+    return m, (sq / spp - m * m) * spp / (spp - 1), st
+
+
+def max_z(a, b, spp=SPP):
+    """Largest |z| of the difference of two independent estimates: over the whole image and over its 8 x 8-pixel blocks, per channel."""
+    d, v = a[0] - b[0], (a[1] + b[1]) / spp
+    zs = [np.abs(d.sum((0, 1))) / np.sqrt(v.sum((0, 1)))]
+    for by in range(0, S, 8):
+        for bx in range(0, S, 8):
+            zs.append(np.abs(d[by:by + 8, bx:bx + 8].sum((0, 1))) / np.sqrt(v[by:by + 8, bx:bx + 8].sum((0, 1))))
+    return float(np.max(zs))
+
+
+def scene(P, name):
+    N = P.native
+    if name == "cornell":
+        return P.make_scene(N.PT_SCENE_CORNELL, 0, 3, S, S)
+    if name == "glass":
+        return P.make_scene(N.PT_SCENE_CORNELL_GLASS, 0, 3, S, S)
+    return nc.two_lights_scene(P, S, S)
+
+
+@pytest.fixture(scope="module")
+def brute(P, pto):
+    """The plain estimator (§5) of each scene: the checker without NEE, which is pto_render bit for bit."""
+    out = {}
+    for name in ("cornell", "glass", "two"):
+        sd = scene(P, name)
+        m, v, st = moments(P, pto, sd, 0)
+        ref, ost = pto.render(pto.Scene(sd), P.make_params(S, S, spp=SPP, max_depth=8, streams=1, seed=11))
+        assert np.array_equal(m, ref[..., :3].astype(np.float64)) and st.ext_rays == ost.rays and st.shadow_rays == 0, name
+        out[name] = (m, v)
+    return out
+
+
+@pytest.mark.parametrize("name", ["cornell", "glass", "two"])
+def test_nee_is_unbiased(P, pto, brute, name):
+    """NEE's mean equals the brute-force mean within 4 sigma, over the image and over blocks."""
+    m, v, st = moments(P, pto, scene(P, name), nc.NEE)
+    assert st.shadow_rays > 0
+    assert max_z((m, v), brute[name]) < Z, name
+
+
+@pytest.mark.parametrize("name,flags", [("cornell", nc.NO_MIS), ("glass", nc.NO_MIS), ("cornell", nc.NO_COSL), ("glass", nc.NO_COSL),
+                                        ("two", nc.SWAP_PMF)])
+def test_negative_controls_fail(P, pto, brute, name, flags):
+    """The same test catches the mistakes it is there for: no MIS weights (direct light counted twice), cos_l left out of the light
+    pdf, and the pmfs of a two-light scene swapped."""
+    m, v, _ = moments(P, pto, scene(P, name), nc.NEE | flags)
+    assert max_z((m, v), brute[name]) > 5 * Z, (name, flags)
+
+
+def test_variance_is_lower(P, pto, brute):
+    """At equal spp on C1, NEE's per-pixel variance is lower (measured: 3.4x on average over the pixels)."""
+    _, v, _ = moments(P, pto, scene(P, "cornell"), nc.NEE)
+    ratio = brute["cornell"][1].mean() / v.mean()
+    assert ratio >= 2.0, ratio
+
+
+def test_no_emissive_triangle_is_the_plain_frame(P, pto):
+    """C3 (a sky-lit soup, no emissive triangle): the NEE frame is the plain frame bit for bit, with the same rays."""
+    sd = P.make_scene(P.native.PT_SCENE_TRIANGLE_SOUP, 300, 3, S, S)
+    params = P.make_params(S, S, spp=16, max_depth=8, streams=4)
+    plain, ps, _ = nc.render(pto, pto.Scene(sd), params, flags=0)
+    nee, st, _ = nc.render(pto, pto.Scene(sd), params, flags=nc.NEE)
+    assert st.n_lights == 0 and st.shadow_rays == 0 and st.ext_rays == ps.ext_rays
+    assert np.array_equal(nee, plain)
+
+
+@pytest.mark.parametrize("name", ["cornell", "glass", "lights", "grazing"])
+def test_extension_rays_are_the_plain_rays(P, pto, name):
+    """§7 draws its random numbers from dimensions of its own, so the BSDF-sampled paths are the plain ones: the extension rays of a
+    NEE frame are the plain frame's rays (pto_render's count)."""
+    sd = {"lights": lambda: nc.many_lights_scene(P, S, S), "grazing": lambda: nc.grazing_scene(P, S, S)}.get(name, lambda: scene(P, name))()
+    params = P.make_params(S, S, spp=8, max_depth=8, streams=2)
+    _, ost = pto.render(pto.Scene(sd), params)
+    _, st, _ = nc.render(pto, pto.Scene(sd), params)
+    assert st.ext_rays == ost.rays and st.shadow_rays > 0
+
+
+def test_grazing_and_point_blank_stay_finite(P, pto):
+    """Lights edge-on on the floor, a hair above it, flush with the back wall and inside ray_eps: no NaN or Inf anywhere."""
+    sd = nc.grazing_scene(P, S, S)
+    for eps in (1e-4, 0.0):
+        params = P.make_params(S, S, spp=64, max_depth=8, streams=2, ray_eps=eps)
+        img, st, sq = nc.render(pto, pto.Scene(sd), params, with_sq=True)
+        assert st.n_lights == 6 and st.shadow_rays > 0  # the four and the ceiling quad
+        assert np.isfinite(img).all() and np.isfinite(sq).all(), eps
+
+
+def test_flag_plumbing(P):
+    """PT_FLAG_NEXT_EVENT = 256 in the header, the Python binding and the C# binding."""
+    hdr = open(os.path.join(ROOT, "include", "ptrt.h")).read()
+    assert re.search(r"PT_FLAG_NEXT_EVENT\s*=\s*256u", hdr)
+    assert P.native.PT_FLAG_NEXT_EVENT == 256
+    cs = open(os.path.join(ROOT, "host", "csharp", "PtrtNative.cs")).read()
+    assert re.search(r"\bNextEvent\s*=\s*256\b", cs)
+
+
+def test_product_does_not_reference_the_checker():
+    for dirpath, _, files in os.walk(os.path.join(ROOT, "pathtracing_amd")):
+        for f in files:
+            if f.endswith((".py", ".cpp", ".h", ".hip", "Makefile")):
+                txt = open(os.path.join(dirpath, f), errors="replace").read()
+                assert "nee_ref" not in txt and "nee_checker" not in txt and "nr_render" not in txt, f
