@@ -1,12 +1,15 @@
 // ptrt_cli — headless counterpart of Program.cs / App.Run (RayTracing/Program.cs:1-9, App.cs:15-21):
 // build a renderer, render N frames, write the image the reference would have shown in its window.
 //   ptrt_cli [--scene reference|cornell|glass|soup|tess] [--detail N] [--size WxH] [--spp N] [--depth N]
-//            [--frames N] [--ppm out.ppm] [--pfm out.pfm] [--gpus N] [--virtual 0|1|2] [--nee]
+//            [--frames N] [--ppm out.ppm] [--pfm out.pfm] [--gpus N] [--virtual 0|1|2] [--nee] [--denoise N]
 // --nee: next-event estimation (PT_FLAG_NEXT_EVENT, docs/SPEC.md §7).
+// --denoise N: denoise the last frame with N filter passes (0 = the default; docs/SPEC.md §8) and write the denoised image to --ppm /
+// --pfm instead of the frame (the PPM by SPEC §1's unorm8 rule).
 // --gpus N: the frame's tiles over N devices of this node, one RCCL gather per frame (pt_comm); with --virtual 1 the N ranks are
 // rendered one after the other on device 0 (rehearsal of the partition on a single GPU); with --virtual 2 every rank has its own
 // context on device 0, the ranks render concurrently (one host thread each) and exchange their tiles by device copies.
 #include "ptrt_host.hpp"
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -16,6 +19,7 @@ int main(int argc, char **argv)
 {
     std::string scene = "reference", ppm = "frame.ppm", pfm;
     uint32_t w = 1920, h = 1080, detail = 0, spp = 64, depth = 8, frames = 1, gpus = 1, virt = 0, flags = 0;
+    int denoise = -1; // filter passes of --denoise (0 = default); -1 = no denoise
     for (int i = 1; i < argc; i += 2) {
         const std::string a = argv[i];
         if (a == "--nee") { flags |= PT_FLAG_NEXT_EVENT; --i; continue; } // a switch: no value
@@ -30,6 +34,7 @@ int main(int argc, char **argv)
         else if (a == "--virtual") virt = (uint32_t)std::atoi(argv[i + 1]);
         else if (a == "--ppm") ppm = argv[i + 1];
         else if (a == "--pfm") pfm = argv[i + 1];
+        else if (a == "--denoise") denoise = std::atoi(argv[i + 1]);
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     try {
@@ -58,8 +63,21 @@ int main(int argc, char **argv)
             std::printf("%llu rays, %.3f ms, %.1f Mrays/s\n", (unsigned long long)s.rays, s.gpu_ms, s.rays / s.gpu_ms / 1e3);
         }
         ptrt_host::Renderer &r = multi ? multi->Root() : *single;
+        std::vector<float> denoised;
+        if (denoise >= 0) {
+            const pt_stats d = r.Denoise((uint32_t)denoise);
+            std::printf("denoise: %u passes, guides %.3f ms, filter %.3f ms\n", d.iterations, d.extend_ms, d.other_ms);
+            denoised = r.ReadDenoised();
+        }
         if (!ppm.empty()) { // 8-bit image = the reference's R8G8B8A8Unorm storage image (Renderer.cs:124)
-            const auto px = r.ReadFramebufferRgba8();
+            std::vector<uint8_t> px;
+            if (denoise >= 0) { // the same rule on the host: docs/SPEC.md §1 unorm8 (NaN -> 0)
+                px.resize(denoised.size());
+                for (size_t i = 0; i < px.size(); ++i) {
+                    const float c = denoised[i];
+                    px[i] = !(c > 0.0f) ? 0 : c >= 1.0f ? 255 : (uint8_t)std::floor(c * 255.0f + 0.5f);
+                }
+            } else px = r.ReadFramebufferRgba8();
             FILE *f = std::fopen(ppm.c_str(), "wb");
             if (!f) throw std::runtime_error("cannot open " + ppm);
             std::fprintf(f, "P6\n%u %u\n255\n", w, h);
@@ -67,7 +85,7 @@ int main(int argc, char **argv)
             std::fclose(f);
         }
         if (!pfm.empty()) { // linear float radiance, bottom-up rows, little endian
-            const auto px = r.ReadFramebuffer();
+            const auto px = denoise >= 0 ? denoised : r.ReadFramebuffer();
             FILE *f = std::fopen(pfm.c_str(), "wb");
             if (!f) throw std::runtime_error("cannot open " + pfm);
             std::fprintf(f, "PF\n%u %u\n-1.0\n", w, h);

@@ -69,6 +69,20 @@ public:
         check(pt_framebuffer_read_rgba8(ctx_, px.data(), px.size()), ctx_);
         return px;
     }
+    // docs/SPEC.md §8: guides on the current scene, then the edge-aware à-trous filter over the last frame (iterations 0 = default)
+    pt_stats Denoise(uint32_t iterations = 0, uint32_t flags = 0)
+    {
+        pt_denoise_params dp{}; dp.iterations = iterations; dp.flags = flags;
+        pt_stats st{};
+        check(pt_denoise(ctx_, scene_, &dp, &st), ctx_);
+        return st;
+    }
+    std::vector<float> ReadDenoised()
+    {
+        std::vector<float> px((size_t)Params.width * Params.height * 4);
+        check(pt_denoised_read(ctx_, px.data(), px.size()), ctx_);
+        return px;
+    }
     void Dispose()
     {
         if (scene_) pt_scene_destroy(scene_);

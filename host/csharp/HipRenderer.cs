@@ -124,6 +124,35 @@ public unsafe class HipRenderer : IDisposable
         return st;
     }
 
+    // Denoise the last frame (docs/SPEC.md §8): first-hit guides traced on the current scene, then the edge-aware à-trous filter.
+    // Zeros mean the defaults. The framebuffer and the accumulated sums stay as they are; ReadDenoised / ReadGuides hold until the
+    // next Render. Returns the stats (extend_ms = guide pass, other_ms = filter passes).
+    public PtStats Denoise(uint iterations = 0, float sigmaColor = 0f, float sigmaNormal = 0f, float sigmaDepth = 0f, float sigmaAlbedo = 0f,
+                           bool guidesOnly = false, bool edgeStops = true)
+    {
+        var dp = new PtDenoiseParams { iterations = iterations, sigma_color = sigmaColor, sigma_normal = sigmaNormal, sigma_depth = sigmaDepth,
+                                       sigma_albedo = sigmaAlbedo,
+                                       flags = (guidesOnly ? (uint)PtDenoiseFlags.GuidesOnly : 0u) | (edgeStops ? 0u : (uint)PtDenoiseFlags.NoEdgeStops) };
+        PtStats st;
+        Ptrt.Check(Ptrt.pt_denoise(_ctx, _scene, &dp, &st), _ctx);
+        return st;
+    }
+
+    public float[] ReadDenoised()
+    {
+        float[] rgba = new float[(ulong)Width * Height * 4];
+        fixed (float* p = rgba) Ptrt.Check(Ptrt.pt_denoised_read(_ctx, p, (ulong)rgba.Length), _ctx);
+        return rgba;
+    }
+
+    // 8 floats per pixel: front-facing normal, t, albedo, prim id bits (a miss: t = +inf, id 0xFFFFFFFF) — a host denoiser's features
+    public float[] ReadGuides()
+    {
+        float[] g = new float[(ulong)Width * Height * 8];
+        fixed (float* p = g) Ptrt.Check(Ptrt.pt_guides_read(_ctx, p, (ulong)g.Length), _ctx);
+        return g;
+    }
+
     internal void* Context => _ctx;
     internal void* Scene => _scene;
 

@@ -30,8 +30,9 @@ extern "C" {
 
 /* 2: pt_tuning grew to 40 bytes (extend_kernel, readback); pt_comm_*, pt_framebuffer_read_srgb8, PT_FLAG_EXTEND_POOL, pt_bvh_info.stack_need and
  * the BVH2 default for small scenes had arrived under version 1. pt_trace_rays and PT_TRACE_* arrived later under version 2, and after them
- * pt_scene_update_triangles / pt_scene_update_spheres and PT_UPDATE_HOST_MEMORY, then PT_FLAG_NEXT_EVENT (additions only: no struct or existing
- * signature changed). Hosts compare pt_abi_version() with the header they were built against. */
+ * pt_scene_update_triangles / pt_scene_update_spheres and PT_UPDATE_HOST_MEMORY, then PT_FLAG_NEXT_EVENT, then pt_denoise, pt_denoise_params,
+ * PT_DENOISE_*, pt_denoised_read / pt_denoised_device_ptr and pt_guides_read (additions only: no struct or existing signature changed).
+ * Hosts compare pt_abi_version() with the header they were built against. */
 #define PTRT_ABI_VERSION 2
 
 typedef int32_t pt_status;
@@ -254,6 +255,41 @@ pt_status pt_scene_update_triangles(pt_scene *s, const void *verts9, uint64_t co
 /* New centres and radii for the committed spheres (host memory, 4 floats each, same count); materials stay. Bad spheres as
  * pt_scene_set_spheres defines them are PT_ERR_INVALID_ARGUMENT. */
 pt_status pt_scene_update_spheres(pt_scene *s, const float *cxyzr, uint64_t count);
+
+/* ---- denoising (docs/SPEC.md §8): the first-hit guide buffers of the assembled frame and an edge-aware à-trous filter over it (Dammertz
+ *      et al. 2010) — what turns the few-sample frames of a render-every-frame loop (App.cs:39-42) into a watchable picture, or what a host's
+ *      own denoiser needs (pt_guides_read). */
+/* pt_denoise_params.flags */
+enum {
+    PT_DENOISE_GUIDES_ONLY = 1u,  /* trace and store the guides only: no filter pass, no denoised image */
+    PT_DENOISE_NO_EDGE_STOPS = 2u /* every edge-stop weight 1: the plain B3 à-trous blur (the control the guides are measured against) */
+};
+/* iterations: filter passes, 0 = default (4), at most 8; pass i filters with step 2^i. sigma_*: edge-stop widths of colour, normal,
+ * depth and albedo; 0 = default (docs/SPEC.md §8.2 states the defaults as exact values). */
+typedef struct pt_denoise_params {
+    uint32_t iterations;
+    float sigma_color, sigma_normal, sigma_depth, sigma_albedo;
+    uint32_t flags;
+    uint32_t pad[2];
+} pt_denoise_params; /* 32 B */
+/* Denoise the context's assembled framebuffer, with guides traced on `scene` (the scene the frame was rendered on; its camera). Synchronous
+ * on the context's stream, like pt_render. Checked in this order; a refused call changes nothing:
+ *   dp NULL, unknown flag bits, iterations > 8, a negative, NaN or infinite sigma; then ctx or scene NULL   -> PT_ERR_INVALID_ARGUMENT
+ *   a detached scene, a scene of another context or one committed under the PTRT_UNIFIED experiment        -> PT_ERR_UNSUPPORTED
+ *   scene not committed                                                                                     -> PT_ERR_NOT_COMMITTED
+ *   the framebuffer holds a PT_REFERENCE_SPHERE frame                                                       -> PT_ERR_UNSUPPORTED
+ *   no assembled framebuffer (a PT_PATH_TRACE frame with nranks == 1, or pt_assemble_tiles / pt_comm_* on
+ *   the root, makes one)                                                                                    -> PT_ERR_NOT_COMMITTED
+ * It never touches the framebuffer, the accumulated sums or anything pt_framebuffer_read* return: a later PT_FLAG_ACCUMULATE frame
+ * continues as if no denoise had run. The guides (W x H of the framebuffer, 8 floats per pixel: g0 = (n.xyz, t), g1 = (albedo.rgb,
+ * prim id bits); a miss is (0, 0, 0, +inf), (0, 0, 0, 0xFFFFFFFF)) and the denoised image (float4 per pixel, alpha copied) stay readable
+ * until the context's next pt_render or pt_assemble_tiles; then the read functions return PT_ERR_NOT_COMMITTED, as the denoised ones do
+ * after a PT_DENOISE_GUIDES_ONLY call. stats (may be NULL): rays = W*H guide rays, gpu_ms all kernels, extend_ms the guide pass,
+ * other_ms the filter passes, iterations = filter passes run. A failed call drains the context's stream. */
+pt_status pt_denoise(pt_context *ctx, const pt_scene *scene, const pt_denoise_params *dp, pt_stats *stats);
+pt_status pt_denoised_read(pt_context *ctx, float *rgba, uint64_t n_floats);               /* row-major float4, W*H*4 floats */
+pt_status pt_denoised_device_ptr(pt_context *ctx, void **dptr, uint64_t *n_floats);       /* the same on the device (valid as above) */
+pt_status pt_guides_read(pt_context *ctx, float *g8, uint64_t n_floats);                  /* 8 floats per pixel: g0, g1 (W*H*8 floats) */
 
 /* ---- results: the reference never reads its image back (it is sampled by the display pass,
  *      Renderer.cs:1042-1121); these replace that consumer. float4 linear radiance, row-major. */

@@ -42,6 +42,7 @@ PT_BVH_WIDTH_2, PT_BVH_WIDTH_4, PT_BVH_WIDTH_4Q, PT_BVH_WIDTH_8Q, PT_BVH_WIDTH_8
 PT_COMM_FORCE_RCCL, PT_COMM_COPY_EXCHANGE = 1, 2
 PT_TRACE_OCCLUSION, PT_TRACE_COUNT_VISITS, PT_TRACE_HOST_MEMORY = 1, 2, 4
 PT_UPDATE_HOST_MEMORY = 1
+PT_DENOISE_GUIDES_ONLY, PT_DENOISE_NO_EDGE_STOPS = 1, 2
 
 
 class pt_device_desc(C.Structure):
@@ -89,11 +90,17 @@ class pt_tile_layout(C.Structure):
                 ("tiles_mine", C.c_uint32), ("tiles_per_rank", C.c_uint32), ("floats_per_tile", C.c_uint64)]
 
 
+class pt_denoise_params(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
+                ("sigma_albedo", C.c_float), ("flags", C.c_uint32), ("pad", C.c_uint32 * 2)]
+
+
 class pt_scene_counts(C.Structure):
     _fields_ = [("n_tris", C.c_uint64), ("n_spheres", C.c_uint64), ("n_mats", C.c_uint64)]
 
 
 assert C.sizeof(pt_material) == 48 and C.sizeof(pt_camera) == 64 and C.sizeof(pt_render_params) == 64 and C.sizeof(pt_tuning) == 40
+assert C.sizeof(pt_denoise_params) == 32
 
 _vp, _u32, _u64, _st = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int32
 _P = C.POINTER
@@ -120,6 +127,10 @@ SYMBOLS = {
     "pt_trace_rays": (_st, [_vp, _vp, _vp, _vp, _u64, _u32, _P(pt_stats)]),
     "pt_scene_update_triangles": (_st, [_vp, _vp, _u64, _u32, _P(pt_stats)]),
     "pt_scene_update_spheres": (_st, [_vp, _vp, _u64]),
+    "pt_denoise": (_st, [_vp, _vp, _P(pt_denoise_params), _P(pt_stats)]),
+    "pt_denoised_read": (_st, [_vp, _vp, _u64]),
+    "pt_denoised_device_ptr": (_st, [_vp, _P(_vp), _P(_u64)]),
+    "pt_guides_read": (_st, [_vp, _vp, _u64]),
     "pt_framebuffer_read": (_st, [_vp, _vp, _u64]),
     "pt_framebuffer_read_rgba8": (_st, [_vp, _vp, _u64]),
     "pt_framebuffer_read_srgb8": (_st, [_vp, _vp, _u64]),

@@ -5,6 +5,7 @@
 #include "ptrt_internal.h"
 #include "bvh_build.h"
 #include "refit.h"
+#include "denoise.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
@@ -175,6 +176,14 @@ struct pt_context {
     DevBuf<int32_t> trace_ovf;
     DevBuf<float4> trace_rays, trace_hits;
     hipEvent_t ev_trace[2] = {};
+    bool fb_reference = false;       // the framebuffer holds a PT_REFERENCE_SPHERE frame (pt_denoise refuses it)
+    // pt_denoise (docs/SPEC.md §8): guide rays (2 rows per pixel; then the filter's two ping-pong images), their hits, the two guide
+    // planes and the denoised image of a dn_w x dn_h framebuffer. dn_guides / dn_image: what the read functions may hand out (until the
+    // next pt_render or pt_assemble_tiles)
+    DevBuf<float4> dn_work, dn_hits, dn_g0, dn_g1, dn_out;
+    uint32_t dn_w = 0, dn_h = 0;
+    bool dn_guides = false, dn_image = false;
+    hipEvent_t ev_denoise[3] = {};   // start, guides done, filter done
 };
 
 struct pt_scene {
@@ -221,6 +230,10 @@ struct pt_scene {
     uint32_t cand_lo = 0, n_lights = 0;
     DevBuf<float4> d_lights;
     DevBuf<float> d_cdf, d_pa;
+    // pt_denoise: original triangle id -> blob index (where a guide finds its hit's shading row), made by the first denoise after a
+    // commit; updates keep it (they keep every record's id and place)
+    mutable DevBuf<uint32_t> d_blob_of;
+    mutable bool blob_of_ready = false;
 };
 
 namespace {
@@ -428,6 +441,7 @@ void pt_context_destroy(pt_context *c)
     c->sd.release(); c->q_ext0.release(); c->q_ext1.release(); c->counters.release(); c->fb8.release(); c->stack_ovf.release();
     c->q_init.release(); c->cnt_init.release(); c->q_metal.release(); c->q_dielectric.release();
     c->trace_cnt.release(); c->trace_ovf.release(); c->trace_rays.release(); c->trace_hits.release();
+    c->dn_work.release(); c->dn_hits.release(); c->dn_g0.release(); c->dn_g1.release(); c->dn_out.release();
     if (c->h_counts) (void)hipHostFree(c->h_counts);
     if (c->h_ring) (void)hipHostFree(c->h_ring);
     for (auto &row : c->ev_lag) for (auto &e : row) if (e) (void)hipEventDestroy(e);
@@ -436,6 +450,7 @@ void pt_context_destroy(pt_context *c)
     for (auto &gs : c->group_stream) if (gs) (void)hipStreamDestroy(gs);
     for (auto &e : c->ev_probe) if (e) (void)hipEventDestroy(e);
     for (auto &e : c->ev_trace) if (e) (void)hipEventDestroy(e);
+    for (auto &e : c->ev_denoise) if (e) (void)hipEventDestroy(e);
     if (c->ev_start) (void)hipEventDestroy(c->ev_start);
     if (c->ev_stop) (void)hipEventDestroy(c->ev_stop);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
@@ -461,7 +476,7 @@ void pt_scene_destroy(pt_scene *s)
 {
     if (!s) return;
     if (s->ctx) { (void)hipSetDevice(s->ctx->device); (void)hipStreamSynchronize(s->ctx->stream); }
-    s->d_nodes.release(); s->d_tris.release();s->d_spheres.release(); s->d_mats.release(); s->d_sph_mat.release();
+    s->d_nodes.release(); s->d_tris.release();s->d_spheres.release(); s->d_mats.release(); s->d_sph_mat.release(); s->d_blob_of.release();
     auto &R = s->refit;
     R.list.release(); R.flag.release(); R.tbox.release(); R.nbox.release(); R.carea.release(); R.verts[0].release(); R.verts[1].release(); R.sah.release();
     for (auto &e : R.ev) if (e) (void)hipEventDestroy(e);
@@ -559,6 +574,7 @@ pt_status pt_scene_commit(pt_scene *s, uint32_t bvh_width)
         s->verts_on_device = false;
     }
     s->refit.ready = false;
+    s->blob_of_ready = false;
 
     const bool oct = bvh_width == PT_BVH_WIDTH_8O;
     const uint32_t fan = bvh_width == PT_BVH_WIDTH_2 ? 2u : (bvh_width == PT_BVH_WIDTH_8Q || oct) ? 8u : 4u;
@@ -1053,7 +1069,8 @@ static pt_status render_frame(pt_context *c, const pt_scene *s, const pt_render_
     pt_tile_layout lay; pt_status st = layout_of(p, &lay);
     if (st != PT_OK) return fail(c, st, "pt_render: bad width/height/rank/nranks/tile_size");
     HIP_TRY(c, hipSetDevice(c->device));
-    c->fb_valid = false;
+    c->fb_valid = false; c->fb_reference = false;
+    c->dn_guides = c->dn_image = false; // the denoised results belong to the frame this call replaces
     if (p->mode == PT_REFERENCE_SPHERE) { // Renderer.ComputeFrame: one dispatch, then the host blocks on the fence (Renderer.cs:1020,1036,972)
         if ((st = ensure_frame(c, p->width, p->height)) != PT_OK) return st;
         HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
@@ -1063,7 +1080,7 @@ static pt_status render_frame(pt_context *c, const pt_scene *s, const pt_render_
         float ms = 0.f; HIP_TRY(c, hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
         pt_stats out; std::memset(&out, 0, sizeof out);
         out.gpu_ms = ms; out.other_ms = ms; out.rays = out.paths = (uint64_t)p->width * p->height; out.iterations = 1;
-        c->fb_valid = true; if (stats) *stats = out;
+        c->fb_valid = true; c->fb_reference = true; if (stats) *stats = out;
         return PT_OK;
     }
     if (p->mode != PT_PATH_TRACE) return fail(c, PT_ERR_INVALID_ARGUMENT, "unknown mode %u", p->mode);
@@ -1107,6 +1124,38 @@ pt_status check_device_array(pt_context *c, const void *p, uint64_t bytes, const
 }
 } // namespace
 
+// The plumbing of a query (pt_trace_rays, pt_denoise's guide pass): the context's own counter block and overflow area, never pt_render's
+// (the frame-start template, the partial sums, the queues and their counters stay untouched). trace_setup sizes the overflow area for
+// launches of up to n_rays rays and zeroes the counter words the kernels use; trace_launch enqueues the launches (k_trace indexes with 32
+// bits); trace_readback copies those words back (error flag first, then the visit counters) for the caller's synchronise.
+constexpr uint64_t kTraceChunk = 1ull << 31;                   // rays per launch
+constexpr uint32_t kTraceWords = kCntTotalWords - kCntGlobals; // the counter words of a query
+static pt_status trace_setup(pt_context *c, const pt_scene *s, uint64_t n_rays, PathState &ps)
+{
+    const uint32_t blocks = trace_blocks((uint32_t)std::min<uint64_t>(n_rays, kTraceChunk)), lanes = blocks * kExtBlock;
+    ps = PathState{};
+    ps.shard_cap = (lanes + kShards - 1u) / kShards; // one overflow column per lane of the grid, reused by its every ray
+    ps.stack_ovf_entries = s->bvh.stack_need > kStackLds ? s->bvh.stack_need - kStackLds : 0u;
+    if (ps.stack_ovf_entries) HIP_TRY(c, c->trace_ovf.ensure((size_t)ps.stack_ovf_entries * kShards * ps.shard_cap));
+    ps.stack_ovf = c->trace_ovf.p;
+    HIP_TRY(c, c->trace_cnt.ensure(kCntTotalWords)); // the kernels use the global words only: error flag and visit counters
+    ps.counters = c->trace_cnt.p;
+    HIP_TRY(c, hipMemsetAsync(c->trace_cnt.p + kCntGlobals, 0, sizeof(uint32_t) * kTraceWords, c->stream));
+    return PT_OK;
+}
+static pt_status trace_launch(pt_context *c, const pt_scene *s, const PathState &ps, const float4 *rays, float4 *hits, uint64_t n_rays,
+                              bool occlusion, bool count)
+{
+    for (uint64_t first = 0; first < n_rays; first += kTraceChunk)
+        HIP_TRY(c, launch_trace(c->stream, s->ds, ps, rays + 2u * first, hits + first, (uint32_t)std::min(kTraceChunk, n_rays - first), occlusion, count));
+    return PT_OK;
+}
+static pt_status trace_readback(pt_context *c, uint32_t (&hc)[kTraceWords])
+{
+    HIP_TRY(c, hipMemcpyAsync(hc, c->trace_cnt.p + kCntGlobals, sizeof hc, hipMemcpyDeviceToHost, c->stream));
+    return PT_OK;
+}
+
 static pt_status trace_rays(pt_context *c, const pt_scene *s, const void *rays, void *hits, uint64_t n_rays, uint32_t flags, pt_stats *stats)
 {
     constexpr uint32_t known = PT_TRACE_OCCLUSION | PT_TRACE_COUNT_VISITS | PT_TRACE_HOST_MEMORY;
@@ -1127,15 +1176,8 @@ static pt_status trace_rays(pt_context *c, const pt_scene *s, const void *rays, 
     pt_status st;
     if (!host && ((st = check_device_array(c, rays, n_rays * 32u, "rays")) != PT_OK || (st = check_device_array(c, hits, n_rays * 16u, "hits")) != PT_OK)) return st;
     hipStream_t q = c->stream;
-    const uint64_t chunk = 1ull << 31; // rays per launch (k_trace indexes with 32 bits)
-    const uint32_t blocks = trace_blocks((uint32_t)std::min<uint64_t>(n_rays, chunk)), lanes = blocks * kExtBlock;
-    PathState ps{};
-    ps.shard_cap = (lanes + kShards - 1u) / kShards; // one overflow column per lane of the grid, reused by its every ray
-    ps.stack_ovf_entries = s->bvh.stack_need > kStackLds ? s->bvh.stack_need - kStackLds : 0u;
-    if (ps.stack_ovf_entries) HIP_TRY(c, c->trace_ovf.ensure((size_t)ps.stack_ovf_entries * kShards * ps.shard_cap));
-    ps.stack_ovf = c->trace_ovf.p;
-    HIP_TRY(c, c->trace_cnt.ensure(kCntTotalWords)); // the kernels use the global words only: error flag and visit counters
-    ps.counters = c->trace_cnt.p;
+    PathState ps;
+    if ((st = trace_setup(c, s, n_rays, ps)) != PT_OK) return st;
     const float4 *d_rays = (const float4 *)rays;
     float4 *d_hits = (float4 *)hits;
     if (host) { // staged through the context's own buffers
@@ -1143,15 +1185,12 @@ static pt_status trace_rays(pt_context *c, const pt_scene *s, const void *rays, 
         HIP_TRY(c, hipMemcpyAsync(c->trace_rays.p, rays, n_rays * 32u, hipMemcpyHostToDevice, q));
         d_rays = c->trace_rays.p; d_hits = c->trace_hits.p;
     }
-    constexpr uint32_t words = kCntTotalWords - kCntGlobals;
-    HIP_TRY(c, hipMemsetAsync(c->trace_cnt.p + kCntGlobals, 0, sizeof(uint32_t) * words, q));
     HIP_TRY(c, hipEventRecord(c->ev_trace[0], q));
-    for (uint64_t first = 0; first < n_rays; first += chunk)
-        HIP_TRY(c, launch_trace(q, s->ds, ps, d_rays + 2u * first, d_hits + first, (uint32_t)std::min(chunk, n_rays - first), occlusion, count));
+    if ((st = trace_launch(c, s, ps, d_rays, d_hits, n_rays, occlusion, count)) != PT_OK) return st;
     HIP_TRY(c, hipEventRecord(c->ev_trace[1], q));
     if (host) HIP_TRY(c, hipMemcpyAsync(hits, d_hits, n_rays * 16u, hipMemcpyDeviceToHost, q));
-    uint32_t hc[words];
-    HIP_TRY(c, hipMemcpyAsync(hc, c->trace_cnt.p + kCntGlobals, sizeof hc, hipMemcpyDeviceToHost, q));
+    uint32_t hc[kTraceWords];
+    if ((st = trace_readback(c, hc)) != PT_OK) return st;
     HIP_TRY(c, hipStreamSynchronize(q));
     if (hc[kCntError - kCntGlobals])
         return fail(c, PT_ERR_INTERNAL, "pt_trace_rays: device error flag 0x%x (1 = traversal stack overflow, 2 = step limit)", hc[kCntError - kCntGlobals]);
@@ -1308,6 +1347,135 @@ pt_status pt_scene_update_spheres(pt_scene *s, const float *cxyzr, uint64_t coun
     return st;
 }
 
+// ------------------------------------------------------------------------------------------------ denoising (docs/SPEC.md §8)
+
+// §8.2 defaults, the exact f32 values SPEC §8.2 states (chosen by the quality sweep of tools/exp_denoise.py)
+constexpr uint32_t kDenoiseIterations = 4u;
+constexpr float kSigmaColor = 16.0f, kSigmaNormal = 0.0625f, kSigmaDepth = 0.0078125f, kSigmaAlbedo = 0.25f;
+
+static pt_status denoise(pt_context *c, const pt_scene *s, const pt_denoise_params *dp, pt_stats *stats)
+{
+    if (!dp) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_denoise: dp is NULL");
+    constexpr uint32_t known = PT_DENOISE_GUIDES_ONLY | PT_DENOISE_NO_EDGE_STOPS;
+    if (dp->flags & ~known) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_denoise: unknown flag bits 0x%x", dp->flags & ~known);
+    if (dp->iterations > 8u) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_denoise: iterations %u (0 = default, at most 8)", dp->iterations);
+    const float sigma[4] = { dp->sigma_color, dp->sigma_normal, dp->sigma_depth, dp->sigma_albedo };
+    static const char *const sigma_name[4] = { "sigma_color", "sigma_normal", "sigma_depth", "sigma_albedo" };
+    for (int k = 0; k < 4; ++k)
+        if (!(sigma[k] >= 0.0f) || std::isinf(sigma[k]))
+            return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_denoise: %s = %g (must be finite and >= 0; 0 = default)", sigma_name[k], (double)sigma[k]);
+    if (!c || !s) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_denoise: NULL context or scene");
+    if (s->ctx != c) return fail(c, PT_ERR_UNSUPPORTED, "pt_denoise: the scene is %s", s->ctx ? "of another context" : "detached (no device copy to trace)");
+    if (s->unified) return fail(c, PT_ERR_UNSUPPORTED, "pt_denoise: not for a scene committed under PTRT_UNIFIED");
+    if (!s->committed) return fail(c, PT_ERR_NOT_COMMITTED, "pt_denoise: scene not committed");
+    if (c->fb_valid && c->fb_reference) return fail(c, PT_ERR_UNSUPPORTED, "pt_denoise: the framebuffer holds a PT_REFERENCE_SPHERE frame");
+    if (!c->fb_valid) return fail(c, PT_ERR_NOT_COMMITTED, "pt_denoise: no assembled frame (render with nranks == 1 or assemble the tiles first)");
+    const bool guides_only = (dp->flags & PT_DENOISE_GUIDES_ONLY) != 0;
+    const uint32_t passes = guides_only ? 0u : dp->iterations ? dp->iterations : kDenoiseIterations;
+    const float sc = sigma[0] != 0.0f ? sigma[0] : kSigmaColor, sn = sigma[1] != 0.0f ? sigma[1] : kSigmaNormal;
+    const float sz = sigma[2] != 0.0f ? sigma[2] : kSigmaDepth, sa = sigma[3] != 0.0f ? sigma[3] : kSigmaAlbedo;
+
+    const uint32_t w = c->fb_w, h = c->fb_h;
+    const size_t n = (size_t)w * h;
+    HIP_TRY(c, hipSetDevice(c->device));
+    for (auto &e : c->ev_denoise) if (!e) HIP_TRY(c, hipEventCreate(&e));
+    c->dn_guides = c->dn_image = false; // from here on the buffers are rewritten
+    HIP_TRY(c, c->dn_work.ensure(2 * n)); HIP_TRY(c, c->dn_hits.ensure(n));
+    HIP_TRY(c, c->dn_g0.ensure(n)); HIP_TRY(c, c->dn_g1.ensure(n));
+    if (passes) HIP_TRY(c, c->dn_out.ensure(n));
+    const uint32_t nt = s->ds.n_tris;
+    if (!s->blob_of_ready) HIP_TRY(c, s->d_blob_of.ensure(std::max<size_t>(nt, 1)));
+    pt_status st;
+    PathState ps;
+    if ((st = trace_setup(c, s, n, ps)) != PT_OK) return st;
+    hipStream_t q = c->stream;
+    HIP_TRY(c, hipEventRecord(c->ev_denoise[0], q));
+    if (!s->blob_of_ready) { // (zeroed first: every entry is a valid blob index even if an id were missing)
+        HIP_TRY(c, hipMemsetAsync(s->d_blob_of.p, 0, std::max<size_t>(nt, 1) * sizeof(uint32_t), q));
+        HIP_TRY(c, launch_guide_index(q, s->ds.tris, nt, s->d_blob_of.p));
+    }
+    float4 *rays = c->dn_work.p;
+    HIP_TRY(c, launch_guide_rays(q, s->cam, w, h, rays));
+    if ((st = trace_launch(c, s, ps, rays, c->dn_hits.p, n, false, false)) != PT_OK) return st;
+    HIP_TRY(c, launch_guide_resolve(q, s->ds, s->d_blob_of.p, rays, c->dn_hits.p, (uint32_t)n, c->dn_g0.p, c->dn_g1.p));
+    HIP_TRY(c, hipEventRecord(c->ev_denoise[1], q));
+    // pass i reads the framebuffer (i = 0) or pass i-1's image; the last pass writes dn_out, the others alternate between the two halves
+    // of dn_work (the rays are dead by then)
+    AtrousParams ap{};
+    ap.width = w; ap.height = h; ap.edge_stops = (dp->flags & PT_DENOISE_NO_EDGE_STOPS) == 0;
+    ap.inv_sn = 1.0f / sn; ap.sigma_z = sz; ap.ia = 1.0f / (sa * sa);
+    const float ic = 1.0f / (sc * sc);
+    const float4 *src = c->fb.p;
+    for (uint32_t i = 0; i < passes; ++i) {
+        float4 *dst = i + 1 == passes ? c->dn_out.p : c->dn_work.p + (i & 1u) * n;
+        ap.pass = i; ap.ic_i = ic * (float)(1u << (2u * i));
+        HIP_TRY(c, launch_atrous(q, ap, src, c->dn_g0.p, c->dn_g1.p, dst));
+        src = dst;
+    }
+    HIP_TRY(c, hipEventRecord(c->ev_denoise[2], q));
+    uint32_t hc[kTraceWords];
+    if ((st = trace_readback(c, hc)) != PT_OK) return st;
+    HIP_TRY(c, hipStreamSynchronize(q));
+    if (hc[kCntError - kCntGlobals])
+        return fail(c, PT_ERR_INTERNAL, "pt_denoise: device error flag 0x%x in the guide pass (1 = traversal stack overflow, 2 = step limit)", hc[kCntError - kCntGlobals]);
+    s->blob_of_ready = true;
+    float ms_guides = 0.f, ms_filter = 0.f;
+    HIP_TRY(c, hipEventElapsedTime(&ms_guides, c->ev_denoise[0], c->ev_denoise[1]));
+    HIP_TRY(c, hipEventElapsedTime(&ms_filter, c->ev_denoise[1], c->ev_denoise[2]));
+    pt_stats out; std::memset(&out, 0, sizeof out);
+    out.rays = n; out.iterations = passes;
+    out.extend_ms = ms_guides; out.other_ms = ms_filter; out.gpu_ms = (double)ms_guides + ms_filter;
+    c->dn_w = w; c->dn_h = h; c->dn_guides = true; c->dn_image = passes > 0;
+    if (stats) *stats = out;
+    return PT_OK;
+}
+
+pt_status pt_denoise(pt_context *c, const pt_scene *s, const pt_denoise_params *dp, pt_stats *stats)
+{
+    const pt_status st = denoise(c, s, dp, stats);
+    if (st != PT_OK && c) { (void)hipSetDevice(c->device); drain(c); } // nothing of a failed call runs on after it
+    return st;
+}
+
+pt_status pt_denoised_read(pt_context *c, float *rgba, uint64_t n_floats)
+{
+    if (!c || !rgba) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_denoised_read: NULL argument");
+    if (!c->dn_image) return fail(c, PT_ERR_NOT_COMMITTED, "pt_denoised_read: no denoised image (pt_denoise after the last pt_render, without PT_DENOISE_GUIDES_ONLY)");
+    const uint64_t need = (uint64_t)c->dn_w * c->dn_h * 4;
+    if (n_floats < need) return fail(c, PT_ERR_INVALID_ARGUMENT, "buffer too small: need %llu floats", (unsigned long long)need);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(rgba, c->dn_out.p, need * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return PT_OK;
+}
+
+pt_status pt_denoised_device_ptr(pt_context *c, void **dptr, uint64_t *n_floats)
+{
+    if (!c || !dptr) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_denoised_device_ptr: NULL argument");
+    if (!c->dn_image) return fail(c, PT_ERR_NOT_COMMITTED, "pt_denoised_device_ptr: no denoised image");
+    *dptr = c->dn_out.p;
+    if (n_floats) *n_floats = (uint64_t)c->dn_w * c->dn_h * 4;
+    return PT_OK;
+}
+
+pt_status pt_guides_read(pt_context *c, float *g8, uint64_t n_floats)
+{
+    if (!c || !g8) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_guides_read: NULL argument");
+    if (!c->dn_guides) return fail(c, PT_ERR_NOT_COMMITTED, "pt_guides_read: no guides (pt_denoise after the last pt_render)");
+    const size_t n = (size_t)c->dn_w * c->dn_h;
+    if (n_floats < (uint64_t)n * 8) return fail(c, PT_ERR_INVALID_ARGUMENT, "buffer too small: need %llu floats", (unsigned long long)n * 8);
+    HIP_TRY(c, hipSetDevice(c->device));
+    std::vector<float4> planes(2 * n); // the device keeps g0 and g1 as separate planes (one coalesced row each for the filter)
+    HIP_TRY(c, hipMemcpyAsync(planes.data(), c->dn_g0.p, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(planes.data() + n, c->dn_g1.p, n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < n; ++i) {
+        std::memcpy(g8 + 8 * i, &planes[i], sizeof(float4));
+        std::memcpy(g8 + 8 * i + 4, &planes[n + i], sizeof(float4));
+    }
+    return PT_OK;
+}
+
 pt_status pt_framebuffer_read(pt_context *c, float *rgba, uint64_t n_floats)
 {
     if (!c || !rgba) return fail(c, PT_ERR_INVALID_ARGUMENT, "NULL argument");
@@ -1377,6 +1545,7 @@ pt_status pt_assemble_tiles(pt_context *c, const pt_render_params *p, const void
     const uint64_t per_rank = (uint64_t)lay.tiles_per_rank * kTilePixels;
     if (n_floats < per_rank * nranks * 4) return fail(c, PT_ERR_INVALID_ARGUMENT, "gathered buffer too small: need %llu floats", (unsigned long long)(per_rank * nranks * 4));
     HIP_TRY(c, hipSetDevice(c->device));
+    c->fb_valid = false; c->fb_reference = false; c->dn_guides = c->dn_image = false;
     if ((st = ensure_frame(c, p->width, p->height)) != PT_OK) return st;
     HIP_TRY(c, launch_assemble(c->stream, (const float4 *)gathered, nranks, (uint32_t)per_rank, p->width, p->height, lay.tiles_x, lay.n_tiles,
                                1.0f / (float)(((p->flags & PT_FLAG_ACCUMULATE) ? (uint64_t)p->sample_offset : 0u) + p->spp), c->fb.p, c->fb8.p));

@@ -264,6 +264,32 @@ class Renderer:
             _check(N.lib.pt_scene_update_spheres(self._scene, _ptr(sph), len(sph)), self._ctx)
         return stats
 
+    def Denoise(self, iterations=0, sigma_color=0.0, sigma_normal=0.0, sigma_depth=0.0, sigma_albedo=0.0, guides_only=False,
+                edge_stops=True):
+        """Denoise the last assembled frame with guides traced on the current scene (include/ptrt.h pt_denoise, docs/SPEC.md §8);
+        returns pt_stats (rays = guide rays, extend_ms = guide pass, other_ms = filter passes). Zeros mean the defaults. The frame
+        itself (ReadFramebuffer, accumulated sums) is not touched; ReadDenoised / ReadGuides hold until the next Render."""
+        dp = N.pt_denoise_params(iterations, sigma_color, sigma_normal, sigma_depth, sigma_albedo,
+                                 (N.PT_DENOISE_GUIDES_ONLY if guides_only else 0) | (0 if edge_stops else N.PT_DENOISE_NO_EDGE_STOPS))
+        stats = N.pt_stats()
+        _check(N.lib.pt_denoise(self._ctx, self._scene, C.byref(dp), C.byref(stats)), self._ctx)
+        return stats
+
+    def ReadDenoised(self):
+        """The denoised frame, (H, W, 4) float32 (alpha as in the framebuffer)."""
+        w, h = self.Params.width, self.Params.height
+        out = np.empty((h, w, 4), np.float32)
+        _check(N.lib.pt_denoised_read(self._ctx, _ptr(out), out.size), self._ctx)
+        return out
+
+    def ReadGuides(self):
+        """The guide buffers of the last Denoise, (H, W, 8) float32: front-facing normal, t, albedo, prim id bits
+        (`[..., 7].view(np.uint32)`; a miss is t = +inf, id 0xFFFFFFFF). What a host's own denoiser takes as features."""
+        w, h = self.Params.width, self.Params.height
+        out = np.empty((h, w, 8), np.float32)
+        _check(N.lib.pt_guides_read(self._ctx, _ptr(out), out.size), self._ctx)
+        return out
+
     # Renderer.Update (Renderer.cs:86-89) is empty in the reference
     def Update(self, deltaTime):
         pass

@@ -1,0 +1,74 @@
+"""ctypes binding of tests/denoise_ref/libdenoise_ref.so — the scalar restatement of docs/SPEC.md §8 (pt_denoise) that the denoiser tests
+check the device against. Test infrastructure only, like oracle/pto.py; `build()` runs its Makefile."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+DIR = os.path.join(HERE, "denoise_ref")
+GUIDES_ONLY, NO_EDGE_STOPS = 1, 2
+MISS = 0xFFFFFFFF
+_lib = None
+
+
+class dr_params(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
+                ("sigma_albedo", C.c_float), ("flags", C.c_uint32), ("pad", C.c_uint32 * 2)]
+
+
+assert C.sizeof(dr_params) == 32
+
+
+def build():
+    """make the checker (incremental) and load it."""
+    global _lib
+    subprocess.run(["make", "-s", "-C", DIR], check=True)
+    if _lib is None:
+        _lib = C.CDLL(os.path.join(DIR, "libdenoise_ref.so"))
+        _lib.dr_guides.restype = C.c_int
+        _lib.dr_guides.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        _lib.dr_filter.restype = C.c_int
+        _lib.dr_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(dr_params), C.c_void_p]
+        _lib.dr_resolve.restype = C.c_int
+        _lib.dr_resolve.argtypes = [C.POINTER(dr_params), C.POINTER(dr_params)]
+    return _lib
+
+
+def params(iterations=0, sigma_color=0.0, sigma_normal=0.0, sigma_depth=0.0, sigma_albedo=0.0, flags=0):
+    return dr_params(iterations, sigma_color, sigma_normal, sigma_depth, sigma_albedo, flags)
+
+
+def defaults():
+    """The §8.2 defaults the checker restates (iterations, sigma_color, sigma_normal, sigma_depth, sigma_albedo)."""
+    out = dr_params()
+    assert build().dr_resolve(C.byref(params()), C.byref(out)) > 0
+    return out.iterations, out.sigma_color, out.sigma_normal, out.sigma_depth, out.sigma_albedo
+
+
+def guides(pto, scene, w, h):
+    """(h, w, 8) float32: g0 = (n, t), g1 = (albedo, prim id bits) of §8.1. `scene`: a pto.Scene (brute force or with a blob)."""
+    g = np.zeros((h, w, 8), np.float32)
+    assert build().dr_guides(C.addressof(scene.c), w, h, g.ctypes.data) == 0
+    return g
+
+
+def filter(rgba, g8, p=None):
+    """§8.2 over an (h, w, 4) float32 image with (h, w, 8) guides; returns the filtered (h, w, 4) image (the input for GUIDES_ONLY)."""
+    rgba = np.ascontiguousarray(rgba, np.float32)
+    g8 = np.ascontiguousarray(g8, np.float32)
+    h, w = rgba.shape[:2]
+    assert g8.shape == (h, w, 8)
+    out = np.zeros_like(rgba)
+    n = build().dr_filter(rgba.ctypes.data, g8.ctypes.data, w, h, C.byref(p if p is not None else params()), out.ctypes.data)
+    if n < 0:
+        raise ValueError(f"dr_filter refused the parameters ({n})")
+    return out if n > 0 else rgba.copy()
+
+
+def denoise(pto, scene, rgba, p=None):
+    """(guides, denoised image) of §8 for a framebuffer `rgba` rendered on `scene`."""
+    h, w = rgba.shape[:2]
+    g = guides(pto, scene, w, h)
+    return g, filter(rgba, g, p)
