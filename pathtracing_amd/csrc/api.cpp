@@ -1403,12 +1403,12 @@ static pt_status denoise(pt_context *c, const pt_scene *s, const pt_denoise_para
     // of dn_work (the rays are dead by then)
     AtrousParams ap{};
     ap.width = w; ap.height = h; ap.edge_stops = (dp->flags & PT_DENOISE_NO_EDGE_STOPS) == 0;
-    ap.inv_sn = 1.0f / sn; ap.sigma_z = sz; ap.ia = 1.0f / (sa * sa);
+    ap.inv_sn = atrous_scale(1.0f / sn); ap.sigma_z = sz; ap.ia = atrous_scale(1.0f / (sa * sa));
     const float ic = 1.0f / (sc * sc);
     const float4 *src = c->fb.p;
     for (uint32_t i = 0; i < passes; ++i) {
         float4 *dst = i + 1 == passes ? c->dn_out.p : c->dn_work.p + (i & 1u) * n;
-        ap.pass = i; ap.ic_i = ic * (float)(1u << (2u * i));
+        ap.pass = i; ap.ic_i = atrous_scale(ic * (float)(1u << (2u * i)));
         HIP_TRY(c, launch_atrous(q, ap, src, c->dn_g0.p, c->dn_g1.p, dst));
         src = dst;
     }

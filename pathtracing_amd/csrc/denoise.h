@@ -18,15 +18,17 @@ hipError_t launch_guide_rays(hipStream_t s, const pt_camera &cam, uint32_t w, ui
 hipError_t launch_guide_resolve(hipStream_t s, const DeviceScene &sc, const uint32_t *blob_of, const float4 *rays, const float4 *hits,
                                 uint32_t n, float4 *g0, float4 *g1);
 
-// §8.2 pass `pass` (step 2^pass) of the filter: src -> dst, both w x h row-major float4. The sigmas are the resolved (non-zero) ones.
+// §8.2 pass `pass` (step 2^pass) of the filter: src -> dst, both w x h row-major float4. The sigmas are the resolved (non-zero) ones;
+// every inverse scale is clamped into [2^-149, FLT_MAX] (atrous_scale).
 struct AtrousParams {
     uint32_t width, height, pass;
     bool edge_stops;   // false: PT_DENOISE_NO_EDGE_STOPS
-    float ic_i;        // (1 / sigma_c^2) * 4^pass
-    float inv_sn;      // 1 / sigma_n
+    float ic_i;        // clamp((1 / sigma_c^2) * 4^pass)
+    float inv_sn;      // clamp(1 / sigma_n)
     float sigma_z;
-    float ia;          // 1 / sigma_a^2
+    float ia;          // clamp(1 / sigma_a^2)
 };
+inline float atrous_scale(float v) { return v < 0x1p-149f ? 0x1p-149f : v > 3.40282347e+38f ? 3.40282347e+38f : v; }
 hipError_t launch_atrous(hipStream_t s, const AtrousParams &p, const float4 *src, const float4 *g0, const float4 *g1, float4 *dst);
 
 } // namespace ptrt

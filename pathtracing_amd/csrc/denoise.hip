@@ -73,6 +73,7 @@ __global__ void __launch_bounds__(kBlock) k_guide_resolve(DeviceScene sc, const 
 PT_DEV float edge_d(float x) { return fma_(x, fma_(x, 0.5f, 1.0f), 1.0f); } // ~e^x near 0, no transcendental
 PT_DEV float dot4_3(float4 a, float4 b) { return fma_(a.z, b.z, fma_(a.y, b.y, a.x * b.x)); }
 PT_DEV float b3(int k) { return k == 0 ? 0.375f : (k == 1 || k == -1) ? 0.25f : 0.0625f; }
+PT_DEV float clamp_scale(float v) { return fmin_(fmax_(v, 0x1p-149f), 3.40282347e+38f); } // §8.2: an inverse scale is never 0 or +inf
 
 template <bool EDGE>
 __global__ void __launch_bounds__(kBlock) k_atrous(AtrousParams p, const float4 *__restrict__ src, const float4 *__restrict__ g0,
@@ -85,7 +86,7 @@ __global__ void __launch_bounds__(kBlock) k_atrous(AtrousParams p, const float4 
     const size_t ip = (size_t)y * w + x;
     const float4 cp = src[ip], np = g0[ip], ap = g1[ip];
     const bool miss_p = __float_as_uint(ap.w) == PT_MISS;
-    const float iz = 1.0f / ((p.sigma_z * np.w) * (float)s); // (used only when p is a hit)
+    const float iz = clamp_scale(1.0f / ((p.sigma_z * np.w) * (float)s)); // (used only when p is a hit)
     float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f;
 #pragma unroll
     for (int dy = -2; dy <= 2; ++dy) {
@@ -117,8 +118,10 @@ __global__ void __launch_bounds__(kBlock) k_atrous(AtrousParams p, const float4 
             sr = fma_(wt, cq.x, sr); sg = fma_(wt, cq.y, sg); sb = fma_(wt, cq.z, sb);
         }
     }
-    const float r = 1.0f / sw; // the centre tap alone gives sw >= 0.140625
-    dst[ip] = make_float4(sr * r, sg * r, sb * r, cp.w);
+    // The centre tap usually gives sw >= 0.140625, but its x_n = max(0, 1 - |n|^2) * inv_sn is not 0 where |n|^2 < 1 in f32, so with a
+    // huge inv_sn every weight can vanish: then 1/sw overflows and the pixel is kept as it is (§8.2).
+    const float r = 1.0f / sw;
+    dst[ip] = r <= 3.40282347e+38f ? make_float4(sr * r, sg * r, sb * r, cp.w) : cp;
 }
 
 // ================================================================================================ launchers

@@ -10,6 +10,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 DIR = os.path.join(HERE, "denoise_ref")
 GUIDES_ONLY, NO_EDGE_STOPS = 1, 2
 MISS = 0xFFFFFFFF
+# dr_pass variants: §8.2 as written, then the deliberately wrong ones of the negative controls
+SPEC, SIGMA_C_FIXED, XZ_NO_STEP, D_LINEAR, WRONG_TAP, NO_MISS_SKIP = range(6)
 _lib = None
 
 
@@ -31,6 +33,8 @@ def build():
         _lib.dr_guides.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         _lib.dr_filter.restype = C.c_int
         _lib.dr_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(dr_params), C.c_void_p]
+        _lib.dr_pass.restype = C.c_int
+        _lib.dr_pass.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(dr_params), C.c_uint32, C.c_int, C.c_void_p]
         _lib.dr_resolve.restype = C.c_int
         _lib.dr_resolve.argtypes = [C.POINTER(dr_params), C.POINTER(dr_params)]
     return _lib
@@ -65,6 +69,18 @@ def filter(rgba, g8, p=None):
     if n < 0:
         raise ValueError(f"dr_filter refused the parameters ({n})")
     return out if n > 0 else rgba.copy()
+
+
+def one_pass(rgba, g8, i, p=None, variant=SPEC):
+    """Pass i (0-based, step 2^i) of §8.2 alone over an (h, w, 4) float32 image, or one of the wrong variants (negative controls)."""
+    rgba = np.ascontiguousarray(rgba, np.float32)
+    g8 = np.ascontiguousarray(g8, np.float32)
+    h, w = rgba.shape[:2]
+    assert g8.shape == (h, w, 8)
+    out = np.zeros_like(rgba)
+    if build().dr_pass(rgba.ctypes.data, g8.ctypes.data, w, h, C.byref(p if p is not None else params()), i, variant, out.ctypes.data):
+        raise ValueError("dr_pass refused the parameters")
+    return out
 
 
 def denoise(pto, scene, rgba, p=None):

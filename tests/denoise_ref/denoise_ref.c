@@ -5,8 +5,10 @@
  * call this.
  *
  * dr_guides() is §8.1 on the scene's own arrays (original order), dr_filter() is §8.2 on any colour image and guide buffers, so that the
- * tests can also feed it synthetic guides.
+ * tests can also feed it synthetic guides. dr_pass() is one pass of §8.2, or a deliberately wrong variant of it (DRV_*): the negative
+ * controls of tests/test_denoise64.py, which must fail the float64 comparison. Only the tests call it with a variant.
  */
+#include <float.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -92,22 +94,33 @@ int dr_resolve(const dr_params *in, dr_params *out)
     return (in->flags & DR_GUIDES_ONLY) ? 0 : (int)out->iterations;
 }
 
+/* Wrong variants of a pass, for the negative controls only (0: §8.2 as written). */
+enum { DRV_SPEC = 0, DRV_SIGMA_C_FIXED = 1, DRV_XZ_NO_STEP = 2, DRV_D_LINEAR = 3, DRV_WRONG_TAP = 4, DRV_NO_MISS_SKIP = 5 };
+
+static inline float Dv(float x, int variant) { return variant == DRV_D_LINEAR ? 1.0f + x : D(x); }
+
+/* §8.2's clamp of an inverse scale into [2^-149, FLT_MAX]: never 0 or +inf, so no 0 * inf */
+static inline float clamp_scale(float v) { return fminf(fmaxf(v, 0x1p-149f), FLT_MAX); }
+
 /* One pass i: src -> dst (W*H*4 floats each). */
-static void pass(const float *src, const float *g8, uint32_t W, uint32_t H, const dr_params *p, uint32_t i, float *dst)
+static void pass(const float *src, const float *g8, uint32_t W, uint32_t H, const dr_params *p, uint32_t i, int variant, float *dst)
 {
-    static const float h[5] = { 0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f };
+    static const float h_spec[5] = { 0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f }, h_wrong[5] = { 0.0625f, 0.25f, 0.375f, 0.25f, 0.125f };
+    const float *h = variant == DRV_WRONG_TAP ? h_wrong : h_spec;
     const int s = 1 << i;
     const int edge = !(p->flags & DR_NO_EDGE_STOPS);
     const float ic = 1.0f / (p->sigma_color * p->sigma_color);
-    const float ic_i = ic * (float)(1u << (2u * i));
-    const float in_ = 1.0f / p->sigma_normal;
-    const float ia = 1.0f / (p->sigma_albedo * p->sigma_albedo);
+    const float ic_i = clamp_scale(variant == DRV_SIGMA_C_FIXED ? ic : ic * (float)(1u << (2u * i)));
+    const float in_ = clamp_scale(1.0f / p->sigma_normal);
+    const float ia = clamp_scale(1.0f / (p->sigma_albedo * p->sigma_albedo));
+    const float sz = variant == DRV_XZ_NO_STEP ? 1.0f : (float)s;
 #pragma omp parallel for schedule(static)
     for (int y = 0; y < (int)H; ++y)
         for (int x = 0; x < (int)W; ++x) {
             const size_t ip = (size_t)y * W + x;
             const float *cp = src + ip * 4, *gp = g8 + ip * 8;
             const int miss_p = bits(gp[7]) == MISS;
+            const float iz = clamp_scale(1.0f / ((p->sigma_depth * gp[3]) * sz));
             float sw = 0.0f, sc[3] = { 0.0f, 0.0f, 0.0f };
             for (int dy = -2; dy <= 2; ++dy)
                 for (int dx = -2; dx <= 2; ++dx) {
@@ -116,7 +129,7 @@ static void pass(const float *src, const float *g8, uint32_t W, uint32_t H, cons
                     const size_t iq = (size_t)qy * W + qx;
                     const float *cq = src + iq * 4, *gq = g8 + iq * 8;
                     const int miss_q = bits(gq[7]) == MISS;
-                    if (miss_p != miss_q) continue;
+                    if (miss_p != miss_q && variant != DRV_NO_MISS_SKIP) continue;
                     float den = 1.0f;
                     if (edge) {
                         const float dc[3] = { cp[0] - cq[0], cp[1] - cq[1], cp[2] - cq[2] };
@@ -124,11 +137,11 @@ static void pass(const float *src, const float *g8, uint32_t W, uint32_t H, cons
                         float xn = 0.0f, xz = 0.0f, xa = 0.0f;
                         if (!miss_p) {
                             xn = fmaxf(0.0f, 1.0f - dot3(gp, gq)) * in_;
-                            xz = fabsf(gq[3] - gp[3]) * (1.0f / ((p->sigma_depth * gp[3]) * (float)s));
+                            xz = fabsf(gq[3] - gp[3]) * iz;
                             const float da[3] = { gp[4] - gq[4], gp[5] - gq[5], gp[6] - gq[6] };
                             xa = dot3(da, da) * ia;
                         }
-                        den = ((D(xc) * D(xn)) * D(xz)) * D(xa);
+                        den = ((Dv(xc, variant) * Dv(xn, variant)) * Dv(xz, variant)) * Dv(xa, variant);
                     }
                     const float w = (h[dx + 2] * h[dy + 2]) / den;
                     sw = sw + w;
@@ -136,7 +149,9 @@ static void pass(const float *src, const float *g8, uint32_t W, uint32_t H, cons
                 }
             const float r = 1.0f / sw;
             float *o = dst + ip * 4;
-            o[0] = sc[0] * r; o[1] = sc[1] * r; o[2] = sc[2] * r; o[3] = cp[3];
+            if (r <= FLT_MAX) { o[0] = sc[0] * r; o[1] = sc[1] * r; o[2] = sc[2] * r; }
+            else { o[0] = cp[0]; o[1] = cp[1]; o[2] = cp[2]; } /* every tap lost its weight, the centre's included: p is kept */
+            o[3] = cp[3];
         }
 }
 
@@ -152,9 +167,18 @@ int dr_filter(const float *rgba, const float *g8, uint32_t W, uint32_t H, const 
     for (int i = 0; i < n; ++i) {
         /* the last pass lands in out; the ones before alternate so that a pass never reads what it writes */
         float *dst = ((n - 1 - i) & 1) ? tmp : out;
-        pass(src, g8, W, H, &p, (uint32_t)i, dst);
+        pass(src, g8, W, H, &p, (uint32_t)i, DRV_SPEC, dst);
         src = dst;
     }
     free(tmp);
     return n;
+}
+
+/* Pass i (0-based, step 2^i) of §8.2 alone, src -> dst, in variant `variant` (DRV_*). Returns 0, or -1 for refused parameters or i > 7. */
+int dr_pass(const float *src, const float *g8, uint32_t W, uint32_t H, const dr_params *params, uint32_t i, int variant, float *dst)
+{
+    dr_params p;
+    if (dr_resolve(params, &p) < 0 || i > 7u) return -1;
+    pass(src, g8, W, H, &p, i, variant, dst);
+    return 0;
 }
