@@ -610,6 +610,10 @@ pt_status pt_scene_commit(pt_scene *s, uint32_t bvh_width)
     if (bvh_width == PT_BVH_WIDTH_8Q || oct) quantize_bvh8(s->bvh, s->packed_nodes);
     lap("quantise");
     if (!c) { s->committed = true; return PT_OK; } // detached scene: host-side blob only
+    // the traversal kernels fetch a node or a triangle record by a 32-bit byte offset from its array's base (kernels.hip record())
+    if (s->node_bytes() > (1ull << 32) || s->n_blob_tris() * 64u > (1ull << 32))
+        return fail(c, PT_ERR_UNSUPPORTED, "BVH of %llu node bytes and %llu triangle records: each array must stay within 4 GiB",
+                    (unsigned long long)s->node_bytes(), (unsigned long long)s->n_blob_tris());
 
     HIP_TRY(c, hipSetDevice(c->device));
     static_assert(sizeof(BvhSlot) == 32 && sizeof(BvhTri) == 48 && sizeof(pt_material) == 48, "blob layout");
@@ -648,6 +652,7 @@ pt_status pt_scene_commit(pt_scene *s, uint32_t bvh_width)
                     for (uint32_t j = 0; j < cnt; ++j) tri_unit[first + j] = u++;
                 }
             }
+            if ((uint64_t)u * 64u > (1ull << 32)) return fail(c, PT_ERR_UNSUPPORTED, "PTRT_UNIFIED: %u units exceed 4 GiB", u);
             std::vector<uint8_t> uni((size_t)u * 64);
             for (uint32_t i = 0; i < nn; ++i) {
                 uint8_t *nd = &uni[(size_t)node_unit[i] * 64];
