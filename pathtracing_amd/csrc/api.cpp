@@ -6,6 +6,7 @@
 #include "bvh_build.h"
 #include "refit.h"
 #include "denoise.h"
+#include "device_owner.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
@@ -35,23 +36,6 @@ uint32_t host_pcg(uint32_t x)
     uint32_t w = ((s >> ((s >> 28) + 4u)) ^ s) * 277803737u;
     return (w >> 22) ^ w;
 }
-
-thread_local uint64_t g_device_allocs = 0; // counts DevBuf allocations: a frame that had to allocate is a cold frame (its rate is not a measurement)
-
-template <typename T> struct DevBuf {
-    T *p = nullptr; size_t n = 0;
-    hipError_t ensure(size_t count)
-    {
-        if (p && count <= n && (n <= (1u << 20) || count >= n / 4)) return hipSuccess; // big enough, and not more than 4x too big
-        ++g_device_allocs;
-        if (p) { (void)hipFree(p); p = nullptr; n = 0; }
-        hipError_t e = hipMalloc((void **)&p, (count ? count : 1) * sizeof(T));
-        if (e == hipSuccess) n = count ? count : 1;
-        return e;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-    void adopt(void *q, size_t count) { release(); p = (T *)q; n = count; } // take over a hipMalloc-ed array
-};
 
 // Which extend kernel a frame runs. A frame's PT_FLAG_EXTEND_* beats pt_tuning.extend_kernel, which beats the scene's own choice, measured:
 //   inside a frame : iteration 2 of group 0 runs the one-ray-per-lane kernel, iteration 3 the lane-packing one (bit-identical results), each
@@ -85,7 +69,7 @@ struct ExtendFrame {            // the choice during one frame
     uint32_t bounces(uint32_t g, uint32_t it, int k, uint32_t simple) const { return k != EXT_PACKED ? simple : probing(g, it) ? 8u : 64u; }
     // loop g's readback of iteration `it`, which traced `traced` rays; by iteration 3's, both probe iterations and their events `ev` (start and
     // end of each, pt_context::ev_probe) are complete
-    hipError_t observe(uint32_t g, uint32_t it, uint64_t traced, uint32_t loop_slots, const hipEvent_t *ev)
+    hipError_t observe(uint32_t g, uint32_t it, uint64_t traced, uint32_t loop_slots, const Event *ev)
     {
         if (!probing(g, it)) return hipSuccess;
         probe_n[it - 2u] = traced;
@@ -111,10 +95,11 @@ struct ExtendFrame {            // the choice during one frame
 
 } // namespace
 
+// Every device buffer, event, stream and pinned block below is an owner of device_owner.h: declaring it here is all it takes, the destructor
+// gives it back. pt_context_destroy drains the streams in its body before any member goes, so the order of the members is free.
 struct pt_context {
     int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+    Stream stream;                  // pt_device_desc::stream (borrowed) or the context's own
     std::string err;
     // path state
     DevBuf<float4> ray_o, ray_d, thr, acc, tiles, fb;
@@ -139,12 +124,12 @@ struct pt_context {
                      bool operator==(const InitKey &o) const { return std::memcmp(this, &o, sizeof *this) == 0; } } init_key{};
     bool init_valid = false;
     uint32_t init_bound = 0; // longest shard queue of the template: the first launch's grid bound
-    uint32_t *h_counts = nullptr; // pinned: kLag readbacks of the per-shard queue sizes (pt_tuning.readback = 1) + one copy of all counters
-    uint4 *h_ring = nullptr, *d_ring = nullptr; // mapped pinned memory the extend kernels report their queue sizes to, kLag x kShards lines
-                                                // (host address, device address); PathState::host_ring
-    hipEvent_t ev_lag[kMaxGroups][kLag] = {};
-    hipStream_t group_stream[kMaxGroups] = {}; // group 0 runs on `stream` when there is one group only
-    hipEvent_t ev_fork = nullptr, ev_join[kMaxGroups] = {};
+    Pinned<uint32_t> h_counts;    // kLag readbacks of the per-shard queue sizes (pt_tuning.readback = 1) + one copy of all counters
+    Pinned<uint4> h_ring;         // mapped: the extend kernels report their queue sizes to it, kLag x kShards lines (.p host address, .d device
+                                  // address; PathState::host_ring)
+    Event ev_lag[kMaxGroups][kLag];
+    Stream group_stream[kMaxGroups]; // group 0 runs on `stream` when there is one group only
+    Event ev_fork, ev_join[kMaxGroups];
     pt_tuning tuning = { // the scheduling knobs (include/ptrt.h): defaults and the measurements behind them
         0,    // bounces (1..64): path vertices per launch of the fused kernel (state in registers); 0 = 3/4 max_depth - 2 clamped to
               // [4, 12]: depth 8 -> 4, depth 16 -> 10 (ms per frame with 2 / 3 / 4 / 6 / 8 / 12 vertices: 1M-triangle Cornell, depth 8:
@@ -164,9 +149,9 @@ struct pt_context {
         0,    // extend_kernel: 0 = probed per scene (ExtendChoice), else the ExtendKernel every scene uses
         0,    // readback: 0 = the kernels store the sizes to h_ring, 1 = one 2-4 KB copy per launch (pt_context_create falls back to it)
     };
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-    hipEvent_t ev_probe[4] = {}; // brackets of the two probe iterations that pick the extend kernel
-    std::vector<hipEvent_t> ev_pool;
+    Event ev_start, ev_stop;
+    Event ev_probe[4];           // brackets of the two probe iterations that pick the extend kernel
+    std::vector<Event> ev_pool;  // PT_FLAG_PROFILE_KERNELS: three per iteration, made when a frame first needs them (pool_event)
     uint32_t fb_w = 0, fb_h = 0;
     uint32_t n_slots = 0; // slots of the last path-traced frame (acc layout)
     bool fb_valid = false;
@@ -175,7 +160,7 @@ struct pt_context {
     DevBuf<uint32_t> trace_cnt;
     DevBuf<int32_t> trace_ovf;
     DevBuf<float4> trace_rays, trace_hits;
-    hipEvent_t ev_trace[2] = {};
+    Event ev_trace[2];
     bool fb_reference = false;       // the framebuffer holds a PT_REFERENCE_SPHERE frame (pt_denoise refuses it)
     // pt_denoise (docs/SPEC.md §8): guide rays (2 rows per pixel; then the filter's two ping-pong images), their hits, the two guide
     // planes and the denoised image of a dn_w x dn_h framebuffer. dn_guides / dn_image: what the read functions may hand out (until the
@@ -183,7 +168,7 @@ struct pt_context {
     DevBuf<float4> dn_work, dn_hits, dn_g0, dn_g1, dn_out;
     uint32_t dn_w = 0, dn_h = 0;
     bool dn_guides = false, dn_image = false;
-    hipEvent_t ev_denoise[3] = {};   // start, guides done, filter done
+    Event ev_denoise[3];             // start, guides done, filter done (made by the first pt_denoise)
 };
 
 struct pt_scene {
@@ -219,7 +204,7 @@ struct pt_scene {
         DevBuf<float> verts[2];              // verts[cur]: the scene's current vertices once an update has run; the other one takes the next
         DevBuf<double> sah;                  // per-block partial sums, then the total
         uint32_t cur = 0;
-        hipEvent_t ev[4] = {};
+        Event ev[4];
     } refit;
     bool verts_on_device = false;        // `verts` is stale: the current vertices are refit.verts[refit.cur] (fetched when a commit needs them)
     // The light table of next-event estimation (docs/SPEC.md §7, build_lights): made at every commit and every triangle update from the
@@ -254,6 +239,15 @@ pt_status fail(pt_context *ctx, pt_status code, const char *fmt, ...)
     } while (0)
 
 bool finite3(const float *p) { return std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]); }
+bool sphere_ok(const float *cxyzr) { return finite3(cxyzr) && cxyzr[3] > 0.f && std::isfinite(cxyzr[3]); } // finite centre, finite radius > 0
+
+// The device's {material id, bits of 1.0f / r} per sphere (IEEE single division: the value docs/SPEC.md §5 has the shading step compute)
+std::vector<uint2> sphere_mats(const uint32_t *mat, const float *cxyzr, size_t n)
+{
+    std::vector<uint2> mi(n);
+    for (size_t i = 0; i < n; ++i) { const float inv_r = 1.0f / cxyzr[i * 4 + 3]; mi[i].x = mat[i]; std::memcpy(&mi[i].y, &inv_r, 4); }
+    return mi;
+}
 
 // docs/SPEC.md §7: the light set, its f32 CDF and the per-light records from the current vertices of the candidates (9 floats each, in
 // candidate order), uploaded to the scene's device arrays. Area, normal and pa in the op order of §0 / §7; the weights in double.
@@ -318,9 +312,9 @@ pt_status layout_of(const pt_render_params *p, pt_tile_layout *o)
 hipEvent_t pool_event(pt_context *c, size_t i)
 {
     while (c->ev_pool.size() <= i) {
-        hipEvent_t e = nullptr;
-        if (hipEventCreate(&e) != hipSuccess) return nullptr;
-        c->ev_pool.push_back(e);
+        Event e;
+        if (e.create() != hipSuccess) return nullptr;
+        c->ev_pool.push_back(std::move(e));
     }
     return c->ev_pool[i];
 }
@@ -329,6 +323,15 @@ void drain(pt_context *c) // nothing of the context's may still run: on its loop
 {
     for (auto &gs : c->group_stream) if (gs) (void)hipStreamSynchronize(gs);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+}
+
+// The public half of a call that enqueues work: an error exit may leave kernels or copies in flight (on the loop streams too), and nothing
+// of a failed call runs on after it
+template <typename Call> pt_status drained_on_failure(pt_context *c, Call call)
+{
+    const pt_status st = call();
+    if (st != PT_OK && c) { (void)hipSetDevice(c->device); drain(c); }
+    return st;
 }
 
 struct Frame {                  // a path-traced frame as plan_frame lays it out, and what its loops leave for finish_frame
@@ -376,35 +379,19 @@ pt_status pt_context_create(const pt_device_desc *desc, pt_context **out)
     pt_context *c = new (std::nothrow) pt_context();
     if (!c) return fail(nullptr, PT_ERR_OUT_OF_MEMORY, "host allocation failed");
     c->device = dev;
-    if (desc && desc->stream) { c->stream = (hipStream_t)desc->stream; c->own_stream = false; }
-    else {
-        e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-        if (e != hipSuccess) { delete c; return fail(nullptr, PT_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e)); }
-        c->own_stream = true;
-    }
-    bool ok = hipHostMalloc((void **)&c->h_counts, sizeof(uint32_t) * (kFinalOffset + kCntTotalWords), hipHostMallocDefault) == hipSuccess;
-    if (ok) { // host-mapped ring for the kernels' own size reports; a platform without mapped pinned memory falls back to a copy per launch
-        if (hipHostMalloc((void **)&c->h_ring, sizeof(uint4) * kLag * kShards, hipHostMallocMapped) == hipSuccess &&
-            hipHostGetDevicePointer((void **)&c->d_ring, c->h_ring, 0) == hipSuccess && c->d_ring)
-            std::memset(c->h_ring, 0, sizeof(uint4) * kLag * kShards);
-        else {
-            if (c->h_ring) (void)hipHostFree(c->h_ring);
-            c->h_ring = c->d_ring = nullptr; c->tuning.readback = 1u;
-            (void)hipGetLastError();
-        }
-    }
-    for (uint32_t g = 0; ok && g < kMaxGroups; ++g) {
-        ok = hipStreamCreateWithFlags(&c->group_stream[g], hipStreamNonBlocking) == hipSuccess &&
-             hipEventCreateWithFlags(&c->ev_join[g], hipEventDisableTiming) == hipSuccess;
-    }
-    ok = ok && hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipEventCreate(&c->ev_start) == hipSuccess && hipEventCreate(&c->ev_stop) == hipSuccess;
-    for (uint32_t g = 0; g < kMaxGroups; ++g)
-        for (uint32_t i = 0; ok && i < kLag; ++i) ok = hipEventCreateWithFlags(&c->ev_lag[g][i], hipEventDisableTiming) == hipSuccess;
-    for (uint32_t i = 0; ok && i < 4; ++i) ok = hipEventCreate(&c->ev_probe[i]) == hipSuccess;
-    for (uint32_t i = 0; ok && i < 2; ++i) ok = hipEventCreate(&c->ev_trace[i]) == hipSuccess;
+    if (desc && desc->stream) c->stream.borrow((hipStream_t)desc->stream);
+    else if ((e = c->stream.create()) != hipSuccess) { delete c; return fail(nullptr, PT_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e)); } // (the text this failure has always had)
+    bool ok = c->h_counts.alloc(kFinalOffset + kCntTotalWords) == hipSuccess;
+    // host-mapped ring for the kernels' own size reports; a platform without mapped pinned memory falls back to a copy per launch
+    if (ok && c->h_ring.alloc(kLag * kShards, true) == hipSuccess) std::memset(c->h_ring.p, 0, sizeof(uint4) * kLag * kShards);
+    else if (ok) { c->tuning.readback = 1u; (void)hipGetLastError(); }
+    for (uint32_t g = 0; ok && g < kMaxGroups; ++g) ok = c->group_stream[g].create() == hipSuccess && c->ev_join[g].create(false) == hipSuccess;
+    ok = ok && c->ev_fork.create(false) == hipSuccess && c->ev_start.create() == hipSuccess && c->ev_stop.create() == hipSuccess;
+    for (auto &row : c->ev_lag) for (auto &ev : row) ok = ok && ev.create(false) == hipSuccess;
+    for (auto &ev : c->ev_probe) ok = ok && ev.create() == hipSuccess;
+    for (auto &ev : c->ev_trace) ok = ok && ev.create() == hipSuccess;
     ok = ok && c->counters.ensure(kCntTotalWords) == hipSuccess;
-    if (!ok) { pt_context_destroy(c); return fail(nullptr, PT_ERR_HIP, "context resource creation failed"); }
+    if (!ok) { delete c; return fail(nullptr, PT_ERR_HIP, "context resource creation failed"); } // nothing runs yet: the owners give back what was made
     *out = c;
     return PT_OK;
 }
@@ -427,7 +414,7 @@ pt_status pt_context_set_tuning(pt_context *c, const pt_tuning *t)
         return fail(c, PT_ERR_INVALID_ARGUMENT, "tuning: compact_below must be in [0,2], sparse_below in [0,1]");
     if (t->extend_kernel > (uint32_t)EXT_POOL) return fail(c, PT_ERR_INVALID_ARGUMENT, "tuning: extend_kernel must be 0 (probed), 1 (one ray per lane), 2 (lane-packing) or 3 (pooled)");
     if (t->readback > 1) return fail(c, PT_ERR_INVALID_ARGUMENT, "tuning: readback must be 0 (mapped store) or 1 (copy per launch)");
-    if (t->readback == 0 && !c->d_ring) return fail(c, PT_ERR_UNSUPPORTED, "tuning: readback 0 needs host-mapped pinned memory, which this platform did not provide");
+    if (t->readback == 0 && !c->h_ring.d) return fail(c, PT_ERR_UNSUPPORTED, "tuning: readback 0 needs host-mapped pinned memory, which this platform did not provide");
     c->tuning = *t; // all or nothing: a refused call changes no field
     return PT_OK;
 }
@@ -436,25 +423,7 @@ void pt_context_destroy(pt_context *c)
 {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    drain(c); // nothing may still run on the buffers released below
-    c->ray_o.release(); c->ray_d.release(); c->thr.release(); c->acc.release(); c->tiles.release(); c->fb.release(); c->hit.release();
-    c->sd.release(); c->q_ext0.release(); c->q_ext1.release(); c->counters.release(); c->fb8.release(); c->stack_ovf.release();
-    c->q_init.release(); c->cnt_init.release(); c->q_metal.release(); c->q_dielectric.release();
-    c->trace_cnt.release(); c->trace_ovf.release(); c->trace_rays.release(); c->trace_hits.release();
-    c->dn_work.release(); c->dn_hits.release(); c->dn_g0.release(); c->dn_g1.release(); c->dn_out.release();
-    if (c->h_counts) (void)hipHostFree(c->h_counts);
-    if (c->h_ring) (void)hipHostFree(c->h_ring);
-    for (auto &row : c->ev_lag) for (auto &e : row) if (e) (void)hipEventDestroy(e);
-    for (auto &e : c->ev_join) if (e) (void)hipEventDestroy(e);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    for (auto &gs : c->group_stream) if (gs) (void)hipStreamDestroy(gs);
-    for (auto &e : c->ev_probe) if (e) (void)hipEventDestroy(e);
-    for (auto &e : c->ev_trace) if (e) (void)hipEventDestroy(e);
-    for (auto &e : c->ev_denoise) if (e) (void)hipEventDestroy(e);
-    if (c->ev_start) (void)hipEventDestroy(c->ev_start);
-    if (c->ev_stop) (void)hipEventDestroy(c->ev_stop);
-    for (auto e : c->ev_pool) (void)hipEventDestroy(e);
-    if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
+    drain(c); // nothing may still run on what the members give back
     delete c;
 }
 
@@ -476,10 +445,6 @@ void pt_scene_destroy(pt_scene *s)
 {
     if (!s) return;
     if (s->ctx) { (void)hipSetDevice(s->ctx->device); (void)hipStreamSynchronize(s->ctx->stream); }
-    s->d_nodes.release(); s->d_tris.release();s->d_spheres.release(); s->d_mats.release(); s->d_sph_mat.release(); s->d_blob_of.release();
-    auto &R = s->refit;
-    R.list.release(); R.flag.release(); R.tbox.release(); R.nbox.release(); R.carea.release(); R.verts[0].release(); R.verts[1].release(); R.sah.release();
-    for (auto &e : R.ev) if (e) (void)hipEventDestroy(e);
     delete s;
 }
 
@@ -503,8 +468,7 @@ pt_status pt_scene_set_spheres(pt_scene *s, const float *cxyzr, const uint32_t *
     if (count && !cxyzr) return fail(s->ctx, PT_ERR_INVALID_ARGUMENT, "cxyzr is NULL");
     if (count > kMaxSpheres) return fail(s->ctx, PT_ERR_UNSUPPORTED, "more than %u spheres (they are a flat list)", kMaxSpheres);
     for (uint64_t i = 0; i < count; ++i)
-        if (!finite3(cxyzr + i * 4) || !(cxyzr[i * 4 + 3] > 0.f) || !std::isfinite(cxyzr[i * 4 + 3]))
-            return fail(s->ctx, PT_ERR_INVALID_ARGUMENT, "sphere %llu: non-finite centre or radius <= 0", (unsigned long long)i);
+        if (!sphere_ok(cxyzr + i * 4)) return fail(s->ctx, PT_ERR_INVALID_ARGUMENT, "sphere %llu: non-finite centre or radius <= 0", (unsigned long long)i);
     s->spheres.assign(cxyzr, cxyzr + count * 4);
     if (material_ids) s->sph_mat.assign(material_ids, material_ids + count); else s->sph_mat.assign(count, 0u);
     s->committed = false;
@@ -590,8 +554,7 @@ pt_status pt_scene_commit(pt_scene *s, uint32_t bvh_width)
         HIP_TRY(c, hipSetDevice(c->device));
         DeviceBlob4Q db;
         HIP_TRY(c, build_lbvh_blob4q_device(c->stream, s->verts.data(), s->tri_mat.data(), nt, db));
-        s->d_nodes.adopt(db.nodes, (size_t)db.n_nodes * 4);
-        s->d_tris.adopt(db.tris, (size_t)nt * 4);
+        s->d_nodes = std::move(db.nodes); s->d_tris = std::move(db.tris); // (the scene's earlier arrays are freed here)
         s->bvh = BvhBlob{};
         s->bvh.width = 4; s->bvh.n_nodes = db.n_nodes; s->bvh.max_depth = db.max_depth; s->bvh.stack_need = db.stack_need;
         s->bvh.sah_cost = db.sah_cost; s->bvh.build_ms = db.device_ms;
@@ -681,12 +644,7 @@ pt_status pt_scene_commit(pt_scene *s, uint32_t bvh_width)
     HIP_TRY(c, s->d_mats.ensure((size_t)nm * 3));
     if (ns) {
         HIP_TRY(c, hipMemcpy(s->d_spheres.p, s->spheres.data(), (size_t)ns * 16, hipMemcpyHostToDevice));
-        std::vector<uint2> mi(ns);
-        for (uint32_t i = 0; i < ns; ++i) { // material id + 1.0f / r (IEEE single division: the value docs/SPEC.md §5 has the shading step compute)
-            const float inv_r = 1.0f / s->spheres[(size_t)i * 4 + 3];
-            mi[i].x = s->sph_mat[i]; std::memcpy(&mi[i].y, &inv_r, 4);
-        }
-        HIP_TRY(c, hipMemcpy(s->d_sph_mat.p, mi.data(), (size_t)ns * sizeof(uint2), hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(s->d_sph_mat.p, sphere_mats(s->sph_mat.data(), s->spheres.data(), ns).data(), (size_t)ns * sizeof(uint2), hipMemcpyHostToDevice));
     }
     if (nm) HIP_TRY(c, hipMemcpy(s->d_mats.p, s->mats.data(), (size_t)nm * sizeof(pt_material), hipMemcpyHostToDevice));
     lap("upload nodes + rest");
@@ -878,7 +836,7 @@ static pt_status plan_frame(pt_context *c, const pt_scene *s, const pt_render_pa
     ps.counters = c->counters.p; ps.stack_ovf = c->stack_ovf.p; ps.stack_ovf_entries = ovf; ps.n_slots = f.n_slots; ps.shard_cap = f.shard_cap;
     ps.shard_base = 0; ps.shard_count = kShards; ps.compact_below = t.compact_below; ps.finish_below = t.finish_below; ps.sparse_below = t.sparse_below;
     ps.repack_sticky = (f.samples_per_stream <= t.sticky_samples && t.compact_below > 0.f) ? 1u : 0u;
-    ps.host_ring = f.mapped ? c->d_ring : nullptr; ps.ring_slots = kLag;
+    ps.host_ring = f.mapped ? c->h_ring.d : nullptr; ps.ring_slots = kLag;
     // re-packing forced: buckets re-append (no fixed positions), or next to nothing regenerates (every launch leaves holes)
     f.compact = f.bucket || (ps.repack_sticky && f.samples_per_stream <= 2u);
     FrameParams &fp = f.fp;
@@ -912,10 +870,10 @@ static pt_status start_frame(pt_context *c, const pt_scene *s, const pt_render_p
             HIP_TRY(c, launch_generate(q, s->ds, pt, f.fp, dense ? 2u : 0u)); // also zeroes every slot's sum unless the frame accumulates
             c->init_bound = f.shard_cap;
             if (dense) {
-                HIP_TRY(c, hipMemcpyAsync(c->h_counts + kFinalOffset, c->cnt_init.p, sizeof(uint32_t) * kShards * kCounterStride, hipMemcpyDeviceToHost, q));
+                HIP_TRY(c, hipMemcpyAsync(c->h_counts.p + kFinalOffset, c->cnt_init.p, sizeof(uint32_t) * kShards * kCounterStride, hipMemcpyDeviceToHost, q));
                 HIP_TRY(c, hipStreamSynchronize(q));
                 c->init_bound = 0;
-                for (uint32_t sh = 0; sh < kShards; ++sh) c->init_bound = std::max(c->init_bound, c->h_counts[kFinalOffset + cnt_ext_index(0, sh)]);
+                for (uint32_t sh = 0; sh < kShards; ++sh) c->init_bound = std::max(c->init_bound, c->h_counts.p[kFinalOffset + cnt_ext_index(0, sh)]);
             }
             c->init_key = key; c->init_valid = true;
         }
@@ -959,7 +917,7 @@ static pt_status run_loops(pt_context *c, const pt_scene *s, const pt_render_par
             hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
             if (f.profile) {
                 e0 = pool_event(c, f.n_events++); e1 = pool_event(c, f.n_events++); e2 = pool_event(c, f.n_events++);
-                if (!e0 || !e1 || !e2) return fail(c, PT_ERR_HIP, "hipEventCreate failed");
+                if (!e0 || !e1 || !e2) return fail(c, PT_ERR_HIP, "hipEventCreate failed"); // (the text this failure has always had)
                 HIP_TRY(c, hipEventRecord(e0, L.stream));
             }
             const bool probing = x.probing(g, it); const int kernel = x.launch_kernel(g, it, f.split);
@@ -975,7 +933,7 @@ static pt_status run_loops(pt_context *c, const pt_scene *s, const pt_render_par
             if (f.profile) HIP_TRY(c, hipEventRecord(e2, L.stream));
             const uint32_t ring = L.iters % kLag;
             if (!f.mapped) {
-                uint32_t *h_ring = c->h_counts + ((size_t)g * kLag + ring) * kRingWords;
+                uint32_t *h_ring = c->h_counts.p + ((size_t)g * kLag + ring) * kRingWords;
                 HIP_TRY(c, hipMemcpyAsync(h_ring, c->counters.p + cnt_ext_index((it + 1u) % 3u, L.base), sizeof(uint32_t) * per_group * kCounterStride,
                                           hipMemcpyDeviceToHost, L.stream));
             }
@@ -985,8 +943,8 @@ static pt_status run_loops(pt_context *c, const pt_scene *s, const pt_render_par
             const uint32_t old_iter = L.iters - f.lag; // iteration old_iter traced `traced` rays and left `total` paths alive: its survivors bound every later queue
             // mapped: launch old_iter + 1 stored old_iter's lines (fold_traced); it is at most the launch just enqueued since lag >= 2
             HIP_TRY(c, hipEventSynchronize(c->ev_lag[g][(f.mapped ? old_iter + 1u : old_iter) % kLag]));
-            const volatile uint32_t *h_old = f.mapped ? (const volatile uint32_t *)(c->h_ring + (size_t)(old_iter % kLag) * kShards + L.base)
-                                                      : c->h_counts + ((size_t)g * kLag + old_iter % kLag) * kRingWords;
+            const volatile uint32_t *h_old = f.mapped ? (const volatile uint32_t *)(c->h_ring.p + (size_t)(old_iter % kLag) * kShards + L.base)
+                                                      : c->h_counts.p + ((size_t)g * kLag + old_iter % kLag) * kRingWords;
             // a shard's line: word 0 = queue length (holes included), word 1 = alive entries, words 2-3 = rays the iteration traced
             const uint32_t line = f.mapped ? 4u : kCounterStride;
             uint32_t mx = 0; uint64_t total = 0, traced = 0;
@@ -1018,9 +976,9 @@ static pt_status finish_frame(pt_context *c, const pt_render_params *p, const Fr
     if (f.nranks == 1)
         HIP_TRY(c, launch_assemble(q, c->tiles.p, 1, f.pixel_slots, p->width, p->height, fp.tiles_x, fp.n_tiles, 1.0f / (float)f.total_spp, c->fb.p, c->fb8.p));
     HIP_TRY(c, hipEventRecord(c->ev_stop, q));
-    HIP_TRY(c, hipMemcpyAsync(c->h_counts + kFinalOffset, c->counters.p, sizeof(uint32_t) * kCntTotalWords, hipMemcpyDeviceToHost, q));
+    HIP_TRY(c, hipMemcpyAsync(c->h_counts.p + kFinalOffset, c->counters.p, sizeof(uint32_t) * kCntTotalWords, hipMemcpyDeviceToHost, q));
     HIP_TRY(c, hipStreamSynchronize(q));
-    pt_stats out; std::memset(&out, 0, sizeof out); const uint32_t *hc = c->h_counts + kFinalOffset;
+    pt_stats out{}; const uint32_t *hc = c->h_counts.p + kFinalOffset;
     if (hc[kCntError]) return fail(c, PT_ERR_INTERNAL, "device error flag 0x%x (1 = traversal stack overflow, 2 = step limit)", hc[kCntError]);
     auto u64_at = [&](uint32_t w) { return (uint64_t)hc[w] | ((uint64_t)hc[w + 1] << 32); };
     for (uint32_t sh = 0; sh < kShards; ++sh) {
@@ -1083,7 +1041,7 @@ static pt_status render_frame(pt_context *c, const pt_scene *s, const pt_render_
         HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         float ms = 0.f; HIP_TRY(c, hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
-        pt_stats out; std::memset(&out, 0, sizeof out);
+        pt_stats out{};
         out.gpu_ms = ms; out.other_ms = ms; out.rays = out.paths = (uint64_t)p->width * p->height; out.iterations = 1;
         c->fb_valid = true; c->fb_reference = true; if (stats) *stats = out;
         return PT_OK;
@@ -1099,12 +1057,8 @@ static pt_status render_frame(pt_context *c, const pt_scene *s, const pt_render_
 
 pt_status pt_render(pt_context *c, const pt_scene *s, const pt_render_params *p, pt_stats *stats)
 {
-    const pt_status st = render_frame(c, s, p, stats);
-    if (st != PT_OK && c) { // an error exit may leave kernels in flight on the loop streams: nothing of this frame survives the call
-        (void)hipSetDevice(c->device);
-        drain(c);
-        c->acc_spp = 0; c->fb_valid = false;
-    }
+    const pt_status st = drained_on_failure(c, [&] { return render_frame(c, s, p, stats); });
+    if (st != PT_OK && c) { c->acc_spp = 0; c->fb_valid = false; } // nothing of this frame survives the call
     return st;
 }
 
@@ -1174,7 +1128,7 @@ static pt_status trace_rays(pt_context *c, const pt_scene *s, const void *rays, 
     if (s->ctx != c) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_trace_rays: scene belongs to another context");
     if (!s->committed) return fail(c, PT_ERR_NOT_COMMITTED, "scene not committed");
     if (n_rays >> 40) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_trace_rays: n_rays %llu is not a batch size", (unsigned long long)n_rays);
-    pt_stats out; std::memset(&out, 0, sizeof out);
+    pt_stats out{};
     out.rays = n_rays;
     if (n_rays == 0) { if (stats) *stats = out; return PT_OK; }
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1208,9 +1162,7 @@ static pt_status trace_rays(pt_context *c, const pt_scene *s, const void *rays, 
 
 pt_status pt_trace_rays(pt_context *c, const pt_scene *s, const void *rays, void *hits, uint64_t n_rays, uint32_t flags, pt_stats *stats)
 {
-    const pt_status st = trace_rays(c, s, rays, hits, n_rays, flags, stats);
-    if (st != PT_OK && c) { (void)hipSetDevice(c->device); drain(c); } // nothing of a failed query (e.g. a copy into `hits`) runs on after the call
-    return st;
+    return drained_on_failure(c, [&] { return trace_rays(c, s, rays, hits, n_rays, flags, stats); }); // (e.g. a copy into `hits`)
 }
 
 // ------------------------------------------------------------------------------------------------ geometry updates (docs/SPEC.md §4.3)
@@ -1222,7 +1174,7 @@ static pt_status prepare_refit(pt_scene *s)
     pt_context *c = s->ctx;
     auto &R = s->refit;
     const uint32_t nn = s->bvh.n_nodes, fan = s->bvh.width, nbt = (uint32_t)s->n_blob_tris(), nt = (uint32_t)s->tri_mat.size();
-    for (auto &e : R.ev) if (!e) HIP_TRY(c, hipEventCreate(&e));
+    for (auto &e : R.ev) HIP_TRY(c, e.create());
     std::vector<int32_t> refs((size_t)nn * fan);
     if (s->device_packed) { // BVH4Q nodes that never visited the host: their four refs (bytes 16-31 of every 64-byte node)
         if (nn) HIP_TRY(c, hipMemcpy2D(refs.data(), 16, (const uint8_t *)s->d_nodes.p + 16, 64, 16, nn, hipMemcpyDeviceToHost));
@@ -1255,7 +1207,7 @@ static pt_status update_triangles(pt_scene *s, const void *verts9, uint64_t coun
     }
     if (!c) return fail(c, PT_ERR_UNSUPPORTED, "pt_scene_update_triangles: a detached scene has no device tree to refit (set the triangles and commit)");
     if (s->unified) return fail(c, PT_ERR_UNSUPPORTED, "pt_scene_update_triangles: not for a scene committed under PTRT_UNIFIED");
-    pt_stats out; std::memset(&out, 0, sizeof out);
+    pt_stats out{};
     if (count == 0) { if (stats) *stats = out; return PT_OK; }
     HIP_TRY(c, hipSetDevice(c->device));
     pt_status st;
@@ -1318,18 +1270,13 @@ static pt_status update_spheres(pt_scene *s, const float *cxyzr, uint64_t count)
     const uint64_t ns = s->sph_mat.size();
     if (count != ns) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_scene_update_spheres: count %llu, the scene was committed with %llu spheres", (unsigned long long)count, (unsigned long long)ns);
     if (count && !cxyzr) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_scene_update_spheres: cxyzr is NULL");
-    for (uint64_t i = 0; i < count; ++i) // the rule of pt_scene_set_spheres
-        if (!finite3(cxyzr + i * 4) || !(cxyzr[i * 4 + 3] > 0.f) || !std::isfinite(cxyzr[i * 4 + 3]))
-            return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_scene_update_spheres: sphere %llu: non-finite centre or radius <= 0", (unsigned long long)i);
+    for (uint64_t i = 0; i < count; ++i)
+        if (!sphere_ok(cxyzr + i * 4)) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_scene_update_spheres: sphere %llu: non-finite centre or radius <= 0", (unsigned long long)i);
     if (!c) return fail(c, PT_ERR_UNSUPPORTED, "pt_scene_update_spheres: a detached scene has no device copy to update (set the spheres and commit)");
     if (s->unified) return fail(c, PT_ERR_UNSUPPORTED, "pt_scene_update_spheres: not for a scene committed under PTRT_UNIFIED");
     if (count == 0) return PT_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    std::vector<uint2> mi(count);
-    for (uint64_t i = 0; i < count; ++i) { // material id + 1.0f / r, as pt_scene_commit makes them
-        const float inv_r = 1.0f / cxyzr[i * 4 + 3];
-        mi[i].x = s->sph_mat[i]; std::memcpy(&mi[i].y, &inv_r, 4);
-    }
+    const std::vector<uint2> mi = sphere_mats(s->sph_mat.data(), cxyzr, count);
     hipStream_t q = c->stream;
     HIP_TRY(c, hipMemcpyAsync(s->d_spheres.p, cxyzr, count * 16u, hipMemcpyHostToDevice, q));
     HIP_TRY(c, hipMemcpyAsync(s->d_sph_mat.p, mi.data(), count * sizeof(uint2), hipMemcpyHostToDevice, q));
@@ -1340,16 +1287,12 @@ static pt_status update_spheres(pt_scene *s, const float *cxyzr, uint64_t count)
 
 pt_status pt_scene_update_triangles(pt_scene *s, const void *verts9, uint64_t count, uint32_t flags, pt_stats *stats)
 {
-    const pt_status st = update_triangles(s, verts9, count, flags, stats);
-    if (st != PT_OK && s && s->ctx) { (void)hipSetDevice(s->ctx->device); drain(s->ctx); } // nothing of a failed update runs on after the call
-    return st;
+    return drained_on_failure(s ? s->ctx : nullptr, [&] { return update_triangles(s, verts9, count, flags, stats); });
 }
 
 pt_status pt_scene_update_spheres(pt_scene *s, const float *cxyzr, uint64_t count)
 {
-    const pt_status st = update_spheres(s, cxyzr, count);
-    if (st != PT_OK && s && s->ctx) { (void)hipSetDevice(s->ctx->device); drain(s->ctx); }
-    return st;
+    return drained_on_failure(s ? s->ctx : nullptr, [&] { return update_spheres(s, cxyzr, count); });
 }
 
 // ------------------------------------------------------------------------------------------------ denoising (docs/SPEC.md §8)
@@ -1383,7 +1326,7 @@ static pt_status denoise(pt_context *c, const pt_scene *s, const pt_denoise_para
     const uint32_t w = c->fb_w, h = c->fb_h;
     const size_t n = (size_t)w * h;
     HIP_TRY(c, hipSetDevice(c->device));
-    for (auto &e : c->ev_denoise) if (!e) HIP_TRY(c, hipEventCreate(&e));
+    for (auto &e : c->ev_denoise) HIP_TRY(c, e.create());
     c->dn_guides = c->dn_image = false; // from here on the buffers are rewritten
     HIP_TRY(c, c->dn_work.ensure(2 * n)); HIP_TRY(c, c->dn_hits.ensure(n));
     HIP_TRY(c, c->dn_g0.ensure(n)); HIP_TRY(c, c->dn_g1.ensure(n));
@@ -1427,7 +1370,7 @@ static pt_status denoise(pt_context *c, const pt_scene *s, const pt_denoise_para
     float ms_guides = 0.f, ms_filter = 0.f;
     HIP_TRY(c, hipEventElapsedTime(&ms_guides, c->ev_denoise[0], c->ev_denoise[1]));
     HIP_TRY(c, hipEventElapsedTime(&ms_filter, c->ev_denoise[1], c->ev_denoise[2]));
-    pt_stats out; std::memset(&out, 0, sizeof out);
+    pt_stats out{};
     out.rays = n; out.iterations = passes;
     out.extend_ms = ms_guides; out.other_ms = ms_filter; out.gpu_ms = (double)ms_guides + ms_filter;
     c->dn_w = w; c->dn_h = h; c->dn_guides = true; c->dn_image = passes > 0;
@@ -1437,9 +1380,7 @@ static pt_status denoise(pt_context *c, const pt_scene *s, const pt_denoise_para
 
 pt_status pt_denoise(pt_context *c, const pt_scene *s, const pt_denoise_params *dp, pt_stats *stats)
 {
-    const pt_status st = denoise(c, s, dp, stats);
-    if (st != PT_OK && c) { (void)hipSetDevice(c->device); drain(c); } // nothing of a failed call runs on after it
-    return st;
+    return drained_on_failure(c, [&] { return denoise(c, s, dp, stats); });
 }
 
 pt_status pt_denoised_read(pt_context *c, float *rgba, uint64_t n_floats)

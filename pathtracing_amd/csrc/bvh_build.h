@@ -3,6 +3,7 @@
 #pragma once
 #include <stdint.h>
 #include <vector>
+#include "device_owner.h"
 
 namespace ptrt {
 
@@ -38,9 +39,9 @@ void build_bvh_from_binary(const BinaryBvh &bt, const float *verts9, const uint3
 void build_sah_over_boxes(const float *boxes6, uint32_t n, std::vector<int32_t> &left, std::vector<int32_t> &right, std::vector<float> &node_boxes6, int32_t &root);
 
 // What the GPU builder leaves on the device when it also packs the tree (lbvh.hip build_lbvh_blob4q_device): BVH4Q nodes and 64-byte
-// triangle records in hipMalloc-ed arrays the caller takes over.
+// triangle records in arrays the caller moves out.
 struct DeviceBlob4Q {
-    void *nodes = nullptr; void *tris = nullptr; // n_nodes x 64 B, n_tris x 64 B
+    DevBuf<float4> nodes, tris; // n_nodes x 64 B, n_tris x 64 B
     uint32_t n_nodes = 0, max_depth = 0, stack_need = 0;
     float sah_cost = 0.f;
     double device_ms = 0.0;

@@ -8,6 +8,7 @@
 // that torch already mapped (same SONAME) is the one that is used.
 // The reference has nothing like this (one logical device, GraphicsDevice.cs:176-183).
 #include "ptrt_internal.h"
+#include "device_owner.h"
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h> // types and prototypes only; the functions are resolved at run time
 #include <dlfcn.h>
@@ -68,8 +69,7 @@ struct pt_comm {
     bool shared = false;           // every rank on one context (virtual ranks)
     bool use_rccl = false;
     std::vector<ncclComm_t> comms; // per rank (use_rccl)
-    float *gathered = nullptr;     // root device: n_ranks blocks of tiles_per_rank * 4096 float4
-    uint64_t gathered_floats = 0;
+    DevBuf<float> gathered;        // root device: n_ranks blocks of tiles_per_rank * 4096 float4. Grow-only: callers compare with .n first
     std::vector<uint8_t> staged;   // shared contexts: which blocks pt_comm_stage_tiles has filled
     std::string err;
 };
@@ -97,12 +97,9 @@ pt_status ensure_gathered(pt_comm *c, const pt_render_params *p, uint64_t &per_r
     if (st != PT_OK) return cfail(c, st, "pt_comm: bad render params");
     per_rank_floats = (uint64_t)lay.tiles_per_rank * lay.floats_per_tile;
     const uint64_t need = per_rank_floats * c->ctx.size();
-    if (need > c->gathered_floats) {
+    if (need > c->gathered.n) {
         C_HIP(c, hipSetDevice(context_device(c->ctx[c->root])));
-        if (c->gathered) (void)hipFree(c->gathered);
-        c->gathered = nullptr; c->gathered_floats = 0;
-        C_HIP(c, hipMalloc((void **)&c->gathered, need * sizeof(float)));
-        c->gathered_floats = need;
+        C_HIP(c, c->gathered.ensure(need));
     }
     return PT_OK;
 }
@@ -155,7 +152,7 @@ void pt_comm_destroy(pt_comm *c)
     // Every pt_comm call returns with nothing of its own in flight (pt_comm_assemble waits for every rank's stream), so the
     // contexts are not needed here and may already be gone: the order of pt_comm_destroy and pt_context_destroy is free.
     for (size_t i = 0; i < c->comms.size(); ++i) if (c->comms[i]) { (void)hipSetDevice(c->dev[i]); (void)g_rccl.CommDestroy(c->comms[i]); }
-    if (c->gathered) { (void)hipSetDevice(c->dev[c->root]); (void)hipFree(c->gathered); }
+    if (c->gathered.p) (void)hipSetDevice(c->dev[c->root]); // the buffer goes with the object, on its own device
     delete c;
 }
 
@@ -166,16 +163,13 @@ pt_status pt_comm_stage_tiles(pt_comm *c, uint32_t rank)
     void *tiles = nullptr; uint64_t nf = 0;
     pt_status st = pt_tiles_device_ptr(c->ctx[rank], &tiles, &nf);
     if (st != PT_OK) return cfail(c, st, "pt_comm_stage_tiles: rank %u has no rendered tiles", rank);
-    if (nf * c->ctx.size() > c->gathered_floats) { // first frame of this size: allocate from the block size the context reports
+    if (nf * c->ctx.size() > c->gathered.n) { // first frame of this size: allocate from the block size the context reports
         C_HIP(c, hipSetDevice(context_device(c->ctx[c->root])));
-        if (c->gathered) (void)hipFree(c->gathered);
-        c->gathered = nullptr; c->gathered_floats = 0;
-        C_HIP(c, hipMalloc((void **)&c->gathered, nf * c->ctx.size() * sizeof(float)));
-        c->gathered_floats = nf * c->ctx.size();
+        C_HIP(c, c->gathered.ensure(nf * c->ctx.size()));
         std::fill(c->staged.begin(), c->staged.end(), 0);
     }
     hipStream_t s = context_stream(c->ctx[rank]);
-    C_HIP(c, hipMemcpyAsync(c->gathered + nf * rank, tiles, nf * sizeof(float), hipMemcpyDeviceToDevice, s));
+    C_HIP(c, hipMemcpyAsync(c->gathered.p + nf * rank, tiles, nf * sizeof(float), hipMemcpyDeviceToDevice, s));
     C_HIP(c, hipStreamSynchronize(s)); // the context's next pt_render rewrites its tile buffer
     c->staged[rank] = 1;
     return PT_OK;
@@ -195,7 +189,7 @@ pt_status pt_comm_assemble(pt_comm *c, const pt_render_params *p)
         if (st != PT_OK) return cfail(c, st, "pt_comm_assemble: bad render params");
         per_rank = (uint64_t)lay.tiles_per_rank * lay.floats_per_tile;
         for (uint32_t i = 0; i < n; ++i) if (!c->staged[i]) return cfail(c, PT_ERR_NOT_COMMITTED, "pt_comm_assemble: rank %u was not staged (pt_comm_stage_tiles)", i);
-        if (per_rank * n > c->gathered_floats) return cfail(c, PT_ERR_INVALID_ARGUMENT, "pt_comm_assemble: params do not match the staged blocks");
+        if (per_rank * n > c->gathered.n) return cfail(c, PT_ERR_INVALID_ARGUMENT, "pt_comm_assemble: params do not match the staged blocks");
         std::fill(c->staged.begin(), c->staged.end(), 0);
     } else {
         pt_status st = ensure_gathered(c, p, per_rank);
@@ -216,7 +210,7 @@ pt_status pt_comm_assemble(pt_comm *c, const pt_render_params *p)
             for (uint32_t i = 0; i < n && posted == PT_OK; ++i) {
                 const hipError_t he = hipSetDevice(context_device(c->ctx[i]));
                 if (he != hipSuccess) { posted = cfail(c, PT_ERR_HIP, "hipSetDevice (rank %u) failed: %s", i, hipGetErrorString(he)); break; }
-                const ncclResult_t r = g_rccl.Gather(tiles[i], c->gathered, per_rank, ncclFloat, (int)c->root, c->comms[i], context_stream(c->ctx[i]));
+                const ncclResult_t r = g_rccl.Gather(tiles[i], c->gathered.p, per_rank, ncclFloat, (int)c->root, c->comms[i], context_stream(c->ctx[i]));
                 if (r != ncclSuccess) { posted = cfail(c, PT_ERR_HIP, "ncclGather (rank %u) failed: %s", i, g_rccl.GetErrorString(r)); break; }
                 ++n_posted;
             }
@@ -232,7 +226,7 @@ pt_status pt_comm_assemble(pt_comm *c, const pt_render_params *p)
             for (uint32_t i = 0; i < n; ++i) {
                 const int dev = context_device(c->ctx[i]);
                 C_HIP(c, hipSetDevice(dev));
-                float *dst = c->gathered + (size_t)per_rank * i;
+                float *dst = c->gathered.p + (size_t)per_rank * i;
                 if (dev == rdev) C_HIP(c, hipMemcpyAsync(dst, tiles[i], per_rank * sizeof(float), hipMemcpyDeviceToDevice, context_stream(c->ctx[i])));
                 else C_HIP(c, hipMemcpyPeerAsync(dst, rdev, tiles[i], dev, per_rank * sizeof(float), context_stream(c->ctx[i])));
             }
@@ -241,7 +235,7 @@ pt_status pt_comm_assemble(pt_comm *c, const pt_render_params *p)
         }
     }
     // un-tile on the root: same stream as the root's receive, then the host waits (pt_assemble_tiles is synchronous)
-    pt_status st = pt_assemble_tiles(root, &q, c->gathered, per_rank * n);
+    pt_status st = pt_assemble_tiles(root, &q, c->gathered.p, per_rank * n);
     if (c->use_rccl) // the senders' halves of the gather: done once the root has received, waited for so that nothing outlives the call
         for (uint32_t i = 0; i < n; ++i)
             if (i != c->root) { (void)hipSetDevice(c->dev[i]); (void)hipStreamSynchronize(context_stream(c->ctx[i])); }

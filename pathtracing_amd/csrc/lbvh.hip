@@ -127,30 +127,23 @@ __global__ void __launch_bounds__(256) k_refit(const uint32_t *__restrict__ orde
     }
 }
 
-template <typename T> struct Dev {
-    T *p = nullptr;
-    hipError_t alloc(size_t n) { return hipMalloc((void **)&p, (n ? n : 1) * sizeof(T)); }
-    T *release() { T *q = p; p = nullptr; return q; }
-    ~Dev() { if (p) (void)hipFree(p); }
-};
-
 #define LB_TRY(x) do { hipError_t _e = (x); if (_e != hipSuccess) return _e; } while (0)
 
 // The binary LBVH on the device: construction shared by the two consumers below.
 struct Lbvh {
     uint32_t n = 0;
-    Dev<float> verts, leaf_box, cent, node_box;
-    Dev<uint32_t> bounds, keys, vals, keys2, order, first, last, arrived;
-    Dev<int32_t> left, right, pn, pl;
-    Dev<unsigned char> tmp;
+    DevBuf<float> verts, leaf_box, cent, node_box;
+    DevBuf<uint32_t> bounds, keys, vals, keys2, order, first, last, arrived;
+    DevBuf<int32_t> left, right, pn, pl;
+    DevBuf<unsigned char> tmp;
     hipError_t construct(hipStream_t stream, const float *verts9, uint32_t n_)
     {
         n = n_;
-        LB_TRY(verts.alloc((size_t)n * 9)); LB_TRY(leaf_box.alloc((size_t)n * 6)); LB_TRY(cent.alloc((size_t)n * 3));
-        LB_TRY(node_box.alloc((size_t)(n - 1) * 6)); LB_TRY(bounds.alloc(6));
-        LB_TRY(keys.alloc(n)); LB_TRY(vals.alloc(n)); LB_TRY(keys2.alloc(n)); LB_TRY(order.alloc(n));
-        LB_TRY(first.alloc(n - 1)); LB_TRY(last.alloc(n - 1)); LB_TRY(arrived.alloc(n - 1));
-        LB_TRY(left.alloc(n - 1)); LB_TRY(right.alloc(n - 1)); LB_TRY(pn.alloc(n - 1)); LB_TRY(pl.alloc(n));
+        LB_TRY(verts.ensure((size_t)n * 9)); LB_TRY(leaf_box.ensure((size_t)n * 6)); LB_TRY(cent.ensure((size_t)n * 3));
+        LB_TRY(node_box.ensure((size_t)(n - 1) * 6)); LB_TRY(bounds.ensure(6));
+        LB_TRY(keys.ensure(n)); LB_TRY(vals.ensure(n)); LB_TRY(keys2.ensure(n)); LB_TRY(order.ensure(n));
+        LB_TRY(first.ensure(n - 1)); LB_TRY(last.ensure(n - 1)); LB_TRY(arrived.ensure(n - 1));
+        LB_TRY(left.ensure(n - 1)); LB_TRY(right.ensure(n - 1)); LB_TRY(pn.ensure(n - 1)); LB_TRY(pl.ensure(n));
         LB_TRY(hipMemcpyAsync(verts.p, verts9, (size_t)n * 36, hipMemcpyHostToDevice, stream));
         const uint32_t init_bounds[6] = { 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u };
         LB_TRY(hipMemcpyAsync(bounds.p, init_bounds, sizeof init_bounds, hipMemcpyHostToDevice, stream));
@@ -166,7 +159,7 @@ struct Lbvh {
         hipLaunchKernelGGL(k_morton, grid, block, 0, stream, cent.p, n, cmin, inv, keys.p, vals.p);
         size_t tmp_bytes = 0;
         LB_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys.p, keys2.p, vals.p, order.p, (size_t)n, 0, 30, stream));
-        LB_TRY(tmp.alloc(tmp_bytes));
+        LB_TRY(tmp.ensure(tmp_bytes));
         LB_TRY(rocprim::radix_sort_pairs(tmp.p, tmp_bytes, keys.p, keys2.p, vals.p, order.p, (size_t)n, 0, 30, stream));
         hipLaunchKernelGGL(k_hierarchy, dim3((n - 1 + 255) / 256), block, 0, stream, keys2.p, (int)n, left.p, right.p, first.p, last.p, pn.p, pl.p);
         hipLaunchKernelGGL(k_refit, grid, block, 0, stream, order.p, leaf_box.p, (int)n, left.p, right.p, pn.p, pl.p, node_box.p, arrived.p);
@@ -382,26 +375,26 @@ hipError_t build_lbvh_blob4q_device(hipStream_t stream, const float *verts9, con
     auto blocks = [](uint32_t k) { return dim3((k + 255) / 256); };
 
     // ---- leaf flags + cluster roots
-    Dev<uint8_t> leaf_flag; Dev<int32_t> clusters; Dev<uint32_t> n_clusters, d_mats;
-    LB_TRY(leaf_flag.alloc(n)); LB_TRY(clusters.alloc(n)); LB_TRY(n_clusters.alloc(1));
+    DevBuf<uint8_t> leaf_flag; DevBuf<int32_t> clusters; DevBuf<uint32_t> n_clusters, d_mats;
+    LB_TRY(leaf_flag.ensure(n)); LB_TRY(clusters.ensure(n)); LB_TRY(n_clusters.ensure(1));
     LB_TRY(hipMemsetAsync(n_clusters.p, 0, 4, stream));
-    if (mats) { LB_TRY(d_mats.alloc(n)); LB_TRY(hipMemcpyAsync(d_mats.p, mats, (size_t)n * 4, hipMemcpyHostToDevice, stream)); }
+    if (mats) { LB_TRY(d_mats.ensure(n)); LB_TRY(hipMemcpyAsync(d_mats.p, mats, (size_t)n * 4, hipMemcpyHostToDevice, stream)); }
     TreeView tv{ t.left.p, t.right.p, t.first.p, t.last.p, t.order.p, t.node_box.p, t.leaf_box.p, leaf_flag.p, nullptr, nullptr, nullptr };
     hipLaunchKernelGGL(k_mark, blocks(n), block, 0, stream, tv, n, (uint32_t)PT_LBVH_CLUSTER, t.pn.p, t.pl.p, leaf_flag.p, clusters.p, n_clusters.p);
     uint32_t nc = 0;
     LB_TRY(hipMemcpyAsync(&nc, n_clusters.p, 4, hipMemcpyDeviceToHost, stream));
     LB_TRY(hipStreamSynchronize(stream));
     if (nc == 0 || nc > n) return hipErrorUnknown;
-    Dev<float> d_cbox; Dev<uint32_t> d_cfirst;
-    LB_TRY(d_cbox.alloc((size_t)nc * 6)); LB_TRY(d_cfirst.alloc(nc));
+    DevBuf<float> d_cbox; DevBuf<uint32_t> d_cfirst;
+    LB_TRY(d_cbox.ensure((size_t)nc * 6)); LB_TRY(d_cfirst.ensure(nc));
     hipLaunchKernelGGL(k_cluster_info, blocks(nc), block, 0, stream, tv, clusters.p, nc, d_cbox.p, d_cfirst.p);
     std::vector<int32_t> h_clusters(nc); std::vector<float> h_cbox((size_t)nc * 6); std::vector<uint32_t> h_cfirst(nc);
     LB_TRY(hipMemcpyAsync(h_clusters.data(), clusters.p, (size_t)nc * 4, hipMemcpyDeviceToHost, stream));
     LB_TRY(hipMemcpyAsync(h_cbox.data(), d_cbox.p, (size_t)nc * 24, hipMemcpyDeviceToHost, stream));
     LB_TRY(hipMemcpyAsync(h_cfirst.data(), d_cfirst.p, (size_t)nc * 4, hipMemcpyDeviceToHost, stream));
     // the triangle records need nothing of the above: they run while the host builds the top storey
-    Dev<float4> tris;
-    LB_TRY(tris.alloc((size_t)n * 4));
+    DevBuf<float4> tris;
+    LB_TRY(tris.ensure((size_t)n * 4));
     hipLaunchKernelGGL(k_tri_records, blocks(n), block, 0, stream, t.verts.p, mats ? d_mats.p : nullptr, t.order.p, n, tris.p);
     LB_TRY(hipStreamSynchronize(stream));
 
@@ -420,9 +413,9 @@ hipError_t build_lbvh_blob4q_device(hipStream_t stream, const float *verts9, con
     const float *rb = top_root < 0 ? &sorted_box[(size_t)(uint32_t)~top_root * 6] : &top_box[(size_t)top_root * 6];
     const float rdx = rb[3] - rb[0], rdy = rb[4] - rb[1], rdz = rb[5] - rb[2];
     const float root_area = std::max(2.f * (rdx * rdy + rdy * rdz + rdz * rdx), 1e-30f);
-    Dev<int32_t> d_tl, d_tr; Dev<float> d_tb;
+    DevBuf<int32_t> d_tl, d_tr; DevBuf<float> d_tb;
     const size_t nt_top = top_left.size();
-    LB_TRY(d_tl.alloc(nt_top)); LB_TRY(d_tr.alloc(nt_top)); LB_TRY(d_tb.alloc(nt_top * 6));
+    LB_TRY(d_tl.ensure(nt_top)); LB_TRY(d_tr.ensure(nt_top)); LB_TRY(d_tb.ensure(nt_top * 6));
     if (nt_top) {
         LB_TRY(hipMemcpyAsync(d_tl.p, top_left.data(), nt_top * 4, hipMemcpyHostToDevice, stream));
         LB_TRY(hipMemcpyAsync(d_tr.p, top_right.data(), nt_top * 4, hipMemcpyHostToDevice, stream));
@@ -432,12 +425,12 @@ hipError_t build_lbvh_blob4q_device(hipStream_t stream, const float *verts9, con
 
     // ---- level by level: expand, scan, finalize. A 4-wide inner node has >= 2 children, so there are < n nodes in all.
     const uint32_t cap = n;
-    Dev<uint8_t> nodes; Dev<int32_t> kids, queue_a, queue_b; Dev<uint32_t> inner_count, offs, depth, need; Dev<float> cost; Dev<unsigned char> scan_tmp;
-    LB_TRY(nodes.alloc((size_t)cap * 64)); LB_TRY(kids.alloc((size_t)cap * 4)); LB_TRY(queue_a.alloc(cap)); LB_TRY(queue_b.alloc(cap));
-    LB_TRY(inner_count.alloc(cap + 1)); LB_TRY(offs.alloc(cap + 1)); LB_TRY(depth.alloc(cap)); LB_TRY(need.alloc(cap)); LB_TRY(cost.alloc(cap));
+    DevBuf<uint8_t> nodes; DevBuf<int32_t> kids, queue_a, queue_b; DevBuf<uint32_t> inner_count, offs, depth, need; DevBuf<float> cost; DevBuf<unsigned char> scan_tmp;
+    LB_TRY(nodes.ensure((size_t)cap * 64)); LB_TRY(kids.ensure((size_t)cap * 4)); LB_TRY(queue_a.ensure(cap)); LB_TRY(queue_b.ensure(cap));
+    LB_TRY(inner_count.ensure(cap + 1)); LB_TRY(offs.ensure(cap + 1)); LB_TRY(depth.ensure(cap)); LB_TRY(need.ensure(cap)); LB_TRY(cost.ensure(cap));
     size_t scan_bytes = 0;
     LB_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, inner_count.p, offs.p, 0u, (size_t)cap + 1, rocprim::plus<uint32_t>(), stream));
-    LB_TRY(scan_tmp.alloc(scan_bytes));
+    LB_TRY(scan_tmp.ensure(scan_bytes));
     LB_TRY(hipMemcpyAsync(queue_a.p, &root_ref, 4, hipMemcpyHostToDevice, stream));
     std::vector<uint32_t> level_base;
     uint32_t base = 0, n_cur = 1;
@@ -460,22 +453,22 @@ hipError_t build_lbvh_blob4q_device(hipStream_t stream, const float *verts9, con
     for (size_t l = level_base.size() - 1; l-- > 0;)
         hipLaunchKernelGGL(k_depth, blocks(level_base[l + 1] - level_base[l]), block, 0, stream, nodes.p, level_base[l], level_base[l + 1] - level_base[l], depth.p, need.p);
     size_t red_bytes = 0;
-    Dev<float> d_sum; Dev<unsigned char> red_tmp;
-    LB_TRY(d_sum.alloc(1));
+    DevBuf<float> d_sum; DevBuf<unsigned char> red_tmp;
+    LB_TRY(d_sum.ensure(1));
     LB_TRY(rocprim::reduce(nullptr, red_bytes, cost.p, d_sum.p, 0.f, (size_t)n_nodes, rocprim::plus<float>(), stream));
-    LB_TRY(red_tmp.alloc(red_bytes));
+    LB_TRY(red_tmp.ensure(red_bytes));
     LB_TRY(rocprim::reduce(red_tmp.p, red_bytes, cost.p, d_sum.p, 0.f, (size_t)n_nodes, rocprim::plus<float>(), stream));
     uint32_t h_depth = 0, h_need = 0; float h_cost = 0.f;
     LB_TRY(hipMemcpyAsync(&h_depth, depth.p, 4, hipMemcpyDeviceToHost, stream));
     LB_TRY(hipMemcpyAsync(&h_need, need.p, 4, hipMemcpyDeviceToHost, stream));
     LB_TRY(hipMemcpyAsync(&h_cost, d_sum.p, 4, hipMemcpyDeviceToHost, stream));
     // exact-size node array for the scene (the work array is sized for the worst case)
-    Dev<float4> final_nodes;
-    LB_TRY(final_nodes.alloc((size_t)n_nodes * 4));
+    DevBuf<float4> final_nodes;
+    LB_TRY(final_nodes.ensure((size_t)n_nodes * 4));
     LB_TRY(hipMemcpyAsync(final_nodes.p, nodes.p, (size_t)n_nodes * 64, hipMemcpyDeviceToDevice, stream));
     LB_TRY(hipStreamSynchronize(stream));
     LB_TRY(hipGetLastError());
-    out.nodes = final_nodes.release(); out.tris = tris.release();
+    out.nodes = std::move(final_nodes); out.tris = std::move(tris);
     out.n_nodes = n_nodes; out.max_depth = h_depth; out.stack_need = h_need; out.sah_cost = h_cost;
     out.device_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return hipSuccess;

@@ -51,6 +51,33 @@ def test_product_does_not_reference_oracle():
         assert "pt_oracle" not in open(os.path.join(ROOT, f)).read()
 
 
+def test_device_resources_have_one_owner():
+    """Device buffers, events, streams and pinned blocks are held by the owner types of csrc/device_owner.h and by nothing else: no other
+    source file of the library releases one, none creates one except on a line whose comment says why, and the two destroy functions
+    release nothing by hand (their members do). A resource added to pt_context or pt_scene then cannot be forgotten."""
+    csrc = os.path.join(ROOT, "pathtracing_amd", "csrc")
+    owner, src = "device_owner.h", {}
+    for dirpath, _, files in os.walk(csrc):
+        for f in files:
+            if f.endswith((".cpp", ".hip", ".h")):
+                src[os.path.relpath(os.path.join(dirpath, f), csrc)] = open(os.path.join(dirpath, f), errors="replace").read()
+    assert owner in src and len(src) > 10
+    for f, txt in src.items():
+        if f == owner:
+            continue
+        for call in ("hipFree(", "hipHostFree(", "hipEventDestroy(", "hipStreamDestroy("):
+            assert call not in txt, (f, call)
+        for no, line in enumerate(txt.splitlines(), 1):
+            for call in ("hipMalloc(", "hipHostMalloc(", "hipEventCreate", "hipStreamCreate"):
+                if call in line:
+                    assert "//" in line.split(call, 1)[1], (f, no, call, "outside the owners' header and no comment on the line says why")
+    api = src["api.cpp"]
+    for name in ("pt_context_destroy", "pt_scene_destroy"):
+        body = re.search(r"^void " + name + r"\(.*?^}", api, re.M | re.S)
+        assert body, name
+        assert ".release(" not in body.group(0) and "delete " in body.group(0), name
+
+
 @pytest.mark.parametrize("w,h,nr", [(1920, 1080, 1), (1920, 1080, 8), (3840, 2160, 8), (100, 37, 3), (64, 64, 2), (65, 1, 4)])
 def test_tile_layout_partitions_the_frame(P, w, h, nr):
     seen = np.zeros(((h + 63) // 64) * ((w + 63) // 64), int)

@@ -204,3 +204,60 @@ def test_refused_pipelines(P, pto, renderer):
     p.flags |= N.PT_FLAG_EXTEND_SIMPLE | N.PT_FLAG_PROFILE_KERNELS  # the kernel NEE runs on, forced, and timed: accepted
     renderer.Params = p
     check(P, pto, renderer, sd, p, "after refusals")
+
+
+def test_destroyed_contexts_and_scenes_return_their_device_memory(P):
+    """Object lifetimes: a destroyed context gives back its NEE frame state (nee_ext + nee_rad, 32 bytes per path slot) and a destroyed
+    scene its light table (lights, CDF and the per-triangle pa array, 4 bytes per blob triangle). Free device memory is read from
+    torch.cuda.mem_get_info(). Both bounds are half of what the leak they guard against would take, derived from those sizes:
+      context leg: six create / 1080p NEE frame (8 streams) / destroy cycles after a warm-up cycle may cost at most half of ONE cycle's
+                   nee_ext + nee_rad = 510 tiles x 4096 pixels x 8 streams x 32 B / 2 = 267 MB (leaking them costs six times 535 MB);
+      scene leg:   32 commits of the 1M-triangle tessellated Cornell box (LBVH) on one Renderer, then a small scene, may cost at most
+                   half of 32 x 4 B x blob triangles = 67 MB (leaking pa alone costs 134 MB).
+    Two idle readings a second apart are printed first: the device is shared, and a drift of that size would be the machine's."""
+    import time
+    import torch
+    N = P.native
+    w, h = 1920, 1080
+
+    def free_bytes():
+        torch.cuda.synchronize()
+        return torch.cuda.mem_get_info()[0]
+
+    cornell = P.make_scene(N.PT_SCENE_CORNELL, 0, 3, w, h)
+    params = P.make_params(w, h, spp=8, max_depth=8, streams=8, flags=N.PT_FLAG_NEXT_EVENT)
+    lay = P.tile_layout(params)
+    assert lay.tiles_per_rank == 510
+
+    def cycle():
+        with P.Renderer(P.Window(w, h)) as r:
+            r.Init()
+            r.SetScene(cornell, 0)
+            r.Params = params
+            assert r.Render(0.0).rays > 0
+
+    idle = free_bytes()
+    time.sleep(1.0)
+    print(f"\nidle drift over 1 s: {idle - free_bytes()} B")
+    cycle()  # warm-up: the runtime's own one-time allocations
+    before = free_bytes()
+    for _ in range(6):
+        cycle()
+    ctx_drop, ctx_limit = before - free_bytes(), lay.tiles_per_rank * 4096 * 8 * 32 // 2
+    print(f"context leg: free memory dropped by {ctx_drop} B over six cycles (limit {ctx_limit} B)")
+
+    tess = P.make_scene(N.PT_SCENE_CORNELL_TESS, 1 << 20, 3, w, h)
+    with P.Renderer(P.Window(w, h)) as r:
+        r.Init()
+        r.SetScene(tess, N.PT_BVH_BUILD_LBVH)  # warm-up (the builder's code objects), left the way the measured run ends
+        n_blob = r.BvhInfo().n_tris
+        assert n_blob > 1000000
+        r.SetScene(cornell, 0)
+        before = free_bytes()
+        for _ in range(32):
+            r.SetScene(tess, N.PT_BVH_BUILD_LBVH)
+        r.SetScene(cornell, 0)  # destroys the last big scene
+        scene_drop, scene_limit = before - free_bytes(), 32 * 4 * n_blob // 2
+        print(f"scene leg: free memory dropped by {scene_drop} B over 32 commits of {n_blob} triangles (limit {scene_limit} B)")
+    assert ctx_drop <= ctx_limit, ("context leg", ctx_drop, ctx_limit)  # (both legs are measured before either is judged)
+    assert scene_drop <= scene_limit, ("scene leg", scene_drop, scene_limit)
