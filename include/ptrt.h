@@ -162,8 +162,7 @@ typedef struct {
 
 /* Scheduling knobs of a context (none changes a pixel; tests/test_gpu_parity.py holds every setting to the same frame). Read the
  * current values with pt_context_get_tuning, change what you want, write them back. The library reads no environment variables for
- * these (developer aids aside: the stderr diagnostics PTRT_TRACE / PTRT_TIMING, and PTRT_NODE_ORDER / PTRT_UNIFIED / PTRT_COLLAPSE, which give
- * the same tree another memory order, or collapse it to wide nodes by the old rule, for the builder experiments of DESIGN.md). */
+ * these (developer aids aside: the stderr diagnostics PTRT_TRACE / PTRT_TIMING, which change no tree and no picture). */
 typedef struct {
     uint32_t bounces;       /* path vertices a lane advances per launch of the fused extend kernels, 1..64; 0 (default) = 3/4 max_depth - 2
                                clamped to [4, 12] for the one-ray-per-lane kernel, 64 for the lane-packing one. PT_FLAG_NEXT_EVENT frames:
@@ -242,7 +241,7 @@ pt_status pt_trace_rays(pt_context *ctx, const pt_scene *scene, const void *rays
  *      updated geometry. An update leaves the context's accumulated sums alone: a PT_FLAG_ACCUMULATE frame after it continues the old
  *      sums (the mean then mixes both geometries). Both calls are synchronous on the context's stream; a refused call leaves the scene
  *      as it was. Checked in this order: flags, committed (PT_ERR_NOT_COMMITTED), count (must equal the committed count), NULL,
- *      the values (host arrays), then detached scenes and scenes committed under the PTRT_UNIFIED experiment (PT_ERR_UNSUPPORTED). */
+ *      the values (host arrays), then detached scenes (PT_ERR_UNSUPPORTED). */
 /* pt_scene_update_triangles flags */
 enum {
     PT_UPDATE_HOST_MEMORY = 1u  /* verts9 is a host pointer (staged by the library); default: a device pointer on the scene's context's device */
@@ -275,7 +274,7 @@ typedef struct pt_denoise_params {
 /* Denoise the context's assembled framebuffer, with guides traced on `scene` (the scene the frame was rendered on; its camera). Synchronous
  * on the context's stream, like pt_render. Checked in this order; a refused call changes nothing:
  *   dp NULL, unknown flag bits, iterations > 8, a negative, NaN or infinite sigma; then ctx or scene NULL   -> PT_ERR_INVALID_ARGUMENT
- *   a detached scene, a scene of another context or one committed under the PTRT_UNIFIED experiment        -> PT_ERR_UNSUPPORTED
+ *   a detached scene or a scene of another context                                                          -> PT_ERR_UNSUPPORTED
  *   scene not committed                                                                                     -> PT_ERR_NOT_COMMITTED
  *   the framebuffer holds a PT_REFERENCE_SPHERE frame                                                       -> PT_ERR_UNSUPPORTED
  *   no assembled framebuffer (a PT_PATH_TRACE frame with nranks == 1, or pt_assemble_tiles / pt_comm_* on

@@ -185,11 +185,11 @@ struct pt_scene {
     bool device_packed = false;          // the blob was packed on the device (lbvh.hip build_lbvh_blob4q_device): the host copies below
     mutable bool host_mirror = true;     // false: the host copies of the blob (packed_nodes or bvh.slots, and bvh.tris) are stale — packed on the
                                          // device, or refitted since — and pt_scene_bvh_read fetches them from the device first
-    bool unified = false;                // committed under the PTRT_UNIFIED experiment (one array of nodes and triangles): no updates
     bool quantised() const { return layout == PT_BVH_WIDTH_4Q || layout == PT_BVH_WIDTH_8Q || layout == PT_BVH_WIDTH_8O; }
     const void *node_data() const { return quantised() ? (const void *)packed_nodes.data() : (const void *)bvh.slots.data(); }
     uint64_t node_bytes() const { return device_packed ? (uint64_t)bvh.n_nodes * 64u : quantised() ? packed_nodes.size() : bvh.slots.size() * sizeof(BvhSlot); }
     uint64_t n_blob_tris() const { return device_packed ? tri_mat.size() : bvh.tris.size(); }
+    uint32_t stack_overflow() const { return bvh.stack_need > kStackLds ? bvh.stack_need - kStackLds : 0u; } // traversal-stack entries per ray beyond those in LDS
     DevBuf<float4> d_nodes, d_tris, d_spheres, d_mats;
     bool has_specular = false;
     mutable ExtendChoice ext;            // cache, not scene content: what earlier frames measured
@@ -249,25 +249,35 @@ std::vector<uint2> sphere_mats(const uint32_t *mat, const float *cxyzr, size_t n
     return mi;
 }
 
-// docs/SPEC.md §7: the light set, its f32 CDF and the per-light records from the current vertices of the candidates (9 floats each, in
-// candidate order), uploaded to the scene's device arrays. Area, normal and pa in the op order of §0 / §7; the weights in double.
-pt_status build_lights(pt_context *c, pt_scene *s, const float *cand_verts)
+// n = normalize(cross(e1, e2)) in exactly the op order of docs/SPEC.md §0 (fma, IEEE sqrt and divide), so the bits equal what the kernel
+// would compute from e1, e2: a triangle record's shading row, a light's normal. Returns |cross(e1, e2)|^2.
+float shading_normal(const float *e1, const float *e2, float *n)
+{
+    const float cr[3] = { std::fmaf(e1[1], e2[2], -(e1[2] * e2[1])), std::fmaf(e1[2], e2[0], -(e1[0] * e2[2])), std::fmaf(e1[0], e2[1], -(e1[1] * e2[0])) };
+    const float dd = std::fmaf(cr[2], cr[2], std::fmaf(cr[1], cr[1], cr[0] * cr[0])), inv = 1.0f / std::sqrt(dd);
+    for (int k = 0; k < 3; ++k) n[k] = cr[k] * inv;
+    return dd;
+}
+
+// docs/SPEC.md §7: the light set, its f32 CDF and the per-light records from the current vertices of the candidates, uploaded to the
+// scene's device arrays. `verts` holds the triangles from `first` on (9 floats each, in triangle order). Area, normal and pa in the op
+// order of §0 / §7; the weights in double.
+pt_status build_lights(pt_context *c, pt_scene *s, const float *verts, uint32_t first)
 {
     std::vector<float> rec, cdf; // 16 floats per light: v0|pa, e1|Le.r, e2|Le.g, n_l|Le.b
     std::vector<double> w;       // area * (e.r + e.g + e.b) per light
     std::vector<uint32_t> cand;  // which candidate each light is
     double total = 0.0;
     for (size_t k = 0; k < s->light_cand.size(); ++k) {
-        const float *v = cand_verts + k * 9;
+        const float *v = verts + (size_t)(s->light_cand[k] - first) * 9;
         const float e1[3] = { v[3] - v[0], v[4] - v[1], v[5] - v[2] }, e2[3] = { v[6] - v[0], v[7] - v[1], v[8] - v[2] };
-        const float cr[3] = { std::fmaf(e1[1], e2[2], -(e1[2] * e2[1])), std::fmaf(e1[2], e2[0], -(e1[0] * e2[2])), std::fmaf(e1[0], e2[1], -(e1[1] * e2[0])) };
-        const float dd = std::fmaf(cr[2], cr[2], std::fmaf(cr[1], cr[1], cr[0] * cr[0]));
-        const float area = 0.5f * std::sqrt(dd), inv = 1.0f / std::sqrt(dd); // n_l = normalize(cross(e1, e2)): the bits of the shading row
+        float nl[3]; // n_l: the bits of the shading row
+        const float area = 0.5f * std::sqrt(shading_normal(e1, e2, nl));
         const float *e = s->mats[s->tri_mat[s->light_cand[k]]].emission;
         const double wk = (double)area * ((double)e[0] + (double)e[1] + (double)e[2]);
         if (!(area > 0.f) || !(wk > 0.0)) continue;
         total += wk; w.push_back(wk); cand.push_back((uint32_t)k);
-        const float r[16] = { v[0], v[1], v[2], area, e1[0], e1[1], e1[2], e[0], e2[0], e2[1], e2[2], e[1], cr[0] * inv, cr[1] * inv, cr[2] * inv, e[2] };
+        const float r[16] = { v[0], v[1], v[2], area, e1[0], e1[1], e1[2], e[0], e2[0], e2[1], e2[2], e[1], nl[0], nl[1], nl[2], e[2] };
         rec.insert(rec.end(), r, r + 16);
     }
     const size_t nl = w.size();
@@ -510,11 +520,23 @@ pt_status pt_scene_set_sky(pt_scene *s, const float rgb[3])
     return PT_OK;
 }
 
-pt_status pt_scene_commit(pt_scene *s, uint32_t bvh_width)
+// ---- pt_scene_commit's phases, in the order they run. Each ends with a lap of the commit's clock.
+
+struct CommitClock { // PTRT_TIMING (developer aid): where a commit's time goes, on stderr
+    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+    void lap(const char *what)
+    {
+        static const bool timing = getenv("PTRT_TIMING") != nullptr;
+        if (timing) fprintf(stderr, "ptrt commit: %-28s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count());
+        t = std::chrono::steady_clock::now();
+    }
+};
+
+// Check: the builder flag, the layout (bvh_width leaves as one of PT_BVH_WIDTH_2 .. _8O), the camera and every material id
+static pt_status check_commit(const pt_scene *s, uint32_t &bvh_width, bool &lbvh)
 {
-    if (!s) return fail(nullptr, PT_ERR_INVALID_ARGUMENT, "scene is NULL");
     pt_context *c = s->ctx;
-    const bool lbvh = (bvh_width & PT_BVH_BUILD_LBVH) != 0; // hierarchy built on the GPU instead of the host SAH builder
+    lbvh = (bvh_width & PT_BVH_BUILD_LBVH) != 0; // hierarchy built on the GPU instead of the host SAH builder
     bvh_width &= ~(uint32_t)PT_BVH_BUILD_LBVH;
     if (lbvh && !c) return fail(c, PT_ERR_UNSUPPORTED, "PT_BVH_BUILD_LBVH needs a device context (detached scenes use the host builder)");
     // default layout: BVH4Q; scenes of up to ~200 triangles get BVH2 with float boxes — their whole tree is a handful of L1-resident
@@ -531,7 +553,14 @@ pt_status pt_scene_commit(pt_scene *s, uint32_t bvh_width)
     if ((nt || ns) && nm == 0) return fail(c, PT_ERR_INVALID_ARGUMENT, "primitives but no materials");
     for (uint32_t i = 0; i < nt; ++i) if (s->tri_mat[i] >= nm) return fail(c, PT_ERR_INVALID_ARGUMENT, "triangle %u: material id %u >= %u", i, s->tri_mat[i], nm);
     for (uint32_t i = 0; i < ns; ++i) if (s->sph_mat[i] >= nm) return fail(c, PT_ERR_INVALID_ARGUMENT, "sphere %u: material id %u >= %u", i, s->sph_mat[i], nm);
+    return PT_OK;
+}
 
+// Build tree: the hierarchy and its blob from the scene's current vertices, by one of three builders, then the quantised nodes of the
+// layouts that have them. Sets device_packed and host_mirror: only the first builder leaves the blob on the device alone.
+static pt_status build_tree(pt_scene *s, uint32_t bvh_width, bool lbvh, CommitClock &clock)
+{
+    pt_context *c = s->ctx;
     if (s->verts_on_device) { // updated since the last commit: build from the current vertices
         HIP_TRY(c, hipSetDevice(c->device));
         HIP_TRY(c, hipMemcpy(s->verts.data(), s->refit.verts[s->refit.cur].p, s->verts.size() * sizeof(float), hipMemcpyDeviceToHost));
@@ -539,16 +568,10 @@ pt_status pt_scene_commit(pt_scene *s, uint32_t bvh_width)
     }
     s->refit.ready = false;
     s->blob_of_ready = false;
-
+    const uint32_t nt = (uint32_t)s->tri_mat.size();
     const bool oct = bvh_width == PT_BVH_WIDTH_8O;
     const uint32_t fan = bvh_width == PT_BVH_WIDTH_2 ? 2u : (bvh_width == PT_BVH_WIDTH_8Q || oct) ? 8u : 4u;
-    static const bool timing = getenv("PTRT_TIMING") != nullptr; // developer aid: where a commit's time goes, on stderr
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto ms_since = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(now() - t).count(); };
-    auto t_phase = now();
-    auto lap = [&](const char *what) { if (timing) fprintf(stderr, "ptrt commit: %-28s %8.2f ms\n", what, ms_since(t_phase)); t_phase = now(); };
     s->device_packed = false; s->host_mirror = true;
-    uint32_t unified_units = 0;
     if (lbvh && nt >= 2 && bvh_width == PT_BVH_WIDTH_4Q) {
         // the default layout is also packed on the device: nodes and triangle records are born in device memory
         HIP_TRY(c, hipSetDevice(c->device));
@@ -565,80 +588,51 @@ pt_status pt_scene_commit(pt_scene *s, uint32_t bvh_width)
         HIP_TRY(c, build_lbvh_device(c->stream, s->verts.data(), nt, bt));
         build_bvh_from_binary(bt, s->verts.data(), s->tri_mat.data(), nt, fan, s->bvh, oct);
     } else build_bvh(s->verts.data(), s->tri_mat.data(), nt, fan, s->bvh, oct);
-    lap("hierarchy + blob");
+    clock.lap("hierarchy + blob");
     if (s->bvh.max_depth > 90) return fail(c, PT_ERR_INTERNAL, "BVH depth %u exceeds the supported 90", s->bvh.max_depth);
     s->layout = bvh_width;
     s->packed_nodes.clear();
     if (bvh_width == PT_BVH_WIDTH_4Q && !s->device_packed) quantize_bvh4(s->bvh, s->packed_nodes);
     if (bvh_width == PT_BVH_WIDTH_8Q || oct) quantize_bvh8(s->bvh, s->packed_nodes);
-    lap("quantise");
-    if (!c) { s->committed = true; return PT_OK; } // detached scene: host-side blob only
+    clock.lap("quantise");
+    return PT_OK;
+}
+
+// Upload tree: the host-built blob's triangle records and nodes (a device-packed blob is where it belongs already)
+static pt_status upload_tree(pt_scene *s, CommitClock &clock)
+{
+    pt_context *c = s->ctx;
     // the traversal kernels fetch a node or a triangle record by a 32-bit byte offset from its array's base (kernels.hip record())
     if (s->node_bytes() > (1ull << 32) || s->n_blob_tris() * 64u > (1ull << 32))
         return fail(c, PT_ERR_UNSUPPORTED, "BVH of %llu node bytes and %llu triangle records: each array must stay within 4 GiB",
                     (unsigned long long)s->node_bytes(), (unsigned long long)s->n_blob_tris());
-
     HIP_TRY(c, hipSetDevice(c->device));
     static_assert(sizeof(BvhSlot) == 32 && sizeof(BvhTri) == 48 && sizeof(pt_material) == 48, "blob layout");
-    if (!s->device_packed) {
+    if (s->device_packed) return PT_OK;
     HIP_TRY(c, s->d_nodes.ensure((size_t)(s->node_bytes() / 16)));
     HIP_TRY(c, s->d_tris.ensure(s->bvh.tris.size() * 4));
-    {   // Device triangle record = one 64-byte line: the blob's three rows (docs/SPEC.md §4.1) + a shading row. A 48-byte
-        // record straddles two cache lines 3 times out of 4 when k_extend fetches it; a padded one never does, and the
-        // row that pads it is the one k_shade wants next. Shading row: ng = normalize(cross(e1,e2)) in exactly the op order
-        // of docs/SPEC.md §0 (fma, IEEE sqrt and divide), so the bits equal what the kernel would compute from e1,e2.
-        std::vector<float> rec(s->bvh.tris.size() * 16);
-        for (size_t i = 0; i < s->bvh.tris.size(); ++i) {
-            const BvhTri &t = s->bvh.tris[i];
-            std::memcpy(&rec[i * 16], &t, sizeof(BvhTri));
-            const float *a = t.e1, *b = t.e2;
-            const float cx = std::fmaf(a[1], b[2], -(a[2] * b[1])), cy = std::fmaf(a[2], b[0], -(a[0] * b[2])), cz = std::fmaf(a[0], b[1], -(a[1] * b[0]));
-            const float inv = 1.0f / std::sqrt(std::fmaf(cz, cz, std::fmaf(cy, cy, cx * cx)));
-            rec[i * 16 + 12] = cx * inv; rec[i * 16 + 13] = cy * inv; rec[i * 16 + 14] = cz * inv;
-            std::memcpy(&rec[i * 16 + 15], &t.mat, 4);
-        }
-        lap("triangle records");
-        if (bvh_width == PT_BVH_WIDTH_4Q && getenv("PTRT_UNIFIED") && !rec.empty()) {
-            // EXPERIMENT (layout rows; tools/exp_order.py): nodes and triangle records in ONE array of 64-byte units, every
-            // node followed by the triangles of its leaf children, so that a bottom-level node and the first of its triangles share a
-            // 128-byte line. Refs count units; the kernels are unchanged (nodes and tris are the same base pointer). The device
-            // structure is then a renaming of the blob pt_scene_bvh_read hands out — same tree, same pictures.
-            const uint32_t nn = s->bvh.n_nodes, ntb = (uint32_t)s->bvh.tris.size();
-            std::vector<uint32_t> node_unit(nn), tri_unit(ntb);
-            uint32_t u = 0;
-            for (uint32_t i = 0; i < nn; ++i) {
-                node_unit[i] = u++;
-                for (int k = 0; k < 4; ++k) {
-                    int32_t r; std::memcpy(&r, &s->packed_nodes[(size_t)i * 64 + 16 + 4 * k], 4);
-                    if (r >= 0) continue;
-                    const uint32_t enc = (uint32_t)~r, first = enc >> 3, cnt = (enc & 7u) + 1u;
-                    for (uint32_t j = 0; j < cnt; ++j) tri_unit[first + j] = u++;
-                }
-            }
-            if ((uint64_t)u * 64u > (1ull << 32)) return fail(c, PT_ERR_UNSUPPORTED, "PTRT_UNIFIED: %u units exceed 4 GiB", u);
-            std::vector<uint8_t> uni((size_t)u * 64);
-            for (uint32_t i = 0; i < nn; ++i) {
-                uint8_t *nd = &uni[(size_t)node_unit[i] * 64];
-                std::memcpy(nd, &s->packed_nodes[(size_t)i * 64], 64);
-                for (int k = 0; k < 4; ++k) {
-                    int32_t r; std::memcpy(&r, nd + 16 + 4 * k, 4);
-                    if (r == 0x7fffffff) continue;
-                    if (r >= 0) r = (int32_t)node_unit[(uint32_t)r];
-                    else { const uint32_t enc = (uint32_t)~r; r = (int32_t)~((tri_unit[enc >> 3] << 3) | (enc & 7u)); }
-                    std::memcpy(nd + 16 + 4 * k, &r, 4);
-                }
-            }
-            for (uint32_t j = 0; j < ntb; ++j) std::memcpy(&uni[(size_t)tri_unit[j] * 64], &rec[(size_t)j * 16], 64);
-            HIP_TRY(c, s->d_nodes.ensure((size_t)u * 4));
-            HIP_TRY(c, hipMemcpy(s->d_nodes.p, uni.data(), uni.size(), hipMemcpyHostToDevice));
-            unified_units = u;
-        } else {
-        if (!rec.empty()) HIP_TRY(c, hipMemcpy(s->d_tris.p, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice));
-        lap("upload triangles");
-        }
+    // Device triangle record = one 64-byte line: the blob's three rows (docs/SPEC.md §4.1) + a shading row. A 48-byte
+    // record straddles two cache lines 3 times out of 4 when k_extend fetches it; a padded one never does, and the
+    // row that pads it is the one k_shade wants next: ng (shading_normal) and the material id.
+    std::vector<float> rec(s->bvh.tris.size() * 16);
+    for (size_t i = 0; i < s->bvh.tris.size(); ++i) {
+        const BvhTri &t = s->bvh.tris[i];
+        std::memcpy(&rec[i * 16], &t, sizeof(BvhTri));
+        shading_normal(t.e1, t.e2, &rec[i * 16 + 12]);
+        std::memcpy(&rec[i * 16 + 15], &t.mat, 4);
     }
-    if (s->node_bytes() && !unified_units) HIP_TRY(c, hipMemcpy(s->d_nodes.p, s->node_data(), s->node_bytes(), hipMemcpyHostToDevice));
-    }
+    clock.lap("triangle records");
+    if (!rec.empty()) HIP_TRY(c, hipMemcpy(s->d_tris.p, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice));
+    clock.lap("upload triangles");
+    if (s->node_bytes()) HIP_TRY(c, hipMemcpy(s->d_nodes.p, s->node_data(), s->node_bytes(), hipMemcpyHostToDevice));
+    return PT_OK;
+}
+
+// Upload primitives: the spheres, their {material, 1/r} and the materials
+static pt_status upload_primitives(pt_scene *s, CommitClock &clock)
+{
+    pt_context *c = s->ctx;
+    const uint32_t ns = (uint32_t)s->sph_mat.size(), nm = (uint32_t)s->mats.size();
     HIP_TRY(c, s->d_spheres.ensure((ns + 3u) & ~3u)); // the kernels read the list four spheres (one 64-byte scalar load) at a time
     HIP_TRY(c, s->d_sph_mat.ensure(ns));
     HIP_TRY(c, s->d_mats.ensure((size_t)nm * 3));
@@ -647,47 +641,66 @@ pt_status pt_scene_commit(pt_scene *s, uint32_t bvh_width)
         HIP_TRY(c, hipMemcpy(s->d_sph_mat.p, sphere_mats(s->sph_mat.data(), s->spheres.data(), ns).data(), (size_t)ns * sizeof(uint2), hipMemcpyHostToDevice));
     }
     if (nm) HIP_TRY(c, hipMemcpy(s->d_mats.p, s->mats.data(), (size_t)nm * sizeof(pt_material), hipMemcpyHostToDevice));
-    lap("upload nodes + rest");
-    {   // the light table of next-event estimation (docs/SPEC.md §7): candidates, where their pa lives in the blob order, the table
-        const uint32_t nbt = (uint32_t)s->n_blob_tris();
-        s->light_cand.clear(); s->cand_blob.clear(); s->pa_span.clear(); s->cand_lo = 0; s->n_lights = 0;
-        for (uint32_t i = 0; i < nt; ++i) {
-            const float *e = s->mats[s->tri_mat[i]].emission;
-            if (e[0] != 0.f || e[1] != 0.f || e[2] != 0.f) s->light_cand.push_back(i);
-        }
-        HIP_TRY(c, s->d_pa.ensure(std::max<size_t>(nbt, 1)));
-        HIP_TRY(c, hipMemset(s->d_pa.p, 0, std::max<size_t>(nbt, 1) * sizeof(float)));
-        if (!s->light_cand.empty() && !unified_units) {
-            std::vector<uint32_t> blob_of(nt), ids(nbt);
-            if (s->device_packed) HIP_TRY(c, hipMemcpy2D(ids.data(), 4, (const uint8_t *)s->d_tris.p + 12, 64, 4, nbt, hipMemcpyDeviceToHost)); // row 0 .w
-            else for (uint32_t j = 0; j < nbt; ++j) ids[j] = s->bvh.tris[j].id;
-            for (uint32_t j = 0; j < nbt; ++j) blob_of[ids[j]] = j;
-            uint32_t hi = 0; s->cand_lo = nbt;
-            std::vector<float> cv(s->light_cand.size() * 9);
-            for (size_t k = 0; k < s->light_cand.size(); ++k) {
-                const uint32_t b = blob_of[s->light_cand[k]];
-                s->cand_blob.push_back(b); s->cand_lo = std::min(s->cand_lo, b); hi = std::max(hi, b);
-                std::memcpy(&cv[k * 9], &s->verts[(size_t)s->light_cand[k] * 9], 9 * sizeof(float));
-            }
-            s->pa_span.assign(hi - s->cand_lo + 1u, 0.0f);
-            const pt_status st = build_lights(c, s, cv.data());
-            if (st != PT_OK) return st;
-        }
-        lap("light table");
-    }
+    clock.lap("upload nodes + rest");
+    return PT_OK;
+}
 
+// Light table of next-event estimation (docs/SPEC.md §7): the candidates, where their pa lives in the blob order, the table
+static pt_status light_table(pt_scene *s, CommitClock &clock)
+{
+    pt_context *c = s->ctx;
+    const uint32_t nt = (uint32_t)s->tri_mat.size(), nbt = (uint32_t)s->n_blob_tris();
+    s->light_cand.clear(); s->cand_blob.clear(); s->pa_span.clear(); s->cand_lo = 0; s->n_lights = 0;
+    for (uint32_t i = 0; i < nt; ++i) {
+        const float *e = s->mats[s->tri_mat[i]].emission;
+        if (e[0] != 0.f || e[1] != 0.f || e[2] != 0.f) s->light_cand.push_back(i);
+    }
+    HIP_TRY(c, s->d_pa.ensure(std::max<size_t>(nbt, 1)));
+    HIP_TRY(c, hipMemset(s->d_pa.p, 0, std::max<size_t>(nbt, 1) * sizeof(float)));
+    if (!s->light_cand.empty()) {
+        std::vector<uint32_t> blob_of(nt), ids(nbt);
+        if (s->device_packed) HIP_TRY(c, hipMemcpy2D(ids.data(), 4, (const uint8_t *)s->d_tris.p + 12, 64, 4, nbt, hipMemcpyDeviceToHost)); // row 0 .w
+        else for (uint32_t j = 0; j < nbt; ++j) ids[j] = s->bvh.tris[j].id;
+        for (uint32_t j = 0; j < nbt; ++j) blob_of[ids[j]] = j;
+        uint32_t hi = 0; s->cand_lo = nbt;
+        for (const uint32_t id : s->light_cand) {
+            const uint32_t b = blob_of[id];
+            s->cand_blob.push_back(b); s->cand_lo = std::min(s->cand_lo, b); hi = std::max(hi, b);
+        }
+        s->pa_span.assign(hi - s->cand_lo + 1u, 0.0f);
+        const pt_status st = build_lights(c, s, s->verts.data(), 0);
+        if (st != PT_OK) return st;
+    }
+    clock.lap("light table");
+    return PT_OK;
+}
+
+// Publish: what the kernels see of the scene, and what earlier frames measured on the old one forgotten
+static void publish_scene(pt_scene *s)
+{
     DeviceScene &d = s->ds;
     d.nodes = s->d_nodes.p; d.tris = s->d_tris.p; d.spheres = s->d_spheres.p; d.sph_mat = s->d_sph_mat.p; d.mats = s->d_mats.p;
-    d.n_nodes = s->bvh.n_nodes; d.n_tris = nt; d.n_spheres = ns; d.n_mats = nm;
-    if (unified_units) { d.tris = d.nodes; d.n_tris = unified_units; } // (experiment) triangle refs count units of the one array; sphere refs follow them
+    d.n_nodes = s->bvh.n_nodes; d.n_tris = (uint32_t)s->tri_mat.size(); d.n_spheres = (uint32_t)s->sph_mat.size(); d.n_mats = (uint32_t)s->mats.size();
     for (int k = 0; k < 3; ++k) d.sky[k] = s->sky[k];
-    d.bvh_width = bvh_width;
+    d.bvh_width = s->layout;
     d.cam = s->cam;
     s->ext = ExtendChoice{};
     s->has_specular = false;
     for (const pt_material &m : s->mats) if (m.kind != PT_LAMBERT) s->has_specular = true;
-    s->unified = unified_units != 0;
     s->committed = true;
+}
+
+pt_status pt_scene_commit(pt_scene *s, uint32_t bvh_width)
+{
+    if (!s) return fail(nullptr, PT_ERR_INVALID_ARGUMENT, "scene is NULL");
+    bool lbvh = false;
+    pt_status st = check_commit(s, bvh_width, lbvh);
+    if (st != PT_OK) return st;
+    CommitClock clock;
+    if ((st = build_tree(s, bvh_width, lbvh, clock)) != PT_OK) return st;
+    if (!s->ctx) { s->committed = true; return PT_OK; } // detached scene: host-side blob only
+    if ((st = upload_tree(s, clock)) != PT_OK || (st = upload_primitives(s, clock)) != PT_OK || (st = light_table(s, clock)) != PT_OK) return st;
+    publish_scene(s);
     return PT_OK;
 }
 
@@ -783,7 +796,6 @@ static pt_status plan_frame(pt_context *c, const pt_scene *s, const pt_render_pa
             return fail(c, PT_ERR_UNSUPPORTED, "PT_FLAG_NEXT_EVENT runs on the one-ray-per-lane kernel only: not with PT_FLAG_EXTEND_PACKED, "
                                                "PT_FLAG_EXTEND_POOL, PT_FLAG_SPLIT_KERNELS, PT_FLAG_BUCKET_SPECULAR or pt_tuning.extend_kernel 2 / 3");
         if (f.count) return fail(c, PT_ERR_UNSUPPORTED, "PT_FLAG_NEXT_EVENT does not count visits (PT_FLAG_COUNT_VISITS)");
-        if (s->unified) return fail(c, PT_ERR_UNSUPPORTED, "PT_FLAG_NEXT_EVENT: not for a scene committed under PTRT_UNIFIED");
         f.forced = EXT_SIMPLE;
     }
     // the fused one-ray-per-lane and lane-packing kernels build a slot's initial state in registers in their first launch; k_shade
@@ -823,7 +835,7 @@ static pt_status plan_frame(pt_context *c, const pt_scene *s, const pt_render_pa
     // hit records and the metal / dielectric buckets are k_shade's (no kernel indexes the miss and Lambert buckets)
     if (f.split) { HIP_TRY(c, c->hit.ensure(f.n_slots)); HIP_TRY(c, c->q_metal.ensure(f.q_entries)); HIP_TRY(c, c->q_dielectric.ensure(f.q_entries)); }
     if (!f.full_state) { HIP_TRY(c, c->q_init.ensure(f.q_entries)); HIP_TRY(c, c->cnt_init.ensure(kCntTotalWords)); }
-    const uint32_t ovf = s->bvh.stack_need > kStackLds ? s->bvh.stack_need - kStackLds : 0u;
+    const uint32_t ovf = s->stack_overflow();
     if (ovf) HIP_TRY(c, c->stack_ovf.ensure((size_t)ovf * f.q_entries));
     if (f.nee) {
         HIP_TRY(c, c->nee_ext.ensure(f.n_slots)); HIP_TRY(c, c->nee_rad.ensure(f.n_slots));
@@ -1094,7 +1106,7 @@ static pt_status trace_setup(pt_context *c, const pt_scene *s, uint64_t n_rays, 
     const uint32_t blocks = trace_blocks((uint32_t)std::min<uint64_t>(n_rays, kTraceChunk)), lanes = blocks * kExtBlock;
     ps = PathState{};
     ps.shard_cap = (lanes + kShards - 1u) / kShards; // one overflow column per lane of the grid, reused by its every ray
-    ps.stack_ovf_entries = s->bvh.stack_need > kStackLds ? s->bvh.stack_need - kStackLds : 0u;
+    ps.stack_ovf_entries = s->stack_overflow();
     if (ps.stack_ovf_entries) HIP_TRY(c, c->trace_ovf.ensure((size_t)ps.stack_ovf_entries * kShards * ps.shard_cap));
     ps.stack_ovf = c->trace_ovf.p;
     HIP_TRY(c, c->trace_cnt.ensure(kCntTotalWords)); // the kernels use the global words only: error flag and visit counters
@@ -1167,7 +1179,7 @@ pt_status pt_trace_rays(pt_context *c, const pt_scene *s, const void *rays, void
 
 // ------------------------------------------------------------------------------------------------ geometry updates (docs/SPEC.md §4.3)
 
-// The first update after a commit: level lists from the tree's refs (in device node order, whatever PTRT_NODE_ORDER made of it) and the
+// The first update after a commit: level lists from the tree's refs (in device node order) and the
 // scratch the passes use. Sizes are those of the committed tree, which an update never changes.
 static pt_status prepare_refit(pt_scene *s)
 {
@@ -1206,7 +1218,6 @@ static pt_status update_triangles(pt_scene *s, const void *verts9, uint64_t coun
             if (!std::isfinite(v[i])) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_scene_update_triangles: non-finite vertex coordinate at float %llu", (unsigned long long)i);
     }
     if (!c) return fail(c, PT_ERR_UNSUPPORTED, "pt_scene_update_triangles: a detached scene has no device tree to refit (set the triangles and commit)");
-    if (s->unified) return fail(c, PT_ERR_UNSUPPORTED, "pt_scene_update_triangles: not for a scene committed under PTRT_UNIFIED");
     pt_stats out{};
     if (count == 0) { if (stats) *stats = out; return PT_OK; }
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1249,11 +1260,9 @@ static pt_status update_triangles(pt_scene *s, const void *verts9, uint64_t coun
     out.gpu_ms = (double)ms + ms_check;
     if (!s->pa_span.empty()) { // the light table from the new vertices of the candidates (same candidates: the materials stay)
         const uint32_t lo = s->light_cand.front(), hi = s->light_cand.back(); // in triangle order
-        std::vector<float> span((size_t)(hi - lo + 1u) * 9u), cv(s->light_cand.size() * 9u);
-        if (host) std::memcpy(span.data(), (const float *)verts9 + (size_t)lo * 9u, span.size() * sizeof(float));
-        else HIP_TRY(c, hipMemcpy(span.data(), v + (size_t)lo * 9u, span.size() * sizeof(float), hipMemcpyDeviceToHost));
-        for (size_t k = 0; k < s->light_cand.size(); ++k) std::memcpy(&cv[k * 9], &span[(size_t)(s->light_cand[k] - lo) * 9u], 9 * sizeof(float));
-        if ((st = build_lights(c, s, cv.data())) != PT_OK) return st;
+        std::vector<float> span(host ? 0u : (size_t)(hi - lo + 1u) * 9u); // a device array: only the candidates' span comes back
+        if (!host) HIP_TRY(c, hipMemcpy(span.data(), v + (size_t)lo * 9u, span.size() * sizeof(float), hipMemcpyDeviceToHost));
+        if ((st = host ? build_lights(c, s, (const float *)verts9, 0) : build_lights(c, s, span.data(), lo)) != PT_OK) return st;
     }
     R.cur = nxt; s->verts_on_device = true;
     s->bvh.sah_cost = (float)sah;
@@ -1273,7 +1282,6 @@ static pt_status update_spheres(pt_scene *s, const float *cxyzr, uint64_t count)
     for (uint64_t i = 0; i < count; ++i)
         if (!sphere_ok(cxyzr + i * 4)) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_scene_update_spheres: sphere %llu: non-finite centre or radius <= 0", (unsigned long long)i);
     if (!c) return fail(c, PT_ERR_UNSUPPORTED, "pt_scene_update_spheres: a detached scene has no device copy to update (set the spheres and commit)");
-    if (s->unified) return fail(c, PT_ERR_UNSUPPORTED, "pt_scene_update_spheres: not for a scene committed under PTRT_UNIFIED");
     if (count == 0) return PT_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     const std::vector<uint2> mi = sphere_mats(s->sph_mat.data(), cxyzr, count);
@@ -1314,7 +1322,6 @@ static pt_status denoise(pt_context *c, const pt_scene *s, const pt_denoise_para
             return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_denoise: %s = %g (must be finite and >= 0; 0 = default)", sigma_name[k], (double)sigma[k]);
     if (!c || !s) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_denoise: NULL context or scene");
     if (s->ctx != c) return fail(c, PT_ERR_UNSUPPORTED, "pt_denoise: the scene is %s", s->ctx ? "of another context" : "detached (no device copy to trace)");
-    if (s->unified) return fail(c, PT_ERR_UNSUPPORTED, "pt_denoise: not for a scene committed under PTRT_UNIFIED");
     if (!s->committed) return fail(c, PT_ERR_NOT_COMMITTED, "pt_denoise: scene not committed");
     if (c->fb_valid && c->fb_reference) return fail(c, PT_ERR_UNSUPPORTED, "pt_denoise: the framebuffer holds a PT_REFERENCE_SPHERE frame");
     if (!c->fb_valid) return fail(c, PT_ERR_NOT_COMMITTED, "pt_denoise: no assembled frame (render with nranks == 1 or assemble the tiles first)");

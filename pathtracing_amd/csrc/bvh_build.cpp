@@ -176,8 +176,8 @@ int32_t build_parallel(Builder &B, uint32_t n, uint32_t serial_below = 1u << 16,
     return root;
 }
 
-// Binary tree (tmp nodes, leaves = ranges of idx) -> blob: collapse to `width` children per node by opening the child of
-// largest area, lay nodes out breadth-first, emit triangles in leaf order, compute depth and the worst-case stack need.
+// Binary tree (tmp nodes, leaves = ranges of idx) -> blob: collapse to `width` children per node (the dynamic programme
+// below), lay nodes out breadth-first, emit triangles in leaf order, compute depth and the worst-case stack need.
 // octant_slots (width 8, layout BVH8O): a node's children are placed in the slot whose index names the corner of the node they sit in
 // — bit k of the slot = child lies towards +axis k — so that `slot ^ (sign bits of the ray direction)` is a front-to-back order
 // and the traversal needs no distance sort (the child-to-slot assignment of Ylitie, Karras & Laine, "Efficient incoherent ray
@@ -189,30 +189,25 @@ void emit_blob(const std::vector<Tmp> &tn, int32_t root, const std::vector<uint3
     std::vector<Pending> pend;
     pend.reserve(tn.size());
     // Which binary nodes become the children of a wide node: chosen by the SAH-optimal dynamic programme of Ylitie, Karras & Laine
-    // (HPG 2017, §3.1) — round 1-2 opened the child of largest area until the node was full (PTRT_COLLAPSE=area keeps that for
-    // comparison: 1M-triangle Cornell 7.60 -> 7.48 node visits per ray with 16 % fewer nodes, soup 28.92 -> 28.72).
+    // (HPG 2017, §3.1) — round 1-2 opened the child of largest area until the node was full (against that rule: 1M-triangle Cornell
+    // 7.60 -> 7.48 node visits per ray with 16 % fewer nodes, soup 28.92 -> 28.72).
     // cost[n][i-1] = least SAH cost of the subtree under binary node n when it may take up to i child slots of its parent (i = 1: n is
     // itself a node, or a leaf — the binary builder's leaves stay leaves, so the triangle term is a constant of the tree).
-    const char *collapse_env = getenv("PTRT_COLLAPSE");
-    const bool dp = !(collapse_env && std::strcmp(collapse_env, "area") == 0);
     const float c_tri = 0.6f; // a triangle test relative to a node visit
-    std::vector<float> cost;
+    std::vector<float> cost(tn.size() * width, 0.f);
     auto C = [&](int32_t n, uint32_t i) -> float & { return cost[(size_t)n * width + (i - 1)]; };
     auto best_split = [&](int32_t n, uint32_t j, uint32_t &kbest) { // least cost of giving j >= 2 slots to the two children of n
         float best = kInf; kbest = 1;
         for (uint32_t k = 1; k < j; ++k) { const float v = C(tn[n].left, k) + C(tn[n].right, j - k); if (v < best) { best = v; kbest = k; } }
         return best;
     };
-    if (dp) {
-        cost.assign(tn.size() * width, 0.f);
-        for (int64_t n = (int64_t)tn.size() - 1; n >= 0; --n) { // children have larger indices than their parents
-            const float a = tn[n].box.area() / std::max(tn[root].box.area(), 1e-30f);
-            if (tn[n].count) { for (uint32_t i = 1; i <= width; ++i) C((int32_t)n, i) = a * c_tri * (float)tn[n].count; continue; }
-            if (tn[n].left < 0 || tn[n].right < 0) continue; // (placeholder of the parallel build: never reachable)
-            uint32_t k;
-            C((int32_t)n, 1) = a + best_split((int32_t)n, width, k);
-            for (uint32_t i = 2; i <= width; ++i) C((int32_t)n, i) = std::min(best_split((int32_t)n, i, k), C((int32_t)n, i - 1));
-        }
+    for (int64_t n = (int64_t)tn.size() - 1; n >= 0; --n) { // children have larger indices than their parents
+        const float a = tn[n].box.area() / std::max(tn[root].box.area(), 1e-30f);
+        if (tn[n].count) { for (uint32_t i = 1; i <= width; ++i) C((int32_t)n, i) = a * c_tri * (float)tn[n].count; continue; }
+        if (tn[n].left < 0 || tn[n].right < 0) continue; // (placeholder of the parallel build: never reachable)
+        uint32_t k;
+        C((int32_t)n, 1) = a + best_split((int32_t)n, width, k);
+        for (uint32_t i = 2; i <= width; ++i) C((int32_t)n, i) = std::min(best_split((int32_t)n, i, k), C((int32_t)n, i - 1));
     }
     std::function<void(int32_t, uint32_t, Pending &)> gather = [&](int32_t n, uint32_t j, Pending &p) { // the <= j roots binary node n contributes
         if (tn[n].count || j == 1) { p.kids[p.nk++] = n; return; }
@@ -225,21 +220,8 @@ void emit_blob(const std::vector<Tmp> &tn, int32_t root, const std::vector<uint3
         Pending p; p.nk = 0;
         for (int i = 0; i < 8; ++i) p.kids[i] = -1;
         if (tn[t].count) { p.kids[p.nk++] = t; return p; } // (root is a leaf) single child
-        if (dp) {
-            uint32_t k; (void)best_split(t, width, k);
-            gather(tn[t].left, k, p); gather(tn[t].right, width - k, p);
-        } else {
-        p.kids[p.nk++] = tn[t].left; p.kids[p.nk++] = tn[t].right;
-        }
-        while (!dp && p.nk < (int)width) {
-            int best = -1; float ba = -1.f;
-            for (int i = 0; i < p.nk; ++i)
-                if (!tn[p.kids[i]].count) { const float a = tn[p.kids[i]].box.area(); if (a > ba) { ba = a; best = i; } }
-            if (best < 0) break;
-            const int32_t c = p.kids[best];
-            for (int i = p.nk; i > best + 1; --i) p.kids[i] = p.kids[i - 1];
-            p.kids[best] = tn[c].left; p.kids[best + 1] = tn[c].right; p.nk++;
-        }
+        uint32_t k; (void)best_split(t, width, k);
+        gather(tn[t].left, k, p); gather(tn[t].right, width - k, p);
         if (octant_slots && width == 8) {
             float cen[8][3], mid[3];
             Box all; all.reset();
@@ -318,86 +300,6 @@ void emit_blob(const std::vector<Tmp> &tn, int32_t root, const std::vector<uint3
     out.stack_need = need[0];
 }
 
-// Memory order of the node array (and optionally of the triangle array): pure renaming — refs change, the tree, the boxes and with
-// them every picture and visit counter do not (docs/SPEC.md §4.1: the order of nodes and triangles is not part of the contract).
-// Why it matters: beyond L2 the memory system moves 128-byte lines, a BVH4Q node is 64 bytes, so every node shares its line with
-// one neighbour; which neighbour decides how many of a ray's node fetches are new lines (layout experiments).
-//   order 0 : breadth-first as emitted (the children of a node are consecutive: a line holds two siblings)
-//   order 1 : depth-first pre-order (a line holds a node and its first inner child, or two nodes of neighbouring subtrees)
-//   order 2 : parent + largest child pairs, pairs in breadth-first order: a 128-byte line holds a node and the inner child of
-//             largest surface area (the one a ray that visits the node most probably visits too); nodes without inner children
-//             pair up among themselves in queue order
-//   order 3 : the same pairs in depth-first order (pairs of one subtree contiguous: van-Emde-Boas-like blocks of two)
-//   +16     : triangles re-emitted in the order the new node array references them
-void reorder_blob(BvhBlob &b, uint32_t mode)
-{
-    const uint32_t W = b.width, n = b.n_nodes, order = mode & 15u;
-    if (n < 2 || (order == 0 && !(mode & 16u))) return;
-    std::vector<uint32_t> ord; // new position -> old index
-    ord.reserve(n);
-    auto slot = [&](uint32_t i, uint32_t c) -> const BvhSlot & { return b.slots[(size_t)i * W + c]; };
-    if (order == 0) { for (uint32_t i = 0; i < n; ++i) ord.push_back(i); }
-    else if (order == 1) {
-        std::vector<uint32_t> st{ 0u };
-        while (!st.empty()) {
-            const uint32_t x = st.back(); st.pop_back();
-            ord.push_back(x);
-            for (int c = (int)W - 1; c >= 0; --c) { const int32_t r = slot(x, (uint32_t)c).ref; if (r >= 0 && r != kEmpty) st.push_back((uint32_t)r); }
-        }
-    } else {
-        std::vector<uint32_t> heads{ 0u }; // FIFO (order 2: read index) or LIFO (order 3)
-        size_t rd = 0;
-        int64_t pending = -1;
-        while (order == 2 ? rd < heads.size() : !heads.empty()) {
-            uint32_t x;
-            if (order == 2) x = heads[rd++]; else { x = heads.back(); heads.pop_back(); }
-            int best = -1; float ba = -1.f;
-            for (uint32_t c = 0; c < W; ++c) {
-                const BvhSlot &k = slot(x, c);
-                if (k.ref < 0 || k.ref == kEmpty) continue;
-                Box bx; for (int a = 0; a < 3; ++a) { bx.lo[a] = k.lo[a]; bx.hi[a] = k.hi[a]; }
-                const float ar = bx.area();
-                if (ar > ba) { ba = ar; best = (int)c; }
-            }
-            if (best < 0) { // no inner child: shares a line with the next node of its kind
-                if (pending >= 0) { ord.push_back((uint32_t)pending); ord.push_back(x); pending = -1; } else pending = x;
-                continue;
-            }
-            const uint32_t y = (uint32_t)slot(x, (uint32_t)best).ref;
-            ord.push_back(x); ord.push_back(y);
-            std::vector<uint32_t> next;
-            for (uint32_t c = 0; c < W; ++c) { const int32_t r = slot(x, c).ref; if (r >= 0 && r != kEmpty && (int)c != best) next.push_back((uint32_t)r); }
-            for (uint32_t c = 0; c < W; ++c) { const int32_t r = slot(y, c).ref; if (r >= 0 && r != kEmpty) next.push_back((uint32_t)r); }
-            if (order == 2) heads.insert(heads.end(), next.begin(), next.end());
-            else heads.insert(heads.end(), next.rbegin(), next.rend());
-        }
-        if (pending >= 0) ord.push_back((uint32_t)pending);
-    }
-    if (ord.size() != n) return; // (cannot happen for a tree) leave the blob as it is
-    std::vector<uint32_t> pos(n);
-    for (uint32_t i = 0; i < n; ++i) pos[ord[i]] = i;
-    std::vector<BvhSlot> ns((size_t)n * W);
-    for (uint32_t i = 0; i < n; ++i)
-        for (uint32_t c = 0; c < W; ++c) {
-            BvhSlot k = slot(ord[i], c);
-            if (k.ref >= 0 && k.ref != kEmpty) k.ref = (int32_t)pos[(uint32_t)k.ref];
-            ns[(size_t)i * W + c] = k;
-        }
-    b.slots.swap(ns);
-    if (mode & 16u) {
-        std::vector<BvhTri> nt;
-        nt.reserve(b.tris.size());
-        for (size_t i = 0; i < b.slots.size(); ++i) {
-            BvhSlot &k = b.slots[i];
-            if (k.ref >= 0) continue; // inner node or kEmpty (0x7fffffff)
-            const uint32_t enc = (uint32_t)~k.ref, first = enc >> 3, cnt = (enc & 7u) + 1u, nf = (uint32_t)nt.size();
-            for (uint32_t j = 0; j < cnt; ++j) nt.push_back(b.tris[first + j]);
-            k.ref = (int32_t)~((nf << 3) | (cnt - 1u));
-        }
-        b.tris.swap(nt);
-    }
-}
-
 } // namespace
 
 void build_bvh(const float *verts9, const uint32_t *mats, uint32_t n_tris, uint32_t width, BvhBlob &out, bool octant_slots)
@@ -423,7 +325,6 @@ void build_bvh(const float *verts9, const uint32_t *mats, uint32_t n_tris, uint3
     Builder B(prims, idx);
     const int32_t root = build_parallel(B, n_tris);
     emit_blob(B.nodes, root, idx, verts9, mats, n_tris, width, out, octant_slots);
-    if (const char *e = getenv("PTRT_NODE_ORDER")) reorder_blob(out, (uint32_t)atoi(e)); // developer aid: layout experiments (tools/exp_order.py)
     out.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 

@@ -78,6 +78,23 @@ def test_device_resources_have_one_owner():
         assert ".release(" not in body.group(0) and "delete " in body.group(0), name
 
 
+def test_environment_changes_no_tree():
+    """The library's sources and its header name two environment variables, PTRT_TRACE and PTRT_TIMING (stderr diagnostics), and every
+    getenv reads one of them: an exported variable cannot change a tree, a picture or a benchmarked number."""
+    allowed = {"PTRT_TRACE", "PTRT_TIMING"}
+    csrc = os.path.join(ROOT, "pathtracing_amd", "csrc")
+    paths = [os.path.join(d, f) for d, _, files in os.walk(csrc) for f in files if f.endswith((".cpp", ".hip", ".h", "Makefile"))]
+    assert len(paths) > 10
+    reads = []
+    for path in paths + [os.path.join(ROOT, "include", "ptrt.h")]:
+        txt = open(path, errors="replace").read()
+        named = set(re.findall(r"\bPTRT_[A-Z0-9_]+", txt)) - {"PTRT_H", "PTRT_ABI_VERSION"}
+        assert named <= allowed, (path, named - allowed)
+        if path.startswith(csrc):
+            reads += [(path, m) for m in re.findall(r"getenv\s*\(\s*([^)]*)\)", txt)]
+    assert reads and all(arg.strip('"') in allowed for _, arg in reads), reads
+
+
 @pytest.mark.parametrize("w,h,nr", [(1920, 1080, 1), (1920, 1080, 8), (3840, 2160, 8), (100, 37, 3), (64, 64, 2), (65, 1, 4)])
 def test_tile_layout_partitions_the_frame(P, w, h, nr):
     seen = np.zeros(((h + 63) // 64) * ((w + 63) // 64), int)
