@@ -11,8 +11,8 @@
 //   k_shade<MODE>      : the split pipeline's second kernel (PT_FLAG_SPLIT_KERNELS / PT_FLAG_BUCKET_SPECULAR): walks
 //                        the queue k_extend<.., SHADE_NONE> just walked; QUEUE/INLINE shade in queue order, BUCKETS
 //                        shades the metal / dielectric hits that QUEUE deferred to per-kind bucket queues
-//   k_trace<L,MODE>    : pt_trace_rays: caller rays -> closest hit (or any hit: occlusion), one ray per lane on k_extend's
-//                        traversal core, no path state
+//   k_trace<L,MODE>    : pt_trace_rays: caller rays -> closest hit (or any hit: occlusion), one ray per lane through trace_ray,
+//                        the function k_extend traces its rays with; no path state
 //   k_reduce_streams   : fixed-order sum of a pixel's stream partials
 //   k_assemble         : tile-major slots (of 1..R ranks) -> row-major float4 + RGBA8 frame
 //
@@ -26,6 +26,7 @@
 #include "pt_device.h"
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 
 using namespace ptd;
@@ -57,6 +58,14 @@ PT_DEV uint32_t spheres_test(const float4 *spheres, uint32_t n_spheres, uint32_t
     }
     return n_spheres;
 }
+// The hot arguments of the one-ray-per-lane kernels (k_extend, k_trace), as trace_ray takes them: copied out of the kernel's DeviceScene
+// once, they stay in SGPRs across the traversal loop (everything else is read through cold() where it is used, see ExtArgs).
+struct HotScene {
+    const float4 *__restrict__ nodes, *__restrict__ tris, *__restrict__ spheres;
+    uint32_t n_spheres, n_tris, n_nodes;
+};
+PT_DEV HotScene hot_scene(const DeviceScene &sc) { return HotScene{ sc.nodes, sc.tris, sc.spheres, sc.n_spheres, sc.n_tris, sc.n_nodes }; }
+PT_DEV uint32_t spheres_test(const HotScene &g, V3 o, V3 d, Hit &h) { return spheres_test(g.spheres, g.n_spheres, g.n_tris, o, d, h); }
 
 // Append `value` of every lane with `pred` to queue: one ballot, one atomic per wavefront, mbcnt prefix.
 // Must be reached by all live lanes of the wave in uniform control flow.
@@ -447,6 +456,20 @@ PT_DEV void path_init(const DeviceScene &sc, const FrameParams &fp, uint32_t slo
     camera_ray_of(sc.cam, x, y, r.key, r.o, r.d);
     r.T = v3(1.f, 1.f, 1.f);
     r.depth = 0u;
+}
+// The state a fused extend kernel starts a slot with in launch `it`: the frame's first launch makes it itself (api.cpp: q_init) and
+// starts the slot's radiance sum; every later one loads what the launch before it stored (NEE: and the words path_store_nee added).
+template <bool NEE = false>
+PT_DEV void path_begin(uint32_t it, uint32_t slot, PathRegs &r, NeeRegs *nr = nullptr)
+{
+    if (it == 0u) {
+        path_init(cold().sc, cold().fp, slot, r);
+        if (!cold().fp.accumulate) at(cold().ps.acc, slot) = make_float4(0.f, 0.f, 0.f, 0.f);
+    } else {
+        const PathState &ps = cold().ps;
+        path_load(ps, slot, r);
+        if constexpr (NEE) { nr->flags = __float_as_uint(at(ps.ray_o, slot).w); nr->aux = at(ps.ray_d, slot).w; }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -860,6 +883,20 @@ PT_DEV uint32_t leaf_step(const float4 *__restrict__ tris, const StackCtx &k, V3
     cur = pop_after_leaf(k, sp);
     return n;
 }
+// Occlusion leaf: its triangles in array order until one is accepted, which ends the ray (cur = PT_BVH_EMPTY); else the next stack entry.
+PT_DEV void leaf_step_any(const float4 *__restrict__ tris, const StackCtx &k, V3 o, V3 d, Hit &h, int32_t &cur, uint32_t &sp)
+{
+    const uint32_t enc = (uint32_t)~cur;
+    uint32_t first = enc >> 3, more = enc & 7u;
+    for (;;) {
+        const float4 *base = tris + (size_t)first * 4;
+        tri_test(base[0], base[1], base[2], first, o, d, h);
+        if (h.id != PT_MISS) { cur = PT_BVH_EMPTY; return; }
+        if (more == 0u) break;
+        ++first; --more;
+    }
+    cur = pop_after_leaf(k, sp);
+}
 
 // Finish mode (n_alive <= finish_below): a launch keeps going until its paths end, but never for more than this many
 // vertices per lane, so that a launch stays bounded whatever spp and max_depth are; the host loop simply goes on.
@@ -935,6 +972,63 @@ PT_DEV void flush_visit_counters(const PathState &ps, const VisitCounts &v)
     add(kCntSph, v.sph);
 }
 
+// The life of one ray of the one-ray-per-lane kernels (k_extend, k_trace): the sphere list, then the tree from its root. `h` comes in
+// as the hit the ray starts with — (+inf, MISS), or (tmax, MISS) for a shadow ray or a caller's query — and goes back as its closest hit.
+//   COUNT : tally node visits / triangle tests / sphere tests (docs/SPEC.md §4.1) in `vc`
+//   DIAG  : k_extend<COUNT>'s wave diagnostics on top: wave_iters, wave_iters_late, idle_leaf, idle_done, read from `s_state`, where
+//           every lane of the wave mirrors its `cur` (the caller has written 0 = a ray, 1 = none). k_trace<TRACE_COUNT> records none
+//   ANY   : occlusion (§4.2): a sphere hit skips the tree, the first accepted triangle ends the leaf and the node loop of its lane
+template <int L, bool COUNT, bool DIAG, bool ANY>
+PT_DEV Hit trace_ray(const HotScene &g, const StackCtx &stk, V3 o, V3 d, Hit h, VisitCounts &vc, int32_t *s_state)
+{
+    { const uint32_t ns = spheres_test(g, o, d, h); if (COUNT) vc.sph += ns; }
+
+    const RaySetup rs = ray_setup(o, d);
+    int32_t cur = PT_BVH_EMPTY;
+    uint32_t sp = 0, steps = 0;
+    // Every ray starts at node 0, whose rows are the same for the whole wave: this first visit reads them with one scalar load
+    // (no vector gather to wait for) and runs at full width before the divergent node loop (headline 17.03 -> 16.88 ms, Cornell
+    // 7.31 -> 7.02, Cornell+glass+metal 32.6 -> 31.9).
+    if (g.n_nodes && !(ANY && h.id != PT_MISS)) {
+        ++steps;
+        if (COUNT) vc.nodes++;
+        if (DIAG && lane_id() == (uint32_t)(__ffsll((long long)__ballot(1)) - 1)) vc.wave_iters++;
+        const uniform_f4 root = as_uniform(g.nodes);
+        node_visit_rows<L>(g.nodes, uniform_load(root, 0), uniform_load(root, 1), uniform_load(root, 2), uniform_load(root, 3), stk, rs, h.t, cur, sp);
+        if (DIAG) s_state[stk.tid & 63u] = cur;
+    }
+
+    // while-while: a lane that reaches a leaf waits at the reconvergence point of the node loop until every lane of
+    // the wave is at a leaf or done; then the leaves are tested together. Each lane still makes exactly the visits,
+    // in exactly the order, of docs/SPEC.md §4.1 (only the interleaving across lanes changes), so hits and visit
+    // counters are the oracle's. Why: with one loop for both kinds of step the wave issued the ~160-instruction node
+    // code AND the ~125-instruction triangle code in practically every iteration, the latter for ~1 lane in 8; the
+    // kernel is VALU-issue bound (rocprofv3: 34 % of wave time waits for an issue slot, 43 % of VALU lanes active).
+    bool late_cycle = false; // (DIAG) set once this wave has run a leaf phase for the current rays
+    for (;;) {
+        while ((uint32_t)cur < (uint32_t)PT_BVH_EMPTY) { // ---- node phase: inner-node refs are 0 .. 0x7ffffffe (EMPTY = 0x7fffffff)
+            if (++steps > (1u << 22)) { atomicOr(&cold().ps.counters[kCntError], 2u); cur = PT_BVH_EMPTY; break; }
+            if (COUNT) vc.nodes++;
+            // one lane per wave-iteration counts it; [1]: iterations after the wave's first leaf phase of this ray
+            if (DIAG && lane_id() == (uint32_t)(__ffsll((long long)__ballot(1)) - 1)) {
+                vc.wave_iters++; if (late_cycle) vc.wave_iters_late++;
+                // why the other lanes of this iteration are idle (their state sits in LDS: they are masked off here)
+                uint32_t n_leaf = 0, n_done = 0;
+                for (uint32_t l = 0; l < 64u; ++l) { const int32_t c2 = s_state[l]; n_leaf += c2 < 0 ? 1u : 0u; n_done += c2 == PT_BVH_EMPTY ? 1u : 0u; }
+                vc.idle_leaf += n_leaf; vc.idle_done += n_done;
+            }
+            node_step<L>(g.nodes, stk, rs, h.t, cur, sp);
+            if (DIAG) s_state[stk.tid & 63u] = cur;
+        }
+        if (cur == PT_BVH_EMPTY) break;
+        if (DIAG) late_cycle = true;
+        if (ANY) leaf_step_any(g.tris, stk, o, d, h, cur, sp); // ---- leaf phase
+        else { const uint32_t nt = leaf_step(g.tris, stk, o, d, h, cur, sp); if (COUNT) vc.tris += nt; }
+        if (DIAG) s_state[stk.tid & 63u] = cur;
+    }
+    return h;
+}
+
 // NEE (PT_FLAG_NEXT_EVENT; fused, not counting): one ray per lane per pass, a shadow ray or an extension ray (see NeeRegs); `bounces`
 // then counts passes.
 template <int L, bool COUNT, int FUSE, bool NEE = false>
@@ -942,9 +1036,7 @@ __global__ void __launch_bounds__(kExtBlock) __attribute__((amdgpu_waves_per_eu(
 k_extend(typename ExtArgsOf<NEE>::type a)
 {
     static_assert(!NEE || (FUSE != SHADE_NONE && !COUNT), "NEE: fused shading, no visit counters");
-    // hot arguments (stay in SGPRs across the traversal loop); everything else goes through cold()
-    const float4 *__restrict__ nodes = a.sc.nodes, *__restrict__ tris = a.sc.tris, *__restrict__ spheres = a.sc.spheres;
-    const uint32_t n_spheres = a.sc.n_spheres, n_tris = a.sc.n_tris, n_nodes = a.sc.n_nodes;
+    const HotScene g = hot_scene(a.sc);
     const uint32_t it = a.it;
     __shared__ int32_t s_stack[kStackLds * kExtBlock];
     __shared__ uint32_t s_stash[(FUSE != SHADE_NONE ? (NEE ? 7 : 5) : 1) * kExtBlock];
@@ -973,21 +1065,13 @@ k_extend(typename ExtArgsOf<NEE>::type a)
     const StackCtx stk{ s_stack, kExtBlock, tid, qbase + gid };
 
     VisitCounts vc;
-    __shared__ int32_t s_state[COUNT ? 64 : 1]; // COUNT diagnostics: every lane's `cur` (1 = no ray), readable by the lane that counts
+    __shared__ int32_t s_state[COUNT ? 64 : 1]; // trace_ray's DIAG: every lane's `cur` (1 = no ray), readable by the lane that counts
     PathRegs r;
     r.o = v3(0.f, 0.f, 0.f); r.d = v3(0.f, 0.f, 1.f); r.T = v3(0.f, 0.f, 0.f); r.key = r.sample = r.depth = 0u;
     NeeRegs nr{ 0.0f, 0u };
     if (active) {
-        const PathState &ps = cold().ps;
-        if (FUSE == SHADE_NONE) { r.o = xyz(at(ps.ray_o, slot)); r.d = xyz(at(ps.ray_d, slot)); }
-        else if (it == 0u) { // the frame's first launch makes the state of its slots itself (api.cpp: q_init) and starts their radiance sums
-            path_init(cold().sc, cold().fp, slot, r);
-            if (!cold().fp.accumulate) at(ps.acc, slot) = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        else {
-            path_load(ps, slot, r);
-            if constexpr (NEE) { nr.flags = __float_as_uint(at(ps.ray_o, slot).w); nr.aux = at(ps.ray_d, slot).w; }
-        }
+        if (FUSE == SHADE_NONE) { const PathState &ps = cold().ps; r.o = xyz(at(ps.ray_o, slot)); r.d = xyz(at(ps.ray_d, slot)); }
+        else path_begin<NEE>(it, slot, r, &nr);
     }
     bool alive = active;
     uint32_t wave_rays = 0;
@@ -1005,50 +1089,7 @@ k_extend(typename ExtArgsOf<NEE>::type a)
             asm volatile("" ::: "memory");
         }
 
-        { const uint32_t ns = spheres_test(spheres, n_spheres, n_tris, o, d, h); if (COUNT) vc.sph += ns; }
-
-        const RaySetup rs = ray_setup(o, d);
-        int32_t cur = n_nodes ? 0 : PT_BVH_EMPTY;
-        uint32_t sp = 0, steps = 0;
-        // Every ray starts at node 0, whose rows are the same for the whole wave: this first visit reads them with one scalar load
-        // (no vector gather to wait for) and runs at full width before the divergent node loop (headline 17.03 -> 16.88 ms, Cornell
-        // 7.31 -> 7.02, Cornell+glass+metal 32.6 -> 31.9).
-        if (n_nodes) {
-            ++steps;
-            if (COUNT) { vc.nodes++; if (lane_id() == (uint32_t)(__ffsll((long long)__ballot(1)) - 1)) vc.wave_iters++; }
-            const uniform_f4 root = as_uniform(nodes);
-            node_visit_rows<L>(nodes, uniform_load(root, 0), uniform_load(root, 1), uniform_load(root, 2), uniform_load(root, 3), stk, rs, h.t, cur, sp);
-            if (COUNT) s_state[tid & 63u] = cur;
-        }
-
-        // while-while: a lane that reaches a leaf waits at the reconvergence point of the node loop until every lane of
-        // the wave is at a leaf or done; then the leaves are tested together. Each lane still makes exactly the visits,
-        // in exactly the order, of docs/SPEC.md §4.1 (only the interleaving across lanes changes), so hits and visit
-        // counters are the oracle's. Why: with one loop for both kinds of step the wave issued the ~160-instruction node
-        // code AND the ~125-instruction triangle code in practically every iteration, the latter for ~1 lane in 8; the
-        // kernel is VALU-issue bound (rocprofv3: 34 % of wave time waits for an issue slot, 43 % of VALU lanes active).
-        bool late_cycle = false; // (COUNT diagnostics) set once this wave has run a leaf phase for the current rays
-        for (;;) {
-            while ((uint32_t)cur < (uint32_t)PT_BVH_EMPTY) { // ---- node phase: inner-node refs are 0 .. 0x7ffffffe (EMPTY = 0x7fffffff)
-                if (++steps > (1u << 22)) { atomicOr(&cold().ps.counters[kCntError], 2u); cur = PT_BVH_EMPTY; break; }
-                if (COUNT) { // one lane per wave-iteration counts it; [1]: iterations after the wave's first leaf phase of this ray
-                    vc.nodes++;
-                    if (lane_id() == (uint32_t)(__ffsll((long long)__ballot(1)) - 1)) {
-                        vc.wave_iters++; if (late_cycle) vc.wave_iters_late++;
-                        // why the other lanes of this iteration are idle (their state sits in LDS: they are masked off here)
-                        uint32_t n_leaf = 0, n_done = 0;
-                        for (uint32_t l = 0; l < 64u; ++l) { const int32_t c2 = s_state[l]; n_leaf += c2 < 0 ? 1u : 0u; n_done += c2 == PT_BVH_EMPTY ? 1u : 0u; }
-                        vc.idle_leaf += n_leaf; vc.idle_done += n_done;
-                    }
-                }
-                node_step<L>(nodes, stk, rs, h.t, cur, sp);
-                if (COUNT) s_state[tid & 63u] = cur;
-            }
-            if (cur == PT_BVH_EMPTY) break;
-            if (COUNT) late_cycle = true;
-            const uint32_t nt = leaf_step(tris, stk, o, d, h, cur, sp); // ---- leaf phase
-            if (COUNT) { vc.tris += nt; s_state[tid & 63u] = cur; }
-        }
+        h = trace_ray<L, COUNT, COUNT, false>(g, stk, o, d, h, vc, s_state);
 
         if (FUSE == SHADE_NONE) at(cold().ps.hit, slot) = make_float2(h.t, __uint_as_float(h.ref)); // k_shade walks the same queue in the same order
         else {
@@ -1097,7 +1138,8 @@ template <int L, bool COUNT, int FUSE>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT_PACKED_WAVES(FUSE), PT_PACKED_WAVES(FUSE))))
 k_extend_packed(ExtArgs a)
 {
-    // hot arguments stay in SGPRs; everything else is read through cold() where it is used (see ExtArgs)
+    // hot arguments stay in SGPRs; everything else is read through cold() where it is used (see ExtArgs). Not folded into a HotScene:
+    // through one, this kernel's and k_extend_pool's instruction schedules change
     const float4 *__restrict__ nodes = a.sc.nodes, *__restrict__ tris = a.sc.tris, *__restrict__ spheres = a.sc.spheres;
     const uint32_t n_spheres = a.sc.n_spheres, n_tris = a.sc.n_tris, n_nodes = a.sc.n_nodes;
     const uint32_t it = a.it, chunk = a.chunk, bounces = a.bounces;
@@ -1175,11 +1217,7 @@ k_extend_packed(ExtArgs a)
                 if (FUSE != SHADE_NONE && !do_compact) q_next[pos] = kInvalidSlot;
             } else if (pull) {
                 if (FUSE == SHADE_NONE) { o = xyz(at(cold().ps.ray_o, slot)); d = xyz(at(cold().ps.ray_d, slot)); }
-                else if (it == 0u) { // see k_extend
-                    path_init(cold().sc, cold().fp, slot, r);
-                    if (!cold().fp.accumulate) at(cold().ps.acc, slot) = make_float4(0.f, 0.f, 0.f, 0.f);
-                }
-                else path_load(cold().ps, slot, r);
+                else path_begin(it, slot, r);
                 budget = budget0;
                 start_ray();
                 has = true;
@@ -1403,15 +1441,14 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT_POOL
 
 // ------------------------------------------------------------------------------------------------
 // k_trace<L, MODE>: pt_trace_rays (docs/SPEC.md §4.2). Caller rays {o.xyz | tmax, d.xyz | 0} -> hit records {t, prim id, u, v}, one
-// ray per lane on k_extend's while-while traversal (sphere list, root visit from one scalar load, node_step / leaf_step phases), the
-// closest hit started from (tmax, MISS) instead of (+inf, MISS). Grid-stride: a grid of at most kTraceBlocks one-wave workgroups walks
+// ray per lane through trace_ray, the function k_extend traces its rays with, the closest hit started from (tmax, MISS) instead of
+// (+inf, MISS). Grid-stride: a grid of at most kTraceBlocks one-wave workgroups walks
 // the batch and every lane keeps its overflow-stack column (blockIdx.x * 64 + lane) for all of its rays, so the overflow area is
 // bounded by the grid, not by the batch.
 //   TRACE_CLOSEST   : closest hit; a triangle's u, v are recomputed from the winning record after traversal (tri_uv), so tri_test
 //                     carries nothing more through the loop
 //   TRACE_COUNT     : the same, counting node visits / triangle / sphere tests (SPEC §4.1) into the trace's own counter block
-//   TRACE_OCCLUSION : any hit with t <= tmax ends the ray: a sphere hit skips the traversal, the first accepted triangle ends the leaf
-//                     and the node loop of its lane (no visit order is promised, so there is no counting variant)
+//   TRACE_OCCLUSION : any hit with t <= tmax ends the ray (trace_ray's ANY; no visit order is promised, so there is no counting variant)
 // The kernel arguments begin with an ExtArgs of which only ps.counters / stack_ovf / stack_ovf_entries / shard_cap are set: cold()
 // and the stack helpers reach the overflow area and the error word exactly as they do from the extend kernels.
 enum TraceMode { TRACE_CLOSEST = 0, TRACE_COUNT = 1, TRACE_OCCLUSION = 2 };
@@ -1421,28 +1458,13 @@ struct TraceArgs : ExtArgs {
     uint32_t n;
 };
 
-// Occlusion leaf: its triangles in array order until one is accepted, which ends the ray (cur = PT_BVH_EMPTY); else the next stack entry.
-PT_DEV void leaf_step_any(const float4 *__restrict__ tris, const StackCtx &k, V3 o, V3 d, Hit &h, int32_t &cur, uint32_t &sp)
-{
-    const uint32_t enc = (uint32_t)~cur;
-    uint32_t first = enc >> 3, more = enc & 7u;
-    for (;;) {
-        const float4 *base = tris + (size_t)first * 4;
-        tri_test(base[0], base[1], base[2], first, o, d, h);
-        if (h.id != PT_MISS) { cur = PT_BVH_EMPTY; return; }
-        if (more == 0u) break;
-        ++first; --more;
-    }
-    cur = pop_after_leaf(k, sp);
-}
-
 template <int L, int MODE>
 __global__ void __launch_bounds__(kExtBlock) __attribute__((amdgpu_waves_per_eu(PT_EXT_WAVES(L, SHADE_NONE), PT_EXT_WAVES(L, SHADE_NONE))))
 k_trace(TraceArgs a)
 {
     constexpr bool COUNT = MODE == TRACE_COUNT, ANY = MODE == TRACE_OCCLUSION;
-    const float4 *__restrict__ nodes = a.sc.nodes, *__restrict__ tris = a.sc.tris, *__restrict__ spheres = a.sc.spheres;
-    const uint32_t n_spheres = a.sc.n_spheres, n_tris = a.sc.n_tris, n_nodes = a.sc.n_nodes, n = a.n;
+    const HotScene g = hot_scene(a.sc);
+    const uint32_t n = a.n;
     const float4 *__restrict__ rays = a.rays;
     float4 *__restrict__ hits = a.hits;
     __shared__ int32_t s_stack[kStackLds * kExtBlock];
@@ -1455,30 +1477,9 @@ k_trace(TraceArgs a)
         const float4 ro = rays[2u * (size_t)i], rd = rays[2u * (size_t)i + 1u];
         const V3 o = xyz(ro), d = xyz(rd);
         Hit h{ ro.w, PT_MISS, PT_MISS };
-        if (ro.w > 0.0f) { // tmax <= 0 or NaN: nothing can be accepted (docs/SPEC.md §4.2)
-            { const uint32_t ns = spheres_test(spheres, n_spheres, n_tris, o, d, h); if (COUNT) vc.sph += ns; }
-            const RaySetup rs = ray_setup(o, d);
-            int32_t cur = PT_BVH_EMPTY;
-            uint32_t sp = 0, steps = 0;
-            if (n_nodes && !(ANY && h.id != PT_MISS)) { // root visit: one scalar load of node 0's rows, as in k_extend
-                ++steps;
-                if (COUNT) vc.nodes++;
-                const uniform_f4 root = as_uniform(nodes);
-                node_visit_rows<L>(nodes, uniform_load(root, 0), uniform_load(root, 1), uniform_load(root, 2), uniform_load(root, 3), stk, rs, h.t, cur, sp);
-            }
-            for (;;) { // while-while, as in k_extend
-                while ((uint32_t)cur < (uint32_t)PT_BVH_EMPTY) {
-                    if (++steps > (1u << 22)) { atomicOr(&cold().ps.counters[kCntError], 2u); cur = PT_BVH_EMPTY; break; }
-                    if (COUNT) vc.nodes++;
-                    node_step<L>(nodes, stk, rs, h.t, cur, sp);
-                }
-                if (cur == PT_BVH_EMPTY) break;
-                if (ANY) leaf_step_any(tris, stk, o, d, h, cur, sp);
-                else { const uint32_t nt = leaf_step(tris, stk, o, d, h, cur, sp); if (COUNT) vc.tris += nt; }
-            }
-        }
+        if (ro.w > 0.0f) h = trace_ray<L, COUNT, false, ANY>(g, stk, o, d, h, vc, nullptr); // tmax <= 0 or NaN: nothing can be accepted (§4.2)
         float u = 0.0f, v = 0.0f;
-        if (!ANY && h.ref < n_tris) { const float4 *t = tris + (size_t)h.ref * 4; tri_uv(t[0], t[1], t[2], o, d, u, v); }
+        if (!ANY && h.ref < g.n_tris) { const float4 *t = g.tris + (size_t)h.ref * 4; tri_uv(t[0], t[1], t[2], o, d, u, v); }
         hits[i] = h.id == PT_MISS ? make_float4(__builtin_inff(), __uint_as_float(PT_MISS), 0.0f, 0.0f) : make_float4(h.t, __uint_as_float(h.id), u, v);
     }
     if (COUNT) flush_visit_counters(cold().ps, vc);
@@ -1595,24 +1596,26 @@ hipError_t launch_generate(hipStream_t s, const DeviceScene &sc, const PathState
     return hipGetLastError();
 }
 
-template <int L, bool C>
-static void extend_lc(hipStream_t s, dim3 grid, const ExtArgs &a, int kernel, int fuse)
+// Run-time launch parameters -> template arguments: f is called with a std::integral_constant of the node layout / the fused shading.
+// with_layout returns false, without calling f, for a layout that does not exist.
+template <typename F>
+static bool with_layout(uint32_t width, F &&f)
 {
-    if (kernel == EXT_POOL && fuse == SHADE_INLINE) hipLaunchKernelGGL((k_extend_pool<L, C, SHADE_INLINE>), grid, dim3(64), 0, s, a);
-    else if (kernel == EXT_POOL) hipLaunchKernelGGL((k_extend_pool<L, C, SHADE_QUEUE>), grid, dim3(64), 0, s, a);
-    else if (kernel == EXT_PACKED && fuse == SHADE_QUEUE) hipLaunchKernelGGL((k_extend_packed<L, C, SHADE_QUEUE>), grid, dim3(64), 0, s, a);
-    else if (kernel == EXT_PACKED && fuse == SHADE_INLINE) hipLaunchKernelGGL((k_extend_packed<L, C, SHADE_INLINE>), grid, dim3(64), 0, s, a);
-    else if (kernel == EXT_PACKED) hipLaunchKernelGGL((k_extend_packed<L, C, SHADE_NONE>), grid, dim3(64), 0, s, a);
-    else if (fuse == SHADE_QUEUE) hipLaunchKernelGGL((k_extend<L, C, SHADE_QUEUE>), grid, dim3(kExtBlock), 0, s, a);
-    else if (fuse == SHADE_INLINE) hipLaunchKernelGGL((k_extend<L, C, SHADE_INLINE>), grid, dim3(kExtBlock), 0, s, a);
-    else hipLaunchKernelGGL((k_extend<L, C, SHADE_NONE>), grid, dim3(kExtBlock), 0, s, a);
+    switch (width) {
+    case PT_BVH_WIDTH_2: f(std::integral_constant<int, PT_BVH_WIDTH_2>{}); return true;
+    case PT_BVH_WIDTH_4: f(std::integral_constant<int, PT_BVH_WIDTH_4>{}); return true;
+    case PT_BVH_WIDTH_4Q: f(std::integral_constant<int, PT_BVH_WIDTH_4Q>{}); return true;
+    case PT_BVH_WIDTH_8Q: f(std::integral_constant<int, PT_BVH_WIDTH_8Q>{}); return true;
+    case PT_BVH_WIDTH_8O: f(std::integral_constant<int, PT_BVH_WIDTH_8O>{}); return true;
+    default: return false;
+    }
 }
-
-template <int L>
-static void extend_nee(hipStream_t s, dim3 grid, const ExtArgsNee &a, int fuse)
+template <typename F>
+static void with_fuse(int fuse, F &&f)
 {
-    if (fuse == SHADE_INLINE) hipLaunchKernelGGL((k_extend<L, false, SHADE_INLINE, true>), grid, dim3(kExtBlock), 0, s, a);
-    else hipLaunchKernelGGL((k_extend<L, false, SHADE_QUEUE, true>), grid, dim3(kExtBlock), 0, s, a);
+    if (fuse == SHADE_QUEUE) f(std::integral_constant<int, SHADE_QUEUE>{});
+    else if (fuse == SHADE_INLINE) f(std::integral_constant<int, SHADE_INLINE>{});
+    else f(std::integral_constant<int, SHADE_NONE>{});
 }
 
 hipError_t launch_extend(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp, uint32_t it, uint32_t shard_bound, bool count,
@@ -1627,37 +1630,25 @@ hipError_t launch_extend(hipStream_t s, const DeviceScene &sc, const PathState &
     const dim3 grid = shard_grid(shard_bound ? (shard_bound + per_block - 1) / per_block : 1u, ps.shard_count);
     ExtArgs a;
     a.sc = sc; a.ps = ps; a.fp = fp; a.it = it; a.compact = compact ? 1u : 0u; a.bounces = bounces ? bounces : 1u; a.chunk = chunk;
-    if (nee) { // the one-ray-per-lane kernel, fused, not counting (api.cpp refuses every other combination before it gets here)
-        if (kernel != EXT_SIMPLE || count || fuse == SHADE_NONE) return hipErrorInvalidValue;
-        ExtArgsNee an;
-        static_cast<ExtArgs &>(an) = a; an.nee = *nee;
-        switch (sc.bvh_width) {
-        case PT_BVH_WIDTH_2: extend_nee<PT_BVH_WIDTH_2>(s, grid, an, fuse); break;
-        case PT_BVH_WIDTH_4: extend_nee<PT_BVH_WIDTH_4>(s, grid, an, fuse); break;
-        case PT_BVH_WIDTH_4Q: extend_nee<PT_BVH_WIDTH_4Q>(s, grid, an, fuse); break;
-        case PT_BVH_WIDTH_8Q: extend_nee<PT_BVH_WIDTH_8Q>(s, grid, an, fuse); break;
-        case PT_BVH_WIDTH_8O: extend_nee<PT_BVH_WIDTH_8O>(s, grid, an, fuse); break;
-        default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    switch (sc.bvh_width) {
-    case PT_BVH_WIDTH_2:  count ? extend_lc<PT_BVH_WIDTH_2, true>(s, grid, a, kernel, fuse) : extend_lc<PT_BVH_WIDTH_2, false>(s, grid, a, kernel, fuse); break;
-    case PT_BVH_WIDTH_4:  count ? extend_lc<PT_BVH_WIDTH_4, true>(s, grid, a, kernel, fuse) : extend_lc<PT_BVH_WIDTH_4, false>(s, grid, a, kernel, fuse); break;
-    case PT_BVH_WIDTH_4Q: count ? extend_lc<PT_BVH_WIDTH_4Q, true>(s, grid, a, kernel, fuse) : extend_lc<PT_BVH_WIDTH_4Q, false>(s, grid, a, kernel, fuse); break;
-    case PT_BVH_WIDTH_8Q: count ? extend_lc<PT_BVH_WIDTH_8Q, true>(s, grid, a, kernel, fuse) : extend_lc<PT_BVH_WIDTH_8Q, false>(s, grid, a, kernel, fuse); break;
-    case PT_BVH_WIDTH_8O: count ? extend_lc<PT_BVH_WIDTH_8O, true>(s, grid, a, kernel, fuse) : extend_lc<PT_BVH_WIDTH_8O, false>(s, grid, a, kernel, fuse); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
-template <int L>
-static void trace_l(hipStream_t s, dim3 grid, const TraceArgs &a, int mode)
-{
-    if (mode == TRACE_OCCLUSION) hipLaunchKernelGGL((k_trace<L, TRACE_OCCLUSION>), grid, dim3(kExtBlock), 0, s, a);
-    else if (mode == TRACE_COUNT) hipLaunchKernelGGL((k_trace<L, TRACE_COUNT>), grid, dim3(kExtBlock), 0, s, a);
-    else hipLaunchKernelGGL((k_trace<L, TRACE_CLOSEST>), grid, dim3(kExtBlock), 0, s, a);
+    // NEE: the one-ray-per-lane kernel, fused, not counting (api.cpp refuses every other combination before it gets here)
+    if (nee && (kernel != EXT_SIMPLE || count || fuse == SHADE_NONE)) return hipErrorInvalidValue;
+    ExtArgsNee an;
+    static_cast<ExtArgs &>(an) = a;
+    if (nee) an.nee = *nee;
+    // layout x fuse x (NEE | count x kernel): the pool and NEE kernels always shade, so they have no SHADE_NONE instantiation
+    const bool known = with_layout(sc.bvh_width, [&](auto lc) { with_fuse(fuse, [&](auto fc) {
+        constexpr int L = decltype(lc)::value, F = decltype(fc)::value, FS = F == SHADE_NONE ? SHADE_QUEUE : F;
+        auto go = [&](auto cc) {
+            constexpr bool C = decltype(cc)::value;
+            if (kernel == EXT_POOL) hipLaunchKernelGGL((k_extend_pool<L, C, FS>), grid, dim3(64), 0, s, a);
+            else if (kernel == EXT_PACKED) hipLaunchKernelGGL((k_extend_packed<L, C, F>), grid, dim3(64), 0, s, a);
+            else hipLaunchKernelGGL((k_extend<L, C, F>), grid, dim3(kExtBlock), 0, s, a);
+        };
+        if (nee) hipLaunchKernelGGL((k_extend<L, false, FS, true>), grid, dim3(kExtBlock), 0, s, an);
+        else if (count) go(std::true_type{});
+        else go(std::false_type{});
+    }); });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 uint32_t trace_blocks(uint32_t n) { return std::max(1u, std::min(kTraceBlocks, (n + kExtBlock - 1u) / kExtBlock)); }
@@ -1667,16 +1658,13 @@ hipError_t launch_trace(hipStream_t s, const DeviceScene &sc, const PathState &p
     TraceArgs a{};
     a.sc = sc; a.ps = ps; a.rays = rays; a.hits = hits; a.n = n;
     const dim3 grid(trace_blocks(n));
-    const int mode = occlusion ? TRACE_OCCLUSION : count ? TRACE_COUNT : TRACE_CLOSEST;
-    switch (sc.bvh_width) {
-    case PT_BVH_WIDTH_2: trace_l<PT_BVH_WIDTH_2>(s, grid, a, mode); break;
-    case PT_BVH_WIDTH_4: trace_l<PT_BVH_WIDTH_4>(s, grid, a, mode); break;
-    case PT_BVH_WIDTH_4Q: trace_l<PT_BVH_WIDTH_4Q>(s, grid, a, mode); break;
-    case PT_BVH_WIDTH_8Q: trace_l<PT_BVH_WIDTH_8Q>(s, grid, a, mode); break;
-    case PT_BVH_WIDTH_8O: trace_l<PT_BVH_WIDTH_8O>(s, grid, a, mode); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    const bool known = with_layout(sc.bvh_width, [&](auto lc) {
+        constexpr int L = decltype(lc)::value;
+        if (occlusion) hipLaunchKernelGGL((k_trace<L, TRACE_OCCLUSION>), grid, dim3(kExtBlock), 0, s, a);
+        else if (count) hipLaunchKernelGGL((k_trace<L, TRACE_COUNT>), grid, dim3(kExtBlock), 0, s, a);
+        else hipLaunchKernelGGL((k_trace<L, TRACE_CLOSEST>), grid, dim3(kExtBlock), 0, s, a);
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 hipError_t launch_shade(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp, uint32_t it, uint32_t shard_bound, int mode, bool compact)

@@ -36,7 +36,8 @@ constexpr uint32_t kTraceBlocks = 16384;
 constexpr uint32_t kPool = PT_POOL;                // queue entries per wavefront of k_extend_pool (64 P)
 enum ExtendKernel : int { EXT_SIMPLE = 1, EXT_PACKED = 2, EXT_POOL = 3 }; // pt_stats.reserved[0]
 
-// Queue sharding. A slot belongs to shard (slot >> kShardGroupShift) % kShards for the whole frame, every queue is kShards
+// Queue sharding. A slot belongs to one shard for the whole frame — k_generate (kernels.hip) deals the groups of 2^kShardGroupShift slots
+// out in rotation: slot group g goes to shard (g % kShards + g / kShards) % kShards, as entry group g / kShards —, every queue is kShards
 // independent regions of `shard_cap` entries with one counter line each, and a workgroup works on exactly one shard
 // (kernels.hip block_pos: 1-D grids with the shard as the fastest index).
 // Why: a queue push is one returning atomic per wavefront; on ONE address that saturates at ~88 atomics/us
