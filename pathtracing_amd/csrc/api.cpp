@@ -4,6 +4,7 @@
 // HIP only: there is no CPU fallback anywhere in this library.
 #include "ptrt_internal.h"
 #include "bvh_build.h"
+#include "blob_rules.h"
 #include "refit.h"
 #include "denoise.h"
 #include "device_owner.h"
@@ -185,9 +186,9 @@ struct pt_scene {
     bool device_packed = false;          // the blob was packed on the device (lbvh.hip build_lbvh_blob4q_device): the host copies below
     mutable bool host_mirror = true;     // false: the host copies of the blob (packed_nodes or bvh.slots, and bvh.tris) are stale — packed on the
                                          // device, or refitted since — and pt_scene_bvh_read fetches them from the device first
-    bool quantised() const { return layout == PT_BVH_WIDTH_4Q || layout == PT_BVH_WIDTH_8Q || layout == PT_BVH_WIDTH_8O; }
+    bool quantised() const { return layout_quantised(layout); }
     const void *node_data() const { return quantised() ? (const void *)packed_nodes.data() : (const void *)bvh.slots.data(); }
-    uint64_t node_bytes() const { return device_packed ? (uint64_t)bvh.n_nodes * 64u : quantised() ? packed_nodes.size() : bvh.slots.size() * sizeof(BvhSlot); }
+    uint64_t node_bytes() const { return device_packed ? (uint64_t)bvh.n_nodes * layout_node_bytes(layout) : quantised() ? packed_nodes.size() : bvh.slots.size() * sizeof(BvhSlot); }
     uint64_t n_blob_tris() const { return device_packed ? tri_mat.size() : bvh.tris.size(); }
     uint32_t stack_overflow() const { return bvh.stack_need > kStackLds ? bvh.stack_need - kStackLds : 0u; } // traversal-stack entries per ray beyond those in LDS
     DevBuf<float4> d_nodes, d_tris, d_spheres, d_mats;
@@ -247,16 +248,6 @@ std::vector<uint2> sphere_mats(const uint32_t *mat, const float *cxyzr, size_t n
     std::vector<uint2> mi(n);
     for (size_t i = 0; i < n; ++i) { const float inv_r = 1.0f / cxyzr[i * 4 + 3]; mi[i].x = mat[i]; std::memcpy(&mi[i].y, &inv_r, 4); }
     return mi;
-}
-
-// n = normalize(cross(e1, e2)) in exactly the op order of docs/SPEC.md §0 (fma, IEEE sqrt and divide), so the bits equal what the kernel
-// would compute from e1, e2: a triangle record's shading row, a light's normal. Returns |cross(e1, e2)|^2.
-float shading_normal(const float *e1, const float *e2, float *n)
-{
-    const float cr[3] = { std::fmaf(e1[1], e2[2], -(e1[2] * e2[1])), std::fmaf(e1[2], e2[0], -(e1[0] * e2[2])), std::fmaf(e1[0], e2[1], -(e1[1] * e2[0])) };
-    const float dd = std::fmaf(cr[2], cr[2], std::fmaf(cr[1], cr[1], cr[0] * cr[0])), inv = 1.0f / std::sqrt(dd);
-    for (int k = 0; k < 3; ++k) n[k] = cr[k] * inv;
-    return dd;
 }
 
 // docs/SPEC.md §7: the light set, its f32 CDF and the per-light records from the current vertices of the candidates, uploaded to the
@@ -570,7 +561,7 @@ static pt_status build_tree(pt_scene *s, uint32_t bvh_width, bool lbvh, CommitCl
     s->blob_of_ready = false;
     const uint32_t nt = (uint32_t)s->tri_mat.size();
     const bool oct = bvh_width == PT_BVH_WIDTH_8O;
-    const uint32_t fan = bvh_width == PT_BVH_WIDTH_2 ? 2u : (bvh_width == PT_BVH_WIDTH_8Q || oct) ? 8u : 4u;
+    const uint32_t fan = layout_fan(bvh_width);
     s->device_packed = false; s->host_mirror = true;
     if (lbvh && nt >= 2 && bvh_width == PT_BVH_WIDTH_4Q) {
         // the default layout is also packed on the device: nodes and triangle records are born in device memory
@@ -579,7 +570,7 @@ static pt_status build_tree(pt_scene *s, uint32_t bvh_width, bool lbvh, CommitCl
         HIP_TRY(c, build_lbvh_blob4q_device(c->stream, s->verts.data(), s->tri_mat.data(), nt, db));
         s->d_nodes = std::move(db.nodes); s->d_tris = std::move(db.tris); // (the scene's earlier arrays are freed here)
         s->bvh = BvhBlob{};
-        s->bvh.width = 4; s->bvh.n_nodes = db.n_nodes; s->bvh.max_depth = db.max_depth; s->bvh.stack_need = db.stack_need;
+        s->bvh.width = fan; s->bvh.n_nodes = db.n_nodes; s->bvh.max_depth = db.max_depth; s->bvh.stack_need = db.stack_need;
         s->bvh.sah_cost = db.sah_cost; s->bvh.build_ms = db.device_ms;
         s->device_packed = true; s->host_mirror = false;
     } else if (lbvh && nt >= 2) {
@@ -592,8 +583,10 @@ static pt_status build_tree(pt_scene *s, uint32_t bvh_width, bool lbvh, CommitCl
     if (s->bvh.max_depth > 90) return fail(c, PT_ERR_INTERNAL, "BVH depth %u exceeds the supported 90", s->bvh.max_depth);
     s->layout = bvh_width;
     s->packed_nodes.clear();
-    if (bvh_width == PT_BVH_WIDTH_4Q && !s->device_packed) quantize_bvh4(s->bvh, s->packed_nodes);
-    if (bvh_width == PT_BVH_WIDTH_8Q || oct) quantize_bvh8(s->bvh, s->packed_nodes);
+    if (layout_quantised(bvh_width) && !s->device_packed) {
+        if (fan == 4) quantize_bvh4(s->bvh, s->packed_nodes);
+        else quantize_bvh8(s->bvh, s->packed_nodes);
+    }
     clock.lap("quantise");
     return PT_OK;
 }
@@ -613,13 +606,12 @@ static pt_status upload_tree(pt_scene *s, CommitClock &clock)
     HIP_TRY(c, s->d_tris.ensure(s->bvh.tris.size() * 4));
     // Device triangle record = one 64-byte line: the blob's three rows (docs/SPEC.md §4.1) + a shading row. A 48-byte
     // record straddles two cache lines 3 times out of 4 when k_extend fetches it; a padded one never does, and the
-    // row that pads it is the one k_shade wants next: ng (shading_normal) and the material id.
+    // row that pads it is the one k_shade wants next: ng and the material id (blob_rules.h shading_row; rows 0-2 are the blob's triangle).
     std::vector<float> rec(s->bvh.tris.size() * 16);
     for (size_t i = 0; i < s->bvh.tris.size(); ++i) {
         const BvhTri &t = s->bvh.tris[i];
         std::memcpy(&rec[i * 16], &t, sizeof(BvhTri));
-        shading_normal(t.e1, t.e2, &rec[i * 16 + 12]);
-        std::memcpy(&rec[i * 16 + 15], &t.mat, 4);
+        shading_row(t.e1, t.e2, t.mat, &rec[i * 16 + 12]);
     }
     clock.lap("triangle records");
     if (!rec.empty()) HIP_TRY(c, hipMemcpy(s->d_tris.p, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -728,7 +720,7 @@ pt_status pt_scene_bvh_read(const pt_scene *s, void *nodes, uint64_t node_bytes,
         HIP_TRY(c, hipSetDevice(c->device));
         const size_t nn = s->bvh.n_nodes;
         void *host_nodes = nullptr; size_t bytes = 0;
-        if (s->quantised()) { m->packed_nodes.resize(nn * (s->layout == PT_BVH_WIDTH_4Q ? 64 : 128)); host_nodes = m->packed_nodes.data(); bytes = m->packed_nodes.size(); }
+        if (s->quantised()) { m->packed_nodes.resize(nn * layout_node_bytes(s->layout)); host_nodes = m->packed_nodes.data(); bytes = m->packed_nodes.size(); }
         else { m->bvh.slots.resize(nn * s->bvh.width); host_nodes = m->bvh.slots.data(); bytes = m->bvh.slots.size() * sizeof(BvhSlot); }
         std::vector<float> rec(s->n_blob_tris() * 16);
         if (bytes) HIP_TRY(c, hipMemcpy(host_nodes, s->d_nodes.p, bytes, hipMemcpyDeviceToHost));
@@ -1188,8 +1180,8 @@ static pt_status prepare_refit(pt_scene *s)
     const uint32_t nn = s->bvh.n_nodes, fan = s->bvh.width, nbt = (uint32_t)s->n_blob_tris(), nt = (uint32_t)s->tri_mat.size();
     for (auto &e : R.ev) HIP_TRY(c, e.create());
     std::vector<int32_t> refs((size_t)nn * fan);
-    if (s->device_packed) { // BVH4Q nodes that never visited the host: their four refs (bytes 16-31 of every 64-byte node)
-        if (nn) HIP_TRY(c, hipMemcpy2D(refs.data(), 16, (const uint8_t *)s->d_nodes.p + 16, 64, 16, nn, hipMemcpyDeviceToHost));
+    if (s->device_packed) { // quantised nodes that never visited the host: the run of refs in every node
+        if (nn) HIP_TRY(c, hipMemcpy2D(refs.data(), 4 * fan, (const uint8_t *)s->d_nodes.p + layout_ref_at(s->layout, 0), layout_node_bytes(s->layout), 4 * fan, nn, hipMemcpyDeviceToHost));
     } else for (size_t k = 0; k < refs.size(); ++k) refs[k] = s->bvh.slots[k].ref; // the host blob the device nodes were packed from
     std::vector<uint32_t> list;
     if (!refit_levels(refs.data(), nn, fan, nbt, list, R.level_off)) return fail(c, PT_ERR_INTERNAL, "pt_scene_update_triangles: the committed tree's refs do not form a tree");

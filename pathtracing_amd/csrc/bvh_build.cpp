@@ -1,6 +1,8 @@
 // bvh_build.cpp — binned-SAH BVH2 build (16 bins/axis), optional SAH-area collapse to BVH4, breadth-first
-// node layout (top levels contiguous => stageable in LDS, one 128-B line per BVH4 node). docs/SPEC.md §4.1.
+// node layout (top levels contiguous => stageable in LDS, one 128-B line per BVH4 node). docs/SPEC.md §4.1. The blob's own rules — box,
+// padding, leaf refs, triangle rows, quantiser, SAH term — are blob_rules.h's, shared with lbvh.hip and refit.hip.
 #include "bvh_build.h"
+#include "blob_rules.h"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -20,36 +22,11 @@ namespace {
 #define PT_SAH_BINS 64
 #endif
 constexpr int kBins = PT_SAH_BINS;
-constexpr uint32_t kMaxLeaf = 4;
-constexpr int32_t kEmpty = 0x7fffffff;
 constexpr float kInf = std::numeric_limits<float>::infinity();
 
-struct Box {
-    float lo[3], hi[3];
-    void reset() { for (int k = 0; k < 3; ++k) { lo[k] = kInf; hi[k] = -kInf; } }
-    void grow(const Box &b) { for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], b.lo[k]); hi[k] = std::max(hi[k], b.hi[k]); } }
-    void grow(const float p[3]) { for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], p[k]); hi[k] = std::max(hi[k], p[k]); } }
-    float area() const
-    {
-        const float dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
-        return (dx < 0.f) ? 0.f : 2.f * (dx * dy + dy * dz + dz * dx);
-    }
-};
 struct Prim { Box box; float c[3]; };
 struct Tmp { Box box; int32_t left, right; uint32_t first, count; }; // count > 0: leaf over idx[first, first+count)
-
-inline float pad_of(float c) { return 1e-6f * std::max(1.0f, std::fabs(c)); }
-
-inline Box tri_box(const float *verts9, uint32_t id) // the padded leaf box of docs/SPEC.md §4.1
-{
-    const float *p = verts9 + (size_t)id * 9;
-    Box b;
-    for (int k = 0; k < 3; ++k) {
-        const float lo = std::min(p[k], std::min(p[3 + k], p[6 + k])), hi = std::max(p[k], std::max(p[3 + k], p[6 + k]));
-        b.lo[k] = lo - pad_of(lo); b.hi[k] = hi + pad_of(hi);
-    }
-    return b;
-}
+inline void grow_point(Box &b, const float p[3]) { for (int k = 0; k < 3; ++k) { b.lo[k] = std::min(b.lo[k], p[k]); b.hi[k] = std::max(b.hi[k], p[k]); } }
 
 struct Builder {
     const std::vector<Prim> &prims;
@@ -79,9 +56,8 @@ struct Builder {
             deferred.push_back(Deferred{ (int32_t)nodes.size() - 1, b, e, depth });
             return (int32_t)nodes.size() - 1;
         }
-        Box box, cb;
-        box.reset(); cb.reset();
-        for (uint32_t i = b; i < e; ++i) { box.grow(prims[idx[i]].box); cb.grow(prims[idx[i]].c); }
+        Box box = Box::empty(), cb = Box::empty();
+        for (uint32_t i = b; i < e; ++i) { box.grow(prims[idx[i]].box); grow_point(cb, prims[idx[i]].c); }
         if (n == 1) return make_leaf(b, e, box);
 
         uint32_t mid = 0;
@@ -92,7 +68,7 @@ struct Builder {
                 const float ext = cb.hi[ax] - cb.lo[ax];
                 if (!(ext > 0.f)) continue;
                 Box bb[kBins]; uint32_t cnt[kBins];
-                for (int k = 0; k < kBins; ++k) { bb[k].reset(); cnt[k] = 0; }
+                for (int k = 0; k < kBins; ++k) { bb[k] = Box::empty(); cnt[k] = 0; }
                 const float sc = (float)kBins / ext;
                 for (uint32_t i = b; i < e; ++i) {
                     const Prim &p = prims[idx[i]];
@@ -101,9 +77,9 @@ struct Builder {
                     bb[k].grow(p.box); cnt[k]++;
                 }
                 float ra[kBins]; uint32_t rc[kBins];
-                Box acc; acc.reset(); uint32_t c = 0;
+                Box acc = Box::empty(); uint32_t c = 0;
                 for (int k = kBins - 1; k >= 1; --k) { acc.grow(bb[k]); c += cnt[k]; ra[k] = acc.area(); rc[k] = c; }
-                acc.reset(); c = 0;
+                acc = Box::empty(); c = 0;
                 for (int k = 0; k < kBins - 1; ++k) {
                     acc.grow(bb[k]); c += cnt[k];
                     if (c == 0 || rc[k + 1] == 0) continue;
@@ -202,7 +178,7 @@ void emit_blob(const std::vector<Tmp> &tn, int32_t root, const std::vector<uint3
         return best;
     };
     for (int64_t n = (int64_t)tn.size() - 1; n >= 0; --n) { // children have larger indices than their parents
-        const float a = tn[n].box.area() / std::max(tn[root].box.area(), 1e-30f);
+        const float a = tn[n].box.area() / sah_root_area(tn[root].box);
         if (tn[n].count) { for (uint32_t i = 1; i <= width; ++i) C((int32_t)n, i) = a * c_tri * (float)tn[n].count; continue; }
         if (tn[n].left < 0 || tn[n].right < 0) continue; // (placeholder of the parallel build: never reachable)
         uint32_t k;
@@ -224,7 +200,7 @@ void emit_blob(const std::vector<Tmp> &tn, int32_t root, const std::vector<uint3
         gather(tn[t].left, k, p); gather(tn[t].right, width - k, p);
         if (octant_slots && width == 8) {
             float cen[8][3], mid[3];
-            Box all; all.reset();
+            Box all = Box::empty();
             for (int i = 0; i < p.nk; ++i) all.grow(tn[p.kids[i]].box);
             for (int a = 0; a < 3; ++a) mid[a] = 0.5f * (all.lo[a] + all.hi[a]);
             for (int i = 0; i < p.nk; ++i) for (int a = 0; a < 3; ++a) cen[i][a] = 0.5f * (tn[p.kids[i]].box.lo[a] + tn[p.kids[i]].box.hi[a]) - mid[a];
@@ -250,12 +226,12 @@ void emit_blob(const std::vector<Tmp> &tn, int32_t root, const std::vector<uint3
     pend.push_back(expand(root));
     out.tris.reserve(n_tris);
     out.slots.reserve(tn.size() * width);
-    const float root_area = std::max(tn[root].box.area(), 1e-30f);
+    const float root_area = sah_root_area(tn[root].box);
     double sah = 0.0;
     for (size_t i = 0; i < pend.size(); ++i) { // pend grows while we iterate: index i = output node i
         const Pending p = pend[i];
         BvhSlot s[8];
-        for (uint32_t c = 0; c < width; ++c) { std::memset(&s[c], 0, sizeof(BvhSlot)); s[c].ref = kEmpty; }
+        for (uint32_t c = 0; c < width; ++c) { std::memset(&s[c], 0, sizeof(BvhSlot)); s[c].ref = kEmptyRef; }
         for (int c = 0; c < p.nk; ++c) {
             if (p.kids[c] < 0) continue;
             const Tmp &k = tn[p.kids[c]];
@@ -264,19 +240,17 @@ void emit_blob(const std::vector<Tmp> &tn, int32_t root, const std::vector<uint3
                 const uint32_t first = (uint32_t)out.tris.size();
                 for (uint32_t j = 0; j < k.count; ++j) {
                     const uint32_t id = idx[k.first + j];
-                    const float *v = verts9 + (size_t)id * 9;
-                    BvhTri t; std::memset(&t, 0, sizeof t);
-                    for (int a = 0; a < 3; ++a) { t.v0[a] = v[a]; t.e1[a] = v[3 + a] - v[a]; t.e2[a] = v[6 + a] - v[a]; }
-                    t.id = id; t.mat = mats ? mats[id] : 0u;
+                    float rows[12]; // the record's rows 0-2 are the blob's triangle
+                    tri_rows(verts9 + (size_t)id * 9, id, mats ? mats[id] : 0u, rows);
+                    BvhTri t; std::memcpy(&t, rows, sizeof t);
                     out.tris.push_back(t);
                 }
-                s[c].ref = (int32_t)~((first << 3) | (k.count - 1u));
-                sah += (double)(k.box.area() / root_area) * k.count;
+                s[c].ref = leaf_ref(first, k.count);
             } else {
                 s[c].ref = (int32_t)pend.size();
                 pend.push_back(expand(p.kids[c]));
-                sah += (double)(k.box.area() / root_area);
             }
+            sah += sah_child_term(k.box.area(), root_area, s[c].ref);
         }
         for (uint32_t c = 0; c < width; ++c) out.slots.push_back(s[c]);
     }
@@ -289,7 +263,7 @@ void emit_blob(const std::vector<Tmp> &tn, int32_t root, const std::vector<uint3
         uint32_t k = 0, dmax = 1, nmax = 0;
         for (uint32_t c = 0; c < width; ++c) {
             const int32_t r = out.slots[(size_t)i * width + c].ref;
-            if (r == kEmpty) continue;
+            if (r == kEmptyRef) continue;
             ++k;
             if (r >= 0) { dmax = std::max(dmax, depth[r]); nmax = std::max(nmax, need[r]); }
         }
@@ -312,14 +286,7 @@ void build_bvh(const float *verts9, const uint32_t *mats, uint32_t n_tris, uint3
     std::vector<Prim> prims(n_tris);
     std::vector<uint32_t> idx(n_tris);
     for (uint32_t i = 0; i < n_tris; ++i) {
-        const float *p = verts9 + (size_t)i * 9;
-        Prim &pr = prims[i];
-        for (int k = 0; k < 3; ++k) {
-            const float lo = std::min(p[k], std::min(p[3 + k], p[6 + k])), hi = std::max(p[k], std::max(p[3 + k], p[6 + k]));
-            pr.box.lo[k] = lo - pad_of(lo);
-            pr.box.hi[k] = hi + pad_of(hi);
-            pr.c[k] = 0.5f * (lo + hi);
-        }
+        prims[i].box = tri_box(verts9 + (size_t)i * 9, prims[i].c);
         idx[i] = i;
     }
     Builder B(prims, idx);
@@ -334,21 +301,14 @@ void build_bvh(const float *verts9, const uint32_t *mats, uint32_t n_tris, uint3
 //            their worst there (1M-triangle Cornell: 9.15 -> 7.9 node visits per ray).
 //   bottom : inside a cluster the device's topology and boxes are kept; subtrees of at most kMaxLeaf triangles become leaves unless
 //            splitting them lowers the SAH cost — the leaf rule of Builder::build (their triangles are contiguous in Morton order).
-#ifndef PT_LBVH_CLUSTER
-#define PT_LBVH_CLUSTER 32
-#endif
-constexpr uint32_t kClusterTris = PT_LBVH_CLUSTER; // 0: no SAH storey, the LBVH as it is
 void build_bvh_from_binary(const BinaryBvh &bt, const float *verts9, const uint32_t *mats, uint32_t n_tris, uint32_t width, BvhBlob &out, bool octant_slots)
 {
     const auto t0 = std::chrono::steady_clock::now();
     out = BvhBlob{};
     out.width = width;
     if (n_tris < 2 || bt.order.size() != n_tris) return;
-    auto node_box = [&](int32_t c) {
-        Box b;
-        if (c >= 0) for (int k = 0; k < 3; ++k) { b.lo[k] = bt.box[(size_t)c * 6 + k]; b.hi[k] = bt.box[(size_t)c * 6 + 3 + k]; }
-        else b = tri_box(verts9, bt.order[(uint32_t)~c]); // single-triangle leaf: its padded box, exactly as the device made it
-        return b;
+    auto node_box = [&](int32_t c) { // (a single-triangle leaf: its padded box, exactly as the device made it)
+        return c >= 0 ? Box::of(&bt.box[(size_t)c * 6]) : tri_box(verts9 + (size_t)bt.order[(uint32_t)~c] * 9);
     };
     auto node_count = [&](int32_t c) { return c >= 0 ? bt.last[c] - bt.first[c] + 1 : 1u; };
 
@@ -415,7 +375,7 @@ void build_sah_over_boxes(const float *boxes6, uint32_t n, std::vector<int32_t> 
     std::vector<Prim> prims(n);
     std::vector<uint32_t> idx(n);
     for (uint32_t i = 0; i < n; ++i) {
-        for (int k = 0; k < 3; ++k) { prims[i].box.lo[k] = boxes6[(size_t)i * 6 + k]; prims[i].box.hi[k] = boxes6[(size_t)i * 6 + 3 + k]; }
+        prims[i].box = Box::of(boxes6 + (size_t)i * 6);
         for (int k = 0; k < 3; ++k) prims[i].c[k] = 0.5f * (prims[i].box.lo[k] + prims[i].box.hi[k]);
         idx[i] = i;
     }
@@ -437,59 +397,22 @@ void build_sah_over_boxes(const float *boxes6, uint32_t n, std::vector<int32_t> 
     root = ref(r);
 }
 
-// ---- BVH4Q: 64-byte nodes, child boxes quantised to 8 bits per coordinate on a per-node power-of-two grid
-// (docs/SPEC.md §4.1). decode(q) = fma((float)q, scale, origin) must enclose the float box it replaces; the
-// quantiser checks that with the very expression the traversal uses and nudges q outward when rounding bites.
-namespace {
-inline float scale_of(uint8_t e) { uint32_t b = (uint32_t)e << 23; float f; std::memcpy(&f, &b, 4); return f; }
-} // namespace
-
-// N = 4: 64-byte nodes (layout 68); N = 8: 128-byte nodes (layout 72), same scheme with 8-byte coordinate groups
+// ---- BVH4Q / BVH8Q: a width-4 / width-8 blob repacked into 64- / 128-byte nodes (layouts 68 / 72, 73), child boxes quantised to 8
+// bits per coordinate by blob_rules.h quantize_node, the text the GPU builder and the refit run on the device
 template <int N>
 static void quantize_nodes(const BvhBlob &in, std::vector<uint8_t> &out)
 {
-    constexpr size_t kStride = N == 4 ? 64 : 128, kQ = 16 + 4 * N; // quantised coordinates start after origin|exps and the refs
+    constexpr size_t kStride = N == 4 ? 64 : 128;
     out.assign((size_t)in.n_nodes * kStride, 0);
     auto range = [&](uint32_t i0, uint32_t i1) { // nodes are independent of one another
-    for (uint32_t i = i0; i < i1; ++i) {
-        const BvhSlot *s = &in.slots[(size_t)i * N];
-        uint8_t *nd = &out[(size_t)i * kStride];
-        float org[3]; uint8_t ex[3];
-        uint8_t qlo[3][N] = {}, qhi[3][N] = {};
-        for (int k = 0; k < 3; ++k) {
-            float lo = kInf, hi = -kInf;
-            for (int c = 0; c < N; ++c) if (s[c].ref != kEmpty) { lo = std::min(lo, s[c].lo[k]); hi = std::max(hi, s[c].hi[k]); }
-            if (!(lo <= hi)) { lo = hi = 0.f; } // node without children (cannot happen for a built tree)
-            org[k] = lo;
-            int e = 1;
-            { // smallest power of two with 255*scale >= extent
-                const float ext = hi - lo;
-                int ee; const float m = std::frexp(ext / 255.0f, &ee); // ext/255 = m * 2^ee, m in [0.5,1)
-                e = (ext > 0.f) ? ee + 127 - (m == 0.5f ? 1 : 0) : 1;
-                e = std::min(std::max(e, 1), 254);
-            }
-            for (;;) { // quantise; widen the grid if a coordinate does not fit in 8 bits
-                const float sc = scale_of((uint8_t)e);
-                bool ok = true;
-                for (int c = 0; c < N && ok; ++c) {
-                    if (s[c].ref == kEmpty) continue;
-                    int ql = (int)std::floor((s[c].lo[k] - lo) / sc), qh = (int)std::ceil((s[c].hi[k] - lo) / sc);
-                    ql = std::min(std::max(ql, 0), 255); qh = std::min(std::max(qh, 0), 255);
-                    while (ql > 0 && !(std::fmaf((float)ql, sc, lo) <= s[c].lo[k])) --ql;
-                    while (qh < 255 && !(std::fmaf((float)qh, sc, lo) >= s[c].hi[k])) ++qh;
-                    if (!(std::fmaf((float)ql, sc, lo) <= s[c].lo[k]) || !(std::fmaf((float)qh, sc, lo) >= s[c].hi[k])) { ok = false; break; }
-                    qlo[k][c] = (uint8_t)ql; qhi[k][c] = (uint8_t)qh;
-                }
-                if (ok || e >= 254) break;
-                ++e;
-            }
-            ex[k] = (uint8_t)e;
+        for (uint32_t i = i0; i < i1; ++i) {
+            const BvhSlot *s = &in.slots[(size_t)i * N];
+            bool used[N];
+            uint32_t w[kStride / 4] = {};
+            for (int c = 0; c < N; ++c) { used[c] = s[c].ref != kEmptyRef; w[4 + c] = (uint32_t)s[c].ref; }
+            quantize_node<N>(s, used, w);
+            std::memcpy(&out[(size_t)i * kStride], w, kStride);
         }
-        std::memcpy(nd + 0, org, 12);
-        nd[12] = ex[0]; nd[13] = ex[1]; nd[14] = ex[2]; nd[15] = 0;
-        for (int c = 0; c < N; ++c) std::memcpy(nd + 16 + 4 * c, &s[c].ref, 4);
-        for (int k = 0; k < 3; ++k) { std::memcpy(nd + kQ + N * k, qlo[k], N); std::memcpy(nd + kQ + N * (3 + k), qhi[k], N); }
-    }
     };
     const uint32_t nt = in.n_nodes < (1u << 15) ? 1u : std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
     if (nt == 1) { range(0, in.n_nodes); return; }

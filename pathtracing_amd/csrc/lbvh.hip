@@ -15,29 +15,27 @@
 #include <chrono>
 #include <vector>
 #include "bvh_build.h"
-#include "quantize_node.h"
+#include "blob_rules.h"
 
 namespace ptrt {
 namespace {
 
 __device__ __forceinline__ uint32_t f_ord(float f) { const uint32_t b = __float_as_uint(f); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
 inline float f_unord(uint32_t u) { const uint32_t b = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u; float f; std::memcpy(&f, &b, 4); return f; }
-__device__ __forceinline__ float pad_of(float c) { return 1e-6f * fmaxf(1.0f, fabsf(c)); }
 
 __global__ void __launch_bounds__(256) k_tri_boxes(const float *__restrict__ verts, uint32_t n, float *__restrict__ leaf_box,
                                                    float *__restrict__ cent, uint32_t *__restrict__ bounds /* 3 min, 3 max (ordered uints) */)
 {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float *p = verts + (size_t)i * 9;
+    float c[3];
+    const Box b = tri_box(verts + (size_t)i * 9, c);
     for (int k = 0; k < 3; ++k) {
-        const float lo = fminf(p[k], fminf(p[3 + k], p[6 + k])), hi = fmaxf(p[k], fmaxf(p[3 + k], p[6 + k]));
-        leaf_box[(size_t)i * 6 + k] = lo - pad_of(lo);
-        leaf_box[(size_t)i * 6 + 3 + k] = hi + pad_of(hi);
-        const float c = 0.5f * (lo + hi);
-        cent[(size_t)i * 3 + k] = c;
-        atomicMin(&bounds[k], f_ord(c));
-        atomicMax(&bounds[3 + k], f_ord(c));
+        leaf_box[(size_t)i * 6 + k] = b.lo[k];
+        leaf_box[(size_t)i * 6 + 3 + k] = b.hi[k];
+        cent[(size_t)i * 3 + k] = c[k];
+        atomicMin(&bounds[k], f_ord(c[k]));
+        atomicMax(&bounds[3 + k], f_ord(c[k]));
     }
 }
 
@@ -174,31 +172,21 @@ struct Lbvh {
 // same two-storey scheme for the other node layouts). Then, level by level: expand every node of the level to <= 4 children by
 // opening the child of largest area (as emit_blob does), scan the inner children to number the next level breadth-first,
 // quantise and write the node. Triangles are emitted in Morton order, so every leaf's range [first, last] is contiguous as it is.
+using Lay = Layout<PT_BVH_WIDTH_4Q>;     // the one layout packed here
 constexpr int32_t kTopBase = 0x40000000;  // binary refs: >= kTopBase top-storey node, 0 .. n-2 LBVH node, < 0 LBVH leaf ~j
-constexpr int32_t kNoKid = 0x7fffffff;
-constexpr uint32_t kLeafTris = 4;         // kMaxLeaf of bvh_build.cpp
 
 struct TreeView {
     const int32_t *left, *right; const uint32_t *first, *last, *order; const float *node_box, *leaf_box; const uint8_t *leaf_flag;
     const int32_t *top_left, *top_right; const float *top_box;
 };
-struct BoxF { float lo[3], hi[3]; };
-__device__ __forceinline__ BoxF box_of(const TreeView &t, int32_t r)
+__device__ __forceinline__ Box box_of(const TreeView &t, int32_t r)
 {
-    const float *p = r >= kTopBase ? t.top_box + (size_t)(r - kTopBase) * 6 : r >= 0 ? t.node_box + (size_t)r * 6 : t.leaf_box + (size_t)t.order[~r] * 6;
-    BoxF b;
-    for (int k = 0; k < 3; ++k) { b.lo[k] = p[k]; b.hi[k] = p[3 + k]; }
-    return b;
-}
-__device__ __forceinline__ float area_of(const BoxF &b)
-{
-    const float dx = b.hi[0] - b.lo[0], dy = b.hi[1] - b.lo[1], dz = b.hi[2] - b.lo[2];
-    return dx < 0.f ? 0.f : 2.f * (dx * dy + dy * dz + dz * dx);
+    return Box::of(r >= kTopBase ? t.top_box + (size_t)(r - kTopBase) * 6 : r >= 0 ? t.node_box + (size_t)r * 6 : t.leaf_box + (size_t)t.order[~r] * 6);
 }
 __device__ __forceinline__ uint32_t count_of(const TreeView &t, int32_t r) { return r < 0 ? 1u : t.last[r] - t.first[r] + 1u; } // LBVH refs only
 __device__ __forceinline__ bool blob_leaf(const TreeView &t, int32_t r) { return r < 0 || (r < kTopBase && t.leaf_flag[r]); }
 
-// per LBVH node: does it become a leaf of the blob (<= kLeafTris triangles and splitting does not lower the SAH cost)? and is it a cluster root?
+// per LBVH node: does it become a leaf of the blob (<= kMaxLeaf triangles and splitting does not lower the SAH cost)? and is it a cluster root?
 __global__ void __launch_bounds__(256) k_mark(TreeView t, uint32_t n, uint32_t cluster_tris, const int32_t *__restrict__ parent_node,
                                               const int32_t *__restrict__ parent_leaf, uint8_t *__restrict__ leaf_flag, int32_t *__restrict__ clusters,
                                               uint32_t *__restrict__ n_clusters)
@@ -207,11 +195,11 @@ __global__ void __launch_bounds__(256) k_mark(TreeView t, uint32_t n, uint32_t c
     if (i < n - 1) {
         const uint32_t cnt = t.last[i] - t.first[i] + 1u;
         bool leaf = false;
-        if (cnt <= kLeafTris) {
+        if (cnt <= kMaxLeaf) {
             float split = 0.f;
             const int32_t c[2] = { t.left[i], t.right[i] };
-            for (int s = 0; s < 2; ++s) split += area_of(box_of(t, c[s])) * (float)count_of(t, c[s]);
-            leaf = !(split < area_of(box_of(t, (int32_t)i)) * (float)cnt);
+            for (int s = 0; s < 2; ++s) split += box_of(t, c[s]).area() * (float)count_of(t, c[s]);
+            leaf = !(split < box_of(t, (int32_t)i).area() * (float)cnt);
         }
         leaf_flag[i] = leaf ? 1 : 0;
         const int32_t p = parent_node[i];
@@ -228,7 +216,7 @@ __global__ void __launch_bounds__(256) k_cluster_info(TreeView t, const int32_t 
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= nc) return;
     const int32_t r = clusters[i];
-    const BoxF b = box_of(t, r);
+    const Box b = box_of(t, r);
     for (int k = 0; k < 3; ++k) { boxes[(size_t)i * 6 + k] = b.lo[k]; boxes[(size_t)i * 6 + 3 + k] = b.hi[k]; }
     firsts[i] = r < 0 ? (uint32_t)~r : t.first[r];
 }
@@ -240,7 +228,7 @@ __global__ void __launch_bounds__(256) k_expand(TreeView t, const int32_t *__res
     const uint32_t q = blockIdx.x * 256 + threadIdx.x;
     if (q >= n_cur) return;
     const int32_t r = queue[q];
-    int32_t kid[4] = { kNoKid, kNoKid, kNoKid, kNoKid };
+    int32_t kid[4] = { kEmptyRef, kEmptyRef, kEmptyRef, kEmptyRef };
     int nk = 0;
     if (blob_leaf(t, r)) kid[nk++] = r; // (the whole scene is one leaf) single child
     else {
@@ -250,7 +238,7 @@ __global__ void __launch_bounds__(256) k_expand(TreeView t, const int32_t *__res
         while (nk < 4) {
             int best = -1; float ba = -1.f;
             for (int i = 0; i < nk; ++i)
-                if (!blob_leaf(t, kid[i])) { const float a = area_of(box_of(t, kid[i])); if (a > ba) { ba = a; best = i; } }
+                if (!blob_leaf(t, kid[i])) { const float a = box_of(t, kid[i]).area(); if (a > ba) { ba = a; best = i; } }
             if (best < 0) break;
             const int32_t c = kid[best];
             for (int i = nk; i > best + 1; --i) kid[i] = kid[i - 1];
@@ -262,7 +250,7 @@ __global__ void __launch_bounds__(256) k_expand(TreeView t, const int32_t *__res
     uint32_t ni = 0;
     for (int i = 0; i < 4; ++i) {
         kids[(size_t)(base + q) * 4 + i] = kid[i];
-        if (kid[i] != kNoKid && !blob_leaf(t, kid[i])) ++ni;
+        if (kid[i] != kEmptyRef && !blob_leaf(t, kid[i])) ++ni;
     }
     inner_count[q] = ni;
 }
@@ -275,29 +263,29 @@ __global__ void __launch_bounds__(256) k_finalize(TreeView t, uint32_t n_cur, ui
     if (q >= n_cur) return;
     const uint32_t node = base + q;
     int32_t ref[4];
-    BoxF box[4];
+    Box box[4];
     uint32_t rank = 0;
     float my_cost = 0.f;
     for (int c = 0; c < 4; ++c) {
         const int32_t k = kids[(size_t)node * 4 + c];
-        if (k == kNoKid) { ref[c] = kNoKid; continue; }
+        if (k == kEmptyRef) { ref[c] = kEmptyRef; continue; }
         box[c] = box_of(t, k);
         if (blob_leaf(t, k)) {
             const uint32_t first = k < 0 ? (uint32_t)~k : t.first[k], cnt = count_of(t, k);
-            ref[c] = (int32_t)~((first << 3) | (cnt - 1u));
-            my_cost += area_of(box[c]) * inv_root_area * (float)cnt;
+            ref[c] = leaf_ref(first, cnt);
+            my_cost += box[c].area() * inv_root_area * (float)cnt;
         } else {
             const uint32_t pos = offs[q] + rank++;
             queue_next[pos] = k;
             ref[c] = (int32_t)(base + n_cur + pos);
-            my_cost += area_of(box[c]) * inv_root_area;
+            my_cost += box[c].area() * inv_root_area;
         }
     }
     cost[node] = my_cost;
-    // ---- docs/SPEC.md §4.1 BVH4Q: quantise the children's boxes (quantize_node.h, shared with refit.hip), then the refs
+    // ---- docs/SPEC.md §4.1 BVH4Q: quantise the children's boxes (blob_rules.h, shared with the host builder and refit.hip), then the refs
     bool used[4];
-    for (int c = 0; c < 4; ++c) used[c] = ref[c] != kNoKid;
-    uint32_t *w = reinterpret_cast<uint32_t *>(nodes + (size_t)node * 64);
+    for (int c = 0; c < 4; ++c) used[c] = ref[c] != kEmptyRef;
+    uint32_t *w = reinterpret_cast<uint32_t *>(nodes + (size_t)node * Lay::kStride);
     quantize_node<4>(box, used, w);
     for (int c = 0; c < 4; ++c) w[4 + c] = (uint32_t)ref[c];
 }
@@ -307,11 +295,10 @@ __global__ void __launch_bounds__(256) k_depth(const uint8_t *__restrict__ nodes
 {
     const uint32_t q = blockIdx.x * 256 + threadIdx.x;
     if (q >= n_cur) return;
-    const int32_t *ref = reinterpret_cast<const int32_t *>(nodes + (size_t)(base + q) * 64 + 16);
     uint32_t k = 0, dmax = 1, nmax = 0;
-    for (int c = 0; c < 4; ++c) {
-        const int32_t r = ref[c];
-        if (r == kNoKid) continue;
+    for (int c = 0; c < Lay::N; ++c) {
+        const int32_t r = Lay::ref(nodes + (size_t)(base + q) * Lay::kStride, c);
+        if (r == kEmptyRef) continue;
         ++k;
         if (r >= 0) { dmax = max(dmax, depth[r]); nmax = max(nmax, need[r]); }
     }
@@ -319,30 +306,19 @@ __global__ void __launch_bounds__(256) k_depth(const uint8_t *__restrict__ nodes
     need[base + q] = (k ? k - 1 : 0) + nmax;
 }
 
-// the device triangle record (one 64-byte line, Morton order): the blob's three rows + the shading row normalize(cross(e1, e2)) | material
-// in the op order of docs/SPEC.md §0 (api.cpp builds the same record on the host for the host-built trees)
+// the device triangle record (one 64-byte line, Morton order): blob_rules.h tri_record, as api.cpp makes it for the host-built trees
 __global__ void __launch_bounds__(256) k_tri_records(const float *__restrict__ verts, const uint32_t *__restrict__ mats, const uint32_t *__restrict__ order, uint32_t n,
                                                      float4 *__restrict__ rec)
 {
     const uint32_t j = blockIdx.x * 256 + threadIdx.x;
     if (j >= n) return;
     const uint32_t id = order[j];
-    const float *v = verts + (size_t)id * 9;
-    const float a[3] = { v[3] - v[0], v[4] - v[1], v[5] - v[2] }, b[3] = { v[6] - v[0], v[7] - v[1], v[8] - v[2] };
-    const uint32_t m = mats ? mats[id] : 0u;
-    const float cx = __builtin_fmaf(a[1], b[2], -(a[2] * b[1])), cy = __builtin_fmaf(a[2], b[0], -(a[0] * b[2])), cz = __builtin_fmaf(a[0], b[1], -(a[1] * b[0]));
-    const float inv = 1.0f / __builtin_sqrtf(__builtin_fmaf(cz, cz, __builtin_fmaf(cy, cy, cx * cx)));
-    rec[(size_t)j * 4 + 0] = make_float4(v[0], v[1], v[2], __uint_as_float(id));
-    rec[(size_t)j * 4 + 1] = make_float4(a[0], a[1], a[2], __uint_as_float(m));
-    rec[(size_t)j * 4 + 2] = make_float4(b[0], b[1], b[2], 0.f);
-    rec[(size_t)j * 4 + 3] = make_float4(cx * inv, cy * inv, cz * inv, __uint_as_float(m));
+    float r[16];
+    tri_record(verts + (size_t)id * 9, id, mats ? mats[id] : 0u, r);
+    for (int k = 0; k < 4; ++k) rec[(size_t)j * 4 + k] = make_float4(r[4 * k], r[4 * k + 1], r[4 * k + 2], r[4 * k + 3]);
 }
 
 } // namespace
-
-#ifndef PT_LBVH_CLUSTER
-#define PT_LBVH_CLUSTER 32
-#endif
 
 hipError_t build_lbvh_device(hipStream_t stream, const float *verts9, uint32_t n, BinaryBvh &out)
 {
@@ -380,7 +356,7 @@ hipError_t build_lbvh_blob4q_device(hipStream_t stream, const float *verts9, con
     LB_TRY(hipMemsetAsync(n_clusters.p, 0, 4, stream));
     if (mats) { LB_TRY(d_mats.ensure(n)); LB_TRY(hipMemcpyAsync(d_mats.p, mats, (size_t)n * 4, hipMemcpyHostToDevice, stream)); }
     TreeView tv{ t.left.p, t.right.p, t.first.p, t.last.p, t.order.p, t.node_box.p, t.leaf_box.p, leaf_flag.p, nullptr, nullptr, nullptr };
-    hipLaunchKernelGGL(k_mark, blocks(n), block, 0, stream, tv, n, (uint32_t)PT_LBVH_CLUSTER, t.pn.p, t.pl.p, leaf_flag.p, clusters.p, n_clusters.p);
+    hipLaunchKernelGGL(k_mark, blocks(n), block, 0, stream, tv, n, kClusterTris, t.pn.p, t.pl.p, leaf_flag.p, clusters.p, n_clusters.p);
     uint32_t nc = 0;
     LB_TRY(hipMemcpyAsync(&nc, n_clusters.p, 4, hipMemcpyDeviceToHost, stream));
     LB_TRY(hipStreamSynchronize(stream));
@@ -411,8 +387,7 @@ hipError_t build_lbvh_blob4q_device(hipStream_t stream, const float *verts9, con
     for (auto &c : top_right) c = to_ref(c);
     const int32_t root_ref = to_ref(top_root);
     const float *rb = top_root < 0 ? &sorted_box[(size_t)(uint32_t)~top_root * 6] : &top_box[(size_t)top_root * 6];
-    const float rdx = rb[3] - rb[0], rdy = rb[4] - rb[1], rdz = rb[5] - rb[2];
-    const float root_area = std::max(2.f * (rdx * rdy + rdy * rdz + rdz * rdx), 1e-30f);
+    const float root_area = sah_root_area(Box::of(rb));
     DevBuf<int32_t> d_tl, d_tr; DevBuf<float> d_tb;
     const size_t nt_top = top_left.size();
     LB_TRY(d_tl.ensure(nt_top)); LB_TRY(d_tr.ensure(nt_top)); LB_TRY(d_tb.ensure(nt_top * 6));
