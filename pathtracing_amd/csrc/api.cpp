@@ -1,13 +1,9 @@
-// api.cpp — C ABI of libptrt.so (include/ptrt.h): context, scene, wavefront frame loop.
+// api.cpp — C ABI of libptrt.so (include/ptrt.h): context, wavefront frame loop, ray queries, denoising, read-backs (scenes: scene.cpp).
 // Stands where Renderer.CreateResources / CreateComputePipeline / ComputeFrame + the compute-fence wait stand in
 // the reference (RayTracing/Graphics/Renderer.cs:105-196, 293-403, 1006-1040, 970-972).
 // HIP only: there is no CPU fallback anywhere in this library.
-#include "ptrt_internal.h"
-#include "bvh_build.h"
-#include "blob_rules.h"
-#include "refit.h"
+#include "scene.h"
 #include "denoise.h"
-#include "device_owner.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
@@ -47,11 +43,6 @@ uint32_t host_pcg(uint32_t x)
 // a box) lose ~35 %, and no static property of the tree tells them apart. Counting / profiling frames neither probe nor feed
 // the decision: their kernels are instrumented builds. A probing frame runs one loop and no finish mode, so that its timed iterations compare.
 uint32_t faster(double rate_simple, double rate_packed) { return rate_packed > 1.10 * rate_simple ? EXT_PACKED : EXT_SIMPLE; }
-struct ExtendChoice {           // what a scene remembers
-    uint32_t kernel = 0;        // the ExtendKernel an earlier frame picked (0 = none yet)
-    double rate_simple = 0.0, rate_packed = 0.0; // rays per ms of whole frames run on one kernel (frames too short to probe inside)
-    uint32_t misses = 0;        // warm frames too small to time: after three the scene settles on the one-ray-per-lane kernel for good
-};
 struct ExtendFrame {            // the choice during one frame
     ExtendChoice &mem;
     bool undecided;             // nothing forces a kernel and the scene has not picked one: this frame measures (whole, on frame_kernel)
@@ -172,126 +163,7 @@ struct pt_context {
     Event ev_denoise[3];             // start, guides done, filter done (made by the first pt_denoise)
 };
 
-struct pt_scene {
-    pt_context *ctx = nullptr;
-    std::vector<float> verts; std::vector<uint32_t> tri_mat;
-    std::vector<float> spheres; std::vector<uint32_t> sph_mat;
-    std::vector<pt_material> mats;
-    pt_camera cam{};
-    float sky[3] = { 0.f, 0.f, 0.f };
-    bool have_cam = false, committed = false;
-    mutable BvhBlob bvh;                 // (mutable: pt_scene_bvh_read fills the host copy of a device-packed blob on first use)
-    uint32_t layout = 0;                 // PT_BVH_WIDTH_* the scene was committed with
-    mutable std::vector<uint8_t> packed_nodes; // layouts PT_BVH_WIDTH_4Q / _8Q: the 64- / 128-byte nodes that are uploaded / read back
-    bool device_packed = false;          // the blob was packed on the device (lbvh.hip build_lbvh_blob4q_device): the host copies below
-    mutable bool host_mirror = true;     // false: the host copies of the blob (packed_nodes or bvh.slots, and bvh.tris) are stale — packed on the
-                                         // device, or refitted since — and pt_scene_bvh_read fetches them from the device first
-    bool quantised() const { return layout_quantised(layout); }
-    const void *node_data() const { return quantised() ? (const void *)packed_nodes.data() : (const void *)bvh.slots.data(); }
-    uint64_t node_bytes() const { return device_packed ? (uint64_t)bvh.n_nodes * layout_node_bytes(layout) : quantised() ? packed_nodes.size() : bvh.slots.size() * sizeof(BvhSlot); }
-    uint64_t n_blob_tris() const { return device_packed ? tri_mat.size() : bvh.tris.size(); }
-    uint32_t stack_overflow() const { return bvh.stack_need > kStackLds ? bvh.stack_need - kStackLds : 0u; } // traversal-stack entries per ray beyond those in LDS
-    DevBuf<float4> d_nodes, d_tris, d_spheres, d_mats;
-    bool has_specular = false;
-    mutable ExtendChoice ext;            // cache, not scene content: what earlier frames measured
-    DevBuf<uint2> d_sph_mat;
-    DeviceScene ds{};
-    // pt_scene_update_triangles (refit.hip, docs/SPEC.md §4.3): scratch made by the first update after a commit, kept until the next one
-    struct Refit {
-        bool ready = false;                  // level lists built for the committed tree
-        std::vector<uint32_t> level_off;     // level l (deepest first) = list[level_off[l] .. level_off[l + 1])
-        DevBuf<uint32_t> list, flag;
-        DevBuf<float> tbox, nbox, carea;     // per blob triangle / per node / per child slot
-        DevBuf<float> verts[2];              // verts[cur]: the scene's current vertices once an update has run; the other one takes the next
-        DevBuf<double> sah;                  // per-block partial sums, then the total
-        uint32_t cur = 0;
-        Event ev[4];
-    } refit;
-    bool verts_on_device = false;        // `verts` is stale: the current vertices are refit.verts[refit.cur] (fetched when a commit needs them)
-    // The light table of next-event estimation (docs/SPEC.md §7, build_lights): made at every commit and every triangle update from the
-    // candidates — the triangles whose material emits, in triangle order — of which those with area * (e.r + e.g + e.b) > 0 are lights.
-    std::vector<uint32_t> light_cand;    // original ids of the candidates
-    std::vector<uint32_t> cand_blob;     // the blob index of each candidate (where its pa goes in d_pa)
-    std::vector<float> pa_span;          // host image of d_pa[cand_lo .. cand_hi], the only entries that can be non-zero
-    uint32_t cand_lo = 0, n_lights = 0;
-    DevBuf<float4> d_lights;
-    DevBuf<float> d_cdf, d_pa;
-    // pt_denoise: original triangle id -> blob index (where a guide finds its hit's shading row), made by the first denoise after a
-    // commit; updates keep it (they keep every record's id and place)
-    mutable DevBuf<uint32_t> d_blob_of;
-    mutable bool blob_of_ready = false;
-};
-
 namespace {
-
-pt_status fail(pt_context *ctx, pt_status code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-    g_err = buf;
-    if (ctx) ctx->err = buf;
-    return code;
-}
-#define HIP_TRY(ctx, expr)                                                                          \
-    do { hipError_t _e = (expr);                                                                    \
-         if (_e != hipSuccess)                                                                      \
-             return fail(ctx, _e == hipErrorOutOfMemory ? PT_ERR_OUT_OF_MEMORY : PT_ERR_HIP,        \
-                         "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
-
-bool finite3(const float *p) { return std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]); }
-bool sphere_ok(const float *cxyzr) { return finite3(cxyzr) && cxyzr[3] > 0.f && std::isfinite(cxyzr[3]); } // finite centre, finite radius > 0
-
-// The device's {material id, bits of 1.0f / r} per sphere (IEEE single division: the value docs/SPEC.md §5 has the shading step compute)
-std::vector<uint2> sphere_mats(const uint32_t *mat, const float *cxyzr, size_t n)
-{
-    std::vector<uint2> mi(n);
-    for (size_t i = 0; i < n; ++i) { const float inv_r = 1.0f / cxyzr[i * 4 + 3]; mi[i].x = mat[i]; std::memcpy(&mi[i].y, &inv_r, 4); }
-    return mi;
-}
-
-// docs/SPEC.md §7: the light set, its f32 CDF and the per-light records from the current vertices of the candidates, uploaded to the
-// scene's device arrays. `verts` holds the triangles from `first` on (9 floats each, in triangle order). Area, normal and pa in the op
-// order of §0 / §7; the weights in double.
-pt_status build_lights(pt_context *c, pt_scene *s, const float *verts, uint32_t first)
-{
-    std::vector<float> rec, cdf; // 16 floats per light: v0|pa, e1|Le.r, e2|Le.g, n_l|Le.b
-    std::vector<double> w;       // area * (e.r + e.g + e.b) per light
-    std::vector<uint32_t> cand;  // which candidate each light is
-    double total = 0.0;
-    for (size_t k = 0; k < s->light_cand.size(); ++k) {
-        const float *v = verts + (size_t)(s->light_cand[k] - first) * 9;
-        const float e1[3] = { v[3] - v[0], v[4] - v[1], v[5] - v[2] }, e2[3] = { v[6] - v[0], v[7] - v[1], v[8] - v[2] };
-        float nl[3]; // n_l: the bits of the shading row
-        const float area = 0.5f * std::sqrt(shading_normal(e1, e2, nl));
-        const float *e = s->mats[s->tri_mat[s->light_cand[k]]].emission;
-        const double wk = (double)area * ((double)e[0] + (double)e[1] + (double)e[2]);
-        if (!(area > 0.f) || !(wk > 0.0)) continue;
-        total += wk; w.push_back(wk); cand.push_back((uint32_t)k);
-        const float r[16] = { v[0], v[1], v[2], area, e1[0], e1[1], e1[2], e[0], e2[0], e2[1], e2[2], e[1], nl[0], nl[1], nl[2], e[2] };
-        rec.insert(rec.end(), r, r + 16);
-    }
-    const size_t nl = w.size();
-    cdf.resize(nl);
-    std::fill(s->pa_span.begin(), s->pa_span.end(), 0.0f);
-    double run = 0.0;
-    for (size_t i = 0; i < nl; ++i) {
-        run += w[i]; // the same sums in the same order as above
-        cdf[i] = i + 1 == nl ? 1.0f : (float)(run / total);
-        const float pa = (float)(w[i] / total) / rec[i * 16 + 3]; // pmf (as stored, f32) / area
-        rec[i * 16 + 3] = pa;
-        s->pa_span[s->cand_blob[cand[i]] - s->cand_lo] = pa;
-    }
-    s->n_lights = (uint32_t)nl;
-    if (!c) return PT_OK;
-    HIP_TRY(c, s->d_lights.ensure(std::max<size_t>(nl, 1) * 4)); HIP_TRY(c, s->d_cdf.ensure(std::max<size_t>(nl, 1)));
-    if (nl) {
-        HIP_TRY(c, hipMemcpy(s->d_lights.p, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(c, hipMemcpy(s->d_cdf.p, cdf.data(), nl * sizeof(float), hipMemcpyHostToDevice));
-    }
-    if (!s->pa_span.empty()) HIP_TRY(c, hipMemcpy(s->d_pa.p + s->cand_lo, s->pa_span.data(), s->pa_span.size() * sizeof(float), hipMemcpyHostToDevice));
-    return PT_OK;
-}
 
 pt_status layout_of(const pt_render_params *p, pt_tile_layout *o)
 {
@@ -320,21 +192,6 @@ hipEvent_t pool_event(pt_context *c, size_t i)
     return c->ev_pool[i];
 }
 
-void drain(pt_context *c) // nothing of the context's may still run: on its loop streams or its own
-{
-    for (auto &gs : c->group_stream) if (gs) (void)hipStreamSynchronize(gs);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-}
-
-// The public half of a call that enqueues work: an error exit may leave kernels or copies in flight (on the loop streams too), and nothing
-// of a failed call runs on after it
-template <typename Call> pt_status drained_on_failure(pt_context *c, Call call)
-{
-    const pt_status st = call();
-    if (st != PT_OK && c) { (void)hipSetDevice(c->device); drain(c); }
-    return st;
-}
-
 struct Frame {                  // a path-traced frame as plan_frame lays it out, and what its loops leave for finish_frame
     uint32_t nranks, streams, pixel_slots, n_slots, shard_cap, samples_per_stream, lag, n_loops, packed_chunk, default_bounces;
     uint32_t forced;            // ExtendKernel a frame flag or pt_tuning.extend_kernel forces (0 = none)
@@ -353,6 +210,32 @@ namespace ptrt {
 int context_device(const pt_context *c) { return c->device; }
 hipStream_t context_stream(const pt_context *c) { return c->stream; }
 void context_set_error(pt_context *c, const char *msg) { g_err = msg; if (c) c->err = msg; }
+pt_status fail(pt_context *ctx, pt_status code, const char *fmt, ...)
+{
+    char buf[512];
+    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
+    context_set_error(ctx, buf);
+    return code;
+}
+void context_drain(pt_context *c)
+{
+    for (auto &gs : c->group_stream) if (gs) (void)hipStreamSynchronize(gs);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+}
+pt_status check_device_array(pt_context *c, const void *p, uint64_t bytes, const char *what, const char *who, const char *host_flag)
+{
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess || (at.type != hipMemoryTypeDevice && !at.isManaged) || at.device != c->device) {
+        (void)hipGetLastError();
+        return fail(c, PT_ERR_INVALID_ARGUMENT, "%s: %s is not device memory of the context's device %d (host arrays: %s)", who, what, c->device, host_flag);
+    }
+    hipDeviceptr_t base = nullptr; size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return PT_OK; } // (range unknown: trust the caller)
+    if ((const char *)p + bytes > (const char *)base + size)
+        return fail(c, PT_ERR_INVALID_ARGUMENT, "%s: %s holds %llu bytes from the pointer on, the call needs %llu", who, what,
+                    (unsigned long long)((const char *)base + size - (const char *)p), (unsigned long long)bytes);
+    return PT_OK;
+}
 } // namespace ptrt
 
 extern "C" {
@@ -424,317 +307,18 @@ void pt_context_destroy(pt_context *c)
 {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    drain(c); // nothing may still run on what the members give back
+    context_drain(c); // nothing may still run on what the members give back
     delete c;
 }
 
-// ------------------------------------------------------------------------------------------------ scene
 
-pt_status pt_scene_create(pt_context *ctx, pt_scene **out)
-{
-    // ctx == NULL makes a detached (host-only) scene: commit builds the BVH blob for pt_scene_bvh_read/info,
-    // nothing is uploaded and pt_render rejects it. Used to check the builder where no device exists.
-    if (!out) return fail(ctx, PT_ERR_INVALID_ARGUMENT, "pt_scene_create: NULL argument");
-    pt_scene *s = new (std::nothrow) pt_scene();
-    if (!s) return fail(ctx, PT_ERR_OUT_OF_MEMORY, "host allocation failed");
-    s->ctx = ctx;
-    *out = s;
-    return PT_OK;
-}
-
-void pt_scene_destroy(pt_scene *s)
+void pt_scene_destroy(pt_scene *s) // (the scene's other calls: scene.cpp)
 {
     if (!s) return;
     if (s->ctx) { (void)hipSetDevice(s->ctx->device); (void)hipStreamSynchronize(s->ctx->stream); }
     delete s;
 }
 
-pt_status pt_scene_set_triangles(pt_scene *s, const float *verts9, const uint32_t *material_ids, uint64_t count)
-{
-    if (!s) return fail(nullptr, PT_ERR_INVALID_ARGUMENT, "scene is NULL");
-    if (count && !verts9) return fail(s->ctx, PT_ERR_INVALID_ARGUMENT, "verts9 is NULL");
-    if (count >= (1ull << 28)) return fail(s->ctx, PT_ERR_UNSUPPORTED, "more than 2^28 triangles");
-    for (uint64_t i = 0; i < count * 9; ++i)
-        if (!std::isfinite(verts9[i])) return fail(s->ctx, PT_ERR_INVALID_ARGUMENT, "non-finite vertex coordinate at float %llu", (unsigned long long)i);
-    s->verts.assign(verts9, verts9 + count * 9);
-    s->verts_on_device = false;
-    if (material_ids) s->tri_mat.assign(material_ids, material_ids + count); else s->tri_mat.assign(count, 0u);
-    s->committed = false;
-    return PT_OK;
-}
-
-pt_status pt_scene_set_spheres(pt_scene *s, const float *cxyzr, const uint32_t *material_ids, uint64_t count)
-{
-    if (!s) return fail(nullptr, PT_ERR_INVALID_ARGUMENT, "scene is NULL");
-    if (count && !cxyzr) return fail(s->ctx, PT_ERR_INVALID_ARGUMENT, "cxyzr is NULL");
-    if (count > kMaxSpheres) return fail(s->ctx, PT_ERR_UNSUPPORTED, "more than %u spheres (they are a flat list)", kMaxSpheres);
-    for (uint64_t i = 0; i < count; ++i)
-        if (!sphere_ok(cxyzr + i * 4)) return fail(s->ctx, PT_ERR_INVALID_ARGUMENT, "sphere %llu: non-finite centre or radius <= 0", (unsigned long long)i);
-    s->spheres.assign(cxyzr, cxyzr + count * 4);
-    if (material_ids) s->sph_mat.assign(material_ids, material_ids + count); else s->sph_mat.assign(count, 0u);
-    s->committed = false;
-    return PT_OK;
-}
-
-pt_status pt_scene_set_materials(pt_scene *s, const pt_material *mats, uint64_t count)
-{
-    if (!s) return fail(nullptr, PT_ERR_INVALID_ARGUMENT, "scene is NULL");
-    if (count && !mats) return fail(s->ctx, PT_ERR_INVALID_ARGUMENT, "mats is NULL");
-    for (uint64_t i = 0; i < count; ++i) {
-        if (mats[i].kind > PT_DIELECTRIC) return fail(s->ctx, PT_ERR_INVALID_ARGUMENT, "material %llu: unknown kind %u", (unsigned long long)i, mats[i].kind);
-        if (!finite3(mats[i].albedo) || !finite3(mats[i].emission) || !std::isfinite(mats[i].roughness) || !std::isfinite(mats[i].ior))
-            return fail(s->ctx, PT_ERR_INVALID_ARGUMENT, "material %llu: non-finite field", (unsigned long long)i);
-        if (mats[i].roughness < 0.f || mats[i].roughness > 1.f) return fail(s->ctx, PT_ERR_INVALID_ARGUMENT, "material %llu: roughness outside [0,1]", (unsigned long long)i);
-        if (mats[i].kind == PT_DIELECTRIC && !(mats[i].ior > 0.f)) return fail(s->ctx, PT_ERR_INVALID_ARGUMENT, "material %llu: ior <= 0", (unsigned long long)i);
-    }
-    s->mats.assign(mats, mats + count);
-    s->committed = false;
-    return PT_OK;
-}
-
-pt_status pt_scene_set_camera(pt_scene *s, const pt_camera *cam)
-{
-    if (!s || !cam) return fail(s ? s->ctx : nullptr, PT_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!finite3(cam->origin) || !finite3(cam->forward) || !finite3(cam->right) || !finite3(cam->up) ||
-        !std::isfinite(cam->scale) || !std::isfinite(cam->cx) || !std::isfinite(cam->cy))
-        return fail(s->ctx, PT_ERR_INVALID_ARGUMENT, "camera has a non-finite field");
-    s->cam = *cam; s->have_cam = true;
-    if (s->committed) s->ds.cam = *cam; // camera changes do not need a re-commit
-    return PT_OK;
-}
-
-pt_status pt_scene_set_sky(pt_scene *s, const float rgb[3])
-{
-    if (!s || !rgb) return fail(s ? s->ctx : nullptr, PT_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!finite3(rgb)) return fail(s->ctx, PT_ERR_INVALID_ARGUMENT, "sky is not finite");
-    for (int k = 0; k < 3; ++k) { s->sky[k] = rgb[k]; s->ds.sky[k] = rgb[k]; }
-    return PT_OK;
-}
-
-// ---- pt_scene_commit's phases, in the order they run. Each ends with a lap of the commit's clock.
-
-struct CommitClock { // PTRT_TIMING (developer aid): where a commit's time goes, on stderr
-    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-    void lap(const char *what)
-    {
-        static const bool timing = getenv("PTRT_TIMING") != nullptr;
-        if (timing) fprintf(stderr, "ptrt commit: %-28s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count());
-        t = std::chrono::steady_clock::now();
-    }
-};
-
-// Check: the builder flag, the layout (bvh_width leaves as one of PT_BVH_WIDTH_2 .. _8O), the camera and every material id
-static pt_status check_commit(const pt_scene *s, uint32_t &bvh_width, bool &lbvh)
-{
-    pt_context *c = s->ctx;
-    lbvh = (bvh_width & PT_BVH_BUILD_LBVH) != 0; // hierarchy built on the GPU instead of the host SAH builder
-    bvh_width &= ~(uint32_t)PT_BVH_BUILD_LBVH;
-    if (lbvh && !c) return fail(c, PT_ERR_UNSUPPORTED, "PT_BVH_BUILD_LBVH needs a device context (detached scenes use the host builder)");
-    // default layout: BVH4Q; scenes of up to ~200 triangles get BVH2 with float boxes — their whole tree is a handful of L1-resident
-    // lines, memory does not count and the 2-wide visit is the cheapest in ALU. ms per 1080p / 64 spp frame, BVH8Q | BVH4Q | BVH4 | BVH2
-    // (tools/exp_layouts.py): Cornell (12 triangles) 8.30 | 9.07 | 8.60 | 8.32, Cornell+glass+metal 9.82 | 11.34 | 9.82 | 9.18, walls of
-    // 42 triangles 17.7 | 12.2 | 11.4 | 11.4, of 162: 18.7 | 14.2 | 13.4 | 12.7, of 252: - | 13.0 | 13.7 | 13.4, of 1002: 20.2 | 14.2 | 16.5 |
-    // 15.0; soups of 100 / 400: - | 2.11 / 2.68 | 2.24 / 2.82 | 2.21 / 2.87. (Round 1 gave everything up to 256 triangles BVH8Q, on the
-    // strength of the 12-triangle box alone, where it is one node.)
-    if (bvh_width == PT_BVH_WIDTH_DEFAULT) bvh_width = s->tri_mat.size() <= 192 ? PT_BVH_WIDTH_2 : PT_BVH_WIDTH_4Q;
-    if (bvh_width != PT_BVH_WIDTH_2 && bvh_width != PT_BVH_WIDTH_4 && bvh_width != PT_BVH_WIDTH_4Q && bvh_width != PT_BVH_WIDTH_8Q && bvh_width != PT_BVH_WIDTH_8O)
-        return fail(c, PT_ERR_INVALID_ARGUMENT, "bvh_width must be one of PT_BVH_WIDTH_* (0, 2, 4, 68, 72, 73)");
-    if (!s->have_cam) return fail(c, PT_ERR_INVALID_ARGUMENT, "no camera set");
-    const uint32_t nt = (uint32_t)s->tri_mat.size(), ns = (uint32_t)s->sph_mat.size(), nm = (uint32_t)s->mats.size();
-    if ((nt || ns) && nm == 0) return fail(c, PT_ERR_INVALID_ARGUMENT, "primitives but no materials");
-    for (uint32_t i = 0; i < nt; ++i) if (s->tri_mat[i] >= nm) return fail(c, PT_ERR_INVALID_ARGUMENT, "triangle %u: material id %u >= %u", i, s->tri_mat[i], nm);
-    for (uint32_t i = 0; i < ns; ++i) if (s->sph_mat[i] >= nm) return fail(c, PT_ERR_INVALID_ARGUMENT, "sphere %u: material id %u >= %u", i, s->sph_mat[i], nm);
-    return PT_OK;
-}
-
-// Build tree: the hierarchy and its blob from the scene's current vertices, by one of three builders, then the quantised nodes of the
-// layouts that have them. Sets device_packed and host_mirror: only the first builder leaves the blob on the device alone.
-static pt_status build_tree(pt_scene *s, uint32_t bvh_width, bool lbvh, CommitClock &clock)
-{
-    pt_context *c = s->ctx;
-    if (s->verts_on_device) { // updated since the last commit: build from the current vertices
-        HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, hipMemcpy(s->verts.data(), s->refit.verts[s->refit.cur].p, s->verts.size() * sizeof(float), hipMemcpyDeviceToHost));
-        s->verts_on_device = false;
-    }
-    s->refit.ready = false;
-    s->blob_of_ready = false;
-    const uint32_t nt = (uint32_t)s->tri_mat.size();
-    const bool oct = bvh_width == PT_BVH_WIDTH_8O;
-    const uint32_t fan = layout_fan(bvh_width);
-    s->device_packed = false; s->host_mirror = true;
-    if (lbvh && nt >= 2 && bvh_width == PT_BVH_WIDTH_4Q) {
-        // the default layout is also packed on the device: nodes and triangle records are born in device memory
-        HIP_TRY(c, hipSetDevice(c->device));
-        DeviceBlob4Q db;
-        HIP_TRY(c, build_lbvh_blob4q_device(c->stream, s->verts.data(), s->tri_mat.data(), nt, db));
-        s->d_nodes = std::move(db.nodes); s->d_tris = std::move(db.tris); // (the scene's earlier arrays are freed here)
-        s->bvh = BvhBlob{};
-        s->bvh.width = fan; s->bvh.n_nodes = db.n_nodes; s->bvh.max_depth = db.max_depth; s->bvh.stack_need = db.stack_need;
-        s->bvh.sah_cost = db.sah_cost; s->bvh.build_ms = db.device_ms;
-        s->device_packed = true; s->host_mirror = false;
-    } else if (lbvh && nt >= 2) {
-        HIP_TRY(c, hipSetDevice(c->device));
-        BinaryBvh bt;
-        HIP_TRY(c, build_lbvh_device(c->stream, s->verts.data(), nt, bt));
-        build_bvh_from_binary(bt, s->verts.data(), s->tri_mat.data(), nt, fan, s->bvh, oct);
-    } else build_bvh(s->verts.data(), s->tri_mat.data(), nt, fan, s->bvh, oct);
-    clock.lap("hierarchy + blob");
-    if (s->bvh.max_depth > 90) return fail(c, PT_ERR_INTERNAL, "BVH depth %u exceeds the supported 90", s->bvh.max_depth);
-    s->layout = bvh_width;
-    s->packed_nodes.clear();
-    if (layout_quantised(bvh_width) && !s->device_packed) {
-        if (fan == 4) quantize_bvh4(s->bvh, s->packed_nodes);
-        else quantize_bvh8(s->bvh, s->packed_nodes);
-    }
-    clock.lap("quantise");
-    return PT_OK;
-}
-
-// Upload tree: the host-built blob's triangle records and nodes (a device-packed blob is where it belongs already)
-static pt_status upload_tree(pt_scene *s, CommitClock &clock)
-{
-    pt_context *c = s->ctx;
-    // the traversal kernels fetch a node or a triangle record by a 32-bit byte offset from its array's base (kernels.hip record())
-    if (s->node_bytes() > (1ull << 32) || s->n_blob_tris() * 64u > (1ull << 32))
-        return fail(c, PT_ERR_UNSUPPORTED, "BVH of %llu node bytes and %llu triangle records: each array must stay within 4 GiB",
-                    (unsigned long long)s->node_bytes(), (unsigned long long)s->n_blob_tris());
-    HIP_TRY(c, hipSetDevice(c->device));
-    static_assert(sizeof(BvhSlot) == 32 && sizeof(BvhTri) == 48 && sizeof(pt_material) == 48, "blob layout");
-    if (s->device_packed) return PT_OK;
-    HIP_TRY(c, s->d_nodes.ensure((size_t)(s->node_bytes() / 16)));
-    HIP_TRY(c, s->d_tris.ensure(s->bvh.tris.size() * 4));
-    // Device triangle record = one 64-byte line: the blob's three rows (docs/SPEC.md §4.1) + a shading row. A 48-byte
-    // record straddles two cache lines 3 times out of 4 when k_extend fetches it; a padded one never does, and the
-    // row that pads it is the one k_shade wants next: ng and the material id (blob_rules.h shading_row; rows 0-2 are the blob's triangle).
-    std::vector<float> rec(s->bvh.tris.size() * 16);
-    for (size_t i = 0; i < s->bvh.tris.size(); ++i) {
-        const BvhTri &t = s->bvh.tris[i];
-        std::memcpy(&rec[i * 16], &t, sizeof(BvhTri));
-        shading_row(t.e1, t.e2, t.mat, &rec[i * 16 + 12]);
-    }
-    clock.lap("triangle records");
-    if (!rec.empty()) HIP_TRY(c, hipMemcpy(s->d_tris.p, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice));
-    clock.lap("upload triangles");
-    if (s->node_bytes()) HIP_TRY(c, hipMemcpy(s->d_nodes.p, s->node_data(), s->node_bytes(), hipMemcpyHostToDevice));
-    return PT_OK;
-}
-
-// Upload primitives: the spheres, their {material, 1/r} and the materials
-static pt_status upload_primitives(pt_scene *s, CommitClock &clock)
-{
-    pt_context *c = s->ctx;
-    const uint32_t ns = (uint32_t)s->sph_mat.size(), nm = (uint32_t)s->mats.size();
-    HIP_TRY(c, s->d_spheres.ensure((ns + 3u) & ~3u)); // the kernels read the list four spheres (one 64-byte scalar load) at a time
-    HIP_TRY(c, s->d_sph_mat.ensure(ns));
-    HIP_TRY(c, s->d_mats.ensure((size_t)nm * 3));
-    if (ns) {
-        HIP_TRY(c, hipMemcpy(s->d_spheres.p, s->spheres.data(), (size_t)ns * 16, hipMemcpyHostToDevice));
-        HIP_TRY(c, hipMemcpy(s->d_sph_mat.p, sphere_mats(s->sph_mat.data(), s->spheres.data(), ns).data(), (size_t)ns * sizeof(uint2), hipMemcpyHostToDevice));
-    }
-    if (nm) HIP_TRY(c, hipMemcpy(s->d_mats.p, s->mats.data(), (size_t)nm * sizeof(pt_material), hipMemcpyHostToDevice));
-    clock.lap("upload nodes + rest");
-    return PT_OK;
-}
-
-// Light table of next-event estimation (docs/SPEC.md §7): the candidates, where their pa lives in the blob order, the table
-static pt_status light_table(pt_scene *s, CommitClock &clock)
-{
-    pt_context *c = s->ctx;
-    const uint32_t nt = (uint32_t)s->tri_mat.size(), nbt = (uint32_t)s->n_blob_tris();
-    s->light_cand.clear(); s->cand_blob.clear(); s->pa_span.clear(); s->cand_lo = 0; s->n_lights = 0;
-    for (uint32_t i = 0; i < nt; ++i) {
-        const float *e = s->mats[s->tri_mat[i]].emission;
-        if (e[0] != 0.f || e[1] != 0.f || e[2] != 0.f) s->light_cand.push_back(i);
-    }
-    HIP_TRY(c, s->d_pa.ensure(std::max<size_t>(nbt, 1)));
-    HIP_TRY(c, hipMemset(s->d_pa.p, 0, std::max<size_t>(nbt, 1) * sizeof(float)));
-    if (!s->light_cand.empty()) {
-        std::vector<uint32_t> blob_of(nt), ids(nbt);
-        if (s->device_packed) HIP_TRY(c, hipMemcpy2D(ids.data(), 4, (const uint8_t *)s->d_tris.p + 12, 64, 4, nbt, hipMemcpyDeviceToHost)); // row 0 .w
-        else for (uint32_t j = 0; j < nbt; ++j) ids[j] = s->bvh.tris[j].id;
-        for (uint32_t j = 0; j < nbt; ++j) blob_of[ids[j]] = j;
-        uint32_t hi = 0; s->cand_lo = nbt;
-        for (const uint32_t id : s->light_cand) {
-            const uint32_t b = blob_of[id];
-            s->cand_blob.push_back(b); s->cand_lo = std::min(s->cand_lo, b); hi = std::max(hi, b);
-        }
-        s->pa_span.assign(hi - s->cand_lo + 1u, 0.0f);
-        const pt_status st = build_lights(c, s, s->verts.data(), 0);
-        if (st != PT_OK) return st;
-    }
-    clock.lap("light table");
-    return PT_OK;
-}
-
-// Publish: what the kernels see of the scene, and what earlier frames measured on the old one forgotten
-static void publish_scene(pt_scene *s)
-{
-    DeviceScene &d = s->ds;
-    d.nodes = s->d_nodes.p; d.tris = s->d_tris.p; d.spheres = s->d_spheres.p; d.sph_mat = s->d_sph_mat.p; d.mats = s->d_mats.p;
-    d.n_nodes = s->bvh.n_nodes; d.n_tris = (uint32_t)s->tri_mat.size(); d.n_spheres = (uint32_t)s->sph_mat.size(); d.n_mats = (uint32_t)s->mats.size();
-    for (int k = 0; k < 3; ++k) d.sky[k] = s->sky[k];
-    d.bvh_width = s->layout;
-    d.cam = s->cam;
-    s->ext = ExtendChoice{};
-    s->has_specular = false;
-    for (const pt_material &m : s->mats) if (m.kind != PT_LAMBERT) s->has_specular = true;
-    s->committed = true;
-}
-
-pt_status pt_scene_commit(pt_scene *s, uint32_t bvh_width)
-{
-    if (!s) return fail(nullptr, PT_ERR_INVALID_ARGUMENT, "scene is NULL");
-    bool lbvh = false;
-    pt_status st = check_commit(s, bvh_width, lbvh);
-    if (st != PT_OK) return st;
-    CommitClock clock;
-    if ((st = build_tree(s, bvh_width, lbvh, clock)) != PT_OK) return st;
-    if (!s->ctx) { s->committed = true; return PT_OK; } // detached scene: host-side blob only
-    if ((st = upload_tree(s, clock)) != PT_OK || (st = upload_primitives(s, clock)) != PT_OK || (st = light_table(s, clock)) != PT_OK) return st;
-    publish_scene(s);
-    return PT_OK;
-}
-
-pt_status pt_scene_bvh_info(const pt_scene *s, pt_bvh_info *o)
-{
-    if (!s || !o) return fail(s ? s->ctx : nullptr, PT_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!s->committed) return fail(s->ctx, PT_ERR_NOT_COMMITTED, "scene not committed");
-    std::memset(o, 0, sizeof *o);
-    o->width = s->layout; o->n_nodes = s->bvh.n_nodes; o->n_tris = (uint32_t)s->n_blob_tris();
-    o->max_depth = s->bvh.max_depth;
-    o->node_bytes = s->node_bytes();
-    o->tri_bytes = s->n_blob_tris() * sizeof(BvhTri);
-    o->build_ms = s->bvh.build_ms; o->sah_cost = s->bvh.sah_cost;
-    o->stack_need = s->bvh.stack_need;
-    return PT_OK;
-}
-
-pt_status pt_scene_bvh_read(const pt_scene *s, void *nodes, uint64_t node_bytes, void *tris48, uint64_t tri_bytes)
-{
-    if (!s) return fail(nullptr, PT_ERR_INVALID_ARGUMENT, "scene is NULL");
-    if (!s->committed) return fail(s->ctx, PT_ERR_NOT_COMMITTED, "scene not committed");
-    if (!s->host_mirror) { // packed on the device or refitted: fetch the blob now (nodes as they are, triangles = rows 0-2 of the 64-byte records)
-        const pt_scene *m = s; // fills the (mutable) host copies the scene owns; device data and results are untouched
-        pt_context *c = s->ctx;
-        HIP_TRY(c, hipSetDevice(c->device));
-        const size_t nn = s->bvh.n_nodes;
-        void *host_nodes = nullptr; size_t bytes = 0;
-        if (s->quantised()) { m->packed_nodes.resize(nn * layout_node_bytes(s->layout)); host_nodes = m->packed_nodes.data(); bytes = m->packed_nodes.size(); }
-        else { m->bvh.slots.resize(nn * s->bvh.width); host_nodes = m->bvh.slots.data(); bytes = m->bvh.slots.size() * sizeof(BvhSlot); }
-        std::vector<float> rec(s->n_blob_tris() * 16);
-        if (bytes) HIP_TRY(c, hipMemcpy(host_nodes, s->d_nodes.p, bytes, hipMemcpyDeviceToHost));
-        if (!rec.empty()) HIP_TRY(c, hipMemcpy(rec.data(), s->d_tris.p, rec.size() * sizeof(float), hipMemcpyDeviceToHost));
-        m->bvh.tris.resize(s->n_blob_tris());
-        for (size_t i = 0; i < m->bvh.tris.size(); ++i) std::memcpy(&m->bvh.tris[i], &rec[i * 16], sizeof(BvhTri));
-        s->host_mirror = true;
-    }
-    const uint64_t nb = s->node_bytes(), tb = (uint64_t)s->bvh.tris.size() * sizeof(BvhTri);
-    if (node_bytes < nb || tri_bytes < tb || (nb && !nodes) || (tb && !tris48)) return fail(s->ctx, PT_ERR_INVALID_ARGUMENT, "buffers too small: need %llu + %llu bytes", (unsigned long long)nb, (unsigned long long)tb);
-    if (nb) std::memcpy(nodes, s->node_data(), nb);
-    if (tb) std::memcpy(tris48, s->bvh.tris.data(), tb);
-    return PT_OK;
-}
 
 // ------------------------------------------------------------------------------------------------ frame
 
@@ -827,7 +411,7 @@ static pt_status plan_frame(pt_context *c, const pt_scene *s, const pt_render_pa
     // hit records and the metal / dielectric buckets are k_shade's (no kernel indexes the miss and Lambert buckets)
     if (f.split) { HIP_TRY(c, c->hit.ensure(f.n_slots)); HIP_TRY(c, c->q_metal.ensure(f.q_entries)); HIP_TRY(c, c->q_dielectric.ensure(f.q_entries)); }
     if (!f.full_state) { HIP_TRY(c, c->q_init.ensure(f.q_entries)); HIP_TRY(c, c->cnt_init.ensure(kCntTotalWords)); }
-    const uint32_t ovf = s->stack_overflow();
+    const uint32_t ovf = s->tree.stack_overflow();
     if (ovf) HIP_TRY(c, c->stack_ovf.ensure((size_t)ovf * f.q_entries));
     if (f.nee) {
         HIP_TRY(c, c->nee_ext.ensure(f.n_slots)); HIP_TRY(c, c->nee_rad.ensure(f.n_slots));
@@ -1053,7 +637,7 @@ static pt_status render_frame(pt_context *c, const pt_scene *s, const pt_render_
     if (p->mode != PT_PATH_TRACE) return fail(c, PT_ERR_INVALID_ARGUMENT, "unknown mode %u", p->mode);
     Frame f{};
     if ((st = plan_frame(c, s, p, lay, f)) != PT_OK) return st;
-    ExtendFrame x(s->ext, f.forced, f.count || f.profile);
+    ExtendFrame x(s->cache.ext, f.forced, f.count || f.profile);
     f.n_loops = (f.profile || f.count || x.kernel == 0u) ? 1u : c->tuning.loops ? c->tuning.loops : 2u; // timed kernels run alone
     if ((st = start_frame(c, s, p, f)) != PT_OK || (st = run_loops(c, s, p, f, x)) != PT_OK) return st;
     return finish_frame(c, p, f, x, stats);
@@ -1068,25 +652,6 @@ pt_status pt_render(pt_context *c, const pt_scene *s, const pt_render_params *p,
 
 // ------------------------------------------------------------------------------------------------ ray queries (docs/SPEC.md §4.2)
 
-namespace {
-// A caller's device array must lie inside one allocation on the context's device: the kernel reads / writes `bytes` from `p` unchecked.
-pt_status check_device_array(pt_context *c, const void *p, uint64_t bytes, const char *what, const char *who = "pt_trace_rays",
-                             const char *host_flag = "PT_TRACE_HOST_MEMORY")
-{
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess || (at.type != hipMemoryTypeDevice && !at.isManaged) || at.device != c->device) {
-        (void)hipGetLastError();
-        return fail(c, PT_ERR_INVALID_ARGUMENT, "%s: %s is not device memory of the context's device %d (host arrays: %s)", who, what, c->device, host_flag);
-    }
-    hipDeviceptr_t base = nullptr; size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return PT_OK; } // (range unknown: trust the caller)
-    if ((const char *)p + bytes > (const char *)base + size)
-        return fail(c, PT_ERR_INVALID_ARGUMENT, "%s: %s holds %llu bytes from the pointer on, the call needs %llu", who, what,
-                    (unsigned long long)((const char *)base + size - (const char *)p), (unsigned long long)bytes);
-    return PT_OK;
-}
-} // namespace
-
 // The plumbing of a query (pt_trace_rays, pt_denoise's guide pass): the context's own counter block and overflow area, never pt_render's
 // (the frame-start template, the partial sums, the queues and their counters stay untouched). trace_setup sizes the overflow area for
 // launches of up to n_rays rays and zeroes the counter words the kernels use; trace_launch enqueues the launches (k_trace indexes with 32
@@ -1098,7 +663,7 @@ static pt_status trace_setup(pt_context *c, const pt_scene *s, uint64_t n_rays, 
     const uint32_t blocks = trace_blocks((uint32_t)std::min<uint64_t>(n_rays, kTraceChunk)), lanes = blocks * kExtBlock;
     ps = PathState{};
     ps.shard_cap = (lanes + kShards - 1u) / kShards; // one overflow column per lane of the grid, reused by its every ray
-    ps.stack_ovf_entries = s->stack_overflow();
+    ps.stack_ovf_entries = s->tree.stack_overflow();
     if (ps.stack_ovf_entries) HIP_TRY(c, c->trace_ovf.ensure((size_t)ps.stack_ovf_entries * kShards * ps.shard_cap));
     ps.stack_ovf = c->trace_ovf.p;
     HIP_TRY(c, c->trace_cnt.ensure(kCntTotalWords)); // the kernels use the global words only: error flag and visit counters
@@ -1169,131 +734,6 @@ pt_status pt_trace_rays(pt_context *c, const pt_scene *s, const void *rays, void
     return drained_on_failure(c, [&] { return trace_rays(c, s, rays, hits, n_rays, flags, stats); }); // (e.g. a copy into `hits`)
 }
 
-// ------------------------------------------------------------------------------------------------ geometry updates (docs/SPEC.md §4.3)
-
-// The first update after a commit: level lists from the tree's refs (in device node order) and the
-// scratch the passes use. Sizes are those of the committed tree, which an update never changes.
-static pt_status prepare_refit(pt_scene *s)
-{
-    pt_context *c = s->ctx;
-    auto &R = s->refit;
-    const uint32_t nn = s->bvh.n_nodes, fan = s->bvh.width, nbt = (uint32_t)s->n_blob_tris(), nt = (uint32_t)s->tri_mat.size();
-    for (auto &e : R.ev) HIP_TRY(c, e.create());
-    std::vector<int32_t> refs((size_t)nn * fan);
-    if (s->device_packed) { // quantised nodes that never visited the host: the run of refs in every node
-        if (nn) HIP_TRY(c, hipMemcpy2D(refs.data(), 4 * fan, (const uint8_t *)s->d_nodes.p + layout_ref_at(s->layout, 0), layout_node_bytes(s->layout), 4 * fan, nn, hipMemcpyDeviceToHost));
-    } else for (size_t k = 0; k < refs.size(); ++k) refs[k] = s->bvh.slots[k].ref; // the host blob the device nodes were packed from
-    std::vector<uint32_t> list;
-    if (!refit_levels(refs.data(), nn, fan, nbt, list, R.level_off)) return fail(c, PT_ERR_INTERNAL, "pt_scene_update_triangles: the committed tree's refs do not form a tree");
-    HIP_TRY(c, R.list.ensure(list.size()));
-    if (!list.empty()) HIP_TRY(c, hipMemcpy(R.list.p, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_TRY(c, R.tbox.ensure((size_t)nbt * 6)); HIP_TRY(c, R.nbox.ensure((size_t)nn * 6)); HIP_TRY(c, R.carea.ensure((size_t)nn * fan));
-    HIP_TRY(c, R.verts[0].ensure((size_t)nt * 9)); HIP_TRY(c, R.verts[1].ensure((size_t)nt * 9));
-    HIP_TRY(c, R.sah.ensure(refit_sah_blocks(nn) + 1u)); HIP_TRY(c, R.flag.ensure(1));
-    R.ready = true;
-    return PT_OK;
-}
-
-static pt_status update_triangles(pt_scene *s, const void *verts9, uint64_t count, uint32_t flags, pt_stats *stats)
-{
-    if (!s) return fail(nullptr, PT_ERR_INVALID_ARGUMENT, "pt_scene_update_triangles: scene is NULL");
-    pt_context *c = s->ctx;
-    if (flags & ~(uint32_t)PT_UPDATE_HOST_MEMORY) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_scene_update_triangles: unknown flag bits 0x%x", flags & ~(uint32_t)PT_UPDATE_HOST_MEMORY);
-    if (!s->committed) return fail(c, PT_ERR_NOT_COMMITTED, "pt_scene_update_triangles: scene not committed");
-    const uint64_t nt = s->tri_mat.size();
-    if (count != nt) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_scene_update_triangles: count %llu, the scene was committed with %llu triangles", (unsigned long long)count, (unsigned long long)nt);
-    if (count && !verts9) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_scene_update_triangles: verts9 is NULL");
-    const bool host = (flags & PT_UPDATE_HOST_MEMORY) != 0;
-    if (host) {
-        const float *v = (const float *)verts9;
-        for (uint64_t i = 0; i < count * 9; ++i)
-            if (!std::isfinite(v[i])) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_scene_update_triangles: non-finite vertex coordinate at float %llu", (unsigned long long)i);
-    }
-    if (!c) return fail(c, PT_ERR_UNSUPPORTED, "pt_scene_update_triangles: a detached scene has no device tree to refit (set the triangles and commit)");
-    pt_stats out{};
-    if (count == 0) { if (stats) *stats = out; return PT_OK; }
-    HIP_TRY(c, hipSetDevice(c->device));
-    pt_status st;
-    if (!host) {
-        if ((uintptr_t)verts9 & 3u) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_scene_update_triangles: verts9 must be 4-byte aligned");
-        if ((st = check_device_array(c, verts9, count * 36u, "verts9", "pt_scene_update_triangles", "PT_UPDATE_HOST_MEMORY")) != PT_OK) return st;
-    }
-    auto &R = s->refit;
-    if (!R.ready && (st = prepare_refit(s)) != PT_OK) return st;
-    hipStream_t q = c->stream;
-    const uint32_t nxt = s->verts_on_device ? R.cur ^ 1u : R.cur; // the buffer that does not hold the scene's current vertices
-    float *v = R.verts[nxt].p;
-    if (host) HIP_TRY(c, hipMemcpyAsync(v, verts9, count * 36u, hipMemcpyHostToDevice, q));
-    HIP_TRY(c, hipEventRecord(R.ev[0], q));
-    float ms_check = 0.f;
-    if (!host) { // the non-finite reduction runs (and copies the batch aside) before anything of the scene is written
-        HIP_TRY(c, hipMemsetAsync(R.flag.p, 0, sizeof(uint32_t), q));
-        HIP_TRY(c, launch_refit_stage(q, (const float *)verts9, v, count * 9u, R.flag.p));
-        HIP_TRY(c, hipEventRecord(R.ev[1], q));
-        uint32_t bad = 0;
-        HIP_TRY(c, hipMemcpyAsync(&bad, R.flag.p, sizeof bad, hipMemcpyDeviceToHost, q));
-        HIP_TRY(c, hipStreamSynchronize(q));
-        if (bad) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_scene_update_triangles: non-finite vertex coordinate in the device array");
-        HIP_TRY(c, hipEventElapsedTime(&ms_check, R.ev[0], R.ev[1]));
-        HIP_TRY(c, hipEventRecord(R.ev[0], q));
-    }
-    const uint32_t layout = s->layout;
-    HIP_TRY(c, launch_refit_tris(q, v, s->d_tris.p, (uint32_t)s->n_blob_tris(), R.tbox.p));
-    for (size_t l = 0; l + 1 < R.level_off.size(); ++l)
-        HIP_TRY(c, launch_refit_level(q, layout, s->d_nodes.p, R.list.p + R.level_off[l], R.level_off[l + 1] - R.level_off[l], R.tbox.p, R.nbox.p, R.carea.p));
-    const uint32_t nb = refit_sah_blocks(s->bvh.n_nodes);
-    HIP_TRY(c, launch_refit_sah(q, layout, s->d_nodes.p, s->bvh.n_nodes, R.carea.p, R.nbox.p, R.sah.p, R.sah.p + nb));
-    HIP_TRY(c, hipEventRecord(R.ev[2], q));
-    double sah = 0.0;
-    HIP_TRY(c, hipMemcpyAsync(&sah, R.sah.p + nb, sizeof sah, hipMemcpyDeviceToHost, q));
-    HIP_TRY(c, hipStreamSynchronize(q));
-    float ms = 0.f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, R.ev[0], R.ev[2]));
-    out.gpu_ms = (double)ms + ms_check;
-    if (!s->pa_span.empty()) { // the light table from the new vertices of the candidates (same candidates: the materials stay)
-        const uint32_t lo = s->light_cand.front(), hi = s->light_cand.back(); // in triangle order
-        std::vector<float> span(host ? 0u : (size_t)(hi - lo + 1u) * 9u); // a device array: only the candidates' span comes back
-        if (!host) HIP_TRY(c, hipMemcpy(span.data(), v + (size_t)lo * 9u, span.size() * sizeof(float), hipMemcpyDeviceToHost));
-        if ((st = host ? build_lights(c, s, (const float *)verts9, 0) : build_lights(c, s, span.data(), lo)) != PT_OK) return st;
-    }
-    R.cur = nxt; s->verts_on_device = true;
-    s->bvh.sah_cost = (float)sah;
-    s->host_mirror = false;
-    if (stats) *stats = out;
-    return PT_OK;
-}
-
-static pt_status update_spheres(pt_scene *s, const float *cxyzr, uint64_t count)
-{
-    if (!s) return fail(nullptr, PT_ERR_INVALID_ARGUMENT, "pt_scene_update_spheres: scene is NULL");
-    pt_context *c = s->ctx;
-    if (!s->committed) return fail(c, PT_ERR_NOT_COMMITTED, "pt_scene_update_spheres: scene not committed");
-    const uint64_t ns = s->sph_mat.size();
-    if (count != ns) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_scene_update_spheres: count %llu, the scene was committed with %llu spheres", (unsigned long long)count, (unsigned long long)ns);
-    if (count && !cxyzr) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_scene_update_spheres: cxyzr is NULL");
-    for (uint64_t i = 0; i < count; ++i)
-        if (!sphere_ok(cxyzr + i * 4)) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_scene_update_spheres: sphere %llu: non-finite centre or radius <= 0", (unsigned long long)i);
-    if (!c) return fail(c, PT_ERR_UNSUPPORTED, "pt_scene_update_spheres: a detached scene has no device copy to update (set the spheres and commit)");
-    if (count == 0) return PT_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const std::vector<uint2> mi = sphere_mats(s->sph_mat.data(), cxyzr, count);
-    hipStream_t q = c->stream;
-    HIP_TRY(c, hipMemcpyAsync(s->d_spheres.p, cxyzr, count * 16u, hipMemcpyHostToDevice, q));
-    HIP_TRY(c, hipMemcpyAsync(s->d_sph_mat.p, mi.data(), count * sizeof(uint2), hipMemcpyHostToDevice, q));
-    HIP_TRY(c, hipStreamSynchronize(q));
-    s->spheres.assign(cxyzr, cxyzr + count * 4);
-    return PT_OK;
-}
-
-pt_status pt_scene_update_triangles(pt_scene *s, const void *verts9, uint64_t count, uint32_t flags, pt_stats *stats)
-{
-    return drained_on_failure(s ? s->ctx : nullptr, [&] { return update_triangles(s, verts9, count, flags, stats); });
-}
-
-pt_status pt_scene_update_spheres(pt_scene *s, const float *cxyzr, uint64_t count)
-{
-    return drained_on_failure(s ? s->ctx : nullptr, [&] { return update_spheres(s, cxyzr, count); });
-}
 
 // ------------------------------------------------------------------------------------------------ denoising (docs/SPEC.md §8)
 
@@ -1331,20 +771,20 @@ static pt_status denoise(pt_context *c, const pt_scene *s, const pt_denoise_para
     HIP_TRY(c, c->dn_g0.ensure(n)); HIP_TRY(c, c->dn_g1.ensure(n));
     if (passes) HIP_TRY(c, c->dn_out.ensure(n));
     const uint32_t nt = s->ds.n_tris;
-    if (!s->blob_of_ready) HIP_TRY(c, s->d_blob_of.ensure(std::max<size_t>(nt, 1)));
+    if (!s->cache.blob_of_ready) HIP_TRY(c, s->cache.d_blob_of.ensure(std::max<size_t>(nt, 1)));
     pt_status st;
     PathState ps;
     if ((st = trace_setup(c, s, n, ps)) != PT_OK) return st;
     hipStream_t q = c->stream;
     HIP_TRY(c, hipEventRecord(c->ev_denoise[0], q));
-    if (!s->blob_of_ready) { // (zeroed first: every entry is a valid blob index even if an id were missing)
-        HIP_TRY(c, hipMemsetAsync(s->d_blob_of.p, 0, std::max<size_t>(nt, 1) * sizeof(uint32_t), q));
-        HIP_TRY(c, launch_guide_index(q, s->ds.tris, nt, s->d_blob_of.p));
+    if (!s->cache.blob_of_ready) { // (zeroed first: every entry is a valid blob index even if an id were missing)
+        HIP_TRY(c, hipMemsetAsync(s->cache.d_blob_of.p, 0, std::max<size_t>(nt, 1) * sizeof(uint32_t), q));
+        HIP_TRY(c, launch_guide_index(q, s->ds.tris, nt, s->cache.d_blob_of.p));
     }
     float4 *rays = c->dn_work.p;
     HIP_TRY(c, launch_guide_rays(q, s->cam, w, h, rays));
     if ((st = trace_launch(c, s, ps, rays, c->dn_hits.p, n, false, false)) != PT_OK) return st;
-    HIP_TRY(c, launch_guide_resolve(q, s->ds, s->d_blob_of.p, rays, c->dn_hits.p, (uint32_t)n, c->dn_g0.p, c->dn_g1.p));
+    HIP_TRY(c, launch_guide_resolve(q, s->ds, s->cache.d_blob_of.p, rays, c->dn_hits.p, (uint32_t)n, c->dn_g0.p, c->dn_g1.p));
     HIP_TRY(c, hipEventRecord(c->ev_denoise[1], q));
     // pass i reads the framebuffer (i = 0) or pass i-1's image; the last pass writes dn_out, the others alternate between the two halves
     // of dn_work (the rays are dead by then)
@@ -1365,7 +805,7 @@ static pt_status denoise(pt_context *c, const pt_scene *s, const pt_denoise_para
     HIP_TRY(c, hipStreamSynchronize(q));
     if (hc[kCntError - kCntGlobals])
         return fail(c, PT_ERR_INTERNAL, "pt_denoise: device error flag 0x%x in the guide pass (1 = traversal stack overflow, 2 = step limit)", hc[kCntError - kCntGlobals]);
-    s->blob_of_ready = true;
+    s->cache.blob_of_ready = true;
     float ms_guides = 0.f, ms_filter = 0.f;
     HIP_TRY(c, hipEventElapsedTime(&ms_guides, c->ev_denoise[0], c->ev_denoise[1]));
     HIP_TRY(c, hipEventElapsedTime(&ms_filter, c->ev_denoise[1], c->ev_denoise[2]));

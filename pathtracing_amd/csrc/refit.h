@@ -1,5 +1,5 @@
 // refit.h — pt_scene_update_triangles on the device (refit.hip): new vertices into a committed tree whose topology and leaf assignment
-// stay, docs/SPEC.md §4.3. api.cpp owns the buffers and calls these in order: stage (device input), triangles, levels deepest first, SAH.
+// stay, docs/SPEC.md §4.3. scene.cpp owns the buffers and calls these in order: stage (device input), triangles, levels deepest first, SAH.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>

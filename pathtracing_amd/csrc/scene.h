@@ -1,0 +1,147 @@
+// scene.h — pt_scene, and one owner each for the two things a committed scene keeps on both sides of the bus: its tree and its
+// vertices. Which copy is current is private to the owner; nobody else keeps a flag about it. Private to api.cpp and scene.cpp, as
+// are the helpers every public call uses (defined once, in api.cpp).
+#pragma once
+#include "ptrt_internal.h"
+#include "bvh_build.h"
+#include "blob_rules.h"
+#include "device_owner.h"
+#include <vector>
+
+namespace ptrt {
+
+pt_status fail(pt_context *ctx, pt_status code, const char *fmt, ...); // sets the context's (NULL: the thread's) last error, returns code
+#define HIP_TRY(ctx, expr)                                                                          \
+    do { hipError_t _e = (expr);                                                                    \
+         if (_e != hipSuccess)                                                                      \
+             return fail(ctx, _e == hipErrorOutOfMemory ? PT_ERR_OUT_OF_MEMORY : PT_ERR_HIP,        \
+                         "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
+    } while (0)
+
+void context_drain(pt_context *c); // nothing of the context's may still run: on its loop streams or its own
+
+// The public half of a call that enqueues work: an error exit may leave kernels or copies in flight (on the loop streams too), and nothing
+// of a failed call runs on after it
+template <typename Call> pt_status drained_on_failure(pt_context *c, Call call)
+{
+    const pt_status st = call();
+    if (st != PT_OK && c) { (void)hipSetDevice(context_device(c)); context_drain(c); }
+    return st;
+}
+
+// A caller's device array must lie inside one allocation on the context's device: the kernel reads / writes `bytes` from `p` unchecked.
+pt_status check_device_array(pt_context *c, const void *p, uint64_t bytes, const char *what, const char *who = "pt_trace_rays",
+                             const char *host_flag = "PT_TRACE_HOST_MEMORY");
+
+struct CommitClock;
+
+// The committed tree: the device arrays the kernels traverse, its figures (recorded when the tree is adopted, never re-derived), and the
+// host image of the docs/SPEC.md §4.1 blob. The image is fresh after a host build, lacks current boxes and triangle rows after a refit,
+// and is absent after a build that packed the blob on the device; host_image() fetches exactly then.
+class CommittedTree {
+public:
+    DevBuf<float4> d_nodes, d_tris;      // nodes in the layout's format; one 64-byte record per blob triangle
+    uint32_t layout = 0, fan = 0;        // PT_BVH_WIDTH_* the scene was committed with, children per node
+    uint32_t n_nodes = 0, n_tris = 0;    // n_tris: blob triangle records
+    uint32_t max_depth = 0, stack_need = 0;
+    float sah_cost = 0.f;
+    double build_ms = 0.0;
+    uint64_t node_bytes = 0;
+    uint32_t stack_overflow() const { return stack_need > kStackLds ? stack_need - kStackLds : 0u; } // traversal-stack entries per ray beyond those in LDS
+
+    // A host-built blob (quantised here where the layout wants it): the image is fresh, the upload pending. The device arrays of the
+    // tree before it stay for upload() to reuse.
+    void adopt(BvhBlob &&blob, uint32_t layout_id);
+    // A BVH4Q blob packed on the device (lbvh.hip build_lbvh_blob4q_device) over n_records triangles: no image, nothing to upload
+    void adopt(DeviceBlob4Q &&blob, uint32_t n_records);
+    pt_status upload(pt_context *c, CommitClock &clock);
+    // The refit rewrote every box and triangle row of the device copy. Refs and ids stay: an update never changes the topology.
+    void device_rewritten(float new_sah_cost) { sah_cost = new_sah_cost; if (image == Image::fresh) image = Image::topology_only; }
+    pt_status host_image(pt_context *c, const void *&nodes, const BvhTri *&tris) const;
+    // Narrow reads of the topology, 4 bytes per child slot / per record, from the image if it has them, else by a strided copy:
+    // the refs of every node (n_nodes x fan) and the original triangle id of every blob record
+    pt_status refs(pt_context *c, std::vector<int32_t> &out) const;
+    pt_status ids(pt_context *c, std::vector<uint32_t> &out) const;
+
+private:
+    enum class Image { fresh, topology_only, absent };
+    mutable Image image = Image::fresh;  // (mutable with the vectors below: pt_scene_bvh_read fills them through a const scene)
+    mutable std::vector<BvhSlot> slots;  // f32 layouts: n_nodes * fan
+    mutable std::vector<uint8_t> packed; // layouts PT_BVH_WIDTH_4Q / _8Q / _8O: the 64- / 128-byte nodes
+    mutable std::vector<BvhTri> tris;
+    bool upload_pending = false;
+    const void *node_data() const { return layout_quantised(layout) ? (const void *)packed.data() : (const void *)slots.data(); }
+};
+
+// A scene's triangle vertices (9 floats each): the host vector and the two device buffers updates alternate between. An update
+// writes next(), and only when all of it has succeeded does next_is_current() make that the scene's vertices.
+class SceneVertices {
+public:
+    void set(const float *verts9, uint64_t count) { host_.assign(verts9, verts9 + count * 9); host_stale = false; }
+    pt_status host(pt_context *c, const float *&verts9); // fetched first if an update has run since
+    hipError_t reserve_device()                          // both buffers, for as many vertices as the host vector holds
+    {
+        const hipError_t e = dev[0].ensure(host_.size());
+        return e != hipSuccess ? e : dev[1].ensure(host_.size());
+    }
+    float *next() const { return dev[cur ^ 1u].p; }
+    void next_is_current() { cur ^= 1u; host_stale = true; }
+
+private:
+    std::vector<float> host_;
+    DevBuf<float> dev[2];
+    uint32_t cur = 0;        // dev[cur] holds the scene's vertices while host_stale
+    bool host_stale = false;
+};
+
+struct ExtendChoice {           // what a scene remembers of the extend-kernel probe (api.cpp ExtendFrame)
+    uint32_t kernel = 0;        // the ExtendKernel an earlier frame picked (0 = none yet)
+    double rate_simple = 0.0, rate_packed = 0.0; // rays per ms of whole frames run on one kernel (frames too short to probe inside)
+    uint32_t misses = 0;        // warm frames too small to time: after three the scene settles on the one-ray-per-lane kernel for good
+};
+
+// Everything derived from the committed tree and filled on first use, not scene content: pt_scene_commit forgets it all at once. The
+// device buffers keep their allocations across commits (ensure()); only what they hold stops counting.
+struct CommitCaches {
+    // pt_scene_update_triangles (refit.hip, docs/SPEC.md §4.3): made by the first update after a commit
+    struct Refit {
+        bool ready = false;                  // level lists built for the committed tree
+        std::vector<uint32_t> level_off;     // level l (deepest first) = list[level_off[l] .. level_off[l + 1])
+        DevBuf<uint32_t> list, flag;
+        DevBuf<float> tbox, nbox, carea;     // per blob triangle / per node / per child slot
+        DevBuf<double> sah;                  // per-block partial sums, then the total
+        Event ev[4];
+    } refit;
+    // pt_denoise: original triangle id -> blob index (where a guide finds its hit's shading row), made by the first denoise after a
+    // commit; updates keep it (they keep every record's id and place)
+    DevBuf<uint32_t> d_blob_of;
+    bool blob_of_ready = false;
+    ExtendChoice ext;                        // what earlier frames measured
+    void invalidate() { refit.ready = false; blob_of_ready = false; ext = ExtendChoice{}; }
+};
+
+} // namespace ptrt
+
+struct pt_scene {
+    pt_context *ctx = nullptr;
+    ptrt::SceneVertices verts; std::vector<uint32_t> tri_mat;
+    std::vector<float> spheres; std::vector<uint32_t> sph_mat;
+    std::vector<pt_material> mats;
+    pt_camera cam{};
+    float sky[3] = { 0.f, 0.f, 0.f };
+    bool have_cam = false, committed = false;
+    ptrt::CommittedTree tree;
+    mutable ptrt::CommitCaches cache;    // (mutable: pt_render and pt_denoise fill it through the const scene they receive)
+    ptrt::DevBuf<float4> d_spheres, d_mats;
+    bool has_specular = false;
+    ptrt::DevBuf<uint2> d_sph_mat;
+    ptrt::DeviceScene ds{};
+    // The light table of next-event estimation (docs/SPEC.md §7, build_lights): made at every commit and every triangle update from the
+    // candidates — the triangles whose material emits, in triangle order — of which those with area * (e.r + e.g + e.b) > 0 are lights.
+    std::vector<uint32_t> light_cand;    // original ids of the candidates
+    std::vector<uint32_t> cand_blob;     // the blob index of each candidate (where its pa goes in d_pa)
+    std::vector<float> pa_span;          // host image of d_pa[cand_lo .. cand_hi], the only entries that can be non-zero
+    uint32_t cand_lo = 0, n_lights = 0;
+    ptrt::DevBuf<float4> d_lights;
+    ptrt::DevBuf<float> d_cdf, d_pa;
+};

@@ -226,6 +226,39 @@ def test_long_animation_and_recommit(P, pto, renderer):
         check_against_oracle(P, pto, renderer, cur, (width, build, "recommit"))
 
 
+def test_reads_between_updates_then_recommit_elsewhere(P, pto, renderer):
+    """The blob read before and between updates (the second of two reads in a row comes from the host copy the first one fetched), a
+    host update and a device update, then pt_scene_commit with another layout and the other builder: the commit builds from the
+    twice-moved vertices. A host-built target equals a fresh SetScene of those vertices byte for byte; an LBVH target validates and
+    renders the oracle's frame."""
+    import torch
+    N = P.native
+    L = N.PT_BVH_BUILD_LBVH
+    sd = _scenes(P)["tess"]
+    rng = np.random.default_rng(11)
+    v1 = deform(sd, rng, "large")
+    v2 = deform(moved(sd, v1), rng, "large")
+    for start, target in ((68 | L, 4), (68, 2), (2, 68 | L), (73, 68)):
+        ctx = (start, target)
+        renderer.SetScene(sd, start)
+        blob(renderer)
+        renderer.UpdateGeometry(verts=v1)
+        (_, nodes_a, tris_a), (_, nodes_b, tris_b) = blob(renderer), blob(renderer)
+        assert np.array_equal(nodes_a, nodes_b) and np.array_equal(tris_a, tris_b), ctx
+        renderer.UpdateGeometry(verts=torch.from_numpy(v2).cuda())
+        assert N.lib.pt_scene_commit(renderer._scene, target) == N.PT_OK, ctx
+        cur = moved(sd, v2)
+        check_against_oracle(P, pto, renderer, cur, ctx)
+        info, nodes, tris = blob(renderer)
+        assert info.width == target & ~L, ctx
+        if target & L:
+            continue  # (validate_bvh() == 0 and the oracle's frame: check_against_oracle)
+        renderer.SetScene(cur, target)
+        info1, nodes1, tris1 = blob(renderer)
+        assert np.array_equal(nodes, nodes1) and np.array_equal(tris, tris1), ctx
+        assert (info.n_nodes, info.max_depth, info.stack_need, info.sah_cost) == (info1.n_nodes, info1.max_depth, info1.stack_need, info1.sah_cost), ctx
+
+
 def test_refused_device_update_changes_nothing(P, pto, renderer):
     """A device array with one NaN is PT_ERR_INVALID_ARGUMENT, and the blob and the next frame equal those before the call; so are a
     device pointer that is not 4-byte aligned, host memory passed as device memory, and a wrong count."""
