@@ -1,4 +1,5 @@
-"""ctypes binding of libptrt.so (include/ptrt.h). Plumbing only: every symbol the header declares, nothing else.
+"""ctypes binding of libptrt.so (include/ptrt.h). Plumbing only: every symbol the header declares, and the test-only read-outs of
+csrc/scene.h (INTERNAL_SYMBOLS), nothing else.
 
 There is no fallback: if the HIP library is missing this module raises at import, and without a gfx950 device
 `pt_context_create` fails with PT_ERR_NO_DEVICE (the product path never routes through oracle/ or the CPU).
@@ -148,6 +149,15 @@ SYMBOLS = {
 
 for _name, (_res, _args) in SYMBOLS.items():
     _f = getattr(lib, _name)  # AttributeError here = the library does not export what the header declares
+    _f.restype = _res
+    _f.argtypes = _args
+
+# Not in include/ptrt.h and not part of the renderer API: entry points that csrc/scene.h exports for the test suite alone.
+INTERNAL_SYMBOLS = {
+    "pt_internal_lbvh_binary": (_st, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),  # ctx, verts9, n, order, left, right, first, last, box6
+}
+for _name, (_res, _args) in INTERNAL_SYMBOLS.items():
+    _f = getattr(lib, _name)
     _f.restype = _res
     _f.argtypes = _args
 

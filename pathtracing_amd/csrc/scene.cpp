@@ -549,4 +549,24 @@ pt_status pt_scene_update_spheres(pt_scene *s, const float *cxyzr, uint64_t coun
     return drained_on_failure(s ? s->ctx : nullptr, [&] { return update_spheres(s, cxyzr, count); });
 }
 
+// scene.h: the GPU builder's binary tree, for the tests
+pt_status pt_internal_lbvh_binary(pt_context *c, const float *verts9, uint64_t n, uint32_t *order, int32_t *left, int32_t *right,
+                                  uint32_t *first, uint32_t *last, float *box6)
+{
+    if (!c || !verts9 || !order || !left || !right || !first || !last || !box6) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_internal_lbvh_binary: NULL argument");
+    if (n < 2 || n >= (1ull << 28)) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_internal_lbvh_binary: %llu triangles, need 2 .. 2^28 - 1", (unsigned long long)n);
+    for (uint64_t i = 0; i < n * 9; ++i)
+        if (!std::isfinite(verts9[i])) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_internal_lbvh_binary: non-finite vertex coordinate at float %llu", (unsigned long long)i);
+    return drained_on_failure(c, [&]() -> pt_status {
+        HIP_TRY(c, hipSetDevice(context_device(c)));
+        BinaryBvh bt;
+        HIP_TRY(c, build_lbvh_device(context_stream(c), verts9, (uint32_t)n, bt));
+        std::memcpy(order, bt.order.data(), n * 4);
+        std::memcpy(left, bt.left.data(), (n - 1) * 4); std::memcpy(right, bt.right.data(), (n - 1) * 4);
+        std::memcpy(first, bt.first.data(), (n - 1) * 4); std::memcpy(last, bt.last.data(), (n - 1) * 4);
+        std::memcpy(box6, bt.box.data(), (n - 1) * 24);
+        return PT_OK;
+    });
+}
+
 } // extern "C"

@@ -145,3 +145,10 @@ struct pt_scene {
     ptrt::DevBuf<float4> d_lights;
     ptrt::DevBuf<float> d_cdf, d_pa;
 };
+
+// Not part of include/ptrt.h: the binary tree of build_lbvh_device, read out for the test suite (tests/test_gpu_lbvh.py compares it with a
+// plain reference). Runs on the context's stream; order[n], left/right/first/last[n - 1] and box6[6 * (n - 1)] are the fields of BinaryBvh.
+// PT_ERR_INVALID_ARGUMENT for n < 2, a NULL pointer and, as pt_scene_set_triangles refuses them before a commit, n >= 2^28 or a non-finite
+// coordinate.
+extern "C" pt_status pt_internal_lbvh_binary(pt_context *ctx, const float *verts9, uint64_t n, uint32_t *order, int32_t *left, int32_t *right,
+                                             uint32_t *first, uint32_t *last, float *box6);

@@ -1,7 +1,8 @@
 """The host builder's blobs, byte for byte: every scene of tests/golden/make_blob_digests.py under every node layout must still give
 the digests recorded in tests/golden/blob_digests.json (node bytes, triangle bytes, n_nodes, max_depth, stack_need, sah_cost bits).
 No device: detached scenes. The rules these bytes follow are stated once, in pathtracing_amd/csrc/blob_rules.h, for the host builder,
-the GPU builder and the refit; the GPU suite holds the latter two to the host's bytes (tests/test_gpu_update.py)."""
+the GPU builder and the refit; the GPU suite holds the GPU builder to a plain reference of its tree, leaves and info
+(tests/test_gpu_lbvh.py) and the refit to the host's and the commit's bytes (tests/test_gpu_update.py)."""
 import importlib.util
 import json
 import os

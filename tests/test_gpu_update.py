@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import ray_caster64 as rc
+from lbvh_ref import numpy_sah
 from test_gpu_trace import H, LAYOUTS, MISS, W, _scenes, ids_of, oracle, records
 
 pytestmark = pytest.mark.gpu
@@ -158,26 +159,6 @@ def test_spheres_move(P, pto, renderer):
         sph2[:, 1] += np.float32(0.1)
         renderer.UpdateGeometry(verts=v2, spheres=sph2)
         check_against_oracle(P, pto, renderer, moved(sd, v2, sph2), ("both", width))
-
-
-def numpy_sah(nodes, width):
-    """bvh_build.cpp emit_blob's cost restated on f32 slots: sum of f32(area / root area) (times the count for a leaf), in float64."""
-    n = width
-    slots = np.frombuffer(nodes.tobytes(), np.float32).reshape(-1, n, 8)
-    refs = slots[:, :, 3].view(np.int32)
-    lo, hi = slots[:, :, 0:3], slots[:, :, 4:7]
-
-    def area(lo, hi):
-        d = (hi - lo).astype(np.float32)
-        a = np.float32(2) * (d[..., 0] * d[..., 1] + d[..., 1] * d[..., 2] + d[..., 2] * d[..., 0])
-        return np.where(d[..., 0] < 0, np.float32(0), a).astype(np.float32)
-
-    used = refs != 0x7FFFFFFF
-    rlo, rhi = lo[0][used[0]].min(0), hi[0][used[0]].max(0)
-    ra = np.maximum(area(rlo, rhi), np.float32(1e-30))
-    cnt = np.where(refs < 0, (~refs & 7) + 1, 1).astype(np.float64)
-    q = (area(lo, hi) / ra).astype(np.float32).astype(np.float64)
-    return float((q * cnt)[used].sum())
 
 
 def test_topology_stable_and_sah(P, pto, renderer):
