@@ -1,5 +1,5 @@
 // blob_rules.h — the rules of the docs/SPEC.md §4.1 blob that more than one of its producers follows, stated once: the host SAH builder
-// (bvh_build.cpp, api.cpp), the GPU builder (lbvh.hip) and the refit (refit.hip) promise the same bytes for the same tree, and they get
+// (bvh_build.cpp, scene.cpp), the GPU builder (lbvh.hip) and the refit (refit.hip) promise the same bytes for the same tree, and they get
 // them by calling the same text. Plain C++ and device code both: bvh_build.cpp is compiled without HIP. Every operation has one
 // spelling that both sides compile to the same IEEE result on the finite numbers the builders see (-ffp-contract=off, correctly
 // rounded divide and sqrt): compiler builtins for fma, sqrt, floor, ceil, frexp and fabs, `<` and `?:` for min and max.

@@ -87,15 +87,22 @@ pt_status cfail(pt_comm *c, pt_status code, const char *fmt, ...)
 #define C_HIP(c, expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return cfail(c, PT_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); } while (0)
 #define C_NCCL(c, expr) do { ncclResult_t _r = (expr); if (_r != ncclSuccess) return cfail(c, PT_ERR_HIP, "%s failed: %s", #expr, g_rccl.GetErrorString(_r)); } while (0)
 
-// the gather buffer on the root's device, sized for `params`
-pt_status ensure_gathered(pt_comm *c, const pt_render_params *p, uint64_t &per_rank_floats)
+// A frame of `p` over the communicator's ranks: `q` = the root's view of it (what pt_assemble_tiles takes), and the floats of one rank's
+// block. `who` opens the error text.
+pt_status rank_block(pt_comm *c, const pt_render_params *p, const char *who, pt_render_params &q, uint64_t &per_rank_floats)
 {
-    pt_render_params q = *p;
+    q = *p;
     q.rank = 0; q.nranks = (uint32_t)c->ctx.size();
     pt_tile_layout lay;
     pt_status st = pt_tile_layout_query(&q, &lay);
-    if (st != PT_OK) return cfail(c, st, "pt_comm: bad render params");
+    if (st != PT_OK) return cfail(c, st, "%s: bad render params", who);
     per_rank_floats = (uint64_t)lay.tiles_per_rank * lay.floats_per_tile;
+    return PT_OK;
+}
+
+// the gather buffer on the root's device, sized for a rank's block
+pt_status ensure_gathered(pt_comm *c, uint64_t per_rank_floats)
+{
     const uint64_t need = per_rank_floats * c->ctx.size();
     if (need > c->gathered.n) {
         C_HIP(c, hipSetDevice(context_device(c->ctx[c->root])));
@@ -180,20 +187,16 @@ pt_status pt_comm_assemble(pt_comm *c, const pt_render_params *p)
     if (!c || !p) return cfail(c, PT_ERR_INVALID_ARGUMENT, "pt_comm_assemble: NULL argument");
     const uint32_t n = (uint32_t)c->ctx.size();
     uint64_t per_rank = 0;
-    pt_render_params q = *p;
-    q.rank = 0; q.nranks = n;
+    pt_render_params q;
     pt_context *root = c->ctx[c->root];
+    pt_status st = rank_block(c, p, c->shared ? "pt_comm_assemble" : "pt_comm", q, per_rank);
+    if (st != PT_OK) return st;
     if (c->shared) {
-        pt_tile_layout lay;
-        pt_status st = pt_tile_layout_query(&q, &lay);
-        if (st != PT_OK) return cfail(c, st, "pt_comm_assemble: bad render params");
-        per_rank = (uint64_t)lay.tiles_per_rank * lay.floats_per_tile;
         for (uint32_t i = 0; i < n; ++i) if (!c->staged[i]) return cfail(c, PT_ERR_NOT_COMMITTED, "pt_comm_assemble: rank %u was not staged (pt_comm_stage_tiles)", i);
         if (per_rank * n > c->gathered.n) return cfail(c, PT_ERR_INVALID_ARGUMENT, "pt_comm_assemble: params do not match the staged blocks");
         std::fill(c->staged.begin(), c->staged.end(), 0);
     } else {
-        pt_status st = ensure_gathered(c, p, per_rank);
-        if (st != PT_OK) return st;
+        if ((st = ensure_gathered(c, per_rank)) != PT_OK) return st;
         std::vector<void *> tiles(n);
         for (uint32_t i = 0; i < n; ++i) {
             uint64_t nf = 0;
@@ -235,7 +238,7 @@ pt_status pt_comm_assemble(pt_comm *c, const pt_render_params *p)
         }
     }
     // un-tile on the root: same stream as the root's receive, then the host waits (pt_assemble_tiles is synchronous)
-    pt_status st = pt_assemble_tiles(root, &q, c->gathered.p, per_rank * n);
+    st = pt_assemble_tiles(root, &q, c->gathered.p, per_rank * n);
     if (c->use_rccl) // the senders' halves of the gather: done once the root has received, waited for so that nothing outlives the call
         for (uint32_t i = 0; i < n; ++i)
             if (i != c->root) { (void)hipSetDevice(c->dev[i]); (void)hipStreamSynchronize(context_stream(c->ctx[i])); }

@@ -1,6 +1,6 @@
 // denoise.hip — pt_denoise (docs/SPEC.md §8) on gfx950: the first-hit guide buffers and the edge-aware à-trous filter.
 //
-//   k_guide_index   : original triangle id -> blob index, from every record's row 0 .w (once per commit; api.cpp caches it in the scene)
+//   k_guide_index   : original triangle id -> blob index, from every record's row 0 .w (once per commit; query.cpp caches it in the scene)
 //   k_guide_rays    : the unjittered §3 camera ray of every pixel, as a pt_trace_rays record; kernels.hip's k_trace then finds the hits
 //   k_guide_resolve : {t, prim id} -> g0 = (front-facing normal, t), g1 = (albedo, prim id bits): triangles read the record's shading
 //                     row, spheres the 1/r of sph_mat

@@ -1,0 +1,404 @@
+// frame.cpp — pt_render: the extend-kernel probe and the wavefront frame loop (plan, start, loops, finish) over the owners of context.h.
+// Stands where Renderer.ComputeFrame + the compute-fence wait stand in the reference (RayTracing/Graphics/Renderer.cs:1006-1040, 970-972).
+#include "scene.h"
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+using namespace ptrt;
+
+namespace {
+
+uint32_t host_pcg(uint32_t x)
+{
+    uint32_t s = x * 747796405u + 2891336453u;
+    uint32_t w = ((s >> ((s >> 28) + 4u)) ^ s) * 277803737u;
+    return (w >> 22) ^ w;
+}
+
+// Which extend kernel a frame runs. A frame's PT_FLAG_EXTEND_* beats pt_tuning.extend_kernel, which beats the scene's own choice, measured:
+//   inside a frame : iteration 2 of group 0 runs the one-ray-per-lane kernel, iteration 3 the lane-packing one (bit-identical results), each
+//                    bracketed by events; accepted only if both traced a real share of the frame's slots;
+//   across frames  : a frame too short for that (few samples per stream: it is over in two iterations) runs whole on one kernel — the first
+//                    on the one-ray-per-lane kernel, the next on the lane-packing one — and the rays per millisecond of the two frames decide.
+// The faster per ray wins (packed needs +10 %). Deep incoherent traversals (1M-triangle soup) gain ~2.5x from packing, shallow ones (walls of
+// a box) lose ~35 %, and no static property of the tree tells them apart. Counting / profiling frames neither probe nor feed
+// the decision: their kernels are instrumented builds. A probing frame runs one loop and no finish mode, so that its timed iterations compare.
+uint32_t faster(double rate_simple, double rate_packed) { return rate_packed > 1.10 * rate_simple ? EXT_PACKED : EXT_SIMPLE; }
+struct ExtendFrame {            // the choice during one frame
+    ExtendChoice &mem;
+    bool undecided;             // nothing forces a kernel and the scene has not picked one: this frame measures (whole, on frame_kernel)
+    uint32_t frame_kernel, kernel; // kernel: 0 = probing inside this frame, else the ExtendKernel every iteration uses
+    bool mixed = false;         // this frame ran probe iterations on both kernels: its overall rate says nothing about either
+    uint64_t probe_n[2] = { 0, 0 }; // rays traced by probe iterations 2 and 3
+    ExtendFrame(ExtendChoice &m, uint32_t forced, bool instrumented) : mem(m),
+        undecided(forced == 0u && m.kernel == 0u && !instrumented),
+        frame_kernel((undecided && m.rate_simple > 0.0 && m.rate_packed == 0.0) ? EXT_PACKED : EXT_SIMPLE), // first the default, then the other
+        kernel(forced ? forced : m.kernel ? m.kernel : (undecided && frame_kernel == EXT_SIMPLE) ? 0u : frame_kernel) {}
+    bool probing(uint32_t g, uint32_t it) const { return g == 0u && kernel == 0u && (it == 2u || it == 3u); }
+    int launch_kernel(uint32_t g, uint32_t it, bool split) const { return (kernel == EXT_PACKED || (probing(g, it) && it == 3u)) ? EXT_PACKED : (kernel == EXT_POOL && !split) ? EXT_POOL : EXT_SIMPLE; }
+    // default path vertices per launch. Lane-packing: a lane pulls a new entry whenever its budget ends, so a long budget costs nothing and saves
+    // launches (ms per frame with 8 / 16 / 32 / 64 vertices, tools/exp_packed.py: 1M soup 72.2 / 71.5 / 70.5 / 67.4, at 256 spp 277.6 / 271.8 /
+    // 268.3 / 266.1, 5k soup 7.99 / 7.43 / 7.35 / 7.39); the probe iteration keeps 8 so that it stays comparable with the one before it
+    uint32_t bounces(uint32_t g, uint32_t it, int k, uint32_t simple) const { return k != EXT_PACKED ? simple : probing(g, it) ? 8u : 64u; }
+    // loop g's readback of iteration `it`, which traced `traced` rays; by iteration 3's, both probe iterations and their events `ev` (start and
+    // end of each, pt_context::ev_probe) are complete
+    hipError_t observe(uint32_t g, uint32_t it, uint64_t traced, uint32_t loop_slots, const Event *ev)
+    {
+        if (!probing(g, it)) return hipSuccess;
+        probe_n[it - 2u] = traced;
+        if (it == 2u) return hipSuccess;
+        float ms_simple = 0.f, ms_packed = 0.f; hipError_t e = hipEventElapsedTime(&ms_simple, ev[0], ev[1]);
+        if (e != hipSuccess || (e = hipEventElapsedTime(&ms_packed, ev[2], ev[3])) != hipSuccess) return e;
+        const uint64_t enough = (uint64_t)loop_slots / 8u; // each probe iteration must have traced a real share of the slots
+        if (probe_n[0] < enough || probe_n[1] < enough) { // inconclusive (the frame was all but over): finish on the default, whole frames decide
+            kernel = EXT_SIMPLE; mixed = probe_n[1] >= enough / 8u; // did the lane-packing iteration trace enough to colour this frame's rate?
+        } else kernel = mem.kernel = faster(probe_n[0] / std::max((double)ms_simple, 1e-6), probe_n[1] / std::max((double)ms_packed, 1e-6));
+        return hipSuccess;
+    }
+    // the whole frame: a warm one (cold = it had to allocate: first touch of fresh memory is 30 % slower, not a measurement) on one
+    // kernel of at least 2^20 rays gives that kernel's rate
+    void frame_done(uint64_t rays, double gpu_ms, bool cold)
+    {
+        if (!undecided || mem.kernel != 0u || cold) return;
+        if (mixed || rays < (1u << 20) || !(gpu_ms > 0.0)) { if (++mem.misses >= 3u) mem.kernel = EXT_SIMPLE; return; }
+        (frame_kernel == EXT_PACKED ? mem.rate_packed : mem.rate_simple) = (double)rays / gpu_ms;
+        if (mem.rate_simple > 0.0 && mem.rate_packed > 0.0) mem.kernel = faster(mem.rate_simple, mem.rate_packed);
+    }
+};
+
+hipEvent_t pool_event(pt_context *c, size_t i)
+{
+    while (c->ev_pool.size() <= i) {
+        Event e;
+        if (e.create() != hipSuccess) return nullptr;
+        c->ev_pool.push_back(std::move(e));
+    }
+    return c->ev_pool[i];
+}
+
+struct Frame {                  // a path-traced frame as plan_frame lays it out, and what its loops leave for finish_frame
+    uint32_t nranks, streams, pixel_slots, n_slots, shard_cap, samples_per_stream, lag, n_loops, packed_chunk, default_bounces;
+    uint32_t forced;            // ExtendKernel a frame flag or pt_tuning.extend_kernel forces (0 = none)
+    bool profile, count, split, bucket, full_state, accumulate, mapped, compact;
+    bool nee;                   // PT_FLAG_NEXT_EVENT (docs/SPEC.md §7): the one-ray-per-lane kernel with light samples
+    NeeArgs nee_args;
+    Accumulation::Key sums_key; // what the sums hold once this frame completes
+    size_t q_entries; uint64_t total_spp, allocs_before;
+    PathState ps; FrameParams fp;
+    uint32_t iters; uint64_t slot_launches; size_t n_events; // launches of the longest loop, paths alive at launch starts, profile events
+    std::vector<uint64_t> trace_alive, trace_rays;
+};
+
+} // namespace
+
+// (the frame's stream `q`; ps and fp are the frame's, with the template's own queue and counter block put in place of the frame's)
+pt_status FrameTemplate::build_if_differs(pt_context *c, hipStream_t q, Key key, const DeviceScene &ds, const PathState &ps, const FrameParams &fp,
+                                          const QueueSizes &sizes)
+{
+    key.q = q_init.p;
+    if (valid && key == key_) return PT_OK;
+    valid = false; HIP_TRY(c, hipMemsetAsync(cnt_init.p, 0, sizeof(uint32_t) * kCntTotalWords, q));
+    PathState pt = ps; pt.counters = cnt_init.p; pt.q_ext[0] = q_init.p;
+    // whole streams without a sample (spp < streams): the first queue holds the live slots only, and the first launch is sized by it
+    const bool dense = key.first_spp < key.streams;
+    HIP_TRY(c, launch_generate(q, ds, pt, fp, dense ? 2u : 0u)); // also zeroes every slot's sum unless the frame accumulates
+    bound = key.shard_cap;
+    if (dense) {
+        uint32_t *h = sizes.template_sizes();
+        HIP_TRY(c, hipMemcpyAsync(h, cnt_init.p, sizeof(uint32_t) * kShards * kCounterStride, hipMemcpyDeviceToHost, q));
+        HIP_TRY(c, hipStreamSynchronize(q));
+        bound = 0;
+        for (uint32_t sh = 0; sh < kShards; ++sh) bound = std::max(bound, h[cnt_ext_index(0, sh)]);
+    }
+    key_ = key; valid = true;
+    return PT_OK;
+}
+
+// Plan: validate, derive the frame's geometry and decoded flags, allocate what the frame uses, fill PathState and FrameParams
+static pt_status plan_frame(pt_context *c, const pt_scene *s, const pt_render_params *p, const pt_tile_layout &lay, Frame &f)
+{
+    if (!s) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_render: scene is NULL");
+    if (s->ctx != c) return fail(c, PT_ERR_INVALID_ARGUMENT, "scene belongs to another context");
+    if (!s->committed) return fail(c, PT_ERR_NOT_COMMITTED, "scene not committed");
+    if (p->spp == 0 || p->spp >= (1u << 24)) return fail(c, PT_ERR_INVALID_ARGUMENT, "spp must be in [1, 2^24)");
+    if (p->max_depth == 0 || p->max_depth > 255) return fail(c, PT_ERR_INVALID_ARGUMENT, "max_depth must be in [1,255]");
+    if (!std::isfinite(p->ray_eps) || p->ray_eps < 0.f) return fail(c, PT_ERR_INVALID_ARGUMENT, "ray_eps must be finite and >= 0");
+    if (p->streams > 64) return fail(c, PT_ERR_INVALID_ARGUMENT, "streams must be in [0,64]");
+    const pt_tuning &t = c->tuning;
+    f.nranks = p->nranks ? p->nranks : 1u; f.streams = p->streams ? p->streams : 1u;
+    f.pixel_slots = lay.tiles_per_rank * kTilePixels;                  // one slot per owned pixel ...
+    const uint64_t slots64 = (uint64_t)f.pixel_slots * f.streams;      // ... per sample stream
+    if (slots64 >= (1ull << 28)) return fail(c, PT_ERR_UNSUPPORTED, "frame too large: %llu slots (pixels of this rank x streams), limit 2^28", (unsigned long long)slots64); // kernels.hip at(): 32-bit byte offsets
+    f.n_slots = (uint32_t)slots64;
+    // every queue = kShards regions of shard_cap entries, one per shard. k_generate deals the 2^kShardGroupShift-slot groups out in
+    // rotation: entry group t of shard s starts as slot group t * kShards + (s - t) mod kShards, so a shard owns ceil(groups / kShards)
+    const uint32_t groups = (f.n_slots + (1u << kShardGroupShift) - 1u) >> kShardGroupShift, shard_cap = ((groups + kShards - 1) / kShards) << kShardGroupShift;
+    f.shard_cap = shard_cap; f.q_entries = (size_t)kShards * shard_cap;
+    f.samples_per_stream = (p->spp + f.streams - 1u) / f.streams;
+    f.profile = (p->flags & PT_FLAG_PROFILE_KERNELS) != 0; f.count = (p->flags & PT_FLAG_COUNT_VISITS) != 0;
+    f.bucket = (p->flags & PT_FLAG_BUCKET_SPECULAR) != 0; f.split = f.bucket || (p->flags & PT_FLAG_SPLIT_KERNELS) != 0;
+    f.forced = (p->flags & PT_FLAG_EXTEND_POOL) ? (uint32_t)EXT_POOL : (p->flags & PT_FLAG_EXTEND_PACKED) ? (uint32_t)EXT_PACKED
+               : (p->flags & PT_FLAG_EXTEND_SIMPLE) ? (uint32_t)EXT_SIMPLE : t.extend_kernel;
+    // next-event estimation lives in the fused one-ray-per-lane kernel only. Its frames neither probe the extend kernel nor feed the
+    // scene's choice (a forced kernel does neither), and they have no visit counters: a shadow ray's traversal stops at its tmax, which
+    // §4.1's counters do not describe.
+    f.nee = (p->flags & PT_FLAG_NEXT_EVENT) != 0;
+    if (f.nee) {
+        if (f.split || f.forced == (uint32_t)EXT_PACKED || f.forced == (uint32_t)EXT_POOL)
+            return fail(c, PT_ERR_UNSUPPORTED, "PT_FLAG_NEXT_EVENT runs on the one-ray-per-lane kernel only: not with PT_FLAG_EXTEND_PACKED, "
+                                               "PT_FLAG_EXTEND_POOL, PT_FLAG_SPLIT_KERNELS, PT_FLAG_BUCKET_SPECULAR or pt_tuning.extend_kernel 2 / 3");
+        if (f.count) return fail(c, PT_ERR_UNSUPPORTED, "PT_FLAG_NEXT_EVENT does not count visits (PT_FLAG_COUNT_VISITS)");
+        f.forced = EXT_SIMPLE;
+    }
+    // the fused one-ray-per-lane and lane-packing kernels build a slot's initial state in registers in their first launch; k_shade
+    // (split pipelines) and the pooled kernel read it from memory
+    f.full_state = f.split || f.forced == (uint32_t)EXT_POOL;
+    f.mapped = t.readback == 0u; // queue sizes reach the host by the kernels' own stores (fold_traced) instead of a copy per launch
+    // rays per wavefront of the lane-packing kernel: 256 once several sample streams keep the queues long, else 128 (measured)
+    f.packed_chunk = t.packed_chunk >= 64u ? t.packed_chunk : (f.streams >= 4u ? 256u : 128u);
+    // path vertices per launch of the one-ray-per-lane kernel: 3/4 max_depth - 2 (saturating), clamped to [4, 12]
+    const uint32_t v34 = p->max_depth * 3u / 4u; f.default_bounces = std::min(12u, std::max(4u, v34 > 2u ? v34 - 2u : 0u));
+    // NEE: `bounces` counts rays, and a vertex with a light sample takes two (shadow, then extension): twice the passes for about as many
+    // vertices per launch
+    if (f.nee) f.default_bounces *= 2u;
+    // Iterations the host runs ahead of the queue sizes it reads back (pt_tuning.lag). The frame ends `lag` launches after its last path, on
+    // grids sized `lag` iterations ago: short frames feel that (ms per 1080p frame with lag 4 / 3 / 2, tools/exp_lag.py: 1 spp 0.567 / 0.537 /
+    // 0.529, 8 spp 2.79 / 2.73 / 2.70, glass 8 spp 1.57 / 1.52 / 1.48), long ones not (64 spp 17.73 / 17.68 / 17.73; a rank's 1/8 2.63 / 2.59 /
+    // 2.61), and the lane-packing kernel's short tail launches want the host further ahead (soup 72.3 / 72.4 / 73.1). At least 2: the launch
+    // after the last one that had paths clears that one's counter line. With the sizes stored by the kernels themselves (pt_tuning.readback =
+    // 0) iteration j's line is written by launch j + 1, so the same run-ahead of the GPU takes one more iteration of lag than with a copy.
+    f.lag = t.lag ? t.lag : (f.samples_per_stream <= 2u ? 2u : 3u) + (f.mapped ? 1u : 0u);
+    // progressive accumulation (the reference re-renders every frame, App.cs:39-42; this is its converging analogue):
+    // keep the stream partials of the previous call(s) and divide by the total number of samples at the end
+    f.accumulate = (p->flags & PT_FLAG_ACCUMULATE) != 0;
+    f.sums_key = Accumulation::Key{ p->width, p->height, p->rank, f.nranks, f.streams, p->seed, f.nee };
+    if (f.accumulate)
+        switch (c->sums.continues(f.sums_key, p->sample_offset)) {
+        case Accumulation::Refusal::other_frame:
+            return fail(c, PT_ERR_INVALID_ARGUMENT, "PT_FLAG_ACCUMULATE needs a previous frame with the same size, rank, nranks, streams and seed");
+        case Accumulation::Refusal::other_estimator:
+            return fail(c, PT_ERR_INVALID_ARGUMENT, "PT_FLAG_ACCUMULATE: the sums so far were made %s PT_FLAG_NEXT_EVENT", c->sums.next_event() ? "with" : "without");
+        case Accumulation::Refusal::wrong_offset:
+            return fail(c, PT_ERR_INVALID_ARGUMENT, "PT_FLAG_ACCUMULATE: sample_offset must be %llu (samples so far)", (unsigned long long)c->sums.samples());
+        case Accumulation::Refusal::none: break;
+        }
+    f.total_spp = (f.accumulate ? c->sums.samples() : 0u) + p->spp; c->sums.begin(); // the sums: invalid until this frame completes
+    f.allocs_before = g_device_allocs;
+    HIP_TRY(c, c->ray_o.ensure(f.n_slots)); HIP_TRY(c, c->ray_d.ensure(f.n_slots)); HIP_TRY(c, c->thr.ensure(f.n_slots));
+    HIP_TRY(c, c->acc.ensure(f.n_slots)); HIP_TRY(c, c->out.tiles.ensure(f.pixel_slots)); HIP_TRY(c, c->sd.ensure(f.n_slots));
+    HIP_TRY(c, c->q_ext0.ensure(f.q_entries)); HIP_TRY(c, c->q_ext1.ensure(f.q_entries));
+    // hit records and the metal / dielectric buckets are k_shade's (no kernel indexes the miss and Lambert buckets)
+    if (f.split) { HIP_TRY(c, c->hit.ensure(f.n_slots)); HIP_TRY(c, c->q_metal.ensure(f.q_entries)); HIP_TRY(c, c->q_dielectric.ensure(f.q_entries)); }
+    if (!f.full_state) HIP_TRY(c, c->start.reserve(f.q_entries));
+    const uint32_t ovf = s->tree.stack_overflow();
+    if (ovf) HIP_TRY(c, c->stack_ovf.ensure((size_t)ovf * f.q_entries));
+    if (f.nee) {
+        HIP_TRY(c, c->nee_ext.ensure(f.n_slots)); HIP_TRY(c, c->nee_rad.ensure(f.n_slots));
+        f.nee_args = NeeArgs{ s->d_lights.p, s->d_cdf.p, s->d_pa.p, s->n_lights, c->nee_ext.p, c->nee_rad.p };
+    }
+    if (f.nranks == 1) HIP_TRY(c, c->out.resize(p->width, p->height));
+    PathState &ps = f.ps;
+    ps.ray_o = c->ray_o.p; ps.ray_d = c->ray_d.p; ps.thr = c->thr.p; ps.sd = c->sd.p; ps.acc = c->acc.p; ps.q_ext[0] = c->q_ext0.p; ps.q_ext[1] = c->q_ext1.p;
+    if (f.split) { ps.hit = c->hit.p; ps.q_bucket[B_METAL] = c->q_metal.p; ps.q_bucket[B_DIELECTRIC] = c->q_dielectric.p; }
+    ps.counters = c->counters.p; ps.stack_ovf = c->stack_ovf.p; ps.stack_ovf_entries = ovf; ps.n_slots = f.n_slots; ps.shard_cap = f.shard_cap;
+    ps.shard_base = 0; ps.shard_count = kShards; ps.compact_below = t.compact_below; ps.finish_below = t.finish_below; ps.sparse_below = t.sparse_below;
+    ps.repack_sticky = (f.samples_per_stream <= t.sticky_samples && t.compact_below > 0.f) ? 1u : 0u;
+    ps.host_ring = c->sizes.begin(f.mapped); ps.ring_slots = kLag;
+    // re-packing forced: buckets re-append (no fixed positions), or next to nothing regenerates (every launch leaves holes)
+    f.compact = f.bucket || (ps.repack_sticky && f.samples_per_stream <= 2u);
+    FrameParams &fp = f.fp;
+    fp.width = p->width; fp.height = p->height; fp.spp = p->spp; fp.max_depth = p->max_depth; fp.rr_start = p->rr_start;
+    fp.seed_hashed = host_pcg(p->seed); fp.sample_offset = p->sample_offset; fp.ray_eps = p->ray_eps;
+    fp.rank = p->rank; fp.nranks = f.nranks; fp.tiles_x = lay.tiles_x; fp.n_tiles = lay.n_tiles; fp.streams = f.streams; fp.slots_per_stream = f.pixel_slots;
+    div_magic(f.streams, fp.streams_magic, fp.streams_shift); div_magic(lay.tiles_x, fp.tiles_x_magic, fp.tiles_x_shift);
+    fp.offset_mod = p->sample_offset % f.streams; fp.accumulate = f.accumulate ? 1u : 0u;
+    return PT_OK;
+}
+
+// Start: the first extend queue and counter block, after ev_start. A full-state frame runs k_generate over every slot; a fused one copies the
+// template of its geometry (context.h FrameTemplate: k_generate's output depends on which slots exist and on whether every stream has a sample).
+static pt_status start_frame(pt_context *c, const pt_scene *s, const pt_render_params *p, const Frame &f)
+{
+    hipStream_t q = c->stream;
+    if (f.full_state) {
+        HIP_TRY(c, hipMemsetAsync(c->counters.p, 0, sizeof(uint32_t) * kCntTotalWords, q));
+        HIP_TRY(c, hipEventRecord(c->ev_start, q));
+        HIP_TRY(c, launch_generate(q, s->ds, f.ps, f.fp, 1u));
+    } else {
+        HIP_TRY(c, hipEventRecord(c->ev_start, q));
+        FrameTemplate::Key key{};
+        key.w = p->width; key.h = p->height; key.rank = p->rank; key.nranks = f.nranks; key.streams = f.streams; key.first_spp = std::min(p->spp, f.streams);
+        key.offset = f.fp.offset_mod; key.n_slots = f.n_slots; key.shard_cap = f.shard_cap; key.acc = c->acc.p;
+        const pt_status st = c->start.build_if_differs(c, q, key, s->ds, f.ps, f.fp, c->sizes);
+        if (st != PT_OK) return st;
+        HIP_TRY(c, hipMemcpyAsync(c->counters.p, c->start.counters(), sizeof(uint32_t) * kCntTotalWords, hipMemcpyDeviceToDevice, q));
+    }
+    c->start.frame_ran(f.accumulate || f.full_state); // the template invariant: this frame writes the streams a dense template leaves out
+    return PT_OK;
+}
+
+// Loops. Shards never exchange slots, so the 64 shards are split into `n_loops` independent loops, each on its own HIP stream: the tail of one
+// group's launch (its last wavefronts draining) is filled by the other's launch (pt_tuning.loops has the measurements). Inside a loop a shard's
+// queue can only shrink (slots die, none are born), so the queue sizes read back `lag` iterations ago are valid launch bounds: the host never
+// stalls the GPU to size a grid. Queues are carried over IN PLACE from one iteration to the next: a lane writes its own queue position, dead
+// paths leave holes, and lane <-> slot stays the generation order, so the slot-indexed state keeps its coalescing and no returning atomic is
+// needed. A shard re-packs its survivors (ballot + atomic append) in the iteration in which its alive/length ratio is below `compact_below`,
+// and runs its last `finish_below` paths to their end in one launch; both are decided by the kernels from the shard's counters, the host only
+// sizes grids and notices the end.
+static pt_status run_loops(pt_context *c, const pt_scene *s, const pt_render_params *p, Frame &f, ExtendFrame &x)
+{
+    hipStream_t q = c->stream; const uint32_t n_loops = f.n_loops, per_group = kShards / n_loops;
+    struct Loop { hipStream_t stream; uint32_t base, bound, iters; bool done; } loops[kMaxGroups];
+    HIP_TRY(c, hipEventRecord(c->ev_fork, q));
+    for (uint32_t g = 0; g < n_loops; ++g) {
+        loops[g] = Loop{ n_loops == 1 ? q : c->group_stream[g], g * per_group, f.full_state ? f.shard_cap : c->start.first_bound(), 0u, false }; // no shard's queue can outgrow its first one
+        if (loops[g].stream != q) HIP_TRY(c, hipStreamWaitEvent(loops[g].stream, c->ev_fork, 0));
+    }
+    const uint64_t max_iters = (uint64_t)p->spp * p->max_depth * (f.nee ? 2u : 1u) + kLag + 2; // NEE: up to two rays per vertex
+    const bool trace = f.profile && getenv("PTRT_TRACE") != nullptr; // developer aid: per-iteration table on stderr
+    // One kernel per iteration by default: every extend kernel (one ray per lane, lane-packing, pooled) shades its own hits (mode 0:
+    // Lambert-only scene, lean code; 2: all kinds). PT_FLAG_SPLIT_KERNELS / _BUCKET_SPECULAR run k_shade as a second kernel.
+    const int shade_mode = s->has_specular ? 2 : 0;
+    for (uint32_t live = n_loops; live > 0;) {
+        for (uint32_t g = 0; g < n_loops; ++g) {
+            Loop &L = loops[g];
+            if (L.done) continue;
+            if (L.iters >= max_iters) return fail(c, PT_ERR_INTERNAL, "wavefront loop did not drain after %u iterations", L.iters);
+            const uint32_t it = L.iters; PathState pg = f.ps; pg.shard_base = L.base; pg.shard_count = per_group;
+            if (it == 0u && !f.full_state) pg.q_ext[0] = c->start.first_queue(); // the frame's first queue is the template: read, never written
+            if (x.kernel == 0u) pg.finish_below = 0u; // probing: no finish mode
+            hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+            if (f.profile) {
+                e0 = pool_event(c, f.n_events++); e1 = pool_event(c, f.n_events++); e2 = pool_event(c, f.n_events++);
+                if (!e0 || !e1 || !e2) return fail(c, PT_ERR_HIP, "hipEventCreate failed"); // (the text this failure has always had)
+                HIP_TRY(c, hipEventRecord(e0, L.stream));
+            }
+            const bool probing = x.probing(g, it); const int kernel = x.launch_kernel(g, it, f.split);
+            if (probing) HIP_TRY(c, hipEventRecord(c->ev_probe[(it - 2u) * 2u], L.stream));
+            HIP_TRY(c, launch_extend(L.stream, s->ds, pg, f.fp, it, L.bound, f.count, kernel, f.packed_chunk, f.split ? -1 : shade_mode, f.compact,
+                                     c->tuning.bounces ? c->tuning.bounces : x.bounces(g, it, kernel, f.default_bounces), f.nee ? &f.nee_args : nullptr));
+            if (f.profile) HIP_TRY(c, hipEventRecord(e1, L.stream));
+            if (f.bucket) {
+                HIP_TRY(c, launch_shade(L.stream, s->ds, pg, f.fp, it, L.bound, 0, true));
+                HIP_TRY(c, launch_shade(L.stream, s->ds, pg, f.fp, it, L.bound, 1, true)); // metal + dielectric buckets
+            } else if (f.split) HIP_TRY(c, launch_shade(L.stream, s->ds, pg, f.fp, it, L.bound, shade_mode, f.compact));
+            if (probing) HIP_TRY(c, hipEventRecord(c->ev_probe[(it - 2u) * 2u + 1u], L.stream)); // the whole iteration, either way
+            if (f.profile) HIP_TRY(c, hipEventRecord(e2, L.stream));
+            HIP_TRY(c, c->sizes.post(L.stream, g, it, c->counters.p + cnt_ext_index((it + 1u) % 3u, L.base), per_group));
+            f.iters = std::max(f.iters, ++L.iters);
+            if (L.iters < f.lag) continue;
+            const uint32_t old_iter = L.iters - f.lag; // iteration old_iter traced `traced` rays and left `total` paths alive: its survivors bound every later queue
+            QueueSizes::Sizes left;
+            HIP_TRY(c, c->sizes.wait(g, old_iter, L.base, per_group, left));
+            const uint64_t total = left.alive, traced = left.traced;
+            L.bound = left.longest;
+            if (trace) {
+                f.trace_alive.resize(std::max<size_t>(f.trace_alive.size(), old_iter + 1), 0); f.trace_rays.resize(f.trace_alive.size(), 0);
+                f.trace_alive[old_iter] += total; f.trace_rays[old_iter] += traced;
+            }
+            f.slot_launches += total; // = paths alive at the start of iteration old_iter + 1 (those read after the loop ended are all 0)
+            if (total == 0) { L.done = true; --live; }
+            HIP_TRY(c, x.observe(g, old_iter, traced, f.n_slots / n_loops, c->ev_probe));
+        }
+    }
+    for (uint32_t g = 0; g < n_loops; ++g) // join: the main stream continues after every group's last kernel
+        if (loops[g].stream != q) { HIP_TRY(c, hipEventRecord(c->ev_join[g], loops[g].stream)); HIP_TRY(c, hipStreamWaitEvent(q, c->ev_join[g], 0)); }
+    return PT_OK;
+}
+
+// Finish: reduce the streams and assemble, read every counter back, check that the frame ended clean, fill pt_stats
+static pt_status finish_frame(pt_context *c, const pt_render_params *p, const Frame &f, ExtendFrame &x, pt_stats *stats)
+{
+    hipStream_t q = c->stream; const FrameParams &fp = f.fp;
+    HIP_TRY(c, launch_reduce_streams(q, c->acc.p, c->out.tiles.p, f.pixel_slots, f.streams)); // tiles = the pixel sums = the gather payload
+    if (f.nranks == 1)
+        HIP_TRY(c, launch_assemble(q, c->out.tiles.p, 1, f.pixel_slots, p->width, p->height, fp.tiles_x, fp.n_tiles, 1.0f / (float)f.total_spp, c->out.fb.p, c->out.fb8.p));
+    HIP_TRY(c, hipEventRecord(c->ev_stop, q));
+    HIP_TRY(c, hipMemcpyAsync(c->sizes.frame_end(), c->counters.p, sizeof(uint32_t) * kCntTotalWords, hipMemcpyDeviceToHost, q));
+    HIP_TRY(c, hipStreamSynchronize(q));
+    pt_stats out{}; const CounterView hc{ c->sizes.frame_end(), 0u };
+    if (hc.error()) return fail(c, PT_ERR_INTERNAL, "device error flag 0x%x (1 = traversal stack overflow, 2 = step limit)", hc.error());
+    for (uint32_t sh = 0; sh < kShards; ++sh) {
+        if (hc.word(cnt_alive_index(0, sh)) || hc.word(cnt_alive_index(1, sh)) || hc.word(cnt_alive_index(2, sh))) return fail(c, PT_ERR_INTERNAL, "extend queue of shard %u not empty at frame end", sh);
+        out.rays += hc.u64(cnt_rays_index(sh));
+    }
+    float ms = 0.f; HIP_TRY(c, hipEventElapsedTime(&ms, c->ev_start, c->ev_stop)); out.gpu_ms = ms;
+    out.node_visits = hc.u64(kCntNodes); out.tri_tests = hc.u64(kCntTris); out.sphere_tests = hc.u64(kCntSph);
+    // PT_FLAG_COUNT_VISITS + one-ray-per-lane kernel: wave-level node-loop iterations (bits 0-39) and, from bit 40 up, how many
+    // of them came after the wave's first leaf phase of the ray (diagnostic for tools/exp_util.py)
+    out.reserved[3] = (hc.u64(kCntWaveNodeIters) & 0xFFFFFFFFFFull) | (hc.u64(kCntWaveNodeIters + 2) << 40);
+    if (f.count && getenv("PTRT_TRACE")) { // developer aid: where the node loop's lane-slots go (one-ray-per-lane kernel)
+        const double slots = 64.0 * (double)hc.u64(kCntWaveNodeIters), v = (double)out.node_visits, lf = (double)hc.u64(kCntIdleLeaf), dn = (double)hc.u64(kCntIdleDone);
+        if (slots > 0) fprintf(stderr, "ptrt: node-loop lane-slots %.3g: visiting %.1f %%, waiting at a leaf %.1f %%, ray finished %.1f %%, no ray %.1f %%\n", slots,
+                               100 * v / slots, 100 * lf / slots, 100 * dn / slots, 100 * (slots - v - lf - dn) / slots);
+    }
+    out.iterations = f.iters; out.extend_launches = f.iters;
+    x.frame_done(out.rays, out.gpu_ms, g_device_allocs != f.allocs_before);
+    out.reserved[0] = x.kernel ? x.kernel : (uint32_t)EXT_SIMPLE; // extend kernel in use at frame end (ExtendKernel)
+    out.reserved[1] = hc.word(kCntCompactions); // (shard, iteration) pairs that re-packed their queue (the others carried it over in place)
+    uint64_t px = 0; // paths = owned in-image pixels x spp
+    for (uint32_t t = p->rank; t < fp.n_tiles; t += f.nranks) {
+        const uint32_t tx = t % fp.tiles_x, ty = t / fp.tiles_x;
+        px += (uint64_t)std::min(kTile, p->width - tx * kTile) * std::min(kTile, p->height - ty * kTile);
+    }
+    out.paths = px * p->spp;
+    // path states read + written by the wavefront loop = sum over launches of the paths alive at launch start
+    // (iteration 0 starts every (pixel, stream) pair that has a sample)
+    out.reserved[2] = f.slot_launches + px * std::min(f.streams, p->spp);
+    if (f.profile) {
+        const bool trace = getenv("PTRT_TRACE") != nullptr;
+        for (size_t i = 0; i + 2 < f.n_events; i += 3) { // three events per iteration: before extend, between, after shade
+            float a = 0.f, b = 0.f; HIP_TRY(c, hipEventElapsedTime(&a, c->ev_pool[i], c->ev_pool[i + 1]));
+            HIP_TRY(c, hipEventElapsedTime(&b, c->ev_pool[i + 1], c->ev_pool[i + 2]));
+            out.extend_ms += a; out.shade_ms += b;
+            if (trace) fprintf(stderr, "ptrt: iteration %3zu  rays %10llu  alive after %10llu  extend %8.3f ms  shade %8.3f ms\n", i / 3,
+                               (unsigned long long)(i / 3 < f.trace_rays.size() ? f.trace_rays[i / 3] : 0),
+                               (unsigned long long)(i / 3 < f.trace_alive.size() ? f.trace_alive[i / 3] : 0), a, b);
+        }
+        out.other_ms = out.gpu_ms - out.extend_ms - out.shade_ms;
+    }
+    c->out.tiles_hold(f.pixel_slots); c->sums.complete(f.sums_key, f.total_spp);
+    if (f.nranks == 1) c->out.complete(FrameOutputs::Holds::path_traced);
+    if (stats) *stats = out;
+    return PT_OK;
+}
+
+static pt_status render_frame(pt_context *c, const pt_scene *s, const pt_render_params *p, pt_stats *stats)
+{
+    if (!c || !p) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_render: NULL argument");
+    pt_tile_layout lay; pt_status st = layout_of(p, &lay);
+    if (st != PT_OK) return fail(c, st, "pt_render: bad width/height/rank/nranks/tile_size");
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->out.replace(); // the denoised results belong to the frame this call replaces
+    if (p->mode == PT_REFERENCE_SPHERE) { // Renderer.ComputeFrame: one dispatch, then the host blocks on the fence (Renderer.cs:1020,1036,972)
+        HIP_TRY(c, c->out.resize(p->width, p->height));
+        HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
+        HIP_TRY(c, launch_reference_sphere(c->stream, p->width, p->height, c->out.fb.p, c->out.fb8.p));
+        HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        float ms = 0.f; HIP_TRY(c, hipEventElapsedTime(&ms, c->ev_start, c->ev_stop));
+        pt_stats out{};
+        out.gpu_ms = ms; out.other_ms = ms; out.rays = out.paths = (uint64_t)p->width * p->height; out.iterations = 1;
+        c->out.complete(FrameOutputs::Holds::reference_sphere); if (stats) *stats = out;
+        return PT_OK;
+    }
+    if (p->mode != PT_PATH_TRACE) return fail(c, PT_ERR_INVALID_ARGUMENT, "unknown mode %u", p->mode);
+    Frame f{};
+    if ((st = plan_frame(c, s, p, lay, f)) != PT_OK) return st;
+    ExtendFrame x(s->cache.ext, f.forced, f.count || f.profile);
+    f.n_loops = (f.profile || f.count || x.kernel == 0u) ? 1u : c->tuning.loops ? c->tuning.loops : 2u; // timed kernels run alone
+    if ((st = start_frame(c, s, p, f)) != PT_OK || (st = run_loops(c, s, p, f, x)) != PT_OK) return st;
+    return finish_frame(c, p, f, x, stats);
+}
+
+extern "C" pt_status pt_render(pt_context *c, const pt_scene *s, const pt_render_params *p, pt_stats *stats)
+{
+    const pt_status st = drained_on_failure(c, [&] { return render_frame(c, s, p, stats); });
+    if (st != PT_OK && c) { c->sums.begin(); c->out.lost(); } // nothing of this frame survives the call
+    return st;
+}

@@ -306,7 +306,7 @@ __global__ void __launch_bounds__(256) k_depth(const uint8_t *__restrict__ nodes
     need[base + q] = (k ? k - 1 : 0) + nmax;
 }
 
-// the device triangle record (one 64-byte line, Morton order): blob_rules.h tri_record, as api.cpp makes it for the host-built trees
+// the device triangle record (one 64-byte line, Morton order): blob_rules.h tri_record, as scene.cpp makes it for the host-built trees
 __global__ void __launch_bounds__(256) k_tri_records(const float *__restrict__ verts, const uint32_t *__restrict__ mats, const uint32_t *__restrict__ order, uint32_t n,
                                                      float4 *__restrict__ rec)
 {

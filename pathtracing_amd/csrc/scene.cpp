@@ -1,5 +1,5 @@
 // scene.cpp — the scene half of the C ABI (include/ptrt.h): pt_scene's contents, pt_scene_commit in phases, the blob read-back, geometry
-// updates; and the two owners of scene.h. pt_scene_destroy stands beside pt_context_destroy in api.cpp.
+// updates; and the two owners of scene.h.
 #include "scene.h"
 #include "refit.h"
 #include <hip/hip_runtime.h>
@@ -199,6 +199,13 @@ pt_status pt_scene_create(pt_context *ctx, pt_scene **out)
     s->ctx = ctx;
     *out = s;
     return PT_OK;
+}
+
+void pt_scene_destroy(pt_scene *s)
+{
+    if (!s) return;
+    if (s->ctx) { (void)hipSetDevice(s->ctx->device); (void)hipStreamSynchronize(s->ctx->stream); }
+    delete s;
 }
 
 pt_status pt_scene_set_triangles(pt_scene *s, const float *verts9, const uint32_t *material_ids, uint64_t count)

@@ -1,37 +1,13 @@
 // scene.h — pt_scene, and one owner each for the two things a committed scene keeps on both sides of the bus: its tree and its
-// vertices. Which copy is current is private to the owner; nobody else keeps a flag about it. Private to api.cpp and scene.cpp, as
-// are the helpers every public call uses (defined once, in api.cpp).
+// vertices. Which copy is current is private to the owner; nobody else keeps a flag about it. Private to scene.cpp, frame.cpp and
+// query.cpp; the context a scene belongs to and the helpers every public call uses are context.h's.
 #pragma once
-#include "ptrt_internal.h"
+#include "context.h"
 #include "bvh_build.h"
 #include "blob_rules.h"
-#include "device_owner.h"
 #include <vector>
 
 namespace ptrt {
-
-pt_status fail(pt_context *ctx, pt_status code, const char *fmt, ...); // sets the context's (NULL: the thread's) last error, returns code
-#define HIP_TRY(ctx, expr)                                                                          \
-    do { hipError_t _e = (expr);                                                                    \
-         if (_e != hipSuccess)                                                                      \
-             return fail(ctx, _e == hipErrorOutOfMemory ? PT_ERR_OUT_OF_MEMORY : PT_ERR_HIP,        \
-                         "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
-
-void context_drain(pt_context *c); // nothing of the context's may still run: on its loop streams or its own
-
-// The public half of a call that enqueues work: an error exit may leave kernels or copies in flight (on the loop streams too), and nothing
-// of a failed call runs on after it
-template <typename Call> pt_status drained_on_failure(pt_context *c, Call call)
-{
-    const pt_status st = call();
-    if (st != PT_OK && c) { (void)hipSetDevice(context_device(c)); context_drain(c); }
-    return st;
-}
-
-// A caller's device array must lie inside one allocation on the context's device: the kernel reads / writes `bytes` from `p` unchecked.
-pt_status check_device_array(pt_context *c, const void *p, uint64_t bytes, const char *what, const char *who = "pt_trace_rays",
-                             const char *host_flag = "PT_TRACE_HOST_MEMORY");
 
 struct CommitClock;
 
@@ -94,7 +70,7 @@ private:
     bool host_stale = false;
 };
 
-struct ExtendChoice {           // what a scene remembers of the extend-kernel probe (api.cpp ExtendFrame)
+struct ExtendChoice {           // what a scene remembers of the extend-kernel probe (frame.cpp ExtendFrame)
     uint32_t kernel = 0;        // the ExtendKernel an earlier frame picked (0 = none yet)
     double rate_simple = 0.0, rate_packed = 0.0; // rays per ms of whole frames run on one kernel (frames too short to probe inside)
     uint32_t misses = 0;        // warm frames too small to time: after three the scene settles on the one-ray-per-lane kernel for good

@@ -71,11 +71,10 @@ def test_device_resources_have_one_owner():
             for call in ("hipMalloc(", "hipHostMalloc(", "hipEventCreate", "hipStreamCreate"):
                 if call in line:
                     assert "//" in line.split(call, 1)[1], (f, no, call, "outside the owners' header and no comment on the line says why")
-    api = src["api.cpp"]
-    for name in ("pt_context_destroy", "pt_scene_destroy"):
-        body = re.search(r"^void " + name + r"\(.*?^}", api, re.M | re.S)
-        assert body, name
-        assert ".release(" not in body.group(0) and "delete " in body.group(0), name
+    for name in ("pt_context_destroy", "pt_scene_destroy"):  # each defined once, in whichever source file
+        bodies = [m.group(0) for txt in src.values() for m in re.finditer(r"^void " + name + r"\(.*?^}", txt, re.M | re.S)]
+        assert len(bodies) == 1, (name, len(bodies))
+        assert ".release(" not in bodies[0] and "delete " in bodies[0], name
 
 
 def test_environment_changes_no_tree():

@@ -571,7 +571,7 @@ def test_bucketed_specular_shading_is_identical(P, pto, renderer):
 
 
 def test_shard_groups_on_separate_streams(P, pto, monkeypatch):
-    """pt_tuning.loops = 2/4: the 64 queue shards run as 2/4 independent wavefront loops on their own HIP streams (api.cpp).
+    """pt_tuning.loops = 2/4: the 64 queue shards run as 2/4 independent wavefront loops on their own HIP streams (frame.cpp).
     Shards never exchange slots, so the frame and the ray count must not change."""
     sd = P.make_scene(P.native.PT_SCENE_CORNELL_GLASS, 0, 4, 300, 200)
     p = P.make_params(300, 200, spp=6, max_depth=10, streams=4)
@@ -751,7 +751,7 @@ def test_host_readback_and_kernel_pin(P, pto):
 
 
 def test_frame_start_template_follows_the_geometry(P, pto, renderer):
-    """The first queue and counter block of a frame are cached per frame geometry (api.cpp: q_init / cnt_init). Changing size, rank
+    """The first queue and counter block of a frame are cached per frame geometry (context.h: FrameTemplate). Changing size, rank
     split, stream count, a sample count below the stream count, or the sample offset must rebuild them: every frame of the
     sequence — including returns to an earlier geometry and progressive frames that continue one — equals the oracle's."""
     N = P.native

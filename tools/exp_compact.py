@@ -3,7 +3,7 @@
   ratio   : predicted ratio only (sticky_samples = 0)
   sticky  : sticky at every frame length
   always  : compact_below = 2
-Numbers in api.cpp (pt_context::sticky_samples) and DESIGN.md §4 come from this script."""
+Numbers in context.h (pt_context::tuning, sticky_samples) and DESIGN.md §4 come from this script."""
 import sys; sys.path.insert(0,".")
 import pathtracing_amd as P
 N=P.native
