@@ -23,7 +23,8 @@ constexpr uint32_t kMaxLeaf = 4;          // triangles per leaf, at most
 #ifndef PT_LBVH_CLUSTER
 #define PT_LBVH_CLUSTER 32
 #endif
-constexpr uint32_t kClusterTris = PT_LBVH_CLUSTER; // the GPU builder's LBVH is cut into subtrees of at most this many triangles; 0: no SAH storey
+constexpr uint32_t kClusterTris = PT_LBVH_CLUSTER; // the GPU builder's LBVH is cut into subtrees of at most this many triangles (1: every triangle a cluster)
+static_assert(kClusterTris >= 1, "a cluster holds at least one triangle: there is no build without the SAH top storey");
 
 PT_HD constexpr int32_t leaf_ref(uint32_t first, uint32_t count) { return (int32_t)~((first << 3) | (count - 1u)); } // records [first, first + count)
 PT_HD constexpr uint32_t leaf_first(int32_t ref) { return (uint32_t)~ref >> 3; }
@@ -168,5 +169,29 @@ PT_HD inline double sah_child_term(float area, float root_area, int32_t ref) // 
 {
     return (double)(area / root_area) * (double)(ref < 0 ? leaf_count(ref) : 1u);
 }
+
+// ---- packing a binary LBVH (lbvh.hip on the device for layout 68, bvh_build.cpp build_bvh_from_binary for the others)
+// The leaf rule: a subtree of at most kMaxLeaf triangles becomes one leaf unless splitting it into its two children lowers the SAH cost.
+PT_HD inline bool lbvh_leaf(uint32_t count, float area, uint32_t lcount, float larea, uint32_t rcount, float rarea)
+{
+    if (count > kMaxLeaf) return false;
+    float split = 0.f;
+    split += larea * (float)lcount;
+    split += rarea * (float)rcount;
+    return !(split < area * (float)count);
+}
+
+// ---- depth and worst-case traversal-stack need of one node: give it every child slot's ref, with the figures of the nodes below it
+struct DepthNeed {
+    uint32_t used = 0, dmax = 1, nmax = 0; // children, the largest inner child's depth and need
+    PT_HD void child(int32_t ref, const uint32_t *depth_of, const uint32_t *need_of)
+    {
+        if (ref == kEmptyRef) return;
+        ++used;
+        if (ref >= 0) { dmax = rule_max(dmax, depth_of[ref]); nmax = rule_max(nmax, need_of[ref]); }
+    }
+    PT_HD uint32_t depth() const { return dmax + 1; }
+    PT_HD uint32_t need() const { return (used ? used - 1 : 0) + nmax; } // all children pushed but the one entered, then the deepest of them
+};
 
 } // namespace ptrt

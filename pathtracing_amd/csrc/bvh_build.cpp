@@ -260,15 +260,10 @@ void emit_blob(const std::vector<Tmp> &tn, int32_t root, const std::vector<uint3
     // ---- depth and worst-case traversal-stack need (children have larger indices than parents)
     std::vector<uint32_t> depth(out.n_nodes, 1), need(out.n_nodes, 0);
     for (int64_t i = (int64_t)out.n_nodes - 1; i >= 0; --i) {
-        uint32_t k = 0, dmax = 1, nmax = 0;
-        for (uint32_t c = 0; c < width; ++c) {
-            const int32_t r = out.slots[(size_t)i * width + c].ref;
-            if (r == kEmptyRef) continue;
-            ++k;
-            if (r >= 0) { dmax = std::max(dmax, depth[r]); nmax = std::max(nmax, need[r]); }
-        }
-        depth[i] = dmax + 1;
-        need[i] = (k ? k - 1 : 0) + nmax;
+        DepthNeed f;
+        for (uint32_t c = 0; c < width; ++c) f.child(out.slots[(size_t)i * width + c].ref, depth.data(), need.data());
+        depth[i] = f.depth();
+        need[i] = f.need();
     }
     out.max_depth = depth[0];
     out.stack_need = need[0];
@@ -296,11 +291,13 @@ void build_bvh(const float *verts9, const uint32_t *mats, uint32_t n_tris, uint3
 }
 
 // A binary LBVH built on the device (lbvh.hip) -> blob, in two storeys:
-//   top    : the LBVH is cut where a subtree holds at most kClusterTris triangles; the host's binned-SAH builder makes a binary tree
-//            over those clusters (65 k boxes for 1M triangles, built on threads: a few milliseconds). Every ray crosses the top levels, and Morton splits are at
-//            their worst there (1M-triangle Cornell: 9.15 -> 7.9 node visits per ray).
+//   top    : the LBVH is cut where a subtree holds at most kClusterTris triangles; build_sah_over_boxes makes a binned-SAH binary tree over
+//            those clusters (65 k boxes for 1M triangles; above 8192 boxes the subtrees below its top levels are built on threads: a few
+//            milliseconds). Every ray crosses the top levels, and Morton splits are at their worst there (1M-triangle Cornell:
+//            9.15 -> 7.9 node visits per ray).
 //   bottom : inside a cluster the device's topology and boxes are kept; subtrees of at most kMaxLeaf triangles become leaves unless
-//            splitting them lowers the SAH cost — the leaf rule of Builder::build (their triangles are contiguous in Morton order).
+//            splitting them lowers the SAH cost — blob_rules.h lbvh_leaf, the rule of Builder::build (their triangles are contiguous in
+//            Morton order).
 void build_bvh_from_binary(const BinaryBvh &bt, const float *verts9, const uint32_t *mats, uint32_t n_tris, uint32_t width, BvhBlob &out, bool octant_slots)
 {
     const auto t0 = std::chrono::steady_clock::now();
@@ -318,46 +315,48 @@ void build_bvh_from_binary(const BinaryBvh &bt, const float *verts9, const uint3
         std::vector<int32_t> st{ 0 };
         while (!st.empty()) {
             const int32_t c = st.back(); st.pop_back();
-            if (c < 0 || kClusterTris == 0 || node_count(c) <= kClusterTris) clusters.push_back(c);
+            if (c < 0 || node_count(c) <= kClusterTris) clusters.push_back(c);
             else { st.push_back(bt.right[c]); st.push_back(bt.left[c]); }
         }
     }
     // ---- top storey: binned SAH over the cluster boxes, one cluster per leaf
-    std::vector<Prim> prims(clusters.size());
-    std::vector<uint32_t> cidx(clusters.size());
-    for (size_t i = 0; i < clusters.size(); ++i) {
-        prims[i].box = node_box(clusters[i]);
-        for (int k = 0; k < 3; ++k) prims[i].c[k] = 0.5f * (prims[i].box.lo[k] + prims[i].box.hi[k]);
-        cidx[i] = (uint32_t)i;
+    const uint32_t nc = (uint32_t)clusters.size();
+    std::vector<float> cbox((size_t)nc * 6), top_box;
+    for (uint32_t i = 0; i < nc; ++i) {
+        const Box b = node_box(clusters[i]);
+        for (int k = 0; k < 3; ++k) { cbox[(size_t)i * 6 + k] = b.lo[k]; cbox[(size_t)i * 6 + 3 + k] = b.hi[k]; }
     }
-    Builder top(prims, cidx);
-    top.max_leaf = 1;
-    const int32_t root = top.build(0, (uint32_t)clusters.size(), 0);
-    std::vector<Tmp> tn = top.nodes;
+    std::vector<int32_t> top_left, top_right;
+    int32_t top_root = 0;
+    build_sah_over_boxes(cbox.data(), nc, top_left, top_right, top_box, top_root);
+    // as tmp nodes: the top's inner nodes keep their numbers (parents before children), cluster i follows them at n_top + i, and the
+    // bottom storey goes behind — so children have larger indices than their parents, which emit_blob relies on
+    const int32_t n_top = (int32_t)top_left.size();
+    auto at = [&](int32_t c) { return c < 0 ? n_top + ~c : c; };
+    std::vector<Tmp> tn((size_t)n_top + nc);
     tn.reserve(tn.size() + (size_t)n_tris * 2);
+    for (int32_t i = 0; i < n_top; ++i) tn[i] = Tmp{ Box::of(&top_box[(size_t)i * 6]), at(top_left[i]), at(top_right[i]), 0u, 0u };
+    const int32_t root = at(top_root);
 
-    // ---- bottom storey: every top leaf is replaced, in place, by its cluster's LBVH subtree (iterative: deep chains stay off the C stack)
+    // ---- bottom storey: every cluster's place is filled by its LBVH subtree (iterative: deep chains stay off the C stack)
     struct Work { int32_t node; int32_t at; }; // convert LBVH node `node` into tn[at]
     std::vector<Work> work;
-    const size_t n_top = tn.size();
-    for (size_t i = 0; i < n_top; ++i)
-        if (tn[i].count) work.push_back({ clusters[cidx[tn[i].first]], (int32_t)i });
+    for (uint32_t i = 0; i < nc; ++i) work.push_back({ clusters[i], n_top + (int32_t)i });
     while (!work.empty()) {
         const Work w = work.back(); work.pop_back();
         Tmp t; t.left = t.right = -1; t.first = 0; t.count = 0;
         t.box = node_box(w.node);
         if (w.node >= 0) {
-            const uint32_t f = bt.first[w.node], cnt = node_count(w.node);
-            if (cnt <= kMaxLeaf) {
-                float split_cost = 0.f;
-                for (const int32_t c : { bt.left[w.node], bt.right[w.node] }) split_cost += node_box(c).area() * (float)node_count(c);
-                if (!(split_cost < t.box.area() * (float)cnt)) { t.first = f; t.count = cnt; }
+            const int32_t l = bt.left[w.node], r = bt.right[w.node];
+            const uint32_t cnt = node_count(w.node);
+            if (cnt <= kMaxLeaf && lbvh_leaf(cnt, t.box.area(), node_count(l), node_box(l).area(), node_count(r), node_box(r).area())) { // (asked first: a bigger node's child boxes stay unmade)
+                t.first = bt.first[w.node]; t.count = cnt;
             }
-            if (t.count == 0) {
+            else {
                 t.left = (int32_t)tn.size(); t.right = t.left + 1;
                 tn.push_back(Tmp{}); tn.push_back(Tmp{});
-                work.push_back({ bt.left[w.node], t.left });
-                work.push_back({ bt.right[w.node], t.right });
+                work.push_back({ l, t.left });
+                work.push_back({ r, t.right });
             }
         } else { t.first = (uint32_t)~w.node; t.count = 1; }
         tn[w.at] = t;

@@ -170,8 +170,10 @@ struct Lbvh {
 // the tree ever visiting the host. Only the top storey does: the LBVH is cut into clusters of <= kClusterTris triangles, their
 // boxes (a few thousand) go to the host's binned-SAH builder and the small binary tree over them comes back (bvh_build.cpp has the
 // same two-storey scheme for the other node layouts). Then, level by level: expand every node of the level to <= 4 children by
-// opening the child of largest area (as emit_blob does), scan the inner children to number the next level breadth-first,
-// quantise and write the node. Triangles are emitted in Morton order, so every leaf's range [first, last] is contiguous as it is.
+// opening the child of largest area, scan the inner children to number the next level breadth-first, quantise and write the node.
+// (Opening by area is a deliberate difference from the host: emit_blob chooses a wide node's children by the SAH-optimal dynamic
+// programme, which needs the costs of whole subtrees; the device keeps the local rule. DESIGN.md §7.) Triangles are emitted in Morton
+// order, so every leaf's range [first, last] is contiguous as it is. The leaf rule and the depth / stack-need rule are blob_rules.h's.
 using Lay = Layout<PT_BVH_WIDTH_4Q>;     // the one layout packed here
 constexpr int32_t kTopBase = 0x40000000;  // binary refs: >= kTopBase top-storey node, 0 .. n-2 LBVH node, < 0 LBVH leaf ~j
 
@@ -186,7 +188,7 @@ __device__ __forceinline__ Box box_of(const TreeView &t, int32_t r)
 __device__ __forceinline__ uint32_t count_of(const TreeView &t, int32_t r) { return r < 0 ? 1u : t.last[r] - t.first[r] + 1u; } // LBVH refs only
 __device__ __forceinline__ bool blob_leaf(const TreeView &t, int32_t r) { return r < 0 || (r < kTopBase && t.leaf_flag[r]); }
 
-// per LBVH node: does it become a leaf of the blob (<= kMaxLeaf triangles and splitting does not lower the SAH cost)? and is it a cluster root?
+// per LBVH node: does it become a leaf of the blob (blob_rules.h lbvh_leaf)? and is it a cluster root?
 __global__ void __launch_bounds__(256) k_mark(TreeView t, uint32_t n, uint32_t cluster_tris, const int32_t *__restrict__ parent_node,
                                               const int32_t *__restrict__ parent_leaf, uint8_t *__restrict__ leaf_flag, int32_t *__restrict__ clusters,
                                               uint32_t *__restrict__ n_clusters)
@@ -195,11 +197,9 @@ __global__ void __launch_bounds__(256) k_mark(TreeView t, uint32_t n, uint32_t c
     if (i < n - 1) {
         const uint32_t cnt = t.last[i] - t.first[i] + 1u;
         bool leaf = false;
-        if (cnt <= kMaxLeaf) {
-            float split = 0.f;
-            const int32_t c[2] = { t.left[i], t.right[i] };
-            for (int s = 0; s < 2; ++s) split += box_of(t, c[s]).area() * (float)count_of(t, c[s]);
-            leaf = !(split < box_of(t, (int32_t)i).area() * (float)cnt);
+        if (cnt <= kMaxLeaf) { // (the rule says so itself: asked here first, a bigger node's boxes stay unread)
+            const int32_t l = t.left[i], r = t.right[i];
+            leaf = lbvh_leaf(cnt, box_of(t, (int32_t)i).area(), count_of(t, l), box_of(t, l).area(), count_of(t, r), box_of(t, r).area());
         }
         leaf_flag[i] = leaf ? 1 : 0;
         const int32_t p = parent_node[i];
@@ -295,15 +295,10 @@ __global__ void __launch_bounds__(256) k_depth(const uint8_t *__restrict__ nodes
 {
     const uint32_t q = blockIdx.x * 256 + threadIdx.x;
     if (q >= n_cur) return;
-    uint32_t k = 0, dmax = 1, nmax = 0;
-    for (int c = 0; c < Lay::N; ++c) {
-        const int32_t r = Lay::ref(nodes + (size_t)(base + q) * Lay::kStride, c);
-        if (r == kEmptyRef) continue;
-        ++k;
-        if (r >= 0) { dmax = max(dmax, depth[r]); nmax = max(nmax, need[r]); }
-    }
-    depth[base + q] = dmax + 1;
-    need[base + q] = (k ? k - 1 : 0) + nmax;
+    DepthNeed f;
+    for (int c = 0; c < Lay::N; ++c) f.child(Lay::ref(nodes + (size_t)(base + q) * Lay::kStride, c), depth, need);
+    depth[base + q] = f.depth();
+    need[base + q] = f.need();
 }
 
 // the device triangle record (one 64-byte line, Morton order): blob_rules.h tri_record, as scene.cpp makes it for the host-built trees
@@ -318,6 +313,133 @@ __global__ void __launch_bounds__(256) k_tri_records(const float *__restrict__ v
     for (int k = 0; k < 4; ++k) rec[(size_t)j * 4 + k] = make_float4(r[4 * k], r[4 * k + 1], r[4 * k + 2], r[4 * k + 3]);
 }
 
+// The device packer: the buffers of build_lbvh_blob4q_device and its four phases, in the order they run. A phase allocates what it is
+// the first to need; the host waits for the stream twice in the cut, once per level and once at the end.
+struct Packer {
+    hipStream_t stream = nullptr;
+    uint32_t n = 0;
+    Lbvh t;
+    TreeView tv{};
+    static dim3 blocks(uint32_t k) { return dim3((k + 255) / 256); }
+    // mark + cut
+    DevBuf<uint8_t> leaf_flag; DevBuf<int32_t> clusters; DevBuf<uint32_t> n_clusters, mats, cfirst; DevBuf<float> cbox; DevBuf<float4> tris;
+    uint32_t nc = 0;
+    std::vector<int32_t> h_clusters; std::vector<float> h_cbox; std::vector<uint32_t> h_cfirst;
+    // top storey
+    DevBuf<int32_t> top_left, top_right; DevBuf<float> top_box;
+    int32_t root_ref = 0; float root_area = 0.f;
+    // levels
+    DevBuf<uint8_t> nodes; DevBuf<int32_t> kids, queue_a, queue_b; DevBuf<uint32_t> inner_count, offs, depth, need; DevBuf<float> cost; DevBuf<unsigned char> scan_tmp;
+    std::vector<uint32_t> level_base; // first node of every level, then n_nodes
+    uint32_t n_nodes = 0;
+    // figures
+    DevBuf<float> sum; DevBuf<unsigned char> red_tmp; DevBuf<float4> final_nodes;
+
+    // leaf flags and cluster roots; the clusters' roots, boxes and first triangles come to the host, the triangle records are started
+    hipError_t mark_and_cut(const uint32_t *h_mats)
+    {
+        const dim3 block(256);
+        LB_TRY(leaf_flag.ensure(n)); LB_TRY(clusters.ensure(n)); LB_TRY(n_clusters.ensure(1));
+        LB_TRY(hipMemsetAsync(n_clusters.p, 0, 4, stream));
+        if (h_mats) { LB_TRY(mats.ensure(n)); LB_TRY(hipMemcpyAsync(mats.p, h_mats, (size_t)n * 4, hipMemcpyHostToDevice, stream)); }
+        tv = TreeView{ t.left.p, t.right.p, t.first.p, t.last.p, t.order.p, t.node_box.p, t.leaf_box.p, leaf_flag.p, nullptr, nullptr, nullptr };
+        hipLaunchKernelGGL(k_mark, blocks(n), block, 0, stream, tv, n, kClusterTris, t.pn.p, t.pl.p, leaf_flag.p, clusters.p, n_clusters.p);
+        LB_TRY(hipMemcpyAsync(&nc, n_clusters.p, 4, hipMemcpyDeviceToHost, stream));
+        LB_TRY(hipStreamSynchronize(stream));
+        if (nc == 0 || nc > n) return hipErrorUnknown;
+        LB_TRY(cbox.ensure((size_t)nc * 6)); LB_TRY(cfirst.ensure(nc));
+        hipLaunchKernelGGL(k_cluster_info, blocks(nc), block, 0, stream, tv, clusters.p, nc, cbox.p, cfirst.p);
+        h_clusters.resize(nc); h_cbox.resize((size_t)nc * 6); h_cfirst.resize(nc);
+        LB_TRY(hipMemcpyAsync(h_clusters.data(), clusters.p, (size_t)nc * 4, hipMemcpyDeviceToHost, stream));
+        LB_TRY(hipMemcpyAsync(h_cbox.data(), cbox.p, (size_t)nc * 24, hipMemcpyDeviceToHost, stream));
+        LB_TRY(hipMemcpyAsync(h_cfirst.data(), cfirst.p, (size_t)nc * 4, hipMemcpyDeviceToHost, stream));
+        // the triangle records need nothing of the above: they run while the host builds the top storey
+        LB_TRY(tris.ensure((size_t)n * 4));
+        hipLaunchKernelGGL(k_tri_records, blocks(n), block, 0, stream, t.verts.p, h_mats ? mats.p : nullptr, t.order.p, n, tris.p);
+        return hipStreamSynchronize(stream);
+    }
+
+    // on the host: binned SAH over the cluster boxes, in Morton order of the clusters (k_mark's append order is not deterministic)
+    hipError_t top_storey()
+    {
+        std::vector<uint32_t> perm(nc);
+        for (uint32_t i = 0; i < nc; ++i) perm[i] = i;
+        std::sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return h_cfirst[a] < h_cfirst[b]; });
+        std::vector<float> sorted_box((size_t)nc * 6);
+        for (uint32_t i = 0; i < nc; ++i) std::memcpy(&sorted_box[(size_t)i * 6], &h_cbox[(size_t)perm[i] * 6], 24);
+        std::vector<int32_t> left, right; std::vector<float> box; int32_t root = 0;
+        build_sah_over_boxes(sorted_box.data(), nc, left, right, box, root);
+        auto to_ref = [&](int32_t c) { return c < 0 ? h_clusters[perm[(uint32_t)~c]] : kTopBase + c; }; // SAH leaf ~i = cluster i
+        for (auto &c : left) c = to_ref(c);
+        for (auto &c : right) c = to_ref(c);
+        root_ref = to_ref(root);
+        root_area = sah_root_area(Box::of(root < 0 ? &sorted_box[(size_t)(uint32_t)~root * 6] : &box[(size_t)root * 6]));
+        const size_t nt = left.size();
+        LB_TRY(top_left.ensure(nt)); LB_TRY(top_right.ensure(nt)); LB_TRY(top_box.ensure(nt * 6));
+        if (nt) {
+            LB_TRY(hipMemcpyAsync(top_left.p, left.data(), nt * 4, hipMemcpyHostToDevice, stream));
+            LB_TRY(hipMemcpyAsync(top_right.p, right.data(), nt * 4, hipMemcpyHostToDevice, stream));
+            LB_TRY(hipMemcpyAsync(top_box.p, box.data(), nt * 24, hipMemcpyHostToDevice, stream));
+        }
+        tv.top_left = top_left.p; tv.top_right = top_right.p; tv.top_box = top_box.p;
+        return hipSuccess;
+    }
+
+    // level by level: expand, scan, finalize. A 4-wide inner node has >= 2 children, so there are < n nodes in all.
+    hipError_t pack_levels()
+    {
+        const dim3 block(256);
+        const uint32_t cap = n;
+        LB_TRY(nodes.ensure((size_t)cap * 64)); LB_TRY(kids.ensure((size_t)cap * 4)); LB_TRY(queue_a.ensure(cap)); LB_TRY(queue_b.ensure(cap));
+        LB_TRY(inner_count.ensure(cap + 1)); LB_TRY(offs.ensure(cap + 1)); LB_TRY(depth.ensure(cap)); LB_TRY(need.ensure(cap)); LB_TRY(cost.ensure(cap));
+        size_t scan_bytes = 0;
+        LB_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, inner_count.p, offs.p, 0u, (size_t)cap + 1, rocprim::plus<uint32_t>(), stream));
+        LB_TRY(scan_tmp.ensure(scan_bytes));
+        LB_TRY(hipMemcpyAsync(queue_a.p, &root_ref, 4, hipMemcpyHostToDevice, stream));
+        uint32_t base = 0, n_cur = 1;
+        int32_t *qc = queue_a.p, *qn = queue_b.p;
+        while (n_cur) {
+            if (base + n_cur > cap || level_base.size() > 200) return hipErrorUnknown;
+            level_base.push_back(base);
+            hipLaunchKernelGGL(k_expand, blocks(n_cur), block, 0, stream, tv, qc, n_cur, base, kids.p, inner_count.p);
+            LB_TRY(hipMemsetAsync(inner_count.p + n_cur, 0, 4, stream)); // the scan's extra element: offs[n_cur] = the next level's size
+            LB_TRY(rocprim::exclusive_scan(scan_tmp.p, scan_bytes, inner_count.p, offs.p, 0u, (size_t)n_cur + 1, rocprim::plus<uint32_t>(), stream));
+            hipLaunchKernelGGL(k_finalize, blocks(n_cur), block, 0, stream, tv, n_cur, base, kids.p, offs.p, qn, nodes.p, cost.p, 1.0f / root_area);
+            uint32_t n_next = 0;
+            LB_TRY(hipMemcpyAsync(&n_next, offs.p + n_cur, 4, hipMemcpyDeviceToHost, stream));
+            LB_TRY(hipStreamSynchronize(stream));
+            base += n_cur; n_cur = n_next;
+            std::swap(qc, qn);
+        }
+        n_nodes = base;
+        level_base.push_back(n_nodes);
+        return hipSuccess;
+    }
+
+    // depth and stack need from the deepest level up, the sum of the nodes' costs, and a node array of the exact size for the scene
+    // (the work array is sized for the worst case)
+    hipError_t figures(DeviceBlob4Q &out)
+    {
+        for (size_t l = level_base.size() - 1; l-- > 0;)
+            hipLaunchKernelGGL(k_depth, blocks(level_base[l + 1] - level_base[l]), dim3(256), 0, stream, nodes.p, level_base[l], level_base[l + 1] - level_base[l], depth.p, need.p);
+        size_t red_bytes = 0;
+        LB_TRY(sum.ensure(1));
+        LB_TRY(rocprim::reduce(nullptr, red_bytes, cost.p, sum.p, 0.f, (size_t)n_nodes, rocprim::plus<float>(), stream));
+        LB_TRY(red_tmp.ensure(red_bytes));
+        LB_TRY(rocprim::reduce(red_tmp.p, red_bytes, cost.p, sum.p, 0.f, (size_t)n_nodes, rocprim::plus<float>(), stream));
+        LB_TRY(hipMemcpyAsync(&out.max_depth, depth.p, 4, hipMemcpyDeviceToHost, stream));
+        LB_TRY(hipMemcpyAsync(&out.stack_need, need.p, 4, hipMemcpyDeviceToHost, stream));
+        LB_TRY(hipMemcpyAsync(&out.sah_cost, sum.p, 4, hipMemcpyDeviceToHost, stream));
+        LB_TRY(final_nodes.ensure((size_t)n_nodes * 4));
+        LB_TRY(hipMemcpyAsync(final_nodes.p, nodes.p, (size_t)n_nodes * 64, hipMemcpyDeviceToDevice, stream));
+        LB_TRY(hipStreamSynchronize(stream));
+        LB_TRY(hipGetLastError());
+        out.nodes = std::move(final_nodes); out.tris = std::move(tris);
+        out.n_nodes = n_nodes;
+        return hipSuccess;
+    }
+};
+
 } // namespace
 
 hipError_t build_lbvh_device(hipStream_t stream, const float *verts9, uint32_t n, BinaryBvh &out)
@@ -327,14 +449,11 @@ hipError_t build_lbvh_device(hipStream_t stream, const float *verts9, uint32_t n
     if (n < 2) return hipErrorInvalidValue;
     Lbvh t;
     LB_TRY(t.construct(stream, verts9, n));
-    out.order.resize(n); out.left.resize(n - 1); out.right.resize(n - 1); out.first.resize(n - 1); out.last.resize(n - 1);
-    out.box.resize((size_t)(n - 1) * 6);
-    LB_TRY(hipMemcpyAsync(out.order.data(), t.order.p, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
-    LB_TRY(hipMemcpyAsync(out.left.data(), t.left.p, (size_t)(n - 1) * 4, hipMemcpyDeviceToHost, stream));
-    LB_TRY(hipMemcpyAsync(out.right.data(), t.right.p, (size_t)(n - 1) * 4, hipMemcpyDeviceToHost, stream));
-    LB_TRY(hipMemcpyAsync(out.first.data(), t.first.p, (size_t)(n - 1) * 4, hipMemcpyDeviceToHost, stream));
-    LB_TRY(hipMemcpyAsync(out.last.data(), t.last.p, (size_t)(n - 1) * 4, hipMemcpyDeviceToHost, stream));
-    LB_TRY(hipMemcpyAsync(out.box.data(), t.node_box.p, (size_t)(n - 1) * 24, hipMemcpyDeviceToHost, stream));
+    auto fetch = [&](auto &v, const auto *src, size_t count) { v.resize(count); return hipMemcpyAsync(v.data(), src, count * sizeof *src, hipMemcpyDeviceToHost, stream); };
+    LB_TRY(fetch(out.order, t.order.p, n));
+    LB_TRY(fetch(out.left, t.left.p, n - 1)); LB_TRY(fetch(out.right, t.right.p, n - 1));
+    LB_TRY(fetch(out.first, t.first.p, n - 1)); LB_TRY(fetch(out.last, t.last.p, n - 1));
+    LB_TRY(fetch(out.box, t.node_box.p, (size_t)(n - 1) * 6));
     LB_TRY(hipStreamSynchronize(stream));
     out.device_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return hipSuccess;
@@ -345,106 +464,13 @@ hipError_t build_lbvh_blob4q_device(hipStream_t stream, const float *verts9, con
     const auto t0 = std::chrono::steady_clock::now();
     out = DeviceBlob4Q{};
     if (n < 2) return hipErrorInvalidValue;
-    Lbvh t;
-    LB_TRY(t.construct(stream, verts9, n));
-    const dim3 block(256);
-    auto blocks = [](uint32_t k) { return dim3((k + 255) / 256); };
-
-    // ---- leaf flags + cluster roots
-    DevBuf<uint8_t> leaf_flag; DevBuf<int32_t> clusters; DevBuf<uint32_t> n_clusters, d_mats;
-    LB_TRY(leaf_flag.ensure(n)); LB_TRY(clusters.ensure(n)); LB_TRY(n_clusters.ensure(1));
-    LB_TRY(hipMemsetAsync(n_clusters.p, 0, 4, stream));
-    if (mats) { LB_TRY(d_mats.ensure(n)); LB_TRY(hipMemcpyAsync(d_mats.p, mats, (size_t)n * 4, hipMemcpyHostToDevice, stream)); }
-    TreeView tv{ t.left.p, t.right.p, t.first.p, t.last.p, t.order.p, t.node_box.p, t.leaf_box.p, leaf_flag.p, nullptr, nullptr, nullptr };
-    hipLaunchKernelGGL(k_mark, blocks(n), block, 0, stream, tv, n, kClusterTris, t.pn.p, t.pl.p, leaf_flag.p, clusters.p, n_clusters.p);
-    uint32_t nc = 0;
-    LB_TRY(hipMemcpyAsync(&nc, n_clusters.p, 4, hipMemcpyDeviceToHost, stream));
-    LB_TRY(hipStreamSynchronize(stream));
-    if (nc == 0 || nc > n) return hipErrorUnknown;
-    DevBuf<float> d_cbox; DevBuf<uint32_t> d_cfirst;
-    LB_TRY(d_cbox.ensure((size_t)nc * 6)); LB_TRY(d_cfirst.ensure(nc));
-    hipLaunchKernelGGL(k_cluster_info, blocks(nc), block, 0, stream, tv, clusters.p, nc, d_cbox.p, d_cfirst.p);
-    std::vector<int32_t> h_clusters(nc); std::vector<float> h_cbox((size_t)nc * 6); std::vector<uint32_t> h_cfirst(nc);
-    LB_TRY(hipMemcpyAsync(h_clusters.data(), clusters.p, (size_t)nc * 4, hipMemcpyDeviceToHost, stream));
-    LB_TRY(hipMemcpyAsync(h_cbox.data(), d_cbox.p, (size_t)nc * 24, hipMemcpyDeviceToHost, stream));
-    LB_TRY(hipMemcpyAsync(h_cfirst.data(), d_cfirst.p, (size_t)nc * 4, hipMemcpyDeviceToHost, stream));
-    // the triangle records need nothing of the above: they run while the host builds the top storey
-    DevBuf<float4> tris;
-    LB_TRY(tris.ensure((size_t)n * 4));
-    hipLaunchKernelGGL(k_tri_records, blocks(n), block, 0, stream, t.verts.p, mats ? d_mats.p : nullptr, t.order.p, n, tris.p);
-    LB_TRY(hipStreamSynchronize(stream));
-
-    // ---- top storey on the host: binned SAH over the cluster boxes, in Morton order of the clusters (the append order above is not deterministic)
-    std::vector<uint32_t> perm(nc);
-    for (uint32_t i = 0; i < nc; ++i) perm[i] = i;
-    std::sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return h_cfirst[a] < h_cfirst[b]; });
-    std::vector<float> sorted_box((size_t)nc * 6);
-    for (uint32_t i = 0; i < nc; ++i) std::memcpy(&sorted_box[(size_t)i * 6], &h_cbox[(size_t)perm[i] * 6], 24);
-    std::vector<int32_t> top_left, top_right; std::vector<float> top_box; int32_t top_root = 0;
-    build_sah_over_boxes(sorted_box.data(), nc, top_left, top_right, top_box, top_root);
-    auto to_ref = [&](int32_t c) { return c < 0 ? h_clusters[perm[(uint32_t)~c]] : kTopBase + c; }; // SAH leaf ~i = cluster i
-    for (auto &c : top_left) c = to_ref(c);
-    for (auto &c : top_right) c = to_ref(c);
-    const int32_t root_ref = to_ref(top_root);
-    const float *rb = top_root < 0 ? &sorted_box[(size_t)(uint32_t)~top_root * 6] : &top_box[(size_t)top_root * 6];
-    const float root_area = sah_root_area(Box::of(rb));
-    DevBuf<int32_t> d_tl, d_tr; DevBuf<float> d_tb;
-    const size_t nt_top = top_left.size();
-    LB_TRY(d_tl.ensure(nt_top)); LB_TRY(d_tr.ensure(nt_top)); LB_TRY(d_tb.ensure(nt_top * 6));
-    if (nt_top) {
-        LB_TRY(hipMemcpyAsync(d_tl.p, top_left.data(), nt_top * 4, hipMemcpyHostToDevice, stream));
-        LB_TRY(hipMemcpyAsync(d_tr.p, top_right.data(), nt_top * 4, hipMemcpyHostToDevice, stream));
-        LB_TRY(hipMemcpyAsync(d_tb.p, top_box.data(), nt_top * 24, hipMemcpyHostToDevice, stream));
-    }
-    tv.top_left = d_tl.p; tv.top_right = d_tr.p; tv.top_box = d_tb.p;
-
-    // ---- level by level: expand, scan, finalize. A 4-wide inner node has >= 2 children, so there are < n nodes in all.
-    const uint32_t cap = n;
-    DevBuf<uint8_t> nodes; DevBuf<int32_t> kids, queue_a, queue_b; DevBuf<uint32_t> inner_count, offs, depth, need; DevBuf<float> cost; DevBuf<unsigned char> scan_tmp;
-    LB_TRY(nodes.ensure((size_t)cap * 64)); LB_TRY(kids.ensure((size_t)cap * 4)); LB_TRY(queue_a.ensure(cap)); LB_TRY(queue_b.ensure(cap));
-    LB_TRY(inner_count.ensure(cap + 1)); LB_TRY(offs.ensure(cap + 1)); LB_TRY(depth.ensure(cap)); LB_TRY(need.ensure(cap)); LB_TRY(cost.ensure(cap));
-    size_t scan_bytes = 0;
-    LB_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, inner_count.p, offs.p, 0u, (size_t)cap + 1, rocprim::plus<uint32_t>(), stream));
-    LB_TRY(scan_tmp.ensure(scan_bytes));
-    LB_TRY(hipMemcpyAsync(queue_a.p, &root_ref, 4, hipMemcpyHostToDevice, stream));
-    std::vector<uint32_t> level_base;
-    uint32_t base = 0, n_cur = 1;
-    int32_t *qc = queue_a.p, *qn = queue_b.p;
-    while (n_cur) {
-        if (base + n_cur > cap || level_base.size() > 200) return hipErrorUnknown;
-        level_base.push_back(base);
-        hipLaunchKernelGGL(k_expand, blocks(n_cur), block, 0, stream, tv, qc, n_cur, base, kids.p, inner_count.p);
-        LB_TRY(hipMemsetAsync(inner_count.p + n_cur, 0, 4, stream)); // the scan's extra element: offs[n_cur] = the next level's size
-        LB_TRY(rocprim::exclusive_scan(scan_tmp.p, scan_bytes, inner_count.p, offs.p, 0u, (size_t)n_cur + 1, rocprim::plus<uint32_t>(), stream));
-        hipLaunchKernelGGL(k_finalize, blocks(n_cur), block, 0, stream, tv, n_cur, base, kids.p, offs.p, qn, nodes.p, cost.p, 1.0f / root_area);
-        uint32_t n_next = 0;
-        LB_TRY(hipMemcpyAsync(&n_next, offs.p + n_cur, 4, hipMemcpyDeviceToHost, stream));
-        LB_TRY(hipStreamSynchronize(stream));
-        base += n_cur; n_cur = n_next;
-        std::swap(qc, qn);
-    }
-    const uint32_t n_nodes = base;
-    level_base.push_back(n_nodes);
-    for (size_t l = level_base.size() - 1; l-- > 0;)
-        hipLaunchKernelGGL(k_depth, blocks(level_base[l + 1] - level_base[l]), block, 0, stream, nodes.p, level_base[l], level_base[l + 1] - level_base[l], depth.p, need.p);
-    size_t red_bytes = 0;
-    DevBuf<float> d_sum; DevBuf<unsigned char> red_tmp;
-    LB_TRY(d_sum.ensure(1));
-    LB_TRY(rocprim::reduce(nullptr, red_bytes, cost.p, d_sum.p, 0.f, (size_t)n_nodes, rocprim::plus<float>(), stream));
-    LB_TRY(red_tmp.ensure(red_bytes));
-    LB_TRY(rocprim::reduce(red_tmp.p, red_bytes, cost.p, d_sum.p, 0.f, (size_t)n_nodes, rocprim::plus<float>(), stream));
-    uint32_t h_depth = 0, h_need = 0; float h_cost = 0.f;
-    LB_TRY(hipMemcpyAsync(&h_depth, depth.p, 4, hipMemcpyDeviceToHost, stream));
-    LB_TRY(hipMemcpyAsync(&h_need, need.p, 4, hipMemcpyDeviceToHost, stream));
-    LB_TRY(hipMemcpyAsync(&h_cost, d_sum.p, 4, hipMemcpyDeviceToHost, stream));
-    // exact-size node array for the scene (the work array is sized for the worst case)
-    DevBuf<float4> final_nodes;
-    LB_TRY(final_nodes.ensure((size_t)n_nodes * 4));
-    LB_TRY(hipMemcpyAsync(final_nodes.p, nodes.p, (size_t)n_nodes * 64, hipMemcpyDeviceToDevice, stream));
-    LB_TRY(hipStreamSynchronize(stream));
-    LB_TRY(hipGetLastError());
-    out.nodes = std::move(final_nodes); out.tris = std::move(tris);
-    out.n_nodes = n_nodes; out.max_depth = h_depth; out.stack_need = h_need; out.sah_cost = h_cost;
+    Packer p;
+    p.stream = stream; p.n = n;
+    LB_TRY(p.t.construct(stream, verts9, n));
+    LB_TRY(p.mark_and_cut(mats));
+    LB_TRY(p.top_storey());
+    LB_TRY(p.pack_levels());
+    LB_TRY(p.figures(out));
     out.device_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return hipSuccess;
 }

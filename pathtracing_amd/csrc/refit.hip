@@ -10,6 +10,7 @@
 // the blob, so the refitted blob is a blob a builder could have emitted for the new vertices: it renders that commit's picture (§4.1).
 // Record, box, quantiser, node layouts and SAH term are blob_rules.h's, the text the builders run.
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "refit.h"
 #include "blob_rules.h"
 
@@ -121,6 +122,20 @@ __global__ void __launch_bounds__(kBlock) k_refit_sum(const double *__restrict__
 
 dim3 blocks_for(uint64_t n) { return dim3((uint32_t)((n + kBlock - 1) / kBlock)); }
 
+// layout code -> template argument, for this file's kernels: f(constant) with the layout whose node format the code names (8O is the 8Q
+// node with its children in octant slots). False: no such layout.
+template <class F> bool with_node_layout(uint32_t layout, F f)
+{
+    switch (layout) {
+    case PT_BVH_WIDTH_2:  f(std::integral_constant<int, PT_BVH_WIDTH_2>{}); return true;
+    case PT_BVH_WIDTH_4:  f(std::integral_constant<int, PT_BVH_WIDTH_4>{}); return true;
+    case PT_BVH_WIDTH_4Q: f(std::integral_constant<int, PT_BVH_WIDTH_4Q>{}); return true;
+    case PT_BVH_WIDTH_8Q:
+    case PT_BVH_WIDTH_8O: f(std::integral_constant<int, PT_BVH_WIDTH_8Q>{}); return true;
+    default: return false;
+    }
+}
+
 } // namespace
 
 bool refit_levels(const int32_t *refs, uint32_t n_nodes, uint32_t fan, uint32_t n_tris, std::vector<uint32_t> &list, std::vector<uint32_t> &off)
@@ -178,14 +193,8 @@ hipError_t launch_refit_level(hipStream_t s, uint32_t layout, void *nodes, const
 {
     if (!count) return hipSuccess;
     uint8_t *nd = static_cast<uint8_t *>(nodes);
-    switch (layout) {
-    case PT_BVH_WIDTH_2:  hipLaunchKernelGGL(k_refit_level<PT_BVH_WIDTH_2>, blocks_for(count), dim3(kBlock), 0, s, nd, list, count, tbox, nbox, carea); break;
-    case PT_BVH_WIDTH_4:  hipLaunchKernelGGL(k_refit_level<PT_BVH_WIDTH_4>, blocks_for(count), dim3(kBlock), 0, s, nd, list, count, tbox, nbox, carea); break;
-    case PT_BVH_WIDTH_4Q: hipLaunchKernelGGL(k_refit_level<PT_BVH_WIDTH_4Q>, blocks_for(count), dim3(kBlock), 0, s, nd, list, count, tbox, nbox, carea); break;
-    case PT_BVH_WIDTH_8Q:
-    case PT_BVH_WIDTH_8O: hipLaunchKernelGGL(k_refit_level<PT_BVH_WIDTH_8Q>, blocks_for(count), dim3(kBlock), 0, s, nd, list, count, tbox, nbox, carea); break;
-    default: return hipErrorInvalidValue;
-    }
+    if (!with_node_layout(layout, [&](auto L) { hipLaunchKernelGGL(k_refit_level<decltype(L)::value>, blocks_for(count), dim3(kBlock), 0, s, nd, list, count, tbox, nbox, carea); }))
+        return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
@@ -197,14 +206,8 @@ hipError_t launch_refit_sah(hipStream_t s, uint32_t layout, const void *nodes, u
     if (!n_nodes) return hipMemsetAsync(out, 0, sizeof(double), s);
     const uint8_t *nd = static_cast<const uint8_t *>(nodes);
     const dim3 g = blocks_for(n_nodes);
-    switch (layout) {
-    case PT_BVH_WIDTH_2:  hipLaunchKernelGGL(k_refit_sah<PT_BVH_WIDTH_2>, g, dim3(kBlock), 0, s, nd, n_nodes, carea, nbox, partial); break;
-    case PT_BVH_WIDTH_4:  hipLaunchKernelGGL(k_refit_sah<PT_BVH_WIDTH_4>, g, dim3(kBlock), 0, s, nd, n_nodes, carea, nbox, partial); break;
-    case PT_BVH_WIDTH_4Q: hipLaunchKernelGGL(k_refit_sah<PT_BVH_WIDTH_4Q>, g, dim3(kBlock), 0, s, nd, n_nodes, carea, nbox, partial); break;
-    case PT_BVH_WIDTH_8Q:
-    case PT_BVH_WIDTH_8O: hipLaunchKernelGGL(k_refit_sah<PT_BVH_WIDTH_8Q>, g, dim3(kBlock), 0, s, nd, n_nodes, carea, nbox, partial); break;
-    default: return hipErrorInvalidValue;
-    }
+    if (!with_node_layout(layout, [&](auto L) { hipLaunchKernelGGL(k_refit_sah<decltype(L)::value>, g, dim3(kBlock), 0, s, nd, n_nodes, carea, nbox, partial); }))
+        return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_refit_sum, dim3(1), dim3(kBlock), 0, s, partial, g.x, out);
     return hipGetLastError();
 }
