@@ -102,6 +102,11 @@ typedef struct {
 } pt_device_desc;
 
 typedef struct { uint32_t kind; float albedo[3]; float emission[3]; float roughness; float ior; uint32_t pad[3]; } pt_material; /* 48 B */
+/* Accepted by pt_scene_set_materials: kind <= PT_DIELECTRIC, finite fields, roughness in [0, 1] and, for a dielectric,
+ * PT_IOR_MIN <= ior <= PT_IOR_MAX (2^-20 .. 2^20): the range in which eta*eta is finite and the formulas of docs/SPEC.md §5 give a
+ * finite direction at every incidence, on both sides of the surface. ior is not looked at for the other kinds. */
+#define PT_IOR_MIN 9.5367431640625e-07f /* 2^-20 */
+#define PT_IOR_MAX 1048576.0f           /* 2^20 */
 
 /* pinhole camera, docs/SPEC.md §3. The reference's literal camera (Test.hlsl:6-10) is
  * origin (0,0,1), forward (0,0,-1), right (1,0,0), up (0,1,0), scale 2/1080, cx = cy = 1, jitter 0

@@ -34,6 +34,7 @@ PT_OK, PT_ERR_INVALID_ARGUMENT, PT_ERR_NO_DEVICE, PT_ERR_HIP, PT_ERR_OUT_OF_MEMO
     PT_ERR_UNSUPPORTED, PT_ERR_INTERNAL = range(8)
 PT_REFERENCE_SPHERE, PT_PATH_TRACE = 0, 1
 PT_LAMBERT, PT_METAL, PT_DIELECTRIC = 0, 1, 2
+PT_IOR_MIN, PT_IOR_MAX = 2.0 ** -20, 2.0 ** 20  # the dielectric ior range pt_scene_set_materials accepts
 PT_FLAG_PROFILE_KERNELS, PT_FLAG_COUNT_VISITS, PT_FLAG_EXTEND_PACKED, PT_FLAG_EXTEND_SIMPLE, PT_FLAG_ACCUMULATE, PT_FLAG_BUCKET_SPECULAR = 1, 2, 4, 8, 16, 32
 PT_FLAG_SPLIT_KERNELS = 64
 PT_FLAG_EXTEND_POOL = 128

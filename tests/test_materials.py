@@ -1,0 +1,277 @@
+"""CPU: the material zoo (tests/material_zoo.py) provably reaches the BSDF branches it names, the oracle's BSDF samplers agree with
+their float64 restatement (tests/bsdf64.py) over the whole material grid, and an index of refraction whose square would overflow is
+refused. Everything here runs before any zoo scene goes to a GPU (tests/test_gpu_materials.py)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import bsdf64 as b64
+import census_checker as cc
+import material_zoo as mz
+
+F3 = C.c_float * 3
+# The error of W is taken relative to its largest component, but to no less than W_FLOOR: the Schlick weight of a black metal near
+# normal incidence is m^5 of a rounding error (1e-38 against 0), which no relative bound can describe. The floor governs only the
+# cases whose float64 weight is below it (3 to 6 % of a metal class, counted next to bsdf64.BOUNDS); the rest is truly relative.
+W_FLOOR = 1e-6
+
+
+# ------------------------------------------------------------------------------------------------------------------------- the zoo
+def test_grid_is_covered(P):
+    """Every roughness, ior and albedo of the grid, every kind, and emission on every kind appear in some zoo scene, in use."""
+    rough, ior, alb, kinds, emit = set(), set(), set(), set(), set()
+    for name, view in mz.CONFIGS:
+        sd = mz.build(name, view)
+        assert len(sd.tri_mat) <= 150 and len(sd.sph_mat) <= 16 and sd.cam.jitter == 0
+        for m in sd.mats[np.unique(np.concatenate([sd.tri_mat, sd.sph_mat]))]:
+            kinds.add(int(m["kind"]))
+            alb.add(tuple(m["albedo"].tolist()))
+            if m["kind"] == mz.METAL:
+                rough.add(float(m["roughness"]))
+            if m["kind"] == mz.DIELECTRIC:
+                ior.add(float(m["ior"]))
+            if m["emission"].any():
+                emit.add(int(m["kind"]))
+    f32 = lambda v: float(np.float32(v))
+    assert {f32(r) for r in mz.ROUGHNESS} <= rough and {f32(i) for i in mz.IOR} <= ior
+    assert {tuple(f32(c) for c in a) for a in mz.ALBEDO} <= alb
+    assert kinds == {0, 1, 2} and emit == {0, 1, 2}
+
+
+def test_palette_uses_a_long_material_table(P):
+    sd = mz.build("palette", "front")
+    used = np.concatenate([sd.tri_mat, sd.sph_mat])
+    assert len(sd.mats) >= 300 and len(np.unique(used)) == len(used) and used.max() == len(sd.mats) - 1
+    emissive = sd.mats["emission"].any(axis=1)
+    assert {int(k) for k in sd.mats["kind"][sd.tri_mat[emissive[sd.tri_mat]]]} == {0, 1, 2} and emissive[sd.sph_mat].sum() == 1
+
+
+def zoo_frames(P):
+    """Every (scene, view, parameter set) the GPU tests render, by name."""
+    out = [((name, view, "parity"), (name, view), mz.parity_params(P)) for name, view in mz.CONFIGS]
+    out += [((name, view, key), (name, view), mz.edge_params(P, key)) for name, view in mz.EDGE_SCENES for key in mz.EDGE_PARAMS]
+    out.append((("palette", "front", "spp5"), ("palette", "front"), P.make_params(mz.W, mz.H, spp=5, max_depth=12, streams=2)))
+    return out
+
+
+@pytest.fixture(scope="module")
+def census(P, pto):
+    """{frame name: (classes, equal to pto_render, finite, inconsistent)} of every zoo frame: the walker's counts, and whether its
+    frame, rays and paths are the oracle's bit for bit."""
+    from pathtracing_amd.host import build_bvh_detached
+    cc.build()
+    out = {}
+    for key, cfg, params in zoo_frames(P):
+        sd = mz.build(*cfg)
+        build_bvh_detached(sd)  # the library accepts the scene (materials, camera, geometry)
+        osc = pto.Scene(sd)
+        img, rays, paths, n, bad = cc.render(pto, osc, params)
+        ref, ost = pto.render(osc, params)
+        out[key] = (n, np.array_equal(img, ref) and rays == ost.rays and paths == ost.paths, bool(np.isfinite(ref).all()), bad)
+    return out
+
+
+def test_oracle_frames_of_the_zoo_are_finite(census):
+    assert [k for k, v in census.items() if not v[2]] == []
+
+
+def test_walker_is_the_oracle_bit_for_bit(census):
+    """The census describes the oracle's own paths: same frame, same rays, same paths, on every zoo frame; and the restated branch
+    conditions never contradict the sampler's outputs."""
+    assert [k for k, v in census.items() if not v[1]] == []
+    assert [k for k, v in census.items() if v[3]] == []
+
+
+def test_every_class_is_reached(census):
+    total = {c: sum(census[(n, v, "parity")][0][c] for n, v in mz.CONFIGS) for c in mz.CLASSES}
+    print(total)
+    assert [c for c in mz.CLASSES if total[c] < 100] == []
+    missing = [(cfg, c) for cfg in mz.CONFIGS for c in mz.CLAIMS[cfg] if census[cfg + ("parity",)][0][c] < 1]
+    assert missing == []
+    assert set(mz.CLAIMS) == set(mz.CONFIGS) and all(len(v) >= 3 for v in mz.CLAIMS.values())
+
+
+NEE_CONFIGS = [("palette", "front"), ("glass_box", "outside"), ("glass_box", "inside")]
+
+
+def emissive_triangles(sd):
+    """Mask of the triangles SPEC §7 takes as lights: some emission and a positive area, whatever the material's kind."""
+    e1, e2 = sd.verts[:, 3:6] - sd.verts[:, 0:3], sd.verts[:, 6:9] - sd.verts[:, 0:3]
+    area = 0.5 * np.linalg.norm(np.cross(e1.astype(np.float64), e2.astype(np.float64)), axis=1)
+    return sd.mats["emission"][sd.tri_mat].any(axis=1) & (area > 0)
+
+
+@pytest.mark.parametrize("cfg", NEE_CONFIGS, ids="-".join)
+def test_nee_reference_frames_of_the_zoo(P, pto, cfg):
+    """The next-event frames the GPU tests compare against: finite, with the plain frame's extension rays, and a light set that
+    holds every emissive triangle of positive area — Lambert, metal and dielectric ones alike on the palette."""
+    import nee_checker as nc
+    nc.build()
+    sd = mz.build(*cfg)
+    lit = emissive_triangles(sd)
+    osc = pto.Scene(sd)
+    ref, cst, _ = nc.render(pto, osc, mz.parity_params(P, P.native.PT_FLAG_NEXT_EVENT))
+    plain, ost = pto.render(osc, mz.parity_params(P))
+    assert np.isfinite(ref).all()
+    assert cst.n_lights == int(lit.sum()) > 0 and cst.shadow_rays > 0
+    assert (cst.ext_rays, cst.paths) == (ost.rays, ost.paths)
+    if cfg[0] == "palette":
+        assert {int(k) for k in sd.mats["kind"][sd.tri_mat[lit]]} == {0, 1, 2}
+
+
+def test_depth_and_roulette_edges_do_what_they_say(census):
+    for name, view in mz.EDGE_SCENES:
+        d1 = census[(name, view, "depth1")][0]
+        assert d1["depth_cut"] + d1["miss"] == mz.W * mz.H * 4 and sum(d1[c] for c in mz.CLASSES[:13]) == 0
+        never = census[(name, view, "rr_never")][0]
+        assert never["RR_kill"] == never["RR_survive_clamped"] == never["RR_survive_unclamped"] == 0
+        assert never["depth_cut"] > 0 or name != "glass_box"  # inside glass nothing but max_depth ends a path then
+        rr1 = census[(name, view, "rr1")][0]
+        assert rr1["RR_kill"] > census[(name, view, "parity")][0]["RR_kill"]
+
+
+# ------------------------------------------------------------------------------------------------ the oracle against bsdf64
+def oracle_sample(pto, P, kind, albedo, rough, ior, d, n, front, u):
+    """pto_bsdf_sample over N cases: alive (N,), wi (N, 3), W (N, 3), side (N,)."""
+    m = np.zeros(1, P.MATERIAL_DTYPE)
+    m["kind"], m["albedo"], m["roughness"], m["ior"] = kind, albedo, rough, ior
+    mp = m.ctypes.data_as(C.c_void_p)
+    N = len(d)
+    alive, wi, W, side = np.zeros(N, bool), np.zeros((N, 3), np.float32), np.zeros((N, 3), np.float32), np.zeros(N, np.float32)
+    wo, Wo, so = F3(), F3(), C.c_float()
+    fn = pto.lib.pto_bsdf_sample
+    for i in range(N):
+        alive[i] = fn(mp, F3(*d[i]), F3(*n[i]), int(front[i]), u[i, 0], u[i, 1], u[i, 2], wo, Wo, C.byref(so))
+        wi[i], W[i], side[i] = wo[:], Wo[:], so.value
+    return alive, wi, W, side
+
+
+CLASS_LIST = ([("lambert", mz.LAMBERT, 0.0, 1.5), ("mirror", mz.METAL, 0.0, 1.5)]
+              + [(f"rough_{r:g}", mz.METAL, r, 1.5) for r in mz.ROUGHNESS[1:]] + [(f"ior_{i:g}", mz.DIELECTRIC, 0.0, i) for i in mz.IOR])
+
+
+def compare(pto, P, cls, wrong=None):
+    """The oracle against bsdf64 over the seeded cases of one class (its albedo cycling through the grid's five). Returns per-case
+    arrays: angle between the two wi, relative error of W, flip (alive or side differ), bsdf64's margin, cosi*cosi, and the float32
+    sample itself (alive, wi, side, n) for the geometric checks."""
+    name, kind, rough, ior = cls
+    share = b64.GRAZING_SHARE_IOR1 if (kind == mz.DIELECTRIC and ior == 1.0) else b64.GRAZING_SHARE
+    d, n, front, u = b64.cases(b64.SEED, b64.CASES, share)
+    parts = np.array_split(np.arange(len(d)), len(mz.ALBEDO))
+    ang, relw, flip, margin, floored = (np.zeros(len(d)) for _ in range(5))
+    a32, wi32, side32 = np.zeros(len(d), bool), np.zeros((len(d), 3)), np.zeros(len(d))
+    for alb, ix in zip(mz.ALBEDO, parts):
+        alb32 = np.asarray(alb, np.float32)
+        al, wi, W, sd = oracle_sample(pto, P, kind, alb32, rough, ior, d[ix], n[ix], front[ix], u[ix])
+        al64, wi64, W64, sd64, _, mg = b64.sample(kind, alb32, np.float32(rough), np.float32(ior), d[ix], n[ix], front[ix], u[ix], wrong)
+        fl = (al != al64) | (al & al64 & (sd != sd64))
+        both = al & al64 & ~fl
+        cosang = np.clip(np.sum(wi.astype(np.float64) * wi64, axis=1), -1.0, 1.0)
+        cr = np.linalg.norm(np.cross(wi.astype(np.float64), wi64), axis=1)
+        ang[ix] = np.where(both, np.arctan2(cr, cosang), 0.0)
+        scale = np.abs(W64).max(axis=1)
+        err = np.abs(W.astype(np.float64) - W64).max(axis=1)
+        relw[ix] = np.where(both, err / np.maximum(scale, W_FLOOR), 0.0)
+        flip[ix], margin[ix], floored[ix] = fl, mg, both & (scale < W_FLOOR)
+        a32[ix], wi32[ix], side32[ix] = al, wi, sd
+    cos = np.clip(-np.sum(d.astype(np.float64) * n.astype(np.float64), axis=1), 0.0, 1.0)
+    return dict(angle=ang, relw=relw, flip=flip.astype(bool), margin=margin, cosi2=cos * cos, floored=floored.astype(bool), alive=a32, wi=wi32, side=side32,
+                n=n.astype(np.float64))
+
+
+@pytest.mark.parametrize("cls", CLASS_LIST, ids=[c[0] for c in CLASS_LIST])
+def test_oracle_samplers_against_float64(P, pto, cls):
+    r = compare(pto, P, cls)
+    angle_bound, relw_bound, margin_bound = b64.BOUNDS[cls[0]]
+    flips = r["flip"]
+    print(cls[0], "angle", r["angle"].max(), "relW", r["relw"].max(), "floored", int(r["floored"].sum()), "flips", int(flips.sum()),
+          "margin", np.abs(r["margin"][flips]).max() if flips.any() else 0.0)
+    a = r["alive"]
+    assert np.abs(np.linalg.norm(r["wi"][a], axis=1) - 1.0).max() <= 4 * 2.0 ** -23          # unit: a few float32 roundings
+    assert (r["side"][a] * np.sum(r["wi"][a] * r["n"][a], axis=1) >= -4 * 2.0 ** -23).all()  # on the side `side` says
+    assert r["angle"].max() <= angle_bound and r["relw"].max() <= relw_bound
+    if cls[1] == mz.DIELECTRIC and cls[3] == 1.0:
+        assert (r["cosi2"][flips] <= b64.IOR1_BAND).all()  # SPEC §5's known grazing band of ior == 1, and nowhere else
+    else:
+        assert (np.abs(r["margin"][flips]) <= margin_bound).all()
+    assert flips.sum() <= b64.MAX_EXCLUDED * len(flips)
+
+
+@pytest.mark.parametrize("cls,wrong", [(("ior_1.5", mz.DIELECTRIC, 0.0, 1.5), "eta_inverted"), (("mirror", mz.METAL, 0.0, 1.5), "schlick_m4"),
+                                       (("rough_0.15", mz.METAL, 0.15, 1.5), "schlick_m4"), (("rough_0.5", mz.METAL, 0.5, 1.5), "no_s5")],
+                         ids=["eta_inverted", "schlick_m4_mirror", "schlick_m4_rough", "no_s5"])
+def test_a_wrong_sampler_would_be_caught(P, pto, cls, wrong):
+    """The bounds are tight enough to tell §5 from its near misses: refraction with eta inverted, Schlick with m^4, the VNDF
+    sampler without its s5 blend."""
+    r = compare(pto, P, cls, wrong)
+    angle_bound, relw_bound, margin_bound = b64.BOUNDS[cls[0]]
+    outside = (r["angle"] > angle_bound) | (r["relw"] > relw_bound) | (r["flip"] & (np.abs(r["margin"]) > margin_bound))
+    assert outside.mean() > 0.2, outside.mean()
+
+
+# ---------------------------------------------------------------------------------------------------------- the accepted ior range
+def _with_ior(P, ior, kind=mz.DIELECTRIC):
+    sd = mz.build("shells", "outside")
+    sd.mats = sd.mats.copy()
+    sd.mats[0]["kind"], sd.mats[0]["ior"] = kind, ior
+    return sd
+
+
+def test_ior_outside_the_range_is_refused(P):
+    """pt_scene_set_materials takes a dielectric ior in [2^-20, 2^20] and nothing else (an ior whose square overflows gave a NaN
+    ray at normal incidence); the field is not looked at for the other kinds."""
+    from pathtracing_amd.host import build_bvh_detached
+    lo, hi = np.float32(P.native.PT_IOR_MIN), np.float32(P.native.PT_IOR_MAX)
+    assert (float(lo), float(hi)) == (2.0 ** -20, 2.0 ** 20)
+    for ok in (lo, hi, np.nextafter(lo, np.float32(1)), np.nextafter(hi, np.float32(1)), 1.0):
+        build_bvh_detached(_with_ior(P, ok))
+    for bad in (np.nextafter(lo, np.float32(0)), np.nextafter(hi, np.float32(np.inf)), 1e-20, 1e20, 1e-30, 1e30, 0.0, -1.5):
+        with pytest.raises(P.PtException, match=r"ior outside \[2\^-20, 2\^20\]") as e:
+            build_bvh_detached(_with_ior(P, bad))
+        assert e.value.status == P.native.PT_ERR_INVALID_ARGUMENT
+    build_bvh_detached(_with_ior(P, 1e30, kind=mz.METAL))
+
+
+@pytest.mark.parametrize("ior", [2.0 ** -20, float(np.nextafter(np.float32(2.0 ** -20), np.float32(1))), 2.0 ** 20,
+                                 float(np.nextafter(np.float32(2.0 ** 20), np.float32(1)))])
+def test_the_ends_of_the_ior_range_stay_finite(P, pto, ior):
+    """At the ends of the accepted range the oracle and bsdf64 give finite unit directions at normal and at grazing incidence, on
+    both sides, and agree on them wherever they take the same branch."""
+    d, n, front, u = b64.cases(7, 600, 0.5)
+    al, wi, W, sd = oracle_sample(pto, P, mz.DIELECTRIC, (1.0, 1.0, 1.0), 0.0, ior, d, n, front, u)
+    al64, wi64, W64, sd64, _, _ = b64.sample(mz.DIELECTRIC, (1.0, 1.0, 1.0), 0.0, np.float32(ior), d, n, front, u)
+    normal = (d == -n).all(axis=1)
+    assert normal.sum() >= 5 and set(front[normal]) == {True, False}
+    assert al.all() and al64.all() and np.isfinite(wi).all() and np.isfinite(wi64).all() and np.isfinite(W).all()
+    assert np.abs(np.linalg.norm(wi, axis=1) - 1.0).max() <= 4 * 2.0 ** -23
+    same = sd == sd64
+    assert same.mean() > 0.95
+    # a refracted direction carries roundings of eta * 2^-24 per component (<= 2^-4 at the ends, see scene.cpp): finite, not exact
+    assert (np.sum(wi[same] * wi64[same], axis=1) > 0.9).all()
+
+
+def test_refraction_stays_finite_across_the_ior_range(P, pto):
+    """The argument at pt_scene_set_materials' check covers the ends of the range; this sweeps the whole of it: ior = 2^k for k from
+    -20 to 20 in half steps, both sides, directions a hair off the normal so that eta * |tangential part| runs from 0 past the critical
+    angle (where the float32 cosi is 1 or a float below it and sin2t is anywhere in [0, 1)). Every sample is a finite unit vector."""
+    rng = np.random.default_rng(11)
+    s = np.array([0.0, 1e-6, 1e-3, 0.1, 0.5, 0.9, 0.99, 0.999, 0.9999, 1.0, 1.0001, 1.5])
+    worst, refracted = 0.0, 0
+    for k in np.arange(-20.0, 20.25, 0.5):
+        ior = np.float32(2.0 ** k)
+        for front in (True, False):
+            eta = float(1.0 / ior if front else ior)
+            n = b64._unit(rng.normal(size=(len(s), 3)))
+            n[0], n[1] = (0.0, 0.0, 1.0), (1.0, 0.0, 0.0)
+            t = b64._unit(np.cross(n, rng.normal(size=(len(s), 3))))
+            sin = np.minimum(s / max(eta, 1.0), 0.999)
+            d = -(np.sqrt(1.0 - sin * sin)[:, None] * n + sin[:, None] * t)
+            n32, d32 = n.astype(np.float32), d.astype(np.float32)
+            u = np.full((len(s), 3), 0.999, np.float32)  # u3 above F wherever F < 1: refract whenever the sampler can
+            al, wi, W, sd = oracle_sample(pto, P, mz.DIELECTRIC, (1.0, 1.0, 1.0), 0.0, ior, d32, n32, np.full(len(s), front), u)
+            assert al.all() and np.isfinite(wi).all(), (k, front)
+            worst = max(worst, np.abs(np.linalg.norm(wi.astype(np.float64), axis=1) - 1.0).max())
+            refracted += int((sd == -1.0).sum())  # (far from ior 1 the Fresnel term is near 1 and most samples reflect)
+    print("refracted", refracted)
+    assert worst <= 4 * 2.0 ** -23 and refracted >= 500
