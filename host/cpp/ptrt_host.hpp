@@ -83,6 +83,29 @@ public:
         check(pt_denoised_read(ctx_, px.data(), px.size()), ctx_);
         return px;
     }
+    void SetCamera(const pt_camera &cam) { check(pt_scene_set_camera(scene_, &cam), ctx_); } // no new commit needed
+    // docs/SPEC.md §9: reproject the previous call's accumulated image to this frame and blend the last frame in; with `filter` the
+    // §8.2 filter then runs over the result (ReadDenoised). Zeros mean the defaults; the context keeps the history between calls.
+    pt_stats DenoiseTemporal(uint32_t max_history = 0, uint32_t flags = 0, bool filter = true, uint32_t iterations = 0)
+    {
+        pt_temporal_params tp{}; tp.max_history = max_history; tp.flags = flags;
+        pt_denoise_params dp{}; dp.iterations = iterations;
+        pt_stats st{};
+        check(pt_denoise_temporal(ctx_, scene_, &tp, filter ? &dp : nullptr, &st), ctx_);
+        return st;
+    }
+    std::vector<float> ReadTemporal()
+    {
+        std::vector<float> px((size_t)Params.width * Params.height * 4);
+        check(pt_temporal_read(ctx_, px.data(), px.size()), ctx_);
+        return px;
+    }
+    std::vector<float> ReadHistoryLength()
+    {
+        std::vector<float> len((size_t)Params.width * Params.height);
+        check(pt_temporal_history_read(ctx_, len.data(), len.size()), ctx_);
+        return len;
+    }
     void Dispose()
     {
         if (scene_) pt_scene_destroy(scene_);

@@ -153,6 +153,40 @@ public unsafe class HipRenderer : IDisposable
         return g;
     }
 
+    // Move the current scene's camera (no new commit needed)
+    public void SetCamera(PtCamera cam) { Ptrt.Check(Ptrt.pt_scene_set_camera(_scene, &cam), _ctx); }
+
+    // Temporal accumulation (docs/SPEC.md §9), the call of a render-every-frame loop whose camera or geometry moves: reprojects the
+    // previous call's accumulated image to this frame, blends the last Render in, and (filter = true) runs Denoise's filter over the
+    // result. Zeros mean the defaults. ReadTemporal / ReadHistoryLength / ReadDenoised hold until the next Render; the history itself
+    // is kept by the context until reset = true or a change of size. Returns the stats (paths = pixels that took history,
+    // shade_ms = the temporal pass).
+    public PtStats DenoiseTemporal(uint maxHistory = 0, float planeTolerance = 0f, float normalMin = 0f, bool reset = false, bool matchIds = false,
+                                   bool filter = true, uint iterations = 0)
+    {
+        var tp = new PtTemporalParams { max_history = maxHistory, plane_tolerance = planeTolerance, normal_min = normalMin,
+                                        flags = (reset ? (uint)PtTemporalFlags.Reset : 0u) | (matchIds ? (uint)PtTemporalFlags.MatchIds : 0u) };
+        var dp = new PtDenoiseParams { iterations = iterations };
+        PtStats st;
+        Ptrt.Check(Ptrt.pt_denoise_temporal(_ctx, _scene, &tp, filter ? &dp : null, &st), _ctx);
+        return st;
+    }
+
+    public float[] ReadTemporal()
+    {
+        float[] rgba = new float[(ulong)Width * Height * 4];
+        fixed (float* p = rgba) Ptrt.Check(Ptrt.pt_temporal_read(_ctx, p, (ulong)rgba.Length), _ctx);
+        return rgba;
+    }
+
+    // one float per pixel: how many frames the pixel's accumulated colour stands for (1 = it took no history)
+    public float[] ReadHistoryLength()
+    {
+        float[] len = new float[(ulong)Width * Height];
+        fixed (float* p = len) Ptrt.Check(Ptrt.pt_temporal_history_read(_ctx, p, (ulong)len.Length), _ctx);
+        return len;
+    }
+
     internal void* Context => _ctx;
     internal void* Scene => _scene;
 

@@ -16,6 +16,7 @@ public enum PtSceneKind : uint { Cornell = 0, CornellGlass = 1, TriangleSoup = 2
 [Flags] public enum PtTraceFlags : uint { Occlusion = 1, CountVisits = 2, HostMemory = 4 }
 [Flags] public enum PtUpdateFlags : uint { HostMemory = 1 }
 [Flags] public enum PtDenoiseFlags : uint { GuidesOnly = 1, NoEdgeStops = 2 }
+[Flags] public enum PtTemporalFlags : uint { Reset = 1, MatchIds = 2 }
 public enum PtBvhWidth : uint { Default = 0, W2 = 2, W4 = 4, W4Q = 68, W8Q = 72, W8O = 73, BuildLbvh = 0x100 }
 
 [StructLayout(LayoutKind.Sequential)] public unsafe struct PtDeviceDesc { public int device_ordinal; public void* stream; public uint flags; public uint reserved; }
@@ -38,6 +39,7 @@ public enum PtBvhWidth : uint { Default = 0, W2 = 2, W4 = 4, W4Q = 68, W8Q = 72,
 }
 [StructLayout(LayoutKind.Sequential)] public struct PtTileLayout { public uint tile_size; public uint tiles_x; public uint tiles_y; public uint n_tiles; public uint tiles_mine; public uint tiles_per_rank; public ulong floats_per_tile; }
 [StructLayout(LayoutKind.Sequential)] public unsafe struct PtDenoiseParams { public uint iterations; public float sigma_color; public float sigma_normal; public float sigma_depth; public float sigma_albedo; public uint flags; public fixed uint pad[2]; }
+[StructLayout(LayoutKind.Sequential)] public unsafe struct PtTemporalParams { public uint max_history; public float plane_tolerance; public float normal_min; public uint flags; public fixed uint pad[4]; }
 [StructLayout(LayoutKind.Sequential)] public struct PtSceneCounts { public ulong n_tris; public ulong n_spheres; public ulong n_mats; }
 
 public static unsafe class Ptrt
@@ -69,6 +71,10 @@ public static unsafe class Ptrt
     [DllImport(Lib)] public static extern PtStatus pt_denoised_read(void* ctx, float* rgba, ulong n_floats);
     [DllImport(Lib)] public static extern PtStatus pt_denoised_device_ptr(void* ctx, void** dptr, ulong* n_floats);
     [DllImport(Lib)] public static extern PtStatus pt_guides_read(void* ctx, float* g8, ulong n_floats);
+    [DllImport(Lib)] public static extern PtStatus pt_denoise_temporal(void* ctx, void* scene, PtTemporalParams* tp, PtDenoiseParams* dp, PtStats* stats);
+    [DllImport(Lib)] public static extern PtStatus pt_temporal_read(void* ctx, float* rgba, ulong n_floats);
+    [DllImport(Lib)] public static extern PtStatus pt_temporal_device_ptr(void* ctx, void** dptr, ulong* n_floats);
+    [DllImport(Lib)] public static extern PtStatus pt_temporal_history_read(void* ctx, float* len, ulong n_floats);
     [DllImport(Lib)] public static extern PtStatus pt_framebuffer_read(void* ctx, float* rgba, ulong n_floats);
     [DllImport(Lib)] public static extern PtStatus pt_framebuffer_read_rgba8(void* ctx, byte* rgba8, ulong n_bytes);
     [DllImport(Lib)] public static extern PtStatus pt_framebuffer_read_srgb8(void* ctx, byte* rgba8, ulong n_bytes);

@@ -31,7 +31,8 @@ extern "C" {
 /* 2: pt_tuning grew to 40 bytes (extend_kernel, readback); pt_comm_*, pt_framebuffer_read_srgb8, PT_FLAG_EXTEND_POOL, pt_bvh_info.stack_need and
  * the BVH2 default for small scenes had arrived under version 1. pt_trace_rays and PT_TRACE_* arrived later under version 2, and after them
  * pt_scene_update_triangles / pt_scene_update_spheres and PT_UPDATE_HOST_MEMORY, then PT_FLAG_NEXT_EVENT, then pt_denoise, pt_denoise_params,
- * PT_DENOISE_*, pt_denoised_read / pt_denoised_device_ptr and pt_guides_read (additions only: no struct or existing signature changed).
+ * PT_DENOISE_*, pt_denoised_read / pt_denoised_device_ptr and pt_guides_read, then pt_denoise_temporal, pt_temporal_params, PT_TEMPORAL_*,
+ * pt_temporal_read / pt_temporal_device_ptr / pt_temporal_history_read (additions only: no struct or existing signature changed).
  * Hosts compare pt_abi_version() with the header they were built against. */
 #define PTRT_ABI_VERSION 2
 
@@ -244,7 +245,7 @@ pt_status pt_trace_rays(pt_context *ctx, const pt_scene *scene, const void *rays
  *      recomputed by every update and is the caller's signal to commit again. n_nodes, max_depth, stack_need and the layout stay;
  *      build_ms keeps describing the commit. pt_scene_bvh_read returns the refitted blob. A later pt_scene_commit builds from the
  *      updated geometry. An update leaves the context's accumulated sums alone: a PT_FLAG_ACCUMULATE frame after it continues the old
- *      sums (the mean then mixes both geometries). Both calls are synchronous on the context's stream; a refused call leaves the scene
+ *      sums (the mean then mixes both geometries; pt_denoise_temporal is what keeps samples under motion). Both calls are synchronous on the context's stream; a refused call leaves the scene
  *      as it was. Checked in this order: flags, committed (PT_ERR_NOT_COMMITTED), count (must equal the committed count), NULL,
  *      the values (host arrays), then detached scenes (PT_ERR_UNSUPPORTED). */
 /* pt_scene_update_triangles flags */
@@ -294,6 +295,44 @@ pt_status pt_denoise(pt_context *ctx, const pt_scene *scene, const pt_denoise_pa
 pt_status pt_denoised_read(pt_context *ctx, float *rgba, uint64_t n_floats);               /* row-major float4, W*H*4 floats */
 pt_status pt_denoised_device_ptr(pt_context *ctx, void **dptr, uint64_t *n_floats);       /* the same on the device (valid as above) */
 pt_status pt_guides_read(pt_context *ctx, float *g8, uint64_t n_floats);                  /* 8 floats per pixel: g0, g1 (W*H*8 floats) */
+
+/* ---- temporal accumulation (docs/SPEC.md §9): keep samples while the camera or the geometry moves. Each call reprojects the accumulated
+ *      image of the previous call to this frame's pixels through the two cameras and the first-hit guides, rejects what no longer lies on
+ *      the pixel's surface, and blends the new frame in; the unchanged §8.2 filter then runs over the accumulated image. The loop of a host
+ *      that orbits a camera: pt_scene_set_camera / pt_scene_update_triangles, pt_render (1 spp, a new seed), pt_denoise_temporal. */
+/* pt_temporal_params.flags */
+enum {
+    PT_TEMPORAL_RESET = 1u,     /* forget the history first: this call's accumulated image is the frame itself */
+    PT_TEMPORAL_MATCH_IDS = 2u  /* a history tap also needs the primitive id of the pixel it is reprojected from */
+};
+typedef struct pt_temporal_params {
+    uint32_t max_history;   /* cap of a pixel's history length; the new frame weighs at least 1/max_history. 0 = default (32); at most 1048576; 1 = no history */
+    float plane_tolerance;  /* tau_p: a tap's old world position may lie this far off the pixel's plane, times the distance to the old eye. 0 = default */
+    float normal_min;       /* tau_n: least dot(n, n') of a tap. 0 = default; otherwise in (0, 1] */
+    uint32_t flags;
+    uint32_t pad[4];
+} pt_temporal_params; /* 32 B */
+/* One call: traces the guides of `scene` exactly as pt_denoise does, merges the assembled framebuffer with the context's history into the
+ * accumulated image (float4 per pixel: accumulated rgb, the frame's alpha) and the history lengths (1 = the pixel took no history), makes
+ * them, the guides and the scene's camera the new history, and — if dp is non-NULL and lacks PT_DENOISE_GUIDES_ONLY — runs the §8.2 filter
+ * of pt_denoise with the accumulated image in place of the framebuffer. The filtered image is read with pt_denoised_read /
+ * pt_denoised_device_ptr and the guides with pt_guides_read; without a filter pass pt_denoised_* return PT_ERR_NOT_COMMITTED. Synchronous
+ * on the context's stream. Checked in this order; a refused call changes nothing (history, results, what pt_denoise made):
+ *   tp NULL, unknown tp flag bits, max_history > 1048576, a negative, NaN or infinite plane_tolerance, a normal_min
+ *   outside [0, 1] or NaN                                                                                     -> PT_ERR_INVALID_ARGUMENT
+ *   then pt_denoise's checks of dp (when non-NULL), then pt_denoise's checks of ctx, scene and the framebuffer, same order and statuses.
+ * The accumulated image and the lengths stay readable until the context's next pt_render or pt_assemble_tiles (then
+ * PT_ERR_NOT_COMMITTED). The history itself lives in the context across pt_render, pt_denoise, pt_trace_rays and geometry updates; it is
+ * dropped by PT_TEMPORAL_RESET, when the framebuffer's size differs from the history's, and with the context. The framebuffer, the
+ * accumulated sums of PT_FLAG_ACCUMULATE and everything pt_framebuffer_read* return are never touched. Not detected (docs/SPEC.md §9): a
+ * change of lighting on an unmoved surface lags by up to max_history frames; mirrors and glass reproject their own surface; misses never
+ * accumulate. stats (may be NULL): rays = W*H guide rays, paths = pixels that took history, extend_ms the guide pass, shade_ms the
+ * temporal pass, other_ms the filter passes, gpu_ms their sum, iterations = filter passes run. A failed call drains the context's stream
+ * and leaves the history as it was. */
+pt_status pt_denoise_temporal(pt_context *ctx, const pt_scene *scene, const pt_temporal_params *tp, const pt_denoise_params *dp, pt_stats *stats);
+pt_status pt_temporal_read(pt_context *ctx, float *rgba, uint64_t n_floats);          /* the accumulated image, W*H*4 */
+pt_status pt_temporal_device_ptr(pt_context *ctx, void **dptr, uint64_t *n_floats);   /* the same on the device (valid as above) */
+pt_status pt_temporal_history_read(pt_context *ctx, float *len, uint64_t n_floats);   /* W*H history lengths l (1 = no history taken) */
 
 /* ---- results: the reference never reads its image back (it is sampled by the display pass,
  *      Renderer.cs:1042-1121); these replace that consumer. float4 linear radiance, row-major. */

@@ -45,6 +45,7 @@ PT_COMM_FORCE_RCCL, PT_COMM_COPY_EXCHANGE = 1, 2
 PT_TRACE_OCCLUSION, PT_TRACE_COUNT_VISITS, PT_TRACE_HOST_MEMORY = 1, 2, 4
 PT_UPDATE_HOST_MEMORY = 1
 PT_DENOISE_GUIDES_ONLY, PT_DENOISE_NO_EDGE_STOPS = 1, 2
+PT_TEMPORAL_RESET, PT_TEMPORAL_MATCH_IDS = 1, 2
 
 
 class pt_device_desc(C.Structure):
@@ -97,12 +98,17 @@ class pt_denoise_params(C.Structure):
                 ("sigma_albedo", C.c_float), ("flags", C.c_uint32), ("pad", C.c_uint32 * 2)]
 
 
+class pt_temporal_params(C.Structure):
+    _fields_ = [("max_history", C.c_uint32), ("plane_tolerance", C.c_float), ("normal_min", C.c_float), ("flags", C.c_uint32),
+                ("pad", C.c_uint32 * 4)]
+
+
 class pt_scene_counts(C.Structure):
     _fields_ = [("n_tris", C.c_uint64), ("n_spheres", C.c_uint64), ("n_mats", C.c_uint64)]
 
 
 assert C.sizeof(pt_material) == 48 and C.sizeof(pt_camera) == 64 and C.sizeof(pt_render_params) == 64 and C.sizeof(pt_tuning) == 40
-assert C.sizeof(pt_denoise_params) == 32
+assert C.sizeof(pt_denoise_params) == 32 and C.sizeof(pt_temporal_params) == 32
 
 _vp, _u32, _u64, _st = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int32
 _P = C.POINTER
@@ -133,6 +139,10 @@ SYMBOLS = {
     "pt_denoised_read": (_st, [_vp, _vp, _u64]),
     "pt_denoised_device_ptr": (_st, [_vp, _P(_vp), _P(_u64)]),
     "pt_guides_read": (_st, [_vp, _vp, _u64]),
+    "pt_denoise_temporal": (_st, [_vp, _vp, _P(pt_temporal_params), _P(pt_denoise_params), _P(pt_stats)]),
+    "pt_temporal_read": (_st, [_vp, _vp, _u64]),
+    "pt_temporal_device_ptr": (_st, [_vp, _P(_vp), _P(_u64)]),
+    "pt_temporal_history_read": (_st, [_vp, _vp, _u64]),
     "pt_framebuffer_read": (_st, [_vp, _vp, _u64]),
     "pt_framebuffer_read_rgba8": (_st, [_vp, _vp, _u64]),
     "pt_framebuffer_read_srgb8": (_st, [_vp, _vp, _u64]),

@@ -1,5 +1,5 @@
 // context.h — pt_context, and one owner each for what a context keeps between public calls: the assembled frame with the results
-// denoised from it, the partial sums a PT_FLAG_ACCUMULATE frame continues, the frame-start template, the queue sizes a frame's loops
+// denoised from it, the history of pt_denoise_temporal, the partial sums a PT_FLAG_ACCUMULATE frame continues, the frame-start template, the queue sizes a frame's loops
 // read back, and the plumbing of a ray query. Each owner keeps its validity private and offers the few questions and transitions the
 // calls need; nobody else keeps a flag about it. Private to api.cpp, frame.cpp, query.cpp and scene.cpp, as are the helpers every
 // public call uses (defined once, in api.cpp).
@@ -62,7 +62,9 @@ public:
     DevBuf<float4> fb, tiles;
     DevBuf<uint32_t> fb8;
     DevBuf<float4> dn_work, dn_hits, dn_g0, dn_g1, dn_out;
+    DevBuf<float4> tm_out;           // pt_denoise_temporal: accumulated rgb | the frame's alpha
     Event ev_denoise[3];             // start, guides done, filter done (made by the first pt_denoise)
+    Event ev_temporal;               // temporal pass done (made by the first pt_denoise_temporal)
 
     hipError_t resize(uint32_t width, uint32_t height)
     {
@@ -76,7 +78,7 @@ public:
     uint32_t height() const { return h; }
     uint64_t pixels() const { return (uint64_t)w * h; }
 
-    void replace() { holds_ = Holds::nothing; drop_denoised(); } // this call replaces the frame: nothing of the old one is handed out any more
+    void replace() { holds_ = Holds::nothing; drop_denoised(); temporal_ = false; } // this call replaces the frame: nothing of the old one is handed out any more
     // A pt_render that failed: no frame. (Stale-looking and pinned, tests/test_gpu_context_state.py: a call refused before it began to
     // replace the frame — params == NULL, a bad size — ends here too, with the denoised results still readable.)
     void lost() { holds_ = Holds::nothing; }
@@ -85,9 +87,15 @@ public:
     bool readable() const { return holds_ != Holds::nothing; }
 
     void drop_denoised() { guides_ = image_ = false; }      // pt_denoise rewrites its buffers from here on
-    void denoised(bool with_image) { guides_ = true; image_ = with_image; }
+    void denoised(bool with_image) { denoised(with_image, dn_g0.p, dn_g1.p); }
+    void denoised(bool with_image, const float4 *g0, const float4 *g1) { guides_ = true; image_ = with_image; g0_ = g0; g1_ = g1; }
     bool has_guides() const { return guides_; }
     bool has_image() const { return image_; }
+    void guides_from(const float4 *&g0, const float4 *&g1) const { g0 = g0_; g1 = g1_; } // the two planes has_guides() speaks of
+
+    void drop_temporal() { temporal_ = false; }              // pt_denoise_temporal rewrites tm_out from here on
+    void accumulated() { temporal_ = true; }
+    bool has_temporal() const { return temporal_; }
 
     // The tile block outlives the frame: after a reference-sphere or a failed frame it is still the last path-traced frame's (pinned too).
     void tiles_hold(uint32_t pixel_slots) { tile_slots_ = pixel_slots; }
@@ -96,7 +104,44 @@ public:
 private:
     uint32_t w = 0, h = 0, tile_slots_ = 0;
     Holds holds_ = Holds::nothing;
-    bool guides_ = false, image_ = false;
+    bool guides_ = false, image_ = false, temporal_ = false;
+    const float4 *g0_ = nullptr, *g1_ = nullptr;
+};
+
+// What pt_denoise_temporal keeps between calls (docs/SPEC.md §9): the previous successful call's guides, its accumulated colour with the
+// history length in .w, its camera and its size. Two sets of planes: a call reads the front set and writes the back set, and only
+// commit() — the last thing a successful call does — makes the back set the history, so a call that fails on the way leaves the history
+// as it was, and pt_denoise (which writes FrameOutputs' own guide planes) never touches it. Kept across frames, queries and geometry
+// updates; dropped by drop(), by a size change and with the context.
+class TemporalHistory {
+public:
+    struct Planes { const float4 *g0, *g1, *h; };
+    struct Target { float4 *g0, *g1, *h; };
+    DevBuf<uint32_t> taken;          // counter lines of the call under way: pixels that took history (temporal.h)
+
+    // the planes of a w x h call; a history of another size is dropped (its planes may be reallocated)
+    hipError_t reserve(uint32_t width, uint32_t height, size_t counter_words)
+    {
+        if (width != w_ || height != h_) valid_ = false;
+        const size_t n = (size_t)width * height;
+        for (auto &set : sets_)
+            for (auto *b : { &set.g0, &set.g1, &set.h })
+                if (const hipError_t e = b->ensure(n)) { valid_ = false; return e; }
+        return taken.ensure(counter_words);
+    }
+    bool matches(uint32_t width, uint32_t height) const { return valid_ && width == w_ && height == h_; }
+    const pt_camera &camera() const { return cam_; }
+    Planes front() const { const Set &s = sets_[cur_]; return Planes{ s.g0.p, s.g1.p, s.h.p }; }
+    Target back() { Set &s = sets_[cur_ ^ 1u]; return Target{ s.g0.p, s.g1.p, s.h.p }; }
+    void commit(const pt_camera &cam, uint32_t width, uint32_t height) { cur_ ^= 1u; cam_ = cam; w_ = width; h_ = height; valid_ = true; }
+    void drop() { valid_ = false; }
+
+private:
+    struct Set { DevBuf<float4> g0, g1, h; };
+    Set sets_[2];
+    uint32_t cur_ = 0, w_ = 0, h_ = 0;
+    pt_camera cam_{};
+    bool valid_ = false;
 };
 
 // What the partial sums in pt_context::acc hold, for PT_FLAG_ACCUMULATE to continue: the frame geometry they were made with, whether they
@@ -280,5 +325,6 @@ struct pt_context {
     ptrt::Event ev_probe[4];           // brackets of the two probe iterations that pick the extend kernel
     std::vector<ptrt::Event> ev_pool;  // PT_FLAG_PROFILE_KERNELS: three per iteration, made when a frame first needs them (frame.cpp pool_event)
     ptrt::FrameOutputs out;
+    ptrt::TemporalHistory history;
     ptrt::Queries query;
 };

@@ -174,6 +174,10 @@ class Renderer:
         _check(N.lib.pt_scene_set_sky(s, C.byref(sky)), ctx)
         _check(N.lib.pt_scene_commit(s, bvh_width), ctx)
 
+    def SetCamera(self, cam):
+        """Move the current scene's camera (include/ptrt.h pt_scene_set_camera: no new commit needed)."""
+        _check(N.lib.pt_scene_set_camera(self._scene, C.byref(cam)), self._ctx)
+
     def BvhInfo(self):
         info = N.pt_bvh_info()
         _check(N.lib.pt_scene_bvh_info(self._scene, C.byref(info)), self._ctx)
@@ -288,6 +292,41 @@ class Renderer:
         w, h = self.Params.width, self.Params.height
         out = np.empty((h, w, 8), np.float32)
         _check(N.lib.pt_guides_read(self._ctx, _ptr(out), out.size), self._ctx)
+        return out
+
+    def DenoiseTemporal(self, max_history=0, plane_tolerance=0.0, normal_min=0.0, reset=False, match_ids=False, filter=True, **denoise):
+        """Temporal accumulation (include/ptrt.h pt_denoise_temporal, docs/SPEC.md §9): reproject the previous call's accumulated image
+        to the last rendered frame through the two cameras and the first-hit guides, blend the frame in, keep the result as the next
+        history, and — with `filter` — run Denoise's filter over it (`denoise`: Denoise's keyword arguments). Zeros mean the defaults.
+        Returns pt_stats (paths = pixels that took history, shade_ms = the temporal pass). ReadTemporal / ReadHistoryLength /
+        ReadDenoised / ReadGuides hold until the next Render; the history lives in the context until `reset` or a change of size."""
+        tp = N.pt_temporal_params(max_history, plane_tolerance, normal_min,
+                                  (N.PT_TEMPORAL_RESET if reset else 0) | (N.PT_TEMPORAL_MATCH_IDS if match_ids else 0))
+        dp = None
+        if filter:
+            dp = N.pt_denoise_params(denoise.pop("iterations", 0), denoise.pop("sigma_color", 0.0), denoise.pop("sigma_normal", 0.0),
+                                     denoise.pop("sigma_depth", 0.0), denoise.pop("sigma_albedo", 0.0),
+                                     (N.PT_DENOISE_GUIDES_ONLY if denoise.pop("guides_only", False) else 0)
+                                     | (0 if denoise.pop("edge_stops", True) else N.PT_DENOISE_NO_EDGE_STOPS))
+        if denoise:
+            raise TypeError(f"DenoiseTemporal: unknown arguments {sorted(denoise)}")
+        stats = N.pt_stats()
+        _check(N.lib.pt_denoise_temporal(self._ctx, self._scene, C.byref(tp), C.byref(dp) if dp is not None else None, C.byref(stats)),
+               self._ctx)
+        return stats
+
+    def ReadTemporal(self):
+        """The accumulated image of the last DenoiseTemporal, (H, W, 4) float32 (alpha as in the framebuffer), before any filter."""
+        w, h = self.Params.width, self.Params.height
+        out = np.empty((h, w, 4), np.float32)
+        _check(N.lib.pt_temporal_read(self._ctx, _ptr(out), out.size), self._ctx)
+        return out
+
+    def ReadHistoryLength(self):
+        """(H, W) float32: how many frames each pixel's accumulated colour stands for (1 = it took no history)."""
+        w, h = self.Params.width, self.Params.height
+        out = np.empty((h, w), np.float32)
+        _check(N.lib.pt_temporal_history_read(self._ctx, _ptr(out), out.size), self._ctx)
         return out
 
     # Renderer.Update (Renderer.cs:86-89) is empty in the reference
