@@ -2,9 +2,13 @@
 // build a renderer, render N frames, write the image the reference would have shown in its window.
 //   ptrt_cli [--scene reference|cornell|glass|soup|tess] [--detail N] [--size WxH] [--spp N] [--depth N]
 //            [--frames N] [--ppm out.ppm] [--pfm out.pfm] [--gpus N] [--virtual 0|1|2] [--nee] [--denoise N]
+//            [--display clamp|reinhard|aces] [--auto-exposure]
 // --nee: next-event estimation (PT_FLAG_NEXT_EVENT, docs/SPEC.md §7).
 // --denoise N: denoise the last frame with N filter passes (0 = the default; docs/SPEC.md §8) and write the denoised image to --ppm /
 // --pfm instead of the frame (the PPM by SPEC §1's unorm8 rule).
+// --display CURVE: run the display stage (docs/SPEC.md §10: exposure, tone curve, sRGB8 encode on the device) over the last stage that
+// ran — the denoised image with --denoise, else the frame — and write its image to --ppm. --auto-exposure meters the exposure
+// (alone it implies --display clamp).
 // --gpus N: the frame's tiles over N devices of this node, one RCCL gather per frame (pt_comm); with --virtual 1 the N ranks are
 // rendered one after the other on device 0 (rehearsal of the partition on a single GPU); with --virtual 2 every rank has its own
 // context on device 0, the ranks render concurrently (one host thread each) and exchange their tiles by device copies.
@@ -20,9 +24,12 @@ int main(int argc, char **argv)
     std::string scene = "reference", ppm = "frame.ppm", pfm;
     uint32_t w = 1920, h = 1080, detail = 0, spp = 64, depth = 8, frames = 1, gpus = 1, virt = 0, flags = 0;
     int denoise = -1; // filter passes of --denoise (0 = default); -1 = no denoise
+    int curve = -1;   // PT_TONE_* of --display; -1 = no display stage
+    bool auto_exposure = false;
     for (int i = 1; i < argc; i += 2) {
         const std::string a = argv[i];
         if (a == "--nee") { flags |= PT_FLAG_NEXT_EVENT; --i; continue; } // a switch: no value
+        if (a == "--auto-exposure") { auto_exposure = true; --i; continue; }
         if (i + 1 >= argc) { std::fprintf(stderr, "option %s needs a value\n", a.c_str()); return 2; }
         if (a == "--scene") scene = argv[i + 1];
         else if (a == "--detail") detail = (uint32_t)std::strtoul(argv[i + 1], nullptr, 0);
@@ -35,8 +42,14 @@ int main(int argc, char **argv)
         else if (a == "--ppm") ppm = argv[i + 1];
         else if (a == "--pfm") pfm = argv[i + 1];
         else if (a == "--denoise") denoise = std::atoi(argv[i + 1]);
+        else if (a == "--display") {
+            const std::string v = argv[i + 1];
+            curve = v == "clamp" ? PT_TONE_CLAMP : v == "reinhard" ? PT_TONE_REINHARD : v == "aces" ? PT_TONE_ACES : -1;
+            if (curve < 0) { std::fprintf(stderr, "--display takes clamp, reinhard or aces, not %s\n", v.c_str()); return 2; }
+        }
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
+    if (auto_exposure && curve < 0) curve = PT_TONE_CLAMP;
     try {
         std::unique_ptr<ptrt_host::Renderer> single;
         std::unique_ptr<ptrt_host::MultiRenderer> multi;
@@ -71,7 +84,12 @@ int main(int argc, char **argv)
         }
         if (!ppm.empty()) { // 8-bit image = the reference's R8G8B8A8Unorm storage image (Renderer.cs:124)
             std::vector<uint8_t> px;
-            if (denoise >= 0) { // the same rule on the host: docs/SPEC.md §1 unorm8 (NaN -> 0)
+            if (curve >= 0) { // the display stage's own image of the last stage that ran
+                const pt_stats d = r.Display(denoise >= 0 ? PT_DISPLAY_DENOISED : PT_DISPLAY_FRAME, (uint32_t)curve,
+                                             auto_exposure ? PT_DISPLAY_AUTO_EXPOSURE : 0u);
+                std::printf("display: exposure %g, metering %.3f ms, tone %.3f ms\n", (double)r.DisplayInfo().exposure, d.extend_ms, d.other_ms);
+                px = r.ReadDisplay();
+            } else if (denoise >= 0) { // the same rule on the host: docs/SPEC.md §1 unorm8 (NaN -> 0)
                 px.resize(denoised.size());
                 for (size_t i = 0; i < px.size(); ++i) {
                     const float c = denoised[i];

@@ -106,6 +106,37 @@ public:
         check(pt_temporal_history_read(ctx_, len.data(), len.size()), ctx_);
         return len;
     }
+    // The display stage (include/ptrt.h pt_display, docs/SPEC.md §10), where the reference's display pass samples the image
+    // (Renderer.cs:1042-1121): source PT_DISPLAY_*, curve PT_TONE_*, flags PT_DISPLAY_*; the other fields of dp keep their defaults
+    pt_stats Display(uint32_t source = PT_DISPLAY_FRAME, uint32_t curve = PT_TONE_CLAMP, uint32_t flags = 0, float exposure = 0.0f)
+    {
+        pt_display_params dp{}; dp.source = source; dp.curve = curve; dp.flags = flags; dp.exposure = exposure;
+        return Display(dp);
+    }
+    pt_stats Display(const pt_display_params &dp)
+    {
+        pt_stats st{};
+        check(pt_display(ctx_, &dp, &st), ctx_);
+        return st;
+    }
+    std::vector<uint8_t> ReadDisplay()
+    {
+        std::vector<uint8_t> px((size_t)Params.width * Params.height * 4);
+        check(pt_display_read(ctx_, px.data(), px.size()), ctx_);
+        return px;
+    }
+    pt_display_info DisplayInfo()
+    {
+        pt_display_info info{};
+        check(pt_display_info_read(ctx_, &info), ctx_);
+        return info;
+    }
+    std::vector<uint32_t> ReadDisplayHistogram()
+    {
+        std::vector<uint32_t> bins(512);
+        check(pt_display_histogram_read(ctx_, bins.data(), bins.size()), ctx_);
+        return bins;
+    }
     void Dispose()
     {
         if (scene_) pt_scene_destroy(scene_);

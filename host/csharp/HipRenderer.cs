@@ -187,6 +187,45 @@ public unsafe class HipRenderer : IDisposable
         return len;
     }
 
+    // The display stage (docs/SPEC.md §10), what stands where the reference's display pass samples the image (Renderer.cs:1042-1121):
+    // the frame, the denoised or the accumulated image times an exposure, through a tone curve, encoded to sRGB8 (linear: UNORM8) on
+    // the device. autoExposure meters the exposure from a luminance histogram and adapts it from call to call (adapt, key, trims per
+    // mille); exposure then compensates on top. Zeros mean the defaults. ReadDisplay / DisplayInfo / ReadDisplayHistogram hold until
+    // the next Render; the adapted exposure is kept by the context until reset = true.
+    public PtStats Display(PtDisplaySource source = PtDisplaySource.Frame, PtToneCurve curve = PtToneCurve.Clamp, float exposure = 0f,
+                           bool autoExposure = false, float white = 0f, float key = 0f, float adapt = 0f, uint trimLow = 0, uint trimHigh = 0,
+                           bool linear = false, bool reset = false)
+    {
+        var dp = new PtDisplayParams { source = (uint)source, curve = (uint)curve, exposure = exposure, white = white, key = key, adapt = adapt,
+                                       trim_low = trimLow, trim_high = trimHigh,
+                                       flags = (autoExposure ? (uint)PtDisplayFlags.AutoExposure : 0u) | (linear ? (uint)PtDisplayFlags.Linear : 0u)
+                                             | (reset ? (uint)PtDisplayFlags.ResetAdaptation : 0u) };
+        PtStats st;
+        Ptrt.Check(Ptrt.pt_display(_ctx, &dp, &st), _ctx);
+        return st;
+    }
+
+    public byte[] ReadDisplay()
+    {
+        byte[] rgba = new byte[(ulong)Width * Height * 4];
+        fixed (byte* p = rgba) Ptrt.Check(Ptrt.pt_display_read(_ctx, p, (ulong)rgba.Length), _ctx);
+        return rgba;
+    }
+
+    public PtDisplayInfo DisplayInfo()
+    {
+        PtDisplayInfo info;
+        Ptrt.Check(Ptrt.pt_display_info_read(_ctx, &info), _ctx);
+        return info;
+    }
+
+    public uint[] ReadDisplayHistogram()
+    {
+        uint[] bins = new uint[512];
+        fixed (uint* p = bins) Ptrt.Check(Ptrt.pt_display_histogram_read(_ctx, p, (ulong)bins.Length), _ctx);
+        return bins;
+    }
+
     internal void* Context => _ctx;
     internal void* Scene => _scene;
 

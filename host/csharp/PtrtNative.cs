@@ -17,6 +17,9 @@ public enum PtSceneKind : uint { Cornell = 0, CornellGlass = 1, TriangleSoup = 2
 [Flags] public enum PtUpdateFlags : uint { HostMemory = 1 }
 [Flags] public enum PtDenoiseFlags : uint { GuidesOnly = 1, NoEdgeStops = 2 }
 [Flags] public enum PtTemporalFlags : uint { Reset = 1, MatchIds = 2 }
+public enum PtDisplaySource : uint { Frame = 0, Denoised = 1, Temporal = 2 }
+public enum PtToneCurve : uint { Clamp = 0, Reinhard = 1, Aces = 2 }
+[Flags] public enum PtDisplayFlags : uint { AutoExposure = 1, Linear = 2, ResetAdaptation = 4 }
 public enum PtBvhWidth : uint { Default = 0, W2 = 2, W4 = 4, W4Q = 68, W8Q = 72, W8O = 73, BuildLbvh = 0x100 }
 
 [StructLayout(LayoutKind.Sequential)] public unsafe struct PtDeviceDesc { public int device_ordinal; public void* stream; public uint flags; public uint reserved; }
@@ -40,6 +43,8 @@ public enum PtBvhWidth : uint { Default = 0, W2 = 2, W4 = 4, W4Q = 68, W8Q = 72,
 [StructLayout(LayoutKind.Sequential)] public struct PtTileLayout { public uint tile_size; public uint tiles_x; public uint tiles_y; public uint n_tiles; public uint tiles_mine; public uint tiles_per_rank; public ulong floats_per_tile; }
 [StructLayout(LayoutKind.Sequential)] public unsafe struct PtDenoiseParams { public uint iterations; public float sigma_color; public float sigma_normal; public float sigma_depth; public float sigma_albedo; public uint flags; public fixed uint pad[2]; }
 [StructLayout(LayoutKind.Sequential)] public unsafe struct PtTemporalParams { public uint max_history; public float plane_tolerance; public float normal_min; public uint flags; public fixed uint pad[4]; }
+[StructLayout(LayoutKind.Sequential)] public struct PtDisplayParams { public uint source; public uint curve; public float exposure; public float white; public float key; public float adapt; public uint trim_low; public uint trim_high; public uint flags; public uint pad; }
+[StructLayout(LayoutKind.Sequential)] public struct PtDisplayInfo { public float exposure; public float metered; public float log_average; public uint adapted; public ulong counted; public ulong used; }
 [StructLayout(LayoutKind.Sequential)] public struct PtSceneCounts { public ulong n_tris; public ulong n_spheres; public ulong n_mats; }
 
 public static unsafe class Ptrt
@@ -75,6 +80,11 @@ public static unsafe class Ptrt
     [DllImport(Lib)] public static extern PtStatus pt_temporal_read(void* ctx, float* rgba, ulong n_floats);
     [DllImport(Lib)] public static extern PtStatus pt_temporal_device_ptr(void* ctx, void** dptr, ulong* n_floats);
     [DllImport(Lib)] public static extern PtStatus pt_temporal_history_read(void* ctx, float* len, ulong n_floats);
+    [DllImport(Lib)] public static extern PtStatus pt_display(void* ctx, PtDisplayParams* dp, PtStats* stats);
+    [DllImport(Lib)] public static extern PtStatus pt_display_read(void* ctx, byte* rgba8, ulong n_bytes);
+    [DllImport(Lib)] public static extern PtStatus pt_display_device_ptr(void* ctx, void** dptr, ulong* n_bytes);
+    [DllImport(Lib)] public static extern PtStatus pt_display_info_read(void* ctx, PtDisplayInfo* info);
+    [DllImport(Lib)] public static extern PtStatus pt_display_histogram_read(void* ctx, uint* bins, ulong n_words);
     [DllImport(Lib)] public static extern PtStatus pt_framebuffer_read(void* ctx, float* rgba, ulong n_floats);
     [DllImport(Lib)] public static extern PtStatus pt_framebuffer_read_rgba8(void* ctx, byte* rgba8, ulong n_bytes);
     [DllImport(Lib)] public static extern PtStatus pt_framebuffer_read_srgb8(void* ctx, byte* rgba8, ulong n_bytes);

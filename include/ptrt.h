@@ -32,7 +32,9 @@ extern "C" {
  * the BVH2 default for small scenes had arrived under version 1. pt_trace_rays and PT_TRACE_* arrived later under version 2, and after them
  * pt_scene_update_triangles / pt_scene_update_spheres and PT_UPDATE_HOST_MEMORY, then PT_FLAG_NEXT_EVENT, then pt_denoise, pt_denoise_params,
  * PT_DENOISE_*, pt_denoised_read / pt_denoised_device_ptr and pt_guides_read, then pt_denoise_temporal, pt_temporal_params, PT_TEMPORAL_*,
- * pt_temporal_read / pt_temporal_device_ptr / pt_temporal_history_read (additions only: no struct or existing signature changed).
+ * pt_temporal_read / pt_temporal_device_ptr / pt_temporal_history_read, then pt_display, pt_display_params, pt_display_info, PT_DISPLAY_*,
+ * PT_TONE_*, pt_display_read / pt_display_device_ptr / pt_display_info_read / pt_display_histogram_read (additions only: no struct or
+ * existing signature changed).
  * Hosts compare pt_abi_version() with the header they were built against. */
 #define PTRT_ABI_VERSION 2
 
@@ -333,6 +335,52 @@ pt_status pt_denoise_temporal(pt_context *ctx, const pt_scene *scene, const pt_t
 pt_status pt_temporal_read(pt_context *ctx, float *rgba, uint64_t n_floats);          /* the accumulated image, W*H*4 */
 pt_status pt_temporal_device_ptr(pt_context *ctx, void **dptr, uint64_t *n_floats);   /* the same on the device (valid as above) */
 pt_status pt_temporal_history_read(pt_context *ctx, float *len, uint64_t n_floats);   /* W*H history lengths l (1 = no history taken) */
+
+/* ---- display (docs/SPEC.md §10). The reference's display pass samples the image and writes it to an sRGB swapchain
+ *      (Renderer.cs:1042-1121); pt_framebuffer_read_srgb8 reproduces exactly that, 8-bit quantisation first and no tone mapping. pt_display
+ *      is the path tracer's own last stage: it takes the frame, the denoised image or the accumulated image as floats, multiplies by an
+ *      exposure (given, or metered from a luminance histogram and adapted from call to call), applies a tone curve and encodes each float
+ *      directly to sRGB8, so the dark codes the 8-bit detour skips are all there. */
+enum { PT_DISPLAY_FRAME = 0, PT_DISPLAY_DENOISED = 1, PT_DISPLAY_TEMPORAL = 2 };          /* pt_display_params.source */
+enum { PT_TONE_CLAMP = 0, PT_TONE_REINHARD = 1, PT_TONE_ACES = 2 };                        /* pt_display_params.curve */
+enum { PT_DISPLAY_AUTO_EXPOSURE = 1u, PT_DISPLAY_LINEAR = 2u, PT_DISPLAY_RESET_ADAPTATION = 4u }; /* pt_display_params.flags */
+typedef struct pt_display_params {
+    uint32_t source, curve;
+    float exposure;   /* linear multiplier (with AUTO: compensation on top of the metered one); 0 = 1; else in [2^-40, 2^40] */
+    float white;      /* PT_TONE_REINHARD: the value that maps to 1; 0 = 4; else in [2^-20, 2^20] */
+    float key;        /* AUTO: where the log-average luminance is put; 0 = 0.18f; else in [2^-20, 2^20] */
+    float adapt;      /* AUTO: share of the way from the previous call's exposure to the metered one; 0 = 1; else in (0, 1] */
+    uint32_t trim_low, trim_high; /* AUTO: per mille of the metered pixels ignored at the dark / bright end; trim_low + trim_high < 1000 */
+    uint32_t flags, pad;
+} pt_display_params; /* 40 B */
+typedef struct pt_display_info {
+    float exposure;      /* E: what every pixel was multiplied by */
+    float metered;       /* E_t of this call (0 without AUTO, or when nothing was metered) */
+    float log_average;   /* Y_avg (0 likewise) */
+    uint32_t adapted;    /* 1: an earlier call's exposure was blended in */
+    uint64_t counted, used; /* N and N' of docs/SPEC.md §10: pixels of positive luminance, and those left after the trim */
+} pt_display_info; /* 32 B */
+/* One call: meters the source (PT_DISPLAY_AUTO_EXPOSURE only), multiplies every pixel by the exposure, applies the curve and writes one
+ * R | G<<8 | B<<16 | A<<24 word per pixel — sRGB codes, or linear UNORM8 codes with PT_DISPLAY_LINEAR; alpha is always the source's
+ * alpha as UNORM8. Synchronous on the context's stream. Checked in this order; a refused call changes nothing (neither the displayed
+ * image nor the adaptation state):
+ *   dp NULL, an unknown source / curve / flag bit, a field outside its range above or NaN, trim_low + trim_high >= 1000
+ *                                                                                                             -> PT_ERR_INVALID_ARGUMENT
+ *   ctx NULL                                                                                                  -> PT_ERR_INVALID_ARGUMENT
+ *   the source is not there: FRAME needs what pt_framebuffer_read needs (a frame of either mode), DENOISED what pt_denoised_read needs,
+ *   TEMPORAL what pt_temporal_read needs                                                                      -> PT_ERR_NOT_COMMITTED
+ * The 8-bit image, the info and the histogram are results of the frame the framebuffer holds: they stay readable across pt_denoise,
+ * pt_denoise_temporal and pt_trace_rays until the context's next pt_render or pt_assemble_tiles (then PT_ERR_NOT_COMMITTED). The
+ * adaptation state is one f32, the last adapted exposure: it lives in the context across all calls, is read and written by AUTO calls
+ * only, and is dropped by PT_DISPLAY_RESET_ADAPTATION (before the call meters; without AUTO the flag just drops it) and with the
+ * context. The framebuffer, the sums, the denoised and temporal results and the temporal history are never touched. stats (may be NULL):
+ * paths = W*H, extend_ms the metering kernels, other_ms the tone kernel, gpu_ms their sum, everything else 0. A failed call drains the
+ * context's stream and leaves the adaptation state as it was. */
+pt_status pt_display(pt_context *ctx, const pt_display_params *dp, pt_stats *stats);
+pt_status pt_display_read(pt_context *ctx, uint8_t *rgba8, uint64_t n_bytes);              /* W*H*4, RGBA byte order */
+pt_status pt_display_device_ptr(pt_context *ctx, void **dptr, uint64_t *n_bytes);          /* the same on the device (valid as above) */
+pt_status pt_display_info_read(pt_context *ctx, pt_display_info *out);
+pt_status pt_display_histogram_read(pt_context *ctx, uint32_t *bins, uint64_t n_words);   /* 512 words; all 0 without AUTO */
 
 /* ---- results: the reference never reads its image back (it is sampled by the display pass,
  *      Renderer.cs:1042-1121); these replace that consumer. float4 linear radiance, row-major. */

@@ -46,6 +46,9 @@ PT_TRACE_OCCLUSION, PT_TRACE_COUNT_VISITS, PT_TRACE_HOST_MEMORY = 1, 2, 4
 PT_UPDATE_HOST_MEMORY = 1
 PT_DENOISE_GUIDES_ONLY, PT_DENOISE_NO_EDGE_STOPS = 1, 2
 PT_TEMPORAL_RESET, PT_TEMPORAL_MATCH_IDS = 1, 2
+PT_DISPLAY_FRAME, PT_DISPLAY_DENOISED, PT_DISPLAY_TEMPORAL = 0, 1, 2
+PT_TONE_CLAMP, PT_TONE_REINHARD, PT_TONE_ACES = 0, 1, 2
+PT_DISPLAY_AUTO_EXPOSURE, PT_DISPLAY_LINEAR, PT_DISPLAY_RESET_ADAPTATION = 1, 2, 4
 
 
 class pt_device_desc(C.Structure):
@@ -103,12 +106,23 @@ class pt_temporal_params(C.Structure):
                 ("pad", C.c_uint32 * 4)]
 
 
+class pt_display_params(C.Structure):
+    _fields_ = [("source", C.c_uint32), ("curve", C.c_uint32), ("exposure", C.c_float), ("white", C.c_float), ("key", C.c_float),
+                ("adapt", C.c_float), ("trim_low", C.c_uint32), ("trim_high", C.c_uint32), ("flags", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class pt_display_info(C.Structure):
+    _fields_ = [("exposure", C.c_float), ("metered", C.c_float), ("log_average", C.c_float), ("adapted", C.c_uint32),
+                ("counted", C.c_uint64), ("used", C.c_uint64)]
+
+
 class pt_scene_counts(C.Structure):
     _fields_ = [("n_tris", C.c_uint64), ("n_spheres", C.c_uint64), ("n_mats", C.c_uint64)]
 
 
 assert C.sizeof(pt_material) == 48 and C.sizeof(pt_camera) == 64 and C.sizeof(pt_render_params) == 64 and C.sizeof(pt_tuning) == 40
 assert C.sizeof(pt_denoise_params) == 32 and C.sizeof(pt_temporal_params) == 32
+assert C.sizeof(pt_display_params) == 40 and C.sizeof(pt_display_info) == 32
 
 _vp, _u32, _u64, _st = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int32
 _P = C.POINTER
@@ -143,6 +157,11 @@ SYMBOLS = {
     "pt_temporal_read": (_st, [_vp, _vp, _u64]),
     "pt_temporal_device_ptr": (_st, [_vp, _P(_vp), _P(_u64)]),
     "pt_temporal_history_read": (_st, [_vp, _vp, _u64]),
+    "pt_display": (_st, [_vp, _P(pt_display_params), _P(pt_stats)]),
+    "pt_display_read": (_st, [_vp, _vp, _u64]),
+    "pt_display_device_ptr": (_st, [_vp, _P(_vp), _P(_u64)]),
+    "pt_display_info_read": (_st, [_vp, _P(pt_display_info)]),
+    "pt_display_histogram_read": (_st, [_vp, _vp, _u64]),
     "pt_framebuffer_read": (_st, [_vp, _vp, _u64]),
     "pt_framebuffer_read_rgba8": (_st, [_vp, _vp, _u64]),
     "pt_framebuffer_read_srgb8": (_st, [_vp, _vp, _u64]),

@@ -1,5 +1,5 @@
 // context.h — pt_context, and one owner each for what a context keeps between public calls: the assembled frame with the results
-// denoised from it, the history of pt_denoise_temporal, the partial sums a PT_FLAG_ACCUMULATE frame continues, the frame-start template, the queue sizes a frame's loops
+// denoised and displayed from it, the history of pt_denoise_temporal, the exposure pt_display adapts from, the partial sums a PT_FLAG_ACCUMULATE frame continues, the frame-start template, the queue sizes a frame's loops
 // read back, and the plumbing of a ray query. Each owner keeps its validity private and offers the few questions and transitions the
 // calls need; nobody else keeps a flag about it. Private to api.cpp, frame.cpp, query.cpp and scene.cpp, as are the helpers every
 // public call uses (defined once, in api.cpp).
@@ -52,10 +52,10 @@ struct CounterView {
     uint32_t error() const { return word(kCntError); } // 1 = traversal stack overflow, 2 = step limit
 };
 
-// What a context hands out: the assembled frame (float and UNORM8), this rank's tile block, and what pt_denoise made of the frame
+// What a context hands out: the assembled frame (float and UNORM8), this rank's tile block, what pt_denoise made of the frame
 // (docs/SPEC.md §8: guide rays in dn_work — 2 rows per pixel; then the filter's two ping-pong images —, their hits, the two guide planes and
-// the denoised image). The denoised results are results of the frame the framebuffer holds: they have its size, and they go when a call
-// begins to replace it.
+// the denoised image) and what pt_display made of it (§10). The denoised and displayed results are results of the frame the framebuffer
+// holds: they have its size, and they go when a call begins to replace it.
 class FrameOutputs {
 public:
     enum class Holds { nothing, path_traced, reference_sphere };
@@ -65,6 +65,9 @@ public:
     DevBuf<float4> tm_out;           // pt_denoise_temporal: accumulated rgb | the frame's alpha
     Event ev_denoise[3];             // start, guides done, filter done (made by the first pt_denoise)
     Event ev_temporal;               // temporal pass done (made by the first pt_denoise_temporal)
+    DevBuf<uint32_t> disp8;          // pt_display: one R | G<<8 | B<<16 | A<<24 word per pixel
+    DevBuf<uint32_t> disp_meter;     // its 512 histogram words, then its pt_display_info (display.h kDisplayMeterWords)
+    Event ev_display[3];             // start, metering done, tone pass done (made by the first pt_display)
 
     hipError_t resize(uint32_t width, uint32_t height)
     {
@@ -78,7 +81,7 @@ public:
     uint32_t height() const { return h; }
     uint64_t pixels() const { return (uint64_t)w * h; }
 
-    void replace() { holds_ = Holds::nothing; drop_denoised(); temporal_ = false; } // this call replaces the frame: nothing of the old one is handed out any more
+    void replace() { holds_ = Holds::nothing; drop_denoised(); temporal_ = false; displayed_ = false; } // this call replaces the frame: nothing of the old one is handed out any more
     // A pt_render that failed: no frame. (Stale-looking and pinned, tests/test_gpu_context_state.py: a call refused before it began to
     // replace the frame — params == NULL, a bad size — ends here too, with the denoised results still readable.)
     void lost() { holds_ = Holds::nothing; }
@@ -97,6 +100,10 @@ public:
     void accumulated() { temporal_ = true; }
     bool has_temporal() const { return temporal_; }
 
+    void drop_display() { displayed_ = false; }              // pt_display rewrites disp8 and disp_meter from here on
+    void displayed() { displayed_ = true; }
+    bool has_display() const { return displayed_; }
+
     // The tile block outlives the frame: after a reference-sphere or a failed frame it is still the last path-traced frame's (pinned too).
     void tiles_hold(uint32_t pixel_slots) { tile_slots_ = pixel_slots; }
     uint32_t tile_slots() const { return tile_slots_; }
@@ -104,7 +111,7 @@ public:
 private:
     uint32_t w = 0, h = 0, tile_slots_ = 0;
     Holds holds_ = Holds::nothing;
-    bool guides_ = false, image_ = false, temporal_ = false;
+    bool guides_ = false, image_ = false, temporal_ = false, displayed_ = false;
     const float4 *g0_ = nullptr, *g1_ = nullptr;
 };
 
@@ -141,6 +148,25 @@ private:
     Set sets_[2];
     uint32_t cur_ = 0, w_ = 0, h_ = 0;
     pt_camera cam_{};
+    bool valid_ = false;
+};
+
+// What pt_display keeps between calls (docs/SPEC.md §10): one f32 on the device, the last adapted exposure E_a. Two slots, as the temporal
+// history has two sets of planes: a metering call reads the front slot (when there is a state) and its resolve kernel writes the back
+// slot; only commit() — after the call's final synchronise succeeded — makes that the state, so a call that fails leaves it as it was.
+// Kept across every other call; dropped by drop() and with the context. Calls without PT_DISPLAY_AUTO_EXPOSURE never look at it.
+class DisplayAdaptation {
+public:
+    hipError_t reserve() { return slots_.ensure(2); }
+    bool valid() const { return valid_; }
+    const float *front() const { return slots_.p + cur_; }
+    float *back() { return slots_.p + (cur_ ^ 1u); }
+    void commit() { cur_ ^= 1u; valid_ = true; }
+    void drop() { valid_ = false; }
+
+private:
+    DevBuf<float> slots_;
+    uint32_t cur_ = 0;
     bool valid_ = false;
 };
 
@@ -326,5 +352,6 @@ struct pt_context {
     std::vector<ptrt::Event> ev_pool;  // PT_FLAG_PROFILE_KERNELS: three per iteration, made when a frame first needs them (frame.cpp pool_event)
     ptrt::FrameOutputs out;
     ptrt::TemporalHistory history;
+    ptrt::DisplayAdaptation adaptation;
     ptrt::Queries query;
 };

@@ -329,6 +329,43 @@ class Renderer:
         _check(N.lib.pt_temporal_history_read(self._ctx, _ptr(out), out.size), self._ctx)
         return out
 
+    _DISPLAY_SOURCES = {"frame": N.PT_DISPLAY_FRAME, "denoised": N.PT_DISPLAY_DENOISED, "temporal": N.PT_DISPLAY_TEMPORAL}
+    _TONE_CURVES = {"clamp": N.PT_TONE_CLAMP, "reinhard": N.PT_TONE_REINHARD, "aces": N.PT_TONE_ACES}
+
+    def Display(self, source="frame", curve="clamp", exposure=0.0, auto=False, white=0.0, key=0.0, adapt=0.0, trim_low=0, trim_high=0,
+                linear=False, reset=False):
+        """The display stage (include/ptrt.h pt_display, docs/SPEC.md §10) — what stands where the reference's display pass samples the
+        image (Renderer.cs:1042-1121): the frame, the denoised or the accumulated image times an exposure, through a tone curve, encoded
+        to sRGB8 (`linear`: UNORM8) on the device. `auto` meters the exposure from a luminance histogram (`key`, `trim_*` per mille)
+        and moves `adapt` of the way from the previous call's exposure to it; `exposure` then compensates on top. Zeros mean the
+        defaults. Returns pt_stats (extend_ms = metering, other_ms = tone pass). ReadDisplay / DisplayInfo / ReadDisplayHistogram hold
+        until the next Render; the adapted exposure lives in the context until `reset`."""
+        dp = N.pt_display_params(self._DISPLAY_SOURCES[source], self._TONE_CURVES[curve], exposure, white, key, adapt, trim_low, trim_high,
+                                 (N.PT_DISPLAY_AUTO_EXPOSURE if auto else 0) | (N.PT_DISPLAY_LINEAR if linear else 0)
+                                 | (N.PT_DISPLAY_RESET_ADAPTATION if reset else 0))
+        stats = N.pt_stats()
+        _check(N.lib.pt_display(self._ctx, C.byref(dp), C.byref(stats)), self._ctx)
+        return stats
+
+    def ReadDisplay(self):
+        """The displayed image of the last Display, (H, W, 4) uint8 in RGBA order."""
+        w, h = self.Params.width, self.Params.height
+        out = np.empty((h, w, 4), np.uint8)
+        _check(N.lib.pt_display_read(self._ctx, _ptr(out), out.size), self._ctx)
+        return out
+
+    def DisplayInfo(self):
+        """pt_display_info of the last Display: the exposure applied, the metered one, the log-average luminance, the pixel counts."""
+        info = N.pt_display_info()
+        _check(N.lib.pt_display_info_read(self._ctx, C.byref(info)), self._ctx)
+        return info
+
+    def ReadDisplayHistogram(self):
+        """The 512 luminance bins the last Display metered (uint32; 8 bins per octave from 2^-32; all 0 without `auto`)."""
+        out = np.empty(512, np.uint32)
+        _check(N.lib.pt_display_histogram_read(self._ctx, _ptr(out), out.size), self._ctx)
+        return out
+
     # Renderer.Update (Renderer.cs:86-89) is empty in the reference
     def Update(self, deltaTime):
         pass
@@ -364,11 +401,11 @@ class Renderer:
         _check(N.lib.pt_framebuffer_read_srgb8(self._ctx, _ptr(out), out.size), self._ctx)
         return out
 
-    def SaveImage(self, path, srgb=False):
+    def SaveImage(self, path, srgb=False, display=False):
         """Image output — what replaces the reference's window (display path Renderer.cs:1042-1121).
         `.ppm`: 8-bit, the clamp-and-round R8G8B8A8Unorm image of Renderer.cs:124 — or, with srgb=True, what the reference's
-        sRGB swapchain shows of it (SwapChain.cs:157-158; no tone mapping, values above 1 clip); `.pfm`: linear float radiance,
-        bottom-up rows."""
+        sRGB swapchain shows of it (SwapChain.cs:157-158; no tone mapping, values above 1 clip) — or, with display=True, the image
+        of the last Display (exposed, tone-mapped, encoded from the floats); `.pfm`: linear float radiance, bottom-up rows."""
         w, h = self.Params.width, self.Params.height
         if path.lower().endswith(".pfm"):
             rgb = np.ascontiguousarray(self.ReadFramebuffer()[::-1, :, :3], "<f4")
@@ -376,7 +413,8 @@ class Renderer:
                 f.write(b"PF\n%d %d\n-1.0\n" % (w, h))
                 f.write(rgb.tobytes())
         else:
-            rgb = np.ascontiguousarray((self.ReadFramebufferSRGB8() if srgb else self.ReadFramebufferRGBA8())[..., :3])
+            img = self.ReadDisplay() if display else self.ReadFramebufferSRGB8() if srgb else self.ReadFramebufferRGBA8()
+            rgb = np.ascontiguousarray(img[..., :3])
             with open(path, "wb") as f:
                 f.write(b"P6\n%d %d\n255\n" % (w, h))
                 f.write(rgb.tobytes())
