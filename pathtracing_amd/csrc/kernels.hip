@@ -156,7 +156,7 @@ PT_DEV bool slot_pixel(uint32_t slot_all, const FrameParams &fp, uint32_t &x, ui
     return x < fp.width && y < fp.height;
 }
 
-PT_DEV void camera_ray_of(const pt_camera &c, uint32_t x, uint32_t y, uint32_t key, V3 &o, V3 &d)
+PT_DEV Camera camera_of(const pt_camera &c)
 {
     Camera k;
     k.origin[0] = c.origin[0]; k.origin[1] = c.origin[1]; k.origin[2] = c.origin[2];
@@ -164,8 +164,10 @@ PT_DEV void camera_ray_of(const pt_camera &c, uint32_t x, uint32_t y, uint32_t k
     k.right[0] = c.right[0]; k.right[1] = c.right[1]; k.right[2] = c.right[2];
     k.up[0] = c.up[0]; k.up[1] = c.up[1]; k.up[2] = c.up[2];
     k.scale = c.scale; k.cx = c.cx; k.cy = c.cy; k.jitter = c.jitter;
-    camera_ray(k, x, y, key, o, d);
+    return k;
 }
+PT_DEV void camera_ray_of(const pt_camera &c, uint32_t x, uint32_t y, uint32_t key, V3 &o, V3 &d) { camera_ray(camera_of(c), x, y, key, o, d); }
+PT_DEV V3 camera_vec_of(const pt_camera &c, uint32_t x, uint32_t y, float jx, float jy) { return camera_vec(camera_of(c), x, y, jx, jy); }
 
 // ------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(kBlock) k_reference_sphere(uint32_t w, uint32_t h, float4 *out_f, uint32_t *out8)
@@ -534,6 +536,9 @@ PT_DEV bool next_sample(const DeviceScene &sc, const FrameParams &fp, uint32_t s
 // NEE (k_extend<.., NEE> only): emission hits of light-set triangles after a Lambert vertex are weighted by w_b, and a Lambert vertex
 // below max_depth samples a light (from the T that arrived at it); a traced sample leaves the shadow ray in (r.o, r.d, nr->aux) with
 // NEE_PENDING set (and NEE_END when the path ends at this vertex), so that the caller's next pass resolves it (resolve_shadow).
+// With SHADE_QUEUE / SHADE_BUCKETS and without NEE, the new direction of a Lambert vertex and of a regenerated camera ray are made in one
+// pass at the end (see there). The all-kinds SHADE_INLINE kernels keep one branch per kind: with the shared end they spill registers
+// that the two-branch form leaves them (k_extend<.., SHADE_INLINE> 1 to 5 VGPRs more, k_extend_packed<.., SHADE_INLINE> 4).
 template <int MODE, bool NEE = false>
 PT_DEV bool shade_one(const DeviceScene &sc, const PathState &ps, const FrameParams &fp, uint32_t slot, PathRegs &r, float t, uint32_t ref,
                       uint32_t b, uint32_t &defer, NeeRegs *nr = nullptr)
@@ -546,6 +551,8 @@ PT_DEV bool shade_one(const DeviceScene &sc, const PathState &ps, const FramePar
     // + metal 31.9 -> 31.7, soup 68.2 -> 67.6, 1M-triangle Cornell +-0); written back only if touched.
     float4 A = at(ps.acc, slot);
     bool touched = false, term = false, alive = false;
+    constexpr bool SHARED = !NEE && MODE != SHADE_INLINE;
+    bool lambert = false, regen = false; // which lanes take a new direction at the shared end: a Lambert vertex that goes on, a new sample
     auto add = [&](V3 L) {
         touched = true;
         A.x = fma_(T.x, L.x, A.x); A.y = fma_(T.y, L.y, A.y); A.z = fma_(T.z, L.z, A.z);
@@ -599,72 +606,101 @@ PT_DEV bool shade_one(const DeviceScene &sc, const PathState &ps, const FramePar
         else {
             const uint32_t bb = depth - 1u;
             const uint32_t bk = MODE == SHADE_QUEUE ? (uint32_t)B_LAMBERT : MODE == SHADE_BUCKETS ? b : 1u + kind;
-            BsdfSample bs;
-            if (bk == B_LAMBERT) bs = sample_lambert(alb, n, u01(key, 4u + 4u * bb), u01(key, 5u + 4u * bb));
-            else if (bk == B_METAL) bs = sample_metal(alb, m1.w, d, n, u01(key, 4u + 4u * bb), u01(key, 5u + 4u * bb));
-            else bs = sample_dielectric(alb, m2.x, d, n, front, u01(key, 6u + 4u * bb));
-            const V3 wi = bs.wi, W = bs.W;
-            const float side = bs.side;
-            V3 ta = T; // NEE: T * albedo of a Lambert vertex (W = albedo), before Russian roulette
-            if (!bs.ok) term = true;
-            else {
-                T = v3(T.x * W.x, T.y * W.y, T.z * W.z);
-                ta = T;
+            if (SHARED && bk == B_LAMBERT) {
+                // A Lambert vertex's weight is its albedo, whatever direction it samples: the path's end is decided first, and the
+                // direction is drawn at the shared end of this function by the lanes that go on
+                T = v3(T.x * alb.x, T.y * alb.y, T.z * alb.z);
                 if (!(fmax_(T.x, fmax_(T.y, T.z)) > 0.0f)) term = true;
                 else if (depth >= fp.rr_start) {
                     const float qrr = fmin_(fmax_(T.x, fmax_(T.y, T.z)), 0.95f);
                     if (!(u01(key, 7u + 4u * bb) < qrr)) term = true;
                     else { const float iq = 1.0f / qrr; T = v3(T.x * iq, T.y * iq, T.z * iq); }
                 }
-                if (!term) { o = madd(side * fp.ray_eps, n, P); d = wi; }
-            }
-            if constexpr (NEE) {
-                const NeeArgs &na = cold_nee();
-                // the pdf of the extension ray, for the w_b of the emission it may find (Lambert vertices only)
-                if (!term) nr->aux = (bk == B_LAMBERT && na.n_lights) ? dot(n, wi) * kInvPi : 0.0f;
-                // §7 light sample of a Lambert vertex. Computed after the BSDF sample and Russian roulette to keep it out of their registers;
-                // its random numbers are its own (dimensions 1024 + 3b ..) and it uses only T * albedo of the T that arrived here.
-                if (bk == B_LAMBERT && na.n_lights) {
-                    const float4 *lr = na.lights + (size_t)pick_light(na.cdf, na.n_lights, u01(key, 1024u + 3u * bb)) * 4;
-                    const float4 l0 = lr[0], l1 = lr[1], l2 = lr[2];
-                    const float su = __builtin_sqrtf(u01(key, 1025u + 3u * bb)), b1 = 1.0f - su, b2 = u01(key, 1026u + 3u * bb) * su;
-                    const V3 x = v3(fma_(b2, l2.x, fma_(b1, l1.x, l0.x)), fma_(b2, l2.y, fma_(b1, l1.y, l0.y)), fma_(b2, l2.z, fma_(b1, l1.z, l0.z)));
-                    const V3 so = madd(fp.ray_eps, n, P); // the continuation origin of a Lambert vertex (side +1)
-                    const V3 dl = x - so;
-                    const float dist2 = dot(dl, dl), dist = __builtin_sqrtf(dist2), inv = 1.0f / dist;
-                    const V3 sd = v3(dl.x * inv, dl.y * inv, dl.z * inv);
-                    const float4 l3 = lr[3];
-                    const float cs = dot(n, sd), cl = __builtin_fabsf(dot(xyz(l3), sd));
-                    if (cs > 0.0f && cl > 0.0f) { // the shadow ray goes first; the extension ray (if the path goes on) waits in NeeArgs::ext
-                        const float pl = (l0.w * dist2) / cl, q = (cs * kInvPi) / pl;
-                        const float f = nan_to_zero(q / fma_(q, q, 1.0f)); // w_l * pdf_bsdf / pdf_light
-                        at(na.rad, slot) = make_float4((ta.x * f) * l1.w, (ta.y * f) * l2.w, (ta.z * f) * l3.w, 0.0f);
-                        if (!term) at(na.ext, slot) = make_float4(d.x, d.y, d.z, nr->aux);
-                        nr->flags = NEE_PENDING | (term ? NEE_END : 0u);
-                        nr->aux = dist * 0.9999f;
-                        o = so; d = sd;
-                        term = false;
+                if (!term) { o = madd(fp.ray_eps, n, P); d = n; lambert = true; } // d: the normal, until the shared end replaces it
+            } else {
+                BsdfSample bs;
+                if (bk == B_LAMBERT) bs = sample_lambert(alb, n, u01(key, 4u + 4u * bb), u01(key, 5u + 4u * bb));
+                else if (bk == B_METAL) bs = sample_metal(alb, m1.w, d, n, u01(key, 4u + 4u * bb), u01(key, 5u + 4u * bb));
+                else bs = sample_dielectric(alb, m2.x, d, n, front, u01(key, 6u + 4u * bb));
+                const V3 wi = bs.wi, W = bs.W;
+                const float side = bs.side;
+                V3 ta = T; // NEE: T * albedo of a Lambert vertex (W = albedo), before Russian roulette
+                if (!bs.ok) term = true;
+                else {
+                    T = v3(T.x * W.x, T.y * W.y, T.z * W.z);
+                    ta = T;
+                    if (!(fmax_(T.x, fmax_(T.y, T.z)) > 0.0f)) term = true;
+                    else if (depth >= fp.rr_start) {
+                        const float qrr = fmin_(fmax_(T.x, fmax_(T.y, T.z)), 0.95f);
+                        if (!(u01(key, 7u + 4u * bb) < qrr)) term = true;
+                        else { const float iq = 1.0f / qrr; T = v3(T.x * iq, T.y * iq, T.z * iq); }
+                    }
+                    if (!term) { o = madd(side * fp.ray_eps, n, P); d = wi; }
+                }
+                if constexpr (NEE) {
+                    const NeeArgs &na = cold_nee();
+                    // the pdf of the extension ray, for the w_b of the emission it may find (Lambert vertices only)
+                    if (!term) nr->aux = (bk == B_LAMBERT && na.n_lights) ? dot(n, wi) * kInvPi : 0.0f;
+                    // §7 light sample of a Lambert vertex. Computed after the BSDF sample and Russian roulette to keep it out of their registers;
+                    // its random numbers are its own (dimensions 1024 + 3b ..) and it uses only T * albedo of the T that arrived here.
+                    if (bk == B_LAMBERT && na.n_lights) {
+                        const float4 *lr = na.lights + (size_t)pick_light(na.cdf, na.n_lights, u01(key, 1024u + 3u * bb)) * 4;
+                        const float4 l0 = lr[0], l1 = lr[1], l2 = lr[2];
+                        const float su = __builtin_sqrtf(u01(key, 1025u + 3u * bb)), b1 = 1.0f - su, b2 = u01(key, 1026u + 3u * bb) * su;
+                        const V3 x = v3(fma_(b2, l2.x, fma_(b1, l1.x, l0.x)), fma_(b2, l2.y, fma_(b1, l1.y, l0.y)), fma_(b2, l2.z, fma_(b1, l1.z, l0.z)));
+                        const V3 so = madd(fp.ray_eps, n, P); // the continuation origin of a Lambert vertex (side +1)
+                        const V3 dl = x - so;
+                        const float dist2 = dot(dl, dl), dist = __builtin_sqrtf(dist2), inv = 1.0f / dist;
+                        const V3 sd = v3(dl.x * inv, dl.y * inv, dl.z * inv);
+                        const float4 l3 = lr[3];
+                        const float cs = dot(n, sd), cl = __builtin_fabsf(dot(xyz(l3), sd));
+                        if (cs > 0.0f && cl > 0.0f) { // the shadow ray goes first; the extension ray (if the path goes on) waits in NeeArgs::ext
+                            const float pl = (l0.w * dist2) / cl, q = (cs * kInvPi) / pl;
+                            const float f = nan_to_zero(q / fma_(q, q, 1.0f)); // w_l * pdf_bsdf / pdf_light
+                            at(na.rad, slot) = make_float4((ta.x * f) * l1.w, (ta.y * f) * l2.w, (ta.z * f) * l3.w, 0.0f);
+                            if (!term) at(na.ext, slot) = make_float4(d.x, d.y, d.z, nr->aux);
+                            nr->flags = NEE_PENDING | (term ? NEE_END : 0u);
+                            nr->aux = dist * 0.9999f;
+                            o = so; d = sd;
+                            term = false;
+                        }
                     }
                 }
             }
         }
     }
 
+    uint32_t x = 0, y = 0;
     if (term) {
         touched = true;
         A.w += 1.0f;
         sample += fp.streams;
         if (sample < fp.spp) { // regenerate this stream's next sample of the pixel in place
-            uint32_t x = 0, y = 0;
             slot_pixel(slot, fp, x, y);
             key = path_key(fp.seed_hashed, y * fp.width + x, fp.sample_offset + sample);
-            camera_ray_of(sc.cam, x, y, key, o, d);
+            if constexpr (!SHARED) camera_ray_of(sc.cam, x, y, key, o, d);
+            else { o = v3(sc.cam.origin[0], sc.cam.origin[1], sc.cam.origin[2]); regen = true; }
             T = v3(1.f, 1.f, 1.f);
             depth = 0;
             alive = true;
         }
         if constexpr (NEE) nr->aux = 0.0f; // a camera ray: its emission hits keep weight 1
     } else alive = true;
+    // The new direction of a Lambert vertex that goes on and of a regenerated camera ray, in one pass: a mixed wave (every wave after a
+    // launch's first vertex) used to run sample_lambert in one branch and camera_ray in the next, each with its own pair of u01 draws and
+    // its own normalize (a correctly rounded square root and reciprocal), each for a part of the lanes. Both kinds draw dimensions
+    // (dim, dim + 1) of their key and normalize one vector, so the wave issues the draws and the normalize once; a lane evaluates exactly
+    // the expressions sample_lambert or camera_ray would have (lambert_vec, camera_vec: pt_device.h).
+    if (lambert || regen) {
+        const uint32_t dim = regen ? 0u : 4u * depth; // a Lambert vertex of bounce bb = depth - 1 draws 4 + 4 bb and 5 + 4 bb
+        float u1 = u01(key, dim), u2 = u01(key, dim + 1u);
+        V3 v;
+        if (regen) {
+            if (!sc.cam.jitter) u1 = u2 = 0.5f;
+            v = camera_vec_of(sc.cam, x, y, u1, u2);
+        } else v = lambert_vec(d, u1, u2);
+        d = normalize(v);
+    }
     if (touched) at(ps.acc, slot) = A;
     r.depth = depth;
     return alive;

@@ -63,16 +63,21 @@ PT_DEV void sincos2pi(float u, float &sn, float &cs)
 // ---------------------------------------------------------------- SPEC §3 camera
 struct Camera { float origin[3], forward[3], right[3], up[3]; float scale, cx, cy; uint32_t jitter; };
 
+// The camera ray's direction before it is normalised, from the pixel and its jitter (jx, jy). The split form of camera_ray for a caller
+// that shares the normalize with other lanes' vectors (the end of kernels.hip's shade_one).
+PT_DEV V3 camera_vec(const Camera &c, uint32_t x, uint32_t y, float jx, float jy)
+{
+    float sx = ((float)x + jx) * c.scale - c.cx;
+    float sy = ((float)y + jy) * c.scale - c.cy;
+    return V3{ fma_(sy, c.up[0], fma_(sx, c.right[0], c.forward[0])),
+               fma_(sy, c.up[1], fma_(sx, c.right[1], c.forward[1])),
+               fma_(sy, c.up[2], fma_(sx, c.right[2], c.forward[2])) };
+}
 PT_DEV void camera_ray(const Camera &c, uint32_t x, uint32_t y, uint32_t key, V3 &o, V3 &d)
 {
     float jx = 0.5f, jy = 0.5f;
     if (c.jitter) { jx = u01(key, 0); jy = u01(key, 1); }
-    float sx = ((float)x + jx) * c.scale - c.cx;
-    float sy = ((float)y + jy) * c.scale - c.cy;
-    V3 v = V3{ fma_(sy, c.up[0], fma_(sx, c.right[0], c.forward[0])),
-               fma_(sy, c.up[1], fma_(sx, c.right[1], c.forward[1])),
-               fma_(sy, c.up[2], fma_(sx, c.right[2], c.forward[2])) };
-    d = normalize(v);
+    d = normalize(camera_vec(c, x, y, jx, jy));
     o = V3{ c.origin[0], c.origin[1], c.origin[2] };
 }
 
@@ -156,13 +161,13 @@ PT_DEV void basis(V3 n, V3 &tx, V3 &ty)
     tx = V3{ fma_(sg * n.x, n.x * a, 1.0f), sg * b, -(sg * n.x) };
     ty = V3{ b, fma_(n.y, n.y * a, sg), -n.y };
 }
-PT_DEV V3 to_world(V3 l, V3 tx, V3 ty, V3 n)
+PT_DEV V3 to_world_vec(V3 l, V3 tx, V3 ty, V3 n) // to_world before it is normalised
 {
-    V3 w = V3{ fma_(l.z, n.x, fma_(l.y, ty.x, l.x * tx.x)),
+    return V3{ fma_(l.z, n.x, fma_(l.y, ty.x, l.x * tx.x)),
                fma_(l.z, n.y, fma_(l.y, ty.y, l.x * tx.y)),
                fma_(l.z, n.z, fma_(l.y, ty.z, l.x * tx.z)) };
-    return normalize(w);
 }
+PT_DEV V3 to_world(V3 l, V3 tx, V3 ty, V3 n) { return normalize(to_world_vec(l, tx, ty, n)); }
 PT_DEV V3 schlick(V3 alb, float cosF)
 {
     float m = 1.0f - cosF, m2 = m * m, m5 = m2 * m2 * m;
@@ -179,17 +184,18 @@ PT_DEV float clamp01(float x) { return fmin_(fmax_(x, 0.0f), 1.0f); }
 // in one branch of shade_one): direction, throughput weight, side of the surface the next ray leaves from, validity.
 struct BsdfSample { V3 wi, W; float side; bool ok; };
 
-PT_DEV BsdfSample sample_lambert(V3 alb, V3 n, float u1, float u2)
+// The Lambert sample's direction before it is normalised: sample_lambert is { normalize(lambert_vec(n, u1, u2)), alb, 1, true }. The split
+// form for a caller that shares the normalize with other lanes' vectors (the end of kernels.hip's shade_one).
+PT_DEV V3 lambert_vec(V3 n, float u1, float u2)
 {
-    V3 wi;
     V3 tx, ty;
     basis(n, tx, ty);
     float r = __builtin_sqrtf(u1), sn, cs;
     sincos2pi(u2, sn, cs);
     V3 l = V3{ r * cs, r * sn, __builtin_sqrtf(fmax_(0.0f, 1.0f - u1)) };
-    wi = to_world(l, tx, ty, n);
-    return BsdfSample{ wi, alb, 1.0f, true };
+    return to_world_vec(l, tx, ty, n);
 }
+PT_DEV BsdfSample sample_lambert(V3 alb, V3 n, float u1, float u2) { return BsdfSample{ normalize(lambert_vec(n, u1, u2)), alb, 1.0f, true }; }
 
 PT_DEV BsdfSample sample_metal(V3 alb, float al, V3 d, V3 n, float u1, float u2)
 {
