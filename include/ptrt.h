@@ -205,7 +205,9 @@ uint32_t pt_abi_version(void);
 /* ---- scene: the reference has only shader literals (Test.hlsl:6,8,12,13); this is the API that replaces them */
 pt_status pt_scene_create(pt_context *ctx, pt_scene **out);
 void pt_scene_destroy(pt_scene *scene);
+/* Domain (docs/SPEC.md §4): any finite vertex is accepted; hits are the geometric ones for coordinates and hit distances within 2^±30. */
 pt_status pt_scene_set_triangles(pt_scene *s, const float *verts9, const uint32_t *material_ids, uint64_t count);
+/* Domain (docs/SPEC.md §4): a sphere's outline is uncertain by 7.78 (|oc|/r)^2 2^-24 of r^2: 1 % at 147 radii from the ray origin, noise at 3000. */
 pt_status pt_scene_set_spheres(pt_scene *s, const float *cxyzr, const uint32_t *material_ids, uint64_t count);
 pt_status pt_scene_set_materials(pt_scene *s, const pt_material *mats, uint64_t count);
 pt_status pt_scene_set_camera(pt_scene *s, const pt_camera *cam);
@@ -236,7 +238,8 @@ enum {
  * need |d| = 1 (the library does not normalise); a triangle's t is in units of |d|. Device arrays must lie on ctx's device inside one
  * allocation. stats (may be NULL): rays = n_rays, gpu_ms (the query kernels, staging copies excluded), and with PT_TRACE_COUNT_VISITS
  * node_visits / tri_tests / sphere_tests. PT_TRACE_OCCLUSION | PT_TRACE_COUNT_VISITS is PT_ERR_INVALID_ARGUMENT. A query touches no
- * state of pt_render (accumulated sums, framebuffer, queues). */
+ * state of pt_render (accumulated sums, framebuffer, queues).
+ * Domain (docs/SPEC.md §4): origins and hit distances within 2^±30 as for the scene; outside it the hit is specified but not the geometric one. */
 pt_status pt_trace_rays(pt_context *ctx, const pt_scene *scene, const void *rays, void *hits, uint64_t n_rays,
                         uint32_t flags, pt_stats *stats);
 

@@ -7,7 +7,12 @@ exactly as SPEC §4 defines it. Brute force, vectorised over rays × primitives 
 
 `classify` sorts the disagreements of an f32 implementation (the device or the oracle) with the caster into the classes
 float64 cannot settle — a ray within `EDGE_BAND` of an edge of either candidate (a miss there is a crack), candidates whose
-`t` agree to `T_BAND` — and real disagreements, which a test expects to be none.
+`t` agree to `T_BAND` — and real disagreements, which a test expects to be none. The bands are arguments (scalars or one
+value per ray) with these defaults. A sphere far away in its own radii has a third class of its own: SPEC §4's discriminant
+`b² − (|oc|² − r²)` cancels, so its silhouette is uncertain by `K_S · (|oc|/r)² · 2^-24` of r² (`sphere_band`).
+
+A triangle without area (`cross(e1, e2) == 0` in float64: a repeated vertex, collinear vertices, a point) is never hit and has
+no plane for a ray to lie in.
 """
 import numpy as np
 
@@ -15,6 +20,13 @@ MISS = 0xFFFFFFFF
 EDGE_BAND = 1e-5  # barycentric units
 T_BAND = 1e-5     # relative difference of t
 _PAIRS = 1 << 19  # rays × primitives per chunk
+# The scaled sphere band, in units of (|oc|/r)² · 2^-24 of r². Measured on the oracle over geometry_space's far_sphere and
+# far_camera cases (tests/test_geometry_space.py test_k_s_is_twice_the_measured_value repeats the measurement): the largest
+# |disc64|/r² / ((|oc|/r)² · 2^-24) among the rays that disagree with float64 is K_S_MEASURED; the band is twice that. The
+# rounding argument (three roundings each in b·b, oc·oc and the fma, each half an ulp of |oc|² ~ 2^-24 |oc|²) allows about 4.5.
+# At K_S the band is 1 % of r² at sqrt(0.01 · 2^24 / K_S) = 147 radii; at 3000 radii it is 4.2 r²: the test is noise there.
+K_S_MEASURED = 3.89  # 3.884, on far_camera at 1000 units; far_sphere alone: 2.32
+K_S = 2 * K_S_MEASURED
 
 
 def camera_rays(pto, cam, width, height):
@@ -119,7 +131,7 @@ def cast(verts, spheres, o, d):
                 ok = (det != 0) & (u >= 0) & (v >= 0) & (u + v <= 1) & (t > 0)
             n = np.cross(e1[ts], e2[ts])
             off = np.einsum("rtk,tk->rt", oo - v0[None, ts], n)
-            ri, ti = np.nonzero((det == 0) & (off == 0))
+            ri, ti = np.nonzero((det == 0) & (off == 0) & (n != 0).any(axis=1)[None, :])  # a zero-area triangle has no plane
             if len(ri):
                 ti = ti + t0
                 touch = _meets_in_plane(o[ri + r0], d[ri + r0], v0[ti], e1[ti], e2[ti])
@@ -168,23 +180,64 @@ def candidate(verts, spheres, o, d, ids):
     return t, edge
 
 
-def classify(verts, spheres, o, d, got, cast_result=None):
+def sphere_distance2(verts, spheres, o, ids):
+    """(|oc|/r)² of ray i's origin to sphere ids[i], in float64; NaN where ids[i] is not a sphere."""
+    o = np.asarray(o, np.float32).astype(np.float64)
+    ids = np.asarray(ids, np.uint64)
+    NT = len(np.asarray(verts).reshape(-1, 9))
+    sph = np.asarray(spheres, np.float32).reshape(-1, 4).astype(np.float64)
+    out = np.full(len(o), np.nan)
+    isph = (ids >= NT) & (ids != MISS)
+    if isph.any():
+        s = sph[(ids[isph] - NT).astype(np.int64)]
+        oc = o[isph] - s[:, :3]
+        out[isph] = (oc * oc).sum(-1) / (s[:, 3] * s[:, 3])
+    return out
+
+
+def classify(verts, spheres, o, d, got, cast_result=None, edge_band=EDGE_BAND, t_band=T_BAND, sphere_band=False, t_floor=None):
     """Compare the primitive ids `got` (uint, MISS for none) of an f32 implementation with the caster, ray by ray.
     Returns a dict of index arrays: agree, edge (near an edge of either candidate), crack (the edge rays where `got` misses),
-    coincident (the two candidates' t agree to T_BAND), in_plane (left out), wrong (everything else). `cast_result`: what
-    cast() returned for these rays, to skip recomputing it."""
+    coincident (the two candidates' t agree to t_band), in_plane (left out), wrong (everything else). `cast_result`: what
+    cast() returned for these rays, to skip recomputing it. `edge_band`, `t_band`: scalars or one value per ray. `sphere_band`:
+    a candidate that is a sphere also counts as edge when |disc64|/r² <= K_S · (|oc|/r)² · 2^-24 (the cancellation of SPEC §4's
+    discriminant); the dict then also holds `sphere_ratio`, |disc64|/r² over (|oc|/r)² · 2^-24 of the sphere candidate (the
+    smaller of the two if both are spheres, NaN if neither is) for every ray. `t_floor` (a length, scalar or per ray; only for rays
+    that start on a triangle): the start is a rounded point a few ulps off the triangle's plane, so whether that triangle S is hit at
+    once, at a t of rounding size, is not for float64 to say. A disagreement goes to the class `origin` (always empty without t_floor)
+    only if it is exactly that: either `got` is a triangle S with |t64| <= t_floor and the caster's answer is what the caster finds
+    with S left out, or the caster's answer is such an S and `got` is what the caster finds with S left out. Any other id is judged
+    as usual."""
     got = np.asarray(got).astype(np.uint64)
     want, t_w, edge_w, in_plane = cast_result if cast_result is not None else cast(verts, spheres, o, d)
     t_g, edge_g = candidate(verts, spheres, o, d, got)
     agree = (got == want) & ~in_plane
     dis = (got != want) & ~in_plane
-    near_edge = dis & ((edge_w < EDGE_BAND) | (edge_g < EDGE_BAND))
+    extra = {}
     with np.errstate(invalid="ignore"):
-        close_t = dis & ~near_edge & (np.abs(t_g - t_w) <= T_BAND * np.maximum(np.abs(t_g), np.abs(t_w)))
+        origin = np.zeros(len(got), bool)
+        if t_floor is not None:
+            NT = len(np.asarray(verts).reshape(-1, 9))
+            floor = np.broadcast_to(np.asarray(t_floor, np.float64), got.shape)
+            for i in np.nonzero(dis & (((np.abs(t_g) <= floor) & (got < NT)) | ((t_w <= floor) & (want < NT))))[0]:
+                start = want[i] if t_w[i] <= floor[i] and want[i] < NT else got[i]  # the triangle the ray starts on
+                rest = np.array(np.asarray(verts, np.float32).reshape(-1, 9), copy=True)
+                rest[int(start)] = 0  # without area: never hit
+                without = cast(rest, spheres, o[i:i + 1], d[i:i + 1])[0][0]
+                origin[i] = (got[i] if start == want[i] else want[i]) == without
+        dis = dis & ~origin
+        near_edge = dis & ((edge_w < edge_band) | (edge_g < edge_band))
+        if sphere_band:
+            unit = 2.0 ** -24
+            ratio = np.fmin(edge_w / (sphere_distance2(verts, spheres, o, want) * unit),
+                            edge_g / (sphere_distance2(verts, spheres, o, got) * unit))
+            near_edge |= dis & (ratio <= K_S)
+            extra["sphere_ratio"] = ratio
+        close_t = dis & ~near_edge & (np.abs(t_g - t_w) <= t_band * np.maximum(np.abs(t_g), np.abs(t_w)))
     wrong = dis & ~near_edge & ~close_t
     ix = np.nonzero
     return dict(agree=ix(agree)[0], edge=ix(near_edge)[0], crack=ix(near_edge & (got == MISS))[0], coincident=ix(close_t)[0],
-                in_plane=ix(in_plane)[0], wrong=ix(wrong)[0], want=want)
+                in_plane=ix(in_plane)[0], wrong=ix(wrong)[0], origin=ix(origin)[0], want=want, **extra)
 
 
 def _node_slots(layout, nodes, i):

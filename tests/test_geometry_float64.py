@@ -7,6 +7,7 @@ import pytest
 
 import adversarial_scenes as S
 import ray_caster64 as rc
+from geometry_space import SCALE_FIRST_BAD, SCALE_K
 
 W, H = 65, 49           # odd: the axis camera's centre row and column
 CRACK_RAYS = 300        # rays aimed at interior points of shared edges of the tessellated Cornell box
@@ -115,6 +116,19 @@ def test_caster_in_plane_rule():
     assert list(rc.cast(verts, no_spheres, o, d)[3]) == [True, True, True, False]
     for tri, want in ((0, [True, True, False, False]), (1, [False, True, False, False]), (2, [False, False, True, False])):
         assert list(rc.cast(verts[tri:tri + 1], no_spheres, o, d)[3]) == want, tri
+    # triangles without area (a repeated vertex, collinear vertices with the midpoint in the middle, a point), on or beside the
+    # rays: cross(e1, e2) == 0, so every ray has det == 0 and a zero offset from their "plane". They make no ray in-plane, are never
+    # hit, and leave the other triangles' answers alone.
+    flat = np.float32([[0.2, 0, -1, 0.2, 0, -1, 0.2, 0, -3], [0.2, 0, -1, 0.2, 0, -2, 0.2, 0, -3], [0.2, 0, -1.5] * 3, [7, 7, 7, 7, 7, 7, 8, 9, 10]])
+    for k in range(len(flat)):
+        assert list(rc.cast(flat[k:k + 1], no_spheres, o, d)[3]) == [False] * 4, k
+    assert (rc.cast(flat, no_spheres, o, d)[0] == rc.MISS).all()
+    mixed = np.concatenate([flat[:2], verts, flat[2:]])
+    ids, _, _, in_plane = rc.cast(mixed, no_spheres, o, d)
+    assert list(in_plane) == [True, True, True, False] and not np.isin(ids, [0, 1, 5, 6]).any()
+    off = np.float32([[0.2, 1, 0]] * 2)  # off the plane y = 0, aimed at triangle 0 of `verts` through the zero-area ones' line
+    ids, _, _, in_plane = rc.cast(mixed, no_spheres, off, np.float32([[0, -0.6, -0.8], [0, -1, -1.5]]))
+    assert not in_plane.any() and list(ids) == [2, 2]
 
 
 @pytest.mark.parametrize("layout", [2, 4, 68, 72, 73])
@@ -136,7 +150,10 @@ def test_sphere_list_limit(P):
         build_bvh_detached(S.sphere_list(65, 16, 16))
 
 
-@pytest.mark.parametrize("k", [-30, -8, 8, 30])
+# SCALE_K, the envelope exponent: the largest |k|, in steps of 2 from 30, at which these frames stay bit-identical and the glass box's
+# id image unchanged; at SCALE_FIRST_BAD = ±32 the frames differ (test_scale_envelope_is_pinned)
+
+@pytest.mark.parametrize("k", [-SCALE_K, -8, 8, SCALE_K])
 def test_power_of_two_scale_is_invisible_in_the_oracle(P, pto, k):
     """Scaling every length by 2**k scales every step of SPEC §4-§5 by an exact power of two (only the leaf padding breaks the
     symmetry, which cannot change a hit), so the path-traced frame is bit-identical for every layout of the product's host
@@ -155,6 +172,21 @@ def test_power_of_two_scale_is_invisible_in_the_oracle(P, pto, k):
             info, nodes, tris = build_bvh_detached(s2, layout)
             img, st = pto.render(pto.Scene(s2, (info.width, nodes, tris)), p2)
             assert st.rays == ost.rays and np.array_equal(img, ref), (k, layout)
+
+
+def test_scale_envelope_is_pinned(P, pto):
+    """One step of 2 past the envelope the frame is no longer the unscaled one, at either end: §5's normalize(cross(e1, e2)) takes
+    dot(cr, cr), a fourth-order product of lengths, which overflows at 2^32 for the Cornell walls (2^(4k+4) >= 2^128) and goes
+    denormal at 2^-32 for the tessellated box's small triangles. The hit ids still hold there (geometry_space.HIT_K)."""
+    N = P.native
+    assert SCALE_FIRST_BAD == (-SCALE_K - 2, SCALE_K + 2)
+    for k, kind, detail in ((SCALE_FIRST_BAD[1], N.PT_SCENE_CORNELL, 0), (SCALE_FIRST_BAD[0], N.PT_SCENE_CORNELL_TESS, 2000)):
+        sd = P.make_scene(kind, detail, 5, 48, 36)
+        frames = []
+        for s, eps in ((sd, 1e-4), (S.scaled(sd, k), 1e-4 * 2.0 ** k)):
+            info, nodes, tris = build_bvh_detached(s, 2)
+            frames.append(pto.render(pto.Scene(s, (info.width, nodes, tris)), P.make_params(48, 36, spp=2, max_depth=6, ray_eps=eps))[0])
+        assert not np.array_equal(frames[0], frames[1]), k
 
 
 def crack_rays(P, pto):
@@ -187,3 +219,40 @@ def test_shared_edges_are_watertight(P, pto):
     sd, _, o, d = crack_rays(P, pto)
     bf = pto.Scene(sd)
     assert all(bf.closest(o[i], d[i])[0] != rc.MISS for i in range(len(o)))
+
+
+@pytest.mark.xfail(strict=True, raises=AssertionError, reason="SPEC §4's discriminant b² − (|oc|² − r²) cancels: at 3000 radii its error, about (|oc|/r)² · 2^-24 "
+                                       "= 0.5 r², is the size of the sphere, and 280 of 1728 rays of the fan disagree with float64 far "
+                                       "outside EDGE_BAND. The well-conditioned form r² − |oc − b·d|² (which the caster uses) would turn this.")
+def test_far_sphere_at_3000_radii_agrees_with_float64(P, pto):
+    import geometry_space as G
+    from test_gpu_trace import oracle
+    case = G.find("far_sphere_3000")
+    o, d = case.rays
+    ids, _, _ = oracle(pto, pto.Scene(case.sd), o, d)
+    assert len(rc.classify(case.sd.verts, case.sd.spheres, o, d, ids)["wrong"]) == 0
+
+
+def _scene_at_two_to_the_64(pto):
+    """(unscaled ids, ids with every length times 2^64) of the glass box's camera rays, brute force."""
+    import geometry_space as G
+    from test_gpu_trace import oracle
+    sd = G.glass()
+    o, d = rc.camera_rays(pto, sd.cam, G.W, G.H)
+    want, _, _ = oracle(pto, pto.Scene(sd), o, d)
+    got, _, _ = oracle(pto, pto.Scene(S.scaled(sd, 64)), o * np.float32(2.0 ** 64), d)
+    return want, got
+
+
+def test_scene_at_two_to_the_64_goes_empty(P, pto):
+    """What the xfail below stands on: the unscaled box has 1190 hits of 1728 rays, the scaled one none, and no call fails."""
+    want, got = _scene_at_two_to_the_64(pto)
+    assert (want != rc.MISS).sum() == 1190 and (got == rc.MISS).all()
+
+
+@pytest.mark.xfail(strict=True, raises=AssertionError, reason="Möller–Trumbore's third-order products dot(e2, cross(tv, e1)) ~ 2^(3k+4) overflow f32 long before "
+                                       "the coordinates do: with every length times 2^64 no call fails and every ray misses. The domain "
+                                       "is stated in SPEC §4 (2^±30 for frames, ids hold to 2^±40) rather than enforced.")
+def test_scene_at_two_to_the_64_keeps_its_hits(P, pto):
+    want, got = _scene_at_two_to_the_64(pto)
+    assert np.array_equal(got, want)

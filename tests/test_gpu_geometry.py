@@ -12,7 +12,7 @@ import pytest
 
 import adversarial_scenes as S
 import ray_caster64 as rc
-from test_geometry_float64 import CRACK_RAYS, PINNED_CRACKS, W, H, _size, check_classes, crack_rays, scenes
+from test_geometry_float64 import CRACK_RAYS, PINNED_CRACKS, SCALE_K, W, H, _size, check_classes, crack_rays, scenes
 from test_gpu_parity import run_both
 
 pytestmark = pytest.mark.gpu
@@ -138,7 +138,8 @@ def test_power_of_two_scale_is_invisible_on_the_device(P, renderer):
     one for every layout of both builders. Needs neither the oracle nor the caster. What it can catch is anything that does
     not scale with the scene: an absolute distance constant in the kernels (an epsilon on t, a fixed offset) or an exponent of
     the BVH4Q/8Q quantisers saturating at a clamp. A quantiser rounding error that is itself scale-invariant shifts with k in
-    both frames and stays invisible here; a non-enclosing box is test_oracle_closest_hit_matches_float64's to catch."""
+    both frames and stays invisible here; a non-enclosing box is test_oracle_closest_hit_matches_float64's to catch.
+    The ends, ±SCALE_K, are the envelope of SPEC §4's domain: at ±32 the oracle's frames change."""
     N = P.native
     LBVH = N.PT_BVH_BUILD_LBVH
     for sd in (P.make_scene(N.PT_SCENE_CORNELL, 0, 5, 48, 36), P.make_scene(N.PT_SCENE_CORNELL_GLASS, 0, 5, 48, 36),
@@ -147,7 +148,7 @@ def test_power_of_two_scale_is_invisible_on_the_device(P, renderer):
         renderer.Params = P.make_params(48, 36, spp=2, max_depth=6)
         st0 = renderer.Render(0.0)
         ref = renderer.ReadFramebuffer()
-        for k in (-30, -8, 8, 30):
+        for k in (-SCALE_K, -8, 8, SCALE_K):
             s2 = S.scaled(sd, k)
             for width in LAYOUTS:
                 for build in (0, LBVH):
