@@ -160,12 +160,14 @@ public unsafe class HipRenderer : IDisposable
     // previous call's accumulated image to this frame, blends the last Render in, and (filter = true) runs Denoise's filter over the
     // result. Zeros mean the defaults. ReadTemporal / ReadHistoryLength / ReadDenoised hold until the next Render; the history itself
     // is kept by the context until reset = true or a change of size. Returns the stats (paths = pixels that took history,
-    // shade_ms = the temporal pass).
+    // shade_ms = the temporal pass). motion = true (PT_TEMPORAL_MOTION, §9.1) also records the geometry the call was traced on, and
+    // pixels of primitives that UpdateGeometry moved since the previous such call take their history from where their surface point was.
     public PtStats DenoiseTemporal(uint maxHistory = 0, float planeTolerance = 0f, float normalMin = 0f, bool reset = false, bool matchIds = false,
-                                   bool filter = true, uint iterations = 0)
+                                   bool filter = true, uint iterations = 0, bool motion = false)
     {
         var tp = new PtTemporalParams { max_history = maxHistory, plane_tolerance = planeTolerance, normal_min = normalMin,
-                                        flags = (reset ? (uint)PtTemporalFlags.Reset : 0u) | (matchIds ? (uint)PtTemporalFlags.MatchIds : 0u) };
+                                        flags = (reset ? (uint)PtTemporalFlags.Reset : 0u) | (matchIds ? (uint)PtTemporalFlags.MatchIds : 0u)
+                                                | (motion ? (uint)PtTemporalFlags.Motion : 0u) };
         var dp = new PtDenoiseParams { iterations = iterations };
         PtStats st;
         Ptrt.Check(Ptrt.pt_denoise_temporal(_ctx, _scene, &tp, filter ? &dp : null, &st), _ctx);

@@ -16,7 +16,7 @@ public enum PtSceneKind : uint { Cornell = 0, CornellGlass = 1, TriangleSoup = 2
 [Flags] public enum PtTraceFlags : uint { Occlusion = 1, CountVisits = 2, HostMemory = 4 }
 [Flags] public enum PtUpdateFlags : uint { HostMemory = 1 }
 [Flags] public enum PtDenoiseFlags : uint { GuidesOnly = 1, NoEdgeStops = 2 }
-[Flags] public enum PtTemporalFlags : uint { Reset = 1, MatchIds = 2 }
+[Flags] public enum PtTemporalFlags : uint { Reset = 1, MatchIds = 2, Motion = 8 }
 public enum PtDisplaySource : uint { Frame = 0, Denoised = 1, Temporal = 2 }
 public enum PtToneCurve : uint { Clamp = 0, Reinhard = 1, Aces = 2 }
 [Flags] public enum PtDisplayFlags : uint { AutoExposure = 1, Linear = 2, ResetAdaptation = 4 }

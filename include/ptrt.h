@@ -33,8 +33,8 @@ extern "C" {
  * pt_scene_update_triangles / pt_scene_update_spheres and PT_UPDATE_HOST_MEMORY, then PT_FLAG_NEXT_EVENT, then pt_denoise, pt_denoise_params,
  * PT_DENOISE_*, pt_denoised_read / pt_denoised_device_ptr and pt_guides_read, then pt_denoise_temporal, pt_temporal_params, PT_TEMPORAL_*,
  * pt_temporal_read / pt_temporal_device_ptr / pt_temporal_history_read, then pt_display, pt_display_params, pt_display_info, PT_DISPLAY_*,
- * PT_TONE_*, pt_display_read / pt_display_device_ptr / pt_display_info_read / pt_display_histogram_read (additions only: no struct or
- * existing signature changed).
+ * PT_TONE_*, pt_display_read / pt_display_device_ptr / pt_display_info_read / pt_display_histogram_read, then PT_TEMPORAL_MOTION (additions
+ * only: no struct or existing signature changed).
  * Hosts compare pt_abi_version() with the header they were built against. */
 #define PTRT_ABI_VERSION 2
 
@@ -308,7 +308,10 @@ pt_status pt_guides_read(pt_context *ctx, float *g8, uint64_t n_floats);        
 /* pt_temporal_params.flags */
 enum {
     PT_TEMPORAL_RESET = 1u,     /* forget the history first: this call's accumulated image is the frame itself */
-    PT_TEMPORAL_MATCH_IDS = 2u  /* a history tap also needs the primitive id of the pixel it is reprojected from */
+    PT_TEMPORAL_MATCH_IDS = 2u, /* a history tap also needs the primitive id of the pixel it is reprojected from */
+    PT_TEMPORAL_MOTION = 8u     /* follow moved geometry (docs/SPEC.md §9.1): the call records the triangles and spheres it is traced on, and the
+                                   next flagged call reprojects every pixel of a moved primitive from where its surface point was. (Bit 4u is
+                                   unassigned and refused.) */
 };
 typedef struct pt_temporal_params {
     uint32_t max_history;   /* cap of a pixel's history length; the new frame weighs at least 1/max_history. 0 = default (32); at most 1048576; 1 = no history */
@@ -333,7 +336,15 @@ typedef struct pt_temporal_params {
  * change of lighting on an unmoved surface lags by up to max_history frames; mirrors and glass reproject their own surface; misses never
  * accumulate. stats (may be NULL): rays = W*H guide rays, paths = pixels that took history, extend_ms the guide pass, shade_ms the
  * temporal pass, other_ms the filter passes, gpu_ms their sum, iterations = filter passes run. A failed call drains the context's stream
- * and leaves the history as it was. */
+ * and leaves the history as it was.
+ * PT_TEMPORAL_MOTION (docs/SPEC.md §9.1): a successful flagged call also keeps, as part of the history, the geometry it was traced on
+ * (36 B per triangle, 16 B per sphere, two sets). The next flagged call on the same scene object, with no pt_scene_commit in between,
+ * compares every hit primitive's device record with that snapshot; a pixel whose primitive moved (pt_scene_update_triangles /
+ * pt_scene_update_spheres) carries its surface point back to the old primitive, projects that point through the history's camera and
+ * tests the taps against the surface as it was, so an animated object keeps its history instead of restarting every frame. Unmoved
+ * pixels are exactly the unflagged call's; so is every pixel when the snapshot is missing (first call, after an unflagged call, another
+ * scene, a commit). stats->reserved[0] = hit pixels whose primitive counted as moved (0 without the flag or a usable snapshot). Still not
+ * detected: lighting changes, reflections of moved objects, a sphere's rotation, topology changes. */
 pt_status pt_denoise_temporal(pt_context *ctx, const pt_scene *scene, const pt_temporal_params *tp, const pt_denoise_params *dp, pt_stats *stats);
 pt_status pt_temporal_read(pt_context *ctx, float *rgba, uint64_t n_floats);          /* the accumulated image, W*H*4 */
 pt_status pt_temporal_device_ptr(pt_context *ctx, void **dptr, uint64_t *n_floats);   /* the same on the device (valid as above) */

@@ -46,6 +46,7 @@ PT_TRACE_OCCLUSION, PT_TRACE_COUNT_VISITS, PT_TRACE_HOST_MEMORY = 1, 2, 4
 PT_UPDATE_HOST_MEMORY = 1
 PT_DENOISE_GUIDES_ONLY, PT_DENOISE_NO_EDGE_STOPS = 1, 2
 PT_TEMPORAL_RESET, PT_TEMPORAL_MATCH_IDS = 1, 2
+PT_TEMPORAL_MOTION = 8  # (bit 4 is unassigned)
 PT_DISPLAY_FRAME, PT_DISPLAY_DENOISED, PT_DISPLAY_TEMPORAL = 0, 1, 2
 PT_TONE_CLAMP, PT_TONE_REINHARD, PT_TONE_ACES = 0, 1, 2
 PT_DISPLAY_AUTO_EXPOSURE, PT_DISPLAY_LINEAR, PT_DISPLAY_RESET_ADAPTATION = 1, 2, 4

@@ -120,11 +120,18 @@ private:
 // commit() — the last thing a successful call does — makes the back set the history, so a call that fails on the way leaves the history
 // as it was, and pt_denoise (which writes FrameOutputs' own guide planes) never touches it. Kept across frames, queries and geometry
 // updates; dropped by drop(), by a size change and with the context.
+// With PT_TEMPORAL_MOTION (§9.1) a set also holds the geometry its call was traced on — every triangle's 9 floats by original id, every
+// sphere's 4 — and which scene state that was (SceneState). The snapshot goes the way of the planes: written to the back set, current
+// after commit(), and gone after a commit() without one.
 class TemporalHistory {
 public:
     struct Planes { const float4 *g0, *g1, *h; };
     struct Target { float4 *g0, *g1, *h; };
+    struct SceneState { uint64_t serial, updates; uint32_t n_tris, n_spheres; }; // pt_scene's serial and update count, its primitive counts
+    struct Snapshot { const float *tris; const float4 *spheres; };
+    struct SnapshotTarget { float *tris; float4 *spheres; };
     DevBuf<uint32_t> taken;          // counter lines of the call under way: pixels that took history (temporal.h)
+    DevBuf<uint32_t> moved;          // §9.1's second set of lines: hit pixels whose primitive moved (made by the first flagged call)
 
     // the planes of a w x h call; a history of another size is dropped (its planes may be reallocated)
     hipError_t reserve(uint32_t width, uint32_t height, size_t counter_words)
@@ -136,15 +143,38 @@ public:
                 if (const hipError_t e = b->ensure(n)) { valid_ = false; return e; }
         return taken.ensure(counter_words);
     }
+    // the back set's snapshot arrays for a scene of these counts (the front set's stay as they are: a failed call leaves them readable)
+    hipError_t reserve_snapshot(const SceneState &of, size_t counter_words)
+    {
+        Set &s = sets_[cur_ ^ 1u];
+        if (const hipError_t e = s.snap_tris.ensure((size_t)of.n_tris * 9u)) return e;
+        if (const hipError_t e = s.snap_spheres.ensure(of.n_spheres)) return e;
+        return moved.ensure(counter_words);
+    }
     bool matches(uint32_t width, uint32_t height) const { return valid_ && width == w_ && height == h_; }
     const pt_camera &camera() const { return cam_; }
     Planes front() const { const Set &s = sets_[cur_]; return Planes{ s.g0.p, s.g1.p, s.h.p }; }
     Target back() { Set &s = sets_[cur_ ^ 1u]; return Target{ s.g0.p, s.g1.p, s.h.p }; }
-    void commit(const pt_camera &cam, uint32_t width, uint32_t height) { cur_ ^= 1u; cam_ = cam; w_ = width; h_ = height; valid_ = true; }
+    // the history's snapshot was recorded from this scene (same serial: same object, no commit since)
+    bool snapshot_of(const SceneState &now) const
+    {
+        const Set &s = sets_[cur_];
+        return s.has_snapshot && s.state.serial == now.serial && s.state.n_tris == now.n_tris && s.state.n_spheres == now.n_spheres;
+    }
+    bool snapshot_is_current(const SceneState &now) const { return sets_[cur_].state.updates == now.updates; } // no update has run since
+    Snapshot snapshot() const { const Set &s = sets_[cur_]; return Snapshot{ s.snap_tris.p, s.snap_spheres.p }; }
+    SnapshotTarget snapshot_back() { Set &s = sets_[cur_ ^ 1u]; return SnapshotTarget{ s.snap_tris.p, s.snap_spheres.p }; }
+    // `recorded`: the state the back set's snapshot was copied at, or NULL for a call without PT_TEMPORAL_MOTION (no snapshot stays)
+    void commit(const pt_camera &cam, uint32_t width, uint32_t height, const SceneState *recorded = nullptr)
+    {
+        cur_ ^= 1u; cam_ = cam; w_ = width; h_ = height; valid_ = true;
+        sets_[cur_].has_snapshot = recorded != nullptr;
+        if (recorded) sets_[cur_].state = *recorded;
+    }
     void drop() { valid_ = false; }
 
 private:
-    struct Set { DevBuf<float4> g0, g1, h; };
+    struct Set { DevBuf<float4> g0, g1, h; DevBuf<float> snap_tris; DevBuf<float4> snap_spheres; SceneState state{}; bool has_snapshot = false; };
     Set sets_[2];
     uint32_t cur_ = 0, w_ = 0, h_ = 0;
     pt_camera cam_{};

@@ -231,7 +231,7 @@ static pt_status denoise_temporal(pt_context *c, const pt_scene *s, const pt_tem
 {
     static const char who[] = "pt_denoise_temporal";
     if (!tp) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_denoise_temporal: tp is NULL");
-    constexpr uint32_t known = PT_TEMPORAL_RESET | PT_TEMPORAL_MATCH_IDS;
+    constexpr uint32_t known = PT_TEMPORAL_RESET | PT_TEMPORAL_MATCH_IDS | PT_TEMPORAL_MOTION;
     if (tp->flags & ~known) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_denoise_temporal: unknown flag bits 0x%x", tp->flags & ~known);
     if (tp->max_history > kTemporalMaxHistoryLimit)
         return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_denoise_temporal: max_history %u (0 = default, at most %u)", tp->max_history, kTemporalMaxHistoryLimit);
@@ -258,6 +258,17 @@ static pt_status denoise_temporal(pt_context *c, const pt_scene *s, const pt_tem
     HIP_TRY(c, hist.reserve(w, h, kTemporalCounterWords));
     HIP_TRY(c, o.tm_out.ensure(n));
     HIP_TRY(c, hipMemsetAsync(hist.taken.p, 0, sizeof(uint32_t) * kTemporalCounterWords, c->stream)); // (ahead of the timed passes)
+    const bool motion = (tp->flags & PT_TEMPORAL_MOTION) != 0;
+    const TemporalHistory::SceneState state{ s->serial, s->updates, s->ds.n_tris, s->ds.n_spheres };
+    if (motion) { // §9.1: the geometry this call is traced on, into the back set (ahead of the timed passes too)
+        HIP_TRY(c, hist.reserve_snapshot(state, kTemporalCounterWords));
+        const TemporalHistory::SnapshotTarget snap = hist.snapshot_back();
+        const float *verts = nullptr;
+        if ((st = s->verts.device(c, verts)) != PT_OK) return st; // (the buffer the last update wrote, or one upload of the host vector)
+        if (state.n_tris) HIP_TRY(c, hipMemcpyAsync(snap.tris, verts, (size_t)state.n_tris * 36u, hipMemcpyDeviceToDevice, c->stream));
+        if (state.n_spheres) HIP_TRY(c, hipMemcpyAsync(snap.spheres, s->ds.spheres, (size_t)state.n_spheres * 16u, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(c, hipMemsetAsync(hist.moved.p, 0, sizeof(uint32_t) * kTemporalCounterWords, c->stream));
+    }
     const TemporalHistory::Target next = hist.back();
     if ((st = guide_pass(c, s, plan.passes, next.g0, next.g1)) != PT_OK) return st;
     hipStream_t q = c->stream;
@@ -272,22 +283,34 @@ static pt_status denoise_temporal(pt_context *c, const pt_scene *s, const pt_tem
     ta.frame = o.fb.p; ta.g0 = next.g0; ta.g1 = next.g1;
     ta.old_g0 = prev.g0; ta.old_g1 = prev.g1; ta.old_h = prev.h;
     ta.out = o.tm_out.p; ta.new_h = next.h; ta.taken = hist.taken.p;
-    HIP_TRY(c, launch_temporal(q, ta));
+    // §9.1: the call uses the snapshot when it has a history whose snapshot was recorded from this scene and no commit since. If no
+    // update has run since either, every pixel is unmoved and the pass is §9's
+    const bool use_snapshot = motion && ta.has_history && hist.snapshot_of(state) && !hist.snapshot_is_current(state);
+    if (use_snapshot) {
+        const TemporalHistory::Snapshot was = hist.snapshot();
+        MotionArgs ma{};
+        ma.blob_of = s->cache.d_blob_of.p; ma.tris = s->ds.tris; ma.spheres = s->ds.spheres;
+        ma.snap_tris = was.tris; ma.snap_spheres = was.spheres;
+        ma.n_tris = state.n_tris; ma.n_spheres = state.n_spheres; ma.moved = hist.moved.p;
+        HIP_TRY(c, launch_temporal_motion(q, ta, ma));
+    } else HIP_TRY(c, launch_temporal(q, ta));
     HIP_TRY(c, hipEventRecord(o.ev_temporal, q));
     if ((st = filter_passes(c, plan, o.tm_out.p, next.g0, next.g1)) != PT_OK) return st;
-    uint32_t lines[kTemporalCounterWords];
+    uint32_t lines[kTemporalCounterWords], moved_lines[kTemporalCounterWords];
     HIP_TRY(c, hipMemcpyAsync(lines, hist.taken.p, sizeof lines, hipMemcpyDeviceToHost, q)); // read behind guides_finish's synchronise
+    if (use_snapshot) HIP_TRY(c, hipMemcpyAsync(moved_lines, hist.moved.p, sizeof moved_lines, hipMemcpyDeviceToHost, q));
     if ((st = guides_finish(c, who, s)) != PT_OK) return st;
-    uint64_t taken = 0;
+    uint64_t taken = 0, moved = 0;
     for (uint32_t k = 0; k < kTemporalCounters; ++k) taken += lines[k * (kTemporalCounterWords / kTemporalCounters)];
+    if (use_snapshot) for (uint32_t k = 0; k < kTemporalCounters; ++k) moved += moved_lines[k * (kTemporalCounterWords / kTemporalCounters)];
     float ms_guides = 0.f, ms_temporal = 0.f, ms_filter = 0.f;
     HIP_TRY(c, hipEventElapsedTime(&ms_guides, o.ev_denoise[0], o.ev_denoise[1]));
     HIP_TRY(c, hipEventElapsedTime(&ms_temporal, o.ev_denoise[1], o.ev_temporal));
     HIP_TRY(c, hipEventElapsedTime(&ms_filter, o.ev_temporal, o.ev_denoise[2]));
     pt_stats out{};
-    out.rays = n; out.paths = taken; out.iterations = plan.passes;
+    out.rays = n; out.paths = taken; out.iterations = plan.passes; out.reserved[0] = moved;
     out.extend_ms = ms_guides; out.shade_ms = ms_temporal; out.other_ms = ms_filter; out.gpu_ms = (double)ms_guides + ms_temporal + ms_filter;
-    hist.commit(s->cam, w, h); // the back planes are the history from here on
+    hist.commit(s->cam, w, h, motion ? &state : nullptr); // the back planes (and snapshot) are the history from here on
     o.denoised(plan.passes > 0, next.g0, next.g1);
     o.accumulated();
     if (stats) *stats = out;

@@ -4,6 +4,7 @@
 #include "refit.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -125,6 +126,24 @@ pt_status SceneVertices::host(pt_context *c, const float *&verts9)
     }
     verts9 = host_.data();
     return PT_OK;
+}
+
+pt_status SceneVertices::device(pt_context *c, const float *&verts9) const
+{
+    if (!dev_current) {
+        HIP_TRY(c, hipSetDevice(context_device(c)));
+        HIP_TRY(c, dev[cur].ensure(host_.size()));
+        if (!host_.empty()) HIP_TRY(c, hipMemcpy(dev[cur].p, host_.data(), host_.size() * sizeof(float), hipMemcpyHostToDevice));
+        dev_current = true;
+    }
+    verts9 = dev[cur].p;
+    return PT_OK;
+}
+
+uint64_t ptrt::next_scene_serial()
+{
+    static std::atomic<uint64_t> last{ 0 };
+    return ++last;
 }
 
 // ------------------------------------------------------------------------------------------------ scene contents
@@ -410,6 +429,7 @@ pt_status pt_scene_commit(pt_scene *s, uint32_t bvh_width)
     pt_status st = check_commit(s, bvh_width, lbvh);
     if (st != PT_OK) return st;
     CommitClock clock;
+    s->serial = next_scene_serial(); s->updates = 0; // a new tree: nothing recorded from the old one describes it
     s->cache.invalidate(); // level lists, guide index and what earlier frames measured belong to the tree this commit replaces
     if ((st = build_tree(s, bvh_width, lbvh, clock)) != PT_OK) return st;
     if (!s->ctx) { s->committed = true; return PT_OK; } // detached scene: host-side blob only
@@ -515,6 +535,7 @@ static pt_status update_triangles(pt_scene *s, const void *verts9, uint64_t coun
         HIP_TRY(c, hipEventRecord(R.ev[0], q));
     }
     const uint32_t layout = tree.layout;
+    ++s->updates; // from here on the device records are rewritten (counted even if the update then fails)
     HIP_TRY(c, launch_refit_tris(q, v, tree.d_tris.p, tree.n_tris, R.tbox.p));
     for (size_t l = 0; l + 1 < R.level_off.size(); ++l)
         HIP_TRY(c, launch_refit_level(q, layout, tree.d_nodes.p, R.list.p + R.level_off[l], R.level_off[l + 1] - R.level_off[l], R.tbox.p, R.nbox.p, R.carea.p));
@@ -554,6 +575,7 @@ static pt_status update_spheres(pt_scene *s, const float *cxyzr, uint64_t count)
     HIP_TRY(c, hipSetDevice(context_device(c)));
     const std::vector<uint2> mi = sphere_mats(s->sph_mat.data(), cxyzr, count);
     hipStream_t q = context_stream(c);
+    ++s->updates; // from here on the device records are rewritten
     HIP_TRY(c, hipMemcpyAsync(s->d_spheres.p, cxyzr, count * 16u, hipMemcpyHostToDevice, q));
     HIP_TRY(c, hipMemcpyAsync(s->d_sph_mat.p, mi.data(), count * sizeof(uint2), hipMemcpyHostToDevice, q));
     HIP_TRY(c, hipStreamSynchronize(q));

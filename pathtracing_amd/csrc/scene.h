@@ -11,6 +11,8 @@ namespace ptrt {
 
 struct CommitClock;
 
+uint64_t next_scene_serial(); // never the same value twice in a process (scene.cpp)
+
 // The committed tree: the device arrays the kernels traverse, its figures (recorded when the tree is adopted, never re-derived), and the
 // host image of the docs/SPEC.md §4.1 blob. The image is fresh after a host build, lacks current boxes and triangle rows after a refit,
 // and is absent after a build that packed the blob on the device; host_image() fetches exactly then.
@@ -53,21 +55,25 @@ private:
 // writes next(), and only when all of it has succeeded does next_is_current() make that the scene's vertices.
 class SceneVertices {
 public:
-    void set(const float *verts9, uint64_t count) { host_.assign(verts9, verts9 + count * 9); host_stale = false; }
+    void set(const float *verts9, uint64_t count) { host_.assign(verts9, verts9 + count * 9); host_stale = false; dev_current = false; }
     pt_status host(pt_context *c, const float *&verts9); // fetched first if an update has run since
+    // the current vertices on the device: the host vector is uploaded once if no update has run yet (const: pt_denoise_temporal asks
+    // through the const scene it receives, and the scene's vertices stay what they are)
+    pt_status device(pt_context *c, const float *&verts9) const;
     hipError_t reserve_device()                          // both buffers, for as many vertices as the host vector holds
     {
         const hipError_t e = dev[0].ensure(host_.size());
         return e != hipSuccess ? e : dev[1].ensure(host_.size());
     }
     float *next() const { return dev[cur ^ 1u].p; }
-    void next_is_current() { cur ^= 1u; host_stale = true; }
+    void next_is_current() { cur ^= 1u; host_stale = true; dev_current = true; }
 
 private:
     std::vector<float> host_;
-    DevBuf<float> dev[2];
+    mutable DevBuf<float> dev[2];
     uint32_t cur = 0;        // dev[cur] holds the scene's vertices while host_stale
     bool host_stale = false;
+    mutable bool dev_current = false; // dev[cur] holds the scene's vertices (an update's, or device()'s upload of the host vector)
 };
 
 struct ExtendChoice {           // what a scene remembers of the extend-kernel probe (frame.cpp ExtendFrame)
@@ -100,6 +106,9 @@ struct CommitCaches {
 
 struct pt_scene {
     pt_context *ctx = nullptr;
+    // Which committed geometry this is, for whoever keeps something derived from it across calls (context.h TemporalHistory's
+    // snapshot): `serial` is unique per scene object and per pt_scene_commit, `updates` counts the geometry updates since.
+    uint64_t serial = ptrt::next_scene_serial(), updates = 0;
     ptrt::SceneVertices verts; std::vector<uint32_t> tri_mat;
     std::vector<float> spheres; std::vector<uint32_t> sph_mat;
     std::vector<pt_material> mats;

@@ -294,14 +294,19 @@ class Renderer:
         _check(N.lib.pt_guides_read(self._ctx, _ptr(out), out.size), self._ctx)
         return out
 
-    def DenoiseTemporal(self, max_history=0, plane_tolerance=0.0, normal_min=0.0, reset=False, match_ids=False, filter=True, **denoise):
+    def DenoiseTemporal(self, max_history=0, plane_tolerance=0.0, normal_min=0.0, reset=False, match_ids=False, filter=True, motion=False,
+                        **denoise):
         """Temporal accumulation (include/ptrt.h pt_denoise_temporal, docs/SPEC.md §9): reproject the previous call's accumulated image
         to the last rendered frame through the two cameras and the first-hit guides, blend the frame in, keep the result as the next
         history, and — with `filter` — run Denoise's filter over it (`denoise`: Denoise's keyword arguments). Zeros mean the defaults.
         Returns pt_stats (paths = pixels that took history, shade_ms = the temporal pass). ReadTemporal / ReadHistoryLength /
-        ReadDenoised / ReadGuides hold until the next Render; the history lives in the context until `reset` or a change of size."""
+        ReadDenoised / ReadGuides hold until the next Render; the history lives in the context until `reset` or a change of size.
+        `motion` (PT_TEMPORAL_MOTION, §9.1): the call also records the geometry it was traced on, and a pixel whose primitive
+        UpdateGeometry has moved since the previous `motion` call takes its history from where its surface point was;
+        stats.reserved[0] = pixels of moved primitives."""
         tp = N.pt_temporal_params(max_history, plane_tolerance, normal_min,
-                                  (N.PT_TEMPORAL_RESET if reset else 0) | (N.PT_TEMPORAL_MATCH_IDS if match_ids else 0))
+                                  (N.PT_TEMPORAL_RESET if reset else 0) | (N.PT_TEMPORAL_MATCH_IDS if match_ids else 0)
+                                  | (N.PT_TEMPORAL_MOTION if motion else 0))
         dp = None
         if filter:
             dp = N.pt_denoise_params(denoise.pop("iterations", 0), denoise.pop("sigma_color", 0.0), denoise.pop("sigma_normal", 0.0),
