@@ -1,5 +1,5 @@
 // api.cpp — C ABI of libptrt.so (include/ptrt.h): ABI version and errors, context life cycle and tuning, tile layout, the read-backs and
-// device pointers of a frame, pt_assemble_tiles. (pt_render: frame.cpp; ray queries and denoising: query.cpp; scenes: scene.cpp.)
+// device pointers of a frame, pt_assemble_tiles. (pt_render: frame.cpp; ray queries: query.cpp; denoising: denoise_host.cpp; display: display_host.cpp; scenes: scene.cpp.)
 // Stands where Renderer.CreateResources / CreateComputePipeline stand in the reference (RayTracing/Graphics/Renderer.cs:105-196, 293-403).
 // HIP only: there is no CPU fallback anywhere in this library.
 #include "context.h"

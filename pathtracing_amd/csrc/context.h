@@ -1,8 +1,8 @@
 // context.h — pt_context, and one owner each for what a context keeps between public calls: the assembled frame with the results
 // denoised and displayed from it, the history of pt_denoise_temporal, the exposure pt_display adapts from, the partial sums a PT_FLAG_ACCUMULATE frame continues, the frame-start template, the queue sizes a frame's loops
 // read back, and the plumbing of a ray query. Each owner keeps its validity private and offers the few questions and transitions the
-// calls need; nobody else keeps a flag about it. Private to api.cpp, frame.cpp, query.cpp and scene.cpp, as are the helpers every
-// public call uses (defined once, in api.cpp).
+// calls need; nobody else keeps a flag about it. Private to api.cpp, frame.cpp, query.cpp, denoise_host.cpp,
+// display_host.cpp and scene.cpp, as are the helpers every public call uses (defined once, in api.cpp).
 #pragma once
 #include "ptrt_internal.h"
 #include "device_owner.h"
@@ -321,7 +321,7 @@ private:
 
 // The plumbing of a query (pt_trace_rays, pt_denoise's guide pass): its own counter block, overflow stack, staging buffers
 // (PT_TRACE_HOST_MEMORY) and events, so that a query touches nothing a frame reads (the frame-start template, the partial sums, the queues
-// and their counters). All on the context's stream (query.cpp).
+// and their counters). All on the context's stream (query.cpp; the guide pass is denoise_host.cpp's).
 class Queries {
 public:
     DevBuf<float4> rays, hits;       // staging

@@ -1,5 +1,5 @@
 // denoise.h — pt_denoise on the device (denoise.hip), docs/SPEC.md §8: the guide buffers of the first hit and the edge-aware à-trous
-// filter. query.cpp owns the buffers and calls these in order: index (once per commit), guide rays, launch_trace (kernels.hip), resolve,
+// filter. denoise_host.cpp owns the buffers and calls these in order: index (once per commit), guide rays, launch_trace (kernels.hip), resolve,
 // then one à-trous launch per pass.
 #pragma once
 #include <hip/hip_runtime_api.h>

@@ -1,5 +1,5 @@
 // display.h — pt_display on the device (display.hip), docs/SPEC.md §10: a luminance histogram of the source, one wavefront that turns it
-// into an exposure, and the tone pass that writes the 8-bit image. query.cpp owns the buffers (context.h FrameOutputs, DisplayAdaptation)
+// into an exposure, and the tone pass that writes the 8-bit image. display_host.cpp owns the buffers (context.h FrameOutputs, DisplayAdaptation)
 // and enqueues the three on the context's stream; nothing comes back to the host between them.
 #pragma once
 #include <hip/hip_runtime_api.h>

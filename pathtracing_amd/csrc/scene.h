@@ -1,6 +1,6 @@
 // scene.h — pt_scene, and one owner each for the two things a committed scene keeps on both sides of the bus: its tree and its
-// vertices. Which copy is current is private to the owner; nobody else keeps a flag about it. Private to scene.cpp, frame.cpp and
-// query.cpp; the context a scene belongs to and the helpers every public call uses are context.h's.
+// vertices. Which copy is current is private to the owner; nobody else keeps a flag about it. Private to scene.cpp, frame.cpp,
+// query.cpp and denoise_host.cpp; the context a scene belongs to and the helpers every public call uses are context.h's.
 #pragma once
 #include "context.h"
 #include "bvh_build.h"

@@ -1,5 +1,5 @@
 // temporal.h — pt_denoise_temporal on the device (temporal.hip), docs/SPEC.md §9: one fused pass that reprojects the history of the
-// previous call to this call's pixels and blends the assembled frame into it. query.cpp owns the buffers (context.h TemporalHistory) and
+// previous call to this call's pixels and blends the assembled frame into it. denoise_host.cpp owns the buffers (context.h TemporalHistory) and
 // calls it between the guide pass and the à-trous passes. A call that uses the geometry snapshot of PT_TEMPORAL_MOTION (§9.1) launches
 // the motion kernel instead.
 #pragma once

@@ -11,6 +11,8 @@
 //                barycentrics carried to the old vertices, a sphere's offset scaled to the old radius), projects that point through the
 //                history's camera and tests the taps against the surface as it was. Three gathers per pixel (blob index, 64-B record,
 //                36-B old vertices), which neighbouring pixels of one triangle share. Unmoved pixels run k_temporal's arithmetic.
+// What the two share — the gather through the history's camera, the blend, the two stores, the counter line — is stated once, in the
+// device functions ahead of them.
 // Op order follows §9 and §9.1 exactly (explicit fma, -ffp-contract=off, IEEE division): tests/temporal_ref/ and tests/motion_ref/ restate
 // them bit for bit. Includes pt_device.h for the vector helpers and §3's camera ray only.
 #include "ptrt_internal.h"
@@ -68,6 +70,69 @@ struct MotionKernelArgs {
 
 PT_DEV bool differs(float a, float b) { return __float_as_uint(a) != __float_as_uint(b); }
 PT_DEV bool differs(V3 a, V3 b) { return differs(a.x, b.x) || differs(a.y, b.y) || differs(a.z, b.z); }
+
+// §9's gather for pixel (x, y): surface point P with normal n and id, wv = P - the old camera's origin. `in_place`: P projects to the
+// pixel itself, one tap there; otherwise P goes through the history's camera and up to four bilinear taps count
+PT_DEV TapSums gather_history(const TemporalKernelArgs &a, uint32_t x, uint32_t y, bool in_place, V3 P, V3 n, V3 wv, uint32_t id)
+{
+    const float e2 = dot(wv, wv);
+    TapSums s{ 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
+    if (in_place) {
+        temporal_tap(a, (int)x, (int)y, 1.0f, P, n, id, e2, s);
+    } else {
+        const V3 f2 = V3{ a.old_cam.forward[0], a.old_cam.forward[1], a.old_cam.forward[2] };
+        const V3 r2 = V3{ a.old_cam.right[0], a.old_cam.right[1], a.old_cam.right[2] };
+        const V3 u2 = V3{ a.old_cam.up[0], a.old_cam.up[1], a.old_cam.up[2] };
+        const V3 A = cross(r2, u2), B = cross(u2, f2), Cx = cross(f2, r2);
+        const float det = dot(f2, A), den = dot(wv, A);
+        if ((den > 0.0f && det > 0.0f) || (den < 0.0f && det < 0.0f)) {
+            const float inv = 1.0f / den;
+            const float sx = dot(wv, B) * inv, sy = dot(wv, Cx) * inv;
+            const float fx = (sx + a.old_cam.cx) / a.old_cam.scale - 0.5f;
+            const float fy = (sy + a.old_cam.cy) / a.old_cam.scale - 0.5f;
+            if (fx >= -1.0f && fx < (float)a.width && fy >= -1.0f && fy < (float)a.height) { // (a NaN ends here)
+                const float x0 = __builtin_floorf(fx), y0 = __builtin_floorf(fy);
+                const float bx = fx - x0, by = fy - y0;
+                const int ix = (int)x0, iy = (int)y0;
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+                        temporal_tap(a, ix + i, iy + j, (i ? bx : 1.0f - bx) * (j ? by : 1.0f - by), P, n, id, e2, s);
+            }
+        }
+    }
+    return s;
+}
+
+// §9's blend of the frame's colour c into what the taps gathered: the output colour and the new length l. Sums of too little weight
+// (none: no history, a miss, no tap passed) give c and l = 1
+PT_DEV float4 blend(const TemporalKernelArgs &a, float4 c, const TapSums &s, float &l)
+{
+    l = 1.0f;
+    if (!(s.sw >= 0.25f)) return c;
+    const float r = 1.0f / s.sw;
+    const float hr = s.sr * r, hg = s.sg * r, hb = s.sb * r;
+    l = fmin_(s.sl * r + 1.0f, a.max_history);
+    const float w = 1.0f / l;
+    return make_float4(fma_(w, c.x - hr, hr), fma_(w, c.y - hg, hg), fma_(w, c.z - hb, hb), c.w);
+}
+
+// The two stores of a pixel; true if it took history
+PT_DEV bool store_pixel(const TemporalKernelArgs &a, size_t ip, float4 out, float l)
+{
+    a.out[ip] = out;
+    a.new_h[ip] = make_float4(out.x, out.y, out.z, l);
+    return l > 1.0f;
+}
+
+// A wave is one row segment (threadIdx.y); no lane has left when it counts by ballot, so lane 0 speaks for it. Consecutive waves add to
+// consecutive counter lines: tens of thousands of atomics on one address would take longer than the rest of the kernel
+// (ptrt_internal.h kShards). The first word of this wave's line
+PT_DEV uint32_t counter_line()
+{
+    return (((blockIdx.y * gridDim.x + blockIdx.x) * 4u + threadIdx.y) % kTemporalCounters) * kCounterStride;
+}
 } // namespace
 
 __global__ void __launch_bounds__(kBlock) k_temporal(TemporalKernelArgs a)
@@ -77,65 +142,25 @@ __global__ void __launch_bounds__(kBlock) k_temporal(TemporalKernelArgs a)
     if (x < a.width && y < a.height) {
         const size_t ip = (size_t)y * a.width + x;
         const float4 c = a.frame[ip];
-        float4 out = c;
-        float l = 1.0f;
+        TapSums s{ 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
         if (a.has_history) { // uniform over the grid
             const float4 ap = a.g1[ip];
             const uint32_t id = __float_as_uint(ap.w);
             if (id != PT_MISS) {
                 const float4 np = a.g0[ip];
-                const V3 n = xyz(np);
                 V3 o, d;
                 camera_ray(a.cam, x, y, 0u, o, d); // cam.jitter == 0: §8.1's ray
                 const V3 P = madd(np.w, d, o);
                 const V3 wv = P - V3{ a.old_cam.origin[0], a.old_cam.origin[1], a.old_cam.origin[2] };
-                const float e2 = dot(wv, wv);
-                TapSums s{ 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
-                if (a.same_camera) {
-                    temporal_tap(a, (int)x, (int)y, 1.0f, P, n, id, e2, s);
-                } else {
-                    const V3 f2 = V3{ a.old_cam.forward[0], a.old_cam.forward[1], a.old_cam.forward[2] };
-                    const V3 r2 = V3{ a.old_cam.right[0], a.old_cam.right[1], a.old_cam.right[2] };
-                    const V3 u2 = V3{ a.old_cam.up[0], a.old_cam.up[1], a.old_cam.up[2] };
-                    const V3 A = cross(r2, u2), B = cross(u2, f2), Cx = cross(f2, r2);
-                    const float det = dot(f2, A), den = dot(wv, A);
-                    if ((den > 0.0f && det > 0.0f) || (den < 0.0f && det < 0.0f)) {
-                        const float inv = 1.0f / den;
-                        const float sx = dot(wv, B) * inv, sy = dot(wv, Cx) * inv;
-                        const float fx = (sx + a.old_cam.cx) / a.old_cam.scale - 0.5f;
-                        const float fy = (sy + a.old_cam.cy) / a.old_cam.scale - 0.5f;
-                        if (fx >= -1.0f && fx < (float)a.width && fy >= -1.0f && fy < (float)a.height) { // (a NaN ends here)
-                            const float x0 = __builtin_floorf(fx), y0 = __builtin_floorf(fy);
-                            const float bx = fx - x0, by = fy - y0;
-                            const int ix = (int)x0, iy = (int)y0;
-#pragma unroll
-                            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                                for (int i = 0; i < 2; ++i)
-                                    temporal_tap(a, ix + i, iy + j, (i ? bx : 1.0f - bx) * (j ? by : 1.0f - by), P, n, id, e2, s);
-                        }
-                    }
-                }
-                if (s.sw >= 0.25f) {
-                    const float r = 1.0f / s.sw;
-                    const float hr = s.sr * r, hg = s.sg * r, hb = s.sb * r;
-                    l = fmin_(s.sl * r + 1.0f, a.max_history);
-                    const float w = 1.0f / l;
-                    out = make_float4(fma_(w, c.x - hr, hr), fma_(w, c.y - hg, hg), fma_(w, c.z - hb, hb), c.w);
-                }
+                s = gather_history(a, x, y, a.same_camera, P, xyz(np), wv, id);
             }
         }
-        a.out[ip] = out;
-        a.new_h[ip] = make_float4(out.x, out.y, out.z, l);
-        took = l > 1.0f;
+        float l;
+        const float4 out = blend(a, c, s, l);
+        took = store_pixel(a, ip, out, l);
     }
-    // a wave is one row segment (threadIdx.y); no lane has left, so lane 0 speaks for it. Consecutive waves add to consecutive counter
-    // lines: tens of thousands of atomics on one address would take longer than the rest of the kernel (ptrt_internal.h kShards)
     const unsigned long long m = __ballot(took);
-    if (threadIdx.x == 0u && m) {
-        const uint32_t wave = (blockIdx.y * gridDim.x + blockIdx.x) * 4u + threadIdx.y;
-        atomicAdd(a.taken + (wave % kTemporalCounters) * kCounterStride, (uint32_t)__popcll(m));
-    }
+    if (threadIdx.x == 0u && m) atomicAdd(a.taken + counter_line(), (uint32_t)__popcll(m));
 }
 
 __global__ void __launch_bounds__(kBlock) k_temporal_motion(TemporalKernelArgs a, MotionKernelArgs g)
@@ -145,8 +170,7 @@ __global__ void __launch_bounds__(kBlock) k_temporal_motion(TemporalKernelArgs a
     if (x < a.width && y < a.height) {
         const size_t ip = (size_t)y * a.width + x;
         const float4 c = a.frame[ip];
-        float4 out = c;
-        float l = 1.0f;
+        TapSums s{ 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
         const float4 ap = a.g1[ip];
         const uint32_t id = __float_as_uint(ap.w);
         if (id != PT_MISS) { // (a call that uses the snapshot has a history)
@@ -176,54 +200,21 @@ __global__ void __launch_bounds__(kBlock) k_temporal_motion(TemporalKernelArgs a
                 const float4 sp = g.spheres[id - g.n_tris], ss = g.snap_spheres[id - g.n_tris];
                 moved = differs(xyz(ss), xyz(sp)) || differs(ss.w, sp.w);
                 if (moved) {
-                    const float s = ss.w / sp.w;
-                    P = V3{ fma_(P.x - sp.x, s, ss.x), fma_(P.y - sp.y, s, ss.y), fma_(P.z - sp.z, s, ss.z) };
+                    const float k = ss.w / sp.w;
+                    P = V3{ fma_(P.x - sp.x, k, ss.x), fma_(P.y - sp.y, k, ss.y), fma_(P.z - sp.z, k, ss.z) };
                     wv = P - o2;
                 }
             }
-            const float e2 = dot(wv, wv);
-            TapSums s{ 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
-            if (a.same_camera && !moved) {
-                temporal_tap(a, (int)x, (int)y, 1.0f, P, n, id, e2, s);
-            } else {
-                const V3 f2 = V3{ a.old_cam.forward[0], a.old_cam.forward[1], a.old_cam.forward[2] };
-                const V3 r2 = V3{ a.old_cam.right[0], a.old_cam.right[1], a.old_cam.right[2] };
-                const V3 u2 = V3{ a.old_cam.up[0], a.old_cam.up[1], a.old_cam.up[2] };
-                const V3 A = cross(r2, u2), B = cross(u2, f2), Cx = cross(f2, r2);
-                const float det = dot(f2, A), den = dot(wv, A);
-                if ((den > 0.0f && det > 0.0f) || (den < 0.0f && det < 0.0f)) {
-                    const float inv = 1.0f / den;
-                    const float sx = dot(wv, B) * inv, sy = dot(wv, Cx) * inv;
-                    const float fx = (sx + a.old_cam.cx) / a.old_cam.scale - 0.5f;
-                    const float fy = (sy + a.old_cam.cy) / a.old_cam.scale - 0.5f;
-                    if (fx >= -1.0f && fx < (float)a.width && fy >= -1.0f && fy < (float)a.height) { // (a NaN ends here)
-                        const float x0 = __builtin_floorf(fx), y0 = __builtin_floorf(fy);
-                        const float bx = fx - x0, by = fy - y0;
-                        const int ix = (int)x0, iy = (int)y0;
-#pragma unroll
-                        for (int j = 0; j < 2; ++j)
-#pragma unroll
-                            for (int i = 0; i < 2; ++i)
-                                temporal_tap(a, ix + i, iy + j, (i ? bx : 1.0f - bx) * (j ? by : 1.0f - by), P, n, id, e2, s);
-                    }
-                }
-            }
-            if (s.sw >= 0.25f) {
-                const float r = 1.0f / s.sw;
-                const float hr = s.sr * r, hg = s.sg * r, hb = s.sb * r;
-                l = fmin_(s.sl * r + 1.0f, a.max_history);
-                const float w = 1.0f / l;
-                out = make_float4(fma_(w, c.x - hr, hr), fma_(w, c.y - hg, hg), fma_(w, c.z - hb, hb), c.w);
-            }
+            s = gather_history(a, x, y, a.same_camera && !moved, P, n, wv, id);
         }
-        a.out[ip] = out;
-        a.new_h[ip] = make_float4(out.x, out.y, out.z, l);
-        took = l > 1.0f;
+        float l;
+        const float4 out = blend(a, c, s, l);
+        took = store_pixel(a, ip, out, l);
     }
     // k_temporal's counter scheme, once for each of the two counts
     const unsigned long long m = __ballot(took), mm = __ballot(moved);
     if (threadIdx.x == 0u && (m | mm)) {
-        const uint32_t line = (((blockIdx.y * gridDim.x + blockIdx.x) * 4u + threadIdx.y) % kTemporalCounters) * kCounterStride;
+        const uint32_t line = counter_line();
         if (m) atomicAdd(a.taken + line, (uint32_t)__popcll(m));
         if (mm) atomicAdd(g.moved + line, (uint32_t)__popcll(mm));
     }
