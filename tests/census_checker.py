@@ -1,32 +1,31 @@
 """ctypes binding of tests/census_ref/libcensus_ref.so — the scalar walker of docs/SPEC.md §5 that counts the branch class of every
 path vertex (tests/material_zoo.py names the classes). Test infrastructure only, like oracle/pto.py; `build()` runs its Makefile."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 from material_zoo import CLASSES
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-DIR = os.path.join(HERE, "census_ref")
-_lib = None
+import ref_lib
+
 
 
 class cr_stats(C.Structure):
     _fields_ = [("rays", C.c_uint64), ("paths", C.c_uint64), ("n", C.c_uint64 * (len(CLASSES) + 1))]
 
 
+# name -> (restype, argtypes): the entry points of census_ref.c
+SYMBOLS = {
+    "cr_render": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(cr_stats)]),
+    "cr_num_classes": (C.c_int, []),
+}
+
+
 def build():
-    """make the walker (incremental) and load it."""
-    global _lib
-    subprocess.run(["make", "-s", "-C", DIR], check=True)
-    if _lib is None:
-        _lib = C.CDLL(os.path.join(DIR, "libcensus_ref.so"))
-        _lib.cr_render.restype = C.c_int
-        _lib.cr_render.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(cr_stats)]
-        assert _lib.cr_num_classes() == len(CLASSES) + 1
-    return _lib
+    """The walker, made (incrementally) and loaded on the first call of a process."""
+    lib = ref_lib.load("census_ref", "libcensus_ref.so", SYMBOLS)
+    assert lib.cr_num_classes() == len(CLASSES) + 1
+    return lib
 
 
 def render(pto, scene, params, threads=0):

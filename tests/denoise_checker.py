@@ -2,17 +2,16 @@
 check the device against. Test infrastructure only, like oracle/pto.py; `build()` runs its Makefile."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-DIR = os.path.join(HERE, "denoise_ref")
+import ref_lib
+
+DIR = os.path.join(ref_lib.HERE, "denoise_ref")
 GUIDES_ONLY, NO_EDGE_STOPS = 1, 2
 MISS = 0xFFFFFFFF
 # dr_pass variants: §8.2 as written, then the deliberately wrong ones of the negative controls
 SPEC, SIGMA_C_FIXED, XZ_NO_STEP, D_LINEAR, WRONG_TAP, NO_MISS_SKIP = range(6)
-_lib = None
 
 
 class dr_params(C.Structure):
@@ -23,21 +22,18 @@ class dr_params(C.Structure):
 assert C.sizeof(dr_params) == 32
 
 
+# name -> (restype, argtypes): the entry points of denoise_ref.c
+SYMBOLS = {
+    "dr_guides": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "dr_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(dr_params), C.c_void_p]),
+    "dr_pass": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(dr_params), C.c_uint32, C.c_int, C.c_void_p]),
+    "dr_resolve": (C.c_int, [C.POINTER(dr_params), C.POINTER(dr_params)]),
+}
+
+
 def build():
-    """make the checker (incremental) and load it."""
-    global _lib
-    subprocess.run(["make", "-s", "-C", DIR], check=True)
-    if _lib is None:
-        _lib = C.CDLL(os.path.join(DIR, "libdenoise_ref.so"))
-        _lib.dr_guides.restype = C.c_int
-        _lib.dr_guides.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
-        _lib.dr_filter.restype = C.c_int
-        _lib.dr_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(dr_params), C.c_void_p]
-        _lib.dr_pass.restype = C.c_int
-        _lib.dr_pass.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(dr_params), C.c_uint32, C.c_int, C.c_void_p]
-        _lib.dr_resolve.restype = C.c_int
-        _lib.dr_resolve.argtypes = [C.POINTER(dr_params), C.POINTER(dr_params)]
-    return _lib
+    """The checker, made (incrementally) and loaded on the first call of a process."""
+    return ref_lib.load("denoise_ref", "libdenoise_ref.so", SYMBOLS)
 
 
 def params(iterations=0, sigma_color=0.0, sigma_normal=0.0, sigma_depth=0.0, sigma_albedo=0.0, flags=0):

@@ -6,18 +6,17 @@ from tests/golden/srgb8_thresholds.json, not from the product."""
 import ctypes as C
 import json
 import os
-import subprocess
 
 import numpy as np
 
+import ref_lib
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-DIR = os.path.join(HERE, "display_ref")
 AUTO, LINEAR, RESET = 1, 2, 4
 CLAMP, REINHARD, ACES = 0, 1, 2
 FRAME, DENOISED, TEMPORAL = 0, 1, 2
 # dr_display variants: §10 as written, then the deliberately wrong ones of the negative controls
 SPEC, QUANTISE_FIRST, ARITHMETIC_MEAN, NO_TRIM = range(4)
-_lib = None
 _table = None
 
 
@@ -34,26 +33,21 @@ class dr_info(C.Structure):
 assert C.sizeof(dr_params) == 40 and C.sizeof(dr_info) == 32
 
 
+# name -> (restype, argtypes): the entry points of display_ref.c
+SYMBOLS = {
+    "dr_resolve": (C.c_int, [C.POINTER(dr_params), C.POINTER(dr_params)]),
+    "dr_luminance": (C.c_float, [C.c_float, C.c_float, C.c_float]),
+    "dr_bin": (C.c_int, [C.c_float]),
+    "dr_unorm8": (C.c_uint8, [C.c_float]),
+    "dr_srgb8": (C.c_uint8, [C.c_void_p, C.c_float]),
+    "dr_display": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(dr_params), C.c_int, C.c_void_p, C.c_int, C.c_float,
+                             C.c_void_p, C.c_void_p, C.POINTER(dr_info), C.POINTER(C.c_int), C.POINTER(C.c_float)]),
+}
+
+
 def build():
-    """make the checker (incremental) and load it."""
-    global _lib
-    subprocess.run(["make", "-s", "-C", DIR], check=True)
-    if _lib is None:
-        _lib = C.CDLL(os.path.join(DIR, "libdisplay_ref.so"))
-        _lib.dr_resolve.restype = C.c_int
-        _lib.dr_resolve.argtypes = [C.POINTER(dr_params), C.POINTER(dr_params)]
-        _lib.dr_luminance.restype = C.c_float
-        _lib.dr_luminance.argtypes = [C.c_float, C.c_float, C.c_float]
-        _lib.dr_bin.restype = C.c_int
-        _lib.dr_bin.argtypes = [C.c_float]
-        _lib.dr_unorm8.restype = C.c_uint8
-        _lib.dr_unorm8.argtypes = [C.c_float]
-        _lib.dr_srgb8.restype = C.c_uint8
-        _lib.dr_srgb8.argtypes = [C.c_void_p, C.c_float]
-        _lib.dr_display.restype = C.c_int
-        _lib.dr_display.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(dr_params), C.c_int, C.c_void_p, C.c_int, C.c_float,
-                                    C.c_void_p, C.c_void_p, C.POINTER(dr_info), C.POINTER(C.c_int), C.POINTER(C.c_float)]
-    return _lib
+    """The checker, made (incrementally) and loaded on the first call of a process."""
+    return ref_lib.load("display_ref", "libdisplay_ref.so", SYMBOLS)
 
 
 def table():

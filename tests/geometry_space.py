@@ -27,6 +27,9 @@ from dataclasses import dataclass, field
 import numpy as np
 
 import adversarial_scenes as S
+import ray_caster64 as rc
+from float64_support import ALLOWED
+from trace_support import ray_sets
 
 W, H = 48, 36
 N_RAYS = 400
@@ -312,7 +315,78 @@ def find(name):
 
 def case_rays(pto, case):
     """The rays a case is traced with: its own, or the camera rays (SPEC §3, key 0, jittered as the generator's cameras are) of the W x H frame."""
-    import ray_caster64 as rc
     if case.rays is not None:
         return case.rays
     return rc.camera_rays(pto, case.sd.cam, W, H)
+
+
+# ---- what every implementation's ids have to pass on a case (the oracle in tests/test_geometry_space.py, the device in
+# tests/test_gpu_geometry_space.py)
+RAY_SET_FAMILIES = ("translate", "needles", "corridor")
+ORIGIN_CAP = 0.5 * 400 / 2362  # half the share of needles among a needle scene's triangles: 8.5 % (3.2 % seen)
+COUNTS = {}  # context -> class sizes of every check_case call, for whoever runs the tests from a script and wants the figures
+_CASES = {}
+
+
+def cases():
+    """name -> Case, built once for the session and never changed."""
+    if not _CASES:
+        _CASES.update((c.name, c) for c in all_cases())
+    return _CASES
+
+
+CASE_NAMES = [c for fam in ("translate_glass", "translate_tess") for c in (f"{fam}_{i}" for i in range(4))] + \
+    ["scale_glass_-40", "scale_glass_+40", "scale_tess_-40", "scale_tess_+40", "needles_0.01", "needles_0.0001", "needles_1e-06",
+     "degenerate", "corridor_x4096", "corridor_x2^-12", "flat_grid", "flat_line", "mixed_2^-12"] + \
+    [f"far_camera_{d}_{k}" for d in CAMERA_DISTANCES for k in ("spheres", "triangles")] + \
+    [f"far_sphere{t}_{n}" for t in ("", "_oblique") for n in SPHERE_RADII]
+
+
+def counts(c):
+    return {k: len(v) for k, v in c.items() if k not in ("want", "sphere_ratio")}
+
+
+def check_case(case, rs, o, d, ids, cast, ctx):
+    """The assertions every f32 implementation's ids have to pass on a case's ray set `rs`; returns the classes' sizes.
+
+    wrong == 0. in_plane == 0, except that rays along an axis (the zero-component set) of a translated scene may run in the plane of
+    an axis-aligned wall: at most 1 %. edge + coincident <= ALLOWED of the rays; for the zero-component rays at the offset of 65537
+    the cap is 2.5 %: f32's grid is 2^-8 there, so origins and walls snap to it and 1.75 % of such rays graze an edge in float64. On a
+    case with far spheres the cap holds for what the unscaled bands explain; what only the scaled sphere band explains is not capped
+    (its size follows from the distance: 8.6 % of the frame at 1000 units), but none may lie outside it. No degenerate triangle is hit.
+    At the offset of 1e6 every coordinate lies on f32's grid of 1/16, 33 values across the box. The three extra ray sets start on that
+    grid: an axis ray lies in a wall's plane when its origin has the wall's coordinate (2 of 33 values, the end ones at half weight)
+    and no component along the wall's normal (5 of the 9 directions), 3 · 1/32 · 5/9 = 5.2 % at most (3 % seen); and it runs along a
+    mesh line of the tessellated box, where float64 cannot say what f32 should do, far more often than a ray of a continuum does.
+    Their edge + coincident cap is 5 % (3.5 % seen on the axis rays, 1.25 % on the incoherent ones), as 2.5 % is at 65537.
+    On the needle scenes a ray of the on-surface set may start on an oblique triangle, a rounded point a few ulps off its plane;
+    whether that triangle is hit at once is the class `origin` of ray_caster64.classify, which holds the rest of the answer to the
+    caster. The floor is 16 ulps of the origin's largest coordinate (3 ulps off the plane at a cosine of 0.2). Such rays are at most
+    half of those that start on a needle (float64 puts the start in front of the triangle for half of them), needles being 400 of
+    the scene's triangles: ORIGIN_CAP of the set."""
+    sd = case.sd
+    floor = None
+    if rs == "on_surface" and case.family == "needles":
+        floor = 16 * np.spacing(np.abs(o).max(axis=1)).astype(np.float64)
+    c = rc.classify(sd.verts, sd.spheres, o, d, ids, cast, sphere_band=case.sphere_band, t_floor=floor)
+    n = counts(c)
+    COUNTS[ctx] = n
+    assert n["wrong"] == 0, (ctx, n, c["wrong"][:10], ids[c["wrong"][:10]], c["want"][c["wrong"][:10]])
+    assert n["origin"] <= ORIGIN_CAP * len(o), (ctx, n)
+    axis_rays = rs == "zero_components" and case.family == "translate"
+    on_grid = case.M == 1e6 and rs != "camera"
+    assert n["in_plane"] <= ((0.052 if on_grid else 0.01) * len(o) if axis_rays else 0), (ctx, n)
+    capped = counts(rc.classify(sd.verts, sd.spheres, o, d, ids, cast, t_floor=floor)) if case.sphere_band else n
+    cap = 0.05 if on_grid else 0.025 if axis_rays and case.M == 65537.0 else ALLOWED
+    assert capped["edge"] + capped["coincident"] <= cap * len(o), (ctx, capped)
+    assert not np.isin(ids, case.degenerate).any(), ctx
+    if case.family == "far_sphere" and case.name.rsplit("_", 1)[0] == "far_sphere" and case.M <= 300 * SPHERE_R:
+        assert n["agree"] == len(o), (ctx, n)  # on the axis, up to 300 radii: no disagreement at all
+    return n
+
+
+def case_ray_sets(pto, case):
+    sets = [("camera",) + tuple(case_rays(pto, case))]
+    if case.family in RAY_SET_FAMILIES:
+        sets += [s for s in ray_sets(pto, case.sd, n=N_RAYS) if s[0] != "camera"]
+    return sets

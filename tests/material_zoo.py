@@ -270,3 +270,14 @@ EDGE_PARAMS = {  # depth and roulette edges on slabs and glass_box
 
 def edge_params(P, key, flags=0):
     return P.make_params(W, H, flags=flags, **EDGE_PARAMS[key])
+
+
+# the configurations whose next-event frames are compared (tests/test_materials.py, tests/test_gpu_materials.py)
+NEE_CONFIGS = [("palette", "front"), ("glass_box", "outside"), ("glass_box", "inside")]
+
+
+def emissive_triangles(sd):
+    """Mask of the triangles SPEC §7 takes as lights: some emission and a positive area, whatever the material's kind."""
+    e1, e2 = sd.verts[:, 3:6] - sd.verts[:, 0:3], sd.verts[:, 6:9] - sd.verts[:, 0:3]
+    area = 0.5 * np.linalg.norm(np.cross(e1.astype(np.float64), e2.astype(np.float64)), axis=1)
+    return sd.mats["emission"][sd.tri_mat].any(axis=1) & (area > 0)

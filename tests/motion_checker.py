@@ -6,18 +6,15 @@ The history and the snapshot are explicit: `accumulate()` takes a `History` (or 
 snapshot its call recorded (flagged calls only) and a `scene_key` of the caller's choosing: §9.1's "same scene object, no commit since" is
 `history.scene_key == scene_key`."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-DIR = os.path.join(HERE, "motion_ref")
+import ref_lib
+
 RESET, MATCH_IDS, MOTION = 1, 2, 8
 MISS = 0xFFFFFFFF
 # mr_accumulate variants: the spec as written, then the deliberately wrong ones of the negative controls
 SPEC, IGNORE_MOTION, NEW_PLANE, NEW_NORMAL, NO_RADIUS_RATIO = range(5)
-_lib = None
 
 
 class mr_params(C.Structure):
@@ -33,19 +30,18 @@ class mr_camera(C.Structure):  # pt_camera / pto_camera
 assert C.sizeof(mr_params) == 32 and C.sizeof(mr_camera) == 64
 
 
+# name -> (restype, argtypes): the entry points of motion_ref.c
+SYMBOLS = {
+    "mr_resolve": (C.c_int, [C.POINTER(mr_params), C.POINTER(mr_params)]),
+    "mr_accumulate": (C.c_long, [C.c_void_p, C.c_void_p, C.POINTER(mr_camera), C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
+                                 C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(mr_camera), C.c_void_p, C.c_void_p,
+                                 C.POINTER(mr_params), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_long)]),
+}
+
+
 def build():
-    """make the checker (incremental) and load it."""
-    global _lib
-    subprocess.run(["make", "-s", "-C", DIR], check=True)
-    if _lib is None:
-        _lib = C.CDLL(os.path.join(DIR, "libmotion_ref.so"))
-        _lib.mr_resolve.restype = C.c_int
-        _lib.mr_resolve.argtypes = [C.POINTER(mr_params), C.POINTER(mr_params)]
-        _lib.mr_accumulate.restype = C.c_long
-        _lib.mr_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(mr_camera), C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
-                                       C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(mr_camera), C.c_void_p, C.c_void_p,
-                                       C.POINTER(mr_params), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_long)]
-    return _lib
+    """The checker, made (incrementally) and loaded on the first call of a process."""
+    return ref_lib.load("motion_ref", "libmotion_ref.so", SYMBOLS)
 
 
 def params(max_history=0, plane_tolerance=0.0, normal_min=0.0, flags=0):

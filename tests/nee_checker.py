@@ -1,30 +1,27 @@
 """ctypes binding of tests/nee_ref/libnee_ref.so — the scalar restatement of docs/SPEC.md §7 (next-event estimation) that the NEE tests
-check the device against. Test infrastructure only, like oracle/pto.py; `build()` (the module fixture) runs its Makefile."""
+check the device against. Test infrastructure only, like oracle/pto.py; `build()` runs its Makefile."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-DIR = os.path.join(HERE, "nee_ref")
+import ref_lib
+
 NEE, NO_MIS, NO_COSL, SWAP_PMF = 1, 2, 4, 8
-_lib = None
 
 
 class nr_stats(C.Structure):
     _fields_ = [("ext_rays", C.c_uint64), ("shadow_rays", C.c_uint64), ("paths", C.c_uint64), ("n_lights", C.c_uint64)]
 
 
+# name -> (restype, argtypes): the entry points of nee_ref.c
+SYMBOLS = {
+    "nr_render": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(nr_stats)]),
+}
+
+
 def build():
-    """make the checker (incremental) and load it."""
-    global _lib
-    subprocess.run(["make", "-s", "-C", DIR], check=True)
-    if _lib is None:
-        _lib = C.CDLL(os.path.join(DIR, "libnee_ref.so"))
-        _lib.nr_render.restype = C.c_int
-        _lib.nr_render.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(nr_stats)]
-    return _lib
+    """The checker, made (incrementally) and loaded on the first call of a process."""
+    return ref_lib.load("nee_ref", "libnee_ref.so", SYMBOLS)
 
 
 def render(pto, scene, params, flags=NEE, with_sq=False, threads=0):

@@ -3,18 +3,15 @@ temporal tests check the device against. Test infrastructure only, like tests/de
 
 The history is explicit: `accumulate()` takes a `History` (or None) and returns the next one."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-DIR = os.path.join(HERE, "temporal_ref")
+import ref_lib
+
 RESET, MATCH_IDS = 1, 2
 MISS = 0xFFFFFFFF
 # tr_accumulate variants: §9 as written, then the deliberately wrong ones of the negative controls
 SPEC, NO_REPROJECTION, NO_PLANE_TEST, NEAREST_TAP, FIXED_ALPHA = range(5)
-_lib = None
 
 
 class tr_params(C.Structure):
@@ -30,18 +27,17 @@ class tr_camera(C.Structure):  # pt_camera / pto_camera
 assert C.sizeof(tr_params) == 32 and C.sizeof(tr_camera) == 64
 
 
+# name -> (restype, argtypes): the entry points of temporal_ref.c
+SYMBOLS = {
+    "tr_resolve": (C.c_int, [C.POINTER(tr_params), C.POINTER(tr_params)]),
+    "tr_accumulate": (C.c_long, [C.c_void_p, C.c_void_p, C.POINTER(tr_camera), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                 C.POINTER(tr_camera), C.POINTER(tr_params), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
+
 def build():
-    """make the checker (incremental) and load it."""
-    global _lib
-    subprocess.run(["make", "-s", "-C", DIR], check=True)
-    if _lib is None:
-        _lib = C.CDLL(os.path.join(DIR, "libtemporal_ref.so"))
-        _lib.tr_resolve.restype = C.c_int
-        _lib.tr_resolve.argtypes = [C.POINTER(tr_params), C.POINTER(tr_params)]
-        _lib.tr_accumulate.restype = C.c_long
-        _lib.tr_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(tr_camera), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
-                                       C.POINTER(tr_camera), C.POINTER(tr_params), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    return _lib
+    """The checker, made (incrementally) and loaded on the first call of a process."""
+    return ref_lib.load("temporal_ref", "libtemporal_ref.so", SYMBOLS)
 
 
 def params(max_history=0, plane_tolerance=0.0, normal_min=0.0, flags=0):

@@ -13,6 +13,7 @@ import pytest
 
 import blob_ref as B
 import lbvh_ref as L
+from trace_support import LAYOUTS
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 _spec = importlib.util.spec_from_file_location("make_blob_digests", os.path.join(GOLDEN, "make_blob_digests.py"))
@@ -20,7 +21,6 @@ M = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(M)
 
 SCENES = ("cornell", "cornell_glass", "tess_2k", "tess_70k", "soup_5k", "soup_50k", "duplicates", "stacked_layers")
-LAYOUTS = (2, 4, 68, 72, 73)
 F = np.float32
 
 
@@ -102,7 +102,7 @@ def test_quantiser_extent_255_times_a_power_of_two():
 
 
 def test_quantiser_axis_with_only_the_padding():
-    """The z axis of the `planar` scene of tests/test_gpu_lbvh.py: every vertex at z = -0.5, every child [-0.5 - pad, -0.5 + pad] with
+    """The z axis of the `planar` scene of tests/blob_scenes.py: every vertex at z = -0.5, every child [-0.5 - pad, -0.5 + pad] with
     pad = 1e-6f. Floats are 2^-24 apart above 0.5 in magnitude and 2^-25 below: lo = -(0.5 + 17 * 2^-24) (1e-6 = 16.8 * 2^-24),
     hi = -(0.5 - 34 * 2^-25) (1e-6 = 33.6 * 2^-25), ext = 34 * 2^-24 = 17 * 2^-23 exactly. ext / 255 = 2^-23 / 15 lies between 2^-27 and
     2^-26: s = 2^-26, exponent 101, qlo = 0, qhi = 17 * 8 = 136, whose decode is hi exactly."""

@@ -15,11 +15,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 H3 = np.array([0.0625, 0.25, 0.375, 0.25, 0.0625])
 
 
-@pytest.fixture(scope="session", autouse=True)
-def _checker():
-    dc.build()
-
-
 def hit_guides(h, w, ids=None, normal=(0.0, 0.0, 1.0), t=2.0, albedo=(0.5, 0.5, 0.5)):
     g = np.zeros((h, w, 8), np.float32)
     g[..., 0:3], g[..., 3], g[..., 4:7] = normal, t, albedo
@@ -49,6 +44,7 @@ def b3_atrous64(img, passes):
 
 
 def test_checker_builds():
+    dc.build()
     assert os.path.exists(os.path.join(dc.DIR, "libdenoise_ref.so"))
     it, sc, sn, sz, sa = dc.defaults()
     assert 1 <= it <= 8 and min(sc, sn, sz, sa) > 0

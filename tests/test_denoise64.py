@@ -20,11 +20,6 @@ SIGMAS = ("sigma_color", "sigma_normal", "sigma_depth", "sigma_albedo")
 COLOUR_LIMIT = 2.0 ** 126
 
 
-@pytest.fixture(scope="session", autouse=True)
-def _checker():
-    dc.build()
-
-
 def field(kind, h, w, seed=0):
     """(image, guides) of a synthetic (h, w) frame: `kind` picks the colours and guides."""
     rng = np.random.default_rng(seed)

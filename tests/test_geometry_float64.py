@@ -7,58 +7,13 @@ import pytest
 
 import adversarial_scenes as S
 import ray_caster64 as rc
+import geometry_space as G
+from float64_support import H, PINNED_CRACKS, W, _size, build_bvh_detached, check_classes, crack_rays, oracle_ids, scenes
 from geometry_space import SCALE_FIRST_BAD, SCALE_K
-
-W, H = 65, 49           # odd: the axis camera's centre row and column
-CRACK_RAYS = 300        # rays aimed at interior points of shared edges of the tessellated Cornell box
-PINNED_CRACKS = 44      # of them, the rays SPEC §4's Möller–Trumbore lets through (brute force and BVH alike)
-ALLOWED = 0.01          # the edge and coincident classes together stay below this fraction of a frame's pixels
+from trace_support import LAYOUTS, oracle
 
 
-def build_bvh_detached(scene, layout=0):
-    """The product's host builder on a detached scene. Imported late: libptrt.so exists only once the build fixture has run,
-    after collection."""
-    from pathtracing_amd.host import build_bvh_detached as build
-    return build(scene, layout)
-
-
-def oracle_ids(pto, sd, layout, w, h):
-    sd = S.id_scene(sd)
-    info, nodes, tris = build_bvh_detached(sd, layout)
-    img, _ = pto.render(pto.Scene(sd, (info.width, nodes, tris)), S.params_id(w, h))
-    return S.ids_of(img)
-
-
-def scenes(P, w=W, h=H):
-    N = P.native
-    c1 = P.make_scene(N.PT_SCENE_CORNELL, 0, 1, w, h)
-    return {
-        "tess": P.make_scene(N.PT_SCENE_CORNELL_TESS, 2000, 5, w + 1, h + 1),
-        "c4": P.make_scene(N.PT_SCENE_CORNELL_GLASS, 0, 5, w, h),
-        "layers": S.stacked_layers(w, h),
-        "duplicates": S.duplicates(w, h)[0],
-        "axis": S.axis_camera(c1, w, h),
-        "floor": S.floor_camera(c1, w, h),
-        "spheres64": S.sphere_list(64, w, h),
-        "inside_sphere": S.sphere_list(31, w, h, camera_inside=True),
-    }
-
-
-def check_classes(sd, o, d, ids, name, cast_result=None):
-    """Assert the classification of `ids` against the caster; returns the classes."""
-    c = rc.classify(sd.verts, sd.spheres, o, d, ids, cast_result)
-    n = {k: len(v) for k, v in c.items() if k != "want"}
-    assert n["wrong"] == 0, (name, n, c["wrong"][:10], ids[c["wrong"][:10]], c["want"][c["wrong"][:10]])
-    assert n["edge"] + n["coincident"] <= ALLOWED * len(o), (name, n)
-    return c
-
-
-# the frame size the tessellated scene is checked at: its regular grid lines up with every 4th pixel column of a 65-wide frame
-def _size(name):
-    return (W + 1, H + 1) if name == "tess" else (W, H)
-
-
-@pytest.mark.parametrize("layout", [2, 4, 68, 72, 73])
+@pytest.mark.parametrize("layout", LAYOUTS)
 def test_oracle_closest_hit_matches_float64(P, pto, layout):
     """Every adversarial scene: the oracle's primary-hit id image (pto_render of an id_scene) classified against the caster.
     The floor camera's centre row lies in the floor's plane; those rays are the only ones left out."""
@@ -131,7 +86,7 @@ def test_caster_in_plane_rule():
     assert not in_plane.any() and list(ids) == [2, 2]
 
 
-@pytest.mark.parametrize("layout", [2, 4, 68, 72, 73])
+@pytest.mark.parametrize("layout", LAYOUTS)
 def test_stacked_layers_overflow_the_lds_stack(P, pto, layout):
     """Walking the product's blob (SPEC §4 push order, float64 boxes shrunk by a margin) shows that every sampled camera ray of
     the stacked-layers scene holds more than 12 + 4 stack entries, and never more than pt_bvh_info.stack_need."""
@@ -168,7 +123,7 @@ def test_power_of_two_scale_is_invisible_in_the_oracle(P, pto, k):
         ref, ost = pto.render(pto.Scene(sd, (info.width, nodes, tris)), p)
         s2 = S.scaled(sd, k)
         p2 = P.make_params(48, 36, spp=2, max_depth=6, ray_eps=1e-4 * 2.0 ** k)
-        for layout in (2, 4, 68, 72, 73):
+        for layout in LAYOUTS:
             info, nodes, tris = build_bvh_detached(s2, layout)
             img, st = pto.render(pto.Scene(s2, (info.width, nodes, tris)), p2)
             assert st.rays == ost.rays and np.array_equal(img, ref), (k, layout)
@@ -187,16 +142,6 @@ def test_scale_envelope_is_pinned(P, pto):
             info, nodes, tris = build_bvh_detached(s, 2)
             frames.append(pto.render(pto.Scene(s, (info.width, nodes, tris)), P.make_params(48, 36, spp=2, max_depth=6, ray_eps=eps))[0])
         assert not np.array_equal(frames[0], frames[1]), k
-
-
-def crack_rays(P, pto):
-    """The tessellated Cornell box (30,000 triangles, 160x120 camera) and CRACK_RAYS rays from its camera to shared-edge points,
-    each as the only pixel of a 1x1 camera (so the device can trace exactly these rays)."""
-    sd = P.make_scene(P.native.PT_SCENE_CORNELL_TESS, 30000, 0x5EED0001, 160, 120)
-    org = np.array(sd.cam.origin[:], np.float32)
-    cams = [S.ray_camera(sd, org, p - org) for p in S.shared_edge_targets(sd, CRACK_RAYS)]
-    rays = [pto.camera_ray(c.cam, 0, 0) for c in cams]
-    return sd, cams, np.array([r[0] for r in rays]), np.array([r[1] for r in rays])
 
 
 def test_shared_edge_leak_is_pinned(P, pto):
@@ -225,8 +170,6 @@ def test_shared_edges_are_watertight(P, pto):
                                        "= 0.5 r², is the size of the sphere, and 280 of 1728 rays of the fan disagree with float64 far "
                                        "outside EDGE_BAND. The well-conditioned form r² − |oc − b·d|² (which the caster uses) would turn this.")
 def test_far_sphere_at_3000_radii_agrees_with_float64(P, pto):
-    import geometry_space as G
-    from test_gpu_trace import oracle
     case = G.find("far_sphere_3000")
     o, d = case.rays
     ids, _, _ = oracle(pto, pto.Scene(case.sd), o, d)
@@ -235,8 +178,6 @@ def test_far_sphere_at_3000_radii_agrees_with_float64(P, pto):
 
 def _scene_at_two_to_the_64(pto):
     """(unscaled ids, ids with every length times 2^64) of the glass box's camera rays, brute force."""
-    import geometry_space as G
-    from test_gpu_trace import oracle
     sd = G.glass()
     o, d = rc.camera_rays(pto, sd.cam, G.W, G.H)
     want, _, _ = oracle(pto, pto.Scene(sd), o, d)

@@ -13,10 +13,9 @@ import pytest
 import adversarial_scenes as S
 import blob_ref as B
 import lbvh_ref as L
-from test_gpu_lbvh import NAMES
-from test_gpu_lbvh import scene as lbvh_scene
-from test_gpu_trace import LAYOUTS, _scenes
-from test_gpu_update import SCENES, blob, deform, moved
+from blob_scenes import NAMES, SCENES, blob, deform, moved
+from blob_scenes import scene as lbvh_scene
+from trace_support import LAYOUTS, scenes
 
 pytestmark = pytest.mark.gpu
 
@@ -28,7 +27,7 @@ _update_scenes = {}
 def get_scene(P, name):
     if name in SCENES:
         if not _update_scenes:
-            _update_scenes.update(_scenes(P))
+            _update_scenes.update(scenes(P))
         return _update_scenes[name]
     return lbvh_scene(P, name)[0]
 

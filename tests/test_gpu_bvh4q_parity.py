@@ -6,8 +6,8 @@ import numpy as np
 import pytest
 
 import adversarial_scenes as S
-from test_geometry_float64 import W, H, _size, scenes
-from test_gpu_parity import assert_parity, run_both
+from float64_support import W, H, _size, scenes
+from frame_checks import assert_parity, run_both
 
 pytestmark = pytest.mark.gpu
 
@@ -38,7 +38,7 @@ def test_generator_scenes_match_oracle(P, pto, renderer, kind):
 
 
 def test_adversarial_scenes_match_oracle(P, pto, renderer):
-    """Every scene of tests/adversarial_scenes.py (through test_geometry_float64.scenes): the id image and the path-traced frame."""
+    """Every scene of tests/adversarial_scenes.py (through float64_support.scenes): the id image and the path-traced frame."""
     for name, sd in scenes(P).items():
         w, h = _size(name)
         img, ref = _frame(P, pto, renderer, S.id_scene(sd), S.params_id(w, h))

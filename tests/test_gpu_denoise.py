@@ -10,17 +10,10 @@ import numpy as np
 import pytest
 
 import denoise_checker as dc
-import nee_checker as nc
+from frame_checks import check_denoise as check
+from trace_support import LAYOUTS
 
 pytestmark = pytest.mark.gpu
-
-LAYOUTS = [2, 4, 68, 72, 73]
-
-
-@pytest.fixture(scope="session", autouse=True)
-def _checkers():
-    dc.build()
-    nc.build()
 
 
 def sky_scene(P, w, h):
@@ -34,32 +27,6 @@ def sky_scene(P, w, h):
     cam.forward[:], cam.right[:], cam.up[:] = f.tolist(), (r * 0.3).tolist(), (u * 0.3).tolist()
     cam.scale, cam.cx, cam.cy, cam.jitter = 2.0 / h, w / h, 1.0, 1
     return dataclasses.replace(sd, cam=cam, sky=np.array([0.3, 0.4, 0.6], np.float32))
-
-
-def check(P, pto, r, sd, ctx, p=None, **kw):
-    """Denoise the renderer's current frame; its guides and image equal the checker's bit for bit."""
-    h, w = r.Params.height, r.Params.width
-    st = r.Denoise(**kw)
-    g = r.ReadGuides()
-    want_g = dc.guides(pto, pto.Scene(sd), w, h)
-    bad = np.argwhere((g.view(np.uint32) != want_g.view(np.uint32)).any(axis=2))
-    assert len(bad) == 0, (ctx, len(bad), bad[:3].tolist(), g[tuple(bad[0])].tolist() if len(bad) else None,
-                           want_g[tuple(bad[0])].tolist() if len(bad) else None)
-    assert st.rays == w * h, ctx
-    p = p if p is not None else dc.params(kw.get("iterations", 0), kw.get("sigma_color", 0.0), kw.get("sigma_normal", 0.0),
-                                          kw.get("sigma_depth", 0.0), kw.get("sigma_albedo", 0.0),
-                                          (dc.GUIDES_ONLY if kw.get("guides_only") else 0) | (0 if kw.get("edge_stops", True) else dc.NO_EDGE_STOPS))
-    if p.flags & dc.GUIDES_ONLY:
-        with pytest.raises(P.PtException) as e:
-            r.ReadDenoised()
-        assert e.value.status == P.native.PT_ERR_NOT_COMMITTED
-        return st, g, None
-    img = r.ReadDenoised()
-    want = dc.filter(r.ReadFramebuffer(), want_g, p)
-    bad = np.argwhere((img.view(np.uint32) != want.view(np.uint32)).any(axis=2))
-    assert len(bad) == 0, (ctx, len(bad), bad[:3].tolist(), img[tuple(bad[0])].tolist() if len(bad) else None,
-                           want[tuple(bad[0])].tolist() if len(bad) else None)
-    return st, g, img
 
 
 @pytest.mark.parametrize("name", ["cornell", "sky"])

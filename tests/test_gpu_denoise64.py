@@ -12,18 +12,13 @@ import pytest
 import adversarial_scenes as adv
 import denoise64 as d64
 import denoise_checker as dc
+from trace_support import LAYOUTS
 
 pytestmark = pytest.mark.gpu
 
-LAYOUTS = [2, 4, 68, 72, 73]
 FLT_MAX = d64.FLT_MAX
 SIGMA_GRID = [2.0 ** -140, 2.0 ** -126, 2.0 ** -60, 2.0 ** -8, 0.3, 1.0, 2.0 ** 8, 3e19, 2.0 ** 60, FLT_MAX]
 W, H = 48, 32
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _checker():
-    dc.build()
 
 
 def sky_scene(P, w, h):

@@ -24,11 +24,6 @@ SOURCES = {"frame": dc.FRAME, "denoised": dc.DENOISED, "temporal": dc.TEMPORAL}
 SPECIALS = [0.0, -0.0, -1.5, 1e-40, -1e-40, np.inf, -np.inf, np.nan, 2.0 ** 32, 3e38, 2.0 ** -33]
 
 
-@pytest.fixture(scope="session", autouse=True)
-def _checker():
-    dc.build()
-
-
 def assemble(P, r, img):
     """Make `img` ((h, w, 4) float32) the renderer's framebuffer through the public ABI: a tile-major buffer in SPEC §6 slot order,
     pt_assemble_tiles with spp = 1 (the framebuffer is then the buffer times 1.0f). Returns the framebuffer as read back."""

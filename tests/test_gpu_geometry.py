@@ -12,12 +12,12 @@ import pytest
 
 import adversarial_scenes as S
 import ray_caster64 as rc
-from test_geometry_float64 import CRACK_RAYS, PINNED_CRACKS, SCALE_K, W, H, _size, check_classes, crack_rays, scenes
-from test_gpu_parity import run_both
+from float64_support import CRACK_RAYS, PINNED_CRACKS, W, H, _size, check_classes, crack_rays, scenes
+from frame_checks import _config_grid, run_both
+from geometry_space import SCALE_K
+from trace_support import LAYOUTS
 
 pytestmark = pytest.mark.gpu
-
-LAYOUTS = [2, 4, 68, 72, 73]
 
 
 def device_ids(P, pto, r, sd, width, w, h):
@@ -64,20 +64,6 @@ def test_duplicates_lowest_id_wins_on_every_kernel(P, pto, renderer):
             assert tri.sum() > 0.5 * W * H
             assert np.array_equal(ids[tri], lowest[ids[tri].astype(np.int64)]), (flags, width)
             assert np.array_equal(img, ref), (flags, width)
-
-
-def _config_grid(P):
-    """12 (layout | builder, extend flags, count) configurations: every extend kernel in both its counting and its plain
-    instantiation (6 x 2), with the layouts cycling underneath them and the builder switching after each pass over the
-    five layouts, so every layout and both builders appear too."""
-    N = P.native
-    kernels = [0, N.PT_FLAG_EXTEND_SIMPLE, N.PT_FLAG_EXTEND_PACKED, N.PT_FLAG_EXTEND_POOL, N.PT_FLAG_SPLIT_KERNELS,
-               N.PT_FLAG_SPLIT_KERNELS | N.PT_FLAG_EXTEND_PACKED]
-    out = []
-    for i in range(2 * len(kernels)):
-        width = LAYOUTS[i % len(LAYOUTS)] | (N.PT_BVH_BUILD_LBVH if (i // len(LAYOUTS)) % 2 else 0)
-        out.append((width, kernels[i // 2], i % 2 == 0))
-    return out
 
 
 @pytest.mark.parametrize("name", ["layers", "duplicates", "axis", "floor", "spheres64", "inside_sphere"])

@@ -13,10 +13,9 @@ import pytest
 import adversarial_scenes as S
 import geometry_space as G
 import ray_caster64 as rc
-from test_geometry_space import CASE_NAMES, case_ray_sets, cases, check_case
-from test_gpu_geometry import _config_grid
-from test_gpu_parity import run_both
-from test_gpu_trace import LAYOUTS, MISS, check_closest, commit, ids_of, oracle, records, same
+from frame_checks import _config_grid, run_both
+from geometry_space import CASE_NAMES, case_ray_sets, cases, check_case
+from trace_support import LAYOUTS, MISS, check_closest, commit, ids_of, oracle, records, same
 
 pytestmark = pytest.mark.gpu
 
@@ -75,7 +74,7 @@ def test_id_image_matches_the_query(P, pto, renderer, name):
 
 @pytest.mark.parametrize("name", PATH_TRACE)
 def test_full_path_trace(P, pto, renderer, name):
-    """47 x 35, spp 3, depth 8, two streams, the case's ray_eps, on the twelve configurations of test_gpu_geometry._config_grid
+    """47 x 35, spp 3, depth 8, two streams, the case's ray_eps, on the twelve configurations of frame_checks._config_grid
     (every extend kernel counting and plain, the layouts and builders cycling): frame, rays, paths and visit counters are the
     oracle's, and Render raises nothing (BvhInfo().stack_need is reachable: a stack overflow raises). The needle case's trees need
     more than the 12 LDS entries, so its rays run through the overflow columns."""

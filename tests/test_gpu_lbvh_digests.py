@@ -11,7 +11,8 @@ import os
 
 import pytest
 
-import test_gpu_lbvh as T
+from blob_scenes import NAMES
+from trace_support import LAYOUTS
 
 pytestmark = pytest.mark.gpu
 
@@ -20,7 +21,7 @@ _spec = importlib.util.spec_from_file_location("make_lbvh_blob_digests", os.path
 M = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(M)
 
-SCENES = tuple(T.NAMES) + (M.BIG,)
+SCENES = tuple(NAMES) + (M.BIG,)
 
 
 @pytest.fixture(scope="module")
@@ -34,12 +35,12 @@ def built_scenes(P):
 def golden():
     with open(M.FIXTURE) as f:
         g = json.load(f)
-    assert set(g["blobs"]) == set(SCENES) and all(set(v) == {str(x) for x in T.LAYOUTS} for v in g["blobs"].values())
+    assert set(g["blobs"]) == set(SCENES) and all(set(v) == {str(x) for x in LAYOUTS} for v in g["blobs"].values())
     assert g["clusters"][M.BIG] > 8192  # bvh_build.cpp build_sah_over_boxes: the threaded top storey
     return g["blobs"]
 
 
 @pytest.mark.parametrize("scene", SCENES)
 def test_lbvh_blob_matches_recorded_digest(P, renderer, built_scenes, golden, scene):
-    for layout in T.LAYOUTS:
+    for layout in LAYOUTS:
         assert M.digest(P, renderer, built_scenes[scene], layout) == golden[scene][str(layout)], (scene, layout)

@@ -8,21 +8,12 @@ import pytest
 
 import denoise_checker as dc
 import material_zoo as mz
-import nee_checker as nc
-from test_gpu_denoise import check as check_denoise
-from test_gpu_nee import check as check_nee
-from test_gpu_parity import run_both
-from test_materials import NEE_CONFIGS, emissive_triangles
+from frame_checks import check_denoise, check_nee, run_both
+from material_zoo import NEE_CONFIGS, emissive_triangles
 
 pytestmark = pytest.mark.gpu
 
-LAYOUTS = [0, 68, 73]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _checkers():
-    dc.build()
-    nc.build()
+ZOO_LAYOUTS = [0, 68, 73]
 
 
 def pipelines(P):
@@ -43,11 +34,11 @@ def equal_to_the_oracle(P, pto, r, sd, params, layout, count, ctx):
     return st
 
 
-@pytest.mark.parametrize("layout", LAYOUTS)
+@pytest.mark.parametrize("layout", ZOO_LAYOUTS)
 @pytest.mark.parametrize("cfg", mz.CONFIGS, ids=["-".join(c) for c in mz.CONFIGS])
 def test_parity_on_every_pipeline(P, pto, renderer, cfg, layout):
     sd = mz.build(*cfg)
-    pair = mz.CONFIGS.index(cfg) * len(LAYOUTS) + LAYOUTS.index(layout)
+    pair = mz.CONFIGS.index(cfg) * len(ZOO_LAYOUTS) + ZOO_LAYOUTS.index(layout)
     for i, (name, flags) in enumerate(pipelines(P)):  # visit counters on every second case: each pipeline on half of the pairs
         equal_to_the_oracle(P, pto, renderer, sd, mz.parity_params(P, flags), layout, (pair + i) % 2 == 1, (cfg, layout, name))
 
@@ -89,7 +80,7 @@ def test_next_event_estimation(P, pto, renderer, cfg):
     lit = emissive_triangles(sd)
     if cfg[0] == "palette":
         assert {int(k) for k in sd.mats["kind"][sd.tri_mat[lit]]} == {0, 1, 2}
-    for layout in LAYOUTS:
+    for layout in ZOO_LAYOUTS:
         renderer.SetScene(sd, layout)
         params = mz.parity_params(P, P.native.PT_FLAG_NEXT_EVENT)
         renderer.Params = params
@@ -100,7 +91,7 @@ def test_next_event_estimation(P, pto, renderer, cfg):
 def test_guides_of_every_material(P, pto, renderer):
     """pt_denoise's guides on the palette: normal, depth, the albedo of every material hit and the primitive id, bit for bit."""
     sd = mz.build("palette", "front")
-    for layout in LAYOUTS:
+    for layout in ZOO_LAYOUTS:
         renderer.SetScene(sd, layout)
         renderer.Params = mz.parity_params(P)
         renderer.Render(0.0)

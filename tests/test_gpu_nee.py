@@ -7,16 +7,11 @@ import numpy as np
 import pytest
 
 import nee_checker as nc
+from frame_checks import check_nee as check
+from frame_checks import nee_params
+from trace_support import H, LAYOUTS, W
 
 pytestmark = pytest.mark.gpu
-
-W, H = 48, 36
-LAYOUTS = [2, 4, 68, 72, 73]
-
-
-@pytest.fixture(scope="session", autouse=True)
-def _checker():
-    nc.build()
 
 
 def scenes(P):
@@ -28,27 +23,6 @@ def scenes(P):
         "lights": nc.many_lights_scene(P, W, H),
         "grazing": nc.grazing_scene(P, W, H),
     }
-
-
-def nee_params(P, **kw):
-    p = P.make_params(W, H, **kw)
-    p.flags |= P.native.PT_FLAG_NEXT_EVENT
-    return p
-
-
-def check(P, pto, r, sd, params, ctx):
-    """The device's NEE frame equals the checker's bit for bit; rays = extension + shadow rays; the extension rays are the plain
-    frame's rays."""
-    st = r.Render(0.0)
-    img = r.ReadFramebuffer()
-    ref, cst, _ = nc.render(pto, pto.Scene(sd), params)
-    assert np.isfinite(img).all(), ctx
-    bad = np.argwhere((img != ref).any(axis=2))
-    assert len(bad) == 0, (ctx, len(bad), bad[:4].tolist(), img[tuple(bad[0])].tolist() if len(bad) else None,
-                           ref[tuple(bad[0])].tolist() if len(bad) else None)
-    assert st.rays == cst.ext_rays + cst.shadow_rays, (ctx, st.rays, cst.ext_rays, cst.shadow_rays)
-    assert st.paths == cst.paths, ctx
-    return st, cst
 
 
 @pytest.mark.parametrize("name", ["cornell", "glass", "lights", "grazing"])

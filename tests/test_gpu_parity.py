@@ -8,41 +8,14 @@ import os
 import numpy as np
 import pytest
 
-from test_oracle_reference_kat import check_against_kat
+from frame_checks import RMSE_TOL, assert_parity, rmse, run_both
+from numpy_radiance import numpy_radiance
+from reference_kat import check_against_kat
+from trace_support import LAYOUTS
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 pytestmark = pytest.mark.gpu
-RMSE_TOL = 1e-4  # BASELINE.json north_star: "images within 1e-4 RMSE of the CPU reference"
-
-
-def rmse(a, b):
-    return float(np.sqrt(np.mean((a[..., :3].astype(np.float64) - b[..., :3].astype(np.float64)) ** 2)))
-
-
-def run_both(P, pto, r, sd, params, width=4, count=False):
-    r.SetScene(sd, width)
-    r.Params = params
-    if count:
-        r.Params.flags |= P.native.PT_FLAG_COUNT_VISITS
-    st = r.Render(0.0)
-    img = r.ReadFramebuffer()
-    info = r.BvhInfo()
-    osc = pto.Scene(sd, (info.width,) + r.BvhRead())
-    assert osc.validate_bvh()[0] == 0
-    ref, ost = pto.render(osc, params)
-    return img, st, ref, ost
-
-
-def assert_parity(img, st, ref, ost, exact=True):
-    assert st.rays == ost.rays, (st.rays, ost.rays)
-    assert st.paths == ost.paths
-    e = rmse(img, ref)
-    nbad = int((img != ref).any(axis=-1).sum())
-    assert e <= RMSE_TOL, (e, nbad)
-    assert np.array_equal(img[..., 3], ref[..., 3])
-    if exact:
-        assert nbad == 0, f"{nbad} pixels differ, rmse {e}"
 
 
 def test_reference_sphere_full_frame(P, pto, renderer):
@@ -66,7 +39,7 @@ def test_reference_sphere_ragged_sizes(P, pto, renderer, w, h):
     assert np.array_equal(renderer.ReadFramebuffer(), of) and np.array_equal(renderer.ReadFramebufferRGBA8(), ob)
 
 
-@pytest.mark.parametrize("width", [2, 4, 68, 72, 73])
+@pytest.mark.parametrize("width", LAYOUTS)
 def test_c1_cornell(P, pto, renderer, width):
     """BASELINE config C1: Cornell box, 4 Lambert spheres + area light, 256x256, 4 spp."""
     sd = P.make_scene(P.native.PT_SCENE_CORNELL, 0, 0x5EED0001, 256, 256)
@@ -75,14 +48,14 @@ def test_c1_cornell(P, pto, renderer, width):
     assert (st.node_visits, st.tri_tests, st.sphere_tests) == (ost.node_visits, ost.tri_tests, ost.sphere_tests)
 
 
-@pytest.mark.parametrize("width", [2, 4, 68, 72, 73])
+@pytest.mark.parametrize("width", LAYOUTS)
 def test_c4_glass_metal_depth16(P, pto, renderer, width):
     sd = P.make_scene(P.native.PT_SCENE_CORNELL_GLASS, 0, 0x5EED0001, 200, 150)
     img, st, ref, ost = run_both(P, pto, renderer, sd, P.make_params(200, 150, spp=8, max_depth=16), width)
     assert_parity(img, st, ref, ost)
 
 
-@pytest.mark.parametrize("width", [2, 4, 68, 72, 73])
+@pytest.mark.parametrize("width", LAYOUTS)
 def test_c3_triangle_soup(P, pto, renderer, width):
     sd = P.make_scene(P.native.PT_SCENE_TRIANGLE_SOUP, 50000, 0x5EED0001, 160, 120)
     img, st, ref, ost = run_both(P, pto, renderer, sd, P.make_params(160, 120, spp=4, max_depth=8), width, count=True)
@@ -106,7 +79,7 @@ def test_pool_extend_kernel_is_identical(P, pto, renderer):
     """PT_FLAG_EXTEND_POOL (a wavefront owns 128 queue entries, refills idle lanes while it traverses, shades the pool at full
     width) must not change a single bit nor a single visit count — on every node layout, with holes, streams and deep paths."""
     N = P.native
-    for width in (2, 4, 68, 72, 73):
+    for width in LAYOUTS:
         sd = P.make_scene(N.PT_SCENE_TRIANGLE_SOUP, 30000, 3, 200, 150)
         p = P.make_params(200, 150, spp=5, max_depth=8, streams=3, flags=N.PT_FLAG_EXTEND_POOL)
         img, st, ref, ost = run_both(P, pto, renderer, sd, p, width, count=True)
@@ -288,7 +261,7 @@ def test_4k_frame_and_full_hd_soup(P, pto, renderer):
     assert_parity(img, st, ref, ost)
 
 
-@pytest.mark.parametrize("layout", [2, 4, 68, 72, 73])
+@pytest.mark.parametrize("layout", LAYOUTS)
 def test_gpu_lbvh_builder(P, pto, renderer, layout):
     """hierarchy built on the GPU (Morton sort + Karras + refit). The blob must pass the oracle's structural
     validator, the HIP frame must equal the oracle traversing THOSE bytes (rays and visit counts included), and — because the
@@ -526,7 +499,7 @@ def test_edge_cases(P, pto, renderer):
     sd = P.SceneData(cam=cam)
     sd.verts = np.array([[-1, -1, 0, 1, -1, 0, 0, 1, 0]], np.float32); sd.tri_mat = np.zeros(1, np.uint32)
     m = np.zeros(1, P.MATERIAL_DTYPE); m["albedo"] = 0.5; m["emission"] = (1, 2, 3); sd.mats = m
-    for width in (2, 4, 68, 72, 73):
+    for width in LAYOUTS:
         img, st, ref, ost = run_both(P, pto, renderer, sd, P.make_params(70, 40, spp=1, max_depth=1), width)
         assert_parity(img, st, ref, ost)
         assert st.rays == 70 * 40 and img[..., 0].max() == 1.0
@@ -799,7 +772,6 @@ def test_hip_frames_match_the_independent_estimator(P, renderer, kind, depth, sp
     """The physics pin of tests/test_physics_pin.py applied to the HIP path itself, without the oracle in between: converged 4 x 4
     frames of the Cornell box and of C4's glass + rough-metal scene FROM THE DEVICE against the float64 numpy tracer that shares no
     sampling routine, RNG, weight formula or intersection code with it — every channel within the same bands (3 sigma, chi-square)."""
-    from test_physics_pin import numpy_radiance
     w = h = 4
     sd = P.make_scene(kind, 0, 0x5EED0001, w, h)
     renderer.SetScene(sd, 0)

@@ -18,7 +18,7 @@ import pytest
 
 import material_zoo as mz
 import nee_checker as nc
-from test_gpu_nee import check as check_nee
+from frame_checks import check_nee
 
 pytestmark = pytest.mark.gpu
 

@@ -16,12 +16,12 @@ import numpy as np
 import pytest
 
 import material_zoo as mz
-from test_gpu_trace import MISS, check_closest, commit, ids_of, oracle, records, same
+from trace_support import MISS, check_closest, commit, ids_of, oracle, records, same
 
 pytestmark = pytest.mark.gpu
 
 COUNTS = [0, 1, 3, 4, 5, 8, 9]
-LAYOUTS = [2, 68, 73]
+SPHERE_PASS_LAYOUTS = [2, 68, 73]
 W, H = 64, 48
 CASES = [(n, t) for n in COUNTS for t in (True, False) if n or t]  # lists with and without triangles around them (not the empty scene)
 CASE_IDS = [f"{n}-{'tris' if t else 'no_tris'}" for n, t in CASES]
@@ -124,7 +124,7 @@ def test_trace_rays(P, pto, renderer, ray_set, n, with_tris):
     o, d = ray_set
     rec = records(o, d)
     want = None
-    for layout in LAYOUTS if with_tris else LAYOUTS[:1]:
+    for layout in SPHERE_PASS_LAYOUTS if with_tris else SPHERE_PASS_LAYOUTS[:1]:
         osc = commit(P, pto, renderer, sd, layout)
         ctx = (n, with_tris, layout)
         ids, ts, ost = oracle(pto, osc, o, d)

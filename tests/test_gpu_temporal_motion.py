@@ -21,12 +21,6 @@ pytestmark = pytest.mark.gpu
 SHAPES = [(1, 1), (7, 5), (65, 3), (64, 48), (257, 63)]
 
 
-@pytest.fixture(scope="session", autouse=True)
-def _checkers():
-    dc.build()
-    mr.build()
-
-
 def same_bits(a, b):
     return np.array_equal(np.ascontiguousarray(a, np.float32).view(np.uint32), np.ascontiguousarray(b, np.float32).view(np.uint32))
 

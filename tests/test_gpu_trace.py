@@ -10,96 +10,10 @@ import pytest
 
 import adversarial_scenes as S
 import ray_caster64 as rc
-from test_geometry_float64 import CRACK_RAYS, PINNED_CRACKS, crack_rays
+from float64_support import CRACK_RAYS, PINNED_CRACKS, crack_rays
+from trace_support import H, LAYOUTS, MISS, W, check_closest, commit, ids_of, oracle, ray_sets, records, same, scenes
 
 pytestmark = pytest.mark.gpu
-
-LAYOUTS = [2, 4, 68, 72, 73]
-MISS = 0xFFFFFFFF
-W, H = 48, 36
-
-
-def _scenes(P):
-    N = P.native
-    return {
-        "cornell": P.make_scene(N.PT_SCENE_CORNELL, 0, 3, W, H),
-        "glass": P.make_scene(N.PT_SCENE_CORNELL_GLASS, 0, 3, W, H),
-        "tess": P.make_scene(N.PT_SCENE_CORNELL_TESS, 3000, 3, W, H),
-        "soup": P.make_scene(N.PT_SCENE_TRIANGLE_SOUP, 4000, 3, W, H),
-        "layers": S.stacked_layers(W, H),
-        "duplicates": S.duplicates(W, H)[0],
-        "spheres64": S.sphere_list(64, W, H),
-    }
-
-
-def _unit(v):
-    v = np.asarray(v, np.float64)
-    return (v / np.linalg.norm(v, axis=1, keepdims=True)).astype(np.float32)
-
-
-def ray_sets(pto, sd, n=600, seed=11):
-    """(name, origins, directions): camera rays, rays with exactly-zero direction components, incoherent unit rays from inside the
-    scene's bounds, and rays that start on surfaces."""
-    rng = np.random.default_rng(seed)
-    o, d = rc.camera_rays(pto, sd.cam, W, H)
-    pts = np.concatenate([np.asarray(sd.verts, np.float32).reshape(-1, 3), np.asarray(sd.spheres, np.float32).reshape(-1, 4)[:, :3]])
-    lo, hi = pts.min(0), pts.max(0)
-    inside = (lo + rng.random((n, 3)) * (hi - lo)).astype(np.float32)
-    axes = np.array([[1, 0, 0], [-1, 0, 0], [0, 1, 0], [0, -1, 0], [0, 0, 1], [0, 0, -1], [0, 0.6, -0.8], [0.8, 0, 0.6], [-0.6, -0.8, 0]], np.float32)
-    zero_d = axes[rng.integers(0, len(axes), n)]
-    out = [("camera", o, d), ("zero_components", inside, zero_d), ("incoherent", inside[::-1].copy(), _unit(rng.normal(size=(n, 3))))]
-    if len(sd.verts):
-        v = np.asarray(sd.verts, np.float32).reshape(-1, 3, 3)
-        k = rng.integers(0, len(v), n)
-        a, b = rng.random(n), rng.random(n)
-        flip = a + b > 1
-        a[flip], b[flip] = 1 - a[flip], 1 - b[flip]
-        on = (v[k, 0] + a[:, None] * (v[k, 1] - v[k, 0]) + b[:, None] * (v[k, 2] - v[k, 0])).astype(np.float32)
-        out.append(("on_surface", on, _unit(rng.normal(size=(n, 3)))))
-    return out
-
-
-def records(o, d, tmax=np.inf):
-    r = np.zeros((len(o), 8), np.float32)
-    r[:, 0:3], r[:, 3], r[:, 4:7] = o, tmax, d
-    return r
-
-
-def oracle(pto, osc, o, d):
-    """(ids uint64, t float32, summed pto_stats) of pto_closest over the rays."""
-    st = pto.pto_stats()
-    t = C.c_float()
-    ids, ts = np.empty(len(o), np.uint64), np.empty(len(o), np.float32)
-    fo, fd = C.c_float * 3, C.c_float * 3
-    for i in range(len(o)):
-        ids[i] = pto.lib.pto_closest(C.byref(osc.c), fo(*o[i].tolist()), fd(*d[i].tolist()), C.byref(t), C.byref(st))
-        ts[i] = t.value
-    return ids, ts, st
-
-
-def same(a, b):
-    """Hit records equal bit for bit (a miss's id bits are a NaN as a float)."""
-    return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
-
-
-def ids_of(hits):
-    return np.ascontiguousarray(hits[:, 1]).view(np.uint32).astype(np.uint64)
-
-
-def commit(P, pto, r, sd, width):
-    r.SetScene(sd, width)
-    info = r.BvhInfo()
-    osc = pto.Scene(sd, (info.width,) + r.BvhRead())
-    assert osc.validate_bvh()[0] == 0
-    return osc
-
-
-def check_closest(hits, ids, ts, ctx):
-    got = ids_of(hits)
-    assert np.array_equal(got, ids), (ctx, np.nonzero(got != ids)[0][:8])
-    hit = ids != MISS
-    assert np.array_equal(hits[hit, 0].view(np.uint32), ts[hit].view(np.uint32)), ctx
-    assert (hits[~hit, 0] == np.inf).all() and (hits[~hit, 2:] == 0).all(), ctx
 
 
 @pytest.mark.parametrize("name", ["cornell", "glass", "tess", "soup", "layers", "duplicates", "spheres64"])
@@ -107,7 +21,7 @@ def test_trace_matches_the_oracle(P, pto, renderer, name):
     """Every layout and builder, four ray sets: closest hits bit for bit, the visit counters (tmax = inf), the tmax rule at
     t_oracle, just below it and at random finite values, and occlusion."""
     N = P.native
-    sd = _scenes(P)[name]
+    sd = scenes(P)[name]
     rng = np.random.default_rng(5)
     for width in LAYOUTS:
         for build in (0, N.PT_BVH_BUILD_LBVH):
@@ -146,7 +60,7 @@ def test_trace_matches_the_oracle(P, pto, renderer, name):
 
 def test_tmax_degenerate_values_miss(P, pto, renderer):
     """tmax <= 0 and NaN give misses, in both query kinds."""
-    sd = _scenes(P)["glass"]
+    sd = scenes(P)["glass"]
     commit(P, pto, renderer, sd, 0)
     o, d = rc.camera_rays(pto, sd.cam, W, H)
     for tm in (0.0, -0.0, -1.0, np.nan):
@@ -159,7 +73,7 @@ def test_tmax_degenerate_values_miss(P, pto, renderer):
 def test_barycentrics(P, pto, renderer, name):
     """Triangle hits: u, v >= 0, u + v <= 1, o + t d = v0 + u e1 + v e2 to float32 tolerance, and u, v equal the float64 caster's
     away from edges; sphere hits report 0, 0."""
-    sd = _scenes(P)[name]
+    sd = scenes(P)[name]
     o, d = rc.camera_rays(pto, sd.cam, W, H)
     want, t64, edge, in_plane = rc.cast(sd.verts, sd.spheres, o, d)
     v = np.asarray(sd.verts, np.float64).reshape(-1, 3, 3)
@@ -202,7 +116,7 @@ def test_shared_edge_rays_in_one_call(P, pto, renderer):
 
 def test_same_ids_as_the_render_path(P, pto, renderer):
     """Camera rays of an id scene: the query's prim ids equal the id image that pt_render makes of the same scene."""
-    for sd in (_scenes(P)["glass"], _scenes(P)["tess"]):
+    for sd in (scenes(P)["glass"], scenes(P)["tess"]):
         ids = S.id_scene(sd)
         o, d = rc.camera_rays(pto, ids.cam, W, H)
         for width in LAYOUTS:
@@ -218,7 +132,7 @@ def test_sizes_and_memory_kinds(P, pto, renderer):
     """n = 1, 63, 65 and a 4M-ray batch (past the 2^20-lane grid: lanes reuse their overflow columns, on a scene whose every ray
     spills out of LDS); torch device tensors and numpy host arrays give identical hits."""
     import torch
-    sd = _scenes(P)["layers"]
+    sd = scenes(P)["layers"]
     osc = commit(P, pto, renderer, sd, 68)
     assert renderer.BvhInfo().stack_need > 12
     o, d = rc.camera_rays(pto, sd.cam, W, H)
@@ -246,7 +160,7 @@ def test_refused_calls(P, pto, renderer):
     status; n_rays == 0 is a no-op."""
     import torch
     N = P.native
-    sd = _scenes(P)["cornell"]
+    sd = scenes(P)["cornell"]
     commit(P, pto, renderer, sd, 0)
     o, d = rc.camera_rays(pto, sd.cam, W, H)
     rays = torch.from_numpy(records(o, d)).cuda()
@@ -278,7 +192,7 @@ def test_queries_between_progressive_frames(P, pto, renderer):
     """A progressive sequence (PT_FLAG_ACCUMULATE, 8 streams, offsets 0, 4, 8) and a restart at 0 with queries between every two
     frames: every frame equals the same sequence without queries, and the oracle's."""
     N = P.native
-    sd = _scenes(P)["glass"]
+    sd = scenes(P)["glass"]
     osc = commit(P, pto, renderer, sd, 0)
     o, d = rc.camera_rays(pto, sd.cam, W, H)
     big = np.tile(records(o, d), (64, 1))

@@ -6,66 +6,16 @@ the oracle does, and give the frame of a fresh commit of the moved geometry. Als
 input agree, spheres move, topology and sah_cost behave, long animations and a re-commit work, a refused device update changes
 nothing, progressive rendering is undisturbed, and a 1M-triangle tree refits."""
 import ctypes as C
-import dataclasses
 
 import numpy as np
 import pytest
 
-import ray_caster64 as rc
 from lbvh_ref import numpy_sah
-from test_gpu_trace import H, LAYOUTS, MISS, W, _scenes, ids_of, oracle, records
+from blob_scenes import SCENES, blob, deform, moved
+from frame_checks import check_against_oracle
+from trace_support import H, LAYOUTS, W, scenes
 
 pytestmark = pytest.mark.gpu
-
-SCENES = ["cornell", "glass", "tess", "soup", "layers", "duplicates", "spheres64"]
-
-
-def moved(sd, verts=None, spheres=None):
-    return dataclasses.replace(sd, verts=sd.verts if verts is None else np.asarray(verts, np.float32).reshape(-1, 9),
-                               spheres=sd.spheres if spheres is None else np.asarray(spheres, np.float32).reshape(-1, 4))
-
-
-def deform(sd, rng, kind):
-    """'small': every vertex jittered by 1e-3 of the scene's extent; 'large': every triangle carried up to 40 % of the extent across
-    the scene (plus jitter), so that leaves overlap and boxes grow."""
-    v = np.asarray(sd.verts, np.float32).reshape(-1, 3, 3)
-    if len(v) == 0:
-        return np.zeros((0, 9), np.float32)
-    ext = float(np.ptp(v.reshape(-1, 3), axis=0).max())
-    out = v.astype(np.float64) + rng.normal(scale=1e-3 * ext, size=v.shape)
-    if kind == "large":
-        out += rng.uniform(-0.4 * ext, 0.4 * ext, size=(len(v), 1, 3))
-    return out.astype(np.float32).reshape(-1, 9)
-
-
-def blob(r):
-    info = r.BvhInfo()
-    nodes, tris = r.BvhRead()
-    return info, nodes.copy(), tris.copy()
-
-
-def check_against_oracle(P, pto, r, sd, ctx, params=None):
-    """The renderer's current blob validates against sd's vertices, renders the oracle's frame bit for bit (rays and paths too), and
-    its closest-hit queries with visit counters equal pto_closest's."""
-    info, nodes, tris = blob(r)
-    osc = pto.Scene(sd, (info.width, nodes, tris))
-    assert osc.validate_bvh()[0] == 0, ctx
-    params = params or P.make_params(W, H, spp=2, max_depth=8, streams=2)
-    r.Params = params
-    st = r.Render(0.0)
-    ref, ost = pto.render(osc, params)
-    assert np.array_equal(r.ReadFramebuffer(), ref), ctx
-    assert (st.rays, st.paths) == (ost.rays, ost.paths), ctx
-    o, d = rc.camera_rays(pto, sd.cam, W, H)
-    sel = slice(None, None, 3)
-    o, d = o[sel], d[sel]
-    ids, ts, ost = oracle(pto, osc, o, d)
-    hits, qst = r.TraceRays(records(o, d), count_visits=True)
-    assert np.array_equal(ids_of(hits), ids), ctx
-    hit = ids != MISS
-    assert np.array_equal(hits[hit, 0].view(np.uint32), ts[hit].view(np.uint32)), ctx
-    assert (qst.node_visits, qst.tri_tests, qst.sphere_tests) == (ost.node_visits, ost.tri_tests, ost.sphere_tests), ctx
-    return osc
 
 
 @pytest.mark.parametrize("name", SCENES)
@@ -73,7 +23,7 @@ def test_refit_is_exact(P, pto, renderer, name):
     """Small jitter, then large motion, on every layout and builder: the refitted blob validates against the new vertices and the
     device equals the oracle on it (frames, rays, paths, closest hits, visit counters)."""
     N = P.native
-    sd = _scenes(P)[name]
+    sd = scenes(P)[name]
     for width in LAYOUTS:
         for build in (0, N.PT_BVH_BUILD_LBVH):
             rng = np.random.default_rng(width + build)
@@ -90,7 +40,7 @@ def test_refit_is_exact(P, pto, renderer, name):
 def test_same_picture_as_a_rebuild(P, pto, renderer, name):
     """The frame after an update equals the frame from a fresh SetScene of the deformed geometry, bit for bit."""
     N = P.native
-    sd = _scenes(P)[name]
+    sd = scenes(P)[name]
     params = P.make_params(W, H, spp=4, max_depth=8, streams=4)
     for width in LAYOUTS:
         for build in (0, N.PT_BVH_BUILD_LBVH):
@@ -110,7 +60,7 @@ def test_noop_update_changes_nothing(P, pto, renderer, name):
     """Every builder puts exact unions of the padded triangle boxes in its blob, and the refit computes the same unions with the same
     quantiser: updating with the unchanged vertices leaves every byte as the commit made it, and sah_cost within 1e-5."""
     N = P.native
-    sd = _scenes(P)[name]
+    sd = scenes(P)[name]
     for width in LAYOUTS:
         for build in (0, N.PT_BVH_BUILD_LBVH):
             renderer.SetScene(sd, width | build)
@@ -127,7 +77,7 @@ def test_device_input_equals_host_input(P, pto, renderer):
     """A float32 torch tensor on the device and a numpy array give identical blob bytes and sah_cost."""
     import torch
     N = P.native
-    sd = _scenes(P)["tess"]
+    sd = scenes(P)["tess"]
     v2 = deform(sd, np.random.default_rng(3), "large")
     for width in (2, 68, 73):
         for build in (0, N.PT_BVH_BUILD_LBVH):
@@ -144,7 +94,7 @@ def test_device_input_equals_host_input(P, pto, renderer):
 
 def test_spheres_move(P, pto, renderer):
     """Moved and resized spheres (triangles unchanged, then both at once) give the oracle's frame."""
-    sd = _scenes(P)["spheres64"]
+    sd = scenes(P)["spheres64"]
     rng = np.random.default_rng(5)
     for width in (2, 68):
         renderer.SetScene(sd, width)
@@ -168,7 +118,7 @@ def test_topology_stable_and_sah(P, pto, renderer):
     tests/test_gpu_blob_ref.py test_refit_blob_is_the_expected_blob's.)"""
     N = P.native
     for name in ("tess", "soup", "layers"):
-        sd = _scenes(P)[name]
+        sd = scenes(P)[name]
         for width in LAYOUTS:
             for build in (0, N.PT_BVH_BUILD_LBVH):
                 renderer.SetScene(sd, width | build)
@@ -189,7 +139,7 @@ def test_long_animation_and_recommit(P, pto, renderer):
     """Ten consecutive updates (a wave through the mesh) all validate and match the oracle; a pt_scene_commit after them builds from
     the updated geometry."""
     N = P.native
-    sd = _scenes(P)["tess"]
+    sd = scenes(P)["tess"]
     v = np.asarray(sd.verts, np.float32).reshape(-1, 3, 3)
     ext = float(np.ptp(v.reshape(-1, 3), axis=0).max())
     for width, build in ((68, N.PT_BVH_BUILD_LBVH), (73, 0), (4, 0)):
@@ -217,7 +167,7 @@ def test_reads_between_updates_then_recommit_elsewhere(P, pto, renderer):
     import torch
     N = P.native
     L = N.PT_BVH_BUILD_LBVH
-    sd = _scenes(P)["tess"]
+    sd = scenes(P)["tess"]
     rng = np.random.default_rng(11)
     v1 = deform(sd, rng, "large")
     v2 = deform(moved(sd, v1), rng, "large")
@@ -247,7 +197,7 @@ def test_refused_device_update_changes_nothing(P, pto, renderer):
     device pointer that is not 4-byte aligned, host memory passed as device memory, and a wrong count."""
     import torch
     N = P.native
-    sd = _scenes(P)["glass"]
+    sd = scenes(P)["glass"]
     for width in (2, 68):
         renderer.SetScene(sd, width)
         renderer.UpdateGeometry(verts=deform(sd, np.random.default_rng(2), "small"))
@@ -279,7 +229,7 @@ def test_progressive_frames_then_update(P, pto, renderer):
     """Progressive frames (PT_FLAG_ACCUMULATE), an update, then a non-accumulate frame with spp >= streams: the oracle's frame of the
     new geometry. The update keeps the scene's extend-kernel choice and the context's frame-start template; neither may show."""
     N = P.native
-    sd = _scenes(P)["glass"]
+    sd = scenes(P)["glass"]
     renderer.SetScene(sd, 0)
     for offset, flags in ((0, 0), (4, N.PT_FLAG_ACCUMULATE), (8, N.PT_FLAG_ACCUMULATE)):
         renderer.Params = P.make_params(W, H, spp=4, max_depth=8, streams=4, sample_offset=offset, flags=flags)

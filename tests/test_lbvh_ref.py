@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import lbvh_ref as L
+from trace_support import LAYOUTS
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 _spec = importlib.util.spec_from_file_location("make_blob_digests", os.path.join(GOLDEN, "make_blob_digests.py"))
@@ -20,7 +21,6 @@ M = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(M)
 
 SCENES = ("cornell", "tess_2k", "soup_5k", "duplicates", "stacked_layers")
-LAYOUTS = (2, 4, 68, 72, 73)
 F = np.float32
 
 

@@ -9,6 +9,7 @@ import pytest
 import bsdf64 as b64
 import census_checker as cc
 import material_zoo as mz
+from material_zoo import NEE_CONFIGS, emissive_triangles
 
 F3 = C.c_float * 3
 # The error of W is taken relative to its largest component, but to no less than W_FLOOR: the Schlick weight of a black metal near
@@ -90,16 +91,6 @@ def test_every_class_is_reached(census):
     missing = [(cfg, c) for cfg in mz.CONFIGS for c in mz.CLAIMS[cfg] if census[cfg + ("parity",)][0][c] < 1]
     assert missing == []
     assert set(mz.CLAIMS) == set(mz.CONFIGS) and all(len(v) >= 3 for v in mz.CLAIMS.values())
-
-
-NEE_CONFIGS = [("palette", "front"), ("glass_box", "outside"), ("glass_box", "inside")]
-
-
-def emissive_triangles(sd):
-    """Mask of the triangles SPEC §7 takes as lights: some emission and a positive area, whatever the material's kind."""
-    e1, e2 = sd.verts[:, 3:6] - sd.verts[:, 0:3], sd.verts[:, 6:9] - sd.verts[:, 0:3]
-    area = 0.5 * np.linalg.norm(np.cross(e1.astype(np.float64), e2.astype(np.float64)), axis=1)
-    return sd.mats["emission"][sd.tri_mat].any(axis=1) & (area > 0)
 
 
 @pytest.mark.parametrize("cfg", NEE_CONFIGS, ids="-".join)

@@ -17,11 +17,6 @@ SPP = 2048   # samples per pixel of the statistical tests
 Z = 4.0      # the statistical tests' bound, in standard deviations
 
 
-@pytest.fixture(scope="session", autouse=True)
-def _checker():
-    nc.build()
-
-
 def moments(P, pto, sd, flags, spp=SPP):
     """(per-pixel mean, per-pixel sample variance of one sample's radiance, stats) of the checker at S x S."""
     params = P.make_params(S, S, spp=spp, max_depth=8, streams=1, seed=11)

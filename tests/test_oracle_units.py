@@ -8,6 +8,8 @@ import os
 import numpy as np
 import pytest
 
+from trace_support import LAYOUTS
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 F3 = C.c_float * 3
 
@@ -119,7 +121,7 @@ def test_oracle_bvh_equals_brute_force(P, pto):
 
 
 @pytest.mark.parametrize("kind,detail", [(0, 0), (1, 0), (2, 5000), (3, 4000)])
-@pytest.mark.parametrize("width", [2, 4, 68, 72, 73])
+@pytest.mark.parametrize("width", LAYOUTS)
 def test_product_bvh_blob_validates_and_matches_brute_force(P, pto, kind, detail, width):
     """The product's host-side builder (detached scene, no device) against the oracle's structural validator, and the
     oracle traversing those bytes against brute force."""
@@ -216,7 +218,7 @@ def test_quantised_slab_test_is_conservative_on_grazing_rays(P, pto):
         if n > 1e-6:
             rays.append((o, (d / n).astype(np.float32)))
     brute = pto.Scene(sd)
-    for width in (2, 4, 68, 72, 73):
+    for width in LAYOUTS:
         info, nodes, tris = build_bvh_detached(sd, width)
         s = pto.Scene(sd, (width, nodes, tris))
         for o, d in rays:

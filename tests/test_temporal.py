@@ -14,12 +14,6 @@ import temporal_cases as tc
 import temporal_checker as tr
 
 
-@pytest.fixture(scope="session", autouse=True)
-def _checkers():
-    dc.build()
-    tr.build()
-
-
 def hit_guides(h, w, t=2.0):
     """Every pixel a hit of primitive 0 at depth t along its ray, the normal facing the axis camera."""
     g = np.zeros((h, w, 8), np.float32)

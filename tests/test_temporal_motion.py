@@ -17,13 +17,6 @@ import temporal_cases as tc
 import temporal_checker as tr
 
 
-@pytest.fixture(scope="session", autouse=True)
-def _checkers():
-    dc.build()
-    tr.build()
-    mr.build()
-
-
 def same_bits(a, b):
     return np.array_equal(np.ascontiguousarray(a, np.float32).view(np.uint32), np.ascontiguousarray(b, np.float32).view(np.uint32))
 

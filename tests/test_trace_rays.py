@@ -7,9 +7,8 @@ import numpy as np
 
 import adversarial_scenes as S
 import ray_caster64 as rc
-from test_geometry_float64 import build_bvh_detached
-
-MISS = 0xFFFFFFFF
+from float64_support import build_bvh_detached
+from trace_support import MISS
 
 
 def test_trace_rays_is_exported_with_the_documented_argtypes(P):
