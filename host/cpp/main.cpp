@@ -2,8 +2,9 @@
 // build a renderer, render N frames, write the image the reference would have shown in its window.
 //   ptrt_cli [--scene reference|cornell|glass|soup|tess] [--detail N] [--size WxH] [--spp N] [--depth N]
 //            [--frames N] [--ppm out.ppm] [--pfm out.pfm] [--gpus N] [--virtual 0|1|2] [--nee] [--denoise N]
-//            [--display clamp|reinhard|aces] [--auto-exposure]
+//            [--display clamp|reinhard|aces] [--auto-exposure] [--env FILE.pfm]
 // --nee: next-event estimation (PT_FLAG_NEXT_EVENT, docs/SPEC.md §7).
+// --env FILE.pfm: a square colour PFM read as the scene's octahedral environment map (docs/SPEC.md §11; rows in file order).
 // --denoise N: denoise the last frame with N filter passes (0 = the default; docs/SPEC.md §8) and write the denoised image to --ppm /
 // --pfm instead of the frame (the PPM by SPEC §1's unorm8 rule).
 // --display CURVE: run the display stage (docs/SPEC.md §10: exposure, tone curve, sRGB8 encode on the device) over the last stage that
@@ -18,10 +19,31 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <stdexcept>
+#include <utility>
+
+// A square colour PFM ("PF", either byte order by the sign of its scale) as n x n x 3 floats, rows in file order
+static std::vector<float> read_square_pfm(const std::string &path, uint32_t &n)
+{
+    FILE *f = std::fopen(path.c_str(), "rb");
+    if (!f) throw std::runtime_error("cannot open " + path);
+    char magic[3] = { 0, 0, 0 }; unsigned w = 0, h = 0; float scale = 0.f;
+    const bool head = std::fscanf(f, "%2s %u %u %f", magic, &w, &h, &scale) == 4 && std::fgetc(f) != EOF;
+    if (!head || std::strcmp(magic, "PF") != 0 || w != h || w == 0 || w > 2048) { std::fclose(f); throw std::runtime_error(path + ": not a square colour PFM of at most 2048 x 2048"); }
+    std::vector<float> px((size_t)w * h * 3);
+    const bool whole = std::fread(px.data(), sizeof(float), px.size(), f) == px.size();
+    std::fclose(f);
+    if (!whole) throw std::runtime_error(path + ": truncated");
+    const uint16_t one = 1; const bool host_little = *(const uint8_t *)&one == 1;
+    if ((scale < 0.f) != host_little)
+        for (float &v : px) { uint8_t b[4]; std::memcpy(b, &v, 4); std::swap(b[0], b[3]); std::swap(b[1], b[2]); std::memcpy(&v, b, 4); }
+    n = w;
+    return px;
+}
 
 int main(int argc, char **argv)
 {
-    std::string scene = "reference", ppm = "frame.ppm", pfm;
+    std::string scene = "reference", ppm = "frame.ppm", pfm, env;
     uint32_t w = 1920, h = 1080, detail = 0, spp = 64, depth = 8, frames = 1, gpus = 1, virt = 0, flags = 0;
     int denoise = -1; // filter passes of --denoise (0 = default); -1 = no denoise
     int curve = -1;   // PT_TONE_* of --display; -1 = no display stage
@@ -41,6 +63,7 @@ int main(int argc, char **argv)
         else if (a == "--virtual") virt = (uint32_t)std::atoi(argv[i + 1]);
         else if (a == "--ppm") ppm = argv[i + 1];
         else if (a == "--pfm") pfm = argv[i + 1];
+        else if (a == "--env") env = argv[i + 1];
         else if (a == "--denoise") denoise = std::atoi(argv[i + 1]);
         else if (a == "--display") {
             const std::string v = argv[i + 1];
@@ -59,6 +82,7 @@ int main(int argc, char **argv)
             multi.reset(new ptrt_host::MultiRenderer(gpus, w, h, (int)virt));
             multi->Init();
             multi->LoadSyntheticScene(kind, detail);
+            if (!env.empty()) { uint32_t n = 0; const auto map = read_square_pfm(env, n); multi->set_environment(map, n); }
             multi->Params.spp = spp; multi->Params.max_depth = depth; multi->Params.flags |= flags;
             for (uint32_t f = 0; f < frames; ++f) multi->Render(0.f);
             unsigned long long rays = 0; double ms = 0;
@@ -69,6 +93,7 @@ int main(int argc, char **argv)
             single->Init();
             if (scene != "reference") {
                 single->LoadSyntheticScene(kind, detail);
+                if (!env.empty()) { uint32_t n = 0; const auto map = read_square_pfm(env, n); single->set_environment(map, n); }
                 single->Params.spp = spp; single->Params.max_depth = depth; single->Params.flags |= flags;
             }
             for (uint32_t f = 0; f < frames; ++f) single->Render(0.f);

@@ -84,6 +84,12 @@ public:
         return px;
     }
     void SetCamera(const pt_camera &cam) { check(pt_scene_set_camera(scene_, &cam), ctx_); } // no new commit needed
+    // docs/SPEC.md §11: n x n texels of linear RGB, octahedral layout; an empty vector with n = 0 removes the map. No new commit needed.
+    void set_environment(const std::vector<float> &rgb, uint32_t n)
+    {
+        if (n && rgb.size() < (size_t)n * n * 3) throw Error(PT_ERR_INVALID_ARGUMENT, "set_environment: fewer than n * n * 3 floats");
+        check(pt_scene_set_environment(scene_, n ? rgb.data() : nullptr, n), ctx_);
+    }
     // docs/SPEC.md §9: reproject the previous call's accumulated image to this frame and blend the last frame in; with `filter` the
     // §8.2 filter then runs over the result (ReadDenoised). Zeros mean the defaults; the context keeps the history between calls.
     pt_stats DenoiseTemporal(uint32_t max_history = 0, uint32_t flags = 0, bool filter = true, uint32_t iterations = 0)
@@ -195,6 +201,7 @@ public:
         check(pt_comm_render(comm_, scenes.data(), &Params, LastStats.data()), r_[0]->Context());
         r_[0]->Params = Params;
     }
+    void set_environment(const std::vector<float> &rgb, uint32_t n) { for (auto &r : r_) r->set_environment(rgb, n); }
     Renderer &Root() { return *r_[0]; }
     void Dispose()
     {

@@ -156,6 +156,15 @@ public unsafe class HipRenderer : IDisposable
     // Move the current scene's camera (no new commit needed)
     public void SetCamera(PtCamera cam) { Ptrt.Check(Ptrt.pt_scene_set_camera(_scene, &cam), _ctx); }
 
+    // Give the current scene an environment map (docs/SPEC.md §11): n x n texels of linear RGB in octahedral layout, or null to remove
+    // it. No new commit needed; while set it replaces the sky on every miss, and NextEvent frames sample it as a light.
+    public void SetEnvironment(float[] rgb, uint n)
+    {
+        if (rgb == null) { Ptrt.Check(Ptrt.pt_scene_set_environment(_scene, null, 0), _ctx); return; }
+        if ((ulong)rgb.Length < (ulong)n * n * 3) throw new ArgumentException("SetEnvironment: fewer than n * n * 3 floats");
+        fixed (float* p = rgb) Ptrt.Check(Ptrt.pt_scene_set_environment(_scene, p, n), _ctx);
+    }
+
     // Temporal accumulation (docs/SPEC.md §9), the call of a render-every-frame loop whose camera or geometry moves: reprojects the
     // previous call's accumulated image to this frame, blends the last Render in, and (filter = true) runs Denoise's filter over the
     // result. Zeros mean the defaults. ReadTemporal / ReadHistoryLength / ReadDenoised hold until the next Render; the history itself

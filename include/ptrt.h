@@ -33,8 +33,9 @@ extern "C" {
  * pt_scene_update_triangles / pt_scene_update_spheres and PT_UPDATE_HOST_MEMORY, then PT_FLAG_NEXT_EVENT, then pt_denoise, pt_denoise_params,
  * PT_DENOISE_*, pt_denoised_read / pt_denoised_device_ptr and pt_guides_read, then pt_denoise_temporal, pt_temporal_params, PT_TEMPORAL_*,
  * pt_temporal_read / pt_temporal_device_ptr / pt_temporal_history_read, then pt_display, pt_display_params, pt_display_info, PT_DISPLAY_*,
- * PT_TONE_*, pt_display_read / pt_display_device_ptr / pt_display_info_read / pt_display_histogram_read, then PT_TEMPORAL_MOTION (additions
- * only: no struct or existing signature changed).
+ * PT_TONE_*, pt_display_read / pt_display_device_ptr / pt_display_info_read / pt_display_histogram_read, then PT_TEMPORAL_MOTION, then
+ * pt_scene_set_environment, pt_environment_info and pt_scene_environment_info / pt_scene_environment_read (additions only: no struct or
+ * existing signature changed).
  * Hosts compare pt_abi_version() with the header they were built against. */
 #define PTRT_ABI_VERSION 2
 
@@ -212,6 +213,21 @@ pt_status pt_scene_set_spheres(pt_scene *s, const float *cxyzr, const uint32_t *
 pt_status pt_scene_set_materials(pt_scene *s, const pt_material *mats, uint64_t count);
 pt_status pt_scene_set_camera(pt_scene *s, const pt_camera *cam);
 pt_status pt_scene_set_sky(pt_scene *s, const float rgb[3]);
+/* Environment map (docs/SPEC.md §11): n x n texels, row-major, 3 floats each (linear RGB radiance), octahedral layout. rgb == NULL &&
+ * n == 0 removes it. 1 <= n <= 2048 and every component finite and >= 0, else PT_ERR_INVALID_ARGUMENT (a refused call keeps the previous
+ * environment). While set it replaces `sky` on every miss of a PT_PATH_TRACE frame (`sky` is kept and returns when the environment is
+ * removed), and PT_FLAG_NEXT_EVENT frames sample it as a light with MIS if its total is positive. Works before and after pt_scene_commit —
+ * like pt_scene_set_sky it takes effect for the next pt_render without a new commit (the upload waits on the context's stream), and it
+ * survives commits and geometry updates — and on a detached scene (host table only). A caller that changes it restarts accumulation.
+ * Frames of a scene with an environment run on the one-ray-per-lane kernel (pt_stats.reserved[0] = 1, no kernel probe): with
+ * PT_FLAG_EXTEND_PACKED / _POOL, PT_FLAG_SPLIT_KERNELS / _BUCKET_SPECULAR, PT_FLAG_COUNT_VISITS or pt_tuning.extend_kernel 2 / 3 they are
+ * PT_ERR_UNSUPPORTED. PT_REFERENCE_SPHERE, pt_trace_rays, the guides of pt_denoise / pt_denoise_temporal and pt_display do not see it. */
+pt_status pt_scene_set_environment(pt_scene *s, const float *rgb, uint32_t n);
+typedef struct pt_environment_info { uint32_t n, lit; uint64_t device_bytes; double total; } pt_environment_info;   /* n == 0: none set; lit: 1 if it is a light for NEE */
+pt_status pt_scene_environment_info(const pt_scene *s, pt_environment_info *out);
+/* the sampling table exactly as the kernels read it: n*n float4 (r,g,b,p), n marginal cdf entries, n*n conditional cdf entries;
+ * n_texels = the texels the three arrays have room for (>= n*n) */
+pt_status pt_scene_environment_read(const pt_scene *s, float *texels4, float *mcdf, float *ccdf, uint64_t n_texels);
 /* builds the BVH on the host (binned SAH) and uploads everything; replaces CreateComputePipeline's one-time
  * descriptor/pipeline set-up (Renderer.cs:293-403). bvh_width: PT_BVH_WIDTH_* */
 pt_status pt_scene_commit(pt_scene *s, uint32_t bvh_width);

@@ -117,13 +117,17 @@ class pt_display_info(C.Structure):
                 ("counted", C.c_uint64), ("used", C.c_uint64)]
 
 
+class pt_environment_info(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("lit", C.c_uint32), ("device_bytes", C.c_uint64), ("total", C.c_double)]
+
+
 class pt_scene_counts(C.Structure):
     _fields_ = [("n_tris", C.c_uint64), ("n_spheres", C.c_uint64), ("n_mats", C.c_uint64)]
 
 
 assert C.sizeof(pt_material) == 48 and C.sizeof(pt_camera) == 64 and C.sizeof(pt_render_params) == 64 and C.sizeof(pt_tuning) == 40
 assert C.sizeof(pt_denoise_params) == 32 and C.sizeof(pt_temporal_params) == 32
-assert C.sizeof(pt_display_params) == 40 and C.sizeof(pt_display_info) == 32
+assert C.sizeof(pt_display_params) == 40 and C.sizeof(pt_display_info) == 32 and C.sizeof(pt_environment_info) == 24
 
 _vp, _u32, _u64, _st = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int32
 _P = C.POINTER
@@ -143,6 +147,9 @@ SYMBOLS = {
     "pt_scene_set_materials": (_st, [_vp, _vp, _u64]),
     "pt_scene_set_camera": (_st, [_vp, _P(pt_camera)]),
     "pt_scene_set_sky": (_st, [_vp, _P(C.c_float * 3)]),
+    "pt_scene_set_environment": (_st, [_vp, _vp, _u32]),
+    "pt_scene_environment_info": (_st, [_vp, _P(pt_environment_info)]),
+    "pt_scene_environment_read": (_st, [_vp, _vp, _vp, _vp, _u64]),
     "pt_scene_commit": (_st, [_vp, _u32]),
     "pt_scene_bvh_info": (_st, [_vp, _P(pt_bvh_info)]),
     "pt_scene_bvh_read": (_st, [_vp, _vp, _u64, _vp, _u64]),

@@ -87,6 +87,8 @@ struct Frame {                  // a path-traced frame as plan_frame lays it out
     bool profile, count, split, bucket, full_state, accumulate, mapped, compact;
     bool nee;                   // PT_FLAG_NEXT_EVENT (docs/SPEC.md §7): the one-ray-per-lane kernel with light samples
     NeeArgs nee_args;
+    bool env;                   // the scene has an environment map (docs/SPEC.md §11): the same kernel, in its environment instantiation
+    EnvArgs env_args;
     Accumulation::Key sums_key; // what the sums hold once this frame completes
     size_t q_entries; uint64_t total_spp, allocs_before;
     PathState ps; FrameParams fp;
@@ -144,6 +146,14 @@ static pt_status plan_frame(pt_context *c, const pt_scene *s, const pt_render_pa
     f.bucket = (p->flags & PT_FLAG_BUCKET_SPECULAR) != 0; f.split = f.bucket || (p->flags & PT_FLAG_SPLIT_KERNELS) != 0;
     f.forced = (p->flags & PT_FLAG_EXTEND_POOL) ? (uint32_t)EXT_POOL : (p->flags & PT_FLAG_EXTEND_PACKED) ? (uint32_t)EXT_PACKED
                : (p->flags & PT_FLAG_EXTEND_SIMPLE) ? (uint32_t)EXT_SIMPLE : t.extend_kernel;
+    // an environment map is looked up (and, in NEE frames, sampled) by the fused one-ray-per-lane kernel only, as NEE is: no probe, no counters
+    f.env = s->env.present();
+    if (f.env) {
+        if (f.split || f.count || f.forced == (uint32_t)EXT_PACKED || f.forced == (uint32_t)EXT_POOL)
+            return fail(c, PT_ERR_UNSUPPORTED, "a scene with an environment map renders on the one-ray-per-lane kernel only: not with PT_FLAG_EXTEND_PACKED, "
+                                               "PT_FLAG_EXTEND_POOL, PT_FLAG_SPLIT_KERNELS, PT_FLAG_BUCKET_SPECULAR, PT_FLAG_COUNT_VISITS or pt_tuning.extend_kernel 2 / 3");
+        f.forced = EXT_SIMPLE;
+    }
     // next-event estimation lives in the fused one-ray-per-lane kernel only. Its frames neither probe the extend kernel nor feed the
     // scene's choice (a forced kernel does neither), and they have no visit counters: a shadow ray's traversal stops at its tmax, which
     // §4.1's counters do not describe.
@@ -201,6 +211,8 @@ static pt_status plan_frame(pt_context *c, const pt_scene *s, const pt_render_pa
         HIP_TRY(c, c->nee_ext.ensure(f.n_slots)); HIP_TRY(c, c->nee_rad.ensure(f.n_slots));
         f.nee_args = NeeArgs{ s->d_lights.p, s->d_cdf.p, s->d_pa.p, s->n_lights, c->nee_ext.p, c->nee_rad.p };
     }
+    // §11: a light sample picks one of the two kinds of light with probability 1/2 when the frame has both
+    if (f.env) f.env_args = s->env.args(f.nee && s->env.lit() && s->n_lights ? 0.5f : 1.0f);
     if (f.nranks == 1) HIP_TRY(c, c->out.resize(p->width, p->height));
     PathState &ps = f.ps;
     ps.ray_o = c->ray_o.p; ps.ray_d = c->ray_d.p; ps.thr = c->thr.p; ps.sd = c->sd.p; ps.acc = c->acc.p; ps.q_ext[0] = c->q_ext0.p; ps.q_ext[1] = c->q_ext1.p;
@@ -263,7 +275,7 @@ static pt_status run_loops(pt_context *c, const pt_scene *s, const pt_render_par
     const bool trace = f.profile && getenv("PTRT_TRACE") != nullptr; // developer aid: per-iteration table on stderr
     // One kernel per iteration by default: every extend kernel (one ray per lane, lane-packing, pooled) shades its own hits (mode 0:
     // Lambert-only scene, lean code; 2: all kinds). PT_FLAG_SPLIT_KERNELS / _BUCKET_SPECULAR run k_shade as a second kernel.
-    const int shade_mode = s->has_specular ? 2 : 0;
+    const int shade_mode = (s->has_specular || f.env) ? 2 : 0; // (the environment instantiations shade every kind, whatever the materials)
     for (uint32_t live = n_loops; live > 0;) {
         for (uint32_t g = 0; g < n_loops; ++g) {
             Loop &L = loops[g];
@@ -281,7 +293,8 @@ static pt_status run_loops(pt_context *c, const pt_scene *s, const pt_render_par
             const bool probing = x.probing(g, it); const int kernel = x.launch_kernel(g, it, f.split);
             if (probing) HIP_TRY(c, hipEventRecord(c->ev_probe[(it - 2u) * 2u], L.stream));
             HIP_TRY(c, launch_extend(L.stream, s->ds, pg, f.fp, it, L.bound, f.count, kernel, f.packed_chunk, f.split ? -1 : shade_mode, f.compact,
-                                     c->tuning.bounces ? c->tuning.bounces : x.bounces(g, it, kernel, f.default_bounces), f.nee ? &f.nee_args : nullptr));
+                                     c->tuning.bounces ? c->tuning.bounces : x.bounces(g, it, kernel, f.default_bounces), f.nee ? &f.nee_args : nullptr,
+                                     f.env ? &f.env_args : nullptr));
             if (f.profile) HIP_TRY(c, hipEventRecord(e1, L.stream));
             if (f.bucket) {
                 HIP_TRY(c, launch_shade(L.stream, s->ds, pg, f.fp, it, L.bound, 0, true));

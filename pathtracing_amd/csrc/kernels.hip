@@ -113,6 +113,18 @@ PT_DEV const NeeArgs &cold_nee()
     asm volatile("" : "+s"(p));
     return ((const ExtArgsNee *)p)->nee;
 }
+// The arguments of a frame of a scene with an environment map (docs/SPEC.md §11): the map's table (ptrt_internal.h EnvArgs) behind
+// whatever the frame has otherwise, ExtArgs or ExtArgsNee, read through cold_env<NEE>().
+template <bool NEE> struct ExtArgsEnv : ExtArgsOf<NEE>::type { EnvArgs env; };
+template <bool NEE, bool ENV> struct ExtArgsFor { using type = typename ExtArgsOf<NEE>::type; };
+template <bool NEE> struct ExtArgsFor<NEE, true> { using type = ExtArgsEnv<NEE>; };
+template <bool NEE>
+PT_DEV const EnvArgs &cold_env()
+{
+    auto p = __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return ((const ExtArgsEnv<NEE> *)p)->env;
+}
 
 // Slot order. A slot is one (pixel slot, stream) pair; 64 consecutive slots are one 8x8 pixel block of one stream (a
 // wavefront). The K streams of a block are K consecutive 64-slot groups, so that wavefronts that run at the same time
@@ -434,6 +446,31 @@ PT_DEV uint32_t pick_light(const float *cdf, uint32_t n, float u)
     }
     return lo;
 }
+// ------------------------------------------------------------------------------------------------ environment map (docs/SPEC.md §11)
+// decode: a point (u, v) of the map's square [-1, 1]^2 -> its unit direction (the octahedron, lower half folded outwards)
+PT_DEV V3 env_decode(float u, float v)
+{
+    const float z = (1.0f - __builtin_fabsf(u)) - __builtin_fabsf(v);
+    float x = u, y = v;
+    if (z < 0.0f) { x = (1.0f - __builtin_fabsf(v)) * __builtin_copysignf(1.0f, u); y = (1.0f - __builtin_fabsf(u)) * __builtin_copysignf(1.0f, v); }
+    return normalize(v3(x, y, z));
+}
+// One coordinate of the square -> its texel column / row. The clamp is on the integer, so that whatever arrives (a NaN converts to 0)
+// the index stays inside the table.
+PT_DEV uint32_t env_cell(float u, float nf, uint32_t n)
+{
+    const int i = (int)__builtin_floorf(fma_(u, 0.5f, 0.5f) * nf);
+    return (uint32_t)min(max(i, 0), (int)n - 1);
+}
+// encode: the texel of direction d (row-major index) and s, the 1-norm of d: d omega = s^3 dA on the square
+PT_DEV uint32_t env_texel(const EnvArgs &e, V3 d, float &s)
+{
+    s = (__builtin_fabsf(d.x) + __builtin_fabsf(d.y)) + __builtin_fabsf(d.z);
+    const float is = 1.0f / s, px = d.x * is, py = d.y * is;
+    float u = px, v = py;
+    if (d.z < 0.0f) { u = (1.0f - __builtin_fabsf(py)) * __builtin_copysignf(1.0f, px); v = (1.0f - __builtin_fabsf(px)) * __builtin_copysignf(1.0f, py); }
+    return env_cell(v, e.nf, e.n) * e.n + env_cell(u, e.nf, e.n);
+}
 PT_DEV void path_store_nee(const PathState &ps, uint32_t slot, const PathRegs &r, const NeeRegs &nr)
 {
     at(ps.ray_o, slot) = make_float4(r.o.x, r.o.y, r.o.z, __uint_as_float(nr.flags));
@@ -539,7 +576,9 @@ PT_DEV bool next_sample(const DeviceScene &sc, const FrameParams &fp, uint32_t s
 // With SHADE_QUEUE / SHADE_BUCKETS and without NEE, the new direction of a Lambert vertex and of a regenerated camera ray are made in one
 // pass at the end (see there). The all-kinds SHADE_INLINE kernels keep one branch per kind: with the shared end they spill registers
 // that the two-branch form leaves them (k_extend<.., SHADE_INLINE> 1 to 5 VGPRs more, k_extend_packed<.., SHADE_INLINE> 4).
-template <int MODE, bool NEE = false>
+// ENV (k_extend<.., ENV> only, docs/SPEC.md §11): a miss looks the environment map up instead of the sky, and in a NEE frame the light
+// sample of a Lambert vertex goes to the map or to a light triangle (half each while the frame has both), its shadow ray without a tmax.
+template <int MODE, bool NEE = false, bool ENV = false>
 PT_DEV bool shade_one(const DeviceScene &sc, const PathState &ps, const FrameParams &fp, uint32_t slot, PathRegs &r, float t, uint32_t ref,
                       uint32_t b, uint32_t &defer, NeeRegs *nr = nullptr)
 {
@@ -559,6 +598,19 @@ PT_DEV bool shade_one(const DeviceScene &sc, const PathState &ps, const FramePar
     };
 
     if (ref == PT_MISS) {
+        if constexpr (ENV) {
+            const EnvArgs &ea = cold_env<NEE>();
+            float s;
+            const float4 tx = ea.texels[env_texel(ea, d, s)];
+            V3 e = xyz(tx);
+            if constexpr (NEE) // §11 w: the ray left a Lambert vertex (aux = its pdf) of a frame that also samples the map
+                if (ea.lit && nr->aux > 0.0f) {
+                    const float pl = ea.psel * (tx.w / ((s * s) * s)), q = pl / nr->aux;
+                    const float w = nan_to_zero(1.0f / fma_(q, q, 1.0f));
+                    e = v3(tx.x * w, tx.y * w, tx.z * w);
+                }
+            add(e);
+        } else
         add(v3(sc.sky[0], sc.sky[1], sc.sky[2]));
         term = true;
     } else {
@@ -591,8 +643,9 @@ PT_DEV bool shade_one(const DeviceScene &sc, const PathState &ps, const FramePar
         if (emi.x != 0.0f || emi.y != 0.0f || emi.z != 0.0f) {
             if constexpr (NEE) { // §7 w_b: the ray left a Lambert vertex (aux = its pdf) and hit a light-set triangle (pa > 0)
                 V3 e = emi;
-                if (nr->aux > 0.0f && ref < sc.n_tris) {
-                    const float pa = cold_nee().pa[ref];
+                if (nr->aux > 0.0f && ref < sc.n_tris && (!ENV || cold_nee().n_lights)) { // (ENV: aux is also set when the map is the only light)
+                    float pa = cold_nee().pa[ref];
+                    if constexpr (ENV) pa = pa * cold_env<NEE>().psel;
                     if (pa > 0.0f) {
                         const float pl = (pa * (t * t)) / __builtin_fabsf(dot(ng, d)), q = pl / nr->aux;
                         const float w = nan_to_zero(1.0f / fma_(q, q, 1.0f));
@@ -640,11 +693,40 @@ PT_DEV bool shade_one(const DeviceScene &sc, const PathState &ps, const FramePar
                 if constexpr (NEE) {
                     const NeeArgs &na = cold_nee();
                     // the pdf of the extension ray, for the w_b of the emission it may find (Lambert vertices only)
-                    if (!term) nr->aux = (bk == B_LAMBERT && na.n_lights) ? dot(n, wi) * kInvPi : 0.0f;
+                    auto lights = [&]() -> bool { // does this frame sample a light at all
+                        if constexpr (ENV) return na.n_lights || cold_env<NEE>().lit;
+                        else return na.n_lights;
+                    };
+                    if (!term) nr->aux = (bk == B_LAMBERT && lights()) ? dot(n, wi) * kInvPi : 0.0f;
                     // §7 light sample of a Lambert vertex. Computed after the BSDF sample and Russian roulette to keep it out of their registers;
                     // its random numbers are its own (dimensions 1024 + 3b ..) and it uses only T * albedo of the T that arrived here.
-                    if (bk == B_LAMBERT && na.n_lights) {
-                        const float4 *lr = na.lights + (size_t)pick_light(na.cdf, na.n_lights, u01(key, 1024u + 3u * bb)) * 4;
+                    if (bk == B_LAMBERT && lights()) {
+                        float uc = 0.0f; // (ENV) the choice number u' of the strategy taken
+                        bool to_env = false;
+                        if constexpr (ENV) {
+                            uc = u01(key, 1024u + 3u * bb); // §11 strategy: the map iff uc < 1/2 while the frame has both kinds of light, else the kind there is
+                            to_env = cold_env<NEE>().lit != 0u;
+                            if (to_env && na.n_lights) { to_env = uc < 0.5f; uc = to_env ? uc * 2.0f : fma_(uc, 2.0f, -1.0f); }
+                        }
+                        if (ENV && to_env) {
+                            const EnvArgs &ea = cold_env<NEE>();
+                            const uint32_t j = pick_light(ea.mcdf, ea.n, uc), i = pick_light(ea.ccdf + (size_t)j * ea.n, ea.n, u01(key, 1025u + 3u * bb));
+                            const float u = fma_((float)i + u01(key, 1026u + 3u * bb), ea.step, -1.0f), v = fma_((float)j + u01(key, 2048u + bb), ea.step, -1.0f);
+                            const V3 wl = env_decode(u, v);
+                            float s;
+                            const float4 tx = ea.texels[env_texel(ea, wl, s)]; // the lookup decides, not (i, j)
+                            const float cs = dot(n, wl), pl = ea.psel * (tx.w / ((s * s) * s));
+                            if (cs > 0.0f && pl > 0.0f) {
+                                const float q = (cs * kInvPi) / pl, f = nan_to_zero(q / fma_(q, q, 1.0f));
+                                at(na.rad, slot) = make_float4((ta.x * f) * tx.x, (ta.y * f) * tx.y, (ta.z * f) * tx.z, 0.0f);
+                                if (!term) at(na.ext, slot) = make_float4(d.x, d.y, d.z, nr->aux);
+                                nr->flags = NEE_PENDING | (term ? NEE_END : 0u);
+                                nr->aux = __builtin_inff(); // no tmax: visible iff the shadow ray misses everything
+                                o = madd(fp.ray_eps, n, P); d = wl;
+                                term = false;
+                            }
+                        } else {
+                        const float4 *lr = na.lights + (size_t)pick_light(na.cdf, na.n_lights, ENV ? uc : u01(key, 1024u + 3u * bb)) * 4;
                         const float4 l0 = lr[0], l1 = lr[1], l2 = lr[2];
                         const float su = __builtin_sqrtf(u01(key, 1025u + 3u * bb)), b1 = 1.0f - su, b2 = u01(key, 1026u + 3u * bb) * su;
                         const V3 x = v3(fma_(b2, l2.x, fma_(b1, l1.x, l0.x)), fma_(b2, l2.y, fma_(b1, l1.y, l0.y)), fma_(b2, l2.z, fma_(b1, l1.z, l0.z)));
@@ -655,7 +737,9 @@ PT_DEV bool shade_one(const DeviceScene &sc, const PathState &ps, const FramePar
                         const float4 l3 = lr[3];
                         const float cs = dot(n, sd), cl = __builtin_fabsf(dot(xyz(l3), sd));
                         if (cs > 0.0f && cl > 0.0f) { // the shadow ray goes first; the extension ray (if the path goes on) waits in NeeArgs::ext
-                            const float pl = (l0.w * dist2) / cl, q = (cs * kInvPi) / pl;
+                            float pa = l0.w;
+                            if constexpr (ENV) pa = pa * cold_env<NEE>().psel;
+                            const float pl = (pa * dist2) / cl, q = (cs * kInvPi) / pl;
                             const float f = nan_to_zero(q / fma_(q, q, 1.0f)); // w_l * pdf_bsdf / pdf_light
                             at(na.rad, slot) = make_float4((ta.x * f) * l1.w, (ta.y * f) * l2.w, (ta.z * f) * l3.w, 0.0f);
                             if (!term) at(na.ext, slot) = make_float4(d.x, d.y, d.z, nr->aux);
@@ -663,6 +747,7 @@ PT_DEV bool shade_one(const DeviceScene &sc, const PathState &ps, const FramePar
                             nr->aux = dist * 0.9999f;
                             o = so; d = sd;
                             term = false;
+                        }
                         }
                     }
                 }
@@ -799,6 +884,12 @@ PT_DEV void queue_next(const PathState &ps, uint32_t shard, uint32_t cnext, uint
 #define PT_EXT_WAVES_NEE(L, FUSE) ((FUSE) == SHADE_QUEUE && (L) != PT_BVH_WIDTH_8Q && (L) != PT_BVH_WIDTH_8O ? 7 : 6)
 #endif
 #define PT_EXT_WAVES_OF(L, FUSE, NEE) ((NEE) ? PT_EXT_WAVES_NEE(L, FUSE) : PT_EXT_WAVES(L, FUSE))
+// The environment instantiations (docs/SPEC.md §11; all-kinds shading only) hold the map lookup on top of that: the highest budgets at
+// which none of them spills (DESIGN.md has the table): plain 72 VGPRs = 7 waves (BVH8O 80 = 6), with NEE 96 = 5.
+#ifndef PT_EXT_WAVES_ENV
+#define PT_EXT_WAVES_ENV(L, NEE) ((NEE) ? 5 : (L) == PT_BVH_WIDTH_8O ? 6 : 7)
+#endif
+#define PT_EXT_WAVES_FOR(L, FUSE, NEE, ENV) ((ENV) ? PT_EXT_WAVES_ENV(L, NEE) : PT_EXT_WAVES_OF(L, FUSE, NEE))
 // A lane's traversal stack: kStackLds entries in its LDS column ([level][lane]: conflict-free), the rest in a global
 // overflow column sized by the builder's exact worst case (pt_bvh_info.stack_need).
 struct StackCtx { int32_t *lds; uint32_t stride, tid, col; }; // col: the lane's column of the overflow area, unique per thread of a launch
@@ -1067,11 +1158,13 @@ PT_DEV Hit trace_ray(const HotScene &g, const StackCtx &stk, V3 o, V3 d, Hit h, 
 
 // NEE (PT_FLAG_NEXT_EVENT; fused, not counting): one ray per lane per pass, a shadow ray or an extension ray (see NeeRegs); `bounces`
 // then counts passes.
-template <int L, bool COUNT, int FUSE, bool NEE = false>
-__global__ void __launch_bounds__(kExtBlock) __attribute__((amdgpu_waves_per_eu(PT_EXT_WAVES_OF(L, FUSE, NEE), PT_EXT_WAVES_OF(L, FUSE, NEE))))
-k_extend(typename ExtArgsOf<NEE>::type a)
+// ENV (a scene with an environment map, docs/SPEC.md §11; all-kinds shading, not counting): shade_one's environment paths.
+template <int L, bool COUNT, int FUSE, bool NEE = false, bool ENV = false>
+__global__ void __launch_bounds__(kExtBlock) __attribute__((amdgpu_waves_per_eu(PT_EXT_WAVES_FOR(L, FUSE, NEE, ENV), PT_EXT_WAVES_FOR(L, FUSE, NEE, ENV))))
+k_extend(typename ExtArgsFor<NEE, ENV>::type a)
 {
     static_assert(!NEE || (FUSE != SHADE_NONE && !COUNT), "NEE: fused shading, no visit counters");
+    static_assert(!ENV || (FUSE == SHADE_INLINE && !COUNT), "ENV: all-kinds fused shading, no visit counters");
     const HotScene g = hot_scene(a.sc);
     const uint32_t it = a.it;
     __shared__ int32_t s_stack[kStackLds * kExtBlock];
@@ -1135,9 +1228,9 @@ k_extend(typename ExtArgsOf<NEE>::type a)
             if constexpr (NEE) {
                 nr.aux = __uint_as_float(s_stash[5 * kExtBlock + tid]); nr.flags = s_stash[6 * kExtBlock + tid];
                 if (nr.flags & NEE_PENDING) alive = resolve_shadow(c.sc, c.ps, c.fp, cold_nee(), slot, r, nr, h.ref == PT_MISS);
-                else alive = shade_one<FUSE, true>(c.sc, c.ps, c.fp, slot, r, h.t, h.ref, B_LAMBERT, defer, &nr);
+                else alive = shade_one<FUSE, true, ENV>(c.sc, c.ps, c.fp, slot, r, h.t, h.ref, B_LAMBERT, defer, &nr);
             } else
-            alive = shade_one<FUSE>(c.sc, c.ps, c.fp, slot, r, h.t, h.ref, B_LAMBERT, defer);
+            alive = shade_one<FUSE, false, ENV>(c.sc, c.ps, c.fp, slot, r, h.t, h.ref, B_LAMBERT, defer);
         }
     }
     }
@@ -1655,7 +1748,7 @@ static void with_fuse(int fuse, F &&f)
 }
 
 hipError_t launch_extend(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp, uint32_t it, uint32_t shard_bound, bool count,
-                         int kernel, uint32_t packed_chunk, int fuse, bool compact, uint32_t bounces, const NeeArgs *nee)
+                         int kernel, uint32_t packed_chunk, int fuse, bool compact, uint32_t bounces, const NeeArgs *nee, const EnvArgs *env)
 {
     // kernel: EXT_SIMPLE one ray per lane; EXT_PACKED a wavefront owns `packed_chunk` (>= 64) queue entries and refills idle lanes,
     // shading each finished ray on the spot; EXT_POOL a wavefront owns kPool entries, refills idle lanes during traversal and shades
@@ -1671,6 +1764,19 @@ hipError_t launch_extend(hipStream_t s, const DeviceScene &sc, const PathState &
     ExtArgsNee an;
     static_cast<ExtArgs &>(an) = a;
     if (nee) an.nee = *nee;
+    // an environment map: the same kernel, all-kinds shading, not counting (api.cpp refuses the rest), in its environment instantiation
+    if (env) {
+        if (kernel != EXT_SIMPLE || count || fuse != SHADE_INLINE) return hipErrorInvalidValue;
+        ExtArgsEnv<false> ae; ExtArgsEnv<true> ane;
+        static_cast<ExtArgs &>(ae) = a; ae.env = *env;
+        static_cast<ExtArgsNee &>(ane) = an; ane.env = *env;
+        const bool known = with_layout(sc.bvh_width, [&](auto lc) {
+            constexpr int L = decltype(lc)::value;
+            if (nee) hipLaunchKernelGGL((k_extend<L, false, SHADE_INLINE, true, true>), grid, dim3(kExtBlock), 0, s, ane);
+            else hipLaunchKernelGGL((k_extend<L, false, SHADE_INLINE, false, true>), grid, dim3(kExtBlock), 0, s, ae);
+        });
+        return known ? hipGetLastError() : hipErrorInvalidValue;
+    }
     // layout x fuse x (NEE | count x kernel): the pool and NEE kernels always shade, so they have no SHADE_NONE instantiation
     const bool known = with_layout(sc.bvh_width, [&](auto lc) { with_fuse(fuse, [&](auto fc) {
         constexpr int L = decltype(lc)::value, F = decltype(fc)::value, FS = F == SHADE_NONE ? SHADE_QUEUE : F;

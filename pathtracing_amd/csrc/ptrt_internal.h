@@ -132,6 +132,19 @@ struct NeeArgs {
     float4 *rad;           // per slot, while a shadow ray is pending: the radiance the shadow ray adds if it reaches the light | -
 };
 
+// The environment map of a scene (pt_scene_set_environment, docs/SPEC.md §11; environment.cpp builds and uploads the table). Like
+// NeeArgs a block of its own behind ExtArgs / ExtArgsNee (kernels.hip ExtArgsEnv), for the same reason; only the environment
+// instantiations of k_extend have it.
+struct EnvArgs {
+    const float4 *texels;  // n * n records, row-major: r, g, b, p (the texel's pdf over the unit square of the map, x n * n / 4)
+    const float *mcdf;     // n entries: the marginal cdf over rows, the last one 1.0f
+    const float *ccdf;     // n * n entries: row j's conditional cdf over columns, the last one of every row 1.0f
+    uint32_t n;
+    float nf, step;        // (float)n, 2.0f / (float)n
+    uint32_t lit;          // the table's total is positive: the environment is a light for PT_FLAG_NEXT_EVENT frames
+    float psel;            // this frame's probability of the strategy a light sample takes: 0.5f with both kinds of light, else 1.0f
+};
+
 struct FrameParams {
     uint32_t width, height, spp, max_depth, rr_start, seed_hashed, sample_offset;
     float ray_eps;
@@ -169,8 +182,10 @@ hipError_t launch_generate(hipStream_t s, const DeviceScene &sc, const PathState
 // queues the next iteration, honouring `compact` like launch_shade. packed_chunk: queue entries per wavefront of EXT_PACKED.
 // bounces (fused only): path vertices a lane advances per launch.
 // nee (may be NULL): a PT_FLAG_NEXT_EVENT frame; only the one-ray-per-lane kernel, fused (fuse 0 / 2), without counting, has it.
+// env (may be NULL): a frame of a scene with an environment map; the same kernel, with all-kinds shading (fuse 2) only.
 hipError_t launch_extend(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp, uint32_t it, uint32_t shard_bound, bool count,
-                         int kernel, uint32_t packed_chunk, int fuse, bool compact, uint32_t bounces, const NeeArgs *nee = nullptr);
+                         int kernel, uint32_t packed_chunk, int fuse, bool compact, uint32_t bounces, const NeeArgs *nee = nullptr,
+                         const EnvArgs *env = nullptr);
 // mode: 0 = queue order, specular kinds deferred to buckets; 1 = the specular buckets; 2 = queue order, everything shaded in place
 // compact: 1 = survivors are appended densely to the next queue (ballot + one returning atomic per wavefront);
 //          0 = every lane writes its own position of the next queue (slot or kInvalidSlot): no returning atomics, and the

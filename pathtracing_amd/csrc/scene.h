@@ -5,6 +5,7 @@
 #include "context.h"
 #include "bvh_build.h"
 #include "blob_rules.h"
+#include "environment.h"
 #include <vector>
 
 namespace ptrt {
@@ -114,6 +115,8 @@ struct pt_scene {
     std::vector<pt_material> mats;
     pt_camera cam{};
     float sky[3] = { 0.f, 0.f, 0.f };
+    ptrt::Environment env;               // while present it replaces `sky` on the misses of a path-traced frame (docs/SPEC.md §11); not
+                                         // scene content in the commit's sense: set, replaced and removed at any time, kept by commits and updates
     bool have_cam = false, committed = false;
     ptrt::CommittedTree tree;
     mutable ptrt::CommitCaches cache;    // (mutable: pt_render and pt_denoise fill it through the const scene they receive)

@@ -48,6 +48,49 @@ class SceneData:
     mats: np.ndarray = field(default_factory=lambda: np.zeros((0,), MATERIAL_DTYPE))
     cam: N.pt_camera = field(default_factory=N.pt_camera)
     sky: np.ndarray = field(default_factory=lambda: np.zeros(3, np.float32))
+    environment: np.ndarray = None  # optional n x n x 3 octahedral map (docs/SPEC.md §11); SetScene applies it
+
+
+def _octahedral_directions(n, sub):
+    """Unit directions (float64, (n, n, sub, sub, 3), indexed row, column, sub-row, sub-column) of a sub x sub grid of points in every
+    texel of the n x n octahedral map: docs/SPEC.md §11's decode, in numpy."""
+    t = (np.arange(n * sub) + 0.5) * (2.0 / (n * sub)) - 1.0
+    u, v = np.meshgrid(t, t)  # v varies along rows
+    z = 1.0 - np.abs(u) - np.abs(v)
+    x = np.where(z < 0, (1.0 - np.abs(v)) * np.copysign(1.0, u), u)
+    y = np.where(z < 0, (1.0 - np.abs(u)) * np.copysign(1.0, v), v)
+    d = np.stack([x, y, z], -1)
+    d /= np.linalg.norm(d, axis=-1, keepdims=True)
+    return d.reshape(n, sub, n, sub, 3).transpose(0, 2, 1, 3, 4)
+
+
+def _octahedral_mean(values, n, sub):
+    """Mean of per-point values (n, n, sub, sub, 3) over each texel's solid angle: the points weigh s^3 (d omega = s^3 dA, §11)."""
+    d = _octahedral_directions(n, sub)
+    w = (np.abs(d).sum(-1) ** 3)[..., None]
+    return ((values * w).sum((2, 3)) / w.sum((2, 3))).astype(np.float32)
+
+
+def environment_from_latlong(img, n, sub=4):
+    """Resample a latitude-longitude image (rows from the +y pole down, columns by azimuth atan2(x, -z) from -pi to pi, 3 channels) to
+    the n x n octahedral map pt_scene_set_environment takes: every texel is the solid-angle mean of a fixed sub x sub grid of nearest
+    lookups. Host code: libm is allowed here, the device never sees a latitude or a longitude."""
+    img = np.asarray(img, np.float64)
+    h, w = img.shape[:2]
+    d = _octahedral_directions(n, sub)
+    row = np.clip((np.arccos(np.clip(d[..., 1], -1.0, 1.0)) / np.pi * h).astype(int), 0, h - 1)
+    col = np.clip(((np.arctan2(d[..., 0], -d[..., 2]) / (2.0 * np.pi) + 0.5) * w).astype(int), 0, w - 1)
+    return _octahedral_mean(img[row, col, :3], n, sub)
+
+
+def sun_sky_environment(n, sun_dir, sun_rgb, sun_cos, sky_rgb, sub=4):
+    """A deterministic n x n octahedral map: `sky_rgb` everywhere plus `sun_rgb` inside the cone of directions d with
+    dot(d, sun_dir) >= sun_cos (a texel the cone's edge crosses gets the covered share of a fixed sub x sub grid)."""
+    s = np.asarray(sun_dir, np.float64)
+    s = s / np.linalg.norm(s)
+    d = _octahedral_directions(n, sub)
+    inside = ((d @ s) >= sun_cos)[..., None]
+    return _octahedral_mean(np.asarray(sky_rgb, np.float64) + inside * np.asarray(sun_rgb, np.float64), n, sub)
 
 
 def make_scene(kind, detail=0, seed=0x5EED0001, width=1920, height=1080):
@@ -172,7 +215,25 @@ class Renderer:
         _check(N.lib.pt_scene_set_camera(s, C.byref(scene.cam)), ctx)
         sky = (C.c_float * 3)(*[float(v) for v in scene.sky])
         _check(N.lib.pt_scene_set_sky(s, C.byref(sky)), ctx)
+        if getattr(scene, "environment", None) is not None:
+            self.SetEnvironment(scene.environment)
         _check(N.lib.pt_scene_commit(s, bvh_width), ctx)
+
+    def SetEnvironment(self, rgb):
+        """Give the current scene an environment map (include/ptrt.h pt_scene_set_environment: n x n x 3 floats, octahedral layout,
+        docs/SPEC.md §11; no new commit needed), or remove it with None."""
+        if rgb is None:
+            _check(N.lib.pt_scene_set_environment(self._scene, None, 0), self._ctx)
+            return
+        a = np.ascontiguousarray(rgb, np.float32)
+        if a.ndim != 3 or a.shape[0] != a.shape[1] or a.shape[2] != 3:
+            raise ValueError(f"environment must be n x n x 3, got {a.shape}")
+        _check(N.lib.pt_scene_set_environment(self._scene, _ptr(a), a.shape[0]), self._ctx)
+
+    def EnvironmentInfo(self):
+        info = N.pt_environment_info()
+        _check(N.lib.pt_scene_environment_info(self._scene, C.byref(info)), self._ctx)
+        return info
 
     def SetCamera(self, cam):
         """Move the current scene's camera (include/ptrt.h pt_scene_set_camera: no new commit needed)."""
