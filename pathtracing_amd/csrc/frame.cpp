@@ -81,6 +81,64 @@ hipEvent_t pool_event(pt_context *c, size_t i)
     return c->ev_pool[i];
 }
 
+// The frame's scene pixels (ptrt_internal.h FrameParams::scene_x0 ..): a rectangle of pixels outside of which no camera ray can hit
+// anything, so that those pixels' samples need no tracing (kernels.hip k_sky_pixels). Returns whether the image has such a pixel; if not,
+// or if nothing can be said, the rectangle is everything.
+//   The box: the union of the root node's child boxes as the device holds them (a ray reaches a triangle only through the slab test of
+// one of them) and of every sphere's box, the radius taken as sqrt(r^2 + 2^-16 (|c - o| + r)^2): sphere_test's discriminant b^2 - (|oc|^2
+// - r^2) carries a rounding error of about 13 * 2^-24 |oc|^2 (three roundings in each dot product, the ray's direction normalised to 3
+// ulp), so a ray that passes a small far sphere at several radii can still be accepted. Each side then moves out by 1e-4 of the largest
+// coordinate in play (box, camera origin): the slab test's t = fma(plane, inv, -(o * inv)) is off by at most 3 * 2^-24 (|o| + |plane|)
+// in units of the plane's position, the quantised layouts' fused form and the 1.0000004 on the far side by as little.
+//   The projection: camera_vec's map inverted, v = a right + b up + c forward, pixel = ((a / c + cx) / scale, (b / c + cy) / scale), in
+// double, of the box's 8 corners; their bounding rectangle (the box is convex and in front of the camera plane) widened by one pixel and
+// by 1e-4 of the image's size and principal point, against the 2^-24 relative roundings of camera_vec and normalize. A pixel is a scene
+// pixel unless its footprint [x, x + 1) x [y, y + 1) lies outside that. Everything is a scene pixel if a corner has c <= 1e-4 (|a| + |b| +
+// |c|) (beside or behind the camera plane, or the camera inside the box), if the basis is near-singular, scale is not positive, a
+// coordinate is beyond 1e15 (the slab test's 1e20 reciprocals would overflow) or the tree's bound is stale.
+bool scene_pixels(const pt_scene *s, const pt_camera &cam, uint32_t W, uint32_t H, FrameParams &fp)
+{
+    fp.scene_x0 = fp.scene_y0 = 0u; fp.scene_x1 = fp.scene_y1 = ~0u;
+    Box tb;
+    if (!s->tree.root_bound(tb)) return false;
+    double lo[3], hi[3], o[3], big = 0.0;
+    for (int k = 0; k < 3; ++k) { lo[k] = tb.lo[k]; hi[k] = tb.hi[k]; o[k] = cam.origin[k]; big = std::max(big, std::fabs(o[k])); }
+    for (size_t i = 0; i < s->sph_mat.size(); ++i) {
+        const float *sp = &s->spheres[i * 4];
+        const double r = sp[3], dx = sp[0] - o[0], dy = sp[1] - o[1], dz = sp[2] - o[2], reach = std::sqrt(dx * dx + dy * dy + dz * dz) + r;
+        const double rr = std::sqrt(r * r + std::ldexp(reach * reach, -16));
+        for (int k = 0; k < 3; ++k) { lo[k] = std::min(lo[k], sp[k] - rr); hi[k] = std::max(hi[k], sp[k] + rr); }
+    }
+    if (!(lo[0] <= hi[0])) { fp.scene_x0 = fp.scene_x1 = fp.scene_y0 = fp.scene_y1 = ~0u; return true; } // nothing to hit: every pixel is sky
+    for (int k = 0; k < 3; ++k) big = std::max(big, std::max(std::fabs(lo[k]), std::fabs(hi[k])));
+    if (!(big < 1e15)) return false;
+    for (int k = 0; k < 3; ++k) { lo[k] -= 1e-4 * big; hi[k] += 1e-4 * big; }
+    const double R[3] = { cam.right[0], cam.right[1], cam.right[2] }, U[3] = { cam.up[0], cam.up[1], cam.up[2] }, F[3] = { cam.forward[0], cam.forward[1], cam.forward[2] };
+    auto cross = [](const double *a, const double *b, double *c) { c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0]; };
+    auto dot = [](const double *a, const double *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; };
+    double UF[3], FR[3], RU[3];
+    cross(U, F, UF); cross(F, R, FR); cross(R, U, RU);
+    const double det = dot(R, UF), scale = cam.scale;
+    if (!(std::fabs(det) > 1e-6 * std::sqrt(dot(R, R) * dot(U, U) * dot(F, F))) || !(scale > 0.0) || !std::isfinite(scale)) return false;
+    double x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
+    for (int i = 0; i < 8; ++i) {
+        const double v[3] = { ((i & 1) ? hi[0] : lo[0]) - o[0], ((i & 2) ? hi[1] : lo[1]) - o[1], ((i & 4) ? hi[2] : lo[2]) - o[2] };
+        const double a = dot(v, UF) / det, b = dot(v, FR) / det, c = dot(v, RU) / det;
+        if (!(c > 1e-4 * (std::fabs(a) + std::fabs(b) + std::fabs(c)))) return false;
+        const double px = (a / c + cam.cx) / scale, py = (b / c + cam.cy) / scale;
+        x0 = std::min(x0, px); x1 = std::max(x1, px); y0 = std::min(y0, py); y1 = std::max(y1, py);
+    }
+    const double mx = 1.0 + 1e-4 * ((double)W + std::fabs(cam.cx / scale)), my = 1.0 + 1e-4 * ((double)H + std::fabs(cam.cy / scale));
+    x0 -= mx; x1 += mx; y0 -= my; y1 += my;
+    if (!std::isfinite(x0) || !std::isfinite(x1) || !std::isfinite(y0) || !std::isfinite(y1)) return false;
+    // pixel x is sky iff x + 1 <= x0 or x >= x1: x < floor(x0) or x >= ceil(x1)
+    auto px_of = [](double v, uint32_t n) { return (uint32_t)std::min(std::max(v, 0.0), (double)n); };
+    fp.scene_x0 = px_of(std::floor(x0), W); fp.scene_x1 = px_of(std::ceil(x1), W);
+    fp.scene_y0 = px_of(std::floor(y0), H); fp.scene_y1 = px_of(std::ceil(y1), H);
+    if (fp.scene_x0 == 0u && fp.scene_x1 >= W && fp.scene_y0 == 0u && fp.scene_y1 >= H) { fp.scene_x1 = fp.scene_y1 = ~0u; return false; }
+    return true;
+}
+
 struct Frame {                  // a path-traced frame as plan_frame lays it out, and what its loops leave for finish_frame
     uint32_t nranks, streams, pixel_slots, n_slots, shard_cap, samples_per_stream, lag, n_loops, packed_chunk, default_bounces;
     uint32_t forced;            // ExtendKernel a frame flag or pt_tuning.extend_kernel forces (0 = none)
@@ -89,6 +147,7 @@ struct Frame {                  // a path-traced frame as plan_frame lays it out
     NeeArgs nee_args;
     bool env;                   // the scene has an environment map (docs/SPEC.md §11): the same kernel, in its environment instantiation
     EnvArgs env_args;
+    bool sky;                   // the frame has sky pixels (scene_pixels) and resolves them at its start instead of tracing their paths
     Accumulation::Key sums_key; // what the sums hold once this frame completes
     size_t q_entries; uint64_t total_spp, allocs_before;
     PathState ps; FrameParams fp;
@@ -229,6 +288,11 @@ static pt_status plan_frame(pt_context *c, const pt_scene *s, const pt_render_pa
     fp.rank = p->rank; fp.nranks = f.nranks; fp.tiles_x = lay.tiles_x; fp.n_tiles = lay.n_tiles; fp.streams = f.streams; fp.slots_per_stream = f.pixel_slots;
     div_magic(f.streams, fp.streams_magic, fp.streams_shift); div_magic(lay.tiles_x, fp.tiles_x_magic, fp.tiles_x_shift);
     fp.offset_mod = p->sample_offset % f.streams; fp.accumulate = f.accumulate ? 1u : 0u;
+    // Sky pixels are resolved by the frames whose first launch builds the slots' state in registers (path_begin: the fused one-ray-per-lane
+    // and lane-packing kernels, next-event estimation included: a camera ray's miss adds the sky with weight 1 there too). Not by counting
+    // frames, whose visit counters are the spec's, nor with an environment map, where a miss depends on the ray's direction.
+    fp.scene_x0 = fp.scene_y0 = 0u; fp.scene_x1 = fp.scene_y1 = ~0u;
+    f.sky = !f.full_state && !f.count && !f.env && scene_pixels(s, s->ds.cam, p->width, p->height, fp);
     return PT_OK;
 }
 
@@ -249,6 +313,8 @@ static pt_status start_frame(pt_context *c, const pt_scene *s, const pt_render_p
         const pt_status st = c->start.build_if_differs(c, q, key, s->ds, f.ps, f.fp, c->sizes);
         if (st != PT_OK) return st;
         HIP_TRY(c, hipMemcpyAsync(c->counters.p, c->start.counters(), sizeof(uint32_t) * kCntTotalWords, hipMemcpyDeviceToDevice, q));
+        // the template is the geometry's, not the camera's: it still queues the sky pixels' slots, and the first launch leaves them out
+        if (f.sky) HIP_TRY(c, launch_sky_pixels(q, s->ds, f.ps, f.fp));
     }
     c->start.frame_ran(f.accumulate || f.full_state); // the template invariant: this frame writes the streams a dense template leaves out
     return PT_OK;
@@ -351,15 +417,20 @@ static pt_status finish_frame(pt_context *c, const pt_render_params *p, const Fr
                                100 * v / slots, 100 * lf / slots, 100 * dn / slots, 100 * (slots - v - lf - dn) / slots);
     }
     out.iterations = f.iters; out.extend_launches = f.iters;
-    x.frame_done(out.rays, out.gpu_ms, g_device_allocs != f.allocs_before);
+    x.frame_done(out.rays, out.gpu_ms, g_device_allocs != f.allocs_before); // (the rays the extend kernels traced: resolved sky pixels join below)
     out.reserved[0] = x.kernel ? x.kernel : (uint32_t)EXT_SIMPLE; // extend kernel in use at frame end (ExtendKernel)
     out.reserved[1] = hc.word(kCntCompactions); // (shard, iteration) pairs that re-packed their queue (the others carried it over in place)
-    uint64_t px = 0; // paths = owned in-image pixels x spp
+    uint64_t px = 0, scene_px = 0; // paths = owned in-image pixels x spp; scene_px: those of them inside the frame's scene rectangle
     for (uint32_t t = p->rank; t < fp.n_tiles; t += f.nranks) {
         const uint32_t tx = t % fp.tiles_x, ty = t / fp.tiles_x;
-        px += (uint64_t)std::min(kTile, p->width - tx * kTile) * std::min(kTile, p->height - ty * kTile);
+        const uint32_t xa = tx * kTile, ya = ty * kTile, xb = xa + std::min(kTile, p->width - xa), yb = ya + std::min(kTile, p->height - ya);
+        px += (uint64_t)(xb - xa) * (yb - ya);
+        const int64_t ix = (int64_t)std::min(xb, fp.scene_x1) - (int64_t)std::max(xa, fp.scene_x0), iy = (int64_t)std::min(yb, fp.scene_y1) - (int64_t)std::max(ya, fp.scene_y0);
+        scene_px += (uint64_t)(std::max<int64_t>(ix, 0) * std::max<int64_t>(iy, 0));
     }
     out.paths = px * p->spp;
+    // every sample of a sky pixel is one camera ray that k_sky_pixels resolved instead of the extend kernels tracing (and counting) it
+    out.rays += (px - scene_px) * p->spp;
     // path states read + written by the wavefront loop = sum over launches of the paths alive at launch start
     // (iteration 0 starts every (pixel, stream) pair that has a sample)
     out.reserved[2] = f.slot_launches + px * std::min(f.streams, p->spp);
@@ -374,6 +445,8 @@ static pt_status finish_frame(pt_context *c, const pt_render_params *p, const Fr
                                (unsigned long long)(i / 3 < f.trace_alive.size() ? f.trace_alive[i / 3] : 0), a, b);
         }
         out.other_ms = out.gpu_ms - out.extend_ms - out.shade_ms;
+        if (trace && f.sky) fprintf(stderr, "ptrt: sky pixels x [%u, %u) y [%u, %u) excepted: %llu of %llu pixels, %llu rays resolved at frame start\n", fp.scene_x0,
+                                    fp.scene_x1, fp.scene_y0, fp.scene_y1, (unsigned long long)(px - scene_px), (unsigned long long)px, (unsigned long long)((px - scene_px) * p->spp));
     }
     c->out.tiles_hold(f.pixel_slots); c->sums.complete(f.sums_key, f.total_spp);
     if (f.nranks == 1) c->out.complete(FrameOutputs::Holds::path_traced);

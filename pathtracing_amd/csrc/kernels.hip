@@ -2,6 +2,7 @@
 //
 //   k_reference_sphere : the reference's CSMain (Test.hlsl:1-40; dispatch Renderer.cs:1020), one lane = one pixel
 //   k_generate         : camera ray of the first sample of every (owned pixel, sample stream), fills the extend queues
+//   k_sky_pixels       : the sums and ray counts of the slots whose pixel provably sees only the sky, once per frame
 //   k_extend<L,C,FUSE> : ray -> closest hit. BVH traversal for node layout L, stack in LDS ([level][lane],
 //                        conflict-free), spheres by scalar loads, one 4-row fetch per step for node or triangle.
 //                        FUSE (the default pipeline): the lane also shades its hit (shade_one: emission, BSDF sample,
@@ -510,6 +511,17 @@ PT_DEV void path_begin(uint32_t it, uint32_t slot, PathRegs &r, NeeRegs *nr = nu
         if constexpr (NEE) { nr->flags = __float_as_uint(at(ps.ray_o, slot).w); nr->aux = at(ps.ray_d, slot).w; }
     }
 }
+// A queue entry as a fused extend kernel takes it up in launch `it`. In the frame's first launch the slot of a sky pixel (ptrt_internal.h
+// FrameParams::scene_x0 ..) is a hole: k_sky_pixels has made its sum, the host counts its rays, it holds no path and path_begin never sees it.
+PT_DEV uint32_t queued_slot(uint32_t it, uint32_t slot)
+{
+    if (it == 0u && slot != kInvalidSlot) {
+        uint32_t x = 0, y = 0;
+        slot_pixel(slot, cold().fp, x, y);
+        if (sky_pixel(cold().fp, x, y)) slot = kInvalidSlot;
+    }
+    return slot;
+}
 
 // ------------------------------------------------------------------------------------------------
 // grid (ceil(shard_cap/256), kShards). Which slots a shard owns is decided here and nowhere else (queues only ever hand a slot on to
@@ -548,6 +560,27 @@ __global__ void __launch_bounds__(kBlock) k_generate(DeviceScene sc, PathState p
         if (n_alive) atomicAdd(&ps.counters[cnt_alive_index(0, shard)], n_alive);
         if (bx == 0 && full != 2u) ps.counters[cnt_ext_index(0, shard)] = ps.shard_cap;
     }
+}
+
+// The frame's sky pixels (FrameParams::scene_x0 ..: no camera ray of theirs can hit anything), one lane per slot in slot order. Every
+// sample of such a slot's stream is a camera ray that misses: shade_one adds the sky with the throughput (1, 1, 1) it starts with, counts
+// the path and regenerates the next sample, whatever the jitter, the random numbers and the tree. The slot's sum therefore gets exactly
+// those additions here, in sample order, from 0 or from the sum an accumulating frame continues. The fused extend kernels' first launch
+// leaves these slots out (queued_slot), so nothing else of the frame writes their sums. Their rays (one per sample; a pixel's streams
+// share out its spp samples) are counted by the host, which knows the rectangle (frame.cpp finish_frame).
+__global__ void __launch_bounds__(kBlock) k_sky_pixels(DeviceScene sc, PathState ps, FrameParams fp)
+{
+    const uint32_t slot = blockIdx.x * kBlock + threadIdx.x;
+    uint32_t x = 0, y = 0;
+    if (slot >= ps.n_slots || !slot_pixel(slot, fp, x, y) || !sky_pixel(fp, x, y)) return;
+    const uint32_t first = first_sample(slot, fp);
+    if (first >= fp.spp) return;
+    float4 A = fp.accumulate ? ps.acc[slot] : make_float4(0.f, 0.f, 0.f, 0.f);
+    for (uint32_t s = first; s < fp.spp; s += fp.streams) {
+        A.x = fma_(1.0f, sc.sky[0], A.x); A.y = fma_(1.0f, sc.sky[1], A.y); A.z = fma_(1.0f, sc.sky[2], A.z);
+        A.w += 1.0f;
+    }
+    ps.acc[slot] = A;
 }
 
 
@@ -1179,6 +1212,7 @@ k_extend(typename ExtArgsFor<NEE, ENV>::type a)
         if (hd.idle) return;
         qbase = hd.shard * ps.shard_cap;
         if (gid < hd.n) slot = at(ps.q_ext[hd.parity], qbase + gid);
+        if (FUSE != SHADE_NONE) slot = queued_slot(it, slot);
         // FUSE: up to `bounces` path vertices per launch with the path state in registers (a terminated path continues with
         // its stream's next camera ray, so most lanes stay busy); the state goes back to memory once, at the end.
         // Once few paths are left in the shard (the frame's tail) the launch runs them to their end instead (bounded by
@@ -1341,7 +1375,7 @@ k_extend_packed(ExtArgs a)
         if (idle && avail) {
             const uint32_t prefix = lane_prefix(idle);
             const bool pull = !has && prefix < avail;
-            if (pull) { pos = next + prefix; slot = queue[pos]; }
+            if (pull) { pos = next + prefix; slot = queue[pos]; if (FUSE != SHADE_NONE) slot = queued_slot(it, slot); }
             if (pull && slot == kInvalidSlot) { // a hole leaves the lane idle until the next refill
                 if (FUSE != SHADE_NONE && !do_compact) q_next[pos] = kInvalidSlot;
             } else if (pull) {
@@ -1722,6 +1756,12 @@ hipError_t launch_reference_sphere(hipStream_t s, uint32_t w, uint32_t h, float4
 hipError_t launch_generate(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp, uint32_t mode)
 {
     hipLaunchKernelGGL(k_generate, shard_grid(blocks_for(ps.shard_cap), ps.shard_count), dim3(kBlock), 0, s, sc, ps, fp, mode);
+    return hipGetLastError();
+}
+
+hipError_t launch_sky_pixels(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp)
+{
+    hipLaunchKernelGGL(k_sky_pixels, dim3(blocks_for(ps.n_slots)), dim3(kBlock), 0, s, sc, ps, fp);
     return hipGetLastError();
 }
 

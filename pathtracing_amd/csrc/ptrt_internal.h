@@ -158,7 +158,15 @@ struct FrameParams {
     // l = ceil(log2 d)); magic 0 stands for d == 1. div_magic() below makes the pair on the host.
     uint32_t streams_magic, streams_shift, tiles_x_magic, tiles_x_shift;
     uint32_t offset_mod;       // sample_offset % streams
+    // The frame's scene pixels: x in [scene_x0, scene_x1) and y in [scene_y0, scene_y1). No camera ray of a pixel outside can hit anything
+    // (frame.cpp scene_pixels), so its samples are all the sky: k_sky_pixels sums them at frame start and the fused extend kernels'
+    // first launch does not start its slots. (0, ~0, 0, ~0): every pixel may see the scene, nothing is resolved.
+    uint32_t scene_x0, scene_x1, scene_y0, scene_y1;
 };
+inline __host__ __device__ bool sky_pixel(const FrameParams &fp, uint32_t x, uint32_t y)
+{
+    return x < fp.scene_x0 || x >= fp.scene_x1 || y < fp.scene_y0 || y >= fp.scene_y1;
+}
 inline void div_magic(uint32_t d, uint32_t &magic, uint32_t &shift)
 {
     if (d <= 1u) { magic = 0u; shift = 0u; return; }
@@ -177,6 +185,9 @@ hipError_t launch_reference_sphere(hipStream_t s, uint32_t w, uint32_t h, float4
 // launch is a fused one-ray-per-lane or lane-packing kernel, which builds the state in registers; 2: like 0 with the queue dense (only
 // slots that hold a path: frames in which whole sample streams are empty)
 hipError_t launch_generate(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp, uint32_t mode);
+// The frame's sky pixels (FrameParams::scene_x0 ..), once per frame before the first extend launch: every sample of their slots added
+// to the slot's sum as the traced frame would have. Their rays, one per sample, are the host's to count (frame.cpp finish_frame).
+hipError_t launch_sky_pixels(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp);
 // `it` = iteration index of the wavefront loop: queues alternate by it & 1, queue counters rotate by it % 3.
 // kernel: ExtendKernel. fuse: -1 = extend only (k_shade follows); 0 / 2 = the kernel also shades (Lambert-only / all kinds) and
 // queues the next iteration, honouring `compact` like launch_shade. packed_chunk: queue entries per wavefront of EXT_PACKED.

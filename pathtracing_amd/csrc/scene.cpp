@@ -37,7 +37,7 @@ void CommittedTree::adopt(BvhBlob &&blob, uint32_t layout_id)
     }
     slots = std::move(blob.slots); tris = std::move(blob.tris);
     node_bytes = layout_quantised(layout) ? packed.size() : slots.size() * sizeof(BvhSlot);
-    image = Image::fresh; upload_pending = true;
+    image = Image::fresh; upload_pending = true; bound_valid = false;
 }
 
 void CommittedTree::adopt(DeviceBlob4Q &&blob, uint32_t n_records)
@@ -47,7 +47,7 @@ void CommittedTree::adopt(DeviceBlob4Q &&blob, uint32_t n_records)
     max_depth = blob.max_depth; stack_need = blob.stack_need; sah_cost = blob.sah_cost; build_ms = blob.device_ms;
     node_bytes = (uint64_t)n_nodes * layout_node_bytes(layout);
     slots.clear(); packed.clear(); tris.clear();
-    image = Image::absent; upload_pending = false;
+    image = Image::absent; upload_pending = false; bound_valid = false;
 }
 
 pt_status CommittedTree::upload(pt_context *c, CommitClock &clock)
@@ -115,6 +115,40 @@ pt_status CommittedTree::ids(pt_context *c, std::vector<uint32_t> &out) const
     if (image == Image::absent) { if (n_tris) HIP_TRY(c, hipMemcpy2D(out.data(), 4, (const uint8_t *)d_tris.p + 12, 64, 4, n_tris, hipMemcpyDeviceToHost)); } // row 0 .w
     else for (uint32_t j = 0; j < n_tris; ++j) out[j] = tris[j].id;
     return PT_OK;
+}
+
+hipError_t CommittedTree::fetch_root(hipStream_t q)
+{
+    if (!n_nodes) return hipSuccess;
+    if (layout_node_bytes(layout) > sizeof root_bytes) return hipErrorInvalidValue;
+    return hipMemcpyAsync(root_bytes, d_nodes.p, layout_node_bytes(layout), hipMemcpyDeviceToHost, q);
+}
+
+void CommittedTree::root_fetched()
+{
+    bound = Box::empty();
+    if (n_nodes) {
+        uint32_t w[sizeof root_bytes / 4];
+        std::memcpy(w, root_bytes, sizeof root_bytes);
+        for (uint32_t c = 0; c < fan; ++c) {
+            int32_t ref; std::memcpy(&ref, root_bytes + layout_ref_at(layout, c), 4);
+            if (ref == kEmptyRef) continue;
+            Box b;
+            if (layout_quantised(layout)) { // docs/SPEC.md §4.1: fma((float)q, 2^e, origin), the q of child c in byte c of its coordinate group
+                const uint32_t kw = fan / 4u, q0 = 4u + fan;
+                for (uint32_t a = 0; a < 3; ++a) {
+                    const float org = bits_as_float(w[a]), sc = quant_scale_of((w[3] >> (8u * a)) & 0xffu);
+                    const uint32_t ql = (w[q0 + kw * a + c / 4u] >> (8u * (c % 4u))) & 0xffu, qh = (w[q0 + kw * (3u + a) + c / 4u] >> (8u * (c % 4u))) & 0xffu;
+                    b.lo[a] = __builtin_fmaf((float)ql, sc, org); b.hi[a] = __builtin_fmaf((float)qh, sc, org);
+                }
+            } else {
+                BvhSlot sl; std::memcpy(&sl, root_bytes + 32u * c, sizeof sl);
+                for (int a = 0; a < 3; ++a) { b.lo[a] = sl.lo[a]; b.hi[a] = sl.hi[a]; }
+            }
+            bound.grow(b);
+        }
+    }
+    bound_valid = true;
 }
 
 pt_status SceneVertices::host(pt_context *c, const float *&verts9)
@@ -434,6 +468,9 @@ pt_status pt_scene_commit(pt_scene *s, uint32_t bvh_width)
     if ((st = build_tree(s, bvh_width, lbvh, clock)) != PT_OK) return st;
     if (!s->ctx) { s->committed = true; return PT_OK; } // detached scene: host-side blob only
     if ((st = s->tree.upload(s->ctx, clock)) != PT_OK || (st = upload_primitives(s, clock)) != PT_OK || (st = light_table(s, clock)) != PT_OK) return st;
+    // the root's boxes as the device holds them, whichever builder made them (frame.cpp scene_pixels)
+    HIP_TRY(s->ctx, s->tree.fetch_root(context_stream(s->ctx))); HIP_TRY(s->ctx, hipStreamSynchronize(context_stream(s->ctx)));
+    s->tree.root_fetched();
     publish_scene(s);
     return PT_OK;
 }
@@ -536,6 +573,7 @@ static pt_status update_triangles(pt_scene *s, const void *verts9, uint64_t coun
     }
     const uint32_t layout = tree.layout;
     ++s->updates; // from here on the device records are rewritten (counted even if the update then fails)
+    s->tree.bound_stale(); // ... and the root's boxes with them: read back below, behind the last pass
     HIP_TRY(c, launch_refit_tris(q, v, tree.d_tris.p, tree.n_tris, R.tbox.p));
     for (size_t l = 0; l + 1 < R.level_off.size(); ++l)
         HIP_TRY(c, launch_refit_level(q, layout, tree.d_nodes.p, R.list.p + R.level_off[l], R.level_off[l + 1] - R.level_off[l], R.tbox.p, R.nbox.p, R.carea.p));
@@ -544,7 +582,9 @@ static pt_status update_triangles(pt_scene *s, const void *verts9, uint64_t coun
     HIP_TRY(c, hipEventRecord(R.ev[2], q));
     double sah = 0.0;
     HIP_TRY(c, hipMemcpyAsync(&sah, R.sah.p + nb, sizeof sah, hipMemcpyDeviceToHost, q));
+    HIP_TRY(c, s->tree.fetch_root(q));
     HIP_TRY(c, hipStreamSynchronize(q));
+    s->tree.root_fetched();
     float ms = 0.f;
     HIP_TRY(c, hipEventElapsedTime(&ms, R.ev[0], R.ev[2]));
     out.gpu_ms = (double)ms + ms_check;

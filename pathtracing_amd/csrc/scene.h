@@ -41,8 +41,19 @@ public:
     // the refs of every node (n_nodes x fan) and the original triangle id of every blob record
     pt_status refs(pt_context *c, std::vector<int32_t> &out) const;
     pt_status ids(pt_context *c, std::vector<uint32_t> &out) const;
+    // The union of the root node's child boxes as the device copy holds them (decoded as the kernels decode them): every ray that
+    // reaches a triangle has passed the slab test of one of them. Kept current by whoever rewrites the device copy: bound_stale()
+    // before the first write, fetch_root() enqueued behind the last one, root_fetched() once the stream has been waited for. A tree
+    // without nodes has the empty box. False while stale: the caller then assumes nothing about where the triangles are.
+    void bound_stale() { bound_valid = false; }
+    hipError_t fetch_root(hipStream_t q);
+    void root_fetched();
+    bool root_bound(Box &out) const { out = bound; return bound_valid; }
 
 private:
+    Box bound = Box::empty();
+    bool bound_valid = false;
+    uint8_t root_bytes[256] = {};        // node 0 as fetch_root() copied it (the largest node, BVH4 / BVH8Q, has 128 bytes)
     enum class Image { fresh, topology_only, absent };
     mutable Image image = Image::fresh;  // (mutable with the vectors below: pt_scene_bvh_read fills them through a const scene)
     mutable std::vector<BvhSlot> slots;  // f32 layouts: n_nodes * fan
