@@ -120,7 +120,7 @@ struct PathState {           // SoA over slots
 };
 
 // Next-event estimation (PT_FLAG_NEXT_EVENT, docs/SPEC.md §7): the light table of the committed scene (api.cpp build_lights) and the
-// per-slot state a pending shadow ray leaves behind. A separate block behind ExtArgs (kernels.hip ExtArgsNee) rather than fields of
+// per-slot state a pending shadow ray leaves behind. A separate block behind ExtArgs (kernels.hip ExtArgsT) rather than fields of
 // DeviceScene / PathState: those sit in the kernarg segment of every extend kernel, and growing them would move the offsets every other
 // kernel loads its arguments from.
 struct NeeArgs {
@@ -133,7 +133,7 @@ struct NeeArgs {
 };
 
 // The environment map of a scene (pt_scene_set_environment, docs/SPEC.md §11; environment.cpp builds and uploads the table). Like
-// NeeArgs a block of its own behind ExtArgs / ExtArgsNee (kernels.hip ExtArgsEnv), for the same reason; only the environment
+// NeeArgs a block of its own behind ExtArgs / NeeArgs (kernels.hip ExtArgsT), for the same reason; only the environment
 // instantiations of k_extend have it.
 struct EnvArgs {
     const float4 *texels;  // n * n records, row-major: r, g, b, p (the texel's pdf over the unit square of the map, x n * n / 4)
