@@ -152,7 +152,11 @@ typedef struct {
                                [1] iterations that re-packed their queues, [2] path states loaded+stored by the loop
                                (sum over iterations of the paths alive at its start), [3] with PT_FLAG_COUNT_VISITS: wave-level
                                iterations of k_extend's node loop in bits 0-39 (node_visits / (64 * that) = lane utilisation of the
-                               loop), those after the wave's first leaf phase from bit 40 up */
+                               loop), those after the wave's first leaf phase from bit 40 up; without that flag: the pixels the
+                               frame traced, where it resolved the others as sky at its start: 0 = nothing was resolved, else the
+                               rectangle x0 | x1 << 16 | y0 << 32 | y1 << 48 of pixels x0 <= x < x1, y0 <= y < y1 that were still
+                               traced (every pixel outside it was resolved), or all ones where every pixel was resolved (the
+                               rectangle is empty). Images with a side beyond 65535 report 0 */
 } pt_stats;
 
 typedef struct {

@@ -139,6 +139,15 @@ bool scene_pixels(const pt_scene *s, const pt_camera &cam, uint32_t W, uint32_t 
     return true;
 }
 
+// pt_stats.reserved[3] of a frame that resolved sky pixels (include/ptrt.h): the rectangle scene_pixels left to be traced, 16 bits a side;
+// all ones if it holds no pixel (every pixel was resolved); 0 for an image with a side beyond 65535, which has no such code.
+uint64_t scene_pixels_code(const FrameParams &fp)
+{
+    if (fp.scene_x0 >= fp.scene_x1 || fp.scene_y0 >= fp.scene_y1) return ~0ull;
+    if (fp.width > 0xFFFFu || fp.height > 0xFFFFu) return 0ull;
+    return (uint64_t)fp.scene_x0 | (uint64_t)fp.scene_x1 << 16 | (uint64_t)fp.scene_y0 << 32 | (uint64_t)fp.scene_y1 << 48;
+}
+
 struct Frame {                  // a path-traced frame as plan_frame lays it out, and what its loops leave for finish_frame
     uint32_t nranks, streams, pixel_slots, n_slots, shard_cap, samples_per_stream, lag, n_loops, packed_chunk, default_bounces;
     uint32_t forced;            // ExtendKernel a frame flag or pt_tuning.extend_kernel forces (0 = none)
@@ -411,6 +420,7 @@ static pt_status finish_frame(pt_context *c, const pt_render_params *p, const Fr
     // PT_FLAG_COUNT_VISITS + one-ray-per-lane kernel: wave-level node-loop iterations (bits 0-39) and, from bit 40 up, how many
     // of them came after the wave's first leaf phase of the ray (diagnostic for tools/exp_util.py)
     out.reserved[3] = (hc.u64(kCntWaveNodeIters) & 0xFFFFFFFFFFull) | (hc.u64(kCntWaveNodeIters + 2) << 40);
+    if (f.sky) out.reserved[3] = scene_pixels_code(fp); // (a frame that resolves sky pixels never counts: the counters above are 0)
     if (f.count && getenv("PTRT_TRACE")) { // developer aid: where the node loop's lane-slots go (one-ray-per-lane kernel)
         const double slots = 64.0 * (double)hc.u64(kCntWaveNodeIters), v = (double)out.node_visits, lf = (double)hc.u64(kCntIdleLeaf), dn = (double)hc.u64(kCntIdleDone);
         if (slots > 0) fprintf(stderr, "ptrt: node-loop lane-slots %.3g: visiting %.1f %%, waiting at a leaf %.1f %%, ray finished %.1f %%, no ray %.1f %%\n", slots,

@@ -8,22 +8,16 @@ exactly the value of the same frame of an empty scene.
 
 test_sky_frame_needs_no_launches shows that the shortcut acts at all: a frame whose scene is wholly off-screen ends within the host's
 run-ahead instead of after spp / bounces launches."""
-import copy
 import dataclasses
 
 import numpy as np
 import pytest
 
 import env_checker as ec
+from camera_space import SKY, empty_like, scene_of, spheres_only, turned
 from frame_checks import check_nee, run_both
 
 pytestmark = pytest.mark.gpu
-
-SKY = np.float32([0.3, 0.5, 0.9])  # (the generator scenes' own sky is black: a sky pixel would look like an unlit one)
-
-
-def empty_like(P, sd):
-    return P.SceneData(mats=sd.mats, cam=sd.cam, sky=sd.sky)
 
 
 def has_both(P, pto, sd, params, ref):
@@ -41,28 +35,6 @@ def exact(P, pto, r, sd, params, width=0, both=True):
     assert len(bad) == 0, (len(bad), bad[:4].tolist(), img[tuple(bad[0])].tolist(), ref[tuple(bad[0])].tolist())
     assert (st.rays, st.paths) == (ost.rays, ost.paths), (st.rays, ost.rays, st.paths, ost.paths)
     return img, st, ref, ost
-
-
-def scene_of(P, kind, w, h, seed=5):
-    N = P.native
-    return dataclasses.replace(P.make_scene(getattr(N, kind), 3000 if kind == "PT_SCENE_CORNELL_TESS" else 0, seed, w, h), sky=SKY)
-
-
-def turned(sd, yaw, shift=(0.0, 0.0, 0.0)):
-    """sd with its camera turned about the y axis by `yaw` radians and moved by `shift`."""
-    sd = copy.copy(sd)
-    cam = type(sd.cam)()
-    cam.scale, cam.cx, cam.cy, cam.jitter = sd.cam.scale, sd.cam.cx, sd.cam.cy, sd.cam.jitter
-    c, s = np.cos(yaw), np.sin(yaw)
-    for k in range(3):
-        cam.origin[k] = sd.cam.origin[k] + shift[k]
-    for name in ("forward", "right", "up"):
-        v = getattr(sd.cam, name)
-        out = (c * v[0] + s * v[2], v[1], -s * v[0] + c * v[2])
-        for k in range(3):
-            getattr(cam, name)[k] = out[k]
-    sd.cam = cam
-    return sd
 
 
 @pytest.mark.parametrize("kind", ["PT_SCENE_CORNELL", "PT_SCENE_CORNELL_GLASS", "PT_SCENE_CORNELL_TESS"])
@@ -127,14 +99,6 @@ def test_both_kernels(P, pto, renderer):
             for spp, streams in ((7, 4), (3, 8)):
                 _, st, _, _ = exact(P, pto, renderer, sd, P.make_params(w, h, spp=spp, max_depth=8, streams=streams, flags=flag))
                 assert st.reserved[0] == (2 if flag == N.PT_FLAG_EXTEND_PACKED else 1)
-
-
-def spheres_only(P, w, h):
-    """Spheres and no triangle: one in the middle, one across the left border of the image, one across its top, and a small one far
-    away whose test is the least exact."""
-    sd = scene_of(P, "PT_SCENE_CORNELL", w, h)
-    sph = np.array([[0.0, 0.0, 0.0, 0.45], [-1.9, 0.1, -0.5, 0.5], [0.4, 1.35, -0.3, 0.3], [0.9, -0.6, -30.0, 0.12]], np.float32)
-    return P.SceneData(spheres=sph, sph_mat=np.zeros(len(sph), np.uint32), mats=sd.mats, cam=sd.cam, sky=sd.sky)
 
 
 def test_spheres_only(P, pto, renderer):
