@@ -182,7 +182,8 @@ __global__ void __launch_bounds__(kBlock) k_reference_sphere(uint32_t w, uint32_
 
 // ------------------------------------------------------------------------------------------------
 // One inner-node visit for node layout L (PT_BVH_WIDTH_*): fetch the node, slab-test its children against the ray,
-// return (key, ref) sorted by ascending key = (bits(tn) & ~3) | slot; children that are missed/empty get key ~0.
+// return (key, ref) in slot order, key = (bits(tn) & ~3) | slot (SLOT: what ORDER_SPEC sorts by) or plain bits(tn); children that
+// are missed/empty get key ~0. visit_node below puts them into the node's VisitOrder.
 // L = 2 / 4 : N slots of {lo.xyz|ref, hi.xyz|0}  -> 2N 16-byte loads per lane
 // L = 4Q    : 64-byte node {origin|exps, refs, qlo x/y/z + qhi x, qhi y/z}, boxes decoded as fma(q, 2^e, origin)
 //             -> 4 loads per lane: half the bytes and half the (fully divergent) memory instructions per visit.
@@ -196,7 +197,7 @@ PT_DEV constexpr int node_rows() { return (L == PT_BVH_WIDTH_4 || L == PT_BVH_WI
 template <int L>
 PT_DEV constexpr int fanout() { return L == PT_BVH_WIDTH_2 ? 2 : (L == PT_BVH_WIDTH_8Q || L == PT_BVH_WIDTH_8O) ? 8 : 4; }
 
-template <int L>
+template <int L, bool SLOT>
 PT_DEV void visit_node_keys(const float4 *__restrict__ nd, float4 r0, float4 r1, float4 r2, float4 r3, const RaySetup &rs, float t_best,
                             uint32_t (&key)[fanout<L>()], int32_t (&ref)[fanout<L>()])
 {
@@ -269,7 +270,7 @@ PT_DEV void visit_node_keys(const float4 *__restrict__ nd, float4 r0, float4 r1,
             const float tn = fmax_(fmax_(tnk[0], tnk[1]), fmax_(tnk[2], 0.0f));
             const float tf = fmin_(fmin_(tfk[0], tfk[1]), fmin_(tfk[2], t_best)) * 1.0000004f;
             const bool hb = tn <= tf && ref[c] != PT_BVH_EMPTY;
-            key[c] = hb ? ((__float_as_uint(tn) & ~3u) | (uint32_t)c) : 0xFFFFFFFFu;
+            key[c] = hb ? (SLOT ? ((__float_as_uint(tn) & ~3u) | (uint32_t)c) : __float_as_uint(tn)) : 0xFFFFFFFFu;
         }
     } else {
         float4 r[2 * N];
@@ -281,7 +282,7 @@ PT_DEV void visit_node_keys(const float4 *__restrict__ nd, float4 r0, float4 r1,
             float tn;
             ref[c] = __float_as_int(r[2 * c].w);
             const bool hb = box_test(r[2 * c], r[2 * c + 1], rs, t_best, tn) && ref[c] != PT_BVH_EMPTY;
-            key[c] = hb ? ((__float_as_uint(tn) & ~3u) | (uint32_t)c) : 0xFFFFFFFFu;
+            key[c] = hb ? (SLOT ? ((__float_as_uint(tn) & ~3u) | (uint32_t)c) : __float_as_uint(tn)) : 0xFFFFFFFFu;
         }
     }
 }
@@ -336,7 +337,7 @@ PT_DEV void visit_node_oct8(const float4 *__restrict__ nd, float4 r0, float4 r1,
     hits = m;
 }
 
-// Sorting network over (key, ref), ascending key, in two halves: after sort_head the nearest hit child is in slot 0 (so its
+// ORDER_SPEC's sorting network over (key, ref), ascending key, in two halves: after sort_head the nearest hit child is in slot 0 (so its
 // fetch can be issued), sort_tail finishes the order of the others (which only the pushes need).
 template <int N>
 PT_DEV void cswap(uint32_t (&key)[N], int32_t (&ref)[N], int a, int b)
@@ -374,12 +375,27 @@ PT_DEV void sort_tail(uint32_t (&key)[N], int32_t (&ref)[N])
 {
     if constexpr (N == 4) { cswap(key, ref, 1, 2); } // (0,1)(2,3) | (0,2)(1,3) | (1,2): the five comparators, in three rounds
 }
-template <int L>
+// The order in which a traversal visits the hit children of a node (docs/SPEC.md §4.1). The hit does not depend on it (§4), the visit
+// counters do: the counting kernels keep the spec's order, the others enter the nearest child first and leave the rest unsorted.
+//   ORDER_SPEC    : ascending key = (bits(tn) & ~3) | slot: the five-comparator network for four children
+//   ORDER_NEAREST : three comparators bring the smallest key to slot 0, the others are pushed as they fall; key = bits(tn), no slot bits
+//                   (which of two equally near children is entered first changes no hit)
+// Four children only (layouts 4 and 4Q). With two the one comparator is the whole sort. With eight (8Q) the seven-comparator tournament
+// spills registers in one non-counting kernel or another in every form tried ("Nearest child first"): it keeps ORDER_SPEC.
+// Layout 8O orders its children without keys, whatever the VisitOrder.
+enum VisitOrder { ORDER_SPEC = 0, ORDER_NEAREST = 1 };
+template <int L, bool COUNT>
+PT_DEV constexpr VisitOrder visit_order() { return (!COUNT && fanout<L>() == 4) ? ORDER_NEAREST : ORDER_SPEC; }
+
+// ORDER_NEAREST's tournament for four children: the smallest key to slot 0, the others as they fall.
+PT_DEV void sort_nearest(uint32_t (&key)[4], int32_t (&ref)[4]) { cswap2(key, ref, 0, 1, 2, 3); cswap(key, ref, 0, 2); }
+template <int L, VisitOrder ORD>
 PT_DEV void visit_node(const float4 *__restrict__ nd, float4 r0, float4 r1, float4 r2, float4 r3, const RaySetup &rs, float t_best,
                        uint32_t (&key)[fanout<L>()], int32_t (&ref)[fanout<L>()])
 {
-    visit_node_keys<L>(nd, r0, r1, r2, r3, rs, t_best, key, ref);
-    sort_head(key, ref); sort_tail(key, ref);
+    visit_node_keys<L, ORD == ORDER_SPEC>(nd, r0, r1, r2, r3, rs, t_best, key, ref);
+    if constexpr (ORD == ORDER_SPEC) { sort_head(key, ref); sort_tail(key, ref); }
+    else sort_nearest(key, ref);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -937,7 +953,7 @@ PT_DEV int32_t pop_after_leaf(const StackCtx &k, uint32_t &sp)
 // stack top) becomes `cur`. Stack fast path: while every calling lane still has room for a whole node's pushes in its LDS column
 // (the common case), a push is an unconditional LDS store plus a predicated increment and a pop is a plain LDS load — no
 // LDS-or-spill branch per push.
-template <int L>
+template <int L, VisitOrder ORD>
 PT_DEV void node_visit_rows(const float4 *__restrict__ base, float4 r0, float4 r1, float4 r2, float4 r3, const StackCtx &k, const RaySetup &rs,
                             float t_best, int32_t &cur, uint32_t &sp);
 // Record `i` of an array of ROWS-row records (nodes, triangle records) by a 32-bit byte offset, as at() does for the slot arrays: an SGPR
@@ -948,14 +964,14 @@ PT_DEV const float4 *record(const float4 *base, uint32_t i)
 {
     return reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(base) + (size_t)(i * (uint32_t)(ROWS * 16)));
 }
-template <int L>
+template <int L, VisitOrder ORD>
 PT_DEV void node_step(const float4 *__restrict__ nodes, const StackCtx &k, const RaySetup &rs, float t_best, int32_t &cur, uint32_t &sp)
 {
     const float4 *base = record<node_rows<L>()>(nodes, (uint32_t)cur);
-    node_visit_rows<L>(base, base[0], base[1], base[2], base[3], k, rs, t_best, cur, sp);
+    node_visit_rows<L, ORD>(base, base[0], base[1], base[2], base[3], k, rs, t_best, cur, sp);
 }
 // The visit of the node whose first four rows are r0..r3 (`base`: where layouts with more rows find the rest).
-template <int L>
+template <int L, VisitOrder ORD>
 PT_DEV void node_visit_rows(const float4 *__restrict__ base, float4 r0, float4 r1, float4 r2, float4 r3, const StackCtx &k, const RaySetup &rs,
                             float t_best, int32_t &cur, uint32_t &sp)
 {
@@ -985,7 +1001,8 @@ PT_DEV void node_visit_rows(const float4 *__restrict__ base, float4 r0, float4 r
     }
     uint32_t key[N];
     int32_t ref[N];
-    visit_node<L>(base, r0, r1, r2, r3, rs, t_best, key, ref); // keys sorted ascending, misses = 0xFFFFFFFF at the end
+    visit_node<L, ORD>(base, r0, r1, r2, r3, rs, t_best, key, ref);
+    // the nearest hit child in slot 0; ORDER_SPEC: all sorted ascending, misses = 0xFFFFFFFF at the end; ORDER_NEAREST: hits and misses mixed
     if (!deep) {
 #pragma unroll
         for (int i = N - 1; i >= 1; --i) { // farthest first, nearest stays in `cur`
@@ -1115,6 +1132,7 @@ PT_DEV void flush_visit_counters(const PathState &ps, const VisitCounts &v)
 template <int L, bool COUNT, bool DIAG, bool ANY>
 PT_DEV Hit trace_ray(const HotScene &g, const StackCtx &stk, V3 o, V3 d, Hit h, VisitCounts &vc, int32_t *s_state)
 {
+    constexpr VisitOrder ORD = visit_order<L, COUNT>(); // the spec's order where visits are counted, nearest first elsewhere
     { const uint32_t ns = spheres_test(g, o, d, h); if (COUNT) vc.sph += ns; }
 
     const RaySetup rs = ray_setup(o, d);
@@ -1128,14 +1146,15 @@ PT_DEV Hit trace_ray(const HotScene &g, const StackCtx &stk, V3 o, V3 d, Hit h, 
         if (COUNT) vc.nodes++;
         if (DIAG && lane_id() == (uint32_t)(__ffsll((long long)__ballot(1)) - 1)) vc.wave_iters++;
         const uniform_f4 root = as_uniform(g.nodes);
-        node_visit_rows<L>(g.nodes, uniform_load(root, 0), uniform_load(root, 1), uniform_load(root, 2), uniform_load(root, 3), stk, rs, h.t, cur, sp);
+        node_visit_rows<L, ORD>(g.nodes, uniform_load(root, 0), uniform_load(root, 1), uniform_load(root, 2), uniform_load(root, 3), stk, rs, h.t, cur, sp);
         if (DIAG) s_state[stk.tid & 63u] = cur;
     }
 
     // while-while: a lane that reaches a leaf waits at the reconvergence point of the node loop until every lane of
-    // the wave is at a leaf or done; then the leaves are tested together. Each lane still makes exactly the visits,
-    // in exactly the order, of docs/SPEC.md §4.1 (only the interleaving across lanes changes), so hits and visit
-    // counters are the oracle's. Why: with one loop for both kinds of step the wave issued the ~160-instruction node
+    // the wave is at a leaf or done; then the leaves are tested together. Only the interleaving across lanes changes:
+    // a lane makes the visits its VisitOrder prescribes, in that order. Under COUNT that is the order of docs/SPEC.md
+    // §4.1, so the visit counters are the oracle's; the hit is the oracle's under either order (§4).
+    // Why: with one loop for both kinds of step the wave issued the ~160-instruction node
     // code AND the ~125-instruction triangle code in practically every iteration, the latter for ~1 lane in 8; the
     // kernel is VALU-issue bound (rocprofv3: 34 % of wave time waits for an issue slot, 43 % of VALU lanes active).
     bool late_cycle = false; // (DIAG) set once this wave has run a leaf phase for the current rays
@@ -1151,7 +1170,7 @@ PT_DEV Hit trace_ray(const HotScene &g, const StackCtx &stk, V3 o, V3 d, Hit h, 
                 for (uint32_t l = 0; l < 64u; ++l) { const int32_t c2 = s_state[l]; n_leaf += c2 < 0 ? 1u : 0u; n_done += c2 == PT_BVH_EMPTY ? 1u : 0u; }
                 vc.idle_leaf += n_leaf; vc.idle_done += n_done;
             }
-            node_step<L>(g.nodes, stk, rs, h.t, cur, sp);
+            node_step<L, ORD>(g.nodes, stk, rs, h.t, cur, sp);
             if (DIAG) s_state[stk.tid & 63u] = cur;
         }
         if (cur == PT_BVH_EMPTY) break;
@@ -1249,8 +1268,9 @@ k_extend(ExtArgsT<NEE, ENV> args)
 }
 
 // ------------------------------------------------------------------------------------------------
-// k_extend_packed: same per-ray work and the same per-ray traversal order as k_extend (so hits AND visit counters
-// are identical), but a wavefront owns `chunk` consecutive queue entries instead of 64 and keeps its lanes packed:
+// k_extend_packed: same per-ray work as k_extend, in the spec's per-ray traversal order whether it counts or not (hits are
+// k_extend's, visit counters those of the counting k_extend; on the soup ORDER_NEAREST's extra visits cost this kernel more than
+// the comparators it saves), but a wavefront owns `chunk` consecutive queue entries instead of 64 and keeps its lanes packed:
 // whenever >= kRefillIdle lanes have finished their ray (ballot + popcount), the finished lanes retire (hit record,
 // bucket push) and idle lanes pull the next entries of the chunk by mbcnt prefix. With one ray per lane a wave runs
 // as long as its slowest ray (measured 19 % lane utilisation on the 1M-triangle soup); with refill the wave's time
@@ -1371,7 +1391,7 @@ k_extend_packed(ExtArgs a)
                 const float4 r0 = base[0], r1 = base[1], r2 = base[2], r3 = base[3];
                 if (++steps > (1u << 22)) { atomicOr(&cold().ps.counters[kCntError], 2u); cur = PT_BVH_EMPTY; }
                 else if (inner) {
-                    node_visit_rows<L>(base, r0, r1, r2, r3, stk, rs, h.t, cur, sp);
+                    node_visit_rows<L, ORDER_SPEC>(base, r0, r1, r2, r3, stk, rs, h.t, cur, sp);
                     if (COUNT) vc.nodes++;
                 } else { // one triangle per step: the wave may refill between the triangles of a leaf
                     tri_test(r0, r1, r2, first, o, d, h);
@@ -1519,7 +1539,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PT_POOL
                     if (++steps > (1u << 22)) { atomicOr(&cold().ps.counters[kCntError], 2u); cur = PT_BVH_EMPTY; }
                     else {
                         if (COUNT) { vc.nodes++; if (lane == (uint32_t)(__ffsll((long long)m_n) - 1)) vc.wave_iters++; }
-                        node_step<L>(nodes, stk, rs, h.t, cur, sp);
+                        node_step<L, ORDER_SPEC>(nodes, stk, rs, h.t, cur, sp);
                     }
                 }
             }
