@@ -83,6 +83,17 @@ public:
         check(pt_denoised_read(ctx_, px.data(), px.size()), ctx_);
         return px;
     }
+    // docs/SPEC.md §12: ambient occlusion, sky irradiance and the bent normal at surface points of the current scene. points: 8 floats per
+    // point {p.xyz, 0, n.xyz, 0}; returns 8 floats per point {E.rgb, visibility, bent.xyz, 0}. gp.flags is set for host arrays here.
+    std::vector<float> Gather(const std::vector<float> &points, pt_gather_params gp = {}, pt_stats *stats = nullptr)
+    {
+        if (points.size() % 8) throw Error(PT_ERR_INVALID_ARGUMENT, "Gather: 8 floats per point");
+        std::vector<float> rows(points.size());
+        if (points.empty()) return rows; // (an empty vector has no storage to point at)
+        gp.flags |= PT_GATHER_HOST_MEMORY;
+        check(pt_gather(ctx_, scene_, points.data(), rows.data(), points.size() / 8, &gp, stats), ctx_);
+        return rows;
+    }
     void SetCamera(const pt_camera &cam) { check(pt_scene_set_camera(scene_, &cam), ctx_); } // no new commit needed
     // docs/SPEC.md §11: n x n texels of linear RGB, octahedral layout; an empty vector with n = 0 removes the map. No new commit needed.
     void set_environment(const std::vector<float> &rgb, uint32_t n)

@@ -90,6 +90,22 @@ public unsafe class HipRenderer : IDisposable
         set { Ptrt.Check(Ptrt.pt_context_set_tuning(_ctx, &value), _ctx); }
     }
 
+    // Hemisphere gathers on the current scene (docs/SPEC.md §12): ambient occlusion, sky irradiance and the bent normal of a bake. points: 8
+    // floats per point {p.xyz, 0, n.xyz, 0}; returns 8 floats per point {E.rgb, visibility, bent.xyz, 0} (visibility -1: an invalid point).
+    // samples cosine-weighted occlusion rays per point are made, traced and summed on the device. Host arrays: the library stages them.
+    public float[] Gather(float[] points, uint samples = 64, uint seed = 0, float maxDistance = 0f, float rayEps = 1e-3f,
+                          uint sampleOffset = 0, uint pointOffset = 0)
+    {
+        if (points.Length % 8 != 0) throw new ArgumentException("points: 8 floats per point");
+        var rows = new float[points.Length];
+        var gp = new PtGatherParams { samples = samples, seed = seed, sample_offset = sampleOffset, point_offset = pointOffset,
+                                      max_distance = maxDistance, ray_eps = rayEps, flags = (uint)PtGatherFlags.HostMemory };
+        PtStats st;
+        fixed (float* p = points) fixed (float* o = rows)
+            Ptrt.Check(Ptrt.pt_gather(_ctx, _scene, p, o, (ulong)(points.Length / 8), &gp, &st), _ctx);
+        return rows;
+    }
+
     // Ray queries on the current scene (docs/SPEC.md §4.2). rays: 8 floats per ray {o.xyz, tmax, d.xyz, 0} (|d| = 1 for spheres);
     // returns 4 floats per ray {t, prim id bits, u, v}, a miss = {+inf, 0xFFFFFFFF bits, 0, 0}. Host arrays: the library stages them.
     public float[] TraceRays(float[] rays, bool occlusion = false)

@@ -34,7 +34,8 @@ extern "C" {
  * PT_DENOISE_*, pt_denoised_read / pt_denoised_device_ptr and pt_guides_read, then pt_denoise_temporal, pt_temporal_params, PT_TEMPORAL_*,
  * pt_temporal_read / pt_temporal_device_ptr / pt_temporal_history_read, then pt_display, pt_display_params, pt_display_info, PT_DISPLAY_*,
  * PT_TONE_*, pt_display_read / pt_display_device_ptr / pt_display_info_read / pt_display_histogram_read, then PT_TEMPORAL_MOTION, then
- * pt_scene_set_environment, pt_environment_info and pt_scene_environment_info / pt_scene_environment_read (additions only: no struct or
+ * pt_scene_set_environment, pt_environment_info and pt_scene_environment_info / pt_scene_environment_read, then pt_gather, pt_gather_params and
+ * PT_GATHER_HOST_MEMORY (additions only: no struct or
  * existing signature changed).
  * Hosts compare pt_abi_version() with the header they were built against. */
 #define PTRT_ABI_VERSION 2
@@ -262,6 +263,41 @@ enum {
  * Domain (docs/SPEC.md §4): origins and hit distances within 2^±30 as for the scene; outside it the hit is specified but not the geometric one. */
 pt_status pt_trace_rays(pt_context *ctx, const pt_scene *scene, const void *rays, void *hits, uint64_t n_rays,
                         uint32_t flags, pt_stats *stats);
+
+/* ---- hemisphere gathers (docs/SPEC.md §12): ambient occlusion, sky irradiance and the bent normal at caller points — what a lightmap or
+ *      probe bake wants from every texel. The K cosine-weighted rays of a point are made, traced (the occlusion query of §4.2) and summed
+ *      on the device: neither a ray nor a hit record passes through memory, 32 B in and 32 B out per point whatever K is. */
+enum { PT_GATHER_HOST_MEMORY = 1u };   /* points / out are host pointers, staged by the library */
+typedef struct pt_gather_params {
+    uint32_t samples;       /* K directions per point, 1..4096; 0 = 64 */
+    uint32_t seed;
+    uint32_t sample_offset; /* index of the first sample: calls over [a,b) and [b,c) merge to [a,c) */
+    uint32_t point_offset;  /* added to a point's index in the RNG key: a bake split over calls or GPUs gives the same numbers */
+    float max_distance;     /* occluders farther than this do not count; 0 = unbounded; else finite and > 0 */
+    float ray_eps;          /* origin offset along the unit normal; finite and >= 0, taken literally */
+    uint32_t flags;
+    uint32_t pad;
+} pt_gather_params;         /* 32 B */
+/* Gather at n_points caller points of a committed scene. Synchronous on the context's stream, like pt_render.
+ * points: n_points records of 32 B  {p.x, p.y, p.z, 0, n.x, n.y, n.z, 0}             (f32, 16-B aligned; 4-B with PT_GATHER_HOST_MEMORY)
+ * out:    n_points records of 32 B  {E.r, E.g, E.b, visibility, bent.x, bent.y, bent.z, 0}                           (likewise)
+ * Sample k of point i leaves p + ray_eps * normalize(n) in the Lambert direction d of the random numbers keyed by (seed, point_offset + i,
+ * sample_offset + k); it is visible (V = 1) unless the occlusion query finds a hit within max_distance. visibility = sum V / K (the count
+ * is exact: round(visibility * K) recovers it), bent = sum V d / K (unnormalised: its length is the share of unoccluded cosine-weighted
+ * solid angle around its direction), E = sum V L(d) / K with L the scene's environment map if it has one, else its sky; the pdf is
+ * cos / pi, so pi * E is the irradiance the sky sends to the point. The sums have one fixed order (§12): a call gives the same bits every
+ * time and on every BVH layout. A point with a non-finite p or n, or with dot(n, n) zero or not finite, is invalid: it traces nothing
+ * and gets {0, 0, 0, -1, 0, 0, 0, 0}. No output is ever NaN or infinite (a mean beyond the largest float is stored as that float).
+ * Device arrays must lie on ctx's device inside one allocation. Checked in this order:
+ *   gp NULL, unknown flag bits, samples > 4096, max_distance negative, NaN or infinite, ray_eps likewise  -> PT_ERR_INVALID_ARGUMENT
+ *   ctx, scene, points or out NULL; misalignment; a detached scene or a scene of another context         -> PT_ERR_INVALID_ARGUMENT
+ *   scene not committed                                                                                   -> PT_ERR_NOT_COMMITTED
+ *   n_points >= 2^32                                                                                      -> PT_ERR_INVALID_ARGUMENT
+ * n_points == 0 is PT_OK. stats (may be NULL): paths = n_points, rays = K * (valid points), gpu_ms (the gather kernels, staging copies
+ * excluded), everything else 0. A gather touches no state of pt_render, pt_denoise* or pt_display and never runs the extend-kernel
+ * probe. A failed call drains the context's stream. */
+pt_status pt_gather(pt_context *ctx, const pt_scene *scene, const void *points, void *out, uint64_t n_points,
+                    const pt_gather_params *gp, pt_stats *stats);
 
 /* ---- geometry updates (docs/SPEC.md §4.3): move a committed scene's triangles or spheres without a new commit — what a host's
  *      per-frame Update hook (Renderer.Update, Renderer.cs:86-89) uses to animate. The BVH keeps its topology and leaf assignment;

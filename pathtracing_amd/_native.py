@@ -44,6 +44,7 @@ PT_BVH_WIDTH_2, PT_BVH_WIDTH_4, PT_BVH_WIDTH_4Q, PT_BVH_WIDTH_8Q, PT_BVH_WIDTH_8
 PT_COMM_FORCE_RCCL, PT_COMM_COPY_EXCHANGE = 1, 2
 PT_TRACE_OCCLUSION, PT_TRACE_COUNT_VISITS, PT_TRACE_HOST_MEMORY = 1, 2, 4
 PT_UPDATE_HOST_MEMORY = 1
+PT_GATHER_HOST_MEMORY = 1
 PT_DENOISE_GUIDES_ONLY, PT_DENOISE_NO_EDGE_STOPS = 1, 2
 PT_TEMPORAL_RESET, PT_TEMPORAL_MATCH_IDS = 1, 2
 PT_TEMPORAL_MOTION = 8  # (bit 4 is unassigned)
@@ -121,6 +122,11 @@ class pt_environment_info(C.Structure):
     _fields_ = [("n", C.c_uint32), ("lit", C.c_uint32), ("device_bytes", C.c_uint64), ("total", C.c_double)]
 
 
+class pt_gather_params(C.Structure):
+    _fields_ = [("samples", C.c_uint32), ("seed", C.c_uint32), ("sample_offset", C.c_uint32), ("point_offset", C.c_uint32),
+                ("max_distance", C.c_float), ("ray_eps", C.c_float), ("flags", C.c_uint32), ("pad", C.c_uint32)]
+
+
 class pt_scene_counts(C.Structure):
     _fields_ = [("n_tris", C.c_uint64), ("n_spheres", C.c_uint64), ("n_mats", C.c_uint64)]
 
@@ -128,6 +134,7 @@ class pt_scene_counts(C.Structure):
 assert C.sizeof(pt_material) == 48 and C.sizeof(pt_camera) == 64 and C.sizeof(pt_render_params) == 64 and C.sizeof(pt_tuning) == 40
 assert C.sizeof(pt_denoise_params) == 32 and C.sizeof(pt_temporal_params) == 32
 assert C.sizeof(pt_display_params) == 40 and C.sizeof(pt_display_info) == 32 and C.sizeof(pt_environment_info) == 24
+assert C.sizeof(pt_gather_params) == 32
 
 _vp, _u32, _u64, _st = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int32
 _P = C.POINTER
@@ -155,6 +162,7 @@ SYMBOLS = {
     "pt_scene_bvh_read": (_st, [_vp, _vp, _u64, _vp, _u64]),
     "pt_render": (_st, [_vp, _vp, _P(pt_render_params), _P(pt_stats)]),
     "pt_trace_rays": (_st, [_vp, _vp, _vp, _vp, _u64, _u32, _P(pt_stats)]),
+    "pt_gather": (_st, [_vp, _vp, _vp, _vp, _u64, _P(pt_gather_params), _P(pt_stats)]),
     "pt_scene_update_triangles": (_st, [_vp, _vp, _u64, _u32, _P(pt_stats)]),
     "pt_scene_update_spheres": (_st, [_vp, _vp, _u64]),
     "pt_denoise": (_st, [_vp, _vp, _P(pt_denoise_params), _P(pt_stats)]),

@@ -15,6 +15,8 @@
 //                        shades the metal / dielectric hits that QUEUE deferred to per-kind bucket queues
 //   k_trace<L,MODE>    : pt_trace_rays: caller rays -> closest hit (or any hit: occlusion), one ray per lane through trace_ray,
 //                        the function k_extend traces its rays with; no path state
+//   k_gather<L,ENV>    : pt_gather: caller points -> K cosine-weighted occlusion rays each, made and traced (trace_ray's any-hit) by a
+//                        group of lanes and reduced in the wave to visibility, sky irradiance and bent normal
 //   k_reduce_streams   : fixed-order sum of a pixel's stream partials
 //   k_assemble         : tile-major slots (of 1..R ranks) -> row-major float4 + RGBA8 frame
 //
@@ -1638,6 +1640,106 @@ k_trace(TraceArgs a)
 }
 
 // ------------------------------------------------------------------------------------------------
+// k_gather<L, ENV>: pt_gather (docs/SPEC.md §12). Caller points {p.xyz | 0, n.xyz | 0} -> {E.rgb | visibility, bent.xyz | 0}: K
+// cosine-weighted occlusion rays per point, generated here (path_key / u01 / lambert_vec), traced with trace_ray's ANY and reduced in
+// the wave, so that neither a ray nor a hit record ever exists in memory.
+// A group of G = 2^gshift lanes (G = min(64, the power of two >= K)) owns one point, a wave 64 / G points; lane g of the group takes the
+// samples g, g + G, ... in increasing order. Grid-stride over waves' point blocks like k_trace (the bound is wave-uniform, the lane keeps
+// its LDS stack column and its overflow column for all of its rays). Lanes of an invalid point, of a point beyond n and lanes g >= K
+// trace nothing but stay in the loop: the reduction below runs in uniform control flow.
+// §12's summation order: a lane adds its visible samples' terms to 0 in increasing k, then log2 G butterfly steps s = s + s[lane ^ m],
+// m = G/2 .. 1 (f32 addition commutes, so every lane of the group ends with the same bits); the count is an integer. Lane 0 of the group
+// divides by K and stores the two rows.
+// ENV: the radiance of a direction is the environment map's texel (§11 encode) instead of the scene's sky.
+// The kernel counts the invalid points it met into the low word of kCntNodes (one atomic each: they are the exception).
+struct GatherArgs : ExtArgs {
+    const float4 *points; // two rows per point
+    float4 *out;          // two rows per point
+    uint32_t n, samples, gshift, seed, point_offset, sample_offset;
+    float tmax, ray_eps;  // tmax: max_distance, +inf for 0
+};
+template <bool ENV> struct GatherArgsT { GatherArgs x; };
+template <> struct GatherArgsT<true> { GatherArgs x; EnvArgs env; };
+
+template <int L, bool ENV>
+__global__ void __launch_bounds__(kExtBlock) __attribute__((amdgpu_waves_per_eu(PT_EXT_WAVES(L, SHADE_NONE), PT_EXT_WAVES(L, SHADE_NONE))))
+k_gather(GatherArgsT<ENV> args)
+{
+    static_assert(kExtBlock == 64u, "a group of lanes lives in one wave");
+    const GatherArgs &a = args.x;
+    const HotScene g = hot_scene(a.sc);
+    const uint32_t n = a.n, K = a.samples, gshift = a.gshift;
+    const float4 *__restrict__ points = a.points;
+    float4 *__restrict__ out = a.out;
+    __shared__ int32_t s_stack[kStackLds * kExtBlock];
+    const uint32_t tid = threadIdx.x;
+    const StackCtx stk{ s_stack, kExtBlock, tid, blockIdx.x * kExtBlock + tid };
+    const uint32_t per_wave = kExtBlock >> gshift, G = 1u << gshift, lane = tid & (G - 1u);
+    const uint32_t seed_hashed = pcg(a.seed); // wave-uniform
+    // A lane's six float sums and its count live in its LDS column (7 rows behind the stack's 12: 4864 B per wave, 8 waves per SIMD still
+    // fit the CU's 160 KB) and are touched after a ray only: traversal keeps k_trace's register budget.
+    __shared__ uint32_t s_sum[7 * kExtBlock];
+    auto sum_add = [&](uint32_t j, float x) { s_sum[j * kExtBlock + tid] = __float_as_uint(__uint_as_float(s_sum[j * kExtBlock + tid]) + x); };
+    auto sum_of = [&](uint32_t j) { return __uint_as_float(s_sum[j * kExtBlock + tid]); };
+    VisitCounts vc;
+    for (uint32_t base = blockIdx.x * per_wave; base < n; base += gridDim.x * per_wave) { // wave-uniform; n <= 2^31 (query.cpp): no wrap
+        const uint32_t i = base + (tid >> gshift);
+        bool valid = false;
+        if (i < n) {
+            const V3 p = xyz(points[2u * (size_t)i]), nv = xyz(points[2u * (size_t)i + 1u]);
+            const float n2 = dot(nv, nv);
+            // finite p and n, and a dot(n, n) that is neither 0 nor infinite (x - x is 0 exactly for a finite x, NaN otherwise)
+            valid = (p.x - p.x) == 0.0f && (p.y - p.y) == 0.0f && (p.z - p.z) == 0.0f && (n2 - n2) == 0.0f && n2 > 0.0f;
+            if (!valid && lane == 0u) atomicAdd(&cold().ps.counters[kCntNodes], 1u);
+        }
+        for (uint32_t j = 0; j < 7u; ++j) s_sum[j * kExtBlock + tid] = 0u;
+        if (valid)
+            for (uint32_t k = lane; k < K; k += G) {
+                // The point is read again for every sample (its line is in the cache) behind an index the compiler cannot see through:
+                // neither the normal nor the sample's key stays in registers across the traversal. (Keeping the first read's normal for
+                // the first sample and reading again only for the later ones spills 1-3 VGPRs in every layout.)
+                uint32_t ii = i;
+                asm volatile("" : "+v"(ii));
+                const V3 nn = normalize(xyz(points[2u * (size_t)ii + 1u]));
+                const V3 o = madd(a.ray_eps, nn, xyz(points[2u * (size_t)ii]));
+                const uint32_t key = path_key(seed_hashed, a.point_offset + ii, a.sample_offset + k);
+                const V3 d = normalize(lambert_vec(nn, u01(key, 0u), u01(key, 1u)));
+                asm volatile("" ::: "memory");
+                const Hit h = trace_ray<L, false, false, true>(g, stk, o, d, Hit{ a.tmax, PT_MISS, PT_MISS }, vc, nullptr);
+                asm volatile("" ::: "memory");
+                if (h.id == PT_MISS) {
+                    V3 e;
+                    if constexpr (ENV) {
+                        const EnvArgs &ea = reinterpret_cast<const GatherArgsT<true> &>(kernargs<false, false>()).env; // read where it is used, like cold()
+                        float s;
+                        e = xyz(ea.texels[env_texel(ea, d, s)]);
+                    } else {
+                        const DeviceScene &sc = cold().sc;
+                        e = v3(sc.sky[0], sc.sky[1], sc.sky[2]);
+                    }
+                    sum_add(0u, e.x); sum_add(1u, e.y); sum_add(2u, e.z);
+                    sum_add(3u, d.x); sum_add(4u, d.y); sum_add(5u, d.z);
+                    s_sum[6u * kExtBlock + tid] += 1u;
+                }
+            }
+        asm volatile("" ::: "memory");
+        float ex = sum_of(0u), ey = sum_of(1u), ez = sum_of(2u), bx = sum_of(3u), by = sum_of(4u), bz = sum_of(5u);
+        uint32_t cnt = s_sum[6u * kExtBlock + tid];
+        for (uint32_t m = G >> 1; m; m >>= 1) { // the butterfly stays inside the group: m < G
+            cnt += (uint32_t)__shfl_xor((int)cnt, (int)m, 64);
+            ex = ex + __shfl_xor(ex, (int)m, 64); ey = ey + __shfl_xor(ey, (int)m, 64); ez = ez + __shfl_xor(ez, (int)m, 64);
+            bx = bx + __shfl_xor(bx, (int)m, 64); by = by + __shfl_xor(by, (int)m, 64); bz = bz + __shfl_xor(bz, (int)m, 64);
+        }
+        if (lane == 0u && i < n) {
+            const float fk = (float)K, big = 3.40282347e38f; // a sum that overflowed is stored as the largest finite float
+            auto mean = [&](float s) { return fmin_(fmax_(s / fk, -big), big); };
+            out[2u * (size_t)i] = valid ? make_float4(mean(ex), mean(ey), mean(ez), (float)cnt / fk) : make_float4(0.f, 0.f, 0.f, -1.0f);
+            out[2u * (size_t)i + 1u] = valid ? make_float4(bx / fk, by / fk, bz / fk, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // k_shade<SHADE_QUEUE>   : walks the extend queue of this iteration in the SAME order k_extend did, so ray/throughput/hit
 //                          reads are the coalesced, L2-warm lines k_extend just touched. Misses and Lambert hits are shaded
 //                          in place; specular kinds (metal, dielectric) are deferred to per-kind bucket queues.
@@ -1829,6 +1931,36 @@ hipError_t launch_trace(hipStream_t s, const DeviceScene &sc, const PathState &p
         if (occlusion) hipLaunchKernelGGL((k_trace<L, TRACE_OCCLUSION>), grid, dim3(kExtBlock), 0, s, a);
         else if (count) hipLaunchKernelGGL((k_trace<L, TRACE_COUNT>), grid, dim3(kExtBlock), 0, s, a);
         else hipLaunchKernelGGL((k_trace<L, TRACE_CLOSEST>), grid, dim3(kExtBlock), 0, s, a);
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
+}
+
+uint32_t gather_group_shift(uint32_t samples)
+{
+    uint32_t sh = 0;
+    while (sh < 6u && (1u << sh) < samples) ++sh;
+    return sh;
+}
+uint32_t gather_blocks(uint32_t n, uint32_t samples)
+{
+    const uint32_t per_wave = kExtBlock >> gather_group_shift(samples);
+    return std::max(1u, std::min(kTraceBlocks, (uint32_t)(((uint64_t)n + per_wave - 1u) / per_wave)));
+}
+
+hipError_t launch_gather(hipStream_t s, const DeviceScene &sc, const PathState &ps, const float4 *points, float4 *out, uint32_t n, const GatherParams &gp,
+                         const EnvArgs *env)
+{
+    GatherArgsT<true> t{};
+    GatherArgs &a = t.x;
+    a.sc = sc; a.ps = ps; a.points = points; a.out = out; a.n = n;
+    a.samples = gp.samples; a.gshift = gather_group_shift(gp.samples); a.seed = gp.seed;
+    a.point_offset = gp.point_offset; a.sample_offset = gp.sample_offset; a.tmax = gp.tmax; a.ray_eps = gp.ray_eps;
+    if (env) t.env = *env;
+    const dim3 grid(gather_blocks(n, gp.samples));
+    const bool known = with_layout(sc.bvh_width, [&](auto lc) {
+        constexpr int L = decltype(lc)::value;
+        if (env) hipLaunchKernelGGL((k_gather<L, true>), grid, dim3(kExtBlock), 0, s, t);
+        else hipLaunchKernelGGL((k_gather<L, false>), grid, dim3(kExtBlock), 0, s, GatherArgsT<false>{ a });
     });
     return known ? hipGetLastError() : hipErrorInvalidValue;
 }

@@ -1,8 +1,9 @@
-// query.cpp — ray queries (pt_trace_rays, docs/SPEC.md §4.2) and the query plumbing of context.h (Queries), which pt_denoise's guide pass
-// shares (denoise_host.cpp).
+// query.cpp — ray queries (pt_trace_rays, docs/SPEC.md §4.2), hemisphere gathers (pt_gather, §12) and the query plumbing of context.h
+// (Queries), which pt_denoise's guide pass shares (denoise_host.cpp).
 #include "scene.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cmath>
 
 using namespace ptrt;
 
@@ -81,6 +82,68 @@ static pt_status trace_rays(pt_context *c, const pt_scene *s, const void *rays, 
     if (count) { out.node_visits = n.node_visits; out.tri_tests = n.tri_tests; out.sphere_tests = n.sphere_tests; }
     if (stats) *stats = out;
     return PT_OK;
+}
+
+// pt_gather (docs/SPEC.md §12): the rays are made, traced and reduced inside k_gather; the host only checks, stages and launches.
+static pt_status gather(pt_context *c, const pt_scene *s, const void *points, void *out_rows, uint64_t n_points, const pt_gather_params *gp, pt_stats *stats)
+{
+    if (!gp) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_gather: params is NULL");
+    if (gp->flags & ~(uint32_t)PT_GATHER_HOST_MEMORY) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_gather: unknown flag bits 0x%x", gp->flags & ~(uint32_t)PT_GATHER_HOST_MEMORY);
+    if (gp->samples > 4096u) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_gather: samples %u is more than 4096", gp->samples);
+    if (!(gp->max_distance >= 0.0f) || std::isinf(gp->max_distance)) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_gather: max_distance must be 0 (unbounded) or finite and positive");
+    if (!(gp->ray_eps >= 0.0f) || std::isinf(gp->ray_eps)) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_gather: ray_eps must be finite and not negative");
+    const bool host = (gp->flags & PT_GATHER_HOST_MEMORY) != 0;
+    if (!c || !s || !points || !out_rows) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_gather: NULL argument");
+    const uintptr_t align = host ? 3u : 15u; // the kernel loads and stores 16-byte rows; staged host arrays only need float alignment
+    if (((uintptr_t)points & align) || ((uintptr_t)out_rows & align))
+        return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_gather: points and out must be %u-byte aligned", (unsigned)align + 1u);
+    if (s->ctx != c) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_gather: scene belongs to another context");
+    if (!s->committed) return fail(c, PT_ERR_NOT_COMMITTED, "scene not committed");
+    if (n_points >> 32) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_gather: n_points %llu is not a batch size", (unsigned long long)n_points);
+    pt_stats res{};
+    res.paths = n_points;
+    if (n_points == 0) { if (stats) *stats = res; return PT_OK; }
+    GatherParams k{};
+    k.samples = gp->samples ? gp->samples : 64u; k.seed = gp->seed;
+    k.point_offset = gp->point_offset; k.sample_offset = gp->sample_offset;
+    k.tmax = gp->max_distance > 0.0f ? gp->max_distance : INFINITY; k.ray_eps = gp->ray_eps;
+    HIP_TRY(c, hipSetDevice(c->device));
+    pt_status st;
+    if (!host && ((st = check_device_array(c, points, n_points * 32u, "points", "pt_gather", "PT_GATHER_HOST_MEMORY")) != PT_OK ||
+                  (st = check_device_array(c, out_rows, n_points * 32u, "out", "pt_gather", "PT_GATHER_HOST_MEMORY")) != PT_OK)) return st;
+    hipStream_t q = c->stream;
+    PathState ps;
+    // one overflow column per lane of the largest grid a launch of this call uses: setup sizes it for that many one-ray lanes
+    const uint64_t lanes = (uint64_t)gather_blocks((uint32_t)std::min(n_points, kTraceChunk), k.samples) * kExtBlock;
+    if ((st = c->query.setup(c, s->tree.stack_overflow(), lanes, ps)) != PT_OK) return st;
+    const float4 *d_points = (const float4 *)points;
+    float4 *d_out = (float4 *)out_rows;
+    if (host) { // staged through the context's own buffers (two rows per point each way)
+        HIP_TRY(c, c->query.rays.ensure((size_t)n_points * 2u)); HIP_TRY(c, c->query.hits.ensure((size_t)n_points * 2u));
+        HIP_TRY(c, hipMemcpyAsync(c->query.rays.p, points, n_points * 32u, hipMemcpyHostToDevice, q));
+        d_points = c->query.rays.p; d_out = c->query.hits.p;
+    }
+    const EnvArgs env = s->env.present() ? s->env.args(1.0f) : EnvArgs{};
+    HIP_TRY(c, hipEventRecord(c->query.ev[0], q));
+    for (uint64_t first = 0; first < n_points; first += kTraceChunk) { // point_offset + first wraps like the key's own u32 arithmetic
+        GatherParams kc = k; kc.point_offset = k.point_offset + (uint32_t)first;
+        HIP_TRY(c, launch_gather(q, s->ds, ps, d_points + 2u * first, d_out + 2u * first, (uint32_t)std::min(kTraceChunk, n_points - first), kc,
+                                 s->env.present() ? &env : nullptr));
+    }
+    HIP_TRY(c, hipEventRecord(c->query.ev[1], q));
+    if (host) HIP_TRY(c, hipMemcpyAsync(out_rows, d_out, n_points * 32u, hipMemcpyDeviceToHost, q));
+    Queries::Counts n;
+    if ((st = c->query.finish(c, n)) != PT_OK) return st;
+    if (n.error) return fail(c, PT_ERR_INTERNAL, "pt_gather: device error flag 0x%x (1 = traversal stack overflow, 2 = step limit)", n.error);
+    float ms = 0.f; HIP_TRY(c, hipEventElapsedTime(&ms, c->query.ev[0], c->query.ev[1])); res.gpu_ms = ms;
+    res.rays = (uint64_t)k.samples * (n_points - n.node_visits); // the kernel counted the invalid points where the visit counter lives
+    if (stats) *stats = res;
+    return PT_OK;
+}
+
+extern "C" pt_status pt_gather(pt_context *c, const pt_scene *s, const void *points, void *out, uint64_t n_points, const pt_gather_params *gp, pt_stats *stats)
+{
+    return drained_on_failure(c, [&] { return gather(c, s, points, out, n_points, gp, stats); }); // (e.g. a copy into `out`)
 }
 
 extern "C" pt_status pt_trace_rays(pt_context *c, const pt_scene *s, const void *rays, void *hits, uint64_t n_rays, uint32_t flags, pt_stats *stats)

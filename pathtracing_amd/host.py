@@ -299,6 +299,44 @@ class Renderer:
                                    C.byref(stats)), self._ctx)
         return hits, stats
 
+    def Gather(self, points, normals, samples=64, seed=0, sample_offset=0, point_offset=0, max_distance=0.0, ray_eps=1e-3):
+        """Hemisphere gathers at surface points of the current scene (include/ptrt.h pt_gather, docs/SPEC.md §12): ambient occlusion, sky
+        irradiance and the bent normal of a bake; returns (E, visibility, bent, pt_stats).
+
+        points, normals: (N, 3) positions and (not necessarily unit) normals. float32 torch tensors on the renderer's device go in as
+        device pointers and the results are tensors on that device (the current stream is synchronised first); numpy arrays take the
+        staged host path. E: (N, 3), the mean radiance of the unoccluded directions (pi * E = irradiance from the sky or the
+        environment map); visibility: (N,), the unoccluded share of the `samples` cosine-weighted directions (1 - ambient occlusion; -1
+        marks an invalid point); bent: (N, 3), the mean unoccluded direction, not normalised."""
+        gp = N.pt_gather_params(samples=samples, seed=seed, sample_offset=sample_offset, point_offset=point_offset,
+                                max_distance=max_distance, ray_eps=ray_eps, flags=0)
+        stats = N.pt_stats()
+        if N.torch is not None and isinstance(points, N.torch.Tensor):
+            torch = N.torch
+            dev = points.device
+            if dev.type != "cuda" or (dev.index if dev.index is not None else torch.cuda.current_device()) != self._device:
+                raise ValueError(f"points are on {dev}, the renderer on cuda:{self._device}")
+            p, n = (torch.as_tensor(a, dtype=torch.float32, device=dev).reshape(-1, 3) for a in (points, normals))
+            if p.shape != n.shape:
+                raise ValueError(f"{p.shape[0]} points, {n.shape[0]} normals")
+            zero = torch.zeros_like(p[:, :1])
+            rec = torch.cat([p, zero, n, zero], dim=1)
+            out = torch.empty((rec.shape[0], 8), dtype=torch.float32, device=dev)
+            if rec.shape[0]:  # (an empty tensor has no storage to point at)
+                torch.cuda.current_stream(dev).synchronize()  # the library runs on its own stream: the records must be complete
+                _check(N.lib.pt_gather(self._ctx, self._scene, C.c_void_p(rec.data_ptr()), C.c_void_p(out.data_ptr()), rec.shape[0],
+                                       C.byref(gp), C.byref(stats)), self._ctx)
+            return out[:, 0:3], out[:, 3], out[:, 4:7], stats
+        p, n = (np.asarray(a, np.float32).reshape(-1, 3) for a in (points, normals))
+        if p.shape != n.shape:
+            raise ValueError(f"{p.shape[0]} points, {n.shape[0]} normals")
+        rec = np.zeros((len(p), 8), np.float32)
+        rec[:, 0:3], rec[:, 4:7] = p, n
+        out = np.empty((len(rec), 8), np.float32)
+        gp.flags = N.PT_GATHER_HOST_MEMORY
+        _check(N.lib.pt_gather(self._ctx, self._scene, _ptr(rec), _ptr(out), len(rec), C.byref(gp), C.byref(stats)), self._ctx)
+        return out[:, 0:3], out[:, 3], out[:, 4:7], stats
+
     def UpdateGeometry(self, verts=None, spheres=None):
         """Move the current scene's triangles and/or spheres without a new commit (include/ptrt.h pt_scene_update_triangles /
         pt_scene_update_spheres, docs/SPEC.md §4.3); returns the triangle update's pt_stats (gpu_ms), zeros without one.
