@@ -130,7 +130,7 @@ pt_status pt_context_set_tuning(pt_context *c, const pt_tuning *t)
     if (t->lag != 0 && (t->lag < 2 || t->lag > kLag)) return fail(c, PT_ERR_INVALID_ARGUMENT, "tuning: lag must be 0 (default) or 2..%u", kLag);
     if (!(t->compact_below >= 0.f && t->compact_below <= 2.f) || !(t->sparse_below >= 0.f && t->sparse_below <= 1.f))
         return fail(c, PT_ERR_INVALID_ARGUMENT, "tuning: compact_below must be in [0,2], sparse_below in [0,1]");
-    if (t->extend_kernel > (uint32_t)EXT_POOL) return fail(c, PT_ERR_INVALID_ARGUMENT, "tuning: extend_kernel must be 0 (probed), 1 (one ray per lane), 2 (lane-packing) or 3 (pooled)");
+    if (t->extend_kernel > kExtendKernelLast) return fail(c, PT_ERR_INVALID_ARGUMENT, "tuning: extend_kernel must be 0 (probed), 1 (one ray per lane), 2 (lane-packing) or 3 (pooled)");
     if (t->readback > 1) return fail(c, PT_ERR_INVALID_ARGUMENT, "tuning: readback must be 0 (mapped store) or 1 (copy per launch)");
     if (t->readback == 0 && !c->sizes.can_map()) return fail(c, PT_ERR_UNSUPPORTED, "tuning: readback 0 needs host-mapped pinned memory, which this platform did not provide");
     c->tuning = *t; // all or nothing: a refused call changes no field

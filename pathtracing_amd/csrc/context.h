@@ -305,8 +305,8 @@ public:
         return e != hipSuccess ? e : cnt_init.ensure(kCntTotalWords);
     }
     // Build it on `q` if this key differs from the one it was built for (frame.cpp); `sizes` lends the host block for a dense template's bound
-    pt_status build_if_differs(pt_context *c, hipStream_t q, Key key, const DeviceScene &ds, const PathState &ps, const FrameParams &fp,
-                               const QueueSizes &sizes);
+    pt_status build_if_differs(pt_context *c, hipStream_t q, Key key, const Pipeline &pipe, const DeviceScene &ds, const PathState &ps,
+                               const FrameParams &fp, const QueueSizes &sizes);
     void frame_ran(bool accumulate_or_full_state) { if (accumulate_or_full_state && key_.first_spp < key_.streams) valid = false; }
     const uint32_t *counters() const { return cnt_init.p; }   // what the frame's counter block starts as
     uint32_t *first_queue() const { return q_init.p; }        // what the frame's first launch reads: read, never written

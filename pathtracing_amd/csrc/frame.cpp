@@ -28,6 +28,7 @@ uint32_t host_pcg(uint32_t x)
 // The faster per ray wins (packed needs +10 %). Deep incoherent traversals (1M-triangle soup) gain ~2.5x from packing, shallow ones (walls of
 // a box) lose ~35 %, and no static property of the tree tells them apart. Counting / profiling frames neither probe nor feed
 // the decision: their kernels are instrumented builds. A probing frame runs one loop and no finish mode, so that its timed iterations compare.
+// Which kernel one launch runs, given this frame's choice, is the pipeline's to say (pipeline.h Pipeline::kernel_for).
 uint32_t faster(double rate_simple, double rate_packed) { return rate_packed > 1.10 * rate_simple ? EXT_PACKED : EXT_SIMPLE; }
 struct ExtendFrame {            // the choice during one frame
     ExtendChoice &mem;
@@ -35,12 +36,11 @@ struct ExtendFrame {            // the choice during one frame
     uint32_t frame_kernel, kernel; // kernel: 0 = probing inside this frame, else the ExtendKernel every iteration uses
     bool mixed = false;         // this frame ran probe iterations on both kernels: its overall rate says nothing about either
     uint64_t probe_n[2] = { 0, 0 }; // rays traced by probe iterations 2 and 3
-    ExtendFrame(ExtendChoice &m, uint32_t forced, bool instrumented) : mem(m),
-        undecided(forced == 0u && m.kernel == 0u && !instrumented),
+    ExtendFrame(ExtendChoice &m, const Pipeline &p) : mem(m),
+        undecided(p.forced == 0u && m.kernel == 0u && !p.instrumented()),
         frame_kernel((undecided && m.rate_simple > 0.0 && m.rate_packed == 0.0) ? EXT_PACKED : EXT_SIMPLE), // first the default, then the other
-        kernel(forced ? forced : m.kernel ? m.kernel : (undecided && frame_kernel == EXT_SIMPLE) ? 0u : frame_kernel) {}
+        kernel(p.forced ? p.forced : m.kernel ? m.kernel : (undecided && frame_kernel == EXT_SIMPLE) ? 0u : frame_kernel) {}
     bool probing(uint32_t g, uint32_t it) const { return g == 0u && kernel == 0u && (it == 2u || it == 3u); }
-    int launch_kernel(uint32_t g, uint32_t it, bool split) const { return (kernel == EXT_PACKED || (probing(g, it) && it == 3u)) ? EXT_PACKED : (kernel == EXT_POOL && !split) ? EXT_POOL : EXT_SIMPLE; }
     // default path vertices per launch. Lane-packing: a lane pulls a new entry whenever its budget ends, so a long budget costs nothing and saves
     // launches (ms per frame with 8 / 16 / 32 / 64 vertices, tools/exp_packed.py: 1M soup 72.2 / 71.5 / 70.5 / 67.4, at 256 spp 277.6 / 271.8 /
     // 268.3 / 266.1, 5k soup 7.99 / 7.43 / 7.35 / 7.39); the probe iteration keeps 8 so that it stays comparable with the one before it
@@ -150,12 +150,9 @@ uint64_t scene_pixels_code(const FrameParams &fp)
 
 struct Frame {                  // a path-traced frame as plan_frame lays it out, and what its loops leave for finish_frame
     uint32_t nranks, streams, pixel_slots, n_slots, shard_cap, samples_per_stream, lag, n_loops, packed_chunk, default_bounces;
-    uint32_t forced;            // ExtendKernel a frame flag or pt_tuning.extend_kernel forces (0 = none)
-    bool profile, count, split, bucket, full_state, accumulate, mapped, compact;
-    bool nee;                   // PT_FLAG_NEXT_EVENT (docs/SPEC.md §7): the one-ray-per-lane kernel with light samples
-    NeeArgs nee_args;
-    bool env;                   // the scene has an environment map (docs/SPEC.md §11): the same kernel, in its environment instantiation
-    EnvArgs env_args;
+    Pipeline pipe;              // what the frame's flags, pt_tuning.extend_kernel and the scene decode to (pipeline.h)
+    bool accumulate, mapped, compact;
+    NeeArgs nee_args; EnvArgs env_args; // the blocks of a pipe.nee / pipe.env frame
     bool sky;                   // the frame has sky pixels (scene_pixels) and resolves them at its start instead of tracing their paths
     Accumulation::Key sums_key; // what the sums hold once this frame completes
     size_t q_entries; uint64_t total_spp, allocs_before;
@@ -167,8 +164,8 @@ struct Frame {                  // a path-traced frame as plan_frame lays it out
 } // namespace
 
 // (the frame's stream `q`; ps and fp are the frame's, with the template's own queue and counter block put in place of the frame's)
-pt_status FrameTemplate::build_if_differs(pt_context *c, hipStream_t q, Key key, const DeviceScene &ds, const PathState &ps, const FrameParams &fp,
-                                          const QueueSizes &sizes)
+pt_status FrameTemplate::build_if_differs(pt_context *c, hipStream_t q, Key key, const Pipeline &pipe, const DeviceScene &ds, const PathState &ps,
+                                          const FrameParams &fp, const QueueSizes &sizes)
 {
     key.q = q_init.p;
     if (valid && key == key_) return PT_OK;
@@ -176,7 +173,7 @@ pt_status FrameTemplate::build_if_differs(pt_context *c, hipStream_t q, Key key,
     PathState pt = ps; pt.counters = cnt_init.p; pt.q_ext[0] = q_init.p;
     // whole streams without a sample (spp < streams): the first queue holds the live slots only, and the first launch is sized by it
     const bool dense = key.first_spp < key.streams;
-    HIP_TRY(c, launch_generate(q, ds, pt, fp, dense ? 2u : 0u)); // also zeroes every slot's sum unless the frame accumulates
+    HIP_TRY(c, launch_generate(q, ds, pt, fp, pipe.generate_mode(dense))); // also zeroes every slot's sum unless the frame accumulates
     bound = key.shard_cap;
     if (dense) {
         uint32_t *h = sizes.template_sizes();
@@ -210,32 +207,9 @@ static pt_status plan_frame(pt_context *c, const pt_scene *s, const pt_render_pa
     const uint32_t groups = (f.n_slots + (1u << kShardGroupShift) - 1u) >> kShardGroupShift, shard_cap = ((groups + kShards - 1) / kShards) << kShardGroupShift;
     f.shard_cap = shard_cap; f.q_entries = (size_t)kShards * shard_cap;
     f.samples_per_stream = (p->spp + f.streams - 1u) / f.streams;
-    f.profile = (p->flags & PT_FLAG_PROFILE_KERNELS) != 0; f.count = (p->flags & PT_FLAG_COUNT_VISITS) != 0;
-    f.bucket = (p->flags & PT_FLAG_BUCKET_SPECULAR) != 0; f.split = f.bucket || (p->flags & PT_FLAG_SPLIT_KERNELS) != 0;
-    f.forced = (p->flags & PT_FLAG_EXTEND_POOL) ? (uint32_t)EXT_POOL : (p->flags & PT_FLAG_EXTEND_PACKED) ? (uint32_t)EXT_PACKED
-               : (p->flags & PT_FLAG_EXTEND_SIMPLE) ? (uint32_t)EXT_SIMPLE : t.extend_kernel;
-    // an environment map is looked up (and, in NEE frames, sampled) by the fused one-ray-per-lane kernel only, as NEE is: no probe, no counters
-    f.env = s->env.present();
-    if (f.env) {
-        if (f.split || f.count || f.forced == (uint32_t)EXT_PACKED || f.forced == (uint32_t)EXT_POOL)
-            return fail(c, PT_ERR_UNSUPPORTED, "a scene with an environment map renders on the one-ray-per-lane kernel only: not with PT_FLAG_EXTEND_PACKED, "
-                                               "PT_FLAG_EXTEND_POOL, PT_FLAG_SPLIT_KERNELS, PT_FLAG_BUCKET_SPECULAR, PT_FLAG_COUNT_VISITS or pt_tuning.extend_kernel 2 / 3");
-        f.forced = EXT_SIMPLE;
-    }
-    // next-event estimation lives in the fused one-ray-per-lane kernel only. Its frames neither probe the extend kernel nor feed the
-    // scene's choice (a forced kernel does neither), and they have no visit counters: a shadow ray's traversal stops at its tmax, which
-    // §4.1's counters do not describe.
-    f.nee = (p->flags & PT_FLAG_NEXT_EVENT) != 0;
-    if (f.nee) {
-        if (f.split || f.forced == (uint32_t)EXT_PACKED || f.forced == (uint32_t)EXT_POOL)
-            return fail(c, PT_ERR_UNSUPPORTED, "PT_FLAG_NEXT_EVENT runs on the one-ray-per-lane kernel only: not with PT_FLAG_EXTEND_PACKED, "
-                                               "PT_FLAG_EXTEND_POOL, PT_FLAG_SPLIT_KERNELS, PT_FLAG_BUCKET_SPECULAR or pt_tuning.extend_kernel 2 / 3");
-        if (f.count) return fail(c, PT_ERR_UNSUPPORTED, "PT_FLAG_NEXT_EVENT does not count visits (PT_FLAG_COUNT_VISITS)");
-        f.forced = EXT_SIMPLE;
-    }
-    // the fused one-ray-per-lane and lane-packing kernels build a slot's initial state in registers in their first launch; k_shade
-    // (split pipelines) and the pooled kernel read it from memory
-    f.full_state = f.split || f.forced == (uint32_t)EXT_POOL;
+    const PipelineDecode d = decode_pipeline(p->flags, t.extend_kernel, s->env.present(), s->has_specular);
+    if (d.status != PT_OK) return fail(c, d.status, "%s", d.message);
+    const Pipeline &pipe = f.pipe = d.pipeline;
     f.mapped = t.readback == 0u; // queue sizes reach the host by the kernels' own stores (fold_traced) instead of a copy per launch
     // rays per wavefront of the lane-packing kernel: 256 once several sample streams keep the queues long, else 128 (measured)
     f.packed_chunk = t.packed_chunk >= 64u ? t.packed_chunk : (f.streams >= 4u ? 256u : 128u);
@@ -243,7 +217,7 @@ static pt_status plan_frame(pt_context *c, const pt_scene *s, const pt_render_pa
     const uint32_t v34 = p->max_depth * 3u / 4u; f.default_bounces = std::min(12u, std::max(4u, v34 > 2u ? v34 - 2u : 0u));
     // NEE: `bounces` counts rays, and a vertex with a light sample takes two (shadow, then extension): twice the passes for about as many
     // vertices per launch
-    if (f.nee) f.default_bounces *= 2u;
+    if (pipe.nee) f.default_bounces *= 2u;
     // Iterations the host runs ahead of the queue sizes it reads back (pt_tuning.lag). The frame ends `lag` launches after its last path, on
     // grids sized `lag` iterations ago: short frames feel that (ms per 1080p frame with lag 4 / 3 / 2, tools/exp_lag.py: 1 spp 0.567 / 0.537 /
     // 0.529, 8 spp 2.79 / 2.73 / 2.70, glass 8 spp 1.57 / 1.52 / 1.48), long ones not (64 spp 17.73 / 17.68 / 17.73; a rank's 1/8 2.63 / 2.59 /
@@ -254,7 +228,7 @@ static pt_status plan_frame(pt_context *c, const pt_scene *s, const pt_render_pa
     // progressive accumulation (the reference re-renders every frame, App.cs:39-42; this is its converging analogue):
     // keep the stream partials of the previous call(s) and divide by the total number of samples at the end
     f.accumulate = (p->flags & PT_FLAG_ACCUMULATE) != 0;
-    f.sums_key = Accumulation::Key{ p->width, p->height, p->rank, f.nranks, f.streams, p->seed, f.nee };
+    f.sums_key = Accumulation::Key{ p->width, p->height, p->rank, f.nranks, f.streams, p->seed, pipe.nee };
     if (f.accumulate)
         switch (c->sums.continues(f.sums_key, p->sample_offset)) {
         case Accumulation::Refusal::other_frame:
@@ -271,37 +245,33 @@ static pt_status plan_frame(pt_context *c, const pt_scene *s, const pt_render_pa
     HIP_TRY(c, c->acc.ensure(f.n_slots)); HIP_TRY(c, c->out.tiles.ensure(f.pixel_slots)); HIP_TRY(c, c->sd.ensure(f.n_slots));
     HIP_TRY(c, c->q_ext0.ensure(f.q_entries)); HIP_TRY(c, c->q_ext1.ensure(f.q_entries));
     // hit records and the metal / dielectric buckets are k_shade's (no kernel indexes the miss and Lambert buckets)
-    if (f.split) { HIP_TRY(c, c->hit.ensure(f.n_slots)); HIP_TRY(c, c->q_metal.ensure(f.q_entries)); HIP_TRY(c, c->q_dielectric.ensure(f.q_entries)); }
-    if (!f.full_state) HIP_TRY(c, c->start.reserve(f.q_entries));
+    if (pipe.split) { HIP_TRY(c, c->hit.ensure(f.n_slots)); HIP_TRY(c, c->q_metal.ensure(f.q_entries)); HIP_TRY(c, c->q_dielectric.ensure(f.q_entries)); }
+    if (!pipe.full_state()) HIP_TRY(c, c->start.reserve(f.q_entries));
     const uint32_t ovf = s->tree.stack_overflow();
     if (ovf) HIP_TRY(c, c->stack_ovf.ensure((size_t)ovf * f.q_entries));
-    if (f.nee) {
+    if (pipe.nee) {
         HIP_TRY(c, c->nee_ext.ensure(f.n_slots)); HIP_TRY(c, c->nee_rad.ensure(f.n_slots));
         f.nee_args = NeeArgs{ s->d_lights.p, s->d_cdf.p, s->d_pa.p, s->n_lights, c->nee_ext.p, c->nee_rad.p };
     }
     // §11: a light sample picks one of the two kinds of light with probability 1/2 when the frame has both
-    if (f.env) f.env_args = s->env.args(f.nee && s->env.lit() && s->n_lights ? 0.5f : 1.0f);
+    if (pipe.env) f.env_args = s->env.args(pipe.nee && s->env.lit() && s->n_lights ? 0.5f : 1.0f);
     if (f.nranks == 1) HIP_TRY(c, c->out.resize(p->width, p->height));
     PathState &ps = f.ps;
     ps.ray_o = c->ray_o.p; ps.ray_d = c->ray_d.p; ps.thr = c->thr.p; ps.sd = c->sd.p; ps.acc = c->acc.p; ps.q_ext[0] = c->q_ext0.p; ps.q_ext[1] = c->q_ext1.p;
-    if (f.split) { ps.hit = c->hit.p; ps.q_bucket[B_METAL] = c->q_metal.p; ps.q_bucket[B_DIELECTRIC] = c->q_dielectric.p; }
+    if (pipe.split) { ps.hit = c->hit.p; ps.q_bucket[B_METAL] = c->q_metal.p; ps.q_bucket[B_DIELECTRIC] = c->q_dielectric.p; }
     ps.counters = c->counters.p; ps.stack_ovf = c->stack_ovf.p; ps.stack_ovf_entries = ovf; ps.n_slots = f.n_slots; ps.shard_cap = f.shard_cap;
     ps.shard_base = 0; ps.shard_count = kShards; ps.compact_below = t.compact_below; ps.finish_below = t.finish_below; ps.sparse_below = t.sparse_below;
     ps.repack_sticky = (f.samples_per_stream <= t.sticky_samples && t.compact_below > 0.f) ? 1u : 0u;
     ps.host_ring = c->sizes.begin(f.mapped); ps.ring_slots = kLag;
-    // re-packing forced: buckets re-append (no fixed positions), or next to nothing regenerates (every launch leaves holes)
-    f.compact = f.bucket || (ps.repack_sticky && f.samples_per_stream <= 2u);
+    f.compact = pipe.forces_compact(ps.repack_sticky != 0u, f.samples_per_stream);
     FrameParams &fp = f.fp;
     fp.width = p->width; fp.height = p->height; fp.spp = p->spp; fp.max_depth = p->max_depth; fp.rr_start = p->rr_start;
     fp.seed_hashed = host_pcg(p->seed); fp.sample_offset = p->sample_offset; fp.ray_eps = p->ray_eps;
     fp.rank = p->rank; fp.nranks = f.nranks; fp.tiles_x = lay.tiles_x; fp.n_tiles = lay.n_tiles; fp.streams = f.streams; fp.slots_per_stream = f.pixel_slots;
     div_magic(f.streams, fp.streams_magic, fp.streams_shift); div_magic(lay.tiles_x, fp.tiles_x_magic, fp.tiles_x_shift);
     fp.offset_mod = p->sample_offset % f.streams; fp.accumulate = f.accumulate ? 1u : 0u;
-    // Sky pixels are resolved by the frames whose first launch builds the slots' state in registers (path_begin: the fused one-ray-per-lane
-    // and lane-packing kernels, next-event estimation included: a camera ray's miss adds the sky with weight 1 there too). Not by counting
-    // frames, whose visit counters are the spec's, nor with an environment map, where a miss depends on the ray's direction.
     fp.scene_x0 = fp.scene_y0 = 0u; fp.scene_x1 = fp.scene_y1 = ~0u;
-    f.sky = !f.full_state && !f.count && !f.env && scene_pixels(s, s->ds.cam, p->width, p->height, fp);
+    f.sky = pipe.resolves_sky() && scene_pixels(s, s->ds.cam, p->width, p->height, fp);
     return PT_OK;
 }
 
@@ -309,23 +279,23 @@ static pt_status plan_frame(pt_context *c, const pt_scene *s, const pt_render_pa
 // template of its geometry (context.h FrameTemplate: k_generate's output depends on which slots exist and on whether every stream has a sample).
 static pt_status start_frame(pt_context *c, const pt_scene *s, const pt_render_params *p, const Frame &f)
 {
-    hipStream_t q = c->stream;
-    if (f.full_state) {
+    hipStream_t q = c->stream; const bool full_state = f.pipe.full_state();
+    if (full_state) {
         HIP_TRY(c, hipMemsetAsync(c->counters.p, 0, sizeof(uint32_t) * kCntTotalWords, q));
         HIP_TRY(c, hipEventRecord(c->ev_start, q));
-        HIP_TRY(c, launch_generate(q, s->ds, f.ps, f.fp, 1u));
+        HIP_TRY(c, launch_generate(q, s->ds, f.ps, f.fp, f.pipe.generate_mode(false)));
     } else {
         HIP_TRY(c, hipEventRecord(c->ev_start, q));
         FrameTemplate::Key key{};
         key.w = p->width; key.h = p->height; key.rank = p->rank; key.nranks = f.nranks; key.streams = f.streams; key.first_spp = std::min(p->spp, f.streams);
         key.offset = f.fp.offset_mod; key.n_slots = f.n_slots; key.shard_cap = f.shard_cap; key.acc = c->acc.p;
-        const pt_status st = c->start.build_if_differs(c, q, key, s->ds, f.ps, f.fp, c->sizes);
+        const pt_status st = c->start.build_if_differs(c, q, key, f.pipe, s->ds, f.ps, f.fp, c->sizes);
         if (st != PT_OK) return st;
         HIP_TRY(c, hipMemcpyAsync(c->counters.p, c->start.counters(), sizeof(uint32_t) * kCntTotalWords, hipMemcpyDeviceToDevice, q));
         // the template is the geometry's, not the camera's: it still queues the sky pixels' slots, and the first launch leaves them out
         if (f.sky) HIP_TRY(c, launch_sky_pixels(q, s->ds, f.ps, f.fp));
     }
-    c->start.frame_ran(f.accumulate || f.full_state); // the template invariant: this frame writes the streams a dense template leaves out
+    c->start.frame_ran(f.accumulate || full_state); // the template invariant: this frame writes the streams a dense template leaves out
     return PT_OK;
 }
 
@@ -339,44 +309,43 @@ static pt_status start_frame(pt_context *c, const pt_scene *s, const pt_render_p
 // sizes grids and notices the end.
 static pt_status run_loops(pt_context *c, const pt_scene *s, const pt_render_params *p, Frame &f, ExtendFrame &x)
 {
-    hipStream_t q = c->stream; const uint32_t n_loops = f.n_loops, per_group = kShards / n_loops;
+    hipStream_t q = c->stream; const Pipeline &pipe = f.pipe; const bool full_state = pipe.full_state();
+    const uint32_t n_loops = f.n_loops, per_group = kShards / n_loops;
     struct Loop { hipStream_t stream; uint32_t base, bound, iters; bool done; } loops[kMaxGroups];
     HIP_TRY(c, hipEventRecord(c->ev_fork, q));
     for (uint32_t g = 0; g < n_loops; ++g) {
-        loops[g] = Loop{ n_loops == 1 ? q : c->group_stream[g], g * per_group, f.full_state ? f.shard_cap : c->start.first_bound(), 0u, false }; // no shard's queue can outgrow its first one
+        loops[g] = Loop{ n_loops == 1 ? q : c->group_stream[g], g * per_group, full_state ? f.shard_cap : c->start.first_bound(), 0u, false }; // no shard's queue can outgrow its first one
         if (loops[g].stream != q) HIP_TRY(c, hipStreamWaitEvent(loops[g].stream, c->ev_fork, 0));
     }
-    const uint64_t max_iters = (uint64_t)p->spp * p->max_depth * (f.nee ? 2u : 1u) + kLag + 2; // NEE: up to two rays per vertex
-    const bool trace = f.profile && getenv("PTRT_TRACE") != nullptr; // developer aid: per-iteration table on stderr
-    // One kernel per iteration by default: every extend kernel (one ray per lane, lane-packing, pooled) shades its own hits (mode 0:
-    // Lambert-only scene, lean code; 2: all kinds). PT_FLAG_SPLIT_KERNELS / _BUCKET_SPECULAR run k_shade as a second kernel.
-    const int shade_mode = (s->has_specular || f.env) ? 2 : 0; // (the environment instantiations shade every kind, whatever the materials)
+    const uint64_t max_iters = (uint64_t)p->spp * p->max_depth * (pipe.nee ? 2u : 1u) + kLag + 2; // NEE: up to two rays per vertex
+    const bool trace = pipe.profile && getenv("PTRT_TRACE") != nullptr; // developer aid: per-iteration table on stderr
     for (uint32_t live = n_loops; live > 0;) {
         for (uint32_t g = 0; g < n_loops; ++g) {
             Loop &L = loops[g];
             if (L.done) continue;
             if (L.iters >= max_iters) return fail(c, PT_ERR_INTERNAL, "wavefront loop did not drain after %u iterations", L.iters);
             const uint32_t it = L.iters; PathState pg = f.ps; pg.shard_base = L.base; pg.shard_count = per_group;
-            if (it == 0u && !f.full_state) pg.q_ext[0] = c->start.first_queue(); // the frame's first queue is the template: read, never written
+            if (it == 0u && !full_state) pg.q_ext[0] = c->start.first_queue(); // the frame's first queue is the template: read, never written
             if (x.kernel == 0u) pg.finish_below = 0u; // probing: no finish mode
             hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
-            if (f.profile) {
+            if (pipe.profile) {
                 e0 = pool_event(c, f.n_events++); e1 = pool_event(c, f.n_events++); e2 = pool_event(c, f.n_events++);
                 if (!e0 || !e1 || !e2) return fail(c, PT_ERR_HIP, "hipEventCreate failed"); // (the text this failure has always had)
                 HIP_TRY(c, hipEventRecord(e0, L.stream));
             }
-            const bool probing = x.probing(g, it); const int kernel = x.launch_kernel(g, it, f.split);
+            const bool probing = x.probing(g, it); const ExtendKernel kernel = pipe.kernel_for(x.kernel, probing ? it : 0u);
             if (probing) HIP_TRY(c, hipEventRecord(c->ev_probe[(it - 2u) * 2u], L.stream));
-            HIP_TRY(c, launch_extend(L.stream, s->ds, pg, f.fp, it, L.bound, f.count, kernel, f.packed_chunk, f.split ? -1 : shade_mode, f.compact,
-                                     c->tuning.bounces ? c->tuning.bounces : x.bounces(g, it, kernel, f.default_bounces), f.nee ? &f.nee_args : nullptr,
-                                     f.env ? &f.env_args : nullptr));
-            if (f.profile) HIP_TRY(c, hipEventRecord(e1, L.stream));
-            if (f.bucket) {
-                HIP_TRY(c, launch_shade(L.stream, s->ds, pg, f.fp, it, L.bound, 0, true));
-                HIP_TRY(c, launch_shade(L.stream, s->ds, pg, f.fp, it, L.bound, 1, true)); // metal + dielectric buckets
-            } else if (f.split) HIP_TRY(c, launch_shade(L.stream, s->ds, pg, f.fp, it, L.bound, shade_mode, f.compact));
+            const ExtendLaunch launch{ it, L.bound, kernel, pipe.fuse(), pipe.count, f.compact, f.packed_chunk,
+                                       c->tuning.bounces ? c->tuning.bounces : x.bounces(g, it, kernel, f.default_bounces),
+                                       pipe.nee ? &f.nee_args : nullptr, pipe.env ? &f.env_args : nullptr };
+            HIP_TRY(c, launch_extend(L.stream, s->ds, pg, f.fp, launch));
+            if (pipe.profile) HIP_TRY(c, hipEventRecord(e1, L.stream));
+            if (pipe.bucket) {
+                HIP_TRY(c, launch_shade(L.stream, s->ds, pg, f.fp, it, L.bound, SHADE_QUEUE, true));
+                HIP_TRY(c, launch_shade(L.stream, s->ds, pg, f.fp, it, L.bound, SHADE_BUCKETS, true)); // metal + dielectric buckets
+            } else if (pipe.split) HIP_TRY(c, launch_shade(L.stream, s->ds, pg, f.fp, it, L.bound, pipe.shade, f.compact));
             if (probing) HIP_TRY(c, hipEventRecord(c->ev_probe[(it - 2u) * 2u + 1u], L.stream)); // the whole iteration, either way
-            if (f.profile) HIP_TRY(c, hipEventRecord(e2, L.stream));
+            if (pipe.profile) HIP_TRY(c, hipEventRecord(e2, L.stream));
             HIP_TRY(c, c->sizes.post(L.stream, g, it, c->counters.p + cnt_ext_index((it + 1u) % 3u, L.base), per_group));
             f.iters = std::max(f.iters, ++L.iters);
             if (L.iters < f.lag) continue;
@@ -421,7 +390,7 @@ static pt_status finish_frame(pt_context *c, const pt_render_params *p, const Fr
     // of them came after the wave's first leaf phase of the ray (diagnostic for tools/exp_util.py)
     out.reserved[3] = (hc.u64(kCntWaveNodeIters) & 0xFFFFFFFFFFull) | (hc.u64(kCntWaveNodeIters + 2) << 40);
     if (f.sky) out.reserved[3] = scene_pixels_code(fp); // (a frame that resolves sky pixels never counts: the counters above are 0)
-    if (f.count && getenv("PTRT_TRACE")) { // developer aid: where the node loop's lane-slots go (one-ray-per-lane kernel)
+    if (f.pipe.count && getenv("PTRT_TRACE")) { // developer aid: where the node loop's lane-slots go (one-ray-per-lane kernel)
         const double slots = 64.0 * (double)hc.u64(kCntWaveNodeIters), v = (double)out.node_visits, lf = (double)hc.u64(kCntIdleLeaf), dn = (double)hc.u64(kCntIdleDone);
         if (slots > 0) fprintf(stderr, "ptrt: node-loop lane-slots %.3g: visiting %.1f %%, waiting at a leaf %.1f %%, ray finished %.1f %%, no ray %.1f %%\n", slots,
                                100 * v / slots, 100 * lf / slots, 100 * dn / slots, 100 * (slots - v - lf - dn) / slots);
@@ -444,7 +413,7 @@ static pt_status finish_frame(pt_context *c, const pt_render_params *p, const Fr
     // path states read + written by the wavefront loop = sum over launches of the paths alive at launch start
     // (iteration 0 starts every (pixel, stream) pair that has a sample)
     out.reserved[2] = f.slot_launches + px * std::min(f.streams, p->spp);
-    if (f.profile) {
+    if (f.pipe.profile) {
         const bool trace = getenv("PTRT_TRACE") != nullptr;
         for (size_t i = 0; i + 2 < f.n_events; i += 3) { // three events per iteration: before extend, between, after shade
             float a = 0.f, b = 0.f; HIP_TRY(c, hipEventElapsedTime(&a, c->ev_pool[i], c->ev_pool[i + 1]));
@@ -486,8 +455,8 @@ static pt_status render_frame(pt_context *c, const pt_scene *s, const pt_render_
     if (p->mode != PT_PATH_TRACE) return fail(c, PT_ERR_INVALID_ARGUMENT, "unknown mode %u", p->mode);
     Frame f{};
     if ((st = plan_frame(c, s, p, lay, f)) != PT_OK) return st;
-    ExtendFrame x(s->cache.ext, f.forced, f.count || f.profile);
-    f.n_loops = (f.profile || f.count || x.kernel == 0u) ? 1u : c->tuning.loops ? c->tuning.loops : 2u; // timed kernels run alone
+    ExtendFrame x(s->cache.ext, f.pipe);
+    f.n_loops = f.pipe.single_loop(x.kernel == 0u) ? 1u : c->tuning.loops ? c->tuning.loops : 2u;
     if ((st = start_frame(c, s, p, f)) != PT_OK || (st = run_loops(c, s, p, f, x)) != PT_OK) return st;
     return finish_frame(c, p, f, x, stats);
 }

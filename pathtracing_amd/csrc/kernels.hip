@@ -407,7 +407,6 @@ PT_DEV void visit_node(const float4 *__restrict__ nd, float4 r0, float4 r1, floa
 //   SHADE_QUEUE   : Lambert and misses; a specular hit sets `defer` to its bucket and leaves the state untouched
 //   SHADE_BUCKETS : the hit's kind is `b` (wave-uniform)
 //   SHADE_INLINE  : every kind, by a divergent branch
-enum ShadeMode { SHADE_NONE = -1, SHADE_QUEUE = 0, SHADE_BUCKETS = 1, SHADE_INLINE = 2 };
 // The path state of a slot, held in registers between path_load and path_store (one bounce in k_shade, several in k_extend).
 struct PathRegs {
     V3 o, d, T;                 // ray, throughput
@@ -1844,9 +1843,9 @@ hipError_t launch_reference_sphere(hipStream_t s, uint32_t w, uint32_t h, float4
     return hipGetLastError();
 }
 
-hipError_t launch_generate(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp, uint32_t mode)
+hipError_t launch_generate(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp, GenerateMode mode)
 {
-    hipLaunchKernelGGL(k_generate, shard_grid(blocks_for(ps.shard_cap), ps.shard_count), dim3(kBlock), 0, s, sc, ps, fp, mode);
+    hipLaunchKernelGGL(k_generate, shard_grid(blocks_for(ps.shard_cap), ps.shard_count), dim3(kBlock), 0, s, sc, ps, fp, (uint32_t)mode);
     return hipGetLastError();
 }
 
@@ -1856,7 +1855,7 @@ hipError_t launch_sky_pixels(hipStream_t s, const DeviceScene &sc, const PathSta
     return hipGetLastError();
 }
 
-// Run-time launch parameters -> template arguments: f is called with a std::integral_constant of the node layout / the fused shading.
+// Run-time launch parameters -> template arguments: f is called with a std::integral_constant of the node layout / a value of the list V.
 // with_layout returns false, without calling f, for a layout that does not exist.
 template <typename F>
 static bool with_layout(uint32_t width, F &&f)
@@ -1870,13 +1869,8 @@ static bool with_layout(uint32_t width, F &&f)
     default: return false;
     }
 }
-template <typename F>
-static void with_fuse(int fuse, F &&f)
-{
-    if (fuse == SHADE_QUEUE) f(std::integral_constant<int, SHADE_QUEUE>{});
-    else if (fuse == SHADE_INLINE) f(std::integral_constant<int, SHADE_INLINE>{});
-    else f(std::integral_constant<int, SHADE_NONE>{});
-}
+template <int... V, typename F>
+static void with_value(int v, F &&f) { (void)((v == V && (f(std::integral_constant<int, V>{}), true)) || ...); }
 
 template <int L, bool COUNT, int FUSE, bool NEE, bool ENV>
 static void launch_k_extend(hipStream_t s, dim3 grid, const ExtArgs &a, const NeeArgs *nee, const EnvArgs *env) // builds only its case's block
@@ -1885,36 +1879,27 @@ static void launch_k_extend(hipStream_t s, dim3 grid, const ExtArgs &a, const Ne
     hipLaunchKernelGGL((k_extend<L, COUNT, FUSE, NEE, ENV>), grid, dim3(kExtBlock), 0, s, t);
 }
 
-hipError_t launch_extend(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp, uint32_t it, uint32_t shard_bound, bool count,
-                         int kernel, uint32_t packed_chunk, int fuse, bool compact, uint32_t bounces, const NeeArgs *nee, const EnvArgs *env)
+hipError_t launch_extend(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp, const ExtendLaunch &x)
 {
-    // kernel: EXT_SIMPLE one ray per lane; EXT_PACKED a wavefront owns `packed_chunk` (>= 64) queue entries and refills idle lanes,
-    // shading each finished ray on the spot; EXT_POOL a wavefront owns kPool entries, refills idle lanes during traversal and shades
-    // the whole pool at full width (fused only: without shading it falls back to EXT_PACKED).
-    if (kernel == EXT_POOL && fuse == SHADE_NONE) kernel = EXT_PACKED;
-    const uint32_t chunk = kernel == EXT_PACKED ? (packed_chunk >= 64u ? packed_chunk : 128u) : 0u;
-    const uint32_t per_block = kernel == EXT_PACKED ? chunk : kernel == EXT_POOL ? kPool : kExtBlock;
-    const dim3 grid = shard_grid(shard_bound ? (shard_bound + per_block - 1) / per_block : 1u, ps.shard_count);
+    const bool has_nee = x.nee != nullptr, has_env = x.env != nullptr;
+    if (!extend_instantiated(x.kernel, x.fuse, x.count, has_nee, has_env)) return hipErrorInvalidValue;
+    const uint32_t chunk = x.kernel == EXT_PACKED ? (x.packed_chunk >= 64u ? x.packed_chunk : 128u) : 0u;
+    const uint32_t per_block = x.kernel == EXT_PACKED ? chunk : x.kernel == EXT_POOL ? kPool : kExtBlock;
+    const dim3 grid = shard_grid(x.shard_bound ? (x.shard_bound + per_block - 1) / per_block : 1u, ps.shard_count);
     ExtArgs a;
-    a.sc = sc; a.ps = ps; a.fp = fp; a.it = it; a.compact = compact ? 1u : 0u; a.bounces = bounces ? bounces : 1u; a.chunk = chunk;
-    // NEE: the one-ray-per-lane kernel, fused, not counting (api.cpp refuses every other combination before it gets here)
-    if (nee && (kernel != EXT_SIMPLE || count || fuse == SHADE_NONE)) return hipErrorInvalidValue;
-    // an environment map: the same kernel, all-kinds shading, not counting (api.cpp refuses the rest), in its environment instantiation
-    if (env && (kernel != EXT_SIMPLE || count || fuse != SHADE_INLINE)) return hipErrorInvalidValue;
-    // layout x fuse x (ENV x NEE | NEE | count x kernel): the pool and NEE kernels always shade, so they have no SHADE_NONE instantiation
-    const bool known = with_layout(sc.bvh_width, [&](auto lc) { with_fuse(fuse, [&](auto fc) {
-        constexpr int L = decltype(lc)::value, F = decltype(fc)::value, FS = F == SHADE_NONE ? SHADE_QUEUE : F;
-        auto go = [&](auto cc) {
-            constexpr bool C = decltype(cc)::value;
-            if (kernel == EXT_POOL) hipLaunchKernelGGL((k_extend_pool<L, C, FS>), grid, dim3(64), 0, s, a);
-            else if (kernel == EXT_PACKED) hipLaunchKernelGGL((k_extend_packed<L, C, F>), grid, dim3(64), 0, s, a);
-            else launch_k_extend<L, C, F, false, false>(s, grid, a, nullptr, nullptr);
-        };
-        if (env && nee) { if constexpr (F == SHADE_INLINE) launch_k_extend<L, false, F, true, true>(s, grid, a, nee, env); }
-        else if (env) { if constexpr (F == SHADE_INLINE) launch_k_extend<L, false, F, false, true>(s, grid, a, nullptr, env); }
-        else if (nee) launch_k_extend<L, false, FS, true, false>(s, grid, a, nee, nullptr);
-        else if (count) go(std::true_type{});
-        else go(std::false_type{});
+    a.sc = sc; a.ps = ps; a.fp = fp; a.it = x.it; a.compact = x.compact ? 1u : 0u; a.bounces = x.bounces ? x.bounces : 1u; a.chunk = chunk;
+    // layout x kernel x fuse x count x NEE x ENV, of which extend_instantiated names the ones that exist
+    const bool known = with_layout(sc.bvh_width, [&](auto lc) { with_value<EXT_SIMPLE, EXT_PACKED, EXT_POOL>(x.kernel, [&](auto kc) {
+        with_value<SHADE_NONE, SHADE_QUEUE, SHADE_INLINE>(x.fuse, [&](auto fc) { with_value<0, 1>(x.count, [&](auto cc) {
+            with_value<0, 1>(has_nee, [&](auto nc) { with_value<0, 1>(has_env, [&](auto ec) {
+                constexpr int L = decltype(lc)::value, K = decltype(kc)::value, F = decltype(fc)::value;
+                constexpr bool C = decltype(cc)::value != 0, N = decltype(nc)::value != 0, E = decltype(ec)::value != 0;
+                if constexpr (!extend_instantiated(K, F, C, N, E)) return;
+                else if constexpr (K == EXT_POOL) hipLaunchKernelGGL((k_extend_pool<L, C, F>), grid, dim3(64), 0, s, a);
+                else if constexpr (K == EXT_PACKED) hipLaunchKernelGGL((k_extend_packed<L, C, F>), grid, dim3(64), 0, s, a);
+                else launch_k_extend<L, C, F, N, E>(s, grid, a, x.nee, x.env);
+            }); });
+        }); });
     }); });
     return known ? hipGetLastError() : hipErrorInvalidValue;
 }
@@ -1965,7 +1950,7 @@ hipError_t launch_gather(hipStream_t s, const DeviceScene &sc, const PathState &
     return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
-hipError_t launch_shade(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp, uint32_t it, uint32_t shard_bound, int mode, bool compact)
+hipError_t launch_shade(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp, uint32_t it, uint32_t shard_bound, ShadeMode mode, bool compact)
 {
     const uint32_t parity = it; // k_shade derives queue parity and counter rotation from the iteration index
     const dim3 grid = shard_grid(blocks_for(shard_bound), ps.shard_count), block(kBlock);

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 #include "../../include/ptrt.h"
+#include "pipeline.h"
 
 namespace ptrt {
 
@@ -34,7 +35,6 @@ constexpr uint32_t kTraceBlocks = 16384;
 #define PT_POOL 128
 #endif
 constexpr uint32_t kPool = PT_POOL;                // queue entries per wavefront of k_extend_pool (64 P)
-enum ExtendKernel : int { EXT_SIMPLE = 1, EXT_PACKED = 2, EXT_POOL = 3 }; // pt_stats.reserved[0]
 
 // Queue sharding. A slot belongs to one shard for the whole frame — k_generate (kernels.hip) deals the groups of 2^kShardGroupShift slots
 // out in rotation: slot group g goes to shard (g % kShards + g / kShards) % kShards, as entry group g / kShards —, every queue is kShards
@@ -181,27 +181,26 @@ inline __host__ __device__ uint32_t div_by(uint32_t n, uint32_t magic, uint32_t 
 // kernel launchers (kernels.hip). All enqueue on `s` and return the launch error.
 // `shard_bound` = upper bound of any shard's queue length for this launch.
 hipError_t launch_reference_sphere(hipStream_t s, uint32_t w, uint32_t h, float4 *out_f, uint32_t *out_rgba8);
-// mode 1: write every slot's initial path state (k_shade and k_extend_pool read it back); 0: queue and counters only — the frame's first
-// launch is a fused one-ray-per-lane or lane-packing kernel, which builds the state in registers; 2: like 0 with the queue dense (only
-// slots that hold a path: frames in which whole sample streams are empty)
-hipError_t launch_generate(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp, uint32_t mode);
+hipError_t launch_generate(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp, GenerateMode mode);
 // The frame's sky pixels (FrameParams::scene_x0 ..), once per frame before the first extend launch: every sample of their slots added
 // to the slot's sum as the traced frame would have. Their rays, one per sample, are the host's to count (frame.cpp finish_frame).
 hipError_t launch_sky_pixels(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp);
-// `it` = iteration index of the wavefront loop: queues alternate by it & 1, queue counters rotate by it % 3.
-// kernel: ExtendKernel. fuse: -1 = extend only (k_shade follows); 0 / 2 = the kernel also shades (Lambert-only / all kinds) and
-// queues the next iteration, honouring `compact` like launch_shade. packed_chunk: queue entries per wavefront of EXT_PACKED.
-// bounces (fused only): path vertices a lane advances per launch.
-// nee (may be NULL): a PT_FLAG_NEXT_EVENT frame; only the one-ray-per-lane kernel, fused (fuse 0 / 2), without counting, has it.
-// env (may be NULL): a frame of a scene with an environment map; the same kernel, with all-kinds shading (fuse 2) only.
-hipError_t launch_extend(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp, uint32_t it, uint32_t shard_bound, bool count,
-                         int kernel, uint32_t packed_chunk, int fuse, bool compact, uint32_t bounces, const NeeArgs *nee = nullptr,
-                         const EnvArgs *env = nullptr);
-// mode: 0 = queue order, specular kinds deferred to buckets; 1 = the specular buckets; 2 = queue order, everything shaded in place
+// One launch of an extend kernel. `it` = iteration index of the wavefront loop: queues alternate by it & 1, queue counters rotate by it % 3.
+// (kernel, fuse, count, nee, env) must name an instantiation that exists (pipeline.h extend_instantiated), else hipErrorInvalidValue.
+struct ExtendLaunch {
+    uint32_t it, shard_bound;   // shard_bound: upper bound of any shard's queue length for this launch
+    ExtendKernel kernel; ShadeMode fuse; bool count, compact; // compact (fused kernels): as for launch_shade
+    uint32_t packed_chunk;      // queue entries per wavefront of EXT_PACKED
+    uint32_t bounces;           // fused only: path vertices a lane advances per launch
+    const NeeArgs *nee;         // a PT_FLAG_NEXT_EVENT frame's block, else NULL
+    const EnvArgs *env;         // the block of a scene with an environment map, else NULL
+};
+hipError_t launch_extend(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp, const ExtendLaunch &x);
+// mode: SHADE_QUEUE, SHADE_BUCKETS or SHADE_INLINE (pipeline.h)
 // compact: 1 = survivors are appended densely to the next queue (ballot + one returning atomic per wavefront);
 //          0 = every lane writes its own position of the next queue (slot or kInvalidSlot): no returning atomics, and the
-//              queue keeps its slot order, which is what keeps the slot-indexed path state coalesced (modes 0 and 2 only)
-hipError_t launch_shade(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp, uint32_t it, uint32_t shard_bound, int mode, bool compact);
+//              queue keeps its slot order, which is what keeps the slot-indexed path state coalesced (SHADE_QUEUE and SHADE_INLINE only)
+hipError_t launch_shade(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp, uint32_t it, uint32_t shard_bound, ShadeMode mode, bool compact);
 // pt_trace_rays: n <= 2^31 caller rays (2 float4 rows each) -> hit records (1 float4 row each), on a grid of trace_blocks(n) workgroups of
 // kExtBlock lanes. ps: only counters (error word and visit counters at kCntGlobals), stack_ovf, stack_ovf_entries and shard_cap are read;
 // shard_cap * kShards must cover trace_blocks(n) * kExtBlock lanes. occlusion and count are exclusive.

@@ -10,6 +10,7 @@ import denoise_checker as dc
 import nee_checker as nc
 import ray_caster64 as rc
 from blob_scenes import blob
+from pipelines import flags_of
 from trace_support import H, LAYOUTS, MISS, W, ids_of, oracle, records
 
 RMSE_TOL = 1e-4  # BASELINE.json north_star: "images within 1e-4 RMSE of the CPU reference"
@@ -120,8 +121,7 @@ def _config_grid(P):
     instantiation (6 x 2), with the layouts cycling underneath them and the builder switching after each pass over the
     five layouts, so every layout and both builders appear too."""
     N = P.native
-    kernels = [0, N.PT_FLAG_EXTEND_SIMPLE, N.PT_FLAG_EXTEND_PACKED, N.PT_FLAG_EXTEND_POOL, N.PT_FLAG_SPLIT_KERNELS,
-               N.PT_FLAG_SPLIT_KERNELS | N.PT_FLAG_EXTEND_PACKED]
+    kernels = flags_of("probed", "simple", "packed", "pool", "split", "split+packed")
     out = []
     for i in range(2 * len(kernels)):
         width = LAYOUTS[i % len(LAYOUTS)] | (N.PT_BVH_BUILD_LBVH if (i // len(LAYOUTS)) % 2 else 0)

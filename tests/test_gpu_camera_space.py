@@ -16,6 +16,7 @@ import camera_space as cs
 import denoise_checker as dc
 import temporal_checker as tr
 from frame_checks import check_denoise, check_nee
+from pipelines import flags_of
 
 pytestmark = pytest.mark.gpu
 
@@ -67,7 +68,7 @@ def test_frames_guides_and_rectangles(P, pto, renderer, case):
         renderer.SetScene(sd, layout)
         p = P.make_params(W, H, spp=4, max_depth=4, streams=2)
         ref, ost, want = reference(P, pto, renderer, sd, p)
-        for flag in (N.PT_FLAG_EXTEND_SIMPLE, N.PT_FLAG_EXTEND_PACKED):
+        for flag in flags_of("simple", "packed"):
             renderer.Params = P.make_params(W, H, spp=4, max_depth=4, streams=2, flags=flag)
             st = renderer.Render(0.0)
             same_frame(renderer, st, ref, ost, (case, name, flag))
@@ -112,7 +113,7 @@ def test_one_camera_ray_per_sample(P, pto, renderer, case):
         table, layout = cases_of(P, name)
         sd = table[case]
         renderer.SetScene(sd, layout)
-        for flag, streams in ((N.PT_FLAG_EXTEND_SIMPLE, 2), (N.PT_FLAG_EXTEND_PACKED, 4)):
+        for flag, streams in zip(flags_of("simple", "packed"), (2, 4)):
             renderer.Params = p = P.make_params(W, H, spp=64, max_depth=1, streams=streams, flags=flag)
             ref, ost, want = reference(P, pto, renderer, sd, p)
             st = renderer.Render(0.0)

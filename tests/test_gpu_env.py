@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import env_checker as ec
+from pipelines import refused
 from trace_support import H, LAYOUTS, W
 
 pytestmark = pytest.mark.gpu
@@ -210,7 +211,7 @@ def test_refused_pipelines(P, pto, renderer, sun):
     sd = dataclasses.replace(ec.scene(P, "cornell", W, H), environment=sun)
     renderer.SetScene(sd, 0)
     for nee in (False, True):
-        for flags in (N.PT_FLAG_EXTEND_PACKED, N.PT_FLAG_EXTEND_POOL, N.PT_FLAG_SPLIT_KERNELS, N.PT_FLAG_BUCKET_SPECULAR, N.PT_FLAG_COUNT_VISITS):
+        for flags in [r.flags for r in refused("env")]:
             p = params_of(P, nee, spp=2, max_depth=8)
             p.flags |= flags
             renderer.Params = p
@@ -219,7 +220,7 @@ def test_refused_pipelines(P, pto, renderer, sun):
             assert e.value.status == N.PT_ERR_UNSUPPORTED, flags
     tuning = renderer.GetTuning().extend_kernel
     try:
-        for k in (2, 3):
+        for k in [r.tuned_kernel for r in refused("env", tuned=True)]:
             renderer.SetTuning(extend_kernel=k)
             renderer.Params = params_of(P, False, spp=2, max_depth=8)
             with pytest.raises(P.PtException, match="environment") as e:

@@ -14,6 +14,7 @@ import adversarial_scenes as S
 import ray_caster64 as rc
 from float64_support import CRACK_RAYS, PINNED_CRACKS, W, H, _size, check_classes, crack_rays, scenes
 from frame_checks import _config_grid, run_both
+from pipelines import flags_of
 from geometry_space import SCALE_K
 from trace_support import LAYOUTS
 
@@ -54,7 +55,7 @@ def test_duplicates_lowest_id_wins_on_every_kernel(P, pto, renderer):
     LBVH = N.PT_BVH_BUILD_LBVH
     sd, src = S.duplicates(W, H)
     lowest = np.array([np.nonzero(src == s)[0].min() for s in src], np.uint64)
-    for flags in (0, N.PT_FLAG_EXTEND_SIMPLE, N.PT_FLAG_EXTEND_PACKED, N.PT_FLAG_EXTEND_POOL, N.PT_FLAG_SPLIT_KERNELS):
+    for flags in flags_of("probed", "simple", "packed", "pool", "split"):
         for width in (68, 2 | LBVH):
             p = S.params_id(W, H)
             p.flags = flags
@@ -93,7 +94,7 @@ def test_stacked_layers_spill_on_shard_groups(P, pto, loops):
     try:
         r.SetTuning(loops=loops)
         for i, width in enumerate(LAYOUTS):
-            for flags in (0, N.PT_FLAG_EXTEND_PACKED, N.PT_FLAG_EXTEND_POOL, N.PT_FLAG_SPLIT_KERNELS):
+            for flags in flags_of("probed", "packed", "pool", "split"):
                 p = P.make_params(96, 64, spp=4, max_depth=12, streams=4, flags=flags)
                 img, st, ref, ost = run_both(P, pto, r, sd, p, width | (LBVH if i % 2 else 0), count=(flags == 0))
                 assert r.BvhInfo().stack_need > 12
@@ -104,7 +105,7 @@ def test_stacked_layers_spill_on_shard_groups(P, pto, loops):
         r.Dispose()
 
 
-@pytest.mark.parametrize("flags", [0, 4, 8, 64, 128])  # probed, lane-packing, one ray per lane, split kernels, pooled
+@pytest.mark.parametrize("flags", flags_of("probed", "packed", "simple", "split", "pool"))
 def test_long_sphere_lists(P, pto, renderer, flags):
     """10, 31 (the camera inside a glass ball: the t1 root), 63 and 64 spheres on every kernel: the oracle's frame, ray count and
     visit counters, with sphere_tests == n * rays. 65 spheres are refused."""

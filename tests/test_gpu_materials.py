@@ -10,6 +10,7 @@ import denoise_checker as dc
 import material_zoo as mz
 from frame_checks import check_denoise, check_nee, run_both
 from material_zoo import NEE_CONFIGS, emissive_triangles
+from pipelines import named_flags
 
 pytestmark = pytest.mark.gpu
 
@@ -17,9 +18,7 @@ ZOO_LAYOUTS = [0, 68, 73]
 
 
 def pipelines(P):
-    N = P.native
-    return [("probed", 0), ("simple", N.PT_FLAG_EXTEND_SIMPLE), ("packed", N.PT_FLAG_EXTEND_PACKED), ("pool", N.PT_FLAG_EXTEND_POOL),
-            ("split", N.PT_FLAG_SPLIT_KERNELS), ("bucket", N.PT_FLAG_BUCKET_SPECULAR)]
+    return named_flags("probed", "simple", "packed", "pool", "split", "bucket")
 
 
 def equal_to_the_oracle(P, pto, r, sd, params, layout, count, ctx):
@@ -49,7 +48,7 @@ def test_depth_and_roulette_edges(P, pto, renderer, cfg, key):
     """max_depth 1, 2 and 255, Russian roulette from the first vertex and never, fewer samples than streams."""
     N = P.native
     sd = mz.build(*cfg)
-    for name, flags in (("probed", 0), ("pool", N.PT_FLAG_EXTEND_POOL), ("bucket", N.PT_FLAG_BUCKET_SPECULAR)):
+    for name, flags in named_flags("probed", "pool", "bucket"):
         st = equal_to_the_oracle(P, pto, renderer, sd, mz.edge_params(P, key, flags), 0, False, (cfg, key, name))
         if key == "depth1":
             assert st.rays == mz.W * mz.H * 4

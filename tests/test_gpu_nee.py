@@ -9,6 +9,7 @@ import pytest
 import nee_checker as nc
 from frame_checks import check_nee as check
 from frame_checks import nee_params
+from pipelines import refused
 from trace_support import H, LAYOUTS, W
 
 pytestmark = pytest.mark.gpu
@@ -157,7 +158,7 @@ def test_refused_pipelines(P, pto, renderer):
     N = P.native
     sd = scenes(P)["cornell"]
     renderer.SetScene(sd, 0)
-    for flags in (N.PT_FLAG_EXTEND_PACKED, N.PT_FLAG_EXTEND_POOL, N.PT_FLAG_SPLIT_KERNELS, N.PT_FLAG_BUCKET_SPECULAR, N.PT_FLAG_COUNT_VISITS):
+    for flags in [r.flags for r in refused("nee")]:
         p = nee_params(P, spp=2, max_depth=8)
         p.flags |= flags
         renderer.Params = p
@@ -166,7 +167,7 @@ def test_refused_pipelines(P, pto, renderer):
         assert e.value.status == N.PT_ERR_UNSUPPORTED, flags
     tuning = renderer.GetTuning().extend_kernel
     try:
-        for k in (2, 3):
+        for k in [r.tuned_kernel for r in refused("nee", tuned=True)]:
             renderer.SetTuning(extend_kernel=k)
             renderer.Params = nee_params(P, spp=2, max_depth=8)
             with pytest.raises(P.PtException) as e:

@@ -10,6 +10,7 @@ import pytest
 
 from frame_checks import RMSE_TOL, assert_parity, rmse, run_both
 from numpy_radiance import numpy_radiance
+from pipelines import flags_of
 from reference_kat import check_against_kat
 from trace_support import LAYOUTS
 
@@ -565,7 +566,7 @@ def test_shard_groups_on_separate_streams(P, pto, monkeypatch):
     assert all(f[0] == frames[0][0] and np.array_equal(f[1], frames[0][1]) for f in frames)
 
 
-@pytest.mark.parametrize("flags", [0, 4, 128, 64, 68])  # fused one-ray-per-lane / lane-packing / pooled kernels, and the first two followed by k_shade (PT_FLAG_SPLIT_KERNELS)
+@pytest.mark.parametrize("flags", flags_of("probed", "packed", "pool", "split", "split+packed"))  # the fused kernels, and the first two followed by k_shade
 def test_queue_compaction_policy_is_invisible(P, pto, monkeypatch, flags):
     """pt_tuning.compact_below / sticky_samples: queues carried over in place with holes (0 = never re-packed), re-packed every
     launch (2), re-packed when the predicted alive/length ratio is < 0.9 or 0.5, and the short-frame rule (2 samples per stream:
@@ -593,7 +594,7 @@ def test_queue_compaction_policy_is_invisible(P, pto, monkeypatch, flags):
     assert frames[4][2] == frames[1][2] and frames[5][2] == 0      # short frame: every launch; compact_below 0 switches that off too
 
 
-@pytest.mark.parametrize("flags", [8, 128])
+@pytest.mark.parametrize("flags", flags_of("simple", "pool"))
 def test_sticky_repacking_of_short_frames(P, pto, flags):
     """A frame of few samples per stream (here 3) re-packs a shard's queue in every launch once the shard has re-packed at all;
     with sticky_samples = 0 only the predicted ratio decides. Same picture, more re-packs."""
@@ -804,8 +805,7 @@ def test_randomised_configurations_against_the_oracle(P, pto, renderer):
                 spp = int(rng.integers(34, 48))  # many samples per stream: the predicted-ratio rule, not the sticky one
             streams = int(rng.choice([0, 1, 2, 3, 8, 16]))
             width = int(rng.choice([0, 2, 4, 68, 72, 73]))
-            flags = int(rng.choice([0, 0, N.PT_FLAG_EXTEND_PACKED, N.PT_FLAG_EXTEND_SIMPLE, N.PT_FLAG_EXTEND_POOL, N.PT_FLAG_EXTEND_POOL,
-                                    N.PT_FLAG_SPLIT_KERNELS, N.PT_FLAG_SPLIT_KERNELS | N.PT_FLAG_EXTEND_PACKED, N.PT_FLAG_BUCKET_SPECULAR]))
+            flags = int(rng.choice(flags_of("probed", "probed", "packed", "simple", "pool", "pool", "split", "split+packed", "bucket")))
             offset = int(rng.integers(0, 5))
             tune = dict(loops=int(rng.choice([0, 1, 2, 4])), bounces=int(rng.choice([0, 0, 1, 2, 3, 5, 8])),
                         compact_below=float(rng.choice([0.0, 0.5, 0.9, 0.9, 1.0, 2.0])), sticky_samples=int(rng.choice([0, 2, 32, 32, 1000])),
@@ -826,7 +826,7 @@ def test_randomised_configurations_against_the_oracle(P, pto, renderer):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("flags", [8, 4, 128])  # one ray per lane, lane-packing, pooled
+@pytest.mark.parametrize("flags", flags_of("simple", "packed", "pool"))
 def test_sphere_lists_of_any_length(P, pto, renderer, flags):
     """The kernels read the sphere list four spheres per scalar load (device arrays padded to a multiple of four): lists of
     0, 1, 2, 3, 5, 6, 9, 10, 31, 63 and 64 (the limit) spheres must give the oracle's frame, ray count and sphere-test count."""

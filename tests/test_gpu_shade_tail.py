@@ -19,6 +19,7 @@ import pytest
 import material_zoo as mz
 import nee_checker as nc
 from frame_checks import check_nee
+from pipelines import named_flags
 
 pytestmark = pytest.mark.gpu
 
@@ -57,9 +58,7 @@ SCENES = {"box": box, "open": open_air, "palette": lambda: mz.build("palette", "
 
 
 def pipelines(P):
-    N = P.native
-    return [("simple", N.PT_FLAG_EXTEND_SIMPLE), ("probed", 0), ("packed", N.PT_FLAG_EXTEND_PACKED), ("split", N.PT_FLAG_SPLIT_KERNELS),
-            ("bucket", N.PT_FLAG_BUCKET_SPECULAR), ("pool", N.PT_FLAG_EXTEND_POOL)]
+    return named_flags("simple", "probed", "packed", "split", "bucket", "pool")
 
 
 def frame(P, r, params):

@@ -16,6 +16,7 @@ import pytest
 import env_checker as ec
 from camera_space import SKY, empty_like, scene_of, spheres_only, turned
 from frame_checks import check_nee, run_both
+from pipelines import flags_of
 
 pytestmark = pytest.mark.gpu
 
@@ -95,7 +96,7 @@ def test_both_kernels(P, pto, renderer):
     N = P.native
     for kind, w, h in (("PT_SCENE_CORNELL_TESS", 200, 150), ("PT_SCENE_CORNELL_GLASS", 100, 37)):
         sd = scene_of(P, kind, w, h)
-        for flag in (N.PT_FLAG_EXTEND_SIMPLE, N.PT_FLAG_EXTEND_PACKED):
+        for flag in flags_of("simple", "packed"):
             for spp, streams in ((7, 4), (3, 8)):
                 _, st, _, _ = exact(P, pto, renderer, sd, P.make_params(w, h, spp=spp, max_depth=8, streams=streams, flags=flag))
                 assert st.reserved[0] == (2 if flag == N.PT_FLAG_EXTEND_PACKED else 1)
@@ -154,7 +155,7 @@ def test_refit_moves_the_bound(P, pto, renderer):
 def test_count_visits_frames_keep_the_specs_visits(P, pto, renderer):
     N = P.native
     sd = scene_of(P, "PT_SCENE_CORNELL_TESS", 200, 150)
-    for flag in (N.PT_FLAG_EXTEND_SIMPLE, N.PT_FLAG_EXTEND_PACKED):
+    for flag in flags_of("simple", "packed"):
         p = P.make_params(200, 150, spp=3, max_depth=6, streams=2, flags=flag)
         img, st, ref, ost = run_both(P, pto, renderer, sd, p, 0, count=True)
         assert has_both(P, pto, sd, p, ref) and np.array_equal(img, ref)
@@ -207,7 +208,7 @@ def test_sky_frame_needs_no_launches(P, pto):
         r.SetTuning(finish_below=0)
         t = r.GetTuning()
         lag = t.lag or 3 + (1 if t.readback == 0 else 0)
-        for flag in (P.native.PT_FLAG_EXTEND_SIMPLE, P.native.PT_FLAG_EXTEND_PACKED):
+        for flag in flags_of("simple", "packed"):
             p = P.make_params(w, h, spp=64, max_depth=8, streams=1, flags=flag)
             img, st, ref, ost = run_both(P, pto, r, sd, p, 0)
             void, _ = pto.render(pto.Scene(empty_like(P, sd)), p)

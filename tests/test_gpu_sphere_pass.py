@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import material_zoo as mz
+from pipelines import named_flags
 from trace_support import MISS, check_closest, commit, ids_of, oracle, records, same
 
 pytestmark = pytest.mark.gpu
@@ -173,7 +174,7 @@ def test_frames(P, pto, renderer, n, with_tris):
         renderer.SetScene(sd, layout)
         osc = pto.Scene(sd, (renderer.BvhInfo().width,) + renderer.BvhRead())
         ref = None
-        for name, flag in (("simple", N.PT_FLAG_EXTEND_SIMPLE), ("packed", N.PT_FLAG_EXTEND_PACKED), ("pool", N.PT_FLAG_EXTEND_POOL)):
+        for name, flag in named_flags("simple", "packed", "pool"):
             params = P.make_params(W, H, spp=4, max_depth=8, streams=2, flags=flag)
             if ref is None:
                 ref, ost = pto.render(osc, params)

@@ -7,9 +7,10 @@ import sys
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle"))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle")); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import pathtracing_amd as P
 import pto  # the checker
+from pipelines import flags_of  # the one table of pipelines
 
 N = P.native
 seed = int(sys.argv[1]) if len(sys.argv) > 1 else 1
@@ -27,8 +28,7 @@ for case in range(cases):
         spp = int(rng.integers(34, 80))
     streams = int(rng.choice([0, 1, 2, 3, 8, 16]))
     width = int(rng.choice([0, 2, 4, 68, 72, 73]))
-    flags = int(rng.choice([0, 0, 0, N.PT_FLAG_EXTEND_PACKED, N.PT_FLAG_EXTEND_SIMPLE, N.PT_FLAG_EXTEND_POOL, N.PT_FLAG_SPLIT_KERNELS,
-                            N.PT_FLAG_SPLIT_KERNELS | N.PT_FLAG_EXTEND_PACKED, N.PT_FLAG_BUCKET_SPECULAR]))
+    flags = int(rng.choice(flags_of("probed", "probed", "probed", "packed", "simple", "pool", "split", "split+packed", "bucket")))
     if rng.integers(4) == 0 and width in (0, 68):
         width = 68 | N.PT_BVH_BUILD_LBVH  # hierarchy built (and, for this layout, packed) on the GPU
     nranks = int(rng.choice([1, 1, 1, 2, 3, 8]))  # > 1: virtual ranks on this GPU through pt_comm
