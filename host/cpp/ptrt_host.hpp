@@ -101,6 +101,15 @@ public:
         if (n && rgb.size() < (size_t)n * n * 3) throw Error(PT_ERR_INVALID_ARGUMENT, "set_environment: fewer than n * n * 3 floats");
         check(pt_scene_set_environment(scene_, n ? rgb.data() : nullptr, n), ctx_);
     }
+    // docs/SPEC.md §3.1: a thin lens of aperture `radius` focused at `focus_distance` (depth of field); radius 0 is the pinhole. No new
+    // commit needed; a caller that changes the lens restarts accumulation.
+    void set_lens(float radius, float focus_distance)
+    {
+        pt_lens lens{}; lens.radius = radius; lens.focus_distance = focus_distance;
+        check(pt_scene_set_lens(scene_, &lens), ctx_);
+    }
+    void clear_lens() { check(pt_scene_set_lens(scene_, nullptr), ctx_); }
+    pt_lens lens() const { pt_lens l{}; check(pt_scene_get_lens(scene_, &l), ctx_); return l; }
     // docs/SPEC.md §9: reproject the previous call's accumulated image to this frame and blend the last frame in; with `filter` the
     // §8.2 filter then runs over the result (ReadDenoised). Zeros mean the defaults; the context keeps the history between calls.
     pt_stats DenoiseTemporal(uint32_t max_history = 0, uint32_t flags = 0, bool filter = true, uint32_t iterations = 0)
@@ -213,6 +222,7 @@ public:
         r_[0]->Params = Params;
     }
     void set_environment(const std::vector<float> &rgb, uint32_t n) { for (auto &r : r_) r->set_environment(rgb, n); }
+    void set_lens(float radius, float focus_distance) { for (auto &r : r_) r->set_lens(radius, focus_distance); }
     Renderer &Root() { return *r_[0]; }
     void Dispose()
     {

@@ -181,6 +181,15 @@ public unsafe class HipRenderer : IDisposable
         fixed (float* p = rgb) Ptrt.Check(Ptrt.pt_scene_set_environment(_scene, p, n), _ctx);
     }
 
+    // Give the current scene a thin lens (docs/SPEC.md §3.1: depth of field): an aperture of `radius` world units focused at
+    // `focusDistance`; radius 0 is the pinhole, and ClearLens removes the lens. No new commit needed; restart accumulation after a change.
+    public void SetLens(float radius, float focusDistance)
+    {
+        var lens = new PtLens { radius = radius, focus_distance = focusDistance };
+        Ptrt.Check(Ptrt.pt_scene_set_lens(_scene, &lens), _ctx);
+    }
+    public void ClearLens() { Ptrt.Check(Ptrt.pt_scene_set_lens(_scene, null), _ctx); }
+
     // Temporal accumulation (docs/SPEC.md §9), the call of a render-every-frame loop whose camera or geometry moves: reprojects the
     // previous call's accumulated image to this frame, blends the last Render in, and (filter = true) runs Denoise's filter over the
     // result. Zeros mean the defaults. ReadTemporal / ReadHistoryLength / ReadDenoised hold until the next Render; the history itself

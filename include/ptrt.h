@@ -35,7 +35,7 @@ extern "C" {
  * pt_temporal_read / pt_temporal_device_ptr / pt_temporal_history_read, then pt_display, pt_display_params, pt_display_info, PT_DISPLAY_*,
  * PT_TONE_*, pt_display_read / pt_display_device_ptr / pt_display_info_read / pt_display_histogram_read, then PT_TEMPORAL_MOTION, then
  * pt_scene_set_environment, pt_environment_info and pt_scene_environment_info / pt_scene_environment_read, then pt_gather, pt_gather_params and
- * PT_GATHER_HOST_MEMORY (additions only: no struct or
+ * PT_GATHER_HOST_MEMORY, then pt_lens and pt_scene_set_lens / pt_scene_get_lens (additions only: no struct or
  * existing signature changed).
  * Hosts compare pt_abi_version() with the header they were built against. */
 #define PTRT_ABI_VERSION 2
@@ -233,6 +233,31 @@ pt_status pt_scene_environment_info(const pt_scene *s, pt_environment_info *out)
 /* the sampling table exactly as the kernels read it: n*n float4 (r,g,b,p), n marginal cdf entries, n*n conditional cdf entries;
  * n_texels = the texels the three arrays have room for (>= n*n) */
 pt_status pt_scene_environment_read(const pt_scene *s, float *texels4, float *mcdf, float *ccdf, uint64_t n_texels);
+/* Thin-lens camera (docs/SPEC.md §3.1): depth of field. With radius > 0 every camera ray of a PT_PATH_TRACE frame starts at a point drawn
+ * uniformly on the disc of that radius around the camera's origin, in the plane of `right` and `up`, and passes through the point the
+ * pinhole ray of the same sample reaches at origin + focus_distance * (forward + sx * right + sy * up): what lies there is sharp, everything
+ * else is blurred by a disc that grows with the aperture. radius == 0 is no lens: every frame is then bit for bit the pinhole frame. The
+ * two random numbers of the disc are RNG dimensions 2 and 3, which nothing else draws, so every other random number of a path is the
+ * pinhole frame's; rays and paths are counted as before. */
+typedef struct pt_lens {
+    float radius;          /* aperture radius in world units; finite, >= 0; 0 = pinhole */
+    float focus_distance;  /* F, in units of |forward| along the view axis; finite, > 0 */
+    uint32_t flags;        /* 0; any bit set is PT_ERR_INVALID_ARGUMENT */
+    uint32_t pad[5];
+} pt_lens;                 /* 32 B */
+/* lens == NULL removes the lens. A refused call (PT_ERR_INVALID_ARGUMENT: a negative, NaN or infinite radius, a focus_distance that is not
+ * finite and > 0, a flag bit) keeps the previous lens. Works before and after pt_scene_commit — like pt_scene_set_sky it takes effect with
+ * the next pt_render without a new commit —, survives commits, pt_scene_update_triangles / pt_scene_update_spheres and pt_scene_set_camera
+ * (the aperture follows the camera's current right and up), and works on a detached scene (host values only). A caller that changes the
+ * lens restarts accumulation: the library does not notice that PT_FLAG_ACCUMULATE sums were made through another lens.
+ * Frames with radius > 0 run on the one-ray-per-lane kernel with all-kinds shading (pt_stats.reserved[0] = 1, no kernel probe), with and
+ * without PT_FLAG_NEXT_EVENT and an environment map: with PT_FLAG_EXTEND_PACKED / _POOL, PT_FLAG_SPLIT_KERNELS / _BUCKET_SPECULAR,
+ * PT_FLAG_COUNT_VISITS or pt_tuning.extend_kernel 2 / 3 they are PT_ERR_UNSUPPORTED. They resolve no sky pixels (pt_stats.reserved[3] = 0).
+ * A camera whose right or up has length 0, or whose aperture axes (radius * right / |right|, radius * up / |up|, in f32) are not finite,
+ * makes such a pt_render PT_ERR_INVALID_ARGUMENT. Only PT_PATH_TRACE frames see the lens: PT_REFERENCE_SPHERE, pt_trace_rays, pt_gather,
+ * the guide pass of pt_denoise / pt_denoise_temporal (with its reprojection: they keep the pinhole centre ray) and pt_display do not. */
+pt_status pt_scene_set_lens(pt_scene *s, const pt_lens *lens);
+pt_status pt_scene_get_lens(const pt_scene *s, pt_lens *out);   /* radius 0, focus_distance 0 when none is set */
 /* builds the BVH on the host (binned SAH) and uploads everything; replaces CreateComputePipeline's one-time
  * descriptor/pipeline set-up (Renderer.cs:293-403). bvh_width: PT_BVH_WIDTH_* */
 pt_status pt_scene_commit(pt_scene *s, uint32_t bvh_width);

@@ -127,6 +127,10 @@ class pt_gather_params(C.Structure):
                 ("max_distance", C.c_float), ("ray_eps", C.c_float), ("flags", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class pt_lens(C.Structure):
+    _fields_ = [("radius", C.c_float), ("focus_distance", C.c_float), ("flags", C.c_uint32), ("pad", C.c_uint32 * 5)]
+
+
 class pt_scene_counts(C.Structure):
     _fields_ = [("n_tris", C.c_uint64), ("n_spheres", C.c_uint64), ("n_mats", C.c_uint64)]
 
@@ -134,7 +138,7 @@ class pt_scene_counts(C.Structure):
 assert C.sizeof(pt_material) == 48 and C.sizeof(pt_camera) == 64 and C.sizeof(pt_render_params) == 64 and C.sizeof(pt_tuning) == 40
 assert C.sizeof(pt_denoise_params) == 32 and C.sizeof(pt_temporal_params) == 32
 assert C.sizeof(pt_display_params) == 40 and C.sizeof(pt_display_info) == 32 and C.sizeof(pt_environment_info) == 24
-assert C.sizeof(pt_gather_params) == 32
+assert C.sizeof(pt_gather_params) == 32 and C.sizeof(pt_lens) == 32
 
 _vp, _u32, _u64, _st = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int32
 _P = C.POINTER
@@ -157,6 +161,8 @@ SYMBOLS = {
     "pt_scene_set_environment": (_st, [_vp, _vp, _u32]),
     "pt_scene_environment_info": (_st, [_vp, _P(pt_environment_info)]),
     "pt_scene_environment_read": (_st, [_vp, _vp, _vp, _vp, _u64]),
+    "pt_scene_set_lens": (_st, [_vp, _P(pt_lens)]),
+    "pt_scene_get_lens": (_st, [_vp, _P(pt_lens)]),
     "pt_scene_commit": (_st, [_vp, _u32]),
     "pt_scene_bvh_info": (_st, [_vp, _P(pt_bvh_info)]),
     "pt_scene_bvh_read": (_st, [_vp, _vp, _u64, _vp, _u64]),

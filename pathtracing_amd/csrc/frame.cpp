@@ -148,11 +148,27 @@ uint64_t scene_pixels_code(const FrameParams &fp)
     return (uint64_t)fp.scene_x0 | (uint64_t)fp.scene_x1 << 16 | (uint64_t)fp.scene_y0 << 32 | (uint64_t)fp.scene_y1 << 48;
 }
 
+// The aperture's axes of a frame through a lens (docs/SPEC.md §3.1), in f32 with §0's dot: radius * right / |right| and radius * up / |up| of
+// the frame's camera. False for a degenerate basis: a zero dot product, or a component that is not finite.
+bool lens_basis(const pt_camera &cam, const pt_lens &lens, LensArgs &out)
+{
+    auto dot = [](const float *a) { return std::fma(a[2], a[2], std::fma(a[1], a[1], a[0] * a[0])); };
+    const float dr = dot(cam.right), du = dot(cam.up);
+    if (dr == 0.0f || du == 0.0f) return false;
+    const float ru = lens.radius * (1.0f / std::sqrt(dr)), rv = lens.radius * (1.0f / std::sqrt(du));
+    for (int k = 0; k < 3; ++k) {
+        out.u[k] = cam.right[k] * ru; out.v[k] = cam.up[k] * rv;
+        if (!std::isfinite(out.u[k]) || !std::isfinite(out.v[k])) return false;
+    }
+    out.focus = lens.focus_distance; out.pad = 0u;
+    return true;
+}
+
 struct Frame {                  // a path-traced frame as plan_frame lays it out, and what its loops leave for finish_frame
     uint32_t nranks, streams, pixel_slots, n_slots, shard_cap, samples_per_stream, lag, n_loops, packed_chunk, default_bounces;
     Pipeline pipe;              // what the frame's flags, pt_tuning.extend_kernel and the scene decode to (pipeline.h)
     bool accumulate, mapped, compact;
-    NeeArgs nee_args; EnvArgs env_args; // the blocks of a pipe.nee / pipe.env frame
+    NeeArgs nee_args; EnvArgs env_args; LensArgs lens_args; // the blocks of a pipe.nee / pipe.env / pipe.lens frame
     bool sky;                   // the frame has sky pixels (scene_pixels) and resolves them at its start instead of tracing their paths
     Accumulation::Key sums_key; // what the sums hold once this frame completes
     size_t q_entries; uint64_t total_spp, allocs_before;
@@ -207,9 +223,11 @@ static pt_status plan_frame(pt_context *c, const pt_scene *s, const pt_render_pa
     const uint32_t groups = (f.n_slots + (1u << kShardGroupShift) - 1u) >> kShardGroupShift, shard_cap = ((groups + kShards - 1) / kShards) << kShardGroupShift;
     f.shard_cap = shard_cap; f.q_entries = (size_t)kShards * shard_cap;
     f.samples_per_stream = (p->spp + f.streams - 1u) / f.streams;
-    const PipelineDecode d = decode_pipeline(p->flags, t.extend_kernel, s->env.present(), s->has_specular);
+    const PipelineDecode d = decode_pipeline(p->flags, t.extend_kernel, s->env.present(), s->has_specular, s->lens.radius > 0.f);
     if (d.status != PT_OK) return fail(c, d.status, "%s", d.message);
     const Pipeline &pipe = f.pipe = d.pipeline;
+    if (pipe.lens && !lens_basis(s->ds.cam, s->lens, f.lens_args))
+        return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_render through a lens: the camera's right or up has length 0, or the aperture's axes are not finite");
     f.mapped = t.readback == 0u; // queue sizes reach the host by the kernels' own stores (fold_traced) instead of a copy per launch
     // rays per wavefront of the lane-packing kernel: 256 once several sample streams keep the queues long, else 128 (measured)
     f.packed_chunk = t.packed_chunk >= 64u ? t.packed_chunk : (f.streams >= 4u ? 256u : 128u);
@@ -337,7 +355,7 @@ static pt_status run_loops(pt_context *c, const pt_scene *s, const pt_render_par
             if (probing) HIP_TRY(c, hipEventRecord(c->ev_probe[(it - 2u) * 2u], L.stream));
             const ExtendLaunch launch{ it, L.bound, kernel, pipe.fuse(), pipe.count, f.compact, f.packed_chunk,
                                        c->tuning.bounces ? c->tuning.bounces : x.bounces(g, it, kernel, f.default_bounces),
-                                       pipe.nee ? &f.nee_args : nullptr, pipe.env ? &f.env_args : nullptr };
+                                       pipe.nee ? &f.nee_args : nullptr, pipe.env ? &f.env_args : nullptr, pipe.lens ? &f.lens_args : nullptr };
             HIP_TRY(c, launch_extend(L.stream, s->ds, pg, f.fp, launch));
             if (pipe.profile) HIP_TRY(c, hipEventRecord(e1, L.stream));
             if (pipe.bucket) {

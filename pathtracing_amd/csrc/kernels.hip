@@ -115,6 +115,20 @@ PT_DEV const ExtArgsT<NEE, ENV> &kernargs()
     return *(const ExtArgsT<NEE, ENV> *)p;
 }
 PT_DEV const ExtArgs &cold() { return kernargs<false, false>().x; }
+// The lens instantiations k_extend<L, false, FUSE_LENS, NEE, ENV> (docs/SPEC.md §3.1): the same block with LensArgs behind it, read through lens_args().
+template <bool NEE, bool ENV> struct ExtLensArgsT { ExtArgsT<NEE, ENV> a; LensArgs lens; };
+static_assert(__builtin_offsetof(ExtLensArgsT<false, false>, lens) == sizeof(ExtArgsT<false, false>) && __builtin_offsetof(ExtLensArgsT<true, false>, lens) == sizeof(ExtArgsT<true, false>) &&
+              __builtin_offsetof(ExtLensArgsT<false, true>, lens) == sizeof(ExtArgsT<false, true>) && __builtin_offsetof(ExtLensArgsT<true, true>, lens) == sizeof(ExtArgsT<true, true>) &&
+              __builtin_offsetof(ExtLensArgsT<true, true>, a) == 0, "the lens block directly behind the others, which stay where every instantiation reads them");
+template <bool NEE, bool ENV>
+PT_DEV const LensArgs &lens_args()
+{
+    auto p = __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return ((const ExtLensArgsT<NEE, ENV> *)p)->lens;
+}
+template <bool NEE, bool ENV> PT_DEV const ExtArgs &ext_of(const ExtArgsT<NEE, ENV> &t) { return t.x; }
+template <bool NEE, bool ENV> PT_DEV const ExtArgs &ext_of(const ExtLensArgsT<NEE, ENV> &t) { return t.a.x; }
 
 // Slot order. A slot is one (pixel slot, stream) pair; 64 consecutive slots are one 8x8 pixel block of one stream (a
 // wavefront). The K streams of a block are K consecutive 64-slot groups, so that wavefronts that run at the same time
@@ -170,6 +184,10 @@ PT_DEV Camera camera_of(const pt_camera &c)
 }
 PT_DEV void camera_ray_of(const pt_camera &c, uint32_t x, uint32_t y, uint32_t key, V3 &o, V3 &d) { camera_ray(camera_of(c), x, y, key, o, d); }
 PT_DEV V3 camera_vec_of(const pt_camera &c, uint32_t x, uint32_t y, float jx, float jy) { return camera_vec(camera_of(c), x, y, jx, jy); }
+PT_DEV void lens_ray_of(const pt_camera &c, const LensArgs &l, uint32_t x, uint32_t y, uint32_t key, V3 &o, V3 &d)
+{
+    lens_ray(camera_of(c), v3(l.u[0], l.u[1], l.u[2]), v3(l.v[0], l.v[1], l.v[2]), l.focus, x, y, key, o, d);
+}
 
 // ------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(kBlock) k_reference_sphere(uint32_t w, uint32_t h, float4 *out_f, uint32_t *out8)
@@ -489,29 +507,35 @@ PT_DEV uint32_t first_sample(uint32_t slot, const FrameParams &fp)
     return v >= fp.streams ? v - fp.streams : v;
 }
 // The start of camera sample r.sample of pixel (x, y). RAY == false: only the ray's origin; shade_one's shared end makes the direction.
-template <bool RAY = true>
-PT_DEV void camera_sample(const DeviceScene &sc, const FrameParams &fp, uint32_t x, uint32_t y, PathRegs &r, uint32_t &depth)
+// LENS (k_extend<.., FUSE_LENS, ..>, docs/SPEC.md §3.1): the ray through `lens`, origin and direction in one piece — the shared
+// end belongs to the lean Lambert-only instantiations, which have no lens form.
+template <bool RAY = true, bool LENS = false>
+PT_DEV void camera_sample(const DeviceScene &sc, const FrameParams &fp, uint32_t x, uint32_t y, PathRegs &r, uint32_t &depth, const LensArgs *lens = nullptr)
 {
+    static_assert(RAY || !LENS, "a lens ray's origin and direction are made together");
     r.key = path_key(fp.seed_hashed, y * fp.width + x, fp.sample_offset + r.sample);
-    if constexpr (RAY) camera_ray_of(sc.cam, x, y, r.key, r.o, r.d);
+    if constexpr (LENS) lens_ray_of(sc.cam, *lens, x, y, r.key, r.o, r.d);
+    else if constexpr (RAY) camera_ray_of(sc.cam, x, y, r.key, r.o, r.d);
     else r.o = v3(sc.cam.origin[0], sc.cam.origin[1], sc.cam.origin[2]);
     r.T = v3(1.f, 1.f, 1.f); depth = 0;
 }
 // The state a slot starts the frame with: the camera ray of its stream's first sample (slot_pixel(slot) must be on the image).
-PT_DEV void path_init(const DeviceScene &sc, const FrameParams &fp, uint32_t slot, PathRegs &r)
+template <bool LENS = false>
+PT_DEV void path_init(const DeviceScene &sc, const FrameParams &fp, uint32_t slot, PathRegs &r, const LensArgs *lens = nullptr)
 {
     uint32_t x = 0, y = 0;
     slot_pixel(slot, fp, x, y);
     r.sample = first_sample(slot, fp);
-    camera_sample(sc, fp, x, y, r, r.depth);
+    camera_sample<true, LENS>(sc, fp, x, y, r, r.depth, lens);
 }
 // The state a fused extend kernel starts a slot with in launch `it`: the frame's first launch makes it itself (api.cpp: q_init) and
-// starts the slot's radiance sum; every later one loads what the launch before it stored (NEE: and the words path_store<NEE> added).
-template <bool NEE = false>
-PT_DEV void path_begin(uint32_t it, uint32_t slot, PathRegs &r, NeeRegs *nr = nullptr)
+// starts the slot's radiance sum; every later one loads what the launch before it stored (NEE: and the words path_store<NEE> added) —
+// its ray's origin included, which is how a lens ray (LENS) keeps its own origin across launches.
+template <bool NEE = false, bool LENS = false>
+PT_DEV void path_begin(uint32_t it, uint32_t slot, PathRegs &r, NeeRegs *nr = nullptr, const LensArgs *lens = nullptr)
 {
     if (it == 0u) {
-        path_init(cold().sc, cold().fp, slot, r);
+        path_init<LENS>(cold().sc, cold().fp, slot, r, lens);
         if (!cold().fp.accumulate) at(cold().ps.acc, slot) = make_float4(0.f, 0.f, 0.f, 0.f);
     } else {
         const PathState &ps = cold().ps;
@@ -592,13 +616,14 @@ __global__ void __launch_bounds__(kBlock) k_sky_pixels(DeviceScene sc, PathState
 }
 
 // The end of a path whose last vertex had a light sample (resolve_shadow): its stream's next sample, regenerated in place, if there is one.
-PT_DEV bool next_sample(const DeviceScene &sc, const FrameParams &fp, uint32_t slot, PathRegs &r, uint32_t &depth)
+template <bool LENS = false>
+PT_DEV bool next_sample(const DeviceScene &sc, const FrameParams &fp, uint32_t slot, PathRegs &r, uint32_t &depth, const LensArgs *lens = nullptr)
 {
     uint32_t x = 0, y = 0;
     r.sample += fp.streams;
     if (!(r.sample < fp.spp)) return false;
     slot_pixel(slot, fp, x, y);
-    camera_sample(sc, fp, x, y, r, depth);
+    camera_sample<true, LENS>(sc, fp, x, y, r, depth, lens);
     return true;
 }
 
@@ -619,7 +644,8 @@ PT_DEV bool roulette_ends(const FrameParams &fp, uint32_t key, uint32_t depth, u
 // pass at the end (see there). The all-kinds SHADE_INLINE kernels keep one branch per kind: with the shared end they spill registers
 // that the two-branch form leaves them (k_extend<.., SHADE_INLINE> 1 to 5 VGPRs more, k_extend_packed<.., SHADE_INLINE> 4).
 // ENV (k_extend<.., ENV> only, docs/SPEC.md §11): a miss looks the map up, and a NEE frame's light sample goes to the map or to a triangle.
-template <int MODE, bool NEE = false, bool ENV = false>
+// LENS (k_extend<.., FUSE_LENS, ..> only, docs/SPEC.md §3.1; SHADE_INLINE, so never the shared end): a regenerated sample's ray goes through the lens.
+template <int MODE, bool NEE = false, bool ENV = false, bool LENS = false>
 PT_DEV bool shade_one(const DeviceScene &sc, const PathState &ps, const FrameParams &fp, uint32_t slot, PathRegs &r, float t, uint32_t ref,
                       uint32_t b, uint32_t &defer, NeeRegs *nr = nullptr)
 {
@@ -632,6 +658,7 @@ PT_DEV bool shade_one(const DeviceScene &sc, const PathState &ps, const FramePar
     float4 A = at(ps.acc, slot);
     bool touched = false, term = false, alive = false;
     constexpr bool SHARED = !NEE && MODE != SHADE_INLINE;
+    static_assert(!LENS || !SHARED, "the shared end makes pinhole rays only");
     bool lambert = false, regen = false; // which lanes take a new direction at the shared end: a Lambert vertex that goes on, a new sample
     auto add = [&](V3 L) {
         touched = true;
@@ -790,6 +817,8 @@ PT_DEV bool shade_one(const DeviceScene &sc, const PathState &ps, const FramePar
         sample += fp.streams;
         if (sample < fp.spp) {
             slot_pixel(slot, fp, x, y);
+            if constexpr (LENS) camera_sample<true, true>(sc, fp, x, y, r, depth, &lens_args<NEE, ENV>());
+            else
             camera_sample<!SHARED>(sc, fp, x, y, r, depth); // SHARED: the direction comes from the shared end
             regen = SHARED; alive = true;
         }
@@ -817,15 +846,16 @@ PT_DEV bool shade_one(const DeviceScene &sc, const PathState &ps, const FramePar
 
 // NEE: the pass after a light sample. A shadow ray that found nothing with t <= tmax adds its radiance (§7); then the path either
 // ends (NEE_END: the vertex's Russian roulette or max_depth ended it) or continues with the extension ray that waited in NeeArgs::ext.
+template <bool LENS = false>
 PT_DEV bool resolve_shadow(const DeviceScene &sc, const PathState &ps, const FrameParams &fp, const NeeArgs &na, uint32_t slot, PathRegs &r,
-                           NeeRegs &nr, bool visible)
+                           NeeRegs &nr, bool visible, const LensArgs *lens = nullptr)
 {
     const bool end = (nr.flags & NEE_END) != 0u;
     bool alive = true;
     if (visible || end) {
         float4 A = at(ps.acc, slot);
         if (visible) { const float4 L = at(na.rad, slot); A.x = A.x + L.x; A.y = A.y + L.y; A.z = A.z + L.z; }
-        if (end) { A.w += 1.0f; alive = next_sample(sc, fp, slot, r, r.depth); nr.aux = 0.0f; }
+        if (end) { A.w += 1.0f; alive = next_sample<LENS>(sc, fp, slot, r, r.depth, lens); nr.aux = 0.0f; }
         at(ps.acc, slot) = A;
     }
     if (!end) { const float4 e = at(na.ext, slot); r.d = xyz(e); nr.aux = e.w; }
@@ -914,6 +944,14 @@ PT_DEV void queue_next(const PathState &ps, uint32_t shard, uint32_t cnext, uint
 #define PT_EXT_WAVES_ENV(L, NEE) ((NEE) ? 5 : (L) == PT_BVH_WIDTH_8O ? 6 : 7)
 #endif
 #define PT_EXT_WAVES_FOR(L, FUSE, NEE, ENV) ((ENV) ? PT_EXT_WAVES_ENV(L, NEE) : PT_EXT_WAVES_OF(L, FUSE, NEE))
+// The lens instantiations (docs/SPEC.md §3.1; all-kinds shading only) add the lens ray to the regeneration code. They keep the budget of
+// the instantiation they are the lens form of, except the 8-wide layouts without NEE: at 7 waves BVH8Q spills 1 VGPR (plain and with the
+// environment) and BVH8O 7 (plain; its pinhole form spills 1), so those three take 80 VGPRs = 6 waves, where nothing spills (DESIGN.md
+// has the table).
+#ifndef PT_EXT_WAVES_LENS
+#define PT_EXT_WAVES_LENS(L, NEE, ENV) (!(NEE) && ((L) == PT_BVH_WIDTH_8Q || (L) == PT_BVH_WIDTH_8O) ? 6 : PT_EXT_WAVES_FOR(L, SHADE_INLINE, NEE, ENV))
+#endif
+#define PT_EXT_WAVES_K(L, FUSE, NEE, ENV) ((FUSE) == 3 /* FUSE_LENS */ ? PT_EXT_WAVES_LENS(L, NEE, ENV) : PT_EXT_WAVES_FOR(L, FUSE, NEE, ENV))
 // A lane's traversal stack: kStackLds entries in its LDS column ([level][lane]: conflict-free), the rest in a global
 // overflow column sized by the builder's exact worst case (pt_bvh_info.stack_need).
 struct StackCtx { int32_t *lds; uint32_t stride, tid, col; }; // col: the lane's column of the overflow area, unique per thread of a launch
@@ -1186,13 +1224,22 @@ PT_DEV Hit trace_ray(const HotScene &g, const StackCtx &stk, V3 o, V3 d, Hit h, 
 // NEE (PT_FLAG_NEXT_EVENT; fused, not counting): one ray per lane per pass, a shadow ray or an extension ray (see NeeRegs); `bounces`
 // then counts passes.
 // ENV (a scene with an environment map, docs/SPEC.md §11; all-kinds shading, not counting): shade_one's environment paths.
-template <int L, bool COUNT, int FUSE, bool NEE = false, bool ENV = false>
-__global__ void __launch_bounds__(kExtBlock) __attribute__((amdgpu_waves_per_eu(PT_EXT_WAVES_FOR(L, FUSE, NEE, ENV), PT_EXT_WAVES_FOR(L, FUSE, NEE, ENV))))
-k_extend(ExtArgsT<NEE, ENV> args)
+// LENS (a frame through a thin lens, docs/SPEC.md §3.1; all-kinds shading, not counting): the camera rays — the first launch's and every
+// regenerated sample's — are lens_ray's. These instantiations are k_extend<L, false, FUSE_LENS, NEE, ENV>: the fuse argument FUSE_LENS
+// stands for "SHADE_INLINE through a lens". A sixth template argument would have renamed every existing instantiation in the profiles and
+// in tools/isa_diff.py, which compare kernels by name, and a body shared by two entry points does not compile to the code the kernel
+// has today (50 of the existing instantiations then differ).
+constexpr int FUSE_LENS = 3;
+template <int L, bool COUNT, int FUSE_, bool NEE = false, bool ENV = false>
+__global__ void __launch_bounds__(kExtBlock) __attribute__((amdgpu_waves_per_eu(PT_EXT_WAVES_K(L, FUSE_, NEE, ENV), PT_EXT_WAVES_K(L, FUSE_, NEE, ENV))))
+k_extend(std::conditional_t<FUSE_ == FUSE_LENS, ExtLensArgsT<NEE, ENV>, ExtArgsT<NEE, ENV>> args)
 {
+    constexpr bool LENS = FUSE_ == FUSE_LENS;
+    constexpr int FUSE = LENS ? (int)SHADE_INLINE : FUSE_;
+    const ExtArgs &a = ext_of(args);
     static_assert(!NEE || (FUSE != SHADE_NONE && !COUNT), "NEE: fused shading, no visit counters");
     static_assert(!ENV || (FUSE == SHADE_INLINE && !COUNT), "ENV: all-kinds fused shading, no visit counters");
-    const ExtArgs &a = args.x;
+    static_assert(!LENS || (FUSE == SHADE_INLINE && !COUNT), "LENS: all-kinds fused shading, no visit counters");
     const HotScene g = hot_scene(a.sc);
     const uint32_t it = a.it;
     __shared__ int32_t s_stack[kStackLds * kExtBlock];
@@ -1228,6 +1275,7 @@ k_extend(ExtArgsT<NEE, ENV> args)
     NeeRegs nr{ 0.0f, 0u };
     if (active) {
         if (FUSE == SHADE_NONE) { const PathState &ps = cold().ps; r.o = xyz(at(ps.ray_o, slot)); r.d = xyz(at(ps.ray_d, slot)); }
+        else if constexpr (LENS) path_begin<NEE, true>(it, slot, r, &nr, &lens_args<NEE, ENV>());
         else path_begin<NEE>(it, slot, r, &nr);
     }
     bool alive = active;
@@ -1253,9 +1301,11 @@ k_extend(ExtArgsT<NEE, ENV> args)
                 const ExtArgs &c = cold();
                 if constexpr (NEE) {
                     nr.aux = __uint_as_float(s_stash[5 * kExtBlock + tid]); nr.flags = s_stash[6 * kExtBlock + tid];
-                    if (nr.flags & NEE_PENDING) alive = resolve_shadow(c.sc, c.ps, c.fp, kernargs<true, ENV>().nee, slot, r, nr, h.ref == PT_MISS);
-                    else alive = shade_one<FUSE, true, ENV>(c.sc, c.ps, c.fp, slot, r, h.t, h.ref, B_LAMBERT, defer, &nr);
-                } else alive = shade_one<FUSE, false, ENV>(c.sc, c.ps, c.fp, slot, r, h.t, h.ref, B_LAMBERT, defer);
+                    if (nr.flags & NEE_PENDING) {
+                        if constexpr (LENS) alive = resolve_shadow<true>(c.sc, c.ps, c.fp, kernargs<true, ENV>().nee, slot, r, nr, h.ref == PT_MISS, &lens_args<true, ENV>());
+                        else alive = resolve_shadow(c.sc, c.ps, c.fp, kernargs<true, ENV>().nee, slot, r, nr, h.ref == PT_MISS);
+                    } else alive = shade_one<FUSE, true, ENV, LENS>(c.sc, c.ps, c.fp, slot, r, h.t, h.ref, B_LAMBERT, defer, &nr);
+                } else alive = shade_one<FUSE, false, ENV, LENS>(c.sc, c.ps, c.fp, slot, r, h.t, h.ref, B_LAMBERT, defer);
             }
         }
     }
@@ -1872,33 +1922,34 @@ static bool with_layout(uint32_t width, F &&f)
 template <int... V, typename F>
 static void with_value(int v, F &&f) { (void)((v == V && (f(std::integral_constant<int, V>{}), true)) || ...); }
 
-template <int L, bool COUNT, int FUSE, bool NEE, bool ENV>
-static void launch_k_extend(hipStream_t s, dim3 grid, const ExtArgs &a, const NeeArgs *nee, const EnvArgs *env) // builds only its case's block
+template <int L, bool COUNT, int FUSE, bool NEE, bool ENV, bool LENS>
+static void launch_k_extend(hipStream_t s, dim3 grid, const ExtArgs &a, const NeeArgs *nee, const EnvArgs *env, const LensArgs *lens) // builds only its case's block
 {
     ExtArgsT<NEE, ENV> t; t.x = a; if constexpr (NEE) t.nee = *nee; if constexpr (ENV) t.env = *env;
-    hipLaunchKernelGGL((k_extend<L, COUNT, FUSE, NEE, ENV>), grid, dim3(kExtBlock), 0, s, t);
+    if constexpr (LENS) hipLaunchKernelGGL((k_extend<L, COUNT, FUSE_LENS, NEE, ENV>), grid, dim3(kExtBlock), 0, s, ExtLensArgsT<NEE, ENV>{ t, *lens });
+    else hipLaunchKernelGGL((k_extend<L, COUNT, FUSE, NEE, ENV>), grid, dim3(kExtBlock), 0, s, t);
 }
 
 hipError_t launch_extend(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp, const ExtendLaunch &x)
 {
-    const bool has_nee = x.nee != nullptr, has_env = x.env != nullptr;
-    if (!extend_instantiated(x.kernel, x.fuse, x.count, has_nee, has_env)) return hipErrorInvalidValue;
+    const bool has_nee = x.nee != nullptr, has_env = x.env != nullptr, has_lens = x.lens != nullptr;
+    if (!extend_instantiated(x.kernel, x.fuse, x.count, has_nee, has_env, has_lens)) return hipErrorInvalidValue;
     const uint32_t chunk = x.kernel == EXT_PACKED ? (x.packed_chunk >= 64u ? x.packed_chunk : 128u) : 0u;
     const uint32_t per_block = x.kernel == EXT_PACKED ? chunk : x.kernel == EXT_POOL ? kPool : kExtBlock;
     const dim3 grid = shard_grid(x.shard_bound ? (x.shard_bound + per_block - 1) / per_block : 1u, ps.shard_count);
     ExtArgs a;
     a.sc = sc; a.ps = ps; a.fp = fp; a.it = x.it; a.compact = x.compact ? 1u : 0u; a.bounces = x.bounces ? x.bounces : 1u; a.chunk = chunk;
-    // layout x kernel x fuse x count x NEE x ENV, of which extend_instantiated names the ones that exist
+    // layout x kernel x fuse x count x NEE x ENV x LENS, of which extend_instantiated names the ones that exist
     const bool known = with_layout(sc.bvh_width, [&](auto lc) { with_value<EXT_SIMPLE, EXT_PACKED, EXT_POOL>(x.kernel, [&](auto kc) {
         with_value<SHADE_NONE, SHADE_QUEUE, SHADE_INLINE>(x.fuse, [&](auto fc) { with_value<0, 1>(x.count, [&](auto cc) {
-            with_value<0, 1>(has_nee, [&](auto nc) { with_value<0, 1>(has_env, [&](auto ec) {
+            with_value<0, 1>(has_nee, [&](auto nc) { with_value<0, 1>(has_env, [&](auto ec) { with_value<0, 1>(has_lens, [&](auto zc) {
                 constexpr int L = decltype(lc)::value, K = decltype(kc)::value, F = decltype(fc)::value;
-                constexpr bool C = decltype(cc)::value != 0, N = decltype(nc)::value != 0, E = decltype(ec)::value != 0;
-                if constexpr (!extend_instantiated(K, F, C, N, E)) return;
+                constexpr bool C = decltype(cc)::value != 0, N = decltype(nc)::value != 0, E = decltype(ec)::value != 0, Z = decltype(zc)::value != 0;
+                if constexpr (!extend_instantiated(K, F, C, N, E, Z)) return;
                 else if constexpr (K == EXT_POOL) hipLaunchKernelGGL((k_extend_pool<L, C, F>), grid, dim3(64), 0, s, a);
                 else if constexpr (K == EXT_PACKED) hipLaunchKernelGGL((k_extend_packed<L, C, F>), grid, dim3(64), 0, s, a);
-                else launch_k_extend<L, C, F, N, E>(s, grid, a, x.nee, x.env);
-            }); });
+                else launch_k_extend<L, C, F, N, E, Z>(s, grid, a, x.nee, x.env, x.lens);
+            }); }); });
         }); });
     }); });
     return known ? hipGetLastError() : hipErrorInvalidValue;

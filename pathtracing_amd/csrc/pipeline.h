@@ -1,5 +1,5 @@
 // pipeline.h — the one statement of which pipeline a path-traced frame runs (DESIGN.md "Pipelines"): what the frame's PT_FLAG_*,
-// pt_tuning.extend_kernel and the scene's environment map and materials decode to, which combinations are refused, and everything the
+// pt_tuning.extend_kernel and the scene's environment map, lens and materials decode to, which combinations are refused, and everything the
 // frame loop (frame.cpp) and the launchers (kernels.hip) derive from that. Host-only and free of HIP: tests/pipeline_ref builds it with a
 // plain C++ compiler and walks every input.
 #pragma once
@@ -26,21 +26,24 @@ enum GenerateMode : uint32_t { GEN_QUEUE = 0, GEN_STATE = 1, GEN_DENSE = 2 };
 // Which k_extend / k_extend_packed / k_extend_pool instantiations exist (each for every node layout). Next-event estimation and the
 // environment map live in the one-ray-per-lane kernel only, fused and without visit counters — a shadow ray's traversal stops at its tmax,
 // which the counters do not describe —, the environment with all-kinds shading whatever the materials; the pooled kernel always shades.
-constexpr bool extend_instantiated(int kernel, int fuse, bool count, bool nee, bool env)
+// The thin lens (docs/SPEC.md §3.1) lives there too, with all-kinds shading, with and without NEE and the environment: 4 instantiations.
+constexpr bool extend_instantiated(int kernel, int fuse, bool count, bool nee, bool env, bool lens = false)
 {
     if (kernel < EXT_SIMPLE || kernel > EXT_POOL || fuse == SHADE_BUCKETS || fuse < SHADE_NONE || fuse > SHADE_INLINE) return false;
+    if (lens) return kernel == EXT_SIMPLE && !count && fuse == SHADE_INLINE;
     if (env) return kernel == EXT_SIMPLE && !count && fuse == SHADE_INLINE;
     if (nee) return kernel == EXT_SIMPLE && !count && fuse != SHADE_NONE;
     return kernel != EXT_POOL || fuse != SHADE_NONE;
 }
 
 struct Pipeline {
-    uint32_t forced;        // ExtendKernel a frame flag, pt_tuning.extend_kernel, NEE or the environment forces (0 = none: the scene's probed choice)
+    uint32_t forced;        // ExtendKernel a frame flag, pt_tuning.extend_kernel, NEE, the environment or the lens forces (0 = none: the scene's probed choice)
     bool profile, count;    // PT_FLAG_PROFILE_KERNELS, PT_FLAG_COUNT_VISITS
     bool split, bucket;     // k_shade as a second kernel (PT_FLAG_SPLIT_KERNELS); with the specular kinds shaded from buckets (_BUCKET_SPECULAR)
     bool nee;               // PT_FLAG_NEXT_EVENT (docs/SPEC.md §7)
     bool env;               // the scene has an environment map (docs/SPEC.md §11)
-    ShadeMode shade;        // Lambert-only scene: lean code; all kinds with specular materials, and with an environment (its instantiations shade every kind)
+    ShadeMode shade;        // Lambert-only scene: lean code; all kinds with specular materials, and with an environment or a lens (their instantiations shade every kind)
+    bool lens;              // the scene's lens has a radius > 0 (docs/SPEC.md §3.1)
 
     // One kernel per iteration by default: every extend kernel shades its own hits. The split pipelines run k_shade behind it.
     constexpr ShadeMode fuse() const { return split ? SHADE_NONE : shade; }
@@ -53,8 +56,8 @@ struct Pipeline {
     constexpr bool forces_compact(bool repack_sticky, uint32_t samples_per_stream) const { return bucket || (repack_sticky && samples_per_stream <= 2u); }
     // Sky pixels are resolved by the frames whose first launch builds the slots' state in registers (next-event estimation included: a
     // camera ray's miss adds the sky with weight 1 there too). Not by counting frames, whose visit counters are the spec's, nor with an
-    // environment map, where a miss depends on the ray's direction.
-    constexpr bool resolves_sky() const { return !full_state() && !count && !env; }
+    // environment map, where a miss depends on the ray's direction, nor through a lens, whose rays leave the frustum the bound is made for.
+    constexpr bool resolves_sky() const { return !full_state() && !count && !env && !lens; }
     // Counting / profiling frames neither probe the extend kernel nor feed the scene's choice: their kernels are instrumented builds.
     constexpr bool instrumented() const { return count || profile; }
     // Timed kernels run alone: instrumented frames, and a frame that probes (so that its timed iterations compare), run one wavefront loop.
@@ -72,25 +75,28 @@ struct PipelineDecode { pt_status status; const char *message; Pipeline pipeline
 
 // A frame's PT_FLAG_EXTEND_* beats pt_tuning.extend_kernel (tuned_kernel), which beats the scene's own choice. An environment map and
 // next-event estimation force the one-ray-per-lane kernel, the only one with their instantiations (extend_instantiated), and refuse what
-// asks for another: the environment first, then NEE with another kernel, then NEE with counting.
-constexpr PipelineDecode decode_pipeline(uint32_t flags, uint32_t tuned_kernel, bool has_env, bool has_specular)
+// asks for another, and so does a lens: the environment first, then the lens, then NEE with another kernel, then NEE with counting.
+constexpr PipelineDecode decode_pipeline(uint32_t flags, uint32_t tuned_kernel, bool has_env, bool has_specular, bool has_lens = false)
 {
     Pipeline p{};
     p.profile = (flags & PT_FLAG_PROFILE_KERNELS) != 0; p.count = (flags & PT_FLAG_COUNT_VISITS) != 0;
     p.bucket = (flags & PT_FLAG_BUCKET_SPECULAR) != 0; p.split = p.bucket || (flags & PT_FLAG_SPLIT_KERNELS) != 0;
-    p.nee = (flags & PT_FLAG_NEXT_EVENT) != 0; p.env = has_env;
-    p.shade = (has_specular || has_env) ? SHADE_INLINE : SHADE_QUEUE;
+    p.nee = (flags & PT_FLAG_NEXT_EVENT) != 0; p.env = has_env; p.lens = has_lens;
+    p.shade = (has_specular || has_env || has_lens) ? SHADE_INLINE : SHADE_QUEUE;
     p.forced = (flags & PT_FLAG_EXTEND_POOL) ? (uint32_t)EXT_POOL : (flags & PT_FLAG_EXTEND_PACKED) ? (uint32_t)EXT_PACKED
                : (flags & PT_FLAG_EXTEND_SIMPLE) ? (uint32_t)EXT_SIMPLE : tuned_kernel;
     const bool other_kernel = p.split || p.forced == (uint32_t)EXT_PACKED || p.forced == (uint32_t)EXT_POOL;
     if (p.env && (other_kernel || p.count))
         return { PT_ERR_UNSUPPORTED, "a scene with an environment map renders on the one-ray-per-lane kernel only: not with PT_FLAG_EXTEND_PACKED, "
                                      "PT_FLAG_EXTEND_POOL, PT_FLAG_SPLIT_KERNELS, PT_FLAG_BUCKET_SPECULAR, PT_FLAG_COUNT_VISITS or pt_tuning.extend_kernel 2 / 3", p };
+    if (p.lens && (other_kernel || p.count))
+        return { PT_ERR_UNSUPPORTED, "a frame through a lens (pt_scene_set_lens, radius > 0) renders on the one-ray-per-lane kernel only: not with PT_FLAG_EXTEND_PACKED, "
+                                     "PT_FLAG_EXTEND_POOL, PT_FLAG_SPLIT_KERNELS, PT_FLAG_BUCKET_SPECULAR, PT_FLAG_COUNT_VISITS or pt_tuning.extend_kernel 2 / 3", p };
     if (p.nee && other_kernel)
         return { PT_ERR_UNSUPPORTED, "PT_FLAG_NEXT_EVENT runs on the one-ray-per-lane kernel only: not with PT_FLAG_EXTEND_PACKED, "
                                      "PT_FLAG_EXTEND_POOL, PT_FLAG_SPLIT_KERNELS, PT_FLAG_BUCKET_SPECULAR or pt_tuning.extend_kernel 2 / 3", p };
     if (p.nee && p.count) return { PT_ERR_UNSUPPORTED, "PT_FLAG_NEXT_EVENT does not count visits (PT_FLAG_COUNT_VISITS)", p };
-    if (p.env || p.nee) p.forced = EXT_SIMPLE;
+    if (p.env || p.nee || p.lens) p.forced = EXT_SIMPLE;
     return { PT_OK, nullptr, p };
 }
 

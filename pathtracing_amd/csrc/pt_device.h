@@ -80,6 +80,20 @@ PT_DEV void camera_ray(const Camera &c, uint32_t x, uint32_t y, uint32_t key, V3
     d = normalize(camera_vec(c, x, y, jx, jy));
     o = V3{ c.origin[0], c.origin[1], c.origin[2] };
 }
+// SPEC §3.1: the camera ray through a thin lens. lu, lv: the aperture's axes (radius * the unit right / up), F: the focus distance. The
+// point on the unit disc takes dimensions 2 and 3 of the key, which nothing else draws; the ray leaves origin + a towards origin + F v.
+PT_DEV void lens_ray(const Camera &c, V3 lu, V3 lv, float F, uint32_t x, uint32_t y, uint32_t key, V3 &o, V3 &d)
+{
+    float jx = 0.5f, jy = 0.5f;
+    if (c.jitter) { jx = u01(key, 0); jy = u01(key, 1); }
+    const V3 v = camera_vec(c, x, y, jx, jy);
+    float r = __builtin_sqrtf(u01(key, 2)), sn, cs;
+    sincos2pi(u01(key, 3), sn, cs);
+    const float lx = r * cs, ly = r * sn;
+    const V3 a = V3{ fma_(ly, lv.x, lx * lu.x), fma_(ly, lv.y, lx * lu.y), fma_(ly, lv.z, lx * lu.z) };
+    o = V3{ c.origin[0] + a.x, c.origin[1] + a.y, c.origin[2] + a.z };
+    d = normalize(V3{ fma_(F, v.x, -a.x), fma_(F, v.y, -a.y), fma_(F, v.z, -a.z) });
+}
 
 // ---------------------------------------------------------------- SPEC §4 intersection
 struct Hit { float t; uint32_t id; uint32_t ref; }; // id = original primitive id (tie-break); ref = blob tri index or n_tris + sphere index

@@ -145,6 +145,16 @@ struct EnvArgs {
     float psel;            // this frame's probability of the strategy a light sample takes: 0.5f with both kinds of light, else 1.0f
 };
 
+// The thin lens of a scene (pt_scene_set_lens, docs/SPEC.md §3.1) as a frame's camera rays use it: the aperture's two axes, made by
+// frame.cpp from the frame's camera (lens_basis), and the focus distance. A block of its own at the end of the lens instantiations'
+// arguments (kernels.hip ExtLensArgsT), for the reason NeeArgs gives; only those instantiations have it.
+struct LensArgs {
+    float u[3], v[3];      // lens_u = radius * right / |right|, lens_v = radius * up / |up|
+    float focus;           // F: every lens ray of a sample passes through origin + F * v (v: §3's vector before it is normalised)
+    uint32_t pad;
+};
+static_assert(sizeof(LensArgs) == 32, "LensArgs is 32 bytes");
+
 struct FrameParams {
     uint32_t width, height, spp, max_depth, rr_start, seed_hashed, sample_offset;
     float ray_eps;
@@ -186,7 +196,7 @@ hipError_t launch_generate(hipStream_t s, const DeviceScene &sc, const PathState
 // to the slot's sum as the traced frame would have. Their rays, one per sample, are the host's to count (frame.cpp finish_frame).
 hipError_t launch_sky_pixels(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp);
 // One launch of an extend kernel. `it` = iteration index of the wavefront loop: queues alternate by it & 1, queue counters rotate by it % 3.
-// (kernel, fuse, count, nee, env) must name an instantiation that exists (pipeline.h extend_instantiated), else hipErrorInvalidValue.
+// (kernel, fuse, count, nee, env, lens) must name an instantiation that exists (pipeline.h extend_instantiated), else hipErrorInvalidValue.
 struct ExtendLaunch {
     uint32_t it, shard_bound;   // shard_bound: upper bound of any shard's queue length for this launch
     ExtendKernel kernel; ShadeMode fuse; bool count, compact; // compact (fused kernels): as for launch_shade
@@ -194,6 +204,7 @@ struct ExtendLaunch {
     uint32_t bounces;           // fused only: path vertices a lane advances per launch
     const NeeArgs *nee;         // a PT_FLAG_NEXT_EVENT frame's block, else NULL
     const EnvArgs *env;         // the block of a scene with an environment map, else NULL
+    const LensArgs *lens;       // the block of a frame through a thin lens (radius > 0), else NULL
 };
 hipError_t launch_extend(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp, const ExtendLaunch &x);
 // mode: SHADE_QUEUE, SHADE_BUCKETS or SHADE_INLINE (pipeline.h)

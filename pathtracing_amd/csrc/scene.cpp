@@ -337,6 +337,24 @@ pt_status pt_scene_set_sky(pt_scene *s, const float rgb[3])
     return PT_OK;
 }
 
+pt_status pt_scene_set_lens(pt_scene *s, const pt_lens *lens)
+{
+    if (!s) return fail(nullptr, PT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!lens) { s->lens = pt_lens{}; return PT_OK; }
+    if (!(std::isfinite(lens->radius) && lens->radius >= 0.f)) return fail(s->ctx, PT_ERR_INVALID_ARGUMENT, "pt_scene_set_lens: radius must be finite and >= 0");
+    if (!(std::isfinite(lens->focus_distance) && lens->focus_distance > 0.f)) return fail(s->ctx, PT_ERR_INVALID_ARGUMENT, "pt_scene_set_lens: focus_distance must be finite and > 0");
+    if (lens->flags) return fail(s->ctx, PT_ERR_INVALID_ARGUMENT, "pt_scene_set_lens: unknown flag bits 0x%x", lens->flags);
+    s->lens = pt_lens{}; s->lens.radius = lens->radius; s->lens.focus_distance = lens->focus_distance;
+    return PT_OK;
+}
+
+pt_status pt_scene_get_lens(const pt_scene *s, pt_lens *out)
+{
+    if (!s || !out) return fail(s ? s->ctx : nullptr, PT_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out = s->lens;
+    return PT_OK;
+}
+
 // ---- pt_scene_commit's phases, in the order they run. Each ends with a lap of the commit's clock.
 
 // Check: the builder flag, the layout (bvh_width leaves as one of PT_BVH_WIDTH_2 .. _8O), the camera and every material id

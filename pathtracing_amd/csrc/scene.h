@@ -128,6 +128,8 @@ struct pt_scene {
     float sky[3] = { 0.f, 0.f, 0.f };
     ptrt::Environment env;               // while present it replaces `sky` on the misses of a path-traced frame (docs/SPEC.md §11); not
                                          // scene content in the commit's sense: set, replaced and removed at any time, kept by commits and updates
+    pt_lens lens{};                      // pt_scene_set_lens (docs/SPEC.md §3.1); radius 0 = none. Like `sky` host values only, read by every pt_render:
+                                         // set and removed at any time, kept by commits, updates and pt_scene_set_camera
     bool have_cam = false, committed = false;
     ptrt::CommittedTree tree;
     mutable ptrt::CommitCaches cache;    // (mutable: pt_render and pt_denoise fill it through the const scene they receive)

@@ -235,6 +235,21 @@ class Renderer:
         _check(N.lib.pt_scene_environment_info(self._scene, C.byref(info)), self._ctx)
         return info
 
+    def SetLens(self, radius, focus_distance):
+        """Give the current scene a thin lens (include/ptrt.h pt_scene_set_lens, docs/SPEC.md §3.1: depth of field; no new commit
+        needed). radius 0 is the pinhole. A caller that changes the lens restarts accumulation."""
+        lens = N.pt_lens(radius=radius, focus_distance=focus_distance)
+        _check(N.lib.pt_scene_set_lens(self._scene, C.byref(lens)), self._ctx)
+
+    def ClearLens(self):
+        _check(N.lib.pt_scene_set_lens(self._scene, None), self._ctx)
+
+    def Lens(self):
+        """(radius, focus_distance) of the current scene's lens; (0.0, 0.0) when none is set."""
+        lens = N.pt_lens()
+        _check(N.lib.pt_scene_get_lens(self._scene, C.byref(lens)), self._ctx)
+        return lens.radius, lens.focus_distance
+
     def SetCamera(self, cam):
         """Move the current scene's camera (include/ptrt.h pt_scene_set_camera: no new commit needed)."""
         _check(N.lib.pt_scene_set_camera(self._scene, C.byref(cam)), self._ctx)

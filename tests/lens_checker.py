@@ -1,0 +1,118 @@
+"""ctypes bindings of tests/lens_ref/liblens_ref.so — the scalar restatement of docs/SPEC.md §3.1 (the thin-lens camera, with §5's loop
+and §7's light sample around it) that the lens tests check the product against — and of tests/lens_pipeline_ref/ (the lens parameters of
+pathtracing_amd/csrc/pipeline.h behind plain C). Test infrastructure only, like oracle/pto.py."""
+import ctypes as C
+
+import numpy as np
+
+import ref_lib
+
+NEE, FOCUS_IGNORED, LINEAR_RADIUS, FIXED_ORIGIN = 1, 2, 4, 8
+
+
+class lr_lens(C.Structure):
+    _fields_ = [("radius", C.c_float), ("focus_distance", C.c_float)]
+
+
+class lr_stats(C.Structure):
+    _fields_ = [("ext_rays", C.c_uint64), ("shadow_rays", C.c_uint64), ("paths", C.c_uint64), ("n_lights", C.c_uint64)]
+
+
+_f3 = C.c_float * 3
+SYMBOLS = {
+    "lr_lens_basis": (C.c_int, [C.c_void_p, C.c_float, _f3, _f3]),
+    "lr_camera_ray": (C.c_int, [C.c_void_p, C.POINTER(lr_lens), C.c_uint32, C.c_uint32, C.c_uint32, _f3, _f3]),
+    "lr_render": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(lr_lens), C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(lr_stats)]),
+}
+
+
+def build():
+    return ref_lib.load("lens_ref", "liblens_ref.so", SYMBOLS)
+
+
+def _cam(pto, cam):
+    c = pto.pto_camera()
+    C.memmove(C.byref(c), C.byref(cam), C.sizeof(pto.pto_camera))
+    return c
+
+
+def lens_basis(pto, cam, radius):
+    """(lens_u, lens_v) float32, or None for a degenerate basis. `cam`: any ctypes struct with the pt_camera layout."""
+    c, u, v = _cam(pto, cam), _f3(), _f3()
+    if build().lr_lens_basis(C.addressof(c), radius, u, v) != 0:
+        return None
+    return np.array(u[:], np.float32), np.array(v[:], np.float32)
+
+
+def camera_ray(pto, cam, lens, x, y, key):
+    """(origin, direction) float32 of the lens ray of pixel (x, y) with `key`; lens = (radius, focus_distance)."""
+    c, o, d = _cam(pto, cam), _f3(), _f3()
+    rc = build().lr_camera_ray(C.addressof(c), C.byref(lr_lens(*lens)), x, y, key, o, d)
+    assert rc == 0, rc
+    return np.array(o[:], np.float32), np.array(d[:], np.float32)
+
+
+def render(pto, scene, params, lens=None, flags=0, with_sq=False, threads=0):
+    """(rgba float32 HxWx4, lr_stats, per-pixel sums of squared sample radiance HxWx3 float64 or None). `scene`: a pto.Scene; `params`:
+    any ctypes struct with the pt_render_params layout; lens: (radius, focus_distance) or None."""
+    lib = build()
+    p = pto.pto_params()
+    C.memmove(C.byref(p), C.byref(params), C.sizeof(pto.pto_params))
+    out = np.zeros((p.height, p.width, 4), np.float32)
+    sq = np.zeros((p.height, p.width, 3), np.float64) if with_sq else None
+    st = lr_stats()
+    rc = lib.lr_render(C.addressof(scene.c), C.addressof(p), None if lens is None else C.byref(lr_lens(*lens)), flags, threads,
+                       out.ctypes.data, None if sq is None else sq.ctypes.data, C.byref(st))
+    if rc != 0:
+        raise RuntimeError(f"lr_render failed: {rc}")
+    return out, st, sq
+
+
+# ------------------------------------------------------------------------------------------------- pipeline.h with its lens parameters
+class Decoded(C.Structure):
+    _fields_ = [("status", C.c_int32), ("message", C.c_char_p), ("forced", C.c_uint32),
+                ("profile", C.c_uint32), ("count", C.c_uint32), ("split", C.c_uint32), ("bucket", C.c_uint32), ("nee", C.c_uint32),
+                ("env", C.c_uint32), ("lens", C.c_uint32), ("shade", C.c_int32), ("fuse", C.c_int32),
+                ("full_state", C.c_uint32), ("resolves_sky", C.c_uint32), ("instrumented", C.c_uint32),
+                ("single_loop", C.c_uint32 * 2), ("generate_mode", C.c_uint32 * 2), ("kernel_for", (C.c_int32 * 3) * 4)]
+
+
+def build_pipeline():
+    return ref_lib.load("lens_pipeline_ref", "liblens_pipeline_ref.so", {
+        "lp_decode": (None, [C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.POINTER(Decoded)]),
+        "lp_extend_instantiated": (C.c_int, [C.c_int] * 6),
+    })
+
+
+def decode(flags, tuned_kernel=0, env=False, specular=False, lens=False):
+    d = Decoded()
+    build_pipeline().lp_decode(flags, tuned_kernel, int(env), int(specular), int(lens), C.byref(d))
+    return d
+
+
+# ----------------------------------------------------------------------------------------------------------------------------- scenes
+def camera(P, w, h, origin=(0.0, 0.0, 0.0), scale=0.03125, jitter=0):
+    """A camera at `origin` looking down -z, right = +x, up = +y, the principal point in the image's centre."""
+    cam = P.native.pt_camera()
+    cam.origin[:] = origin
+    cam.forward[:] = (0.0, 0.0, -1.0)
+    cam.right[:] = (1.0, 0.0, 0.0)
+    cam.up[:] = (0.0, 1.0, 0.0)
+    cam.scale, cam.cx, cam.cy, cam.jitter = scale, 0.5 * w * scale, 0.5 * h * scale, jitter
+    return cam
+
+
+def triangle_scene(P, w, h, tri, cam, emission=(1.0, 0.5, 0.25)):
+    """One emissive black triangle (9 floats) under a black sky, seen by `cam`."""
+    import dataclasses
+    sd = P.make_scene(P.native.PT_SCENE_CORNELL, 0, 3, w, h)
+    mats = np.zeros(1, sd.mats.dtype)
+    mats[0]["kind"], mats[0]["albedo"], mats[0]["emission"], mats[0]["ior"] = 0, (0.0, 0.0, 0.0), emission, 1.0
+    return dataclasses.replace(sd, verts=np.asarray(tri, np.float32).reshape(1, 9), tri_mat=np.zeros(1, np.uint32),
+                               spheres=np.zeros((0, 4), np.float32), sph_mat=np.zeros(0, np.uint32), mats=mats, cam=cam,
+                               sky=np.zeros(3, np.float32))
+
+
+def all_miss_scene(P, w, h, jitter):
+    """A tiny triangle behind the camera: every camera ray, through whatever lens, misses."""
+    return triangle_scene(P, w, h, [0.0, 0.0, 50.0, 0.01, 0.0, 50.0, 0.0, 0.01, 50.0], camera(P, w, h, jitter=jitter))
