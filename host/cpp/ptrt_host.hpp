@@ -94,6 +94,17 @@ public:
         check(pt_gather(ctx_, scene_, points.data(), rows.data(), points.size() / 8, &gp, stats), ctx_);
         return rows;
     }
+    // docs/SPEC.md §12.1: Gather with every sample a whole path that starts at the point (pp.max_depth segments at most, 0 = 8; Russian
+    // roulette from pp.rr_start on): E carries emission and bounced light, visibility and bent are Gather's. stats->rays: segments traced.
+    std::vector<float> GatherPaths(const std::vector<float> &points, pt_gather_params gp = {}, pt_gather_path_params pp = {}, pt_stats *stats = nullptr)
+    {
+        if (points.size() % 8) throw Error(PT_ERR_INVALID_ARGUMENT, "GatherPaths: 8 floats per point");
+        std::vector<float> rows(points.size());
+        if (points.empty()) return rows; // (an empty vector has no storage to point at)
+        gp.flags |= PT_GATHER_HOST_MEMORY;
+        check(pt_gather_paths(ctx_, scene_, points.data(), rows.data(), points.size() / 8, &gp, &pp, stats), ctx_);
+        return rows;
+    }
     void SetCamera(const pt_camera &cam) { check(pt_scene_set_camera(scene_, &cam), ctx_); } // no new commit needed
     // docs/SPEC.md §11: n x n texels of linear RGB, octahedral layout; an empty vector with n = 0 removes the map. No new commit needed.
     void set_environment(const std::vector<float> &rgb, uint32_t n)

@@ -44,6 +44,7 @@ public enum PtBvhWidth : uint { Default = 0, W2 = 2, W4 = 4, W4Q = 68, W8Q = 72,
 [StructLayout(LayoutKind.Sequential)] public struct PtTileLayout { public uint tile_size; public uint tiles_x; public uint tiles_y; public uint n_tiles; public uint tiles_mine; public uint tiles_per_rank; public ulong floats_per_tile; }
 [StructLayout(LayoutKind.Sequential)] public unsafe struct PtDenoiseParams { public uint iterations; public float sigma_color; public float sigma_normal; public float sigma_depth; public float sigma_albedo; public uint flags; public fixed uint pad[2]; }
 [StructLayout(LayoutKind.Sequential)] public struct PtGatherParams { public uint samples; public uint seed; public uint sample_offset; public uint point_offset; public float max_distance; public float ray_eps; public uint flags; public uint pad; }
+[StructLayout(LayoutKind.Sequential)] public unsafe struct PtGatherPathParams { public uint max_depth; public uint rr_start; public uint flags; public fixed uint pad[5]; }
 [StructLayout(LayoutKind.Sequential)] public unsafe struct PtTemporalParams { public uint max_history; public float plane_tolerance; public float normal_min; public uint flags; public fixed uint pad[4]; }
 [StructLayout(LayoutKind.Sequential)] public struct PtDisplayParams { public uint source; public uint curve; public float exposure; public float white; public float key; public float adapt; public uint trim_low; public uint trim_high; public uint flags; public uint pad; }
 [StructLayout(LayoutKind.Sequential)] public struct PtDisplayInfo { public float exposure; public float metered; public float log_average; public uint adapted; public ulong counted; public ulong used; }
@@ -80,6 +81,7 @@ public static unsafe class Ptrt
     [DllImport(Lib)] public static extern PtStatus pt_render(void* ctx, void* scene, PtRenderParams* p, PtStats* stats);
     [DllImport(Lib)] public static extern PtStatus pt_trace_rays(void* ctx, void* scene, void* rays, void* hits, ulong n_rays, uint flags, PtStats* stats);
     [DllImport(Lib)] public static extern PtStatus pt_gather(void* ctx, void* scene, void* points, void* @out, ulong n_points, PtGatherParams* gp, PtStats* stats);
+    [DllImport(Lib)] public static extern PtStatus pt_gather_paths(void* ctx, void* scene, void* points, void* @out, ulong n_points, PtGatherParams* gp, PtGatherPathParams* pp, PtStats* stats);
     [DllImport(Lib)] public static extern PtStatus pt_scene_update_triangles(void* s, void* verts9, ulong count, uint flags, PtStats* stats);
     [DllImport(Lib)] public static extern PtStatus pt_scene_update_spheres(void* s, float* cxyzr, ulong count);
     [DllImport(Lib)] public static extern PtStatus pt_denoise(void* ctx, void* scene, PtDenoiseParams* dp, PtStats* stats);

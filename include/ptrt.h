@@ -35,8 +35,8 @@ extern "C" {
  * pt_temporal_read / pt_temporal_device_ptr / pt_temporal_history_read, then pt_display, pt_display_params, pt_display_info, PT_DISPLAY_*,
  * PT_TONE_*, pt_display_read / pt_display_device_ptr / pt_display_info_read / pt_display_histogram_read, then PT_TEMPORAL_MOTION, then
  * pt_scene_set_environment, pt_environment_info and pt_scene_environment_info / pt_scene_environment_read, then pt_gather, pt_gather_params and
- * PT_GATHER_HOST_MEMORY, then pt_lens and pt_scene_set_lens / pt_scene_get_lens (additions only: no struct or
- * existing signature changed).
+ * PT_GATHER_HOST_MEMORY, then pt_lens and pt_scene_set_lens / pt_scene_get_lens, then pt_gather_paths and pt_gather_path_params
+ * (additions only: no struct or existing signature changed).
  * Hosts compare pt_abi_version() with the header they were built against. */
 #define PTRT_ABI_VERSION 2
 
@@ -323,6 +323,30 @@ typedef struct pt_gather_params {
  * probe. A failed call drains the context's stream. */
 pt_status pt_gather(pt_context *ctx, const pt_scene *scene, const void *points, void *out, uint64_t n_points,
                     const pt_gather_params *gp, pt_stats *stats);
+
+/* ---- path-traced gathers (docs/SPEC.md §12.1): what pt_gather does, with every sample a whole path of §5 that starts at the point
+ *      instead of at the camera — light emitted by surfaces and light that arrives after bounces reach E, so a closed, emitter-lit
+ *      scene bakes. Fused like pt_gather: 32 B in and 32 B out per point whatever samples and max_depth are. */
+typedef struct pt_gather_path_params {
+    uint32_t max_depth;   /* path segments per sample, 1..255; 0 = 8 */
+    uint32_t rr_start;    /* Russian roulette from this depth on, taken literally as in pt_render_params */
+    uint32_t flags;       /* 0; any bit is PT_ERR_INVALID_ARGUMENT (reserved: next-event estimation in the gather) */
+    uint32_t pad[5];
+} pt_gather_path_params;  /* 32 B */
+/* points, out, n_points, gp (every field, PT_GATHER_HOST_MEMORY included), alignment and point_offset are pt_gather's. Sample k of point
+ * i leaves the same origin in the same direction d as pt_gather's (same key, dimensions 0 and 1); from there §5's loop runs unchanged
+ * with T = 1, depth 0, the stated max_depth and rr_start and ray_eps = gp->ray_eps, its vertices drawing dimensions 4 + 4b .. 7 + 4b of
+ * that key. The point stands where the camera stands: it is no vertex and has no albedo. E = (sum of the paths' radiance) / K, summed in
+ * §12's order with one fma per emission or miss term; pi * E is the irradiance for a Lambert texel. visibility and bent are pt_gather's,
+ * bit for bit, for the same gp: V = 1 unless the first segment's closest hit lies within max_distance (the path itself goes on from the
+ * closest hit whatever max_distance is). With max_depth 1, max_distance 0 and no emissive material the whole record is pt_gather's.
+ * Invalid points, finiteness and the clamp of E are pt_gather's.
+ * Checked first: pp NULL, pp->flags != 0, max_depth > 255 -> PT_ERR_INVALID_ARGUMENT; then every check of pt_gather in its order.
+ * n_points == 0 is PT_OK. stats (may be NULL): paths = n_points, rays = path segments traced (exact), gpu_ms, everything else 0. Touches no
+ * state of pt_render, pt_denoise*, pt_display or pt_gather, never runs the extend-kernel probe; a failed call drains the context's stream.
+ * Not there: next-event estimation (pp->flags is reserved for it), the lens, a transmitting or glossy point. */
+pt_status pt_gather_paths(pt_context *ctx, const pt_scene *scene, const void *points, void *out, uint64_t n_points,
+                          const pt_gather_params *gp, const pt_gather_path_params *pp, pt_stats *stats);
 
 /* ---- geometry updates (docs/SPEC.md §4.3): move a committed scene's triangles or spheres without a new commit — what a host's
  *      per-frame Update hook (Renderer.Update, Renderer.cs:86-89) uses to animate. The BVH keeps its topology and leaf assignment;

@@ -127,6 +127,10 @@ class pt_gather_params(C.Structure):
                 ("max_distance", C.c_float), ("ray_eps", C.c_float), ("flags", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class pt_gather_path_params(C.Structure):
+    _fields_ = [("max_depth", C.c_uint32), ("rr_start", C.c_uint32), ("flags", C.c_uint32), ("pad", C.c_uint32 * 5)]
+
+
 class pt_lens(C.Structure):
     _fields_ = [("radius", C.c_float), ("focus_distance", C.c_float), ("flags", C.c_uint32), ("pad", C.c_uint32 * 5)]
 
@@ -169,6 +173,7 @@ SYMBOLS = {
     "pt_render": (_st, [_vp, _vp, _P(pt_render_params), _P(pt_stats)]),
     "pt_trace_rays": (_st, [_vp, _vp, _vp, _vp, _u64, _u32, _P(pt_stats)]),
     "pt_gather": (_st, [_vp, _vp, _vp, _vp, _u64, _P(pt_gather_params), _P(pt_stats)]),
+    "pt_gather_paths": (_st, [_vp, _vp, _vp, _vp, _u64, _P(pt_gather_params), _P(pt_gather_path_params), _P(pt_stats)]),
     "pt_scene_update_triangles": (_st, [_vp, _vp, _u64, _u32, _P(pt_stats)]),
     "pt_scene_update_spheres": (_st, [_vp, _vp, _u64]),
     "pt_denoise": (_st, [_vp, _vp, _P(pt_denoise_params), _P(pt_stats)]),

@@ -319,7 +319,7 @@ private:
     uint32_t bound = 0;
 };
 
-// The plumbing of a query (pt_trace_rays, pt_gather, pt_denoise's guide pass): its own counter block, overflow stack, staging buffers
+// The plumbing of a query (pt_trace_rays, pt_gather, pt_gather_paths, pt_denoise's guide pass): its own counter block, overflow stack, staging buffers
 // (PT_TRACE_HOST_MEMORY) and events, so that a query touches nothing a frame reads (the frame-start template, the partial sums, the queues
 // and their counters). All on the context's stream (query.cpp; the guide pass is denoise_host.cpp's).
 class Queries {

@@ -17,6 +17,8 @@
 //                        the function k_extend traces its rays with; no path state
 //   k_gather<L,ENV>    : pt_gather: caller points -> K cosine-weighted occlusion rays each, made and traced (trace_ray's any-hit) by a
 //                        group of lanes and reduced in the wave to visibility, sky irradiance and bent normal
+//   k_gather_paths<L,ENV> : pt_gather_paths: the same points, groups and sums, each sample a whole path of the path loop (emission and
+//                        bounces reach E), one segment per lane per pass with in-place regeneration of the lane's next sample
 //   k_reduce_streams   : fixed-order sum of a pixel's stream partials
 //   k_assemble         : tile-major slots (of 1..R ranks) -> row-major float4 + RGBA8 frame
 //
@@ -1789,6 +1791,163 @@ k_gather(GatherArgsT<ENV> args)
 }
 
 // ------------------------------------------------------------------------------------------------
+// k_gather_paths<L, ENV>: pt_gather_paths (docs/SPEC.md §12.1). k_gather's points, groups, sums and records, but a sample is a whole
+// path of §5 that starts at the point instead of at the camera: E is the mean radiance the paths bring, emission and bounces included;
+// visibility and bent are k_gather's (V_k = 0 iff the first segment's closest hit lies within tmax). The arguments are GatherArgs with
+// fp.max_depth, fp.rr_start and fp.ray_eps filled in (launch_gather_paths).
+// The flat form of k_extend: one loop whose pass traces one segment per lane (trace_ray's closest hit from (+inf, MISS)) and shades its
+// vertex, all kinds by a divergent branch; a lane whose path ended starts its next sample g + G, g + 2G, ... in place, and the wave
+// leaves the loop when no lane has a sample left (a ballot: the butterfly behind it runs in uniform control flow). A lane adds the same
+// terms in the same order as "each sample's path to its end, samples in increasing k" would: fma(T, L, acc) on its running sums.
+// Across a traversal the lane keeps in its LDS column, behind the stack's rows: the seven sums of k_gather, T, the path's key and
+// k << 8 | depth (12 rows: 6144 B per wave with the stack, which 6 waves per SIMD fit into the CU's 160 KB); o and d stay in
+// registers, the traversal reads them anyway. The vertex is shade_one's SHADE_INLINE branch restated on a lane's own sums (§5: the
+// normal and emission lines, the three samplers, roulette_ends), without a slot, a queue or PathState.
+// Counters: invalid points as k_gather; the segments traced, one 64-bit atomic per wave at the end, where the triangle-test counter
+// lives (kCntTris: pt_stats::rays is exact).
+// The budgets: the highest number of waves at which no instantiation spills (tools/resources.py --filter k_gather_paths).
+#define PT_GATHER_PATH_WAVES(L, ENV) 6
+template <int L, bool ENV>
+__global__ void __launch_bounds__(kExtBlock) __attribute__((amdgpu_waves_per_eu(PT_GATHER_PATH_WAVES(L, ENV), PT_GATHER_PATH_WAVES(L, ENV))))
+k_gather_paths(GatherArgsT<ENV> args)
+{
+    static_assert(kExtBlock == 64u, "a group of lanes lives in one wave");
+    const GatherArgs &a = args.x;
+    const HotScene g = hot_scene(a.sc);
+    const uint32_t n = a.n, K = a.samples, gshift = a.gshift;
+    const float4 *__restrict__ points = a.points;
+    float4 *__restrict__ out = a.out;
+    __shared__ int32_t s_stack[kStackLds * kExtBlock];
+    const uint32_t tid = threadIdx.x;
+    const StackCtx stk{ s_stack, kExtBlock, tid, blockIdx.x * kExtBlock + tid };
+    const uint32_t per_wave = kExtBlock >> gshift, G = 1u << gshift, lane = tid & (G - 1u);
+    const uint32_t seed_hashed = pcg(a.seed); // wave-uniform
+    __shared__ uint32_t s_sum[12 * kExtBlock]; // rows 0-5: E, bent; 6: the count; 7-9: T; 10: key; 11: k << 8 | depth
+    auto row = [&](uint32_t j) -> uint32_t & { return s_sum[j * kExtBlock + tid]; };
+    auto sum_add = [&](uint32_t j, float x) { row(j) = __float_as_uint(__uint_as_float(row(j)) + x); };
+    auto sum_fma = [&](uint32_t j, float t, float x) { row(j) = __float_as_uint(fma_(t, x, __uint_as_float(row(j)))); };
+    auto sum_of = [&](uint32_t j) { return __uint_as_float(row(j)); };
+    VisitCounts vc;
+    unsigned long long wave_rays = 0; // wave-uniform
+    for (uint32_t base = blockIdx.x * per_wave; base < n; base += gridDim.x * per_wave) { // wave-uniform; n <= 2^31 (query.cpp): no wrap
+        const uint32_t i = base + (tid >> gshift);
+        bool valid = false;
+        if (i < n) {
+            const V3 p = xyz(points[2u * (size_t)i]), nv = xyz(points[2u * (size_t)i + 1u]);
+            const float n2 = dot(nv, nv);
+            valid = (p.x - p.x) == 0.0f && (p.y - p.y) == 0.0f && (p.z - p.z) == 0.0f && (n2 - n2) == 0.0f && n2 > 0.0f; // as k_gather
+            if (!valid && lane == 0u) atomicAdd(&cold().ps.counters[kCntNodes], 1u);
+        }
+        for (uint32_t j = 0; j < 7u; ++j) row(j) = 0u;
+        V3 o = v3(0.f, 0.f, 0.f), d = v3(0.f, 0.f, 1.f);
+        // Sample k of the lane's point: §12's origin and direction (the point is read behind an opaque index, as in k_gather), T = 1, depth 0
+        auto start = [&](uint32_t k) {
+            uint32_t ii = i;
+            asm volatile("" : "+v"(ii));
+            const V3 nn = normalize(xyz(points[2u * (size_t)ii + 1u]));
+            o = madd(a.ray_eps, nn, xyz(points[2u * (size_t)ii]));
+            const uint32_t key = path_key(seed_hashed, a.point_offset + ii, a.sample_offset + k);
+            d = normalize(lambert_vec(nn, u01(key, 0u), u01(key, 1u)));
+            row(7u) = row(8u) = row(9u) = __float_as_uint(1.0f);
+            row(10u) = key; row(11u) = k << 8;
+        };
+        bool alive = valid && lane < K;
+        if (alive) start(lane);
+        for (;;) {
+            const uint64_t alive_mask = __ballot(alive);
+            if (alive_mask == 0) break;
+            wave_rays += (unsigned long long)__popcll(alive_mask);
+            if (alive) {
+                asm volatile("" ::: "memory"); // the lane's state really is in LDS across the traversal: no forwarding (stash_park)
+                const Hit h = trace_ray<L, false, false, false>(g, stk, o, d, Hit{ __builtin_inff(), PT_MISS, PT_MISS }, vc, nullptr);
+                asm volatile("" ::: "memory");
+                const DeviceScene &sc = cold().sc;
+                const FrameParams &fp = cold().fp;
+                V3 T = v3(sum_of(7u), sum_of(8u), sum_of(9u));
+                const uint32_t key = row(10u), kd = row(11u);
+                uint32_t k = kd >> 8;
+                const uint32_t depth = (kd & 255u) + 1u;
+                bool term = false;
+                auto add = [&](V3 Lr) { sum_fma(0u, T.x, Lr.x); sum_fma(1u, T.y, Lr.y); sum_fma(2u, T.z, Lr.z); };
+                if (depth == 1u && !(h.ref != PT_MISS && h.t <= a.tmax)) { // §12's V_k and bent: nothing within tmax on the first segment
+                    sum_add(3u, d.x); sum_add(4u, d.y); sum_add(5u, d.z);
+                    row(6u) += 1u;
+                }
+                if (h.ref == PT_MISS) { // ---- a miss: its radiance, and the path ends
+                    if constexpr (ENV) {
+                        const EnvArgs &ea = reinterpret_cast<const GatherArgsT<true> &>(kernargs<false, false>()).env;
+                        float s;
+                        add(xyz(ea.texels[env_texel(ea, d, s)]));
+                    } else add(v3(sc.sky[0], sc.sky[1], sc.sky[2]));
+                    term = true;
+                } else {                // ---- a hit: the surface and its emission (shade_one's lines)
+                    const V3 P = madd(h.t, d, o);
+                    V3 ng;
+                    uint32_t mat;
+                    if (h.ref < sc.n_tris) {
+                        const float4 ts = sc.tris[(size_t)h.ref * 4 + 3];
+                        ng = xyz(ts);
+                        mat = __float_as_uint(ts.w);
+                    } else {
+                        const uint32_t j = h.ref - sc.n_tris;
+                        const float4 s = sc.spheres[j];
+                        const uint2 mi = sc.sph_mat[j];
+                        const float ir = __uint_as_float(mi.y);
+                        ng = v3((P.x - s.x) * ir, (P.y - s.y) * ir, (P.z - s.z) * ir);
+                        mat = mi.x;
+                    }
+                    const bool front = dot(ng, d) < 0.0f;
+                    const V3 nrm = front ? ng : neg(ng);
+                    float4 m0 = sc.mats[(size_t)mat * 3], m1 = sc.mats[(size_t)mat * 3 + 1];
+                    const float4 m2 = sc.mats[(size_t)mat * 3 + 2];
+                    asm volatile("" : "+v"(m0.x), "+v"(m1.x)); // both rows requested before either is looked at
+                    const V3 alb = v3(m0.y, m0.z, m0.w), emi = xyz(m1);
+                    const uint32_t kind = __float_as_uint(m0.x);
+                    if (emi.x != 0.0f || emi.y != 0.0f || emi.z != 0.0f) add(emi);
+                    if (depth >= fp.max_depth) term = true;
+                    else {              // ---- BSDF sample, throughput, Russian roulette
+                        const uint32_t bb = depth - 1u;
+                        BsdfSample bs;
+                        if (kind == (uint32_t)PT_LAMBERT) bs = sample_lambert(alb, nrm, u01(key, 4u + 4u * bb), u01(key, 5u + 4u * bb));
+                        else if (kind == (uint32_t)PT_METAL) bs = sample_metal(alb, m1.w, d, nrm, u01(key, 4u + 4u * bb), u01(key, 5u + 4u * bb));
+                        else bs = sample_dielectric(alb, m2.x, d, nrm, front, u01(key, 6u + 4u * bb));
+                        if (!bs.ok) term = true;
+                        else {
+                            T = v3(T.x * bs.W.x, T.y * bs.W.y, T.z * bs.W.z);
+                            if (roulette_ends(fp, key, depth, bb, T)) term = true;
+                            if (!term) { o = madd(bs.side * fp.ray_eps, nrm, P); d = bs.wi; }
+                        }
+                    }
+                }
+                if (term) { // the lane's next sample, in place
+                    k += G;
+                    alive = k < K;
+                    if (alive) start(k);
+                } else {
+                    row(7u) = __float_as_uint(T.x); row(8u) = __float_as_uint(T.y); row(9u) = __float_as_uint(T.z);
+                    row(11u) = (k << 8) | depth;
+                }
+            }
+        }
+        asm volatile("" ::: "memory");
+        float ex = sum_of(0u), ey = sum_of(1u), ez = sum_of(2u), bx = sum_of(3u), by = sum_of(4u), bz = sum_of(5u);
+        uint32_t cnt = row(6u);
+        for (uint32_t m = G >> 1; m; m >>= 1) { // the butterfly stays inside the group: m < G
+            cnt += (uint32_t)__shfl_xor((int)cnt, (int)m, 64);
+            ex = ex + __shfl_xor(ex, (int)m, 64); ey = ey + __shfl_xor(ey, (int)m, 64); ez = ez + __shfl_xor(ez, (int)m, 64);
+            bx = bx + __shfl_xor(bx, (int)m, 64); by = by + __shfl_xor(by, (int)m, 64); bz = bz + __shfl_xor(bz, (int)m, 64);
+        }
+        if (lane == 0u && i < n) {
+            const float fk = (float)K, big = 3.40282347e38f; // a sum that overflowed is stored as the largest finite float
+            auto mean = [&](float s) { return fmin_(fmax_(s / fk, -big), big); };
+            out[2u * (size_t)i] = valid ? make_float4(mean(ex), mean(ey), mean(ez), (float)cnt / fk) : make_float4(0.f, 0.f, 0.f, -1.0f);
+            out[2u * (size_t)i + 1u] = valid ? make_float4(bx / fk, by / fk, bz / fk, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    }
+    if (wave_rays && lane_id() == 0u) atomicAdd(reinterpret_cast<unsigned long long *>(cold().ps.counters + kCntTris), wave_rays);
+}
+
+// ------------------------------------------------------------------------------------------------
 // k_shade<SHADE_QUEUE>   : walks the extend queue of this iteration in the SAME order k_extend did, so ray/throughput/hit
 //                          reads are the coalesced, L2-warm lines k_extend just touched. Misses and Lambert hits are shaded
 //                          in place; specular kinds (metal, dielectric) are deferred to per-kind bucket queues.
@@ -1983,20 +2142,42 @@ uint32_t gather_blocks(uint32_t n, uint32_t samples)
     return std::max(1u, std::min(kTraceBlocks, (uint32_t)(((uint64_t)n + per_wave - 1u) / per_wave)));
 }
 
-hipError_t launch_gather(hipStream_t s, const DeviceScene &sc, const PathState &ps, const float4 *points, float4 *out, uint32_t n, const GatherParams &gp,
-                         const EnvArgs *env)
+// The argument block of k_gather and k_gather_paths; pp (k_gather_paths only): the path parameters, which travel in the block's FrameParams.
+static GatherArgsT<true> gather_args(const DeviceScene &sc, const PathState &ps, const float4 *points, float4 *out, uint32_t n, const GatherParams &gp,
+                                     const GatherPathParams *pp, const EnvArgs *env)
 {
     GatherArgsT<true> t{};
     GatherArgs &a = t.x;
     a.sc = sc; a.ps = ps; a.points = points; a.out = out; a.n = n;
     a.samples = gp.samples; a.gshift = gather_group_shift(gp.samples); a.seed = gp.seed;
     a.point_offset = gp.point_offset; a.sample_offset = gp.sample_offset; a.tmax = gp.tmax; a.ray_eps = gp.ray_eps;
+    if (pp) { a.fp.max_depth = pp->max_depth; a.fp.rr_start = pp->rr_start; a.fp.ray_eps = gp.ray_eps; }
     if (env) t.env = *env;
+    return t;
+}
+
+hipError_t launch_gather(hipStream_t s, const DeviceScene &sc, const PathState &ps, const float4 *points, float4 *out, uint32_t n, const GatherParams &gp,
+                         const EnvArgs *env)
+{
+    const GatherArgsT<true> t = gather_args(sc, ps, points, out, n, gp, nullptr, env);
     const dim3 grid(gather_blocks(n, gp.samples));
     const bool known = with_layout(sc.bvh_width, [&](auto lc) {
         constexpr int L = decltype(lc)::value;
         if (env) hipLaunchKernelGGL((k_gather<L, true>), grid, dim3(kExtBlock), 0, s, t);
-        else hipLaunchKernelGGL((k_gather<L, false>), grid, dim3(kExtBlock), 0, s, GatherArgsT<false>{ a });
+        else hipLaunchKernelGGL((k_gather<L, false>), grid, dim3(kExtBlock), 0, s, GatherArgsT<false>{ t.x });
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
+}
+
+hipError_t launch_gather_paths(hipStream_t s, const DeviceScene &sc, const PathState &ps, const float4 *points, float4 *out, uint32_t n, const GatherParams &gp,
+                               const GatherPathParams &pp, const EnvArgs *env)
+{
+    const GatherArgsT<true> t = gather_args(sc, ps, points, out, n, gp, &pp, env);
+    const dim3 grid(gather_blocks(n, gp.samples));
+    const bool known = with_layout(sc.bvh_width, [&](auto lc) {
+        constexpr int L = decltype(lc)::value;
+        if (env) hipLaunchKernelGGL((k_gather_paths<L, true>), grid, dim3(kExtBlock), 0, s, t);
+        else hipLaunchKernelGGL((k_gather_paths<L, false>), grid, dim3(kExtBlock), 0, s, GatherArgsT<false>{ t.x });
     });
     return known ? hipGetLastError() : hipErrorInvalidValue;
 }

@@ -1,4 +1,4 @@
-// query.cpp — ray queries (pt_trace_rays, docs/SPEC.md §4.2), hemisphere gathers (pt_gather, §12) and the query plumbing of context.h
+// query.cpp — ray queries (pt_trace_rays, docs/SPEC.md §4.2), hemisphere gathers (pt_gather, §12; pt_gather_paths, §12.1) and the query plumbing of context.h
 // (Queries), which pt_denoise's guide pass shares (denoise_host.cpp).
 #include "scene.h"
 #include <hip/hip_runtime.h>
@@ -84,22 +84,31 @@ static pt_status trace_rays(pt_context *c, const pt_scene *s, const void *rays, 
     return PT_OK;
 }
 
-// pt_gather (docs/SPEC.md §12): the rays are made, traced and reduced inside k_gather; the host only checks, stages and launches.
-static pt_status gather(pt_context *c, const pt_scene *s, const void *points, void *out_rows, uint64_t n_points, const pt_gather_params *gp, pt_stats *stats)
+// pt_gather (docs/SPEC.md §12) and pt_gather_paths (§12.1): the rays are made, traced and reduced inside k_gather / k_gather_paths; the
+// host only checks, stages and launches. paths: the call is pt_gather_paths (fn names it in messages) and pp its own parameters, checked
+// before everything the two calls share.
+static pt_status gather(pt_context *c, const pt_scene *s, const void *points, void *out_rows, uint64_t n_points, const pt_gather_params *gp, pt_stats *stats,
+                        bool paths = false, const pt_gather_path_params *pp = nullptr)
 {
-    if (!gp) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_gather: params is NULL");
-    if (gp->flags & ~(uint32_t)PT_GATHER_HOST_MEMORY) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_gather: unknown flag bits 0x%x", gp->flags & ~(uint32_t)PT_GATHER_HOST_MEMORY);
-    if (gp->samples > 4096u) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_gather: samples %u is more than 4096", gp->samples);
-    if (!(gp->max_distance >= 0.0f) || std::isinf(gp->max_distance)) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_gather: max_distance must be 0 (unbounded) or finite and positive");
-    if (!(gp->ray_eps >= 0.0f) || std::isinf(gp->ray_eps)) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_gather: ray_eps must be finite and not negative");
+    const char *fn = paths ? "pt_gather_paths" : "pt_gather";
+    if (paths) {
+        if (!pp) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_gather_paths: path params is NULL");
+        if (pp->flags) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_gather_paths: unknown path flag bits 0x%x", pp->flags);
+        if (pp->max_depth > 255u) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_gather_paths: max_depth %u is more than 255", pp->max_depth);
+    }
+    if (!gp) return fail(c, PT_ERR_INVALID_ARGUMENT, "%s: params is NULL", fn);
+    if (gp->flags & ~(uint32_t)PT_GATHER_HOST_MEMORY) return fail(c, PT_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", fn, gp->flags & ~(uint32_t)PT_GATHER_HOST_MEMORY);
+    if (gp->samples > 4096u) return fail(c, PT_ERR_INVALID_ARGUMENT, "%s: samples %u is more than 4096", fn, gp->samples);
+    if (!(gp->max_distance >= 0.0f) || std::isinf(gp->max_distance)) return fail(c, PT_ERR_INVALID_ARGUMENT, "%s: max_distance must be 0 (unbounded) or finite and positive", fn);
+    if (!(gp->ray_eps >= 0.0f) || std::isinf(gp->ray_eps)) return fail(c, PT_ERR_INVALID_ARGUMENT, "%s: ray_eps must be finite and not negative", fn);
     const bool host = (gp->flags & PT_GATHER_HOST_MEMORY) != 0;
-    if (!c || !s || !points || !out_rows) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_gather: NULL argument");
+    if (!c || !s || !points || !out_rows) return fail(c, PT_ERR_INVALID_ARGUMENT, "%s: NULL argument", fn);
     const uintptr_t align = host ? 3u : 15u; // the kernel loads and stores 16-byte rows; staged host arrays only need float alignment
     if (((uintptr_t)points & align) || ((uintptr_t)out_rows & align))
-        return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_gather: points and out must be %u-byte aligned", (unsigned)align + 1u);
-    if (s->ctx != c) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_gather: scene belongs to another context");
+        return fail(c, PT_ERR_INVALID_ARGUMENT, "%s: points and out must be %u-byte aligned", fn, (unsigned)align + 1u);
+    if (s->ctx != c) return fail(c, PT_ERR_INVALID_ARGUMENT, "%s: scene belongs to another context", fn);
     if (!s->committed) return fail(c, PT_ERR_NOT_COMMITTED, "scene not committed");
-    if (n_points >> 32) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_gather: n_points %llu is not a batch size", (unsigned long long)n_points);
+    if (n_points >> 32) return fail(c, PT_ERR_INVALID_ARGUMENT, "%s: n_points %llu is not a batch size", fn, (unsigned long long)n_points);
     pt_stats res{};
     res.paths = n_points;
     if (n_points == 0) { if (stats) *stats = res; return PT_OK; }
@@ -107,10 +116,12 @@ static pt_status gather(pt_context *c, const pt_scene *s, const void *points, vo
     k.samples = gp->samples ? gp->samples : 64u; k.seed = gp->seed;
     k.point_offset = gp->point_offset; k.sample_offset = gp->sample_offset;
     k.tmax = gp->max_distance > 0.0f ? gp->max_distance : INFINITY; k.ray_eps = gp->ray_eps;
+    GatherPathParams kp{};
+    if (paths) { kp.max_depth = pp->max_depth ? pp->max_depth : 8u; kp.rr_start = pp->rr_start; }
     HIP_TRY(c, hipSetDevice(c->device));
     pt_status st;
-    if (!host && ((st = check_device_array(c, points, n_points * 32u, "points", "pt_gather", "PT_GATHER_HOST_MEMORY")) != PT_OK ||
-                  (st = check_device_array(c, out_rows, n_points * 32u, "out", "pt_gather", "PT_GATHER_HOST_MEMORY")) != PT_OK)) return st;
+    if (!host && ((st = check_device_array(c, points, n_points * 32u, "points", fn, "PT_GATHER_HOST_MEMORY")) != PT_OK ||
+                  (st = check_device_array(c, out_rows, n_points * 32u, "out", fn, "PT_GATHER_HOST_MEMORY")) != PT_OK)) return st;
     hipStream_t q = c->stream;
     PathState ps;
     // one overflow column per lane of the largest grid a launch of this call uses: setup sizes it for that many one-ray lanes
@@ -127,18 +138,27 @@ static pt_status gather(pt_context *c, const pt_scene *s, const void *points, vo
     HIP_TRY(c, hipEventRecord(c->query.ev[0], q));
     for (uint64_t first = 0; first < n_points; first += kTraceChunk) { // point_offset + first wraps like the key's own u32 arithmetic
         GatherParams kc = k; kc.point_offset = k.point_offset + (uint32_t)first;
-        HIP_TRY(c, launch_gather(q, s->ds, ps, d_points + 2u * first, d_out + 2u * first, (uint32_t)std::min(kTraceChunk, n_points - first), kc,
-                                 s->env.present() ? &env : nullptr));
+        const uint32_t nc = (uint32_t)std::min(kTraceChunk, n_points - first);
+        const EnvArgs *e = s->env.present() ? &env : nullptr;
+        if (paths) HIP_TRY(c, launch_gather_paths(q, s->ds, ps, d_points + 2u * first, d_out + 2u * first, nc, kc, kp, e));
+        else HIP_TRY(c, launch_gather(q, s->ds, ps, d_points + 2u * first, d_out + 2u * first, nc, kc, e));
     }
     HIP_TRY(c, hipEventRecord(c->query.ev[1], q));
     if (host) HIP_TRY(c, hipMemcpyAsync(out_rows, d_out, n_points * 32u, hipMemcpyDeviceToHost, q));
     Queries::Counts n;
     if ((st = c->query.finish(c, n)) != PT_OK) return st;
-    if (n.error) return fail(c, PT_ERR_INTERNAL, "pt_gather: device error flag 0x%x (1 = traversal stack overflow, 2 = step limit)", n.error);
+    if (n.error) return fail(c, PT_ERR_INTERNAL, "%s: device error flag 0x%x (1 = traversal stack overflow, 2 = step limit)", fn, n.error);
     float ms = 0.f; HIP_TRY(c, hipEventElapsedTime(&ms, c->query.ev[0], c->query.ev[1])); res.gpu_ms = ms;
-    res.rays = (uint64_t)k.samples * (n_points - n.node_visits); // the kernel counted the invalid points where the visit counter lives
+    // the kernel counted the invalid points where the visit counter lives, and k_gather_paths its segments where the triangle tests' does
+    res.rays = paths ? n.tri_tests : (uint64_t)k.samples * (n_points - n.node_visits);
     if (stats) *stats = res;
     return PT_OK;
+}
+
+extern "C" pt_status pt_gather_paths(pt_context *c, const pt_scene *s, const void *points, void *out, uint64_t n_points, const pt_gather_params *gp,
+                                     const pt_gather_path_params *pp, pt_stats *stats)
+{
+    return drained_on_failure(c, [&] { return gather(c, s, points, out, n_points, gp, stats, true, pp); });
 }
 
 extern "C" pt_status pt_gather(pt_context *c, const pt_scene *s, const void *points, void *out, uint64_t n_points, const pt_gather_params *gp, pt_stats *stats)

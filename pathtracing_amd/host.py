@@ -325,6 +325,21 @@ class Renderer:
         marks an invalid point); bent: (N, 3), the mean unoccluded direction, not normalised."""
         gp = N.pt_gather_params(samples=samples, seed=seed, sample_offset=sample_offset, point_offset=point_offset,
                                 max_distance=max_distance, ray_eps=ray_eps, flags=0)
+        return self._gather(points, normals, gp, lambda *a: N.lib.pt_gather(*a))
+
+    def GatherPaths(self, points, normals, samples=64, seed=0, sample_offset=0, point_offset=0, max_distance=0.0, ray_eps=1e-3,
+                    max_depth=8, rr_start=3):
+        """Path-traced gathers (include/ptrt.h pt_gather_paths, docs/SPEC.md §12.1): Gather's points, arguments and results, with every
+        sample a whole path of at most `max_depth` segments (Russian roulette from depth `rr_start` on) that starts at the point. E is
+        the mean radiance the paths bring — emissive surfaces and bounced light included, so pi * E is a Lambert texel's irradiance in
+        a closed, emitter-lit scene too; visibility and bent are Gather's. The pt_stats' rays are the path segments traced."""
+        gp = N.pt_gather_params(samples=samples, seed=seed, sample_offset=sample_offset, point_offset=point_offset,
+                                max_distance=max_distance, ray_eps=ray_eps, flags=0)
+        pp = N.pt_gather_path_params(max_depth=max_depth, rr_start=rr_start, flags=0)
+        return self._gather(points, normals, gp, lambda *a: N.lib.pt_gather_paths(*a[:-1], C.byref(pp), a[-1]))
+
+    def _gather(self, points, normals, gp, call):
+        """Gather / GatherPaths: builds the records, calls call(ctx, scene, points, out, n, gp, stats), splits the rows."""
         stats = N.pt_stats()
         if N.torch is not None and isinstance(points, N.torch.Tensor):
             torch = N.torch
@@ -339,8 +354,8 @@ class Renderer:
             out = torch.empty((rec.shape[0], 8), dtype=torch.float32, device=dev)
             if rec.shape[0]:  # (an empty tensor has no storage to point at)
                 torch.cuda.current_stream(dev).synchronize()  # the library runs on its own stream: the records must be complete
-                _check(N.lib.pt_gather(self._ctx, self._scene, C.c_void_p(rec.data_ptr()), C.c_void_p(out.data_ptr()), rec.shape[0],
-                                       C.byref(gp), C.byref(stats)), self._ctx)
+                _check(call(self._ctx, self._scene, C.c_void_p(rec.data_ptr()), C.c_void_p(out.data_ptr()), rec.shape[0],
+                            C.byref(gp), C.byref(stats)), self._ctx)
             return out[:, 0:3], out[:, 3], out[:, 4:7], stats
         p, n = (np.asarray(a, np.float32).reshape(-1, 3) for a in (points, normals))
         if p.shape != n.shape:
@@ -349,7 +364,7 @@ class Renderer:
         rec[:, 0:3], rec[:, 4:7] = p, n
         out = np.empty((len(rec), 8), np.float32)
         gp.flags = N.PT_GATHER_HOST_MEMORY
-        _check(N.lib.pt_gather(self._ctx, self._scene, _ptr(rec), _ptr(out), len(rec), C.byref(gp), C.byref(stats)), self._ctx)
+        _check(call(self._ctx, self._scene, _ptr(rec), _ptr(out), len(rec), C.byref(gp), C.byref(stats)), self._ctx)
         return out[:, 0:3], out[:, 3], out[:, 4:7], stats
 
     def UpdateGeometry(self, verts=None, spheres=None):
