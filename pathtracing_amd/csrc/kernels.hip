@@ -1691,18 +1691,16 @@ k_trace(TraceArgs a)
 }
 
 // ------------------------------------------------------------------------------------------------
-// k_gather<L, ENV>: pt_gather (docs/SPEC.md §12). Caller points {p.xyz | 0, n.xyz | 0} -> {E.rgb | visibility, bent.xyz | 0}: K
-// cosine-weighted occlusion rays per point, generated here (path_key / u01 / lambert_vec), traced with trace_ray's ANY and reduced in
-// the wave, so that neither a ray nor a hit record ever exists in memory.
+// The gather kernels: k_gather (pt_gather, docs/SPEC.md §12) and k_gather_paths (pt_gather_paths, §12.1). Caller points {p.xyz | 0,
+// n.xyz | 0} -> {E.rgb | visibility, bent.xyz | 0}: K cosine-weighted samples per point, generated here (path_key / u01 / lambert_vec),
+// traced with trace_ray and reduced in the wave, so that neither a ray nor a hit record ever exists in memory. What §12 fixes bit for
+// bit (which points count, a sample's ray, a miss's radiance, the order of the sums, the record) is stated once, in the helpers below;
+// a kernel adds its own loop over a lane's samples.
 // A group of G = 2^gshift lanes (G = min(64, the power of two >= K)) owns one point, a wave 64 / G points; lane g of the group takes the
 // samples g, g + G, ... in increasing order. Grid-stride over waves' point blocks like k_trace (the bound is wave-uniform, the lane keeps
 // its LDS stack column and its overflow column for all of its rays). Lanes of an invalid point, of a point beyond n and lanes g >= K
-// trace nothing but stay in the loop: the reduction below runs in uniform control flow.
-// §12's summation order: a lane adds its visible samples' terms to 0 in increasing k, then log2 G butterfly steps s = s + s[lane ^ m],
-// m = G/2 .. 1 (f32 addition commutes, so every lane of the group ends with the same bits); the count is an integer. Lane 0 of the group
-// divides by K and stores the two rows.
+// trace nothing but stay in the loop: gather_finish runs in uniform control flow.
 // ENV: the radiance of a direction is the environment map's texel (§11 encode) instead of the scene's sky.
-// The kernel counts the invalid points it met into the low word of kCntNodes (one atomic each: they are the exception).
 struct GatherArgs : ExtArgs {
     const float4 *points; // two rows per point
     float4 *out;          // two rows per point
@@ -1711,174 +1709,199 @@ struct GatherArgs : ExtArgs {
 };
 template <bool ENV> struct GatherArgsT { GatherArgs x; };
 template <> struct GatherArgsT<true> { GatherArgs x; EnvArgs env; };
+static_assert(kExtBlock == 64u, "a group of lanes lives in one wave");
 
+// What a lane has before its first point: the traversal's scene and stack (k_trace's), its place in its group, the hashed seed.
+struct GatherLane {
+    HotScene g;
+    StackCtx stk;
+    uint32_t tid, per_wave, G, lane, seed_hashed; // per_wave, G and seed_hashed are wave-uniform
+};
+PT_DEV GatherLane gather_lane(const GatherArgs &a, int32_t *s_stack)
+{
+    const uint32_t tid = threadIdx.x, G = 1u << a.gshift;
+    return GatherLane{ hot_scene(a.sc), StackCtx{ s_stack, kExtBlock, tid, blockIdx.x * kExtBlock + tid }, tid, kExtBlock >> a.gshift, G, tid & (G - 1u), pcg(a.seed) };
+}
+
+// A lane's ROWS words of LDS, in its column behind the stack's 12 rows: E's three float sums (rows 0-2), bent's (3-5), the count of
+// visible samples (6), then what the kernel keeps of its own. They are touched after a ray only: traversal keeps k_trace's register budget.
+template <uint32_t ROWS> struct GatherRows {
+    static_assert(ROWS >= 7u, "the sums of a record");
+    static constexpr uint32_t kWords = ROWS * kExtBlock;
+    uint32_t *col; // the block's rows + tid
+    PT_DEV uint32_t &row(uint32_t j) const { return col[j * kExtBlock]; }
+    PT_DEV float get(uint32_t j) const { return __uint_as_float(row(j)); }
+    PT_DEV void add(uint32_t j, float x) const { row(j) = __float_as_uint(get(j) + x); }
+    PT_DEV void fma(uint32_t j, float t, float x) const { row(j) = __float_as_uint(fma_(t, x, get(j))); }
+    PT_DEV void clear() const { for (uint32_t j = 0; j < 7u; ++j) row(j) = 0u; } // a new point: the sums start at 0
+    PT_DEV void visible(V3 d) const { add(3u, d.x); add(4u, d.y); add(5u, d.z); row(6u) += 1u; } // §12's V_k = 1: bent and the count
+};
+
+// Does point i count? Finite p and n, and a dot(n, n) that is neither 0 nor infinite (x - x is 0 exactly for a finite x, NaN otherwise).
+// The invalid points are counted into the low word of kCntNodes (one atomic each: they are the exception).
+PT_DEV bool gather_point_valid(const float4 *__restrict__ points, uint32_t i, uint32_t n, uint32_t lane)
+{
+    if (i >= n) return false;
+    const V3 p = xyz(points[2u * (size_t)i]), nv = xyz(points[2u * (size_t)i + 1u]);
+    const float n2 = dot(nv, nv);
+    const bool valid = (p.x - p.x) == 0.0f && (p.y - p.y) == 0.0f && (p.z - p.z) == 0.0f && (n2 - n2) == 0.0f && n2 > 0.0f;
+    if (!valid && lane == 0u) atomicAdd(&cold().ps.counters[kCntNodes], 1u);
+    return valid;
+}
+
+// Sample k of point i: the origin p + ray_eps * n^ and the cosine-weighted direction of the sample's key, which is returned.
+// The point is read again for every sample (its line is in the cache) behind an index the compiler cannot see through: neither the
+// normal nor the sample's key stays in registers across the traversal. (Keeping the first read's normal for the first sample and
+// reading again only for the later ones spills 1-3 VGPRs in every layout.)
+PT_DEV uint32_t gather_ray(const GatherArgs &a, const float4 *__restrict__ points, uint32_t i, uint32_t k, uint32_t seed_hashed, V3 &o, V3 &d)
+{
+    uint32_t ii = i;
+    asm volatile("" : "+v"(ii));
+    const V3 nn = normalize(xyz(points[2u * (size_t)ii + 1u]));
+    o = madd(a.ray_eps, nn, xyz(points[2u * (size_t)ii]));
+    const uint32_t key = path_key(seed_hashed, a.point_offset + ii, a.sample_offset + k);
+    d = normalize(lambert_vec(nn, u01(key, 0u), u01(key, 1u)));
+    return key;
+}
+
+// One segment through trace_ray from (tmax, MISS). The barriers: the lane's rows really are in LDS across the traversal, no forwarding
+// (stash_park).
+template <int L, bool ANY>
+PT_DEV Hit gather_trace(const GatherLane &w, V3 o, V3 d, float tmax, VisitCounts &vc)
+{
+    asm volatile("" ::: "memory");
+    const Hit h = trace_ray<L, false, false, ANY>(w.g, w.stk, o, d, Hit{ tmax, PT_MISS, PT_MISS }, vc, nullptr);
+    asm volatile("" ::: "memory");
+    return h;
+}
+
+// The radiance of a segment that left the scene in direction d: the map's texel or the scene's sky.
+template <bool ENV>
+PT_DEV V3 gather_miss(V3 d)
+{
+    if constexpr (ENV) {
+        const EnvArgs &ea = reinterpret_cast<const GatherArgsT<true> &>(kernargs<false, false>()).env; // read where it is used, like cold()
+        float s;
+        return xyz(ea.texels[env_texel(ea, d, s)]);
+    } else {
+        const DeviceScene &sc = cold().sc;
+        return v3(sc.sky[0], sc.sky[1], sc.sky[2]);
+    }
+}
+
+// The record of point i from its group's rows, §12's summation order: a lane has added its samples' terms to 0 in increasing k; now log2 G
+// butterfly steps s = s + s[lane ^ m], m = G/2 .. 1 (f32 addition commutes, so every lane of the group ends with the same bits); the
+// count is an integer. Lane 0 of the group divides by K and stores the two rows, (0, 0, 0, -1 | 0, 0, 0, 0) for an invalid point.
+template <uint32_t ROWS>
+PT_DEV void gather_finish(const GatherRows<ROWS> &rows, const GatherLane &w, uint32_t i, uint32_t n, uint32_t K, bool valid, float4 *__restrict__ out)
+{
+    asm volatile("" ::: "memory");
+    float ex = rows.get(0u), ey = rows.get(1u), ez = rows.get(2u), bx = rows.get(3u), by = rows.get(4u), bz = rows.get(5u);
+    uint32_t cnt = rows.row(6u);
+    for (uint32_t m = w.G >> 1; m; m >>= 1) { // the butterfly stays inside the group: m < G
+        cnt += (uint32_t)__shfl_xor((int)cnt, (int)m, 64);
+        ex = ex + __shfl_xor(ex, (int)m, 64); ey = ey + __shfl_xor(ey, (int)m, 64); ez = ez + __shfl_xor(ez, (int)m, 64);
+        bx = bx + __shfl_xor(bx, (int)m, 64); by = by + __shfl_xor(by, (int)m, 64); bz = bz + __shfl_xor(bz, (int)m, 64);
+    }
+    if (w.lane == 0u && i < n) {
+        const float fk = (float)K, big = 3.40282347e38f; // a sum that overflowed is stored as the largest finite float
+        auto mean = [&](float s) { return fmin_(fmax_(s / fk, -big), big); };
+        out[2u * (size_t)i] = valid ? make_float4(mean(ex), mean(ey), mean(ez), (float)cnt / fk) : make_float4(0.f, 0.f, 0.f, -1.0f);
+        out[2u * (size_t)i + 1u] = valid ? make_float4(bx / fk, by / fk, bz / fk, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+
+// k_gather<L, ENV>: K occlusion rays per point (trace_ray's ANY within tmax), a lane's samples one after the other; a visible sample
+// adds the radiance of its direction to E. 7 rows: 4864 B of LDS per wave with the stack, 8 waves per SIMD still fit the CU's 160 KB.
 template <int L, bool ENV>
 __global__ void __launch_bounds__(kExtBlock) __attribute__((amdgpu_waves_per_eu(PT_EXT_WAVES(L, SHADE_NONE), PT_EXT_WAVES(L, SHADE_NONE))))
 k_gather(GatherArgsT<ENV> args)
 {
-    static_assert(kExtBlock == 64u, "a group of lanes lives in one wave");
     const GatherArgs &a = args.x;
-    const HotScene g = hot_scene(a.sc);
-    const uint32_t n = a.n, K = a.samples, gshift = a.gshift;
+    const uint32_t n = a.n, K = a.samples;
     const float4 *__restrict__ points = a.points;
-    float4 *__restrict__ out = a.out;
     __shared__ int32_t s_stack[kStackLds * kExtBlock];
-    const uint32_t tid = threadIdx.x;
-    const StackCtx stk{ s_stack, kExtBlock, tid, blockIdx.x * kExtBlock + tid };
-    const uint32_t per_wave = kExtBlock >> gshift, G = 1u << gshift, lane = tid & (G - 1u);
-    const uint32_t seed_hashed = pcg(a.seed); // wave-uniform
-    // A lane's six float sums and its count live in its LDS column (7 rows behind the stack's 12: 4864 B per wave, 8 waves per SIMD still
-    // fit the CU's 160 KB) and are touched after a ray only: traversal keeps k_trace's register budget.
-    __shared__ uint32_t s_sum[7 * kExtBlock];
-    auto sum_add = [&](uint32_t j, float x) { s_sum[j * kExtBlock + tid] = __float_as_uint(__uint_as_float(s_sum[j * kExtBlock + tid]) + x); };
-    auto sum_of = [&](uint32_t j) { return __uint_as_float(s_sum[j * kExtBlock + tid]); };
+    __shared__ uint32_t s_rows[GatherRows<7>::kWords];
+    const GatherLane w = gather_lane(a, s_stack);
+    const GatherRows<7> rows{ s_rows + w.tid };
     VisitCounts vc;
-    for (uint32_t base = blockIdx.x * per_wave; base < n; base += gridDim.x * per_wave) { // wave-uniform; n <= 2^31 (query.cpp): no wrap
-        const uint32_t i = base + (tid >> gshift);
-        bool valid = false;
-        if (i < n) {
-            const V3 p = xyz(points[2u * (size_t)i]), nv = xyz(points[2u * (size_t)i + 1u]);
-            const float n2 = dot(nv, nv);
-            // finite p and n, and a dot(n, n) that is neither 0 nor infinite (x - x is 0 exactly for a finite x, NaN otherwise)
-            valid = (p.x - p.x) == 0.0f && (p.y - p.y) == 0.0f && (p.z - p.z) == 0.0f && (n2 - n2) == 0.0f && n2 > 0.0f;
-            if (!valid && lane == 0u) atomicAdd(&cold().ps.counters[kCntNodes], 1u);
-        }
-        for (uint32_t j = 0; j < 7u; ++j) s_sum[j * kExtBlock + tid] = 0u;
+    for (uint32_t base = blockIdx.x * w.per_wave; base < n; base += gridDim.x * w.per_wave) { // wave-uniform; n <= 2^31 (query.cpp): no wrap
+        const uint32_t i = base + (w.tid >> a.gshift);
+        const bool valid = gather_point_valid(points, i, n, w.lane);
+        rows.clear();
         if (valid)
-            for (uint32_t k = lane; k < K; k += G) {
-                // The point is read again for every sample (its line is in the cache) behind an index the compiler cannot see through:
-                // neither the normal nor the sample's key stays in registers across the traversal. (Keeping the first read's normal for
-                // the first sample and reading again only for the later ones spills 1-3 VGPRs in every layout.)
-                uint32_t ii = i;
-                asm volatile("" : "+v"(ii));
-                const V3 nn = normalize(xyz(points[2u * (size_t)ii + 1u]));
-                const V3 o = madd(a.ray_eps, nn, xyz(points[2u * (size_t)ii]));
-                const uint32_t key = path_key(seed_hashed, a.point_offset + ii, a.sample_offset + k);
-                const V3 d = normalize(lambert_vec(nn, u01(key, 0u), u01(key, 1u)));
-                asm volatile("" ::: "memory");
-                const Hit h = trace_ray<L, false, false, true>(g, stk, o, d, Hit{ a.tmax, PT_MISS, PT_MISS }, vc, nullptr);
-                asm volatile("" ::: "memory");
-                if (h.id == PT_MISS) {
-                    V3 e;
-                    if constexpr (ENV) {
-                        const EnvArgs &ea = reinterpret_cast<const GatherArgsT<true> &>(kernargs<false, false>()).env; // read where it is used, like cold()
-                        float s;
-                        e = xyz(ea.texels[env_texel(ea, d, s)]);
-                    } else {
-                        const DeviceScene &sc = cold().sc;
-                        e = v3(sc.sky[0], sc.sky[1], sc.sky[2]);
-                    }
-                    sum_add(0u, e.x); sum_add(1u, e.y); sum_add(2u, e.z);
-                    sum_add(3u, d.x); sum_add(4u, d.y); sum_add(5u, d.z);
-                    s_sum[6u * kExtBlock + tid] += 1u;
+            for (uint32_t k = w.lane; k < K; k += w.G) {
+                V3 o, d;
+                gather_ray(a, points, i, k, w.seed_hashed, o, d);
+                if (gather_trace<L, true>(w, o, d, a.tmax, vc).id == PT_MISS) {
+                    const V3 e = gather_miss<ENV>(d);
+                    rows.add(0u, e.x); rows.add(1u, e.y); rows.add(2u, e.z);
+                    rows.visible(d);
                 }
             }
-        asm volatile("" ::: "memory");
-        float ex = sum_of(0u), ey = sum_of(1u), ez = sum_of(2u), bx = sum_of(3u), by = sum_of(4u), bz = sum_of(5u);
-        uint32_t cnt = s_sum[6u * kExtBlock + tid];
-        for (uint32_t m = G >> 1; m; m >>= 1) { // the butterfly stays inside the group: m < G
-            cnt += (uint32_t)__shfl_xor((int)cnt, (int)m, 64);
-            ex = ex + __shfl_xor(ex, (int)m, 64); ey = ey + __shfl_xor(ey, (int)m, 64); ez = ez + __shfl_xor(ez, (int)m, 64);
-            bx = bx + __shfl_xor(bx, (int)m, 64); by = by + __shfl_xor(by, (int)m, 64); bz = bz + __shfl_xor(bz, (int)m, 64);
-        }
-        if (lane == 0u && i < n) {
-            const float fk = (float)K, big = 3.40282347e38f; // a sum that overflowed is stored as the largest finite float
-            auto mean = [&](float s) { return fmin_(fmax_(s / fk, -big), big); };
-            out[2u * (size_t)i] = valid ? make_float4(mean(ex), mean(ey), mean(ez), (float)cnt / fk) : make_float4(0.f, 0.f, 0.f, -1.0f);
-            out[2u * (size_t)i + 1u] = valid ? make_float4(bx / fk, by / fk, bz / fk, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
+        gather_finish(rows, w, i, n, K, valid, a.out);
     }
 }
 
-// ------------------------------------------------------------------------------------------------
-// k_gather_paths<L, ENV>: pt_gather_paths (docs/SPEC.md §12.1). k_gather's points, groups, sums and records, but a sample is a whole
-// path of §5 that starts at the point instead of at the camera: E is the mean radiance the paths bring, emission and bounces included;
-// visibility and bent are k_gather's (V_k = 0 iff the first segment's closest hit lies within tmax). The arguments are GatherArgs with
-// fp.max_depth, fp.rr_start and fp.ray_eps filled in (launch_gather_paths).
+// k_gather_paths<L, ENV>: a sample is a whole path of §5 that starts at the point instead of at the camera: E is the mean radiance the
+// paths bring, emission and bounces included; visibility and bent are k_gather's (V_k = 0 iff the first segment's closest hit lies within
+// tmax). The arguments are GatherArgs with fp.max_depth, fp.rr_start and fp.ray_eps filled in (launch_gather).
 // The flat form of k_extend: one loop whose pass traces one segment per lane (trace_ray's closest hit from (+inf, MISS)) and shades its
 // vertex, all kinds by a divergent branch; a lane whose path ended starts its next sample g + G, g + 2G, ... in place, and the wave
-// leaves the loop when no lane has a sample left (a ballot: the butterfly behind it runs in uniform control flow). A lane adds the same
+// leaves the loop when no lane has a sample left (a ballot: gather_finish behind it runs in uniform control flow). A lane adds the same
 // terms in the same order as "each sample's path to its end, samples in increasing k" would: fma(T, L, acc) on its running sums.
-// Across a traversal the lane keeps in its LDS column, behind the stack's rows: the seven sums of k_gather, T, the path's key and
-// k << 8 | depth (12 rows: 6144 B per wave with the stack, which 6 waves per SIMD fit into the CU's 160 KB); o and d stay in
-// registers, the traversal reads them anyway. The vertex is shade_one's SHADE_INLINE branch restated on a lane's own sums (§5: the
-// normal and emission lines, the three samplers, roulette_ends), without a slot, a queue or PathState.
-// Counters: invalid points as k_gather; the segments traced, one 64-bit atomic per wave at the end, where the triangle-test counter
-// lives (kCntTris: pt_stats::rays is exact).
-// The budgets: the highest number of waves at which no instantiation spills (tools/resources.py --filter k_gather_paths).
-#define PT_GATHER_PATH_WAVES(L, ENV) 6
+// Across a traversal the lane keeps in its rows, behind the seven sums: T (7-9), the path's key (10) and k << 8 | depth (11). 12 rows:
+// 6144 B per wave with the stack, which 6 waves per SIMD fit into the CU's 160 KB; o and d stay in registers, the traversal reads them
+// anyway. The vertex is shade_one's SHADE_INLINE branch restated on a lane's own sums (§5: the normal and emission lines, the three
+// samplers, roulette_ends), without a slot, a queue or PathState; sharing those lines with shade_one costs the extend kernels their
+// register budgets.
+// Counters: the segments traced, one 64-bit atomic per wave at the end, where the triangle-test counter lives (kCntTris: pt_stats::rays
+// is exact).
+// The budget: the highest number of waves at which no instantiation spills (tools/resources.py --filter k_gather_paths).
+constexpr int kGatherPathWaves = 6;
 template <int L, bool ENV>
-__global__ void __launch_bounds__(kExtBlock) __attribute__((amdgpu_waves_per_eu(PT_GATHER_PATH_WAVES(L, ENV), PT_GATHER_PATH_WAVES(L, ENV))))
+__global__ void __launch_bounds__(kExtBlock) __attribute__((amdgpu_waves_per_eu(kGatherPathWaves, kGatherPathWaves)))
 k_gather_paths(GatherArgsT<ENV> args)
 {
-    static_assert(kExtBlock == 64u, "a group of lanes lives in one wave");
     const GatherArgs &a = args.x;
-    const HotScene g = hot_scene(a.sc);
-    const uint32_t n = a.n, K = a.samples, gshift = a.gshift;
+    const uint32_t n = a.n, K = a.samples;
     const float4 *__restrict__ points = a.points;
-    float4 *__restrict__ out = a.out;
     __shared__ int32_t s_stack[kStackLds * kExtBlock];
-    const uint32_t tid = threadIdx.x;
-    const StackCtx stk{ s_stack, kExtBlock, tid, blockIdx.x * kExtBlock + tid };
-    const uint32_t per_wave = kExtBlock >> gshift, G = 1u << gshift, lane = tid & (G - 1u);
-    const uint32_t seed_hashed = pcg(a.seed); // wave-uniform
-    __shared__ uint32_t s_sum[12 * kExtBlock]; // rows 0-5: E, bent; 6: the count; 7-9: T; 10: key; 11: k << 8 | depth
-    auto row = [&](uint32_t j) -> uint32_t & { return s_sum[j * kExtBlock + tid]; };
-    auto sum_add = [&](uint32_t j, float x) { row(j) = __float_as_uint(__uint_as_float(row(j)) + x); };
-    auto sum_fma = [&](uint32_t j, float t, float x) { row(j) = __float_as_uint(fma_(t, x, __uint_as_float(row(j)))); };
-    auto sum_of = [&](uint32_t j) { return __uint_as_float(row(j)); };
+    __shared__ uint32_t s_rows[GatherRows<12>::kWords];
+    const GatherLane w = gather_lane(a, s_stack);
+    const GatherRows<12> rows{ s_rows + w.tid };
+    constexpr uint32_t kT = 7u, kKey = 10u, kSampleDepth = 11u; // the rows of the lane's path
     VisitCounts vc;
     unsigned long long wave_rays = 0; // wave-uniform
-    for (uint32_t base = blockIdx.x * per_wave; base < n; base += gridDim.x * per_wave) { // wave-uniform; n <= 2^31 (query.cpp): no wrap
-        const uint32_t i = base + (tid >> gshift);
-        bool valid = false;
-        if (i < n) {
-            const V3 p = xyz(points[2u * (size_t)i]), nv = xyz(points[2u * (size_t)i + 1u]);
-            const float n2 = dot(nv, nv);
-            valid = (p.x - p.x) == 0.0f && (p.y - p.y) == 0.0f && (p.z - p.z) == 0.0f && (n2 - n2) == 0.0f && n2 > 0.0f; // as k_gather
-            if (!valid && lane == 0u) atomicAdd(&cold().ps.counters[kCntNodes], 1u);
-        }
-        for (uint32_t j = 0; j < 7u; ++j) row(j) = 0u;
+    for (uint32_t base = blockIdx.x * w.per_wave; base < n; base += gridDim.x * w.per_wave) { // wave-uniform; n <= 2^31 (query.cpp): no wrap
+        const uint32_t i = base + (w.tid >> a.gshift);
+        const bool valid = gather_point_valid(points, i, n, w.lane);
+        rows.clear();
         V3 o = v3(0.f, 0.f, 0.f), d = v3(0.f, 0.f, 1.f);
-        // Sample k of the lane's point: §12's origin and direction (the point is read behind an opaque index, as in k_gather), T = 1, depth 0
-        auto start = [&](uint32_t k) {
-            uint32_t ii = i;
-            asm volatile("" : "+v"(ii));
-            const V3 nn = normalize(xyz(points[2u * (size_t)ii + 1u]));
-            o = madd(a.ray_eps, nn, xyz(points[2u * (size_t)ii]));
-            const uint32_t key = path_key(seed_hashed, a.point_offset + ii, a.sample_offset + k);
-            d = normalize(lambert_vec(nn, u01(key, 0u), u01(key, 1u)));
-            row(7u) = row(8u) = row(9u) = __float_as_uint(1.0f);
-            row(10u) = key; row(11u) = k << 8;
+        auto start = [&](uint32_t k) { // sample k of the lane's point: §12's ray, T = 1, depth 0
+            const uint32_t key = gather_ray(a, points, i, k, w.seed_hashed, o, d);
+            rows.row(kT) = rows.row(kT + 1u) = rows.row(kT + 2u) = __float_as_uint(1.0f);
+            rows.row(kKey) = key; rows.row(kSampleDepth) = k << 8;
         };
-        bool alive = valid && lane < K;
-        if (alive) start(lane);
+        bool alive = valid && w.lane < K;
+        if (alive) start(w.lane);
         for (;;) {
             const uint64_t alive_mask = __ballot(alive);
             if (alive_mask == 0) break;
             wave_rays += (unsigned long long)__popcll(alive_mask);
             if (alive) {
-                asm volatile("" ::: "memory"); // the lane's state really is in LDS across the traversal: no forwarding (stash_park)
-                const Hit h = trace_ray<L, false, false, false>(g, stk, o, d, Hit{ __builtin_inff(), PT_MISS, PT_MISS }, vc, nullptr);
-                asm volatile("" ::: "memory");
+                const Hit h = gather_trace<L, false>(w, o, d, __builtin_inff(), vc);
                 const DeviceScene &sc = cold().sc;
                 const FrameParams &fp = cold().fp;
-                V3 T = v3(sum_of(7u), sum_of(8u), sum_of(9u));
-                const uint32_t key = row(10u), kd = row(11u);
+                V3 T = v3(rows.get(kT), rows.get(kT + 1u), rows.get(kT + 2u));
+                const uint32_t key = rows.row(kKey), kd = rows.row(kSampleDepth);
                 uint32_t k = kd >> 8;
                 const uint32_t depth = (kd & 255u) + 1u;
                 bool term = false;
-                auto add = [&](V3 Lr) { sum_fma(0u, T.x, Lr.x); sum_fma(1u, T.y, Lr.y); sum_fma(2u, T.z, Lr.z); };
-                if (depth == 1u && !(h.ref != PT_MISS && h.t <= a.tmax)) { // §12's V_k and bent: nothing within tmax on the first segment
-                    sum_add(3u, d.x); sum_add(4u, d.y); sum_add(5u, d.z);
-                    row(6u) += 1u;
-                }
+                auto add = [&](V3 Lr) { rows.fma(0u, T.x, Lr.x); rows.fma(1u, T.y, Lr.y); rows.fma(2u, T.z, Lr.z); };
+                if (depth == 1u && !(h.ref != PT_MISS && h.t <= a.tmax)) rows.visible(d); // nothing within tmax on the first segment
                 if (h.ref == PT_MISS) { // ---- a miss: its radiance, and the path ends
-                    if constexpr (ENV) {
-                        const EnvArgs &ea = reinterpret_cast<const GatherArgsT<true> &>(kernargs<false, false>()).env;
-                        float s;
-                        add(xyz(ea.texels[env_texel(ea, d, s)]));
-                    } else add(v3(sc.sky[0], sc.sky[1], sc.sky[2]));
+                    add(gather_miss<ENV>(d));
                     term = true;
                 } else {                // ---- a hit: the surface and its emission (shade_one's lines)
                     const V3 P = madd(h.t, d, o);
@@ -1920,29 +1943,16 @@ k_gather_paths(GatherArgsT<ENV> args)
                     }
                 }
                 if (term) { // the lane's next sample, in place
-                    k += G;
+                    k += w.G;
                     alive = k < K;
                     if (alive) start(k);
                 } else {
-                    row(7u) = __float_as_uint(T.x); row(8u) = __float_as_uint(T.y); row(9u) = __float_as_uint(T.z);
-                    row(11u) = (k << 8) | depth;
+                    rows.row(kT) = __float_as_uint(T.x); rows.row(kT + 1u) = __float_as_uint(T.y); rows.row(kT + 2u) = __float_as_uint(T.z);
+                    rows.row(kSampleDepth) = (k << 8) | depth;
                 }
             }
         }
-        asm volatile("" ::: "memory");
-        float ex = sum_of(0u), ey = sum_of(1u), ez = sum_of(2u), bx = sum_of(3u), by = sum_of(4u), bz = sum_of(5u);
-        uint32_t cnt = row(6u);
-        for (uint32_t m = G >> 1; m; m >>= 1) { // the butterfly stays inside the group: m < G
-            cnt += (uint32_t)__shfl_xor((int)cnt, (int)m, 64);
-            ex = ex + __shfl_xor(ex, (int)m, 64); ey = ey + __shfl_xor(ey, (int)m, 64); ez = ez + __shfl_xor(ez, (int)m, 64);
-            bx = bx + __shfl_xor(bx, (int)m, 64); by = by + __shfl_xor(by, (int)m, 64); bz = bz + __shfl_xor(bz, (int)m, 64);
-        }
-        if (lane == 0u && i < n) {
-            const float fk = (float)K, big = 3.40282347e38f; // a sum that overflowed is stored as the largest finite float
-            auto mean = [&](float s) { return fmin_(fmax_(s / fk, -big), big); };
-            out[2u * (size_t)i] = valid ? make_float4(mean(ex), mean(ey), mean(ez), (float)cnt / fk) : make_float4(0.f, 0.f, 0.f, -1.0f);
-            out[2u * (size_t)i + 1u] = valid ? make_float4(bx / fk, by / fk, bz / fk, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
+        gather_finish(rows, w, i, n, K, valid, a.out);
     }
     if (wave_rays && lane_id() == 0u) atomicAdd(reinterpret_cast<unsigned long long *>(cold().ps.counters + kCntTris), wave_rays);
 }
@@ -2142,43 +2152,23 @@ uint32_t gather_blocks(uint32_t n, uint32_t samples)
     return std::max(1u, std::min(kTraceBlocks, (uint32_t)(((uint64_t)n + per_wave - 1u) / per_wave)));
 }
 
-// The argument block of k_gather and k_gather_paths; pp (k_gather_paths only): the path parameters, which travel in the block's FrameParams.
-static GatherArgsT<true> gather_args(const DeviceScene &sc, const PathState &ps, const float4 *points, float4 *out, uint32_t n, const GatherParams &gp,
-                                     const GatherPathParams *pp, const EnvArgs *env)
+hipError_t launch_gather(hipStream_t s, const DeviceScene &sc, const PathState &ps, const float4 *points, float4 *out, uint32_t n, const GatherParams &gp,
+                         const GatherPathParams *pp, const EnvArgs *env)
 {
-    GatherArgsT<true> t{};
-    GatherArgs &a = t.x;
+    GatherArgs a{};
     a.sc = sc; a.ps = ps; a.points = points; a.out = out; a.n = n;
     a.samples = gp.samples; a.gshift = gather_group_shift(gp.samples); a.seed = gp.seed;
     a.point_offset = gp.point_offset; a.sample_offset = gp.sample_offset; a.tmax = gp.tmax; a.ray_eps = gp.ray_eps;
-    if (pp) { a.fp.max_depth = pp->max_depth; a.fp.rr_start = pp->rr_start; a.fp.ray_eps = gp.ray_eps; }
-    if (env) t.env = *env;
-    return t;
-}
-
-hipError_t launch_gather(hipStream_t s, const DeviceScene &sc, const PathState &ps, const float4 *points, float4 *out, uint32_t n, const GatherParams &gp,
-                         const EnvArgs *env)
-{
-    const GatherArgsT<true> t = gather_args(sc, ps, points, out, n, gp, nullptr, env);
+    if (pp) { a.fp.max_depth = pp->max_depth; a.fp.rr_start = pp->rr_start; a.fp.ray_eps = gp.ray_eps; } // the path parameters travel in the block's FrameParams
     const dim3 grid(gather_blocks(n, gp.samples));
-    const bool known = with_layout(sc.bvh_width, [&](auto lc) {
+    // layout x ENV x paths
+    const bool known = with_layout(sc.bvh_width, [&](auto lc) { with_value<0, 1>(env != nullptr, [&](auto ec) { with_value<0, 1>(pp != nullptr, [&](auto pc) {
         constexpr int L = decltype(lc)::value;
-        if (env) hipLaunchKernelGGL((k_gather<L, true>), grid, dim3(kExtBlock), 0, s, t);
-        else hipLaunchKernelGGL((k_gather<L, false>), grid, dim3(kExtBlock), 0, s, GatherArgsT<false>{ t.x });
-    });
-    return known ? hipGetLastError() : hipErrorInvalidValue;
-}
-
-hipError_t launch_gather_paths(hipStream_t s, const DeviceScene &sc, const PathState &ps, const float4 *points, float4 *out, uint32_t n, const GatherParams &gp,
-                               const GatherPathParams &pp, const EnvArgs *env)
-{
-    const GatherArgsT<true> t = gather_args(sc, ps, points, out, n, gp, &pp, env);
-    const dim3 grid(gather_blocks(n, gp.samples));
-    const bool known = with_layout(sc.bvh_width, [&](auto lc) {
-        constexpr int L = decltype(lc)::value;
-        if (env) hipLaunchKernelGGL((k_gather_paths<L, true>), grid, dim3(kExtBlock), 0, s, t);
-        else hipLaunchKernelGGL((k_gather_paths<L, false>), grid, dim3(kExtBlock), 0, s, GatherArgsT<false>{ t.x });
-    });
+        constexpr bool E = decltype(ec)::value != 0;
+        GatherArgsT<E> t; t.x = a; if constexpr (E) t.env = *env;
+        if constexpr (decltype(pc)::value != 0) hipLaunchKernelGGL((k_gather_paths<L, E>), grid, dim3(kExtBlock), 0, s, t);
+        else hipLaunchKernelGGL((k_gather<L, E>), grid, dim3(kExtBlock), 0, s, t);
+    }); }); });
     return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 

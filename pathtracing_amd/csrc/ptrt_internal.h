@@ -220,19 +220,17 @@ hipError_t launch_trace(hipStream_t s, const DeviceScene &sc, const PathState &p
 // pt_gather (docs/SPEC.md §12): n <= 2^31 caller points (2 float4 rows each) -> 2 float4 rows each, a group of 2^gather_group_shift(samples)
 // lanes per point on a grid of gather_blocks(n, samples) workgroups of kExtBlock lanes. ps as for launch_trace; shard_cap * kShards must
 // cover the grid's lanes. The kernel adds the invalid points it met to the low word of kCntNodes. env (may be NULL): the scene's map.
+// pp (NULL for pt_gather): the call is pt_gather_paths (§12.1), the same points, grid and counters; every sample is a path of §5 of at most
+// max_depth (1..255) segments with Russian roulette from rr_start on. The kernel adds the segments it traced to the u64 at kCntTris.
 struct GatherParams {
     uint32_t samples, seed, point_offset, sample_offset; // samples in 1..4096
     float tmax, ray_eps;                                        // tmax: max_distance, +inf for "unbounded"
 };
+struct GatherPathParams { uint32_t max_depth, rr_start; };
 uint32_t gather_group_shift(uint32_t samples); // log2 of min(64, the power of two >= samples)
 uint32_t gather_blocks(uint32_t n, uint32_t samples);
 hipError_t launch_gather(hipStream_t s, const DeviceScene &sc, const PathState &ps, const float4 *points, float4 *out, uint32_t n, const GatherParams &gp,
-                         const EnvArgs *env);
-// pt_gather_paths (docs/SPEC.md §12.1): launch_gather's points, grid and counters; every sample is a path of §5 of at most max_depth (1..255)
-// segments with Russian roulette from rr_start on. The kernel adds the segments it traced to the u64 at kCntTris.
-struct GatherPathParams { uint32_t max_depth, rr_start; };
-hipError_t launch_gather_paths(hipStream_t s, const DeviceScene &sc, const PathState &ps, const float4 *points, float4 *out, uint32_t n, const GatherParams &gp,
-                               const GatherPathParams &pp, const EnvArgs *env);
+                         const GatherPathParams *pp, const EnvArgs *env);
 hipError_t launch_reduce_streams(hipStream_t s, const float4 *acc, float4 *tiles, uint32_t slots_per_stream, uint32_t streams);
 hipError_t launch_assemble(hipStream_t s, const float4 *gathered, uint32_t nranks, uint32_t slots_per_rank,
                            uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t n_tiles, float inv_spp,

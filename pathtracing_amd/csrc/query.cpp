@@ -139,9 +139,7 @@ static pt_status gather(pt_context *c, const pt_scene *s, const void *points, vo
     for (uint64_t first = 0; first < n_points; first += kTraceChunk) { // point_offset + first wraps like the key's own u32 arithmetic
         GatherParams kc = k; kc.point_offset = k.point_offset + (uint32_t)first;
         const uint32_t nc = (uint32_t)std::min(kTraceChunk, n_points - first);
-        const EnvArgs *e = s->env.present() ? &env : nullptr;
-        if (paths) HIP_TRY(c, launch_gather_paths(q, s->ds, ps, d_points + 2u * first, d_out + 2u * first, nc, kc, kp, e));
-        else HIP_TRY(c, launch_gather(q, s->ds, ps, d_points + 2u * first, d_out + 2u * first, nc, kc, e));
+        HIP_TRY(c, launch_gather(q, s->ds, ps, d_points + 2u * first, d_out + 2u * first, nc, kc, paths ? &kp : nullptr, s->env.present() ? &env : nullptr));
     }
     HIP_TRY(c, hipEventRecord(c->query.ev[1], q));
     if (host) HIP_TRY(c, hipMemcpyAsync(out_rows, d_out, n_points * 32u, hipMemcpyDeviceToHost, q));

@@ -12,47 +12,18 @@ import pytest
 
 import env_checker
 import gather_ref as G
+from gather_device import K, LBVH, SENTINEL, SKY, call, other_state_is_untouched, same
 
 pytestmark = pytest.mark.gpu
-
-K = G.K
-LBVH = 0x100
-SKY = np.array([1.0, 2.0, 3.0], np.float32)
 
 
 def bound(samples):
     return (samples + 2) * 2.0 ** -24
 
 
-def gather(P, r, rec, samples=K, host=True, n=None, **kw):
-    """pt_gather through the C ABI on (n, 8) records: (out (n, 8) float32, pt_stats). host=False: through device tensors."""
-    N = P.native
-    n = len(rec) if n is None else n
-    gp = N.pt_gather_params(samples=samples, seed=kw.get("seed", 0), sample_offset=kw.get("sample_offset", 0),
-                            point_offset=kw.get("point_offset", 0), max_distance=kw.get("max_distance", 0.0),
-                            ray_eps=kw.get("ray_eps", G.EPS), flags=N.PT_GATHER_HOST_MEMORY if host else 0)
-    st = N.pt_stats()
-    if host:
-        rec = np.ascontiguousarray(rec, np.float32)
-        out = np.full((n, 8), 7.0, np.float32)
-        rc = N.lib.pt_gather(r._ctx, r._scene, rec.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), n, C.byref(gp), C.byref(st))
-    else:
-        import torch
-        d_rec = torch.as_tensor(np.ascontiguousarray(rec, np.float32), device="cuda")
-        d_out = torch.full((n, 8), 7.0, dtype=torch.float32, device="cuda")
-        torch.cuda.synchronize()
-        rc = N.lib.pt_gather(r._ctx, r._scene, C.c_void_p(d_rec.data_ptr()), C.c_void_p(d_out.data_ptr()), n, C.byref(gp), C.byref(st))
-        out = d_out.cpu().numpy()
-    assert rc == N.PT_OK, (rc, N.lib.pt_last_error(r._ctx))
-    return out, st
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def same(a, b):
-    return a.shape == b.shape and np.array_equal(bits(a), bits(b))
+def gather(P, r, rec, **kw):
+    """pt_gather on (n, 8) records (gather_device.call): (out (n, 8) float32, pt_stats)."""
+    return call(P, r, rec, paths=False, **kw)
 
 
 def counts_of(out, samples):
@@ -73,8 +44,7 @@ def check(out, ref, samples, ctx):
           f"max |dbent| = {np.abs(out[valid, 4:7] - ref['bent'][valid]).max():.3e}, bound {b:.3e}")
     assert (errE <= b * ref["absE"][valid]).all(), ctx
     assert (np.abs(out[valid, 4:7].astype(np.float64) - ref["bent"][valid]) <= b).all(), ctx
-    sentinel = np.array([0, 0, 0, -1, 0, 0, 0, 0], np.float32)
-    assert (out[~valid] == sentinel).all(), ctx
+    assert (out[~valid] == SENTINEL).all(), ctx
 
 
 @pytest.fixture(scope="module")
@@ -244,13 +214,12 @@ def test_invalid_points(P, pto, renderer, glass):
     bad[5, 1] = np.nan
     bad[6, 4] = np.inf
     bad[41, 4:7] = 0.0
-    sentinel = np.array([0, 0, 0, -1, 0, 0, 0, 0], np.float32)
     for samples in (16, K):
         clean, st0 = gather(P, renderer, rec, samples=samples)
         out, st = gather(P, renderer, bad, samples=samples)
         ok = np.ones(70, bool)
         ok[[5, 6, 41]] = False
-        assert same(out[ok], clean[ok]) and (out[~ok] == sentinel).all() and np.isfinite(out).all()
+        assert same(out[ok], clean[ok]) and (out[~ok] == SENTINEL).all() and np.isfinite(out).all()
         assert st0.rays == 70 * samples and st.rays == 67 * samples and st.paths == 70
     # normals of any length are normalised; a subnormal-length normal whose dot underflows to 0 is invalid
     scaled = rec.copy()
@@ -261,38 +230,14 @@ def test_invalid_points(P, pto, renderer, glass):
     tiny = rec[:1].copy()
     tiny[0, 4:7] = (1e-30, 0.0, 0.0)
     out, st = gather(P, renderer, tiny)
-    assert (out[0] == sentinel).all() and st.rays == 0
+    assert (out[0] == SENTINEL).all() and st.rays == 0
 
 
 def test_other_state_is_untouched(P, pto, glass):
     """7. A PT_FLAG_ACCUMULATE sequence with a pt_gather in the middle is the sequence without it, and the displayed and denoised
-    images of the frame survive the call."""
-    N = P.native
+    images, the guides and the temporal history of the frame survive the call."""
     sd, pts, nrm, _ = glass
-    rec = G.records(pts, nrm)
-
-    def sequence(with_gather):
-        r = P.Renderer(P.Window(G.W, G.H))
-        r.Init()
-        try:
-            r.SetScene(sd, 0)
-            r.Params = P.make_params(G.W, G.H, spp=2, max_depth=4, streams=2)
-            r.Render(0.0)
-            r.Denoise()
-            r.Display()
-            dn, disp = r.ReadDenoised(), r.ReadDisplay()
-            if with_gather:
-                out, _ = gather(P, r, rec)
-                assert out[:, 3].min() >= 0
-                assert same(r.ReadDenoised(), dn) and np.array_equal(r.ReadDisplay(), disp)
-            r.Params = P.make_params(G.W, G.H, spp=2, max_depth=4, streams=2, sample_offset=2, flags=N.PT_FLAG_ACCUMULATE)
-            st = r.Render(0.0)
-            return r.ReadFramebuffer(), int(st.rays)
-        finally:
-            r.Dispose()
-
-    a, b = sequence(True), sequence(False)
-    assert same(a[0], b[0]) and a[1] == b[1]
+    other_state_is_untouched(P, sd, G.records(pts, nrm), paths=False)
 
 
 def test_refusals_that_need_a_context(P, pto, renderer, glass):
