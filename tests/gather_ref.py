@@ -119,10 +119,13 @@ def gather(r, max_distance=0.0, sky=None, env=None, L=None):
     return dict(count=count, visibility=vis, E=E, absE=absE, bent=bent, V=V)
 
 
-def first_hits(P, pto, sd, w=W, h=H):
+def first_hits(P, pto, sd, w=W, h=H, step=1):
     """(points, normals) f32 of the first hits of a w x h camera frame of `sd`, from the float64 caster: the hit point and the geometric
-    normal of the primitive, turned against the camera ray. Pixels that miss are left out."""
-    o, d = rc.camera_rays(pto, sd.cam, w, h)
+    normal of the primitive, turned against the camera ray. Pixels that miss are left out. step: the camera is that of a frame of
+    w * step x h * step pixels, of which every step-th of a row and of a column is taken (w x h points over the whole view)."""
+    o, d = rc.camera_rays(pto, sd.cam, w * step, h * step)
+    keep = (np.arange(h)[:, None] * step * (w * step) + np.arange(w)[None, :] * step).ravel()
+    o, d = o[keep], d[keep]
     ids, t, _, _ = rc.cast(sd.verts, sd.spheres, o, d)
     hit = ids != MISS
     o64, d64 = o.astype(np.float64)[hit], d.astype(np.float64)[hit]
@@ -135,6 +138,36 @@ def first_hits(P, pto, sd, w=W, h=H):
     n /= np.linalg.norm(n, axis=1, keepdims=True)
     n[(n * d64).sum(1) > 0] *= -1.0
     return p.astype(np.float32), n.astype(np.float32)
+
+
+def both_sides(points, normals):
+    """The points, then the same points with the normal negated: that hemisphere looks into the surface's far side and ray_eps puts
+    the origin behind the primitive, whose own back is then the first candidate."""
+    return np.concatenate([points, points]), np.concatenate([normals, -np.asarray(normals, np.float32)])
+
+
+def probe(cam, n=64, spread=0.25, seed=5):
+    """`n` points on and around a camera's origin (the first is the origin itself, the rest within `spread` of it along every axis)
+    with the camera's forward direction as normal: points that lie on no surface, for scenes whose first hits all look back at the
+    camera."""
+    rng = np.random.default_rng(seed)
+    o = np.array([cam.origin[i] for i in range(3)], np.float64)
+    pts = o + rng.uniform(-spread, spread, (n, 3))
+    pts[0] = o
+    return pts.astype(np.float32), np.tile(np.array([cam.forward[i] for i in range(3)], np.float32), (n, 1))
+
+
+def centroids(sd, every=16):
+    """(points, normals) f32 on every `every`-th triangle of the scene: its centroid and its unit geometric normal, from float64."""
+    v = np.asarray(sd.verts, np.float32).reshape(-1, 3, 3).astype(np.float64)[::every]
+    n = np.cross(v[:, 1] - v[:, 0], v[:, 2] - v[:, 0])
+    return v.mean(1).astype(np.float32), (n / np.linalg.norm(n, axis=1, keepdims=True)).astype(np.float32)
+
+
+def tiled(points, normals, n):
+    """The point set repeated cyclically up to `n` points (every index of a call has its own key: the records differ)."""
+    idx = np.arange(n) % len(points)
+    return np.ascontiguousarray(points[idx]), np.ascontiguousarray(normals[idx])
 
 
 def records(points, normals):
@@ -191,6 +224,48 @@ def half_box(sd):
     """About half the scene's largest extent: the tests' finite max_distance."""
     v = np.asarray(sd.verts, np.float32).reshape(-1, 3)
     return float(np.float32(0.5 * (v.max(0) - v.min(0)).max()))
+
+
+_SPACE = {}
+
+
+def space_case(P, pto, name):
+    """(scene, points, normals, ray_eps) of a scene of trace_support.scenes or a case of geometry_space (both have cameras of 48 x 36
+    frames), made once per process and never written to. `layers`: the probe set on the camera origin (the first hits of the stacked
+    layers all lie on the nearest one and look back at the camera). The other scenes of trace_support: the first hits of 24 x 18 pixels
+    over the whole view, from both sides; the camera of `soup` sees few triangles between the gaps (4 of 432 pixels hit one), so its set
+    goes on with the centroid of every 16th triangle, from both sides. A geometry_space case: those first hits, and the case's own
+    ray_eps."""
+    if name not in _SPACE:
+        import geometry_space
+        import trace_support
+        if name == "layers":
+            sd = trace_support.scenes(P)[name]
+            _SPACE[name] = (sd,) + probe(sd.cam) + (EPS,)
+        elif name in ("duplicates", "soup", "spheres64", "glass", "tess", "cornell"):
+            sd = trace_support.scenes(P)[name]
+            pts, nrm = first_hits(P, pto, sd, step=2)
+            if name == "soup":
+                more = centroids(sd)
+                pts, nrm = np.concatenate([pts, more[0]]), np.concatenate([nrm, more[1]])
+            _SPACE[name] = (sd,) + both_sides(pts, nrm) + (EPS,)
+        else:
+            c = geometry_space.cases()[name]
+            _SPACE[name] = (c.sd,) + first_hits(P, pto, c.sd, step=2) + (float(np.float32(c.ray_eps)),)
+    return _SPACE[name]
+
+
+def tight_eps(sd):
+    """32 ulps of the scene's largest |coordinate|: a ray_eps that keeps the origins next to their surfaces at large offsets, where a
+    geometry_space case's own (1e-4 of the offset) carries them out of a box two units across."""
+    v = np.asarray(sd.verts, np.float32)
+    return float(32 * np.spacing(np.abs(v).max()))
+
+
+def spread(points, normals, n=64):
+    """`n` of the points, evenly spread over the set (the Python ray loop of `rays` is slow)."""
+    idx = np.unique(np.linspace(0, len(points) - 1, n).astype(np.int64))
+    return points[idx], normals[idx]
 
 
 def case(P, pto, name, samples=K):

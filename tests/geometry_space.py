@@ -22,7 +22,7 @@ from ±30 outwards:
             the range). HIT_K = 40 is what the cases use: a margin of one step above, four below.
   spheres   see ray_caster64.K_S.
 """
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 
 import numpy as np
 
@@ -170,6 +170,20 @@ def needle_placement(sd, thickness=1e-4, n=400, seed=24):
     v = sd.verts.reshape(-1, 9).copy()
     v[rng.choice(len(v), n, replace=False)] = needle_triangles(thickness, n)
     return v
+
+
+def refit_cases():
+    """(the tessellated box, pseudo cases of it moved) for a refit: the box carried to the translate and corridor placements and with
+    400 of its triangles drawn out into needles. Vertex count and spheres' count stay the committed ones (the corridor keeps the box's
+    spheres where they are)."""
+    base = tess()
+    out = []
+    for name in ("translate_tess_0", "translate_tess_1", "translate_tess_2", "translate_tess_3", "corridor_x4096", "corridor_x2^-12"):
+        c = cases()[name]
+        sd = replace(c.sd, spheres=c.sd.spheres if len(c.sd.spheres) else base.spheres, sph_mat=base.sph_mat)
+        out.append(Case("refit_" + name, c.family, sd, c.M))
+    out.append(Case("refit_needles", "needles", replace(base, verts=needle_placement(base)), 1.0))
+    return base, out
 
 
 def degenerate():
@@ -340,6 +354,12 @@ CASE_NAMES = [c for fam in ("translate_glass", "translate_tess") for c in (f"{fa
      "degenerate", "corridor_x4096", "corridor_x2^-12", "flat_grid", "flat_line", "mixed_2^-12"] + \
     [f"far_camera_{d}_{k}" for d in CAMERA_DISTANCES for k in ("spheres", "triangles")] + \
     [f"far_sphere{t}_{n}" for t in ("", "_oblique") for n in SPHERE_RADII]
+
+# the cases whose rays are made on surfaces: the full path trace of tests/test_gpu_geometry_space.py and the gathers of
+# tests/test_gpu_gather_space.py
+PATH_TRACE = ["translate_glass_0", "translate_tess_0", "translate_glass_2", "translate_tess_2", "needles_0.0001", "degenerate",
+              "corridor_x4096", "corridor_x2^-12", "flat_grid", "flat_line", "scale_glass_-40", "scale_glass_+40", "scale_tess_-40",
+              "scale_tess_+40"]
 
 
 def counts(c):

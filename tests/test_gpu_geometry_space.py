@@ -5,8 +5,6 @@ What the device could get wrong here where the scenes around the origin could no
 large offsets and flat or stretched bounds (lbvh.hip), the quantiser's grid regrowing in a refit (refit.hip), octant ordering of
 layout 73 on flat axes, safe_inv with zero direction components at large |o|, the overflow stack on needle trees, and denormal
 products at 2^-40 in the triangle test (the kernels are built not to flush them)."""
-import dataclasses
-
 import numpy as np
 import pytest
 
@@ -14,16 +12,13 @@ import adversarial_scenes as S
 import geometry_space as G
 import ray_caster64 as rc
 from frame_checks import _config_grid, run_both
-from geometry_space import CASE_NAMES, case_ray_sets, cases, check_case
+from geometry_space import CASE_NAMES, PATH_TRACE, case_ray_sets, cases, check_case
 from trace_support import LAYOUTS, MISS, check_closest, commit, ids_of, oracle, records, same
 
 pytestmark = pytest.mark.gpu
 
 OUT_OF_DOMAIN = ["scale_glass_-50", "scale_glass_+44", "scale_tess_-50", "scale_tess_+44"]
 ID_IMAGE = [n for n in CASE_NAMES if n.split("_")[0] in ("translate", "scale") or n.startswith("far_camera")]
-PATH_TRACE = ["translate_glass_0", "translate_tess_0", "translate_glass_2", "translate_tess_2", "needles_0.0001", "degenerate",
-              "corridor_x4096", "corridor_x2^-12", "flat_grid", "flat_line", "scale_glass_-40", "scale_glass_+40", "scale_tess_-40",
-              "scale_tess_+40"]
 
 
 def trace_and_check(pto, renderer, osc, case, sets, ctx, seen):
@@ -91,16 +86,8 @@ def test_full_path_trace(P, pto, renderer, name):
 
 
 def _placements(pto):
-    """(name, pseudo case of the moved scene, its camera rays) for the refit: the tessellated box carried to the translate and
-    corridor placements and with 400 of its triangles drawn out into needles. Vertex count and spheres' count stay the committed ones
-    (the corridor keeps the box's spheres where they are)."""
-    base = G.tess()
-    out = []
-    for name in ("translate_tess_0", "translate_tess_1", "translate_tess_2", "translate_tess_3", "corridor_x4096", "corridor_x2^-12"):
-        c = cases()[name]
-        sd = dataclasses.replace(c.sd, spheres=c.sd.spheres if len(c.sd.spheres) else base.spheres, sph_mat=base.sph_mat)
-        out.append(G.Case("refit_" + name, c.family, sd, c.M))
-    out.append(G.Case("refit_needles", "needles", dataclasses.replace(base, verts=G.needle_placement(base)), 1.0))
+    """(the committed box, [(pseudo case of the moved scene, its camera rays)]) for the refit: geometry_space.refit_cases."""
+    base, out = G.refit_cases()
     return base, [(c, G.case_rays(pto, c)) for c in out]
 
 

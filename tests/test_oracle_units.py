@@ -14,8 +14,69 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 F3 = C.c_float * 3
 
 
+def _pcg(x):
+    """SPEC §2 in Python integers: every product and sum is reduced mod 2^32 where u32 arithmetic wraps."""
+    m = 0xFFFFFFFF
+    s = (x * 747796405 + 2891336453) & m
+    w = (((s >> ((s >> 28) + 4)) ^ s) * 277803737) & m
+    return (w >> 22) ^ w
+
+
+def _pcg_inverse(y):
+    """The x with pcg(x) == y: pcg is a bijection of u32 (an odd multiplier and an xorshift by at least 4 each way)."""
+    m = 0xFFFFFFFF
+    w = y ^ (y >> 22)                                   # the shift is more than half the word: one step undoes it
+    v = (w * pow(277803737, -1, 1 << 32)) & m
+    r = (v >> 28) + 4                                   # the top four bits of s pass through s ^ (s >> r) unchanged
+    s = v
+    for _ in range(8):                                  # each step settles r more bits from the top
+        s = v ^ (s >> r)
+    return ((s - 2891336453) * pow(747796405, -1, 1 << 32)) & m
+
+
+def _path_key(seed, pixel, sample):
+    return _pcg((_pcg((_pcg(seed) + pixel) & 0xFFFFFFFF) + sample) & 0xFFFFFFFF)
+
+
+def _rnd(key, dim):
+    return _pcg((key + dim * 0x9E3779B9) & 0xFFFFFFFF)
+
+
+def _u01(key, dim):
+    return np.float32(_rnd(key, dim) >> 8) * np.float32(2.0 ** -24)  # a 24-bit integer and its product with 2^-24 are exact in f32
+
+
 def test_rng_stream(pto):
-    assert pto.lib.pto_pcg(0) == 129708002 or True  # value pinned below via determinism of the whole chain
+    """pto_pcg, pto_path_key and pto_u01 against SPEC §2 restated in Python integers, on the edges of u32: seed, pixel and sample of 0,
+    1, 2^31 and 2^32 - 1 (the sums pcg(..) + pixel and .. + sample wrap), every dimension a path of 255 segments and a lens draw, and a
+    few beyond (dim * 0x9E3779B9 wraps from dim = 2 on); u01 stays below 1 at the largest rnd."""
+    edge = (0, 1, 1 << 31, 0xFFFFFFFF)
+    for x in edge + (2, 0x7FFFFFFF, 0x80000001, 0x5EED0001, 129708002):
+        assert pto.lib.pto_pcg(x) == _pcg(x), x
+    keys = set()
+    for seed in edge:
+        for pixel in edge:
+            for sample in edge:
+                k = _path_key(seed, pixel, sample)
+                assert pto.lib.pto_path_key(seed, pixel, sample) == k, (seed, pixel, sample)
+                keys.add(k)
+    assert len(keys) == 64  # pcg is a bijection of u32 and every stage adds its argument: distinct triples, distinct keys
+    # the sums wrap: a pixel of 2^32 - 1 is a pixel of -1
+    assert _path_key(5, 0xFFFFFFFF, 7) == _pcg((_pcg((_pcg(5) - 1) & 0xFFFFFFFF) + 7) & 0xFFFFFFFF)
+    dims = list(range(1026 + 3 * 254 + 1)) + [1 << 16, (1 << 31) - 1, 1 << 31, 0xFFFFFFFE, 0xFFFFFFFF]
+    for key in (0, 1, 0xFFFFFFFF, _path_key(0x5EED0001, 12345, 7)):
+        for dim in dims:
+            got = np.float32(pto.lib.pto_u01(key, dim))
+            assert got == _u01(key, dim) and 0.0 <= got < 1.0, (key, dim, got)
+    # the largest rnd: 2^32 - 1 >> 8 = 2^24 - 1, times 2^-24, is the largest float below 1
+    top = np.float32(0xFFFFFFFF >> 8) * np.float32(2.0 ** -24)
+    assert top == np.float32(1.0) - np.float32(2.0 ** -24) and top < 1.0 and np.nextafter(top, np.float32(2.0)) == np.float32(1.0)
+    for r in (0xFFFFFFFF, 0xFFFFFF00, 0xFFFFFEFF, 0):  # keys whose dimension 0, and whose dimension 3, draw exactly r
+        x = _pcg_inverse(r)
+        assert _pcg(x) == r and pto.lib.pto_pcg(x) == r
+        want = top if r >= 0xFFFFFF00 else np.float32(r >> 8) * np.float32(2.0 ** -24)
+        assert np.float32(pto.lib.pto_u01(x, 0)) == want < 1.0, r
+        assert np.float32(pto.lib.pto_u01((x - 3 * 0x9E3779B9) & 0xFFFFFFFF, 3)) == want, r
     k = pto.lib.pto_path_key(0x5EED0001, 12345, 7)
     assert k == pto.lib.pto_path_key(0x5EED0001, 12345, 7)
     assert k != pto.lib.pto_path_key(0x5EED0001, 12346, 7) and k != pto.lib.pto_path_key(0x5EED0001, 12345, 8)
