@@ -238,7 +238,14 @@ pt_status pt_scene_environment_read(const pt_scene *s, float *texels4, float *mc
  * pinhole ray of the same sample reaches at origin + focus_distance * (forward + sx * right + sy * up): what lies there is sharp, everything
  * else is blurred by a disc that grows with the aperture. radius == 0 is no lens: every frame is then bit for bit the pinhole frame. The
  * two random numbers of the disc are RNG dimensions 2 and 3, which nothing else draws, so every other random number of a path is the
- * pinhole frame's; rays and paths are counted as before. */
+ * pinhole frame's; rays and paths are counted as before.
+ * Domain (docs/SPEC.md §3.1 has the rule): the ray's direction is normalize(focus_distance * v - a), a on the aperture, whose squared length
+ * must be a normal, finite f32. pt_render of a frame with radius > 0 is PT_ERR_INVALID_ARGUMENT — before it replaces anything: the previous
+ * frame, its sums and what was made from them stay — unless, for the frame's camera and image size, right and up span a plane
+ * (|cross(right, up)| > 2^-6 |right| |up|), hi = focus_distance * max|v| + radius * sqrt(1 + |cos(right, up)|) has hi^2 <= 2^127 (max |v|
+ * over the image's corners), and focus_distance * (the part of forward off that plane - 2^-11 S) >= 2^-60, S being the sum of the sizes of
+ * the terms v is made from (|forward| + max|sx| |right| + max|sy| |up|, as §3.1 pads them). pt_scene_set_lens itself does
+ * not apply the rule: the camera may change later. */
 typedef struct pt_lens {
     float radius;          /* aperture radius in world units; finite, >= 0; 0 = pinhole */
     float focus_distance;  /* F, in units of |forward| along the view axis; finite, > 0 */

@@ -164,6 +164,45 @@ bool lens_basis(const pt_camera &cam, const pt_lens &lens, LensArgs &out)
     return true;
 }
 
+// The lens domain (docs/SPEC.md §3.1 "Domain"): whether normalize's dot(w, w) of w = F v - a is a normal, finite f32 for every pixel,
+// jitter and point on the lens of a W x H frame. In double, from the camera's f32 words:
+//   n    = cross(right, up): the normal of the plane that holds a and the sx, sy terms of v; refused unless |n| > 2^-6 |right| |up|
+//   vmax = max over the image's corners (x = 0 or W, y = 0 or H) of |v|, each sx and sy moved outwards by 2^-22 (W |scale| + |cx|), the
+//          f32 roundings of §3's sx (|v| is convex in (sx, sy), so its largest value over the image is at a corner)
+//   hi   = F vmax + R sqrt(1 + |dot(right, up)| / (|right| |up|))       >= |w|: |a|^2 <= R^2 (lx^2 + ly^2) (1 + |cos|)
+//   S    = |forward| + (max |sx| + |cx| + W |scale|) |right| + (max |sy| + |cy| + H |scale|) |up|: the size of the terms v is summed from
+//   lo   = F (|dot(forward, n)| / |n| - 2^-11 S)                        <= |w|, see below
+//   accepted iff lo >= 2^-60 and hi^2 <= 2^127.
+// Only forward leaves the plane, so the exact |w| is at least F |dot(forward, n)| / |n|; the f32 w is off by at most 4 u F S (v, u = 2^-24)
+// plus 25 u r R (a, for a lens point at radius r) plus u |w|. With |a| >= k r R, k = sqrt(1 - |cos|) >= 2^-6.5: either k r R <= 2 F S,
+// and the error is at most (4 + 50 / k) u F S < 2^-11 F S; or |a| > 2 F S >= 2 F |v|, and |w| >= |a| / 2 - error > F S (1 - 2^-10).
+// dot(w, w) then lies in [2^-120, 2^127] up to its own roundings: a factor 2 below the overflow, 2^6 above the subnormals, where a
+// product that underflows loses less than 2^-30 of the sum. Anything not finite fails a comparison and is refused.
+bool lens_in_domain(const pt_camera &cam, const pt_lens &lens, uint32_t W, uint32_t H)
+{
+    const double r[3] = { cam.right[0], cam.right[1], cam.right[2] }, u[3] = { cam.up[0], cam.up[1], cam.up[2] }, f[3] = { cam.forward[0], cam.forward[1], cam.forward[2] };
+    auto dot = [](const double *a, const double *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; };
+    const double n[3] = { r[1] * u[2] - r[2] * u[1], r[2] * u[0] - r[0] * u[2], r[0] * u[1] - r[1] * u[0] };
+    const double nn = std::sqrt(dot(n, n)), lr = std::sqrt(dot(r, r)), lu = std::sqrt(dot(u, u)), F = lens.focus_distance, R = lens.radius;
+    if (!(nn > 0x1p-6 * lr * lu)) return false;
+    const double scale = cam.scale, cx = cam.cx, cy = cam.cy, tw = (double)W * std::fabs(scale) + std::fabs(cx), th = (double)H * std::fabs(scale) + std::fabs(cy);
+    const double ax = -cx, bx = (double)W * scale - cx, ay = -cy, by = (double)H * scale - cy;
+    const double sxs[2] = { std::min(ax, bx) - std::ldexp(tw, -22), std::max(ax, bx) + std::ldexp(tw, -22) };
+    const double sys[2] = { std::min(ay, by) - std::ldexp(th, -22), std::max(ay, by) + std::ldexp(th, -22) };
+    double vmax = 0.0;
+    for (int i = 0; i < 4; ++i) {
+        const double sx = sxs[i & 1], sy = sys[i >> 1];
+        const double v[3] = { f[0] + sx * r[0] + sy * u[0], f[1] + sx * r[1] + sy * u[1], f[2] + sx * r[2] + sy * u[2] };
+        const double len = std::sqrt(dot(v, v));
+        if (!std::isfinite(len)) return false;
+        vmax = std::max(vmax, len);
+    }
+    const double hi = F * vmax + R * std::sqrt(1.0 + std::fabs(dot(r, u)) / (lr * lu));
+    const double S = std::sqrt(dot(f, f)) + (std::max(std::fabs(ax), std::fabs(bx)) + tw) * lr + (std::max(std::fabs(ay), std::fabs(by)) + th) * lu;
+    const double lo = F * (std::fabs(dot(f, n)) / nn - std::ldexp(S, -11));
+    return lo >= 0x1p-60 && hi * hi <= 0x1p127;
+}
+
 struct Frame {                  // a path-traced frame as plan_frame lays it out, and what its loops leave for finish_frame
     uint32_t nranks, streams, pixel_slots, n_slots, shard_cap, samples_per_stream, lag, n_loops, packed_chunk, default_bounces;
     Pipeline pipe;              // what the frame's flags, pt_tuning.extend_kernel and the scene decode to (pipeline.h)
@@ -481,6 +520,12 @@ static pt_status render_frame(pt_context *c, const pt_scene *s, const pt_render_
 
 extern "C" pt_status pt_render(pt_context *c, const pt_scene *s, const pt_render_params *p, pt_stats *stats)
 {
+    // A lens outside its domain (lens_in_domain) is refused here, before the call begins to replace the frame: the framebuffer, the sums of
+    // a PT_FLAG_ACCUMULATE sequence, the denoised, temporal and displayed results and the history all stay. Every other refusal is render_frame's.
+    if (c && s && p && p->mode == PT_PATH_TRACE && s->ctx == c && s->committed && s->lens.radius > 0.f && !lens_in_domain(s->ds.cam, s->lens, p->width, p->height))
+        return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_render through a lens: the lens (radius %g, focus_distance %g) is outside its domain for this camera and a %u x %u image "
+                    "(docs/SPEC.md 3.1: focus_distance * |v| + radius too large, focus_distance * forward's part off the plane of right and up too small, or no such plane)",
+                    (double)s->lens.radius, (double)s->lens.focus_distance, p->width, p->height);
     const pt_status st = drained_on_failure(c, [&] { return render_frame(c, s, p, stats); });
     if (st != PT_OK && c) { c->sums.begin(); c->out.lost(); } // nothing of this frame survives the call
     return st;

@@ -21,13 +21,30 @@ class lr_stats(C.Structure):
 _f3 = C.c_float * 3
 SYMBOLS = {
     "lr_lens_basis": (C.c_int, [C.c_void_p, C.c_float, _f3, _f3]),
-    "lr_camera_ray": (C.c_int, [C.c_void_p, C.POINTER(lr_lens), C.c_uint32, C.c_uint32, C.c_uint32, _f3, _f3]),
+    "lr_sincos2pi_error": (C.c_double, [C.c_uint32, C.c_uint32, C.c_uint32]),
+    "lr_lens_domain": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_uint32, C.c_uint32]),
+    "lr_camera_ray": (C.c_int, [C.c_void_p, C.POINTER(lr_lens), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _f3, _f3]),
     "lr_render": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(lr_lens), C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(lr_stats)]),
 }
 
 
+class Refused(RuntimeError):
+    """The checker refuses the frame or ray as pt_render would: `code` is lr_render's or lr_camera_ray's (-1, -3: a degenerate basis;
+    -2, -4: a lens outside §3.1's domain)."""
+
+    def __init__(self, what, code):
+        super().__init__(f"{what} refused: {code}")
+        self.code = code
+
+
 def build():
     return ref_lib.load("lens_ref", "liblens_ref.so", SYMBOLS)
+
+
+def in_domain(pto, cam, lens, w, h):
+    """Whether a w x h frame of `cam` through lens = (radius, focus_distance) is inside §3.1's domain."""
+    c = _cam(pto, cam)
+    return build().lr_lens_domain(C.addressof(c), lens[0], lens[1], w, h) == 0
 
 
 def _cam(pto, cam):
@@ -44,10 +61,14 @@ def lens_basis(pto, cam, radius):
     return np.array(u[:], np.float32), np.array(v[:], np.float32)
 
 
-def camera_ray(pto, cam, lens, x, y, key):
-    """(origin, direction) float32 of the lens ray of pixel (x, y) with `key`; lens = (radius, focus_distance)."""
+def camera_ray(pto, cam, lens, x, y, key, size=None):
+    """(origin, direction) float32 of the lens ray of pixel (x, y) with `key`; lens = (radius, focus_distance). size = (w, h): the
+    frame §3.1's domain is asked for, Refused outside it; None: the caller's frame was accepted already."""
     c, o, d = _cam(pto, cam), _f3(), _f3()
-    rc = build().lr_camera_ray(C.addressof(c), C.byref(lr_lens(*lens)), x, y, key, o, d)
+    w, h = size if size is not None else (0, 0)
+    rc = build().lr_camera_ray(C.addressof(c), C.byref(lr_lens(*lens)), w, h, x, y, key, o, d)
+    if rc == -2:
+        raise Refused("lr_camera_ray", rc)
     assert rc == 0, rc
     return np.array(o[:], np.float32), np.array(d[:], np.float32)
 
@@ -63,6 +84,8 @@ def render(pto, scene, params, lens=None, flags=0, with_sq=False, threads=0):
     st = lr_stats()
     rc = lib.lr_render(C.addressof(scene.c), C.addressof(p), None if lens is None else C.byref(lr_lens(*lens)), flags, threads,
                        out.ctypes.data, None if sq is None else sq.ctypes.data, C.byref(st))
+    if rc in (-3, -4):
+        raise Refused("lr_render", rc)
     if rc != 0:
         raise RuntimeError(f"lr_render failed: {rc}")
     return out, st, sq

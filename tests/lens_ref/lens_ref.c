@@ -7,6 +7,7 @@
  * lr_render() with lens == NULL or radius 0 takes the oracle's pinhole ray: with flags = 0 it must equal pto_render, with LR_NEE
  * nr_render, bit for bit. It reports extension and shadow rays separately and, optionally, per-pixel sums of squared per-sample radiance.
  * LR_FOCUS_IGNORED, LR_LINEAR_RADIUS and LR_FIXED_ORIGIN are deliberate errors for the tests' negative controls.
+ * A lens outside §3.1's domain (lr_lens_domain) is refused by lr_render and lr_camera_ray, as pt_render refuses it.
  */
 #include <math.h>
 #include <stdint.h>
@@ -48,6 +49,51 @@ int lr_lens_basis(const pto_camera *c, float R, float lens_u[3], float lens_v[3]
     return 0;
 }
 
+/* The largest |pto_sincos2pi(u) - (sin, cos)(2 pi u)| in double (libm) over u = i * 2^-24, i = first, first + step, ... < end: what
+ * tests/lens64.py's bound takes for the one function of §3.1 whose error §0 does not state. */
+double lr_sincos2pi_error(uint32_t first, uint32_t end, uint32_t step)
+{
+    double worst = 0.0;
+    for (uint64_t i = first; i < end; i += step ? step : 1u) {
+        const float u = (float)i * 5.9604644775390625e-8f;
+        float sn, cs;
+        pto_sincos2pi(u, &sn, &cs);
+        const double ang = 6.283185307179586476925286766559 * (double)u;
+        worst = fmax(worst, fmax(fabs((double)sn - sin(ang)), fabs((double)cs - cos(ang))));
+    }
+    return worst;
+}
+
+/* §3.1 "Domain", from the section's text: 0 if a w x h frame of camera c through (R, F) is inside it, else -1. */
+int lr_lens_domain(const pto_camera *c, float R, float F, uint32_t w, uint32_t h)
+{
+    double r[3], u[3], f[3], n[3], rr = 0.0, uu = 0.0, ru = 0.0, nn = 0.0, fn = 0.0;
+    for (int k = 0; k < 3; ++k) { r[k] = c->right[k]; u[k] = c->up[k]; f[k] = c->forward[k]; }
+    for (int k = 0; k < 3; ++k) {
+        n[k] = r[(k + 1) % 3] * u[(k + 2) % 3] - r[(k + 2) % 3] * u[(k + 1) % 3];
+        rr += r[k] * r[k]; uu += u[k] * u[k]; ru += r[k] * u[k];
+    }
+    for (int k = 0; k < 3; ++k) { nn += n[k] * n[k]; fn += f[k] * n[k]; }
+    nn = sqrt(nn); rr = sqrt(rr); uu = sqrt(uu);
+    if (!(nn > ldexp(rr * uu, -6))) return -1;
+    const double sc = c->scale, cx = c->cx, cy = c->cy, tw = w * fabs(sc) + fabs(cx), th = h * fabs(sc) + fabs(cy);
+    const double x0 = fmin(-cx, w * sc - cx) - ldexp(tw, -22), x1 = fmax(-cx, w * sc - cx) + ldexp(tw, -22);
+    const double y0 = fmin(-cy, h * sc - cy) - ldexp(th, -22), y1 = fmax(-cy, h * sc - cy) + ldexp(th, -22);
+    double vmax = 0.0, ff = 0.0;
+    for (int i = 0; i < 4; ++i) {
+        const double sx = (i & 1) ? x1 : x0, sy = (i & 2) ? y1 : y0;
+        double l2 = 0.0;
+        for (int k = 0; k < 3; ++k) { const double v = f[k] + sx * r[k] + sy * u[k]; l2 += v * v; }
+        if (!isfinite(l2)) return -1;
+        vmax = fmax(vmax, sqrt(l2));
+    }
+    for (int k = 0; k < 3; ++k) ff += f[k] * f[k];
+    const double hi = (double)F * vmax + (double)R * sqrt(1.0 + fabs(ru) / (rr * uu));
+    const double S = sqrt(ff) + (fmax(fabs(cx), fabs(w * sc - cx)) + tw) * rr + (fmax(fabs(cy), fabs(h * sc - cy)) + th) * uu;
+    const double lo = (double)F * (fabs(fn) / nn - ldexp(S, -11));
+    return (lo >= ldexp(1.0, -60) && hi * hi <= ldexp(1.0, 127)) ? 0 : -1;
+}
+
 /* §3.1: the camera ray of pixel (x, y) with `key` through the lens (lu, lv, F) */
 static void lens_ray(const pto_camera *c, const float lu[3], const float lv[3], float F, uint32_t flags, uint32_t x, uint32_t y, uint32_t key,
                      float o[3], float d[3])
@@ -70,10 +116,12 @@ static void lens_ray(const pto_camera *c, const float lu[3], const float lv[3], 
     d[0] = n.x; d[1] = n.y; d[2] = n.z;
 }
 
-/* 0, or -1 for a degenerate basis (lr_lens_basis) */
-int lr_camera_ray(const pto_camera *c, const lr_lens *lens, uint32_t x, uint32_t y, uint32_t key, float o[3], float d[3])
+/* 0, -1 for a degenerate basis (lr_lens_basis), or -2 for a lens outside §3.1's domain in a w x h frame (w == 0: the caller's frame was
+ * accepted already, the rule is not asked) */
+int lr_camera_ray(const pto_camera *c, const lr_lens *lens, uint32_t w, uint32_t h, uint32_t x, uint32_t y, uint32_t key, float o[3], float d[3])
 {
     float lu[3], lv[3];
+    if (w != 0u && lr_lens_domain(c, lens->radius, lens->focus_distance, w, h) != 0) return -2;
     if (lr_lens_basis(c, lens->radius, lu, lv) != 0) return -1;
     lens_ray(c, lu, lv, lens->focus_distance, 0u, x, y, key, o, d);
     return 0;
@@ -251,13 +299,15 @@ static void trace_pixel(const pto_scene *s, const pto_params *p, const lens_t *l
 }
 
 /* lens (may be NULL; radius 0 = none): the scene's lens. rgba: H*W*4 floats; sq (may be NULL): H*W*3 doubles, per pixel and channel the
- * sum over samples of the squared sample radiance. -3: a degenerate basis (lr_lens_basis). */
+ * sum over samples of the squared sample radiance. -3: a degenerate basis (lr_lens_basis); -4: a lens outside §3.1's domain, checked first
+ * as pt_render does. */
 int lr_render(const pto_scene *s, const pto_params *p, const lr_lens *lens, uint32_t flags, int threads, float *rgba, double *sq, lr_stats *st)
 {
     if (!s || !p || !rgba || !st || p->spp == 0 || p->streams > MAX_STREAMS) return -1;
     lens_t ln;
     memset(&ln, 0, sizeof ln);
     if (lens && lens->radius > 0.0f) {
+        if (lr_lens_domain(&s->cam, lens->radius, lens->focus_distance, p->width, p->height) != 0) return -4;
         if (lr_lens_basis(&s->cam, lens->radius, ln.lu, ln.lv) != 0) return -3;
         ln.on = 1; ln.F = lens->focus_distance;
     }

@@ -105,13 +105,18 @@ def _meets_in_plane(o, d, v0, e1, e2):
     return meets
 
 
-def cast(verts, spheres, o, d):
+def _rays(a, rays64):
+    """Ray origins or directions as float64: through float32, as the product and the oracle see them, unless rays64 says that they are
+    a float64 reference's own (tests/lens64.py), to be cast as they are."""
+    return np.asarray(a, np.float64) if rays64 else np.asarray(a, np.float32).astype(np.float64)
+
+
+def cast(verts, spheres, o, d, rays64=False):
     """Closest hit of every ray: (prim id or MISS as uint64, t float64, edge distance of the hit float64, in_plane bool).
     `in_plane`: the ray lies in the plane of a triangle it touches (det == 0, the origin in the plane, and the ray meets the
     triangle within that plane), where Möller–Trumbore has no answer; such rays are left out of every comparison. A ray that
     is merely coplanar with a triangle it never reaches is compared as usual."""
-    o = np.asarray(o, np.float32).astype(np.float64)
-    d = np.asarray(d, np.float32).astype(np.float64)
+    o, d = _rays(o, rays64), _rays(d, rays64)
     R = len(o)
     best_t = np.full(R, np.inf)
     best_id = np.full(R, MISS, np.uint64)
@@ -155,10 +160,9 @@ def cast(verts, spheres, o, d):
     return best_id, best_t, best_edge, in_plane
 
 
-def candidate(verts, spheres, o, d, ids):
+def candidate(verts, spheres, o, d, ids, rays64=False):
     """float64 t (NaN for a miss or a non-intersection) and edge distance of primitive ids[i] along ray i."""
-    o = np.asarray(o, np.float32).astype(np.float64)
-    d = np.asarray(d, np.float32).astype(np.float64)
+    o, d = _rays(o, rays64), _rays(d, rays64)
     ids = np.asarray(ids, np.uint64)
     t = np.full(len(o), np.nan)
     edge = np.full(len(o), np.nan)
@@ -180,9 +184,9 @@ def candidate(verts, spheres, o, d, ids):
     return t, edge
 
 
-def sphere_distance2(verts, spheres, o, ids):
+def sphere_distance2(verts, spheres, o, ids, rays64=False):
     """(|oc|/r)² of ray i's origin to sphere ids[i], in float64; NaN where ids[i] is not a sphere."""
-    o = np.asarray(o, np.float32).astype(np.float64)
+    o = _rays(o, rays64)
     ids = np.asarray(ids, np.uint64)
     NT = len(np.asarray(verts).reshape(-1, 9))
     sph = np.asarray(spheres, np.float32).reshape(-1, 4).astype(np.float64)
@@ -195,7 +199,8 @@ def sphere_distance2(verts, spheres, o, ids):
     return out
 
 
-def classify(verts, spheres, o, d, got, cast_result=None, edge_band=EDGE_BAND, t_band=T_BAND, sphere_band=False, t_floor=None):
+def classify(verts, spheres, o, d, got, cast_result=None, edge_band=EDGE_BAND, t_band=T_BAND, sphere_band=False, t_floor=None,
+             rays64=False):
     """Compare the primitive ids `got` (uint, MISS for none) of an f32 implementation with the caster, ray by ray.
     Returns a dict of index arrays: agree, edge (near an edge of either candidate), crack (the edge rays where `got` misses),
     coincident (the two candidates' t agree to t_band), in_plane (left out), wrong (everything else). `cast_result`: what
@@ -207,10 +212,10 @@ def classify(verts, spheres, o, d, got, cast_result=None, edge_band=EDGE_BAND, t
     once, at a t of rounding size, is not for float64 to say. A disagreement goes to the class `origin` (always empty without t_floor)
     only if it is exactly that: either `got` is a triangle S with |t64| <= t_floor and the caster's answer is what the caster finds
     with S left out, or the caster's answer is such an S and `got` is what the caster finds with S left out. Any other id is judged
-    as usual."""
+    as usual. `rays64`: o and d are float64 rays of a reference, cast as they are (the default widens float32 rays)."""
     got = np.asarray(got).astype(np.uint64)
-    want, t_w, edge_w, in_plane = cast_result if cast_result is not None else cast(verts, spheres, o, d)
-    t_g, edge_g = candidate(verts, spheres, o, d, got)
+    want, t_w, edge_w, in_plane = cast_result if cast_result is not None else cast(verts, spheres, o, d, rays64)
+    t_g, edge_g = candidate(verts, spheres, o, d, got, rays64)
     agree = (got == want) & ~in_plane
     dis = (got != want) & ~in_plane
     extra = {}
@@ -223,14 +228,14 @@ def classify(verts, spheres, o, d, got, cast_result=None, edge_band=EDGE_BAND, t
                 start = want[i] if t_w[i] <= floor[i] and want[i] < NT else got[i]  # the triangle the ray starts on
                 rest = np.array(np.asarray(verts, np.float32).reshape(-1, 9), copy=True)
                 rest[int(start)] = 0  # without area: never hit
-                without = cast(rest, spheres, o[i:i + 1], d[i:i + 1])[0][0]
+                without = cast(rest, spheres, o[i:i + 1], d[i:i + 1], rays64)[0][0]
                 origin[i] = (got[i] if start == want[i] else want[i]) == without
         dis = dis & ~origin
         near_edge = dis & ((edge_w < edge_band) | (edge_g < edge_band))
         if sphere_band:
             unit = 2.0 ** -24
-            ratio = np.fmin(edge_w / (sphere_distance2(verts, spheres, o, want) * unit),
-                            edge_g / (sphere_distance2(verts, spheres, o, got) * unit))
+            ratio = np.fmin(edge_w / (sphere_distance2(verts, spheres, o, want, rays64) * unit),
+                            edge_g / (sphere_distance2(verts, spheres, o, got, rays64) * unit))
             near_edge |= dis & (ratio <= K_S)
             extra["sphere_ratio"] = ratio
         close_t = dis & ~near_edge & (np.abs(t_g - t_w) <= t_band * np.maximum(np.abs(t_g), np.abs(t_w)))
