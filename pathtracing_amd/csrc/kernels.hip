@@ -1044,13 +1044,26 @@ PT_DEV void node_visit_rows(const float4 *__restrict__ base, float4 r0, float4 r
     int32_t ref[N];
     visit_node<L, ORD>(base, r0, r1, r2, r3, rs, t_best, key, ref);
     // the nearest hit child in slot 0; ORDER_SPEC: all sorted ascending, misses = 0xFFFFFFFF at the end; ORDER_NEAREST: hits and misses mixed
-    if (!deep) {
+    // (layout 4Q under ORDER_NEAREST, the headline's node loop: the fast path is laid out as the fall-through and pops in its own
+    // way below, DESIGN.md §4 "Node loop"; layout 4 spills two registers in its all-kinds kernels with either and keeps the plain form)
+    constexpr bool FLAT = ORD == ORDER_NEAREST && L == PT_BVH_WIDTH_4Q;
+    if (FLAT ? __builtin_expect(!deep, 1) : !deep) {
 #pragma unroll
         for (int i = N - 1; i >= 1; --i) { // farthest first, nearest stays in `cur`
             k.lds[sp * k.stride + k.tid] = ref[i];
             sp += key[i] != 0xFFFFFFFFu ? 1u : 0u;
         }
-        cur = key[0] != 0xFFFFFFFFu ? ref[0] : pop_lds(k, sp);
+        if constexpr (FLAT) {
+            // pop_lds, stated so that the lanes whose nearest slot was hit skip one region and the others run it without a branch
+            // on the empty stack (an empty stack reads its own slot 0 and discards it): same `cur`, same `sp`
+            cur = ref[0];
+            if (key[0] == 0xFFFFFFFFu) {
+                const bool has = sp != 0u;
+                sp -= has ? 1u : 0u;
+                const int32_t top = k.lds[sp * k.stride + k.tid];
+                cur = has ? top : PT_BVH_EMPTY;
+            }
+        } else cur = key[0] != 0xFFFFFFFFu ? ref[0] : pop_lds(k, sp);
     } else {
 #pragma unroll
         for (int i = N - 1; i >= 1; --i)
@@ -1198,6 +1211,29 @@ PT_DEV Hit trace_ray(const HotScene &g, const StackCtx &stk, V3 o, V3 d, Hit h, 
     // Why: with one loop for both kinds of step the wave issued the ~160-instruction node
     // code AND the ~125-instruction triangle code in practically every iteration, the latter for ~1 lane in 8; the
     // kernel is VALU-issue bound (rocprofv3: 34 % of wave time waits for an issue slot, 43 % of VALU lanes active).
+    // The non-counting kernels run the same two phases behind wave-uniform loop branches: the node loop goes round while any lane of
+    // the calling ones is at an inner node and has steps left, a lane takes part under a plain `if` on its own state, and the wave
+    // leaves the outer loop once every lane is done. Per lane the visits and their order are those of the loops below; what changes
+    // is the code between two node fetches (DESIGN.md §4 "Node loop": the per-lane `while` with a `break` inside a per-lane `for`
+    // with a `break` cost a latch of ~20 scalar instructions per iteration). The step guard is part of the loop condition: a lane
+    // that has made 2^22 visits leaves the node loop still at an inner node, which is what sets the error flag, after the loop.
+    if constexpr (!COUNT) {
+        constexpr uint32_t kMaxSteps = 1u << 22;
+        for (;;) {
+            bool go = (uint32_t)cur < (uint32_t)PT_BVH_EMPTY && steps < kMaxSteps;
+            if (__builtin_amdgcn_ballot_w64(go) != 0) do { // ---- node phase (bottom-tested: the top-tested form compiles to a per-lane loop again)
+                if (go) { ++steps; node_step<L, ORD>(g.nodes, stk, rs, h.t, cur, sp); }
+                go = (uint32_t)cur < (uint32_t)PT_BVH_EMPTY && steps < kMaxSteps;
+            } while (__builtin_amdgcn_ballot_w64(go) != 0);
+            if ((uint32_t)cur < (uint32_t)PT_BVH_EMPTY) { atomicOr(&cold().ps.counters[kCntError], 2u); cur = PT_BVH_EMPTY; } // out of steps
+            if (!__any((int)(cur != PT_BVH_EMPTY))) break;
+            if (cur != PT_BVH_EMPTY) { // ---- leaf phase
+                if (ANY) leaf_step_any(g.tris, stk, o, d, h, cur, sp);
+                else leaf_step(g.tris, stk, o, d, h, cur, sp);
+            }
+        }
+        return h;
+    }
     bool late_cycle = false; // (DIAG) set once this wave has run a leaf phase for the current rays
     for (;;) {
         while ((uint32_t)cur < (uint32_t)PT_BVH_EMPTY) { // ---- node phase: inner-node refs are 0 .. 0x7ffffffe (EMPTY = 0x7fffffff)
