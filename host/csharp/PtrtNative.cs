@@ -16,6 +16,7 @@ public enum PtSceneKind : uint { Cornell = 0, CornellGlass = 1, TriangleSoup = 2
 [Flags] public enum PtTraceFlags : uint { Occlusion = 1, CountVisits = 2, HostMemory = 4 }
 [Flags] public enum PtUpdateFlags : uint { HostMemory = 1 }
 [Flags] public enum PtGatherFlags : uint { HostMemory = 1 }
+[Flags] public enum PtGatherPathFlags : uint { NextEvent = 4 }  // PT_GATHER_PATHS_NEXT_EVENT (bits 1 and 2 are unassigned)
 [Flags] public enum PtDenoiseFlags : uint { GuidesOnly = 1, NoEdgeStops = 2 }
 [Flags] public enum PtTemporalFlags : uint { Reset = 1, MatchIds = 2, Motion = 8 }
 public enum PtDisplaySource : uint { Frame = 0, Denoised = 1, Temporal = 2 }

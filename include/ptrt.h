@@ -35,8 +35,8 @@ extern "C" {
  * pt_temporal_read / pt_temporal_device_ptr / pt_temporal_history_read, then pt_display, pt_display_params, pt_display_info, PT_DISPLAY_*,
  * PT_TONE_*, pt_display_read / pt_display_device_ptr / pt_display_info_read / pt_display_histogram_read, then PT_TEMPORAL_MOTION, then
  * pt_scene_set_environment, pt_environment_info and pt_scene_environment_info / pt_scene_environment_read, then pt_gather, pt_gather_params and
- * PT_GATHER_HOST_MEMORY, then pt_lens and pt_scene_set_lens / pt_scene_get_lens, then pt_gather_paths and pt_gather_path_params
- * (additions only: no struct or existing signature changed).
+ * PT_GATHER_HOST_MEMORY, then pt_lens and pt_scene_set_lens / pt_scene_get_lens, then pt_gather_paths and pt_gather_path_params,
+ * then PT_GATHER_PATHS_NEXT_EVENT (additions only: no struct or existing signature changed).
  * Hosts compare pt_abi_version() with the header they were built against. */
 #define PTRT_ABI_VERSION 2
 
@@ -334,10 +334,15 @@ pt_status pt_gather(pt_context *ctx, const pt_scene *scene, const void *points, 
 /* ---- path-traced gathers (docs/SPEC.md §12.1): what pt_gather does, with every sample a whole path of §5 that starts at the point
  *      instead of at the camera — light emitted by surfaces and light that arrives after bounces reach E, so a closed, emitter-lit
  *      scene bakes. Fused like pt_gather: 32 B in and 32 B out per point whatever samples and max_depth are. */
+enum {
+    PT_GATHER_PATHS_NEXT_EVENT = 4u /* pt_gather_path_params.flags: next-event estimation in the gather (docs/SPEC.md §12.2): every sample also takes a
+                                       light sample at the point itself and at each Lambert vertex of its path, combined with the hits by
+                                       multiple importance sampling. (Bits 1u and 2u are unassigned and refused.) */
+};
 typedef struct pt_gather_path_params {
     uint32_t max_depth;   /* path segments per sample, 1..255; 0 = 8 */
     uint32_t rr_start;    /* Russian roulette from this depth on, taken literally as in pt_render_params */
-    uint32_t flags;       /* 0; any bit is PT_ERR_INVALID_ARGUMENT (reserved: next-event estimation in the gather) */
+    uint32_t flags;       /* 0 or PT_GATHER_PATHS_NEXT_EVENT; any other bit is PT_ERR_INVALID_ARGUMENT */
     uint32_t pad[5];
 } pt_gather_path_params;  /* 32 B */
 /* points, out, n_points, gp (every field, PT_GATHER_HOST_MEMORY included), alignment and point_offset are pt_gather's. Sample k of point
@@ -348,10 +353,18 @@ typedef struct pt_gather_path_params {
  * bit for bit, for the same gp: V = 1 unless the first segment's closest hit lies within max_distance (the path itself goes on from the
  * closest hit whatever max_distance is). With max_depth 1, max_distance 0 and no emissive material the whole record is pt_gather's.
  * Invalid points, finiteness and the clamp of E are pt_gather's.
- * Checked first: pp NULL, pp->flags != 0, max_depth > 255 -> PT_ERR_INVALID_ARGUMENT; then every check of pt_gather in its order.
- * n_points == 0 is PT_OK. stats (may be NULL): paths = n_points, rays = path segments traced (exact), gpu_ms, everything else 0. Touches no
- * state of pt_render, pt_denoise*, pt_display or pt_gather, never runs the extend-kernel probe; a failed call drains the context's stream.
- * Not there: next-event estimation (pp->flags is reserved for it), the lens, a transmitting or glossy point. */
+ * PT_GATHER_PATHS_NEXT_EVENT (docs/SPEC.md §12.2): the lights are the committed scene's emissive triangles (PT_FLAG_NEXT_EVENT's light set)
+ * and its environment map if that is lit. Every sample takes one light sample at the point, a Lambert receiver with n = the point's
+ * normal and no albedo, before its first segment, and one at every Lambert vertex of its path as a PT_FLAG_NEXT_EVENT frame does; hits of
+ * lights and misses into a lit map are weighted by the power heuristic, the first segment's included. With max_depth 1 that is a
+ * direct-light bake. visibility and bent do not change (shadow rays never count for them and ignore max_distance); on a scene without
+ * a light of either kind the flagged call is the unflagged call bit for bit. rays then also counts the shadow rays traced.
+ * Checked first: pp NULL, a bit of pp->flags other than PT_GATHER_PATHS_NEXT_EVENT, max_depth > 255 -> PT_ERR_INVALID_ARGUMENT; then every
+ * check of pt_gather in its order.
+ * n_points == 0 is PT_OK. stats (may be NULL): paths = n_points, rays = path segments (+ shadow rays) traced (exact), gpu_ms, everything
+ * else 0. Touches no state of pt_render, pt_denoise*, pt_display or pt_gather, never runs the extend-kernel probe; a failed call drains
+ * the context's stream.
+ * Not there: emissive spheres as lights, next-event estimation at metal or dielectric vertices, the lens, a transmitting or glossy point. */
 pt_status pt_gather_paths(pt_context *ctx, const pt_scene *scene, const void *points, void *out, uint64_t n_points,
                           const pt_gather_params *gp, const pt_gather_path_params *pp, pt_stats *stats);
 

@@ -45,6 +45,7 @@ PT_COMM_FORCE_RCCL, PT_COMM_COPY_EXCHANGE = 1, 2
 PT_TRACE_OCCLUSION, PT_TRACE_COUNT_VISITS, PT_TRACE_HOST_MEMORY = 1, 2, 4
 PT_UPDATE_HOST_MEMORY = 1
 PT_GATHER_HOST_MEMORY = 1
+PT_GATHER_PATHS_NEXT_EVENT = 4  # pt_gather_path_params.flags (bits 1 and 2 are unassigned)
 PT_DENOISE_GUIDES_ONLY, PT_DENOISE_NO_EDGE_STOPS = 1, 2
 PT_TEMPORAL_RESET, PT_TEMPORAL_MATCH_IDS = 1, 2
 PT_TEMPORAL_MOTION = 8  # (bit 4 is unassigned)

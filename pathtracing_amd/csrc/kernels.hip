@@ -19,6 +19,8 @@
 //                        group of lanes and reduced in the wave to visibility, sky irradiance and bent normal
 //   k_gather_paths<L,ENV> : pt_gather_paths: the same points, groups and sums, each sample a whole path of the path loop (emission and
 //                        bounces reach E), one segment per lane per pass with in-place regeneration of the lane's next sample
+//   k_gather_paths_nee<L,ENV> : pt_gather_paths with PT_GATHER_PATHS_NEXT_EVENT: the same paths with a light sample (shadow ray, MIS) at
+//                        the point and at every Lambert vertex; a lane's pass is a shadow ray or a segment
 //   k_reduce_streams   : fixed-order sum of a pixel's stream partials
 //   k_assemble         : tile-major slots (of 1..R ranks) -> row-major float4 + RGBA8 frame
 //
@@ -1789,15 +1791,21 @@ PT_DEV bool gather_point_valid(const float4 *__restrict__ points, uint32_t i, ui
 // The point is read again for every sample (its line is in the cache) behind an index the compiler cannot see through: neither the
 // normal nor the sample's key stays in registers across the traversal. (Keeping the first read's normal for the first sample and
 // reading again only for the later ones spills 1-3 VGPRs in every layout.)
-PT_DEV uint32_t gather_ray(const GatherArgs &a, const float4 *__restrict__ points, uint32_t i, uint32_t k, uint32_t seed_hashed, V3 &o, V3 &d)
+// nn: the normalised normal, for the kernel that takes a light sample at the point (§12.2).
+PT_DEV uint32_t gather_ray(const GatherArgs &a, const float4 *__restrict__ points, uint32_t i, uint32_t k, uint32_t seed_hashed, V3 &o, V3 &d, V3 &nn)
 {
     uint32_t ii = i;
     asm volatile("" : "+v"(ii));
-    const V3 nn = normalize(xyz(points[2u * (size_t)ii + 1u]));
+    nn = normalize(xyz(points[2u * (size_t)ii + 1u]));
     o = madd(a.ray_eps, nn, xyz(points[2u * (size_t)ii]));
     const uint32_t key = path_key(seed_hashed, a.point_offset + ii, a.sample_offset + k);
     d = normalize(lambert_vec(nn, u01(key, 0u), u01(key, 1u)));
     return key;
+}
+PT_DEV uint32_t gather_ray(const GatherArgs &a, const float4 *__restrict__ points, uint32_t i, uint32_t k, uint32_t seed_hashed, V3 &o, V3 &d)
+{
+    V3 nn;
+    return gather_ray(a, points, i, k, seed_hashed, o, d, nn);
 }
 
 // One segment through trace_ray from (tmax, MISS). The barriers: the lane's rows really are in LDS across the traversal, no forwarding
@@ -1993,8 +2001,229 @@ k_gather_paths(GatherArgsT<ENV> args)
     if (wave_rays && lane_id() == 0u) atomicAdd(reinterpret_cast<unsigned long long *>(cold().ps.counters + kCntTris), wave_rays);
 }
 
+// k_gather_paths_nee<L, ENV>: k_gather_paths with PT_GATHER_PATHS_NEXT_EVENT (§12.2) on a scene that has a light: §7's and §11's
+// estimator laid over the same paths, and one light sample at the point itself in front of every sample's first segment. A kernel of
+// its own name, not a third template argument: the existing instantiations keep their names (profiles and tools/isa_diff.py compare
+// kernels by name) and their code.
+// The arguments: GatherArgs, then NeeArgs (the light table; ext and rad are not used), then (ENV) EnvArgs with the call's psel.
+// The loop is k_gather_paths's, with k_extend<.., NEE>'s pass: a lane traces one ray per pass through the one traversal call site, a
+// shadow ray (from (tmax, MISS): visible iff nothing is found, like k_extend's) or a segment, and the wave's loop does not tell them
+// apart. What waits across a shadow ray lives in eight more rows of the lane's column: the radiance it adds if it arrives (12-14), the
+// direction of the segment that follows (15-17: a Lambert vertex's continuation and the point's first segment start where their shadow
+// ray starts, so o stays in its registers), the pdf pb that segment carries (18; without a pending shadow ray: the pb of the ray in
+// flight) and PENDING | END (19). 20 rows: 8192 B per wave with the stack, 5 waves per SIMD in the CU's 160 KB.
+// Counters: shadow rays and segments together, where k_gather_paths counts its segments.
+template <bool ENV> struct GatherNeeArgsT { GatherArgs x; NeeArgs nee; };
+template <> struct GatherNeeArgsT<true> { GatherArgs x; NeeArgs nee; EnvArgs env; };
+template <bool ENV>
+PT_DEV const GatherNeeArgsT<ENV> &gather_nee_args() { return reinterpret_cast<const GatherNeeArgsT<ENV> &>(kernargs<false, false>()); } // read where it is used, like cold()
+
+// One light sample of §7 / §11 for a Lambert receiver with normal n whose shadow rays start at so, throughput Tw: dimensions dc (choice),
+// dc + 1, dc + 2 and dv (the map's v) of key. true: a shadow ray (so, sd, tmax) is to be traced, and Lr is what it adds if it arrives.
+template <bool ENV>
+PT_DEV bool gather_light_sample(uint32_t key, uint32_t dc, uint32_t dv, V3 n, V3 so, V3 Tw, V3 &Lr, V3 &sd, float &tmax)
+{
+    const NeeArgs &na = gather_nee_args<ENV>().nee;
+    float uc = u01(key, dc); // the choice number u' of the strategy taken
+    bool to_env = false;
+    if constexpr (ENV) { // §11: the map iff uc < 1/2 while the call has both kinds of light, else the kind there is
+        to_env = gather_nee_args<true>().env.lit != 0u;
+        if (to_env && na.n_lights) { to_env = uc < 0.5f; uc = to_env ? uc * 2.0f : fma_(uc, 2.0f, -1.0f); }
+    }
+    if (ENV && to_env) {
+        const EnvArgs &ea = gather_nee_args<true>().env;
+        const uint32_t j = pick_light(ea.mcdf, ea.n, uc), i = pick_light(ea.ccdf + (size_t)j * ea.n, ea.n, u01(key, dc + 1u));
+        const float u = fma_((float)i + u01(key, dc + 2u), ea.step, -1.0f), v = fma_((float)j + u01(key, dv), ea.step, -1.0f);
+        const V3 wl = env_decode(u, v);
+        float s;
+        const float4 tx = ea.texels[env_texel(ea, wl, s)]; // the lookup decides, not (i, j)
+        const float cs = dot(n, wl), pl = env_pdf(ea, tx, s);
+        if (!(cs > 0.0f && pl > 0.0f)) return false;
+        const float f = mis_weight_times_q((cs * kInvPi) / pl);
+        Lr = v3((Tw.x * f) * tx.x, (Tw.y * f) * tx.y, (Tw.z * f) * tx.z);
+        sd = wl; tmax = __builtin_inff(); // visible iff the shadow ray misses everything
+        return true;
+    }
+    const float4 *lr = na.lights + (size_t)pick_light(na.cdf, na.n_lights, uc) * 4;
+    const float4 l0 = lr[0], l1 = lr[1], l2 = lr[2];
+    const float su = __builtin_sqrtf(u01(key, dc + 1u)), b1 = 1.0f - su, b2 = u01(key, dc + 2u) * su;
+    const V3 x = v3(fma_(b2, l2.x, fma_(b1, l1.x, l0.x)), fma_(b2, l2.y, fma_(b1, l1.y, l0.y)), fma_(b2, l2.z, fma_(b1, l1.z, l0.z)));
+    const V3 dl = x - so;
+    const float dist2 = dot(dl, dl), dist = __builtin_sqrtf(dist2), inv = 1.0f / dist;
+    const V3 wl = v3(dl.x * inv, dl.y * inv, dl.z * inv);
+    const float4 l3 = lr[3];
+    const float cs = dot(n, wl), cl = __builtin_fabsf(dot(xyz(l3), wl));
+    if (!(cs > 0.0f && cl > 0.0f)) return false;
+    float pa = l0.w;
+    if constexpr (ENV) pa = pa * gather_nee_args<true>().env.psel;
+    const float pl = (pa * dist2) / cl, f = mis_weight_times_q((cs * kInvPi) / pl); // w_l * pdf_bsdf / pdf_light
+    Lr = v3((Tw.x * f) * l1.w, (Tw.y * f) * l2.w, (Tw.z * f) * l3.w);
+    sd = wl; tmax = dist * 0.9999f;
+    return true;
+}
+
+// 5 waves: what the rows leave room for (8192 B per wave); no instantiation spills there (tools/resources.py --filter k_gather_paths_nee).
+constexpr int kGatherNeeWaves = 5;
+template <int L, bool ENV>
+__global__ void __launch_bounds__(kExtBlock) __attribute__((amdgpu_waves_per_eu(kGatherNeeWaves, kGatherNeeWaves)))
+k_gather_paths_nee(GatherNeeArgsT<ENV> args)
+{
+    const GatherArgs &a = args.x;
+    const uint32_t n = a.n, K = a.samples;
+    const float4 *__restrict__ points = a.points;
+    __shared__ int32_t s_stack[kStackLds * kExtBlock];
+    __shared__ uint32_t s_rows[GatherRows<20>::kWords];
+    const GatherLane w = gather_lane(a, s_stack);
+    const GatherRows<20> rows{ s_rows + w.tid };
+    constexpr uint32_t kT = 7u, kKey = 10u, kSampleDepth = 11u, kRad = 12u, kExt = 15u, kPb = 18u, kFlags = 19u; // the rows of the lane's path
+    constexpr uint32_t kPending = 1u, kEnd = 2u;
+    VisitCounts vc;
+    unsigned long long wave_rays = 0; // wave-uniform
+    for (uint32_t base = blockIdx.x * w.per_wave; base < n; base += gridDim.x * w.per_wave) { // wave-uniform; n <= 2^31 (query.cpp): no wrap
+        const uint32_t i = base + (w.tid >> a.gshift);
+        const bool valid = gather_point_valid(points, i, n, w.lane);
+        rows.clear();
+        V3 o = v3(0.f, 0.f, 0.f), d = v3(0.f, 0.f, 1.f);
+        float tmax = __builtin_inff(); // of the ray in flight: a shadow ray's, +inf for a segment
+        // the lane's ray becomes the shadow ray (o, sd, tm); Lr, the waiting segment's direction and END go to the rows
+        auto shadow = [&](V3 Lr, V3 sd, float tm, bool end) {
+            rows.row(kRad) = __float_as_uint(Lr.x); rows.row(kRad + 1u) = __float_as_uint(Lr.y); rows.row(kRad + 2u) = __float_as_uint(Lr.z);
+            if (!end) { rows.row(kExt) = __float_as_uint(d.x); rows.row(kExt + 1u) = __float_as_uint(d.y); rows.row(kExt + 2u) = __float_as_uint(d.z); }
+            rows.row(kFlags) = kPending | (end ? kEnd : 0u);
+            d = sd; tmax = tm;
+        };
+        auto start = [&](uint32_t k) { // sample k of the lane's point: §12's ray, T = 1, depth 0, and §12.2's light sample at the point in front of it
+            V3 nn;
+            const uint32_t key = gather_ray(a, points, i, k, w.seed_hashed, o, d, nn);
+            rows.row(kT) = rows.row(kT + 1u) = rows.row(kT + 2u) = __float_as_uint(1.0f);
+            rows.row(kKey) = key; rows.row(kSampleDepth) = k << 8;
+            rows.row(kPb) = __float_as_uint(dot(nn, d) * kInvPi); rows.row(kFlags) = 0u;
+            tmax = __builtin_inff();
+            V3 Lr, sd;
+            float tm;
+            if (gather_light_sample<ENV>(key, 3072u, 3075u, nn, o, v3(1.0f, 1.0f, 1.0f), Lr, sd, tm)) shadow(Lr, sd, tm, false);
+        };
+        bool alive = valid && w.lane < K;
+        if (alive) start(w.lane);
+        for (;;) {
+            const uint64_t alive_mask = __ballot(alive);
+            if (alive_mask == 0) break;
+            wave_rays += (unsigned long long)__popcll(alive_mask);
+            if (alive) {
+                const Hit h = gather_trace<L, false>(w, o, d, tmax, vc);
+                const uint32_t key = rows.row(kKey), kd = rows.row(kSampleDepth), flags = rows.row(kFlags);
+                uint32_t k = kd >> 8;
+                bool term = false;
+                if (flags & kPending) { // ---- a shadow ray: its radiance if it arrived; then the segment that waited, or the path's end
+                    if (h.ref == PT_MISS) { rows.add(0u, rows.get(kRad)); rows.add(1u, rows.get(kRad + 1u)); rows.add(2u, rows.get(kRad + 2u)); }
+                    rows.row(kFlags) = 0u;
+                    if (flags & kEnd) term = true;
+                    else { d = v3(rows.get(kExt), rows.get(kExt + 1u), rows.get(kExt + 2u)); tmax = __builtin_inff(); }
+                } else {
+                    const DeviceScene &sc = cold().sc;
+                    const FrameParams &fp = cold().fp;
+                    V3 T = v3(rows.get(kT), rows.get(kT + 1u), rows.get(kT + 2u));
+                    const float pb = rows.get(kPb); // of the segment just traced: > 0 iff it left the point or a Lambert vertex
+                    const uint32_t depth = (kd & 255u) + 1u;
+                    bool pending = false;
+                    auto add = [&](V3 Lr) { rows.fma(0u, T.x, Lr.x); rows.fma(1u, T.y, Lr.y); rows.fma(2u, T.z, Lr.z); };
+                    if (depth == 1u && !(h.ref != PT_MISS && h.t <= a.tmax)) rows.visible(d); // nothing within tmax on the first segment
+                    if (h.ref == PT_MISS) { // ---- a miss: its radiance (§11's w against the light sample of where the ray left), and the path ends
+                        if constexpr (ENV) {
+                            const EnvArgs &ea = gather_nee_args<true>().env;
+                            float s;
+                            const float4 tx = ea.texels[env_texel(ea, d, s)];
+                            V3 e = xyz(tx);
+                            if (ea.lit && pb > 0.0f) {
+                                const float wm = mis_weight(env_pdf(ea, tx, s) / pb);
+                                e = v3(tx.x * wm, tx.y * wm, tx.z * wm);
+                            }
+                            add(e);
+                        } else add(v3(sc.sky[0], sc.sky[1], sc.sky[2]));
+                        term = true;
+                    } else {                // ---- a hit: the surface and its emission (shade_one's lines, §7's w_b)
+                        const V3 P = madd(h.t, d, o);
+                        V3 ng;
+                        uint32_t mat;
+                        if (h.ref < sc.n_tris) {
+                            const float4 ts = sc.tris[(size_t)h.ref * 4 + 3];
+                            ng = xyz(ts);
+                            mat = __float_as_uint(ts.w);
+                        } else {
+                            const uint32_t j = h.ref - sc.n_tris;
+                            const float4 s = sc.spheres[j];
+                            const uint2 mi = sc.sph_mat[j];
+                            const float ir = __uint_as_float(mi.y);
+                            ng = v3((P.x - s.x) * ir, (P.y - s.y) * ir, (P.z - s.z) * ir);
+                            mat = mi.x;
+                        }
+                        const bool front = dot(ng, d) < 0.0f;
+                        const V3 nrm = front ? ng : neg(ng);
+                        float4 m0 = sc.mats[(size_t)mat * 3], m1 = sc.mats[(size_t)mat * 3 + 1];
+                        const float4 m2 = sc.mats[(size_t)mat * 3 + 2];
+                        asm volatile("" : "+v"(m0.x), "+v"(m1.x)); // both rows requested before either is looked at
+                        const V3 alb = v3(m0.y, m0.z, m0.w), emi = xyz(m1);
+                        const uint32_t kind = __float_as_uint(m0.x);
+                        if (emi.x != 0.0f || emi.y != 0.0f || emi.z != 0.0f) {
+                            V3 e = emi;
+                            const NeeArgs &na = gather_nee_args<ENV>().nee;
+                            if (pb > 0.0f && h.ref < sc.n_tris && (!ENV || na.n_lights)) { // (ENV: pb is also carried when the map is the only light)
+                                float pa = na.pa[h.ref];
+                                if constexpr (ENV) pa = pa * gather_nee_args<true>().env.psel;
+                                if (pa > 0.0f) {
+                                    const float pl = (pa * (h.t * h.t)) / __builtin_fabsf(dot(ng, d)), wb = mis_weight(pl / pb);
+                                    e = v3(emi.x * wb, emi.y * wb, emi.z * wb);
+                                }
+                            }
+                            add(e);
+                        }
+                        if (depth >= fp.max_depth) term = true;
+                        else {              // ---- BSDF sample, throughput, Russian roulette; a Lambert vertex's light sample
+                            const uint32_t bb = depth - 1u;
+                            BsdfSample bs;
+                            if (kind == (uint32_t)PT_LAMBERT) bs = sample_lambert(alb, nrm, u01(key, 4u + 4u * bb), u01(key, 5u + 4u * bb));
+                            else if (kind == (uint32_t)PT_METAL) bs = sample_metal(alb, m1.w, d, nrm, u01(key, 4u + 4u * bb), u01(key, 5u + 4u * bb));
+                            else bs = sample_dielectric(alb, m2.x, d, nrm, front, u01(key, 6u + 4u * bb));
+                            V3 ta = T; // T * albedo of a Lambert vertex (W = albedo), before Russian roulette
+                            if (!bs.ok) term = true;
+                            else {
+                                T = v3(T.x * bs.W.x, T.y * bs.W.y, T.z * bs.W.z);
+                                ta = T;
+                                if (roulette_ends(fp, key, depth, bb, T)) term = true;
+                                if (!term) { o = madd(bs.side * fp.ray_eps, nrm, P); d = bs.wi; }
+                            }
+                            tmax = __builtin_inff();
+                            if (!term) rows.row(kPb) = __float_as_uint(kind == (uint32_t)PT_LAMBERT ? dot(nrm, bs.wi) * kInvPi : 0.0f);
+                            if (kind == (uint32_t)PT_LAMBERT) {
+                                const V3 so = madd(fp.ray_eps, nrm, P); // the continuation origin of a Lambert vertex (side +1)
+                                V3 Lr, sd;
+                                float tm;
+                                if (gather_light_sample<ENV>(key, 1024u + 3u * bb, 2048u + bb, nrm, so, ta, Lr, sd, tm)) {
+                                    o = so;
+                                    shadow(Lr, sd, tm, term); // the shadow ray goes first; the path's end waits for it too
+                                    pending = true;
+                                }
+                            }
+                        }
+                    }
+                    rows.row(kT) = __float_as_uint(T.x); rows.row(kT + 1u) = __float_as_uint(T.y); rows.row(kT + 2u) = __float_as_uint(T.z);
+                    rows.row(kSampleDepth) = (k << 8) | depth;
+                    if (pending) term = false;
+                }
+                if (term) { // the lane's next sample, in place
+                    k += w.G;
+                    alive = k < K;
+                    if (alive) start(k);
+                }
+            }
+        }
+        gather_finish(rows, w, i, n, K, valid, a.out);
+    }
+    if (wave_rays && lane_id() == 0u) atomicAdd(reinterpret_cast<unsigned long long *>(cold().ps.counters + kCntTris), wave_rays);
+}
+
 // ------------------------------------------------------------------------------------------------
-// k_shade<SHADE_QUEUE>   : walks the extend queue of this iteration in the SAME order k_extend did, so ray/throughput/hit
+// k_shade<SHADE_QUEUE>  : walks the extend queue of this iteration in the SAME order k_extend did, so ray/throughput/hit
 //                          reads are the coalesced, L2-warm lines k_extend just touched. Misses and Lambert hits are shaded
 //                          in place; specular kinds (metal, dielectric) are deferred to per-kind bucket queues.
 // k_shade<SHADE_BUCKETS> : walks the two specular buckets, concatenated, so the kind switch is wave-uniform.
@@ -2189,8 +2418,9 @@ uint32_t gather_blocks(uint32_t n, uint32_t samples)
 }
 
 hipError_t launch_gather(hipStream_t s, const DeviceScene &sc, const PathState &ps, const float4 *points, float4 *out, uint32_t n, const GatherParams &gp,
-                         const GatherPathParams *pp, const EnvArgs *env)
+                         const GatherPathParams *pp, const EnvArgs *env, const NeeArgs *nee)
 {
+    if (nee && !pp) return hipErrorInvalidValue;
     GatherArgs a{};
     a.sc = sc; a.ps = ps; a.points = points; a.out = out; a.n = n;
     a.samples = gp.samples; a.gshift = gather_group_shift(gp.samples); a.seed = gp.seed;
@@ -2202,7 +2432,12 @@ hipError_t launch_gather(hipStream_t s, const DeviceScene &sc, const PathState &
         constexpr int L = decltype(lc)::value;
         constexpr bool E = decltype(ec)::value != 0;
         GatherArgsT<E> t; t.x = a; if constexpr (E) t.env = *env;
-        if constexpr (decltype(pc)::value != 0) hipLaunchKernelGGL((k_gather_paths<L, E>), grid, dim3(kExtBlock), 0, s, t);
+        if constexpr (decltype(pc)::value != 0) {
+            if (nee) { // §12.2 on a scene with a light: the light table travels behind GatherArgs, the map behind it
+                GatherNeeArgsT<E> tn; tn.x = a; tn.nee = *nee; if constexpr (E) tn.env = *env;
+                hipLaunchKernelGGL((k_gather_paths_nee<L, E>), grid, dim3(kExtBlock), 0, s, tn);
+            } else hipLaunchKernelGGL((k_gather_paths<L, E>), grid, dim3(kExtBlock), 0, s, t);
+        }
         else hipLaunchKernelGGL((k_gather<L, E>), grid, dim3(kExtBlock), 0, s, t);
     }); }); });
     return known ? hipGetLastError() : hipErrorInvalidValue;

@@ -222,6 +222,8 @@ hipError_t launch_trace(hipStream_t s, const DeviceScene &sc, const PathState &p
 // cover the grid's lanes. The kernel adds the invalid points it met to the low word of kCntNodes. env (may be NULL): the scene's map.
 // pp (NULL for pt_gather): the call is pt_gather_paths (§12.1), the same points, grid and counters; every sample is a path of §5 of at most
 // max_depth (1..255) segments with Russian roulette from rr_start on. The kernel adds the segments it traced to the u64 at kCntTris.
+// nee (NULL, or with pp): PT_GATHER_PATHS_NEXT_EVENT (§12.2) on a scene that has a light: the light table (ext and rad are not used), and
+// with it env->psel and env->lit as a NEE frame sets them. The shadow rays are counted with the segments.
 struct GatherParams {
     uint32_t samples, seed, point_offset, sample_offset; // samples in 1..4096
     float tmax, ray_eps;                                        // tmax: max_distance, +inf for "unbounded"
@@ -230,7 +232,7 @@ struct GatherPathParams { uint32_t max_depth, rr_start; };
 uint32_t gather_group_shift(uint32_t samples); // log2 of min(64, the power of two >= samples)
 uint32_t gather_blocks(uint32_t n, uint32_t samples);
 hipError_t launch_gather(hipStream_t s, const DeviceScene &sc, const PathState &ps, const float4 *points, float4 *out, uint32_t n, const GatherParams &gp,
-                         const GatherPathParams *pp, const EnvArgs *env);
+                         const GatherPathParams *pp, const EnvArgs *env, const NeeArgs *nee = nullptr);
 hipError_t launch_reduce_streams(hipStream_t s, const float4 *acc, float4 *tiles, uint32_t slots_per_stream, uint32_t streams);
 hipError_t launch_assemble(hipStream_t s, const float4 *gathered, uint32_t nranks, uint32_t slots_per_rank,
                            uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t n_tiles, float inv_spp,

@@ -1,4 +1,4 @@
-// query.cpp — ray queries (pt_trace_rays, docs/SPEC.md §4.2), hemisphere gathers (pt_gather, §12; pt_gather_paths, §12.1) and the query plumbing of context.h
+// query.cpp — ray queries (pt_trace_rays, docs/SPEC.md §4.2), hemisphere gathers (pt_gather, §12; pt_gather_paths, §12.1 and §12.2) and the query plumbing of context.h
 // (Queries), which pt_denoise's guide pass shares (denoise_host.cpp).
 #include "scene.h"
 #include <hip/hip_runtime.h>
@@ -93,7 +93,8 @@ static pt_status gather(pt_context *c, const pt_scene *s, const void *points, vo
     const char *fn = paths ? "pt_gather_paths" : "pt_gather";
     if (paths) {
         if (!pp) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_gather_paths: path params is NULL");
-        if (pp->flags) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_gather_paths: unknown path flag bits 0x%x", pp->flags);
+        if (pp->flags & ~(uint32_t)PT_GATHER_PATHS_NEXT_EVENT)
+            return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_gather_paths: unknown path flag bits 0x%x", pp->flags & ~(uint32_t)PT_GATHER_PATHS_NEXT_EVENT);
         if (pp->max_depth > 255u) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_gather_paths: max_depth %u is more than 255", pp->max_depth);
     }
     if (!gp) return fail(c, PT_ERR_INVALID_ARGUMENT, "%s: params is NULL", fn);
@@ -134,12 +135,16 @@ static pt_status gather(pt_context *c, const pt_scene *s, const void *points, vo
         HIP_TRY(c, hipMemcpyAsync(c->query.rays.p, points, n_points * 32u, hipMemcpyHostToDevice, q));
         d_points = c->query.rays.p; d_out = c->query.hits.p;
     }
-    const EnvArgs env = s->env.present() ? s->env.args(1.0f) : EnvArgs{};
+    // §12.2: a flagged call samples the scene's light set and its map if that is lit; with neither it is the unflagged call, kernel and all
+    const bool env_lit = s->env.present() && s->env.lit();
+    const bool nee = paths && (pp->flags & PT_GATHER_PATHS_NEXT_EVENT) && (s->n_lights || env_lit);
+    const NeeArgs na{ s->d_lights.p, s->d_cdf.p, s->d_pa.p, s->n_lights, nullptr, nullptr };
+    const EnvArgs env = s->env.present() ? s->env.args(nee && env_lit && s->n_lights ? 0.5f : 1.0f) : EnvArgs{};
     HIP_TRY(c, hipEventRecord(c->query.ev[0], q));
     for (uint64_t first = 0; first < n_points; first += kTraceChunk) { // point_offset + first wraps like the key's own u32 arithmetic
         GatherParams kc = k; kc.point_offset = k.point_offset + (uint32_t)first;
         const uint32_t nc = (uint32_t)std::min(kTraceChunk, n_points - first);
-        HIP_TRY(c, launch_gather(q, s->ds, ps, d_points + 2u * first, d_out + 2u * first, nc, kc, paths ? &kp : nullptr, s->env.present() ? &env : nullptr));
+        HIP_TRY(c, launch_gather(q, s->ds, ps, d_points + 2u * first, d_out + 2u * first, nc, kc, paths ? &kp : nullptr, s->env.present() ? &env : nullptr, nee ? &na : nullptr));
     }
     HIP_TRY(c, hipEventRecord(c->query.ev[1], q));
     if (host) HIP_TRY(c, hipMemcpyAsync(out_rows, d_out, n_points * 32u, hipMemcpyDeviceToHost, q));
@@ -147,7 +152,7 @@ static pt_status gather(pt_context *c, const pt_scene *s, const void *points, vo
     if ((st = c->query.finish(c, n)) != PT_OK) return st;
     if (n.error) return fail(c, PT_ERR_INTERNAL, "%s: device error flag 0x%x (1 = traversal stack overflow, 2 = step limit)", fn, n.error);
     float ms = 0.f; HIP_TRY(c, hipEventElapsedTime(&ms, c->query.ev[0], c->query.ev[1])); res.gpu_ms = ms;
-    // the kernel counted the invalid points where the visit counter lives, and k_gather_paths its segments where the triangle tests' does
+    // the kernel counted the invalid points where the visit counter lives, and k_gather_paths its segments (and shadow rays) where the triangle tests' does
     res.rays = paths ? n.tri_tests : (uint64_t)k.samples * (n_points - n.node_visits);
     if (stats) *stats = res;
     return PT_OK;

@@ -328,14 +328,17 @@ class Renderer:
         return self._gather(points, normals, gp, lambda *a: N.lib.pt_gather(*a))
 
     def GatherPaths(self, points, normals, samples=64, seed=0, sample_offset=0, point_offset=0, max_distance=0.0, ray_eps=1e-3,
-                    max_depth=8, rr_start=3):
+                    max_depth=8, rr_start=3, next_event=False):
         """Path-traced gathers (include/ptrt.h pt_gather_paths, docs/SPEC.md §12.1): Gather's points, arguments and results, with every
         sample a whole path of at most `max_depth` segments (Russian roulette from depth `rr_start` on) that starts at the point. E is
         the mean radiance the paths bring — emissive surfaces and bounced light included, so pi * E is a Lambert texel's irradiance in
-        a closed, emitter-lit scene too; visibility and bent are Gather's. The pt_stats' rays are the path segments traced."""
+        a closed, emitter-lit scene too; visibility and bent are Gather's. The pt_stats' rays are the path segments traced.
+        next_event (PT_GATHER_PATHS_NEXT_EVENT, §12.2): every sample also samples the scene's lights (emissive triangles, a lit
+        environment map) at the point and at its Lambert vertices, with multiple importance sampling — the same expectation with less
+        noise under small lights, and with max_depth = 1 a direct-light bake; rays then counts the shadow rays too."""
         gp = N.pt_gather_params(samples=samples, seed=seed, sample_offset=sample_offset, point_offset=point_offset,
                                 max_distance=max_distance, ray_eps=ray_eps, flags=0)
-        pp = N.pt_gather_path_params(max_depth=max_depth, rr_start=rr_start, flags=0)
+        pp = N.pt_gather_path_params(max_depth=max_depth, rr_start=rr_start, flags=N.PT_GATHER_PATHS_NEXT_EVENT if next_event else 0)
         return self._gather(points, normals, gp, lambda *a: N.lib.pt_gather_paths(*a[:-1], C.byref(pp), a[-1]))
 
     def _gather(self, points, normals, gp, call):
