@@ -1,9 +1,10 @@
 // ptrt_cli — headless counterpart of Program.cs / App.Run (RayTracing/Program.cs:1-9, App.cs:15-21):
 // build a renderer, render N frames, write the image the reference would have shown in its window.
 //   ptrt_cli [--scene reference|cornell|glass|soup|tess] [--detail N] [--size WxH] [--spp N] [--depth N]
-//            [--frames N] [--ppm out.ppm] [--pfm out.pfm] [--gpus N] [--virtual 0|1|2] [--nee] [--denoise N]
+//            [--frames N] [--ppm out.ppm] [--pfm out.pfm] [--gpus N] [--virtual 0|1|2] [--nee] [--nee-spheres] [--denoise N]
 //            [--display clamp|reinhard|aces] [--auto-exposure] [--env FILE.pfm]
-// --nee: next-event estimation (PT_FLAG_NEXT_EVENT, docs/SPEC.md §7).
+// --nee: next-event estimation (PT_FLAG_NEXT_EVENT, docs/SPEC.md §7). --nee-spheres: that with the scene's emissive spheres as lights
+//            too (PT_FLAG_NEXT_EVENT | PT_FLAG_NEXT_EVENT_SPHERES, §7.1).
 // --env FILE.pfm: a square colour PFM read as the scene's octahedral environment map (docs/SPEC.md §11; rows in file order).
 // --denoise N: denoise the last frame with N filter passes (0 = the default; docs/SPEC.md §8) and write the denoised image to --ppm /
 // --pfm instead of the frame (the PPM by SPEC §1's unorm8 rule).
@@ -51,6 +52,7 @@ int main(int argc, char **argv)
     for (int i = 1; i < argc; i += 2) {
         const std::string a = argv[i];
         if (a == "--nee") { flags |= PT_FLAG_NEXT_EVENT; --i; continue; } // a switch: no value
+        if (a == "--nee-spheres") { flags |= PT_FLAG_NEXT_EVENT | PT_FLAG_NEXT_EVENT_SPHERES; --i; continue; }
         if (a == "--auto-exposure") { auto_exposure = true; --i; continue; }
         if (i + 1 >= argc) { std::fprintf(stderr, "option %s needs a value\n", a.c_str()); return 2; }
         if (a == "--scene") scene = argv[i + 1];

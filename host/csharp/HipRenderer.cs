@@ -109,14 +109,16 @@ public unsafe class HipRenderer : IDisposable
     // Path-traced gathers (docs/SPEC.md §12.1): Gather's points and rows, with every sample a whole path of at most maxDepth segments that
     // starts at the point (Russian roulette from depth rrStart on). E carries emissive surfaces and bounced light; visibility and bent are Gather's.
     // nextEvent (§12.2): light samples with MIS at the point and at the paths' Lambert vertices; with maxDepth 1 a direct-light bake.
+    // sphereLights (§7.1; needs nextEvent): the scene's emissive spheres are lights too, sampled by the cone they subtend.
     public float[] GatherPaths(float[] points, uint samples = 64, uint seed = 0, float maxDistance = 0f, float rayEps = 1e-3f,
-                               uint sampleOffset = 0, uint pointOffset = 0, uint maxDepth = 8, uint rrStart = 3, bool nextEvent = false)
+                               uint sampleOffset = 0, uint pointOffset = 0, uint maxDepth = 8, uint rrStart = 3, bool nextEvent = false,
+                               bool sphereLights = false)
     {
         if (points.Length % 8 != 0) throw new ArgumentException("points: 8 floats per point");
         var rows = new float[points.Length];
         var gp = new PtGatherParams { samples = samples, seed = seed, sample_offset = sampleOffset, point_offset = pointOffset,
                                       max_distance = maxDistance, ray_eps = rayEps, flags = (uint)PtGatherFlags.HostMemory };
-        var pp = new PtGatherPathParams { max_depth = maxDepth, rr_start = rrStart, flags = nextEvent ? (uint)PtGatherPathFlags.NextEvent : 0 };
+        var pp = new PtGatherPathParams { max_depth = maxDepth, rr_start = rrStart, flags = (nextEvent ? (uint)PtGatherPathFlags.NextEvent : 0) | (sphereLights ? (uint)PtGatherPathLights.SphereLights : 0) };
         PtStats st;
         fixed (float* p = points) fixed (float* o = rows)
             Ptrt.Check(Ptrt.pt_gather_paths(_ctx, _scene, p, o, (ulong)(points.Length / 8), &gp, &pp, &st), _ctx);

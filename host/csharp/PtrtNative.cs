@@ -11,12 +11,13 @@ public enum PtStatus : int { Ok = 0, InvalidArgument, NoDevice, Hip, OutOfMemory
 public enum PtMode : uint { ReferenceSphere = 0, PathTrace = 1 }
 public enum PtMaterialKind : uint { Lambert = 0, Metal = 1, Dielectric = 2 }
 public enum PtSceneKind : uint { Cornell = 0, CornellGlass = 1, TriangleSoup = 2, CornellTess = 3 }
-[Flags] public enum PtFlags : uint { ProfileKernels = 1, CountVisits = 2, ExtendPacked = 4, ExtendSimple = 8, Accumulate = 16, BucketSpecular = 32, SplitKernels = 64, ExtendPool = 128, NextEvent = 256 }
+[Flags] public enum PtFlags : uint { ProfileKernels = 1, CountVisits = 2, ExtendPacked = 4, ExtendSimple = 8, Accumulate = 16, BucketSpecular = 32, SplitKernels = 64, ExtendPool = 128, NextEvent = 256, NextEventSpheres = 512 }
 [Flags] public enum PtCommFlags : uint { ForceRccl = 1, CopyExchange = 2 }
 [Flags] public enum PtTraceFlags : uint { Occlusion = 1, CountVisits = 2, HostMemory = 4 }
 [Flags] public enum PtUpdateFlags : uint { HostMemory = 1 }
 [Flags] public enum PtGatherFlags : uint { HostMemory = 1 }
 [Flags] public enum PtGatherPathFlags : uint { NextEvent = 4 }  // PT_GATHER_PATHS_NEXT_EVENT (bits 1 and 2 are unassigned)
+[Flags] public enum PtGatherPathLights : uint { SphereLights = 16 }  // PT_GATHER_PATHS_SPHERE_LIGHTS: or-ed into the same flags word, with NextEvent (bit 8 is unassigned)
 [Flags] public enum PtDenoiseFlags : uint { GuidesOnly = 1, NoEdgeStops = 2 }
 [Flags] public enum PtTemporalFlags : uint { Reset = 1, MatchIds = 2, Motion = 8 }
 public enum PtDisplaySource : uint { Frame = 0, Denoised = 1, Temporal = 2 }

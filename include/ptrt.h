@@ -36,7 +36,8 @@ extern "C" {
  * PT_TONE_*, pt_display_read / pt_display_device_ptr / pt_display_info_read / pt_display_histogram_read, then PT_TEMPORAL_MOTION, then
  * pt_scene_set_environment, pt_environment_info and pt_scene_environment_info / pt_scene_environment_read, then pt_gather, pt_gather_params and
  * PT_GATHER_HOST_MEMORY, then pt_lens and pt_scene_set_lens / pt_scene_get_lens, then pt_gather_paths and pt_gather_path_params,
- * then PT_GATHER_PATHS_NEXT_EVENT (additions only: no struct or existing signature changed).
+ * then PT_GATHER_PATHS_NEXT_EVENT, then PT_FLAG_NEXT_EVENT_SPHERES and PT_GATHER_PATHS_SPHERE_LIGHTS (additions only: no struct or existing
+ * signature changed).
  * Hosts compare pt_abi_version() with the header they were built against. */
 #define PTRT_ABI_VERSION 2
 
@@ -76,14 +77,20 @@ enum {
     PT_FLAG_EXTEND_POOL = 128u,   /* force the pooled extend kernel (a wavefront owns 128 queue entries, refills idle lanes during
                                      traversal and shades the whole pool at full width) */
     PT_FLAG_ACCUMULATE = 16u,    /* progressive rendering: keep the sums of the previous call(s) (same size/rank/streams/seed and
-                                     PT_FLAG_NEXT_EVENT setting, sample_offset = samples so far) and show the mean over all samples — the
+                                     PT_FLAG_NEXT_EVENT / _SPHERES setting, sample_offset = samples so far) and show the mean over all samples — the
                                      converging analogue of the reference's render-every-frame loop (App.cs:39-42) */
-    PT_FLAG_NEXT_EVENT = 256u     /* next-event estimation (docs/SPEC.md §7): every Lambert vertex also samples a point on an emissive triangle
+    PT_FLAG_NEXT_EVENT = 256u,    /* next-event estimation (docs/SPEC.md §7): every Lambert vertex also samples a point on an emissive triangle
                                      and traces a shadow ray to it, combined with the BSDF-sampled hits by multiple importance sampling. Same
                                      mean, far less noise in scenes lit by small emitters. The BSDF-sampled paths are those of a plain frame;
                                      pt_stats.rays then counts their rays plus the shadow rays traced. Runs on the one-ray-per-lane kernel:
                                      with PT_FLAG_EXTEND_PACKED / _POOL, PT_FLAG_SPLIT_KERNELS / _BUCKET_SPECULAR, pt_tuning.extend_kernel 2 / 3
                                      or PT_FLAG_COUNT_VISITS the frame is PT_ERR_UNSUPPORTED */
+    PT_FLAG_NEXT_EVENT_SPHERES = 512u /* with PT_FLAG_NEXT_EVENT (alone: PT_ERR_INVALID_ARGUMENT): the scene's emissive spheres join the light set
+                                     (docs/SPEC.md §7.1). A light sample that picks one draws a direction in the cone the sphere subtends from
+                                     the vertex, and a hit of such a sphere by a ray that left a Lambert vertex is weighted against that pdf.
+                                     Same mean again; far less noise where a small emissive sphere (a bulb) lights the scene. On a scene
+                                     without an emissive sphere the frame is the PT_FLAG_NEXT_EVENT frame bit for bit. Refuses what
+                                     PT_FLAG_NEXT_EVENT refuses */
 };
 /* pt_scene_commit options */
 enum {
@@ -335,14 +342,17 @@ pt_status pt_gather(pt_context *ctx, const pt_scene *scene, const void *points, 
  *      instead of at the camera — light emitted by surfaces and light that arrives after bounces reach E, so a closed, emitter-lit
  *      scene bakes. Fused like pt_gather: 32 B in and 32 B out per point whatever samples and max_depth are. */
 enum {
-    PT_GATHER_PATHS_NEXT_EVENT = 4u /* pt_gather_path_params.flags: next-event estimation in the gather (docs/SPEC.md §12.2): every sample also takes a
+    PT_GATHER_PATHS_NEXT_EVENT = 4u, /* pt_gather_path_params.flags: next-event estimation in the gather (docs/SPEC.md §12.2): every sample also takes a
                                        light sample at the point itself and at each Lambert vertex of its path, combined with the hits by
                                        multiple importance sampling. (Bits 1u and 2u are unassigned and refused.) */
+    PT_GATHER_PATHS_SPHERE_LIGHTS = 16u /* with PT_GATHER_PATHS_NEXT_EVENT (alone: PT_ERR_INVALID_ARGUMENT): the scene's emissive spheres join the
+                                       light set, sampled by the cone they subtend (docs/SPEC.md §7.1), at the point and at every Lambert
+                                       vertex. (Bit 8u is unassigned and refused.) */
 };
 typedef struct pt_gather_path_params {
     uint32_t max_depth;   /* path segments per sample, 1..255; 0 = 8 */
     uint32_t rr_start;    /* Russian roulette from this depth on, taken literally as in pt_render_params */
-    uint32_t flags;       /* 0 or PT_GATHER_PATHS_NEXT_EVENT; any other bit is PT_ERR_INVALID_ARGUMENT */
+    uint32_t flags;       /* 0, PT_GATHER_PATHS_NEXT_EVENT, or that | PT_GATHER_PATHS_SPHERE_LIGHTS; any other bit is PT_ERR_INVALID_ARGUMENT */
     uint32_t pad[5];
 } pt_gather_path_params;  /* 32 B */
 /* points, out, n_points, gp (every field, PT_GATHER_HOST_MEMORY included), alignment and point_offset are pt_gather's. Sample k of point
@@ -359,12 +369,15 @@ typedef struct pt_gather_path_params {
  * lights and misses into a lit map are weighted by the power heuristic, the first segment's included. With max_depth 1 that is a
  * direct-light bake. visibility and bent do not change (shadow rays never count for them and ignore max_distance); on a scene without
  * a light of either kind the flagged call is the unflagged call bit for bit. rays then also counts the shadow rays traced.
- * Checked first: pp NULL, a bit of pp->flags other than PT_GATHER_PATHS_NEXT_EVENT, max_depth > 255 -> PT_ERR_INVALID_ARGUMENT; then every
- * check of pt_gather in its order.
+ * PT_GATHER_PATHS_SPHERE_LIGHTS (docs/SPEC.md §7.1) adds the committed scene's emissive spheres to that light set: a light sample that picks
+ * one draws a direction in the cone it subtends, and hits of such a sphere are weighted like hits of light triangles. On a scene without
+ * an emissive sphere the call is the PT_GATHER_PATHS_NEXT_EVENT call bit for bit.
+ * Checked first: pp NULL, a bit of pp->flags other than these two, PT_GATHER_PATHS_SPHERE_LIGHTS without PT_GATHER_PATHS_NEXT_EVENT,
+ * max_depth > 255 -> PT_ERR_INVALID_ARGUMENT; then every check of pt_gather in its order.
  * n_points == 0 is PT_OK. stats (may be NULL): paths = n_points, rays = path segments (+ shadow rays) traced (exact), gpu_ms, everything
  * else 0. Touches no state of pt_render, pt_denoise*, pt_display or pt_gather, never runs the extend-kernel probe; a failed call drains
  * the context's stream.
- * Not there: emissive spheres as lights, next-event estimation at metal or dielectric vertices, the lens, a transmitting or glossy point. */
+ * Not there: next-event estimation at metal or dielectric vertices, the lens, a transmitting or glossy point. */
 pt_status pt_gather_paths(pt_context *ctx, const pt_scene *scene, const void *points, void *out, uint64_t n_points,
                           const pt_gather_params *gp, const pt_gather_path_params *pp, pt_stats *stats);
 

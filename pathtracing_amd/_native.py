@@ -39,6 +39,7 @@ PT_FLAG_PROFILE_KERNELS, PT_FLAG_COUNT_VISITS, PT_FLAG_EXTEND_PACKED, PT_FLAG_EX
 PT_FLAG_SPLIT_KERNELS = 64
 PT_FLAG_EXTEND_POOL = 128
 PT_FLAG_NEXT_EVENT = 256
+PT_FLAG_NEXT_EVENT_SPHERES = 512  # with PT_FLAG_NEXT_EVENT: emissive spheres are lights too (docs/SPEC.md §7.1)
 PT_SCENE_CORNELL, PT_SCENE_CORNELL_GLASS, PT_SCENE_TRIANGLE_SOUP, PT_SCENE_CORNELL_TESS = 0, 1, 2, 3
 PT_BVH_WIDTH_2, PT_BVH_WIDTH_4, PT_BVH_WIDTH_4Q, PT_BVH_WIDTH_8Q, PT_BVH_WIDTH_8O, PT_BVH_BUILD_LBVH = 2, 4, 68, 72, 73, 0x100
 PT_COMM_FORCE_RCCL, PT_COMM_COPY_EXCHANGE = 1, 2
@@ -46,6 +47,7 @@ PT_TRACE_OCCLUSION, PT_TRACE_COUNT_VISITS, PT_TRACE_HOST_MEMORY = 1, 2, 4
 PT_UPDATE_HOST_MEMORY = 1
 PT_GATHER_HOST_MEMORY = 1
 PT_GATHER_PATHS_NEXT_EVENT = 4  # pt_gather_path_params.flags (bits 1 and 2 are unassigned)
+PT_GATHER_PATHS_SPHERE_LIGHTS = 16  # with PT_GATHER_PATHS_NEXT_EVENT: emissive spheres are lights too (bit 8 is unassigned)
 PT_DENOISE_GUIDES_ONLY, PT_DENOISE_NO_EDGE_STOPS = 1, 2
 PT_TEMPORAL_RESET, PT_TEMPORAL_MATCH_IDS = 1, 2
 PT_TEMPORAL_MOTION = 8  # (bit 4 is unassigned)

@@ -204,17 +204,19 @@ private:
 // are next-event estimates (the two kinds of sum do not mix), and the samples so far. Invalid from begin() until complete().
 class Accumulation {
 public:
-    struct Key { uint32_t w, h, rank, nranks, streams, seed; bool nee; };
-    enum class Refusal { none, other_frame, other_estimator, wrong_offset };
+    struct Key { uint32_t w, h, rank, nranks, streams, seed; bool nee; bool spheres = false; }; // spheres: PT_FLAG_NEXT_EVENT_SPHERES (docs/SPEC.md §7.1)
+    enum class Refusal { none, other_frame, other_estimator, other_light_set, wrong_offset };
     Refusal continues(const Key &k, uint32_t sample_offset) const
     {
         if (spp == 0 || key.w != k.w || key.h != k.h || key.rank != k.rank || key.nranks != k.nranks || key.streams != k.streams || key.seed != k.seed)
             return Refusal::other_frame;
         if (key.nee != k.nee) return Refusal::other_estimator;
+        if (key.spheres != k.spheres) return Refusal::other_light_set;
         return sample_offset != spp ? Refusal::wrong_offset : Refusal::none;
     }
     uint64_t samples() const { return spp; }
     bool next_event() const { return key.nee; }
+    bool sphere_lights() const { return key.spheres; }
     void begin() { spp = 0; }
     void complete(const Key &k, uint64_t total_spp) { key = k; spp = total_spp; }
 

@@ -208,6 +208,7 @@ struct Frame {                  // a path-traced frame as plan_frame lays it out
     Pipeline pipe;              // what the frame's flags, pt_tuning.extend_kernel and the scene decode to (pipeline.h)
     bool accumulate, mapped, compact;
     NeeArgs nee_args; EnvArgs env_args; LensArgs lens_args; // the blocks of a pipe.nee / pipe.env / pipe.lens frame
+    SphArgs sph_args;           // ... and of a pipe.sph frame, whose nee_args holds the joint table (docs/SPEC.md §7.1)
     bool sky;                   // the frame has sky pixels (scene_pixels) and resolves them at its start instead of tracing their paths
     Accumulation::Key sums_key; // what the sums hold once this frame completes
     size_t q_entries; uint64_t total_spp, allocs_before;
@@ -241,6 +242,22 @@ pt_status FrameTemplate::build_if_differs(pt_context *c, hipStream_t q, Key key,
     return PT_OK;
 }
 
+// What a frame's flags, the context's tuning and the scene decode to (pipeline.h), and what its sums will hold: one statement each for
+// plan_frame and for the refusals pt_render makes before the frame is replaced.
+static PipelineDecode decode_frame(const pt_context *c, const pt_scene *s, const pt_render_params *p)
+{
+    return decode_pipeline(p->flags, c->tuning.extend_kernel, s->env.present(), s->has_specular, s->lens.radius > 0.f, s->n_sph_lights != 0u);
+}
+static Accumulation::Key sums_key_of(const pt_render_params *p)
+{
+    return Accumulation::Key{ p->width, p->height, p->rank, p->nranks ? p->nranks : 1u, p->streams ? p->streams : 1u, p->seed,
+                              (p->flags & PT_FLAG_NEXT_EVENT) != 0, (p->flags & PT_FLAG_NEXT_EVENT_SPHERES) != 0 };
+}
+static pt_status other_light_set(pt_context *c)
+{
+    return fail(c, PT_ERR_INVALID_ARGUMENT, "PT_FLAG_ACCUMULATE: the sums so far were made %s PT_FLAG_NEXT_EVENT_SPHERES", c->sums.sphere_lights() ? "with" : "without");
+}
+
 // Plan: validate, derive the frame's geometry and decoded flags, allocate what the frame uses, fill PathState and FrameParams
 static pt_status plan_frame(pt_context *c, const pt_scene *s, const pt_render_params *p, const pt_tile_layout &lay, Frame &f)
 {
@@ -262,7 +279,7 @@ static pt_status plan_frame(pt_context *c, const pt_scene *s, const pt_render_pa
     const uint32_t groups = (f.n_slots + (1u << kShardGroupShift) - 1u) >> kShardGroupShift, shard_cap = ((groups + kShards - 1) / kShards) << kShardGroupShift;
     f.shard_cap = shard_cap; f.q_entries = (size_t)kShards * shard_cap;
     f.samples_per_stream = (p->spp + f.streams - 1u) / f.streams;
-    const PipelineDecode d = decode_pipeline(p->flags, t.extend_kernel, s->env.present(), s->has_specular, s->lens.radius > 0.f);
+    const PipelineDecode d = decode_frame(c, s, p);
     if (d.status != PT_OK) return fail(c, d.status, "%s", d.message);
     const Pipeline &pipe = f.pipe = d.pipeline;
     if (pipe.lens && !lens_basis(s->ds.cam, s->lens, f.lens_args))
@@ -285,13 +302,14 @@ static pt_status plan_frame(pt_context *c, const pt_scene *s, const pt_render_pa
     // progressive accumulation (the reference re-renders every frame, App.cs:39-42; this is its converging analogue):
     // keep the stream partials of the previous call(s) and divide by the total number of samples at the end
     f.accumulate = (p->flags & PT_FLAG_ACCUMULATE) != 0;
-    f.sums_key = Accumulation::Key{ p->width, p->height, p->rank, f.nranks, f.streams, p->seed, pipe.nee };
+    f.sums_key = sums_key_of(p);
     if (f.accumulate)
         switch (c->sums.continues(f.sums_key, p->sample_offset)) {
         case Accumulation::Refusal::other_frame:
             return fail(c, PT_ERR_INVALID_ARGUMENT, "PT_FLAG_ACCUMULATE needs a previous frame with the same size, rank, nranks, streams and seed");
         case Accumulation::Refusal::other_estimator:
             return fail(c, PT_ERR_INVALID_ARGUMENT, "PT_FLAG_ACCUMULATE: the sums so far were made %s PT_FLAG_NEXT_EVENT", c->sums.next_event() ? "with" : "without");
+        case Accumulation::Refusal::other_light_set: return other_light_set(c);
         case Accumulation::Refusal::wrong_offset:
             return fail(c, PT_ERR_INVALID_ARGUMENT, "PT_FLAG_ACCUMULATE: sample_offset must be %llu (samples so far)", (unsigned long long)c->sums.samples());
         case Accumulation::Refusal::none: break;
@@ -309,9 +327,13 @@ static pt_status plan_frame(pt_context *c, const pt_scene *s, const pt_render_pa
     if (pipe.nee) {
         HIP_TRY(c, c->nee_ext.ensure(f.n_slots)); HIP_TRY(c, c->nee_rad.ensure(f.n_slots));
         f.nee_args = NeeArgs{ s->d_lights.p, s->d_cdf.p, s->d_pa.p, s->n_lights, c->nee_ext.p, c->nee_rad.p };
+        if (pipe.sph) { // §7.1: "the table" is the joint table
+            f.nee_args = NeeArgs{ s->d_jlights.p, s->d_jcdf.p, s->d_jpa.p, s->n_lights + s->n_sph_lights, c->nee_ext.p, c->nee_rad.p };
+            f.sph_args = SphArgs{ s->d_sph_pmf.p, s->n_lights, 0u };
+        }
     }
     // §11: a light sample picks one of the two kinds of light with probability 1/2 when the frame has both
-    if (pipe.env) f.env_args = s->env.args(pipe.nee && s->env.lit() && s->n_lights ? 0.5f : 1.0f);
+    if (pipe.env) f.env_args = s->env.args(pipe.nee && s->env.lit() && (s->n_lights || pipe.sph) ? 0.5f : 1.0f);
     if (f.nranks == 1) HIP_TRY(c, c->out.resize(p->width, p->height));
     PathState &ps = f.ps;
     ps.ray_o = c->ray_o.p; ps.ray_d = c->ray_d.p; ps.thr = c->thr.p; ps.sd = c->sd.p; ps.acc = c->acc.p; ps.q_ext[0] = c->q_ext0.p; ps.q_ext[1] = c->q_ext1.p;
@@ -394,7 +416,8 @@ static pt_status run_loops(pt_context *c, const pt_scene *s, const pt_render_par
             if (probing) HIP_TRY(c, hipEventRecord(c->ev_probe[(it - 2u) * 2u], L.stream));
             const ExtendLaunch launch{ it, L.bound, kernel, pipe.fuse(), pipe.count, f.compact, f.packed_chunk,
                                        c->tuning.bounces ? c->tuning.bounces : x.bounces(g, it, kernel, f.default_bounces),
-                                       pipe.nee ? &f.nee_args : nullptr, pipe.env ? &f.env_args : nullptr, pipe.lens ? &f.lens_args : nullptr };
+                                       pipe.nee ? &f.nee_args : nullptr, pipe.env ? &f.env_args : nullptr, pipe.lens ? &f.lens_args : nullptr,
+                                       pipe.sph ? &f.sph_args : nullptr };
             HIP_TRY(c, launch_extend(L.stream, s->ds, pg, f.fp, launch));
             if (pipe.profile) HIP_TRY(c, hipEventRecord(e1, L.stream));
             if (pipe.bucket) {
@@ -526,6 +549,16 @@ extern "C" pt_status pt_render(pt_context *c, const pt_scene *s, const pt_render
         return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_render through a lens: the lens (radius %g, focus_distance %g) is outside its domain for this camera and a %u x %u image "
                     "(docs/SPEC.md 3.1: focus_distance * |v| + radius too large, focus_distance * forward's part off the plane of right and up too small, or no such plane)",
                     (double)s->lens.radius, (double)s->lens.focus_distance, p->width, p->height);
+    // So are the refusals of sphere lights (docs/SPEC.md §7.1), by plan_frame's own two rules (which it then finds met): what a frame with
+    // PT_FLAG_NEXT_EVENT_SPHERES decodes to — the bit without PT_FLAG_NEXT_EVENT, a pipeline that next-event estimation refuses — and
+    // PT_FLAG_ACCUMULATE over sums that differ from this frame's in the setting of the bit alone.
+    if (c && s && p && p->mode == PT_PATH_TRACE && s->ctx == c && s->committed) {
+        if (p->flags & PT_FLAG_NEXT_EVENT_SPHERES) {
+            const PipelineDecode d = decode_frame(c, s, p);
+            if (d.status != PT_OK) return fail(c, d.status, "%s", d.message);
+        }
+        if ((p->flags & PT_FLAG_ACCUMULATE) && c->sums.continues(sums_key_of(p), p->sample_offset) == Accumulation::Refusal::other_light_set) return other_light_set(c);
+    }
     const pt_status st = drained_on_failure(c, [&] { return render_frame(c, s, p, stats); });
     if (st != PT_OK && c) { c->sums.begin(); c->out.lost(); } // nothing of this frame survives the call
     return st;

@@ -133,6 +133,20 @@ PT_DEV const LensArgs &lens_args()
 }
 template <bool NEE, bool ENV> PT_DEV const ExtArgs &ext_of(const ExtArgsT<NEE, ENV> &t) { return t.x; }
 template <bool NEE, bool ENV> PT_DEV const ExtArgs &ext_of(const ExtLensArgsT<NEE, ENV> &t) { return t.a.x; }
+// The sphere-light instantiations k_extend<L, false, FUSE_SPH / FUSE_SPH_LENS, true, ENV> (docs/SPEC.md §7.1): the NEE block of their pinhole
+// or lens form with SphArgs behind it, read through sph_args().
+template <bool ENV, bool LENS> struct ExtSphArgsT { std::conditional_t<LENS, ExtLensArgsT<true, ENV>, ExtArgsT<true, ENV>> a; SphArgs sph; };
+static_assert(__builtin_offsetof(ExtSphArgsT<false, false>, sph) == sizeof(ExtArgsT<true, false>) && __builtin_offsetof(ExtSphArgsT<true, false>, sph) == sizeof(ExtArgsT<true, true>) &&
+              __builtin_offsetof(ExtSphArgsT<false, true>, sph) == sizeof(ExtLensArgsT<true, false>) && __builtin_offsetof(ExtSphArgsT<true, true>, sph) == sizeof(ExtLensArgsT<true, true>) &&
+              __builtin_offsetof(ExtSphArgsT<true, true>, a) == 0, "the sphere block directly behind the others, which stay where every instantiation reads them");
+template <bool ENV, bool LENS>
+PT_DEV const SphArgs &sph_args()
+{
+    auto p = __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return ((const ExtSphArgsT<ENV, LENS> *)p)->sph;
+}
+template <bool ENV, bool LENS> PT_DEV const ExtArgs &ext_of(const ExtSphArgsT<ENV, LENS> &t) { return ext_of(t.a); }
 
 // Slot order. A slot is one (pixel slot, stream) pair; 64 consecutive slots are one 8x8 pixel block of one stream (a
 // wavefront). The K streams of a block are K consecutive 64-slot groups, so that wavefronts that run at the same time
@@ -450,6 +464,10 @@ PT_DEV void path_load(const PathState &ps, uint32_t slot, PathRegs &r)
 // shadow ray brings if it reaches the light wait in NeeArgs::ext / ::rad; only `aux` and `flags` ride along in registers (and in the .w
 // words of ray_o / ray_d between launches).
 enum : uint32_t { NEE_PENDING = 1u, NEE_END = 2u }; // the ray in r.d is a shadow ray; the path ends once it is resolved
+// (sphere lights, docs/SPEC.md §7.1) From this bit on: 1 + the sphere the pending shadow ray goes to, 0 for every other light. What the ray
+// finds of that sphere itself does not block it: from some hundred radii away §4's sphere test places the lamp's surface radii early.
+constexpr uint32_t NEE_LAMP_SHIFT = 8u;
+PT_DEV bool shadow_reached_lamp(uint32_t flags, uint32_t ref, uint32_t n_tris) { return (flags >> NEE_LAMP_SHIFT) != 0u && ref - n_tris + 1u == flags >> NEE_LAMP_SHIFT; }
 struct NeeRegs {
     float aux;      // NEE_PENDING: the shadow ray's tmax; else the Lambert pdf (cos / pi) of the extension ray in r.d, 0 = none
     uint32_t flags;
@@ -476,6 +494,36 @@ PT_DEV uint32_t pick_light(const float *cdf, uint32_t n, float u)
         if (u < cdf[mid]) hi = mid; else lo = mid + 1u;
     }
     return lo;
+}
+// ------------------------------------------------------------------------------------------------ sphere lights (docs/SPEC.md §7.1)
+constexpr float kTwoPi = 6.28318548f; // f32(2 pi)
+// The cone the sphere (centre c, radius r) subtends from o: oc = c - o, d2 = |oc|^2, r2 = r^2 and omc = 1 - cos(theta_max) = sin2 / (1 + cosm),
+// which keeps its bits where 1.0f - cosm has lost them all (a lamp 10^4 radii away: 5e-9). false: o is on or inside the sphere — no
+// light sample from there, and a hit from there keeps weight 1. Both sides of the power heuristic call this with the same floats.
+struct SphCone { V3 oc; float d2, r2, omc; };
+PT_DEV bool sphere_cone(V3 c, float r, V3 o, SphCone &k)
+{
+    k.oc = c - o; k.d2 = dot(k.oc, k.oc); k.r2 = r * r;
+    if (!(k.d2 > k.r2)) return false;
+    const float sin2 = k.r2 / k.d2, cosm = __builtin_sqrtf(fmax_(0.0f, 1.0f - sin2));
+    k.omc = sin2 / (1.0f + cosm);
+    return true;
+}
+// pl of §7.1: pm = pmf_j (* psel), times the cone's uniform solid-angle pdf 1 / (2 pi omc)
+PT_DEV float sphere_cone_pdf(float pm, float omc) { return pm * (1.0f / (kTwoPi * omc)); }
+// The direction of (u1, u2) in that cone, §5's to_world around oc / |oc|, and thit, the distance to the sphere along it — from the cone's
+// own frame: intersecting the world-space ray with the sphere cancels at large d / r and would reject good samples.
+PT_DEV V3 sphere_cone_dir(const SphCone &k, float u1, float u2, float &thit)
+{
+    const float z = u1 * k.omc, cos_t = 1.0f - z, s2 = z * (2.0f - z), sin_t = __builtin_sqrtf(s2);
+    float sn, cs;
+    sincos2pi(u2, sn, cs);
+    const float dist = __builtin_sqrtf(k.d2), inv = 1.0f / dist;
+    const V3 w = v3(k.oc.x * inv, k.oc.y * inv, k.oc.z * inv);
+    V3 tx, ty;
+    basis(w, tx, ty);
+    thit = dist * cos_t - __builtin_sqrtf(fmax_(0.0f, k.r2 - k.d2 * s2));
+    return to_world(v3(sin_t * cs, sin_t * sn, cos_t), tx, ty, w);
 }
 // ------------------------------------------------------------------------------------------------ environment map (docs/SPEC.md §11)
 // decode: a point (u, v) of the map's square [-1, 1]^2 -> its unit direction (the octahedron, lower half folded outwards)
@@ -649,7 +697,9 @@ PT_DEV bool roulette_ends(const FrameParams &fp, uint32_t key, uint32_t depth, u
 // that the two-branch form leaves them (k_extend<.., SHADE_INLINE> 1 to 5 VGPRs more, k_extend_packed<.., SHADE_INLINE> 4).
 // ENV (k_extend<.., ENV> only, docs/SPEC.md §11): a miss looks the map up, and a NEE frame's light sample goes to the map or to a triangle.
 // LENS (k_extend<.., FUSE_LENS, ..> only, docs/SPEC.md §3.1; SHADE_INLINE, so never the shared end): a regenerated sample's ray goes through the lens.
-template <int MODE, bool NEE = false, bool ENV = false, bool LENS = false>
+// SPH (k_extend<.., FUSE_SPH / FUSE_SPH_LENS, true, ..> only, docs/SPEC.md §7.1; SHADE_INLINE): the frame's table is the joint table — a light
+// sample that picks one of its sphere entries draws from the cone, and an emission hit of a sphere light after a Lambert vertex is weighted.
+template <int MODE, bool NEE = false, bool ENV = false, bool LENS = false, bool SPH = false>
 PT_DEV bool shade_one(const DeviceScene &sc, const PathState &ps, const FrameParams &fp, uint32_t slot, PathRegs &r, float t, uint32_t ref,
                       uint32_t b, uint32_t &defer, NeeRegs *nr = nullptr)
 {
@@ -663,6 +713,7 @@ PT_DEV bool shade_one(const DeviceScene &sc, const PathState &ps, const FramePar
     bool touched = false, term = false, alive = false;
     constexpr bool SHARED = !NEE && MODE != SHADE_INLINE;
     static_assert(!LENS || !SHARED, "the shared end makes pinhole rays only");
+    static_assert(!SPH || (NEE && MODE == SHADE_INLINE), "sphere lights: NEE with all-kinds shading");
     bool lambert = false, regen = false; // which lanes take a new direction at the shared end: a Lambert vertex that goes on, a new sample
     auto add = [&](V3 L) {
         touched = true;
@@ -722,6 +773,17 @@ PT_DEV bool shade_one(const DeviceScene &sc, const PathState &ps, const FramePar
                         e = v3(emi.x * w, emi.y * w, emi.z * w);
                     }
                 }
+                if constexpr (SPH) // §7.1: ... or a sphere light (pmf > 0) from outside it; the cone is the one a light sample at the ray's origin has
+                    if (nr->aux > 0.0f && ref >= sc.n_tris) {
+                        float pm = sph_args<ENV, LENS>().pmf[ref - sc.n_tris];
+                        if constexpr (ENV) pm = pm * kernargs<NEE, true>().env.psel;
+                        const float4 s = sc.spheres[ref - sc.n_tris];
+                        SphCone k;
+                        if (pm > 0.0f && sphere_cone(xyz(s), s.w, o, k)) {
+                            const float w = mis_weight(sphere_cone_pdf(pm, k.omc) / nr->aux);
+                            e = v3(emi.x * w, emi.y * w, emi.z * w);
+                        }
+                    }
                 add(e);
             } else add(emi);
         }
@@ -788,6 +850,26 @@ PT_DEV bool shade_one(const DeviceScene &sc, const PathState &ps, const FramePar
                         } else {
                         const float4 *lr = na.lights + (size_t)pick_light(na.cdf, na.n_lights, ENV ? uc : u01(key, 1024u + 3u * bb)) * 4;
                         const float4 l0 = lr[0], l1 = lr[1], l2 = lr[2];
+                        if (SPH && lr >= na.lights + (size_t)sph_args<ENV, LENS>().n_tri * 4) { // §7.1: a sphere light's rows are centre|pmf, (r, 1 + its sphere, -)|Le.r, -|Le.g, -|Le.b
+                            const V3 so = madd(fp.ray_eps, n, P);
+                            SphCone k;
+                            if (sphere_cone(xyz(l0), l1.x, so, k)) {
+                                float thit, pm = l0.w;
+                                const V3 sd = sphere_cone_dir(k, u01(key, 1025u + 3u * bb), u01(key, 1026u + 3u * bb), thit);
+                                if constexpr (ENV) pm = pm * kernargs<NEE, true>().env.psel;
+                                const float cs = dot(n, sd), pl = sphere_cone_pdf(pm, k.omc);
+                                if (cs > 0.0f && pl > 0.0f) {
+                                    const float4 l3 = lr[3];
+                                    const float f = mis_weight_times_q((cs * kInvPi) / pl);
+                                    at(na.rad, slot) = make_float4((ta.x * f) * l1.w, (ta.y * f) * l2.w, (ta.z * f) * l3.w, 0.0f);
+                                    if (!term) at(na.ext, slot) = make_float4(d.x, d.y, d.z, nr->aux);
+                                    nr->flags = NEE_PENDING | (term ? NEE_END : 0u) | (__float_as_uint(l1.y) << NEE_LAMP_SHIFT);
+                                    nr->aux = thit * 0.9999f;
+                                    o = so; d = sd;
+                                    term = false;
+                                }
+                            }
+                        } else {
                         const float su = __builtin_sqrtf(u01(key, 1025u + 3u * bb)), b1 = 1.0f - su, b2 = u01(key, 1026u + 3u * bb) * su;
                         const V3 x = v3(fma_(b2, l2.x, fma_(b1, l1.x, l0.x)), fma_(b2, l2.y, fma_(b1, l1.y, l0.y)), fma_(b2, l2.z, fma_(b1, l1.z, l0.z)));
                         const V3 so = madd(fp.ray_eps, n, P); // the continuation origin of a Lambert vertex (side +1)
@@ -806,6 +888,7 @@ PT_DEV bool shade_one(const DeviceScene &sc, const PathState &ps, const FramePar
                             nr->aux = dist * 0.9999f;
                             o = so; d = sd;
                             term = false;
+                        }
                         }
                         }
                     }
@@ -955,7 +1038,13 @@ PT_DEV void queue_next(const PathState &ps, uint32_t shard, uint32_t cnext, uint
 #ifndef PT_EXT_WAVES_LENS
 #define PT_EXT_WAVES_LENS(L, NEE, ENV) (!(NEE) && ((L) == PT_BVH_WIDTH_8Q || (L) == PT_BVH_WIDTH_8O) ? 6 : PT_EXT_WAVES_FOR(L, SHADE_INLINE, NEE, ENV))
 #endif
-#define PT_EXT_WAVES_K(L, FUSE, NEE, ENV) ((FUSE) == 3 /* FUSE_LENS */ ? PT_EXT_WAVES_LENS(L, NEE, ENV) : PT_EXT_WAVES_FOR(L, FUSE, NEE, ENV))
+// The sphere-light instantiations (docs/SPEC.md §7.1; NEE with all-kinds shading, pinhole and lens) hold the cone sample beside the triangle
+// sample: the budget of the NEE instantiation they are the sphere form of, except BVH8O through a lens without a map, which spills 4 VGPRs at
+// 6 waves and takes 96 VGPRs = 5 (DESIGN.md §9.1 has the table).
+#ifndef PT_EXT_WAVES_SPH
+#define PT_EXT_WAVES_SPH(L, FUSE, ENV) ((FUSE) == 5 /* FUSE_SPH_LENS */ && (L) == PT_BVH_WIDTH_8O && !(ENV) ? 5 : PT_EXT_WAVES_FOR(L, SHADE_INLINE, true, ENV))
+#endif
+#define PT_EXT_WAVES_K(L, FUSE, NEE, ENV) ((FUSE) >= 4 /* FUSE_SPH, FUSE_SPH_LENS */ ? PT_EXT_WAVES_SPH(L, FUSE, ENV) : (FUSE) == 3 /* FUSE_LENS */ ? PT_EXT_WAVES_LENS(L, NEE, ENV) : PT_EXT_WAVES_FOR(L, FUSE, NEE, ENV))
 // A lane's traversal stack: kStackLds entries in its LDS column ([level][lane]: conflict-free), the rest in a global
 // overflow column sized by the builder's exact worst case (pt_bvh_info.stack_need).
 struct StackCtx { int32_t *lds; uint32_t stride, tid, col; }; // col: the lane's column of the overflow area, unique per thread of a launch
@@ -1269,14 +1358,21 @@ PT_DEV Hit trace_ray(const HotScene &g, const StackCtx &stk, V3 o, V3 d, Hit h, 
 // stands for "SHADE_INLINE through a lens". A sixth template argument would have renamed every existing instantiation in the profiles and
 // in tools/isa_diff.py, which compare kernels by name, and a body shared by two entry points does not compile to the code the kernel
 // has today (50 of the existing instantiations then differ).
-constexpr int FUSE_LENS = 3;
+// SPH (a PT_FLAG_NEXT_EVENT_SPHERES frame on a scene with a sphere light, docs/SPEC.md §7.1; NEE, all-kinds shading): shade_one's sphere-light
+// paths, in the same way: k_extend<L, false, FUSE_SPH, true, ENV> and, through a lens, k_extend<L, false, FUSE_SPH_LENS, true, ENV>.
+constexpr int FUSE_LENS = 3, FUSE_SPH = 4, FUSE_SPH_LENS = 5;
+template <int FUSE_, bool NEE, bool ENV>
+using ExtendArgsOf = std::conditional_t<FUSE_ == FUSE_SPH, ExtSphArgsT<ENV, false>, std::conditional_t<FUSE_ == FUSE_SPH_LENS, ExtSphArgsT<ENV, true>,
+                     std::conditional_t<FUSE_ == FUSE_LENS, ExtLensArgsT<NEE, ENV>, ExtArgsT<NEE, ENV>>>>;
 template <int L, bool COUNT, int FUSE_, bool NEE = false, bool ENV = false>
 __global__ void __launch_bounds__(kExtBlock) __attribute__((amdgpu_waves_per_eu(PT_EXT_WAVES_K(L, FUSE_, NEE, ENV), PT_EXT_WAVES_K(L, FUSE_, NEE, ENV))))
-k_extend(std::conditional_t<FUSE_ == FUSE_LENS, ExtLensArgsT<NEE, ENV>, ExtArgsT<NEE, ENV>> args)
+k_extend(ExtendArgsOf<FUSE_, NEE, ENV> args)
 {
-    constexpr bool LENS = FUSE_ == FUSE_LENS;
-    constexpr int FUSE = LENS ? (int)SHADE_INLINE : FUSE_;
+    constexpr bool SPH = FUSE_ == FUSE_SPH || FUSE_ == FUSE_SPH_LENS;
+    constexpr bool LENS = FUSE_ == FUSE_LENS || FUSE_ == FUSE_SPH_LENS;
+    constexpr int FUSE = (LENS || SPH) ? (int)SHADE_INLINE : FUSE_;
     const ExtArgs &a = ext_of(args);
+    static_assert(!SPH || (NEE && !COUNT), "SPH: NEE's, all-kinds fused shading, no visit counters");
     static_assert(!NEE || (FUSE != SHADE_NONE && !COUNT), "NEE: fused shading, no visit counters");
     static_assert(!ENV || (FUSE == SHADE_INLINE && !COUNT), "ENV: all-kinds fused shading, no visit counters");
     static_assert(!LENS || (FUSE == SHADE_INLINE && !COUNT), "LENS: all-kinds fused shading, no visit counters");
@@ -1342,9 +1438,10 @@ k_extend(std::conditional_t<FUSE_ == FUSE_LENS, ExtLensArgsT<NEE, ENV>, ExtArgsT
                 if constexpr (NEE) {
                     nr.aux = __uint_as_float(s_stash[5 * kExtBlock + tid]); nr.flags = s_stash[6 * kExtBlock + tid];
                     if (nr.flags & NEE_PENDING) {
+                        if constexpr (SPH) { if (shadow_reached_lamp(nr.flags, h.ref, g.n_tris)) h.ref = PT_MISS; }
                         if constexpr (LENS) alive = resolve_shadow<true>(c.sc, c.ps, c.fp, kernargs<true, ENV>().nee, slot, r, nr, h.ref == PT_MISS, &lens_args<true, ENV>());
                         else alive = resolve_shadow(c.sc, c.ps, c.fp, kernargs<true, ENV>().nee, slot, r, nr, h.ref == PT_MISS);
-                    } else alive = shade_one<FUSE, true, ENV, LENS>(c.sc, c.ps, c.fp, slot, r, h.t, h.ref, B_LAMBERT, defer, &nr);
+                    } else alive = shade_one<FUSE, true, ENV, LENS, SPH>(c.sc, c.ps, c.fp, slot, r, h.t, h.ref, B_LAMBERT, defer, &nr);
                 } else alive = shade_one<FUSE, false, ENV, LENS>(c.sc, c.ps, c.fp, slot, r, h.t, h.ref, B_LAMBERT, defer);
             }
         }
@@ -2017,11 +2114,21 @@ template <bool ENV> struct GatherNeeArgsT { GatherArgs x; NeeArgs nee; };
 template <> struct GatherNeeArgsT<true> { GatherArgs x; NeeArgs nee; EnvArgs env; };
 template <bool ENV>
 PT_DEV const GatherNeeArgsT<ENV> &gather_nee_args() { return reinterpret_cast<const GatherNeeArgsT<ENV> &>(kernargs<false, false>()); } // read where it is used, like cold()
+// k_gather_paths_nee<L | kGatherSph, ENV> (PT_GATHER_PATHS_SPHERE_LIGHTS on a scene with a sphere light, docs/SPEC.md §7.1): the same block — its
+// NeeArgs the joint table — with SphArgs behind it.
+template <bool ENV> struct GatherSphArgsT { GatherNeeArgsT<ENV> a; SphArgs sph; };
+static_assert(sizeof(GatherSphArgsT<false>) == sizeof(GatherNeeArgsT<false>) + sizeof(SphArgs) && sizeof(GatherSphArgsT<true>) == sizeof(GatherNeeArgsT<true>) + sizeof(SphArgs),
+              "the sphere block directly behind the others");
+template <bool ENV> PT_DEV const GatherArgs &gather_of(const GatherNeeArgsT<ENV> &t) { return t.x; }
+template <bool ENV> PT_DEV const GatherArgs &gather_of(const GatherSphArgsT<ENV> &t) { return t.a.x; }
+template <bool ENV>
+PT_DEV const SphArgs &gather_sph_args() { return reinterpret_cast<const GatherSphArgsT<ENV> &>(kernargs<false, false>()).sph; }
 
 // One light sample of §7 / §11 for a Lambert receiver with normal n whose shadow rays start at so, throughput Tw: dimensions dc (choice),
 // dc + 1, dc + 2 and dv (the map's v) of key. true: a shadow ray (so, sd, tmax) is to be traced, and Lr is what it adds if it arrives.
-template <bool ENV>
-PT_DEV bool gather_light_sample(uint32_t key, uint32_t dc, uint32_t dv, V3 n, V3 so, V3 Tw, V3 &Lr, V3 &sd, float &tmax)
+// SPH: the table is §7.1's joint table, and an entry from SphArgs::n_tri on is a sphere light, sampled by its cone.
+template <bool ENV, bool SPH = false>
+PT_DEV bool gather_light_sample(uint32_t key, uint32_t dc, uint32_t dv, V3 n, V3 so, V3 Tw, V3 &Lr, V3 &sd, float &tmax, uint32_t *lamp = nullptr)
 {
     const NeeArgs &na = gather_nee_args<ENV>().nee;
     float uc = u01(key, dc); // the choice number u' of the strategy taken
@@ -2046,6 +2153,20 @@ PT_DEV bool gather_light_sample(uint32_t key, uint32_t dc, uint32_t dv, V3 n, V3
     }
     const float4 *lr = na.lights + (size_t)pick_light(na.cdf, na.n_lights, uc) * 4;
     const float4 l0 = lr[0], l1 = lr[1], l2 = lr[2];
+    if (SPH && lr >= na.lights + (size_t)gather_sph_args<ENV>().n_tri * 4) { // a sphere light's rows are centre|pmf, (r, 1 + its sphere, -)|Le.r, -|Le.g, -|Le.b
+        SphCone k;
+        if (!sphere_cone(xyz(l0), l1.x, so, k)) return false;
+        float thit, pm = l0.w;
+        const V3 wl = sphere_cone_dir(k, u01(key, dc + 1u), u01(key, dc + 2u), thit);
+        if constexpr (ENV) pm = pm * gather_nee_args<true>().env.psel;
+        const float cs = dot(n, wl), pl = sphere_cone_pdf(pm, k.omc);
+        if (!(cs > 0.0f && pl > 0.0f)) return false;
+        const float4 l3 = lr[3];
+        const float f = mis_weight_times_q((cs * kInvPi) / pl);
+        Lr = v3((Tw.x * f) * l1.w, (Tw.y * f) * l2.w, (Tw.z * f) * l3.w);
+        sd = wl; tmax = thit * 0.9999f; *lamp = __float_as_uint(l1.y); // 1 + the sphere it is: what the shadow ray finds of it does not block it
+        return true;
+    }
     const float su = __builtin_sqrtf(u01(key, dc + 1u)), b1 = 1.0f - su, b2 = u01(key, dc + 2u) * su;
     const V3 x = v3(fma_(b2, l2.x, fma_(b1, l1.x, l0.x)), fma_(b2, l2.y, fma_(b1, l1.y, l0.y)), fma_(b2, l2.z, fma_(b1, l1.z, l0.z)));
     const V3 dl = x - so;
@@ -2064,11 +2185,17 @@ PT_DEV bool gather_light_sample(uint32_t key, uint32_t dc, uint32_t dv, V3 n, V3
 
 // 5 waves: what the rows leave room for (8192 B per wave); no instantiation spills there (tools/resources.py --filter k_gather_paths_nee).
 constexpr int kGatherNeeWaves = 5;
-template <int L, bool ENV>
+// SPH (docs/SPEC.md §7.1): the instantiations k_gather_paths_nee<L | kGatherSph, ENV> are the kernel of layout L with sphere lights — the layout
+// argument carries the bit for the reason k_extend's fuse argument carries FUSE_LENS: the existing instantiations keep their names and
+// their code, which a third template argument or a body shared by two entry points does not leave them.
+constexpr int kGatherSph = 0x100; // (no node layout has this bit: PT_BVH_WIDTH_* are below 128)
+template <int L_, bool ENV>
 __global__ void __launch_bounds__(kExtBlock) __attribute__((amdgpu_waves_per_eu(kGatherNeeWaves, kGatherNeeWaves)))
-k_gather_paths_nee(GatherNeeArgsT<ENV> args)
+k_gather_paths_nee(std::conditional_t<(L_ & kGatherSph) != 0, GatherSphArgsT<ENV>, GatherNeeArgsT<ENV>> args)
 {
-    const GatherArgs &a = args.x;
+    constexpr bool SPH = (L_ & kGatherSph) != 0;
+    constexpr int L = L_ & ~kGatherSph;
+    const GatherArgs &a = gather_of(args);
     const uint32_t n = a.n, K = a.samples;
     const float4 *__restrict__ points = a.points;
     __shared__ int32_t s_stack[kStackLds * kExtBlock];
@@ -2101,6 +2228,10 @@ k_gather_paths_nee(GatherNeeArgsT<ENV> args)
             tmax = __builtin_inff();
             V3 Lr, sd;
             float tm;
+            if constexpr (SPH) { // (the sphere light the ray goes to rides in the flags' row)
+                uint32_t lamp = 0u;
+                if (gather_light_sample<ENV, true>(key, 3072u, 3075u, nn, o, v3(1.0f, 1.0f, 1.0f), Lr, sd, tm, &lamp)) { shadow(Lr, sd, tm, false); rows.row(kFlags) |= lamp << NEE_LAMP_SHIFT; }
+            } else
             if (gather_light_sample<ENV>(key, 3072u, 3075u, nn, o, v3(1.0f, 1.0f, 1.0f), Lr, sd, tm)) shadow(Lr, sd, tm, false);
         };
         bool alive = valid && w.lane < K;
@@ -2115,7 +2246,9 @@ k_gather_paths_nee(GatherNeeArgsT<ENV> args)
                 uint32_t k = kd >> 8;
                 bool term = false;
                 if (flags & kPending) { // ---- a shadow ray: its radiance if it arrived; then the segment that waited, or the path's end
-                    if (h.ref == PT_MISS) { rows.add(0u, rows.get(kRad)); rows.add(1u, rows.get(kRad + 1u)); rows.add(2u, rows.get(kRad + 2u)); }
+                    bool arrived = h.ref == PT_MISS;
+                    if constexpr (SPH) arrived = arrived || shadow_reached_lamp(flags, h.ref, cold().sc.n_tris);
+                    if (arrived) { rows.add(0u, rows.get(kRad)); rows.add(1u, rows.get(kRad + 1u)); rows.add(2u, rows.get(kRad + 2u)); }
                     rows.row(kFlags) = 0u;
                     if (flags & kEnd) term = true;
                     else { d = v3(rows.get(kExt), rows.get(kExt + 1u), rows.get(kExt + 2u)); tmax = __builtin_inff(); }
@@ -2175,6 +2308,17 @@ k_gather_paths_nee(GatherNeeArgsT<ENV> args)
                                     e = v3(emi.x * wb, emi.y * wb, emi.z * wb);
                                 }
                             }
+                            if constexpr (SPH) // §7.1: ... or a sphere light (pmf > 0) from outside it
+                                if (pb > 0.0f && h.ref >= sc.n_tris) {
+                                    float pm = gather_sph_args<ENV>().pmf[h.ref - sc.n_tris];
+                                    if constexpr (ENV) pm = pm * gather_nee_args<true>().env.psel;
+                                    const float4 s = sc.spheres[h.ref - sc.n_tris];
+                                    SphCone k;
+                                    if (pm > 0.0f && sphere_cone(xyz(s), s.w, o, k)) {
+                                        const float wb = mis_weight(sphere_cone_pdf(pm, k.omc) / pb);
+                                        e = v3(emi.x * wb, emi.y * wb, emi.z * wb);
+                                    }
+                                }
                             add(e);
                         }
                         if (depth >= fp.max_depth) term = true;
@@ -2198,9 +2342,14 @@ k_gather_paths_nee(GatherNeeArgsT<ENV> args)
                                 const V3 so = madd(fp.ray_eps, nrm, P); // the continuation origin of a Lambert vertex (side +1)
                                 V3 Lr, sd;
                                 float tm;
-                                if (gather_light_sample<ENV>(key, 1024u + 3u * bb, 2048u + bb, nrm, so, ta, Lr, sd, tm)) {
+                                uint32_t lamp = 0u;
+                                bool sampled;
+                                if constexpr (SPH) sampled = gather_light_sample<ENV, true>(key, 1024u + 3u * bb, 2048u + bb, nrm, so, ta, Lr, sd, tm, &lamp);
+                                else sampled = gather_light_sample<ENV>(key, 1024u + 3u * bb, 2048u + bb, nrm, so, ta, Lr, sd, tm);
+                                if (sampled) {
                                     o = so;
                                     shadow(Lr, sd, tm, term); // the shadow ray goes first; the path's end waits for it too
+                                    if constexpr (SPH) rows.row(kFlags) |= lamp << NEE_LAMP_SHIFT;
                                     pending = true;
                                 }
                             }
@@ -2221,7 +2370,6 @@ k_gather_paths_nee(GatherNeeArgsT<ENV> args)
     }
     if (wave_rays && lane_id() == 0u) atomicAdd(reinterpret_cast<unsigned long long *>(cold().ps.counters + kCntTris), wave_rays);
 }
-
 // ------------------------------------------------------------------------------------------------
 // k_shade<SHADE_QUEUE>  : walks the extend queue of this iteration in the SAME order k_extend did, so ray/throughput/hit
 //                          reads are the coalesced, L2-warm lines k_extend just touched. Misses and Lambert hits are shaded
@@ -2356,34 +2504,36 @@ static bool with_layout(uint32_t width, F &&f)
 template <int... V, typename F>
 static void with_value(int v, F &&f) { (void)((v == V && (f(std::integral_constant<int, V>{}), true)) || ...); }
 
-template <int L, bool COUNT, int FUSE, bool NEE, bool ENV, bool LENS>
-static void launch_k_extend(hipStream_t s, dim3 grid, const ExtArgs &a, const NeeArgs *nee, const EnvArgs *env, const LensArgs *lens) // builds only its case's block
+template <int L, bool COUNT, int FUSE, bool NEE, bool ENV, bool LENS, bool SPH>
+static void launch_k_extend(hipStream_t s, dim3 grid, const ExtArgs &a, const NeeArgs *nee, const EnvArgs *env, const LensArgs *lens, const SphArgs *sph) // builds only its case's block
 {
     ExtArgsT<NEE, ENV> t; t.x = a; if constexpr (NEE) t.nee = *nee; if constexpr (ENV) t.env = *env;
-    if constexpr (LENS) hipLaunchKernelGGL((k_extend<L, COUNT, FUSE_LENS, NEE, ENV>), grid, dim3(kExtBlock), 0, s, ExtLensArgsT<NEE, ENV>{ t, *lens });
+    if constexpr (SPH && LENS) hipLaunchKernelGGL((k_extend<L, COUNT, FUSE_SPH_LENS, true, ENV>), grid, dim3(kExtBlock), 0, s, ExtSphArgsT<ENV, true>{ { t, *lens }, *sph });
+    else if constexpr (SPH) hipLaunchKernelGGL((k_extend<L, COUNT, FUSE_SPH, true, ENV>), grid, dim3(kExtBlock), 0, s, ExtSphArgsT<ENV, false>{ t, *sph });
+    else if constexpr (LENS) hipLaunchKernelGGL((k_extend<L, COUNT, FUSE_LENS, NEE, ENV>), grid, dim3(kExtBlock), 0, s, ExtLensArgsT<NEE, ENV>{ t, *lens });
     else hipLaunchKernelGGL((k_extend<L, COUNT, FUSE, NEE, ENV>), grid, dim3(kExtBlock), 0, s, t);
 }
 
 hipError_t launch_extend(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp, const ExtendLaunch &x)
 {
-    const bool has_nee = x.nee != nullptr, has_env = x.env != nullptr, has_lens = x.lens != nullptr;
-    if (!extend_instantiated(x.kernel, x.fuse, x.count, has_nee, has_env, has_lens)) return hipErrorInvalidValue;
+    const bool has_nee = x.nee != nullptr, has_env = x.env != nullptr, has_lens = x.lens != nullptr, has_sph = x.sph != nullptr;
+    if (!extend_instantiated(x.kernel, x.fuse, x.count, has_nee, has_env, has_lens, has_sph)) return hipErrorInvalidValue;
     const uint32_t chunk = x.kernel == EXT_PACKED ? (x.packed_chunk >= 64u ? x.packed_chunk : 128u) : 0u;
     const uint32_t per_block = x.kernel == EXT_PACKED ? chunk : x.kernel == EXT_POOL ? kPool : kExtBlock;
     const dim3 grid = shard_grid(x.shard_bound ? (x.shard_bound + per_block - 1) / per_block : 1u, ps.shard_count);
     ExtArgs a;
     a.sc = sc; a.ps = ps; a.fp = fp; a.it = x.it; a.compact = x.compact ? 1u : 0u; a.bounces = x.bounces ? x.bounces : 1u; a.chunk = chunk;
-    // layout x kernel x fuse x count x NEE x ENV x LENS, of which extend_instantiated names the ones that exist
+    // layout x kernel x fuse x count x NEE x ENV x LENS x SPH, of which extend_instantiated names the ones that exist
     const bool known = with_layout(sc.bvh_width, [&](auto lc) { with_value<EXT_SIMPLE, EXT_PACKED, EXT_POOL>(x.kernel, [&](auto kc) {
         with_value<SHADE_NONE, SHADE_QUEUE, SHADE_INLINE>(x.fuse, [&](auto fc) { with_value<0, 1>(x.count, [&](auto cc) {
-            with_value<0, 1>(has_nee, [&](auto nc) { with_value<0, 1>(has_env, [&](auto ec) { with_value<0, 1>(has_lens, [&](auto zc) {
+            with_value<0, 1>(has_nee, [&](auto nc) { with_value<0, 1>(has_env, [&](auto ec) { with_value<0, 1>(has_lens, [&](auto zc) { with_value<0, 1>(has_sph, [&](auto sc_) {
                 constexpr int L = decltype(lc)::value, K = decltype(kc)::value, F = decltype(fc)::value;
-                constexpr bool C = decltype(cc)::value != 0, N = decltype(nc)::value != 0, E = decltype(ec)::value != 0, Z = decltype(zc)::value != 0;
-                if constexpr (!extend_instantiated(K, F, C, N, E, Z)) return;
+                constexpr bool C = decltype(cc)::value != 0, N = decltype(nc)::value != 0, E = decltype(ec)::value != 0, Z = decltype(zc)::value != 0, S = decltype(sc_)::value != 0;
+                if constexpr (!extend_instantiated(K, F, C, N, E, Z, S)) return;
                 else if constexpr (K == EXT_POOL) hipLaunchKernelGGL((k_extend_pool<L, C, F>), grid, dim3(64), 0, s, a);
                 else if constexpr (K == EXT_PACKED) hipLaunchKernelGGL((k_extend_packed<L, C, F>), grid, dim3(64), 0, s, a);
-                else launch_k_extend<L, C, F, N, E, Z>(s, grid, a, x.nee, x.env, x.lens);
-            }); }); });
+                else launch_k_extend<L, C, F, N, E, Z, S>(s, grid, a, x.nee, x.env, x.lens, x.sph);
+            }); }); }); });
         }); });
     }); });
     return known ? hipGetLastError() : hipErrorInvalidValue;
@@ -2418,9 +2568,9 @@ uint32_t gather_blocks(uint32_t n, uint32_t samples)
 }
 
 hipError_t launch_gather(hipStream_t s, const DeviceScene &sc, const PathState &ps, const float4 *points, float4 *out, uint32_t n, const GatherParams &gp,
-                         const GatherPathParams *pp, const EnvArgs *env, const NeeArgs *nee)
+                         const GatherPathParams *pp, const EnvArgs *env, const NeeArgs *nee, const SphArgs *sph)
 {
-    if (nee && !pp) return hipErrorInvalidValue;
+    if ((nee && !pp) || (sph && !nee)) return hipErrorInvalidValue;
     GatherArgs a{};
     a.sc = sc; a.ps = ps; a.points = points; a.out = out; a.n = n;
     a.samples = gp.samples; a.gshift = gather_group_shift(gp.samples); a.seed = gp.seed;
@@ -2435,6 +2585,8 @@ hipError_t launch_gather(hipStream_t s, const DeviceScene &sc, const PathState &
         if constexpr (decltype(pc)::value != 0) {
             if (nee) { // §12.2 on a scene with a light: the light table travels behind GatherArgs, the map behind it
                 GatherNeeArgsT<E> tn; tn.x = a; tn.nee = *nee; if constexpr (E) tn.env = *env;
+                if (sph) hipLaunchKernelGGL((k_gather_paths_nee<L | kGatherSph, E>), grid, dim3(kExtBlock), 0, s, GatherSphArgsT<E>{ tn, *sph }); // §7.1: nee is the joint table
+                else
                 hipLaunchKernelGGL((k_gather_paths_nee<L, E>), grid, dim3(kExtBlock), 0, s, tn);
             } else hipLaunchKernelGGL((k_gather_paths<L, E>), grid, dim3(kExtBlock), 0, s, t);
         }

@@ -27,9 +27,11 @@ enum GenerateMode : uint32_t { GEN_QUEUE = 0, GEN_STATE = 1, GEN_DENSE = 2 };
 // environment map live in the one-ray-per-lane kernel only, fused and without visit counters — a shadow ray's traversal stops at its tmax,
 // which the counters do not describe —, the environment with all-kinds shading whatever the materials; the pooled kernel always shades.
 // The thin lens (docs/SPEC.md §3.1) lives there too, with all-kinds shading, with and without NEE and the environment: 4 instantiations.
-constexpr bool extend_instantiated(int kernel, int fuse, bool count, bool nee, bool env, bool lens = false)
+// Sphere lights (docs/SPEC.md §7.1) are NEE's, with all-kinds shading, with and without the environment and the lens: 4 more.
+constexpr bool extend_instantiated(int kernel, int fuse, bool count, bool nee, bool env, bool lens = false, bool sph = false)
 {
     if (kernel < EXT_SIMPLE || kernel > EXT_POOL || fuse == SHADE_BUCKETS || fuse < SHADE_NONE || fuse > SHADE_INLINE) return false;
+    if (sph) return nee && kernel == EXT_SIMPLE && !count && fuse == SHADE_INLINE;
     if (lens) return kernel == EXT_SIMPLE && !count && fuse == SHADE_INLINE;
     if (env) return kernel == EXT_SIMPLE && !count && fuse == SHADE_INLINE;
     if (nee) return kernel == EXT_SIMPLE && !count && fuse != SHADE_NONE;
@@ -42,8 +44,9 @@ struct Pipeline {
     bool split, bucket;     // k_shade as a second kernel (PT_FLAG_SPLIT_KERNELS); with the specular kinds shaded from buckets (_BUCKET_SPECULAR)
     bool nee;               // PT_FLAG_NEXT_EVENT (docs/SPEC.md §7)
     bool env;               // the scene has an environment map (docs/SPEC.md §11)
-    ShadeMode shade;        // Lambert-only scene: lean code; all kinds with specular materials, and with an environment or a lens (their instantiations shade every kind)
+    ShadeMode shade;        // Lambert-only scene: lean code; all kinds with specular materials, and with an environment, a lens or sphere lights (their instantiations shade every kind)
     bool lens;              // the scene's lens has a radius > 0 (docs/SPEC.md §3.1)
+    bool sph;               // PT_FLAG_NEXT_EVENT_SPHERES on a scene that has a sphere light (docs/SPEC.md §7.1); without one the frame is the NEE frame
 
     // One kernel per iteration by default: every extend kernel shades its own hits. The split pipelines run k_shade behind it.
     constexpr ShadeMode fuse() const { return split ? SHADE_NONE : shade; }
@@ -76,13 +79,18 @@ struct PipelineDecode { pt_status status; const char *message; Pipeline pipeline
 // A frame's PT_FLAG_EXTEND_* beats pt_tuning.extend_kernel (tuned_kernel), which beats the scene's own choice. An environment map and
 // next-event estimation force the one-ray-per-lane kernel, the only one with their instantiations (extend_instantiated), and refuse what
 // asks for another, and so does a lens: the environment first, then the lens, then NEE with another kernel, then NEE with counting.
-constexpr PipelineDecode decode_pipeline(uint32_t flags, uint32_t tuned_kernel, bool has_env, bool has_specular, bool has_lens = false)
+// PT_FLAG_NEXT_EVENT_SPHERES without PT_FLAG_NEXT_EVENT is refused before all of that; with it, it refuses what NEE refuses.
+constexpr PipelineDecode decode_pipeline(uint32_t flags, uint32_t tuned_kernel, bool has_env, bool has_specular, bool has_lens = false,
+                                         bool has_sphere_light = false)
 {
     Pipeline p{};
+    if ((flags & PT_FLAG_NEXT_EVENT_SPHERES) && !(flags & PT_FLAG_NEXT_EVENT))
+        return { PT_ERR_INVALID_ARGUMENT, "PT_FLAG_NEXT_EVENT_SPHERES needs PT_FLAG_NEXT_EVENT", p };
     p.profile = (flags & PT_FLAG_PROFILE_KERNELS) != 0; p.count = (flags & PT_FLAG_COUNT_VISITS) != 0;
     p.bucket = (flags & PT_FLAG_BUCKET_SPECULAR) != 0; p.split = p.bucket || (flags & PT_FLAG_SPLIT_KERNELS) != 0;
     p.nee = (flags & PT_FLAG_NEXT_EVENT) != 0; p.env = has_env; p.lens = has_lens;
-    p.shade = (has_specular || has_env || has_lens) ? SHADE_INLINE : SHADE_QUEUE;
+    p.sph = p.nee && (flags & PT_FLAG_NEXT_EVENT_SPHERES) != 0 && has_sphere_light;
+    p.shade = (has_specular || has_env || has_lens || p.sph) ? SHADE_INLINE : SHADE_QUEUE;
     p.forced = (flags & PT_FLAG_EXTEND_POOL) ? (uint32_t)EXT_POOL : (flags & PT_FLAG_EXTEND_PACKED) ? (uint32_t)EXT_PACKED
                : (flags & PT_FLAG_EXTEND_SIMPLE) ? (uint32_t)EXT_SIMPLE : tuned_kernel;
     const bool other_kernel = p.split || p.forced == (uint32_t)EXT_PACKED || p.forced == (uint32_t)EXT_POOL;

@@ -155,6 +155,17 @@ struct LensArgs {
 };
 static_assert(sizeof(LensArgs) == 32, "LensArgs is 32 bytes");
 
+// Sphere lights (PT_FLAG_NEXT_EVENT_SPHERES / PT_GATHER_PATHS_SPHERE_LIGHTS, docs/SPEC.md §7.1) on a scene that has one. The call's NeeArgs
+// then holds the JOINT table (scene.cpp build_sphere_lights): §7's triangle lights with the joint pa, then the sphere lights, whose 4 rows
+// are centre|pmf, (r, bits of 1 + its sphere index, -)|Le.r, -|Le.g, -|Le.b; NeeArgs::pa is the joint per-triangle pa. This block is what the sphere side adds, at
+// the very end of the arguments of the instantiations that have it (kernels.hip ExtSphArgsT, GatherSphArgsT), for the reason NeeArgs gives.
+struct SphArgs {
+    const float *pmf;      // per sphere of the scene: pmf of the light it is in the joint table, 0 for every other sphere (read on emissive hits only)
+    uint32_t n_tri;        // the joint table's entries [0, n_tri) are triangles, [n_tri, n_lights) spheres
+    uint32_t pad;
+};
+static_assert(sizeof(SphArgs) == 16, "SphArgs is 16 bytes");
+
 struct FrameParams {
     uint32_t width, height, spp, max_depth, rr_start, seed_hashed, sample_offset;
     float ray_eps;
@@ -196,7 +207,7 @@ hipError_t launch_generate(hipStream_t s, const DeviceScene &sc, const PathState
 // to the slot's sum as the traced frame would have. Their rays, one per sample, are the host's to count (frame.cpp finish_frame).
 hipError_t launch_sky_pixels(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp);
 // One launch of an extend kernel. `it` = iteration index of the wavefront loop: queues alternate by it & 1, queue counters rotate by it % 3.
-// (kernel, fuse, count, nee, env, lens) must name an instantiation that exists (pipeline.h extend_instantiated), else hipErrorInvalidValue.
+// (kernel, fuse, count, nee, env, lens, sph) must name an instantiation that exists (pipeline.h extend_instantiated), else hipErrorInvalidValue.
 struct ExtendLaunch {
     uint32_t it, shard_bound;   // shard_bound: upper bound of any shard's queue length for this launch
     ExtendKernel kernel; ShadeMode fuse; bool count, compact; // compact (fused kernels): as for launch_shade
@@ -205,6 +216,7 @@ struct ExtendLaunch {
     const NeeArgs *nee;         // a PT_FLAG_NEXT_EVENT frame's block, else NULL
     const EnvArgs *env;         // the block of a scene with an environment map, else NULL
     const LensArgs *lens;       // the block of a frame through a thin lens (radius > 0), else NULL
+    const SphArgs *sph = nullptr; // the block of a PT_FLAG_NEXT_EVENT_SPHERES frame on a scene with a sphere light (nee: the joint table), else NULL
 };
 hipError_t launch_extend(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp, const ExtendLaunch &x);
 // mode: SHADE_QUEUE, SHADE_BUCKETS or SHADE_INLINE (pipeline.h)
@@ -224,6 +236,7 @@ hipError_t launch_trace(hipStream_t s, const DeviceScene &sc, const PathState &p
 // max_depth (1..255) segments with Russian roulette from rr_start on. The kernel adds the segments it traced to the u64 at kCntTris.
 // nee (NULL, or with pp): PT_GATHER_PATHS_NEXT_EVENT (§12.2) on a scene that has a light: the light table (ext and rad are not used), and
 // with it env->psel and env->lit as a NEE frame sets them. The shadow rays are counted with the segments.
+// sph (NULL, or with nee): PT_GATHER_PATHS_SPHERE_LIGHTS (§7.1) on a scene that has a sphere light; nee is then the joint table.
 struct GatherParams {
     uint32_t samples, seed, point_offset, sample_offset; // samples in 1..4096
     float tmax, ray_eps;                                        // tmax: max_distance, +inf for "unbounded"
@@ -232,7 +245,7 @@ struct GatherPathParams { uint32_t max_depth, rr_start; };
 uint32_t gather_group_shift(uint32_t samples); // log2 of min(64, the power of two >= samples)
 uint32_t gather_blocks(uint32_t n, uint32_t samples);
 hipError_t launch_gather(hipStream_t s, const DeviceScene &sc, const PathState &ps, const float4 *points, float4 *out, uint32_t n, const GatherParams &gp,
-                         const GatherPathParams *pp, const EnvArgs *env, const NeeArgs *nee = nullptr);
+                         const GatherPathParams *pp, const EnvArgs *env, const NeeArgs *nee = nullptr, const SphArgs *sph = nullptr);
 hipError_t launch_reduce_streams(hipStream_t s, const float4 *acc, float4 *tiles, uint32_t slots_per_stream, uint32_t streams);
 hipError_t launch_assemble(hipStream_t s, const float4 *gathered, uint32_t nranks, uint32_t slots_per_rank,
                            uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t n_tiles, float inv_spp,

@@ -93,8 +93,10 @@ static pt_status gather(pt_context *c, const pt_scene *s, const void *points, vo
     const char *fn = paths ? "pt_gather_paths" : "pt_gather";
     if (paths) {
         if (!pp) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_gather_paths: path params is NULL");
-        if (pp->flags & ~(uint32_t)PT_GATHER_PATHS_NEXT_EVENT)
-            return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_gather_paths: unknown path flag bits 0x%x", pp->flags & ~(uint32_t)PT_GATHER_PATHS_NEXT_EVENT);
+        const uint32_t known = PT_GATHER_PATHS_NEXT_EVENT | PT_GATHER_PATHS_SPHERE_LIGHTS;
+        if (pp->flags & ~known) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_gather_paths: unknown path flag bits 0x%x", pp->flags & ~known);
+        if ((pp->flags & PT_GATHER_PATHS_SPHERE_LIGHTS) && !(pp->flags & PT_GATHER_PATHS_NEXT_EVENT))
+            return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_gather_paths: PT_GATHER_PATHS_SPHERE_LIGHTS needs PT_GATHER_PATHS_NEXT_EVENT");
         if (pp->max_depth > 255u) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_gather_paths: max_depth %u is more than 255", pp->max_depth);
     }
     if (!gp) return fail(c, PT_ERR_INVALID_ARGUMENT, "%s: params is NULL", fn);
@@ -137,14 +139,19 @@ static pt_status gather(pt_context *c, const pt_scene *s, const void *points, vo
     }
     // §12.2: a flagged call samples the scene's light set and its map if that is lit; with neither it is the unflagged call, kernel and all
     const bool env_lit = s->env.present() && s->env.lit();
-    const bool nee = paths && (pp->flags & PT_GATHER_PATHS_NEXT_EVENT) && (s->n_lights || env_lit);
-    const NeeArgs na{ s->d_lights.p, s->d_cdf.p, s->d_pa.p, s->n_lights, nullptr, nullptr };
-    const EnvArgs env = s->env.present() ? s->env.args(nee && env_lit && s->n_lights ? 0.5f : 1.0f) : EnvArgs{};
+    // §7.1: with PT_GATHER_PATHS_SPHERE_LIGHTS on a scene that has a sphere light "the table" is the joint table; without one the bit changes nothing
+    const bool sph = paths && (pp->flags & PT_GATHER_PATHS_NEXT_EVENT) && (pp->flags & PT_GATHER_PATHS_SPHERE_LIGHTS) && s->n_sph_lights;
+    const bool nee = paths && (pp->flags & PT_GATHER_PATHS_NEXT_EVENT) && (s->n_lights || env_lit || sph);
+    const NeeArgs na = sph ? NeeArgs{ s->d_jlights.p, s->d_jcdf.p, s->d_jpa.p, s->n_lights + s->n_sph_lights, nullptr, nullptr }
+                           : NeeArgs{ s->d_lights.p, s->d_cdf.p, s->d_pa.p, s->n_lights, nullptr, nullptr };
+    const SphArgs sa{ s->d_sph_pmf.p, s->n_lights, 0u };
+    const EnvArgs env = s->env.present() ? s->env.args(nee && env_lit && na.n_lights ? 0.5f : 1.0f) : EnvArgs{};
     HIP_TRY(c, hipEventRecord(c->query.ev[0], q));
     for (uint64_t first = 0; first < n_points; first += kTraceChunk) { // point_offset + first wraps like the key's own u32 arithmetic
         GatherParams kc = k; kc.point_offset = k.point_offset + (uint32_t)first;
         const uint32_t nc = (uint32_t)std::min(kTraceChunk, n_points - first);
-        HIP_TRY(c, launch_gather(q, s->ds, ps, d_points + 2u * first, d_out + 2u * first, nc, kc, paths ? &kp : nullptr, s->env.present() ? &env : nullptr, nee ? &na : nullptr));
+        HIP_TRY(c, launch_gather(q, s->ds, ps, d_points + 2u * first, d_out + 2u * first, nc, kc, paths ? &kp : nullptr, s->env.present() ? &env : nullptr, nee ? &na : nullptr,
+                                 sph ? &sa : nullptr));
     }
     HIP_TRY(c, hipEventRecord(c->query.ev[1], q));
     if (host) HIP_TRY(c, hipMemcpyAsync(out_rows, d_out, n_points * 32u, hipMemcpyDeviceToHost, q));

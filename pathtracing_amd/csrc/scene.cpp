@@ -195,6 +195,51 @@ std::vector<uint2> sphere_mats(const uint32_t *mat, const float *cxyzr, size_t n
     return mi;
 }
 
+// docs/SPEC.md §7.1: the joint table — the triangle lights build_lights kept (s->light_*), then the scene's sphere lights in sphere order —
+// with one running sum in double, uploaded beside the triangle table. Without a sphere light there is none (n_sph_lights = 0).
+static pt_status build_sphere_lights(pt_context *c, pt_scene *s)
+{
+    const size_t ns = s->sph_mat.size(), nt = s->light_w.size();
+    std::vector<double> w(s->light_w);
+    std::vector<float> rec(s->light_rec), pmf_of(std::max<size_t>(ns, 1), 0.0f);
+    std::vector<uint32_t> sph; // which sphere each sphere light is
+    for (size_t j = 0; j < ns; ++j) {
+        const float *e = s->mats[s->sph_mat[j]].emission, *cr = s->spheres.data() + j * 4;
+        if (e[0] == 0.f && e[1] == 0.f && e[2] == 0.f) continue;
+        const double wj = (6.283185307179586 * ((double)cr[3] * (double)cr[3])) * (((double)e[0] + (double)e[1]) + (double)e[2]);
+        if (!(wj > 0.0)) continue;
+        w.push_back(wj); sph.push_back((uint32_t)j);
+        float lamp; // the bits of 1 + j: which sphere a pending shadow ray goes to
+        const uint32_t lamp_bits = (uint32_t)j + 1u; std::memcpy(&lamp, &lamp_bits, 4);
+        const float r[16] = { cr[0], cr[1], cr[2], 0.f, cr[3], lamp, 0.f, e[0], 0.f, 0.f, 0.f, e[1], 0.f, 0.f, 0.f, e[2] };
+        rec.insert(rec.end(), r, r + 16);
+    }
+    s->n_sph_lights = (uint32_t)sph.size();
+    if (sph.empty() || !c) return PT_OK;
+    const size_t nl = w.size();
+    double total = 0.0, run = 0.0;
+    for (const double wi : w) total += wi;
+    std::vector<float> cdf(nl), jpa(s->pa_span.size(), 0.0f);
+    for (size_t i = 0; i < nl; ++i) {
+        run += w[i]; // the same sums in the same order as above
+        cdf[i] = i + 1 == nl ? 1.0f : (float)(run / total);
+        const float pmf = (float)(w[i] / total);
+        if (i < nt) { rec[i * 16 + 3] = pmf / s->light_area[i]; jpa[s->light_blob[i] - s->cand_lo] = rec[i * 16 + 3]; }
+        else { rec[i * 16 + 3] = pmf; pmf_of[sph[i - nt]] = pmf; }
+    }
+    if (!s->jpa_zeroed) {
+        const size_t nbt = std::max<size_t>(s->tree.n_tris, 1);
+        HIP_TRY(c, s->d_jpa.ensure(nbt)); HIP_TRY(c, hipMemset(s->d_jpa.p, 0, nbt * sizeof(float)));
+        s->jpa_zeroed = true;
+    }
+    HIP_TRY(c, s->d_jlights.ensure(nl * 4)); HIP_TRY(c, s->d_jcdf.ensure(nl)); HIP_TRY(c, s->d_sph_pmf.ensure(pmf_of.size()));
+    HIP_TRY(c, hipMemcpy(s->d_jlights.p, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(s->d_jcdf.p, cdf.data(), nl * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(s->d_sph_pmf.p, pmf_of.data(), pmf_of.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (!jpa.empty()) HIP_TRY(c, hipMemcpy(s->d_jpa.p + s->cand_lo, jpa.data(), jpa.size() * sizeof(float), hipMemcpyHostToDevice));
+    return PT_OK;
+}
+
 // docs/SPEC.md §7: the light set, its f32 CDF and the per-light records from the current vertices of the candidates, uploaded to the
 // scene's device arrays. `verts` holds the triangles from `first` on (9 floats each, in triangle order). Area, normal and pa in the op
 // order of §0 / §7; the weights in double.
@@ -203,6 +248,7 @@ pt_status build_lights(pt_context *c, pt_scene *s, const float *verts, uint32_t 
     std::vector<float> rec, cdf; // 16 floats per light: v0|pa, e1|Le.r, e2|Le.g, n_l|Le.b
     std::vector<double> w;       // area * (e.r + e.g + e.b) per light
     std::vector<uint32_t> cand;  // which candidate each light is
+    std::vector<float> areas;
     double total = 0.0;
     for (size_t k = 0; k < s->light_cand.size(); ++k) {
         const float *v = verts + (size_t)(s->light_cand[k] - first) * 9;
@@ -212,7 +258,7 @@ pt_status build_lights(pt_context *c, pt_scene *s, const float *verts, uint32_t 
         const float *e = s->mats[s->tri_mat[s->light_cand[k]]].emission;
         const double wk = (double)area * ((double)e[0] + (double)e[1] + (double)e[2]);
         if (!(area > 0.f) || !(wk > 0.0)) continue;
-        total += wk; w.push_back(wk); cand.push_back((uint32_t)k);
+        total += wk; w.push_back(wk); cand.push_back((uint32_t)k); areas.push_back(area);
         const float r[16] = { v[0], v[1], v[2], area, e1[0], e1[1], e1[2], e[0], e2[0], e2[1], e2[2], e[1], nl[0], nl[1], nl[2], e[2] };
         rec.insert(rec.end(), r, r + 16);
     }
@@ -228,14 +274,16 @@ pt_status build_lights(pt_context *c, pt_scene *s, const float *verts, uint32_t 
         s->pa_span[s->cand_blob[cand[i]] - s->cand_lo] = pa;
     }
     s->n_lights = (uint32_t)nl;
-    if (!c) return PT_OK;
+    s->light_w = w; s->light_area = areas; s->light_rec = rec; s->light_blob.resize(nl); // §7.1: what the joint table takes from this one
+    for (size_t i = 0; i < nl; ++i) s->light_blob[i] = s->cand_blob[cand[i]];
+    if (!c) return build_sphere_lights(c, s); // (no device copy; the counts stay consistent)
     HIP_TRY(c, s->d_lights.ensure(std::max<size_t>(nl, 1) * 4)); HIP_TRY(c, s->d_cdf.ensure(std::max<size_t>(nl, 1)));
     if (nl) {
         HIP_TRY(c, hipMemcpy(s->d_lights.p, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice));
         HIP_TRY(c, hipMemcpy(s->d_cdf.p, cdf.data(), nl * sizeof(float), hipMemcpyHostToDevice));
     }
     if (!s->pa_span.empty()) HIP_TRY(c, hipMemcpy(s->d_pa.p + s->cand_lo, s->pa_span.data(), s->pa_span.size() * sizeof(float), hipMemcpyHostToDevice));
-    return PT_OK;
+    return build_sphere_lights(c, s);
 }
 
 } // namespace
@@ -436,6 +484,7 @@ static pt_status light_table(pt_scene *s, CommitClock &clock)
     pt_context *c = s->ctx;
     const uint32_t nt = (uint32_t)s->tri_mat.size(), nbt = s->tree.n_tris;
     s->light_cand.clear(); s->cand_blob.clear(); s->pa_span.clear(); s->cand_lo = 0; s->n_lights = 0;
+    s->light_w.clear(); s->light_area.clear(); s->light_rec.clear(); s->light_blob.clear(); s->n_sph_lights = 0; s->jpa_zeroed = false;
     for (uint32_t i = 0; i < nt; ++i) {
         const float *e = s->mats[s->tri_mat[i]].emission;
         if (e[0] != 0.f || e[1] != 0.f || e[2] != 0.f) s->light_cand.push_back(i);
@@ -455,6 +504,9 @@ static pt_status light_table(pt_scene *s, CommitClock &clock)
         s->pa_span.assign(hi - s->cand_lo + 1u, 0.0f);
         const float *verts = nullptr;
         if ((st = s->verts.host(c, verts)) != PT_OK || (st = build_lights(c, s, verts, 0)) != PT_OK) return st;
+    } else { // no triangle can be a light: the joint table is the spheres'
+        const pt_status st = build_sphere_lights(c, s);
+        if (st != PT_OK) return st;
     }
     clock.lap("light table");
     return PT_OK;
@@ -638,7 +690,7 @@ static pt_status update_spheres(pt_scene *s, const float *cxyzr, uint64_t count)
     HIP_TRY(c, hipMemcpyAsync(s->d_sph_mat.p, mi.data(), count * sizeof(uint2), hipMemcpyHostToDevice, q));
     HIP_TRY(c, hipStreamSynchronize(q));
     s->spheres.assign(cxyzr, cxyzr + count * 4);
-    return PT_OK;
+    return build_sphere_lights(c, s); // §7.1: the sphere part of the joint table from the new centres and radii
 }
 
 pt_status pt_scene_update_triangles(pt_scene *s, const void *verts9, uint64_t count, uint32_t flags, pt_stats *stats)

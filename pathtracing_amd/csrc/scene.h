@@ -145,6 +145,17 @@ struct pt_scene {
     uint32_t cand_lo = 0, n_lights = 0;
     ptrt::DevBuf<float4> d_lights;
     ptrt::DevBuf<float> d_cdf, d_pa;
+    // The joint table of docs/SPEC.md §7.1 (build_sphere_lights), beside the one above and only while the scene has a sphere light: the triangle
+    // lights with their joint pa, then the spheres whose material emits and whose 2 pi r^2 (e.r + e.g + e.b) > 0, in sphere order. Made
+    // wherever the table above is made and at every pt_scene_update_spheres, from what build_lights kept of the triangle side.
+    std::vector<double> light_w;         // per triangle light: its weight area * (e.r + e.g + e.b)
+    std::vector<float> light_area;       // ... its area
+    std::vector<float> light_rec;        // ... its 16-float record (with the triangle table's own pa)
+    std::vector<uint32_t> light_blob;    // ... its blob index
+    uint32_t n_sph_lights = 0;           // 0: no joint table; flagged calls are the unflagged ones
+    bool jpa_zeroed = false;             // d_jpa has its size and its zeroes for this commit
+    ptrt::DevBuf<float4> d_jlights;      // n_lights + n_sph_lights records
+    ptrt::DevBuf<float> d_jcdf, d_jpa, d_sph_pmf; // d_jpa: per blob triangle like d_pa; d_sph_pmf: per sphere, 0 for a sphere that is no light
 };
 
 // Not part of include/ptrt.h: the binary tree of build_lbvh_device, read out for the test suite (tests/test_gpu_lbvh.py compares it with a

@@ -134,7 +134,10 @@ def build_bvh_detached(scene, bvh_width=0):
 
 
 def make_params(width, height, spp=1, max_depth=8, rr_start=3, seed=0x5EED0001, mode=N.PT_PATH_TRACE, ray_eps=1e-4,
-                rank=0, nranks=1, flags=0, sample_offset=0, streams=1):
+                rank=0, nranks=1, flags=0, sample_offset=0, streams=1, next_event=False, sphere_lights=False):
+    """next_event / sphere_lights: PT_FLAG_NEXT_EVENT (docs/SPEC.md §7) and, with it, PT_FLAG_NEXT_EVENT_SPHERES (§7.1: the scene's emissive
+    spheres are lights too), or-ed into `flags`."""
+    flags |= (N.PT_FLAG_NEXT_EVENT if next_event else 0) | (N.PT_FLAG_NEXT_EVENT_SPHERES if sphere_lights else 0)
     p = N.pt_render_params()
     p.width, p.height, p.spp, p.max_depth, p.rr_start, p.seed = width, height, spp, max_depth, rr_start, seed
     p.sample_offset, p.mode, p.ray_eps, p.rank, p.nranks, p.tile_size, p.flags = sample_offset, mode, ray_eps, rank, nranks, 0, flags
@@ -328,17 +331,19 @@ class Renderer:
         return self._gather(points, normals, gp, lambda *a: N.lib.pt_gather(*a))
 
     def GatherPaths(self, points, normals, samples=64, seed=0, sample_offset=0, point_offset=0, max_distance=0.0, ray_eps=1e-3,
-                    max_depth=8, rr_start=3, next_event=False):
+                    max_depth=8, rr_start=3, next_event=False, sphere_lights=False):
         """Path-traced gathers (include/ptrt.h pt_gather_paths, docs/SPEC.md §12.1): Gather's points, arguments and results, with every
         sample a whole path of at most `max_depth` segments (Russian roulette from depth `rr_start` on) that starts at the point. E is
         the mean radiance the paths bring — emissive surfaces and bounced light included, so pi * E is a Lambert texel's irradiance in
         a closed, emitter-lit scene too; visibility and bent are Gather's. The pt_stats' rays are the path segments traced.
         next_event (PT_GATHER_PATHS_NEXT_EVENT, §12.2): every sample also samples the scene's lights (emissive triangles, a lit
         environment map) at the point and at its Lambert vertices, with multiple importance sampling — the same expectation with less
-        noise under small lights, and with max_depth = 1 a direct-light bake; rays then counts the shadow rays too."""
+        noise under small lights, and with max_depth = 1 a direct-light bake; rays then counts the shadow rays too.
+        sphere_lights (PT_GATHER_PATHS_SPHERE_LIGHTS, §7.1; needs next_event): the scene's emissive spheres are lights too, sampled by
+        the cone they subtend."""
         gp = N.pt_gather_params(samples=samples, seed=seed, sample_offset=sample_offset, point_offset=point_offset,
                                 max_distance=max_distance, ray_eps=ray_eps, flags=0)
-        pp = N.pt_gather_path_params(max_depth=max_depth, rr_start=rr_start, flags=N.PT_GATHER_PATHS_NEXT_EVENT if next_event else 0)
+        pp = N.pt_gather_path_params(max_depth=max_depth, rr_start=rr_start, flags=(N.PT_GATHER_PATHS_NEXT_EVENT if next_event else 0) | (N.PT_GATHER_PATHS_SPHERE_LIGHTS if sphere_lights else 0))
         return self._gather(points, normals, gp, lambda *a: N.lib.pt_gather_paths(*a[:-1], C.byref(pp), a[-1]))
 
     def _gather(self, points, normals, gp, call):
