@@ -121,6 +121,22 @@ public:
     }
     void clear_lens() { check(pt_scene_set_lens(scene_, nullptr), ctx_); }
     pt_lens lens() const { pt_lens l{}; check(pt_scene_get_lens(scene_, &l), ctx_); return l; }
+    // docs/SPEC.md §13, albedo textures: per-triangle UVs (6 floats per triangle, empty = none), texture `index` (width x height texels of
+    // linear RGB; an empty vector removes it) and one texture index or PT_NO_TEXTURE per material (empty = no binding). All three take
+    // effect with the next commit(). Not there: textured spheres, emission or roughness maps, mip-mapping, textures under a lens or with
+    // sphere lights, textured path gathers.
+    void set_triangle_uvs(const std::vector<float> &uv6) { check(pt_scene_set_triangle_uvs(scene_, uv6.empty() ? nullptr : uv6.data(), uv6.size() / 6), ctx_); }
+    void set_texture(uint32_t index, const std::vector<float> &rgb, uint32_t width, uint32_t height, uint32_t flags = 0)
+    {
+        if (rgb.size() < (size_t)width * height * 3) throw Error(PT_ERR_INVALID_ARGUMENT, "set_texture: fewer than width * height * 3 floats");
+        check(pt_scene_set_texture(scene_, index, rgb.empty() ? nullptr : rgb.data(), width, height, flags), ctx_);
+    }
+    void set_material_textures(const std::vector<uint32_t> &texture_of_material)
+    {
+        check(pt_scene_set_material_textures(scene_, texture_of_material.empty() ? nullptr : texture_of_material.data(), texture_of_material.size()), ctx_);
+    }
+    pt_texture_info texture_info(uint32_t index) const { pt_texture_info i{}; check(pt_scene_texture_info(scene_, index, &i), ctx_); return i; }
+    void commit(uint32_t bvh_width = 0) { check(pt_scene_commit(scene_, bvh_width), ctx_); }
     // docs/SPEC.md §9: reproject the previous call's accumulated image to this frame and blend the last frame in; with `filter` the
     // §8.2 filter then runs over the result (ReadDenoised). Zeros mean the defaults; the context keeps the history between calls.
     pt_stats DenoiseTemporal(uint32_t max_history = 0, uint32_t flags = 0, bool filter = true, uint32_t iterations = 0)
@@ -233,6 +249,11 @@ public:
         r_[0]->Params = Params;
     }
     void set_environment(const std::vector<float> &rgb, uint32_t n) { for (auto &r : r_) r->set_environment(rgb, n); }
+    // docs/SPEC.md §13: the same UVs, texture 0 and binding on every rank's replica of the scene, committed
+    void set_textured(const std::vector<float> &uv6, const std::vector<float> &rgb, uint32_t width, uint32_t height, const std::vector<uint32_t> &texture_of_material)
+    {
+        for (auto &r : r_) { r->set_triangle_uvs(uv6); r->set_texture(0, rgb, width, height); r->set_material_textures(texture_of_material); r->commit(); }
+    }
     void set_lens(float radius, float focus_distance) { for (auto &r : r_) r->set_lens(radius, focus_distance); }
     Renderer &Root() { return *r_[0]; }
     void Dispose()

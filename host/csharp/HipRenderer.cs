@@ -209,6 +209,29 @@ public unsafe class HipRenderer : IDisposable
     }
     public void ClearLens() { Ptrt.Check(Ptrt.pt_scene_set_lens(_scene, null), _ctx); }
 
+    // Albedo textures (docs/SPEC.md §13): per-triangle UVs (six floats per triangle, null removes them), texture `index` (width x height
+    // texels of linear RGB, null removes it; flags 1 = nearest texel) and one texture index or 0xFFFFFFFF per material (null removes the
+    // binding). All three take effect with the next Commit. Not there: textured spheres, emission or roughness maps, mip-mapping,
+    // textures under a lens or with sphere lights, textured path gathers.
+    public void SetTriangleUvs(float[] uv6)
+    {
+        if (uv6 == null) { Ptrt.Check(Ptrt.pt_scene_set_triangle_uvs(_scene, null, 0), _ctx); return; }
+        fixed (float* p = uv6) Ptrt.Check(Ptrt.pt_scene_set_triangle_uvs(_scene, p, (ulong)uv6.Length / 6), _ctx);
+    }
+    public void SetTexture(uint index, float[] rgb, uint width, uint height, uint flags = 0)
+    {
+        if (rgb == null) { Ptrt.Check(Ptrt.pt_scene_set_texture(_scene, index, null, 0, 0, 0), _ctx); return; }
+        if ((ulong)rgb.Length < (ulong)width * height * 3) throw new ArgumentException("SetTexture: fewer than width * height * 3 floats");
+        fixed (float* p = rgb) Ptrt.Check(Ptrt.pt_scene_set_texture(_scene, index, p, width, height, flags), _ctx);
+    }
+    public void SetMaterialTextures(uint[] textureOfMaterial)
+    {
+        if (textureOfMaterial == null) { Ptrt.Check(Ptrt.pt_scene_set_material_textures(_scene, null, 0), _ctx); return; }
+        fixed (uint* p = textureOfMaterial) Ptrt.Check(Ptrt.pt_scene_set_material_textures(_scene, p, (ulong)textureOfMaterial.Length), _ctx);
+    }
+    public PtTextureInfo TextureInfo(uint index) { PtTextureInfo i; Ptrt.Check(Ptrt.pt_scene_texture_info(_scene, index, &i), _ctx); return i; }
+    public void Commit(uint bvhWidth = 0) { Ptrt.Check(Ptrt.pt_scene_commit(_scene, bvhWidth), _ctx); }
+
     // Temporal accumulation (docs/SPEC.md §9), the call of a render-every-frame loop whose camera or geometry moves: reprojects the
     // previous call's accumulated image to this frame, blends the last Render in, and (filter = true) runs Denoise's filter over the
     // result. Zeros mean the defaults. ReadTemporal / ReadHistoryLength / ReadDenoised hold until the next Render; the history itself

@@ -51,6 +51,7 @@ public enum PtBvhWidth : uint { Default = 0, W2 = 2, W4 = 4, W4Q = 68, W8Q = 72,
 [StructLayout(LayoutKind.Sequential)] public struct PtDisplayParams { public uint source; public uint curve; public float exposure; public float white; public float key; public float adapt; public uint trim_low; public uint trim_high; public uint flags; public uint pad; }
 [StructLayout(LayoutKind.Sequential)] public struct PtDisplayInfo { public float exposure; public float metered; public float log_average; public uint adapted; public ulong counted; public ulong used; }
 [StructLayout(LayoutKind.Sequential)] public struct PtEnvironmentInfo { public uint n; public uint lit; public ulong device_bytes; public double total; }
+[StructLayout(LayoutKind.Sequential)] public struct PtTextureInfo { public uint width; public uint height; public uint flags; public uint materials; public ulong device_bytes; }
 [StructLayout(LayoutKind.Sequential)] public unsafe struct PtLens { public float radius; public float focus_distance; public uint flags; public fixed uint pad[5]; }
 [StructLayout(LayoutKind.Sequential)] public struct PtSceneCounts { public ulong n_tris; public ulong n_spheres; public ulong n_mats; }
 
@@ -77,6 +78,10 @@ public static unsafe class Ptrt
     [DllImport(Lib)] public static extern PtStatus pt_scene_environment_read(void* s, float* texels4, float* mcdf, float* ccdf, ulong n_texels);
     [DllImport(Lib)] public static extern PtStatus pt_scene_set_lens(void* s, PtLens* lens);
     [DllImport(Lib)] public static extern PtStatus pt_scene_get_lens(void* s, PtLens* @out);
+    [DllImport(Lib)] public static extern PtStatus pt_scene_set_triangle_uvs(void* s, float* uv6, ulong count);
+    [DllImport(Lib)] public static extern PtStatus pt_scene_set_texture(void* s, uint index, float* rgb, uint width, uint height, uint flags);
+    [DllImport(Lib)] public static extern PtStatus pt_scene_set_material_textures(void* s, uint* texture_of_material, ulong count);
+    [DllImport(Lib)] public static extern PtStatus pt_scene_texture_info(void* s, uint index, PtTextureInfo* @out);
     [DllImport(Lib)] public static extern PtStatus pt_scene_commit(void* s, uint bvh_width);
     [DllImport(Lib)] public static extern PtStatus pt_scene_bvh_info(void* s, PtBvhInfo* info);
     [DllImport(Lib)] public static extern PtStatus pt_scene_bvh_read(void* s, void* nodes, ulong node_bytes, void* tris48, ulong tri_bytes);

@@ -36,7 +36,8 @@ extern "C" {
  * PT_TONE_*, pt_display_read / pt_display_device_ptr / pt_display_info_read / pt_display_histogram_read, then PT_TEMPORAL_MOTION, then
  * pt_scene_set_environment, pt_environment_info and pt_scene_environment_info / pt_scene_environment_read, then pt_gather, pt_gather_params and
  * PT_GATHER_HOST_MEMORY, then pt_lens and pt_scene_set_lens / pt_scene_get_lens, then pt_gather_paths and pt_gather_path_params,
- * then PT_GATHER_PATHS_NEXT_EVENT, then PT_FLAG_NEXT_EVENT_SPHERES and PT_GATHER_PATHS_SPHERE_LIGHTS (additions only: no struct or existing
+ * then PT_GATHER_PATHS_NEXT_EVENT, then PT_FLAG_NEXT_EVENT_SPHERES and PT_GATHER_PATHS_SPHERE_LIGHTS, then pt_scene_set_triangle_uvs,
+ * pt_scene_set_texture, pt_scene_set_material_textures, pt_texture_info and pt_scene_texture_info (additions only: no struct or existing
  * signature changed).
  * Hosts compare pt_abi_version() with the header they were built against. */
 #define PTRT_ABI_VERSION 2
@@ -272,6 +273,34 @@ typedef struct pt_lens {
  * the guide pass of pt_denoise / pt_denoise_temporal (with its reprojection: they keep the pinhole centre ray) and pt_display do not. */
 pt_status pt_scene_set_lens(pt_scene *s, const pt_lens *lens);
 pt_status pt_scene_get_lens(const pt_scene *s, pt_lens *out);   /* radius 0, focus_distance 0 when none is set */
+/* Albedo textures (docs/SPEC.md §13). A scene is TEXTURED when, after pt_scene_commit, it has per-triangle UVs and at least one material
+ * bound to a texture that is set; at a triangle hit of a bound material a PT_PATH_TRACE frame then reads albedo * texel (per component)
+ * wherever it read the albedo: the Lambert weight, the metal and dielectric tint, the T * albedo of a light sample. Emission is not textured,
+ * and a sphere keeps its material's plain albedo. A scene that is not textured renders every frame, gather, guide and blob bit for bit as
+ * without these calls. The three setters behave like pt_scene_set_triangles / _materials: they work on detached scenes, mark the scene
+ * uncommitted and take effect with the next pt_scene_commit, and a refused call keeps what was there. pt_scene_update_triangles keeps the
+ * UVs (they belong to the triangle index). The guide pass of pt_denoise / pt_denoise_temporal writes albedo * texel into g1.rgb.
+ * Textured frames run on the one-ray-per-lane kernel with all-kinds shading (pt_stats.reserved[0] = 1, no kernel probe), with and without
+ * PT_FLAG_NEXT_EVENT and an environment map. PT_ERR_UNSUPPORTED on a textured scene: PT_FLAG_EXTEND_PACKED / _POOL, PT_FLAG_SPLIT_KERNELS /
+ * _BUCKET_SPECULAR, PT_FLAG_COUNT_VISITS, pt_tuning.extend_kernel 2 / 3, a lens of radius > 0, PT_FLAG_NEXT_EVENT_SPHERES on a scene that has
+ * a sphere light, and pt_gather_paths. pt_gather, pt_trace_rays and PT_REFERENCE_SPHERE do not look at textures.
+ * Not there: textured spheres, emission or roughness maps, mip-mapping, textures under a lens or with sphere lights, textured path gathers. */
+#define PT_MAX_TEXTURES 64u
+#define PT_NO_TEXTURE 0xFFFFFFFFu
+enum { PT_TEXTURE_NEAREST = 1u };   /* pt_scene_set_texture flags: the nearest texel instead of the bilinear lookup */
+/* Six floats per triangle, (s, t) at v0, v1, v2, in the order and count of pt_scene_set_triangles. uv6 == NULL && count == 0 removes them.
+ * Every value finite with |x| <= 2^20, else PT_ERR_INVALID_ARGUMENT. A count that differs from the triangle count is refused by
+ * pt_scene_commit (the two setters may come in either order). Wrap is repeat. */
+pt_status pt_scene_set_triangle_uvs(pt_scene *s, const float *uv6, uint64_t count);
+/* Texture `index` < PT_MAX_TEXTURES: width x height texels, row-major (row 0 at t = 0), 3 floats each (linear RGB), 1 <= width, height <= 4096,
+ * every component finite and >= 0. flags: 0 = bilinear, PT_TEXTURE_NEAREST; any other bit is refused. rgb == NULL with width == height == 0
+ * removes the index. */
+pt_status pt_scene_set_texture(pt_scene *s, uint32_t index, const float *rgb, uint32_t width, uint32_t height, uint32_t flags);
+/* One entry per material: a texture index or PT_NO_TEXTURE. NULL, 0 removes the binding. A count other than the material count, or an index
+ * that names no texture that is set, is refused by pt_scene_commit. */
+pt_status pt_scene_set_material_textures(pt_scene *s, const uint32_t *texture_of_material, uint64_t count);
+typedef struct pt_texture_info { uint32_t width, height, flags, materials; uint64_t device_bytes; } pt_texture_info; /* width 0: the index is not set; materials: how many are bound to it; device_bytes: of its texels on the device (0 on a detached scene or before a commit) */
+pt_status pt_scene_texture_info(const pt_scene *s, uint32_t index, pt_texture_info *out);
 /* builds the BVH on the host (binned SAH) and uploads everything; replaces CreateComputePipeline's one-time
  * descriptor/pipeline set-up (Renderer.cs:293-403). bvh_width: PT_BVH_WIDTH_* */
 pt_status pt_scene_commit(pt_scene *s, uint32_t bvh_width);

@@ -46,6 +46,7 @@ PT_COMM_FORCE_RCCL, PT_COMM_COPY_EXCHANGE = 1, 2
 PT_TRACE_OCCLUSION, PT_TRACE_COUNT_VISITS, PT_TRACE_HOST_MEMORY = 1, 2, 4
 PT_UPDATE_HOST_MEMORY = 1
 PT_GATHER_HOST_MEMORY = 1
+PT_MAX_TEXTURES, PT_NO_TEXTURE, PT_TEXTURE_NEAREST = 64, 0xFFFFFFFF, 1  # albedo textures (docs/SPEC.md §13)
 PT_GATHER_PATHS_NEXT_EVENT = 4  # pt_gather_path_params.flags (bits 1 and 2 are unassigned)
 PT_GATHER_PATHS_SPHERE_LIGHTS = 16  # with PT_GATHER_PATHS_NEXT_EVENT: emissive spheres are lights too (bit 8 is unassigned)
 PT_DENOISE_GUIDES_ONLY, PT_DENOISE_NO_EDGE_STOPS = 1, 2
@@ -138,6 +139,10 @@ class pt_lens(C.Structure):
     _fields_ = [("radius", C.c_float), ("focus_distance", C.c_float), ("flags", C.c_uint32), ("pad", C.c_uint32 * 5)]
 
 
+class pt_texture_info(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32), ("materials", C.c_uint32), ("device_bytes", C.c_uint64)]
+
+
 class pt_scene_counts(C.Structure):
     _fields_ = [("n_tris", C.c_uint64), ("n_spheres", C.c_uint64), ("n_mats", C.c_uint64)]
 
@@ -145,7 +150,7 @@ class pt_scene_counts(C.Structure):
 assert C.sizeof(pt_material) == 48 and C.sizeof(pt_camera) == 64 and C.sizeof(pt_render_params) == 64 and C.sizeof(pt_tuning) == 40
 assert C.sizeof(pt_denoise_params) == 32 and C.sizeof(pt_temporal_params) == 32
 assert C.sizeof(pt_display_params) == 40 and C.sizeof(pt_display_info) == 32 and C.sizeof(pt_environment_info) == 24
-assert C.sizeof(pt_gather_params) == 32 and C.sizeof(pt_lens) == 32
+assert C.sizeof(pt_gather_params) == 32 and C.sizeof(pt_lens) == 32 and C.sizeof(pt_texture_info) == 24
 
 _vp, _u32, _u64, _st = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int32
 _P = C.POINTER
@@ -170,6 +175,10 @@ SYMBOLS = {
     "pt_scene_environment_read": (_st, [_vp, _vp, _vp, _vp, _u64]),
     "pt_scene_set_lens": (_st, [_vp, _P(pt_lens)]),
     "pt_scene_get_lens": (_st, [_vp, _P(pt_lens)]),
+    "pt_scene_set_triangle_uvs": (_st, [_vp, _vp, _u64]),
+    "pt_scene_set_texture": (_st, [_vp, _u32, _vp, _u32, _u32, _u32]),
+    "pt_scene_set_material_textures": (_st, [_vp, _vp, _u64]),
+    "pt_scene_texture_info": (_st, [_vp, _u32, _P(pt_texture_info)]),
     "pt_scene_commit": (_st, [_vp, _u32]),
     "pt_scene_bvh_info": (_st, [_vp, _P(pt_bvh_info)]),
     "pt_scene_bvh_read": (_st, [_vp, _vp, _u64, _vp, _u64]),

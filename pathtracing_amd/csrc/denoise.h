@@ -16,7 +16,7 @@ hipError_t launch_guide_index(hipStream_t s, const float4 *tris, uint32_t n_tris
 hipError_t launch_guide_rays(hipStream_t s, const pt_camera &cam, uint32_t w, uint32_t h, float4 *rays);
 // §8.1 step 3: the closest hits {t, prim id, u, v} of those rays -> g0 = (n, t), g1 = (albedo, prim id bits), one plane each.
 hipError_t launch_guide_resolve(hipStream_t s, const DeviceScene &sc, const uint32_t *blob_of, const float4 *rays, const float4 *hits,
-                                uint32_t n, float4 *g0, float4 *g1);
+                                uint32_t n, float4 *g0, float4 *g1, const TexArgs *tex = nullptr); // tex: a textured scene's block (docs/SPEC.md §13: g1.rgb = albedo * texel), else NULL
 
 // §8.2 pass `pass` (step 2^pass) of the filter: src -> dst, both w x h row-major float4. The sigmas are the resolved (non-zero) ones;
 // every inverse scale is clamped into [2^-149, FLT_MAX] (atrous_scale).

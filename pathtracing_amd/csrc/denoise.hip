@@ -4,12 +4,15 @@
 //   k_guide_rays    : the unjittered §3 camera ray of every pixel, as a pt_trace_rays record; kernels.hip's k_trace then finds the hits
 //   k_guide_resolve : {t, prim id} -> g0 = (front-facing normal, t), g1 = (albedo, prim id bits): triangles read the record's shading
 //                     row, spheres the 1/r of sph_mat
+//   k_guide_resolve_tex : the same on a textured scene (docs/SPEC.md §13): g1.rgb = albedo * texel of a triangle hit, the texel looked up
+//                     at the hit record's (u, v); a kernel of its own, so that k_guide_resolve keeps its code
 //   k_atrous<EDGE>  : one filter pass, 64x4 workgroups as k_assemble: a wave covers 64 pixels of one row, so each of a tap's three rows
 //                     (colour, g0, g1) is one coalesced 1 KiB load; the centre pixel's colour and guides stay in registers, one division
 //                     per tap (the four edge-stop denominators multiplied first)
 // Op order follows §8 exactly (explicit fma, -ffp-contract=off, IEEE division): tests/denoise_ref/ restates it bit for bit.
 #include "ptrt_internal.h"
 #include "pt_device.h"
+#include "texture_device.h"
 #include "denoise.h"
 #include <cstring>
 
@@ -68,6 +71,43 @@ __global__ void __launch_bounds__(kBlock) k_guide_resolve(DeviceScene sc, const 
     const float4 m0 = sc.mats[(size_t)mat * 3]; // kind, albedo.rgb
     g0[i] = make_float4(nf.x, nf.y, nf.z, hit.x);
     g1[i] = make_float4(m0.y, m0.z, m0.w, hit.y);
+}
+
+__global__ void __launch_bounds__(kBlock) k_guide_resolve_tex(DeviceScene sc, const uint32_t *__restrict__ blob_of, const float4 *__restrict__ rays,
+                                                              const float4 *__restrict__ hits, uint32_t n, float4 *__restrict__ g0, float4 *__restrict__ g1,
+                                                              TexArgs tex)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const float4 hit = hits[i];
+    const uint32_t id = __float_as_uint(hit.y);
+    if (id == PT_MISS) {
+        g0[i] = make_float4(0.0f, 0.0f, 0.0f, __builtin_inff());
+        g1[i] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(PT_MISS));
+        return;
+    }
+    const V3 d = xyz(rays[2 * (size_t)i + 1]);
+    V3 ng, texel = v3(1.0f, 1.0f, 1.0f);
+    uint32_t mat;
+    if (id < sc.n_tris) {
+        const uint32_t blob = blob_of[id];
+        const float4 row = sc.tris[(size_t)blob * 4 + 3];
+        ng = xyz(row);
+        mat = __float_as_uint(row.w);
+        texel = tex_of_hit(tex, blob, hit.z, hit.w); // §13: (u, v) of the guide ray's hit record
+    } else {
+        const uint32_t j = id - sc.n_tris;
+        const V3 o = xyz(rays[2 * (size_t)i]), c = xyz(sc.spheres[j]);
+        const uint2 sm = sc.sph_mat[j];
+        const float inv_r = __uint_as_float(sm.y);
+        const V3 P = madd(hit.x, d, o);
+        ng = V3{ (P.x - c.x) * inv_r, (P.y - c.y) * inv_r, (P.z - c.z) * inv_r };
+        mat = sm.x;
+    }
+    const V3 nf = dot(ng, d) < 0.0f ? ng : neg(ng);
+    const float4 m0 = sc.mats[(size_t)mat * 3]; // kind, albedo.rgb
+    g0[i] = make_float4(nf.x, nf.y, nf.z, hit.x);
+    g1[i] = make_float4(m0.y * texel.x, m0.z * texel.y, m0.w * texel.z, hit.y);
 }
 
 PT_DEV float edge_d(float x) { return fma_(x, fma_(x, 0.5f, 1.0f), 1.0f); } // ~e^x near 0, no transcendental
@@ -145,9 +185,10 @@ hipError_t launch_guide_rays(hipStream_t s, const pt_camera &cam, uint32_t w, ui
 }
 
 hipError_t launch_guide_resolve(hipStream_t s, const DeviceScene &sc, const uint32_t *blob_of, const float4 *rays, const float4 *hits,
-                                uint32_t n, float4 *g0, float4 *g1)
+                                uint32_t n, float4 *g0, float4 *g1, const TexArgs *tex)
 {
-    hipLaunchKernelGGL(k_guide_resolve, dim3((n + kBlock - 1u) / kBlock), dim3(kBlock), 0, s, sc, blob_of, rays, hits, n, g0, g1);
+    if (tex) hipLaunchKernelGGL(k_guide_resolve_tex, dim3((n + kBlock - 1u) / kBlock), dim3(kBlock), 0, s, sc, blob_of, rays, hits, n, g0, g1, *tex);
+    else hipLaunchKernelGGL(k_guide_resolve, dim3((n + kBlock - 1u) / kBlock), dim3(kBlock), 0, s, sc, blob_of, rays, hits, n, g0, g1);
     return hipGetLastError();
 }
 

@@ -76,7 +76,8 @@ static pt_status guide_pass(pt_context *c, const pt_scene *s, uint32_t passes, f
     float4 *rays = o.dn_work.p;
     HIP_TRY(c, launch_guide_rays(q, s->cam, w, h, rays));
     if ((st = c->query.launch(c, s->ds, ps, rays, o.dn_hits.p, n, false, false)) != PT_OK) return st;
-    HIP_TRY(c, launch_guide_resolve(q, s->ds, s->cache.d_blob_of.p, rays, o.dn_hits.p, (uint32_t)n, g0, g1));
+    const TexArgs tex = s->textures.args(); // docs/SPEC.md §13: on a textured scene g1.rgb = albedo * texel
+    HIP_TRY(c, launch_guide_resolve(q, s->ds, s->cache.d_blob_of.p, rays, o.dn_hits.p, (uint32_t)n, g0, g1, s->textures.textured() ? &tex : nullptr));
     HIP_TRY(c, hipEventRecord(o.ev_denoise[1], q));
     return PT_OK;
 }

@@ -209,6 +209,7 @@ struct Frame {                  // a path-traced frame as plan_frame lays it out
     bool accumulate, mapped, compact;
     NeeArgs nee_args; EnvArgs env_args; LensArgs lens_args; // the blocks of a pipe.nee / pipe.env / pipe.lens frame
     SphArgs sph_args;           // ... and of a pipe.sph frame, whose nee_args holds the joint table (docs/SPEC.md §7.1)
+    TexArgs tex_args;           // ... and of a pipe.tex frame (docs/SPEC.md §13)
     bool sky;                   // the frame has sky pixels (scene_pixels) and resolves them at its start instead of tracing their paths
     Accumulation::Key sums_key; // what the sums hold once this frame completes
     size_t q_entries; uint64_t total_spp, allocs_before;
@@ -246,7 +247,7 @@ pt_status FrameTemplate::build_if_differs(pt_context *c, hipStream_t q, Key key,
 // plan_frame and for the refusals pt_render makes before the frame is replaced.
 static PipelineDecode decode_frame(const pt_context *c, const pt_scene *s, const pt_render_params *p)
 {
-    return decode_pipeline(p->flags, c->tuning.extend_kernel, s->env.present(), s->has_specular, s->lens.radius > 0.f, s->n_sph_lights != 0u);
+    return decode_pipeline(p->flags, c->tuning.extend_kernel, s->env.present(), s->has_specular, s->lens.radius > 0.f, s->n_sph_lights != 0u, s->textures.textured());
 }
 static Accumulation::Key sums_key_of(const pt_render_params *p)
 {
@@ -334,6 +335,7 @@ static pt_status plan_frame(pt_context *c, const pt_scene *s, const pt_render_pa
     }
     // §11: a light sample picks one of the two kinds of light with probability 1/2 when the frame has both
     if (pipe.env) f.env_args = s->env.args(pipe.nee && s->env.lit() && (s->n_lights || pipe.sph) ? 0.5f : 1.0f);
+    if (pipe.tex) f.tex_args = s->textures.args();
     if (f.nranks == 1) HIP_TRY(c, c->out.resize(p->width, p->height));
     PathState &ps = f.ps;
     ps.ray_o = c->ray_o.p; ps.ray_d = c->ray_d.p; ps.thr = c->thr.p; ps.sd = c->sd.p; ps.acc = c->acc.p; ps.q_ext[0] = c->q_ext0.p; ps.q_ext[1] = c->q_ext1.p;
@@ -417,7 +419,7 @@ static pt_status run_loops(pt_context *c, const pt_scene *s, const pt_render_par
             const ExtendLaunch launch{ it, L.bound, kernel, pipe.fuse(), pipe.count, f.compact, f.packed_chunk,
                                        c->tuning.bounces ? c->tuning.bounces : x.bounces(g, it, kernel, f.default_bounces),
                                        pipe.nee ? &f.nee_args : nullptr, pipe.env ? &f.env_args : nullptr, pipe.lens ? &f.lens_args : nullptr,
-                                       pipe.sph ? &f.sph_args : nullptr };
+                                       pipe.sph ? &f.sph_args : nullptr, pipe.tex ? &f.tex_args : nullptr };
             HIP_TRY(c, launch_extend(L.stream, s->ds, pg, f.fp, launch));
             if (pipe.profile) HIP_TRY(c, hipEventRecord(e1, L.stream));
             if (pipe.bucket) {

@@ -32,6 +32,7 @@
 // shard's alive/length ratio says so (want_compact); DESIGN.md §3.
 #include "ptrt_internal.h"
 #include "pt_device.h"
+#include "texture_device.h"
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
@@ -147,6 +148,20 @@ PT_DEV const SphArgs &sph_args()
     return ((const ExtSphArgsT<ENV, LENS> *)p)->sph;
 }
 template <bool ENV, bool LENS> PT_DEV const ExtArgs &ext_of(const ExtSphArgsT<ENV, LENS> &t) { return ext_of(t.a); }
+// The textured instantiations k_extend<L, false, FUSE_TEX, NEE, ENV> (docs/SPEC.md §13): the pinhole block of (NEE, ENV) with TexArgs behind
+// it, read through tex_args().
+template <bool NEE, bool ENV> struct ExtTexArgsT { ExtArgsT<NEE, ENV> a; TexArgs tex; };
+static_assert(__builtin_offsetof(ExtTexArgsT<false, false>, tex) == sizeof(ExtArgsT<false, false>) && __builtin_offsetof(ExtTexArgsT<true, false>, tex) == sizeof(ExtArgsT<true, false>) &&
+              __builtin_offsetof(ExtTexArgsT<false, true>, tex) == sizeof(ExtArgsT<false, true>) && __builtin_offsetof(ExtTexArgsT<true, true>, tex) == sizeof(ExtArgsT<true, true>) &&
+              __builtin_offsetof(ExtTexArgsT<true, true>, a) == 0, "the texture block directly behind the others, which stay where every instantiation reads them");
+template <bool NEE, bool ENV>
+PT_DEV const TexArgs &tex_args()
+{
+    auto p = __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return ((const ExtTexArgsT<NEE, ENV> *)p)->tex;
+}
+template <bool NEE, bool ENV> PT_DEV const ExtArgs &ext_of(const ExtTexArgsT<NEE, ENV> &t) { return t.a.x; }
 
 // Slot order. A slot is one (pixel slot, stream) pair; 64 consecutive slots are one 8x8 pixel block of one stream (a
 // wavefront). The K streams of a block are K consecutive 64-slot groups, so that wavefronts that run at the same time
@@ -699,7 +714,10 @@ PT_DEV bool roulette_ends(const FrameParams &fp, uint32_t key, uint32_t depth, u
 // LENS (k_extend<.., FUSE_LENS, ..> only, docs/SPEC.md §3.1; SHADE_INLINE, so never the shared end): a regenerated sample's ray goes through the lens.
 // SPH (k_extend<.., FUSE_SPH / FUSE_SPH_LENS, true, ..> only, docs/SPEC.md §7.1; SHADE_INLINE): the frame's table is the joint table — a light
 // sample that picks one of its sphere entries draws from the cone, and an emission hit of a sphere light after a Lambert vertex is weighted.
-template <int MODE, bool NEE = false, bool ENV = false, bool LENS = false, bool SPH = false>
+// TEX (k_extend<.., FUSE_TEX, ..> only, docs/SPEC.md §13; SHADE_INLINE, pinhole, no sphere lights): the albedo of a triangle hit is albedo * texel.
+// The frame's hit is {t, ref} alone, so (u, v) are recomputed here from rows 0-2 of the record's 64-byte line — the line the traversal has just
+// fetched and whose row 3 this step reads anyway — with §4's expressions (tri_uv, as k_trace does for §4.2).
+template <int MODE, bool NEE = false, bool ENV = false, bool LENS = false, bool SPH = false, bool TEX = false>
 PT_DEV bool shade_one(const DeviceScene &sc, const PathState &ps, const FrameParams &fp, uint32_t slot, PathRegs &r, float t, uint32_t ref,
                       uint32_t b, uint32_t &defer, NeeRegs *nr = nullptr)
 {
@@ -714,6 +732,7 @@ PT_DEV bool shade_one(const DeviceScene &sc, const PathState &ps, const FramePar
     constexpr bool SHARED = !NEE && MODE != SHADE_INLINE;
     static_assert(!LENS || !SHARED, "the shared end makes pinhole rays only");
     static_assert(!SPH || (NEE && MODE == SHADE_INLINE), "sphere lights: NEE with all-kinds shading");
+    static_assert(!TEX || (MODE == SHADE_INLINE && !LENS && !SPH), "textures: all-kinds shading, pinhole, no sphere lights");
     bool lambert = false, regen = false; // which lanes take a new direction at the shared end: a Lambert vertex that goes on, a new sample
     auto add = [&](V3 L) {
         touched = true;
@@ -739,11 +758,18 @@ PT_DEV bool shade_one(const DeviceScene &sc, const PathState &ps, const FramePar
         const V3 P = madd(t, d, o);
         V3 ng;
         uint32_t mat;
+        V3 texel = v3(1.0f, 1.0f, 1.0f); // (TEX) what multiplies the albedo: the texel of a bound triangle, else 1 (exact)
         if (ref < sc.n_tris) {
             const float4 ts = sc.tris[(size_t)ref * 4 + 3]; // normalize(cross(e1,e2)) precomputed at commit, bit-identical; the
                                                             // 4th row of the line k_extend fetched when it tested this triangle
             ng = xyz(ts);
             mat = __float_as_uint(ts.w);
+            if constexpr (TEX) { // §13: issued before the material's rows are looked at, so that the two chains of loads overlap
+                const float4 *tr = sc.tris + (size_t)ref * 4;
+                float u, v;
+                tri_uv(tr[0], tr[1], tr[2], o, d, u, v);
+                texel = tex_of_hit(tex_args<NEE, ENV>(), ref, u, v);
+            }
         } else {
             const uint32_t j = ref - sc.n_tris;
             const float4 s = sc.spheres[j];
@@ -759,7 +785,7 @@ PT_DEV bool shade_one(const DeviceScene &sc, const PathState &ps, const FramePar
         // Both rows are requested before either is looked at: left alone, the compiler sinks the second load behind the test of the
         // first row's kind — one more dependent round trip in a step that already chains hit record -> material
         asm volatile("" : "+v"(m0.x), "+v"(m1.x));
-        const V3 alb = v3(m0.y, m0.z, m0.w), emi = xyz(m1);
+        const V3 alb = TEX ? v3(m0.y * texel.x, m0.z * texel.y, m0.w * texel.z) : v3(m0.y, m0.z, m0.w), emi = xyz(m1);
         const uint32_t kind = __float_as_uint(m0.x);
         if (MODE == SHADE_QUEUE && kind != (uint32_t)PT_LAMBERT) { defer = 1u + kind; return false; } // shaded by k_shade<SHADE_BUCKETS>
         if (emi.x != 0.0f || emi.y != 0.0f || emi.z != 0.0f) {
@@ -1044,7 +1070,13 @@ PT_DEV void queue_next(const PathState &ps, uint32_t shard, uint32_t cnext, uint
 #ifndef PT_EXT_WAVES_SPH
 #define PT_EXT_WAVES_SPH(L, FUSE, ENV) ((FUSE) == 5 /* FUSE_SPH_LENS */ && (L) == PT_BVH_WIDTH_8O && !(ENV) ? 5 : PT_EXT_WAVES_FOR(L, SHADE_INLINE, true, ENV))
 #endif
-#define PT_EXT_WAVES_K(L, FUSE, NEE, ENV) ((FUSE) >= 4 /* FUSE_SPH, FUSE_SPH_LENS */ ? PT_EXT_WAVES_SPH(L, FUSE, ENV) : (FUSE) == 3 /* FUSE_LENS */ ? PT_EXT_WAVES_LENS(L, NEE, ENV) : PT_EXT_WAVES_FOR(L, FUSE, NEE, ENV))
+// The textured instantiations (docs/SPEC.md §13; all-kinds shading only, pinhole) hold the texel chain on top of the shading step: the budget
+// of the instantiation they are the textured form of, except plain BVH8O, which spills 1 VGPR at 7 waves as its untextured form does and
+// takes 80 VGPRs = 6 waves like its lens and environment forms. None of them spills at these budgets (DESIGN.md §17 has the table).
+#ifndef PT_EXT_WAVES_TEX
+#define PT_EXT_WAVES_TEX(L, NEE, ENV) (!(NEE) && !(ENV) && (L) == PT_BVH_WIDTH_8O ? 6 : PT_EXT_WAVES_FOR(L, SHADE_INLINE, NEE, ENV))
+#endif
+#define PT_EXT_WAVES_K(L, FUSE, NEE, ENV) ((FUSE) == 6 /* FUSE_TEX */ ? PT_EXT_WAVES_TEX(L, NEE, ENV) : (FUSE) >= 4 /* FUSE_SPH, FUSE_SPH_LENS */ ? PT_EXT_WAVES_SPH(L, FUSE, ENV) : (FUSE) == 3 /* FUSE_LENS */ ? PT_EXT_WAVES_LENS(L, NEE, ENV) : PT_EXT_WAVES_FOR(L, FUSE, NEE, ENV))
 // A lane's traversal stack: kStackLds entries in its LDS column ([level][lane]: conflict-free), the rest in a global
 // overflow column sized by the builder's exact worst case (pt_bvh_info.stack_need).
 struct StackCtx { int32_t *lds; uint32_t stride, tid, col; }; // col: the lane's column of the overflow area, unique per thread of a launch
@@ -1360,22 +1392,26 @@ PT_DEV Hit trace_ray(const HotScene &g, const StackCtx &stk, V3 o, V3 d, Hit h, 
 // has today (50 of the existing instantiations then differ).
 // SPH (a PT_FLAG_NEXT_EVENT_SPHERES frame on a scene with a sphere light, docs/SPEC.md §7.1; NEE, all-kinds shading): shade_one's sphere-light
 // paths, in the same way: k_extend<L, false, FUSE_SPH, true, ENV> and, through a lens, k_extend<L, false, FUSE_SPH_LENS, true, ENV>.
-constexpr int FUSE_LENS = 3, FUSE_SPH = 4, FUSE_SPH_LENS = 5;
+// TEX (a textured scene, docs/SPEC.md §13; all-kinds shading, pinhole, no sphere lights): shade_one's texel lookup, in the same way:
+// k_extend<L, false, FUSE_TEX, NEE, ENV>.
+constexpr int FUSE_LENS = 3, FUSE_SPH = 4, FUSE_SPH_LENS = 5, FUSE_TEX = 6;
 template <int FUSE_, bool NEE, bool ENV>
-using ExtendArgsOf = std::conditional_t<FUSE_ == FUSE_SPH, ExtSphArgsT<ENV, false>, std::conditional_t<FUSE_ == FUSE_SPH_LENS, ExtSphArgsT<ENV, true>,
-                     std::conditional_t<FUSE_ == FUSE_LENS, ExtLensArgsT<NEE, ENV>, ExtArgsT<NEE, ENV>>>>;
+using ExtendArgsOf = std::conditional_t<FUSE_ == FUSE_TEX, ExtTexArgsT<NEE, ENV>, std::conditional_t<FUSE_ == FUSE_SPH, ExtSphArgsT<ENV, false>, std::conditional_t<FUSE_ == FUSE_SPH_LENS, ExtSphArgsT<ENV, true>,
+                     std::conditional_t<FUSE_ == FUSE_LENS, ExtLensArgsT<NEE, ENV>, ExtArgsT<NEE, ENV>>>>>;
 template <int L, bool COUNT, int FUSE_, bool NEE = false, bool ENV = false>
 __global__ void __launch_bounds__(kExtBlock) __attribute__((amdgpu_waves_per_eu(PT_EXT_WAVES_K(L, FUSE_, NEE, ENV), PT_EXT_WAVES_K(L, FUSE_, NEE, ENV))))
 k_extend(ExtendArgsOf<FUSE_, NEE, ENV> args)
 {
     constexpr bool SPH = FUSE_ == FUSE_SPH || FUSE_ == FUSE_SPH_LENS;
     constexpr bool LENS = FUSE_ == FUSE_LENS || FUSE_ == FUSE_SPH_LENS;
-    constexpr int FUSE = (LENS || SPH) ? (int)SHADE_INLINE : FUSE_;
+    constexpr bool TEX = FUSE_ == FUSE_TEX;
+    constexpr int FUSE = (LENS || SPH || TEX) ? (int)SHADE_INLINE : FUSE_;
     const ExtArgs &a = ext_of(args);
     static_assert(!SPH || (NEE && !COUNT), "SPH: NEE's, all-kinds fused shading, no visit counters");
     static_assert(!NEE || (FUSE != SHADE_NONE && !COUNT), "NEE: fused shading, no visit counters");
     static_assert(!ENV || (FUSE == SHADE_INLINE && !COUNT), "ENV: all-kinds fused shading, no visit counters");
     static_assert(!LENS || (FUSE == SHADE_INLINE && !COUNT), "LENS: all-kinds fused shading, no visit counters");
+    static_assert(!TEX || !COUNT, "TEX: all-kinds fused shading, no visit counters");
     const HotScene g = hot_scene(a.sc);
     const uint32_t it = a.it;
     __shared__ int32_t s_stack[kStackLds * kExtBlock];
@@ -1441,8 +1477,8 @@ k_extend(ExtendArgsOf<FUSE_, NEE, ENV> args)
                         if constexpr (SPH) { if (shadow_reached_lamp(nr.flags, h.ref, g.n_tris)) h.ref = PT_MISS; }
                         if constexpr (LENS) alive = resolve_shadow<true>(c.sc, c.ps, c.fp, kernargs<true, ENV>().nee, slot, r, nr, h.ref == PT_MISS, &lens_args<true, ENV>());
                         else alive = resolve_shadow(c.sc, c.ps, c.fp, kernargs<true, ENV>().nee, slot, r, nr, h.ref == PT_MISS);
-                    } else alive = shade_one<FUSE, true, ENV, LENS, SPH>(c.sc, c.ps, c.fp, slot, r, h.t, h.ref, B_LAMBERT, defer, &nr);
-                } else alive = shade_one<FUSE, false, ENV, LENS>(c.sc, c.ps, c.fp, slot, r, h.t, h.ref, B_LAMBERT, defer);
+                    } else alive = shade_one<FUSE, true, ENV, LENS, SPH, TEX>(c.sc, c.ps, c.fp, slot, r, h.t, h.ref, B_LAMBERT, defer, &nr);
+                } else alive = shade_one<FUSE, false, ENV, LENS, false, TEX>(c.sc, c.ps, c.fp, slot, r, h.t, h.ref, B_LAMBERT, defer);
             }
         }
     }
@@ -2504,11 +2540,12 @@ static bool with_layout(uint32_t width, F &&f)
 template <int... V, typename F>
 static void with_value(int v, F &&f) { (void)((v == V && (f(std::integral_constant<int, V>{}), true)) || ...); }
 
-template <int L, bool COUNT, int FUSE, bool NEE, bool ENV, bool LENS, bool SPH>
-static void launch_k_extend(hipStream_t s, dim3 grid, const ExtArgs &a, const NeeArgs *nee, const EnvArgs *env, const LensArgs *lens, const SphArgs *sph) // builds only its case's block
+template <int L, bool COUNT, int FUSE, bool NEE, bool ENV, bool LENS, bool SPH, bool TEX>
+static void launch_k_extend(hipStream_t s, dim3 grid, const ExtArgs &a, const NeeArgs *nee, const EnvArgs *env, const LensArgs *lens, const SphArgs *sph, const TexArgs *tex) // builds only its case's block
 {
     ExtArgsT<NEE, ENV> t; t.x = a; if constexpr (NEE) t.nee = *nee; if constexpr (ENV) t.env = *env;
-    if constexpr (SPH && LENS) hipLaunchKernelGGL((k_extend<L, COUNT, FUSE_SPH_LENS, true, ENV>), grid, dim3(kExtBlock), 0, s, ExtSphArgsT<ENV, true>{ { t, *lens }, *sph });
+    if constexpr (TEX) hipLaunchKernelGGL((k_extend<L, COUNT, FUSE_TEX, NEE, ENV>), grid, dim3(kExtBlock), 0, s, ExtTexArgsT<NEE, ENV>{ t, *tex });
+    else if constexpr (SPH && LENS) hipLaunchKernelGGL((k_extend<L, COUNT, FUSE_SPH_LENS, true, ENV>), grid, dim3(kExtBlock), 0, s, ExtSphArgsT<ENV, true>{ { t, *lens }, *sph });
     else if constexpr (SPH) hipLaunchKernelGGL((k_extend<L, COUNT, FUSE_SPH, true, ENV>), grid, dim3(kExtBlock), 0, s, ExtSphArgsT<ENV, false>{ t, *sph });
     else if constexpr (LENS) hipLaunchKernelGGL((k_extend<L, COUNT, FUSE_LENS, NEE, ENV>), grid, dim3(kExtBlock), 0, s, ExtLensArgsT<NEE, ENV>{ t, *lens });
     else hipLaunchKernelGGL((k_extend<L, COUNT, FUSE, NEE, ENV>), grid, dim3(kExtBlock), 0, s, t);
@@ -2516,24 +2553,24 @@ static void launch_k_extend(hipStream_t s, dim3 grid, const ExtArgs &a, const Ne
 
 hipError_t launch_extend(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp, const ExtendLaunch &x)
 {
-    const bool has_nee = x.nee != nullptr, has_env = x.env != nullptr, has_lens = x.lens != nullptr, has_sph = x.sph != nullptr;
-    if (!extend_instantiated(x.kernel, x.fuse, x.count, has_nee, has_env, has_lens, has_sph)) return hipErrorInvalidValue;
+    const bool has_nee = x.nee != nullptr, has_env = x.env != nullptr, has_lens = x.lens != nullptr, has_sph = x.sph != nullptr, has_tex = x.tex != nullptr;
+    if (!extend_instantiated(x.kernel, x.fuse, x.count, has_nee, has_env, has_lens, has_sph, has_tex)) return hipErrorInvalidValue;
     const uint32_t chunk = x.kernel == EXT_PACKED ? (x.packed_chunk >= 64u ? x.packed_chunk : 128u) : 0u;
     const uint32_t per_block = x.kernel == EXT_PACKED ? chunk : x.kernel == EXT_POOL ? kPool : kExtBlock;
     const dim3 grid = shard_grid(x.shard_bound ? (x.shard_bound + per_block - 1) / per_block : 1u, ps.shard_count);
     ExtArgs a;
     a.sc = sc; a.ps = ps; a.fp = fp; a.it = x.it; a.compact = x.compact ? 1u : 0u; a.bounces = x.bounces ? x.bounces : 1u; a.chunk = chunk;
-    // layout x kernel x fuse x count x NEE x ENV x LENS x SPH, of which extend_instantiated names the ones that exist
+    // layout x kernel x fuse x count x NEE x ENV x LENS x SPH x TEX, of which extend_instantiated names the ones that exist
     const bool known = with_layout(sc.bvh_width, [&](auto lc) { with_value<EXT_SIMPLE, EXT_PACKED, EXT_POOL>(x.kernel, [&](auto kc) {
         with_value<SHADE_NONE, SHADE_QUEUE, SHADE_INLINE>(x.fuse, [&](auto fc) { with_value<0, 1>(x.count, [&](auto cc) {
-            with_value<0, 1>(has_nee, [&](auto nc) { with_value<0, 1>(has_env, [&](auto ec) { with_value<0, 1>(has_lens, [&](auto zc) { with_value<0, 1>(has_sph, [&](auto sc_) {
+            with_value<0, 1>(has_nee, [&](auto nc) { with_value<0, 1>(has_env, [&](auto ec) { with_value<0, 1>(has_lens, [&](auto zc) { with_value<0, 1>(has_sph, [&](auto sc_) { with_value<0, 1>(has_tex, [&](auto tc) {
                 constexpr int L = decltype(lc)::value, K = decltype(kc)::value, F = decltype(fc)::value;
-                constexpr bool C = decltype(cc)::value != 0, N = decltype(nc)::value != 0, E = decltype(ec)::value != 0, Z = decltype(zc)::value != 0, S = decltype(sc_)::value != 0;
-                if constexpr (!extend_instantiated(K, F, C, N, E, Z, S)) return;
+                constexpr bool C = decltype(cc)::value != 0, N = decltype(nc)::value != 0, E = decltype(ec)::value != 0, Z = decltype(zc)::value != 0, S = decltype(sc_)::value != 0, T = decltype(tc)::value != 0;
+                if constexpr (!extend_instantiated(K, F, C, N, E, Z, S, T)) return;
                 else if constexpr (K == EXT_POOL) hipLaunchKernelGGL((k_extend_pool<L, C, F>), grid, dim3(64), 0, s, a);
                 else if constexpr (K == EXT_PACKED) hipLaunchKernelGGL((k_extend_packed<L, C, F>), grid, dim3(64), 0, s, a);
-                else launch_k_extend<L, C, F, N, E, Z, S>(s, grid, a, x.nee, x.env, x.lens, x.sph);
-            }); }); }); });
+                else launch_k_extend<L, C, F, N, E, Z, S, T>(s, grid, a, x.nee, x.env, x.lens, x.sph, x.tex);
+            }); }); }); }); });
         }); });
     }); });
     return known ? hipGetLastError() : hipErrorInvalidValue;

@@ -28,9 +28,12 @@ enum GenerateMode : uint32_t { GEN_QUEUE = 0, GEN_STATE = 1, GEN_DENSE = 2 };
 // which the counters do not describe —, the environment with all-kinds shading whatever the materials; the pooled kernel always shades.
 // The thin lens (docs/SPEC.md §3.1) lives there too, with all-kinds shading, with and without NEE and the environment: 4 instantiations.
 // Sphere lights (docs/SPEC.md §7.1) are NEE's, with all-kinds shading, with and without the environment and the lens: 4 more.
-constexpr bool extend_instantiated(int kernel, int fuse, bool count, bool nee, bool env, bool lens = false, bool sph = false)
+// Albedo textures (docs/SPEC.md §13) live there as well, with all-kinds shading, with and without NEE and the environment, and neither through
+// a lens nor with sphere lights: 4 more, not 12.
+constexpr bool extend_instantiated(int kernel, int fuse, bool count, bool nee, bool env, bool lens = false, bool sph = false, bool tex = false)
 {
     if (kernel < EXT_SIMPLE || kernel > EXT_POOL || fuse == SHADE_BUCKETS || fuse < SHADE_NONE || fuse > SHADE_INLINE) return false;
+    if (tex) return kernel == EXT_SIMPLE && !count && fuse == SHADE_INLINE && !lens && !sph;
     if (sph) return nee && kernel == EXT_SIMPLE && !count && fuse == SHADE_INLINE;
     if (lens) return kernel == EXT_SIMPLE && !count && fuse == SHADE_INLINE;
     if (env) return kernel == EXT_SIMPLE && !count && fuse == SHADE_INLINE;
@@ -39,7 +42,7 @@ constexpr bool extend_instantiated(int kernel, int fuse, bool count, bool nee, b
 }
 
 struct Pipeline {
-    uint32_t forced;        // ExtendKernel a frame flag, pt_tuning.extend_kernel, NEE, the environment or the lens forces (0 = none: the scene's probed choice)
+    uint32_t forced;        // ExtendKernel a frame flag, pt_tuning.extend_kernel, NEE, the environment, the lens or textures force (0 = none: the scene's probed choice)
     bool profile, count;    // PT_FLAG_PROFILE_KERNELS, PT_FLAG_COUNT_VISITS
     bool split, bucket;     // k_shade as a second kernel (PT_FLAG_SPLIT_KERNELS); with the specular kinds shaded from buckets (_BUCKET_SPECULAR)
     bool nee;               // PT_FLAG_NEXT_EVENT (docs/SPEC.md §7)
@@ -47,6 +50,7 @@ struct Pipeline {
     ShadeMode shade;        // Lambert-only scene: lean code; all kinds with specular materials, and with an environment, a lens or sphere lights (their instantiations shade every kind)
     bool lens;              // the scene's lens has a radius > 0 (docs/SPEC.md §3.1)
     bool sph;               // PT_FLAG_NEXT_EVENT_SPHERES on a scene that has a sphere light (docs/SPEC.md §7.1); without one the frame is the NEE frame
+    bool tex;               // the scene is textured (docs/SPEC.md §13): UVs and a material bound to a texture that is set
 
     // One kernel per iteration by default: every extend kernel shades its own hits. The split pipelines run k_shade behind it.
     constexpr ShadeMode fuse() const { return split ? SHADE_NONE : shade; }
@@ -80,8 +84,10 @@ struct PipelineDecode { pt_status status; const char *message; Pipeline pipeline
 // next-event estimation force the one-ray-per-lane kernel, the only one with their instantiations (extend_instantiated), and refuse what
 // asks for another, and so does a lens: the environment first, then the lens, then NEE with another kernel, then NEE with counting.
 // PT_FLAG_NEXT_EVENT_SPHERES without PT_FLAG_NEXT_EVENT is refused before all of that; with it, it refuses what NEE refuses.
+// A textured scene (has_textures) forces the one-ray-per-lane kernel with all-kinds shading too and refuses, before the others speak, what
+// asks for another kernel or for counting, then a lens, then sphere lights (extend_instantiated: it has neither of those forms).
 constexpr PipelineDecode decode_pipeline(uint32_t flags, uint32_t tuned_kernel, bool has_env, bool has_specular, bool has_lens = false,
-                                         bool has_sphere_light = false)
+                                         bool has_sphere_light = false, bool has_textures = false)
 {
     Pipeline p{};
     if ((flags & PT_FLAG_NEXT_EVENT_SPHERES) && !(flags & PT_FLAG_NEXT_EVENT))
@@ -90,10 +96,18 @@ constexpr PipelineDecode decode_pipeline(uint32_t flags, uint32_t tuned_kernel, 
     p.bucket = (flags & PT_FLAG_BUCKET_SPECULAR) != 0; p.split = p.bucket || (flags & PT_FLAG_SPLIT_KERNELS) != 0;
     p.nee = (flags & PT_FLAG_NEXT_EVENT) != 0; p.env = has_env; p.lens = has_lens;
     p.sph = p.nee && (flags & PT_FLAG_NEXT_EVENT_SPHERES) != 0 && has_sphere_light;
-    p.shade = (has_specular || has_env || has_lens || p.sph) ? SHADE_INLINE : SHADE_QUEUE;
+    p.tex = has_textures;
+    p.shade = (has_specular || has_env || has_lens || p.sph || p.tex) ? SHADE_INLINE : SHADE_QUEUE;
     p.forced = (flags & PT_FLAG_EXTEND_POOL) ? (uint32_t)EXT_POOL : (flags & PT_FLAG_EXTEND_PACKED) ? (uint32_t)EXT_PACKED
                : (flags & PT_FLAG_EXTEND_SIMPLE) ? (uint32_t)EXT_SIMPLE : tuned_kernel;
     const bool other_kernel = p.split || p.forced == (uint32_t)EXT_PACKED || p.forced == (uint32_t)EXT_POOL;
+    if (p.tex && (other_kernel || p.count))
+        return { PT_ERR_UNSUPPORTED, "a textured scene (docs/SPEC.md §13) renders on the one-ray-per-lane kernel only: not with PT_FLAG_EXTEND_PACKED, "
+                                     "PT_FLAG_EXTEND_POOL, PT_FLAG_SPLIT_KERNELS, PT_FLAG_BUCKET_SPECULAR, PT_FLAG_COUNT_VISITS or pt_tuning.extend_kernel 2 / 3", p };
+    if (p.tex && p.lens)
+        return { PT_ERR_UNSUPPORTED, "a textured scene does not render through a lens (pt_scene_set_lens, radius > 0): remove the lens or the textures", p };
+    if (p.tex && p.sph)
+        return { PT_ERR_UNSUPPORTED, "a textured scene with a sphere light does not render with PT_FLAG_NEXT_EVENT_SPHERES", p };
     if (p.env && (other_kernel || p.count))
         return { PT_ERR_UNSUPPORTED, "a scene with an environment map renders on the one-ray-per-lane kernel only: not with PT_FLAG_EXTEND_PACKED, "
                                      "PT_FLAG_EXTEND_POOL, PT_FLAG_SPLIT_KERNELS, PT_FLAG_BUCKET_SPECULAR, PT_FLAG_COUNT_VISITS or pt_tuning.extend_kernel 2 / 3", p };
@@ -104,7 +118,7 @@ constexpr PipelineDecode decode_pipeline(uint32_t flags, uint32_t tuned_kernel, 
         return { PT_ERR_UNSUPPORTED, "PT_FLAG_NEXT_EVENT runs on the one-ray-per-lane kernel only: not with PT_FLAG_EXTEND_PACKED, "
                                      "PT_FLAG_EXTEND_POOL, PT_FLAG_SPLIT_KERNELS, PT_FLAG_BUCKET_SPECULAR or pt_tuning.extend_kernel 2 / 3", p };
     if (p.nee && p.count) return { PT_ERR_UNSUPPORTED, "PT_FLAG_NEXT_EVENT does not count visits (PT_FLAG_COUNT_VISITS)", p };
-    if (p.env || p.nee || p.lens) p.forced = EXT_SIMPLE;
+    if (p.env || p.nee || p.lens || p.tex) p.forced = EXT_SIMPLE;
     return { PT_OK, nullptr, p };
 }
 

@@ -166,6 +166,23 @@ struct SphArgs {
 };
 static_assert(sizeof(SphArgs) == 16, "SphArgs is 16 bytes");
 
+// Albedo textures (docs/SPEC.md §13) of a textured scene, as scene.cpp's SceneTextures builds them at commit. A block of its own at the very
+// end of the arguments of the instantiations that have it (kernels.hip ExtTexArgsT; denoise.hip k_guide_resolve_tex takes it as a last
+// parameter), not fields of DeviceScene or PathState, for the reason NeeArgs gives: those two sit at the front of every extend kernel's
+// kernarg segment, and a field more would move every offset behind it in kernels that never see a texture.
+// uv: two rows per BLOB triangle, {s0, t0, s1, t1}, {s2, t2, bits of the descriptor index of the triangle's material or PT_NO_TEXTURE, 0}:
+// the material is resolved to its texture at commit, so the chain hit -> uv rows -> descriptor -> texels runs beside hit -> shading row ->
+// material instead of behind it. desc: one row per texture that is set and bound, {first texel, width, height, flags}. texels: every such
+// texture's width * height float4 {r, g, b, 0} in one allocation.
+struct TexArgs {
+    const float4 *uv;
+    const uint4 *desc;
+    const float4 *texels;
+    uint32_t n_desc;       // rows of desc (a descriptor index in uv is below it, or PT_NO_TEXTURE)
+    uint32_t pad;
+};
+static_assert(sizeof(TexArgs) == 32, "TexArgs is 32 bytes");
+
 struct FrameParams {
     uint32_t width, height, spp, max_depth, rr_start, seed_hashed, sample_offset;
     float ray_eps;
@@ -207,7 +224,7 @@ hipError_t launch_generate(hipStream_t s, const DeviceScene &sc, const PathState
 // to the slot's sum as the traced frame would have. Their rays, one per sample, are the host's to count (frame.cpp finish_frame).
 hipError_t launch_sky_pixels(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp);
 // One launch of an extend kernel. `it` = iteration index of the wavefront loop: queues alternate by it & 1, queue counters rotate by it % 3.
-// (kernel, fuse, count, nee, env, lens, sph) must name an instantiation that exists (pipeline.h extend_instantiated), else hipErrorInvalidValue.
+// (kernel, fuse, count, nee, env, lens, sph, tex) must name an instantiation that exists (pipeline.h extend_instantiated), else hipErrorInvalidValue.
 struct ExtendLaunch {
     uint32_t it, shard_bound;   // shard_bound: upper bound of any shard's queue length for this launch
     ExtendKernel kernel; ShadeMode fuse; bool count, compact; // compact (fused kernels): as for launch_shade
@@ -217,6 +234,7 @@ struct ExtendLaunch {
     const EnvArgs *env;         // the block of a scene with an environment map, else NULL
     const LensArgs *lens;       // the block of a frame through a thin lens (radius > 0), else NULL
     const SphArgs *sph = nullptr; // the block of a PT_FLAG_NEXT_EVENT_SPHERES frame on a scene with a sphere light (nee: the joint table), else NULL
+    const TexArgs *tex = nullptr; // the block of a textured scene (docs/SPEC.md §13), else NULL
 };
 hipError_t launch_extend(hipStream_t s, const DeviceScene &sc, const PathState &ps, const FrameParams &fp, const ExtendLaunch &x);
 // mode: SHADE_QUEUE, SHADE_BUCKETS or SHADE_INLINE (pipeline.h)

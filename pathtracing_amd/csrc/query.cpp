@@ -111,6 +111,8 @@ static pt_status gather(pt_context *c, const pt_scene *s, const void *points, vo
         return fail(c, PT_ERR_INVALID_ARGUMENT, "%s: points and out must be %u-byte aligned", fn, (unsigned)align + 1u);
     if (s->ctx != c) return fail(c, PT_ERR_INVALID_ARGUMENT, "%s: scene belongs to another context", fn);
     if (!s->committed) return fail(c, PT_ERR_NOT_COMMITTED, "scene not committed");
+    // docs/SPEC.md §13: a bake that ignored the textures would be wrong, and k_gather_paths has no textured form (pt_gather reads no albedo)
+    if (paths && s->textures.textured()) return fail(c, PT_ERR_UNSUPPORTED, "pt_gather_paths: the scene is textured (pt_scene_set_material_textures); path gathers do not look textures up");
     if (n_points >> 32) return fail(c, PT_ERR_INVALID_ARGUMENT, "%s: n_points %llu is not a batch size", fn, (unsigned long long)n_points);
     pt_stats res{};
     res.paths = n_points;

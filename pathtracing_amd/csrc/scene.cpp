@@ -174,6 +174,79 @@ pt_status SceneVertices::device(pt_context *c, const float *&verts9) const
     return PT_OK;
 }
 
+pt_status SceneTextures::check(pt_context *c, size_t n_tris, size_t n_mats) const
+{
+    if (have_uvs && uvs.size() != n_tris * 6)
+        return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_scene_set_triangle_uvs gave %llu triangles, the scene has %llu", (unsigned long long)(uvs.size() / 6), (unsigned long long)n_tris);
+    if (have_binding) {
+        if (of_material.size() != n_mats)
+            return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_scene_set_material_textures gave %llu materials, the scene has %llu", (unsigned long long)of_material.size(), (unsigned long long)n_mats);
+        for (size_t m = 0; m < n_mats; ++m) {
+            const uint32_t t = of_material[m];
+            if (t != PT_NO_TEXTURE && (t >= PT_MAX_TEXTURES || tex[t].width == 0))
+                return fail(c, PT_ERR_INVALID_ARGUMENT, "material %llu is bound to texture %u, which is not set", (unsigned long long)m, t);
+        }
+    }
+    return PT_OK;
+}
+
+uint32_t SceneTextures::bound_materials(uint32_t index) const
+{
+    uint32_t n = 0;
+    if (have_binding) for (const uint32_t t : of_material) n += t == index ? 1u : 0u;
+    return n;
+}
+
+pt_status SceneTextures::commit(pt_context *c, const std::vector<uint32_t> &tri_mat, const CommittedTree &tree)
+{
+    textured_ = false; n_desc = 0;
+    for (uint64_t &b : dev_bytes) b = 0;
+    // the textures some material is bound to, in index order: descriptor `desc_of[t]`
+    uint32_t desc_of[PT_MAX_TEXTURES];
+    std::vector<uint32_t> used;
+    for (uint32_t t = 0; t < PT_MAX_TEXTURES; ++t) {
+        desc_of[t] = PT_NO_TEXTURE;
+        if (tex[t].width && bound_materials(t)) { desc_of[t] = (uint32_t)used.size(); used.push_back(t); }
+    }
+    if (!have_uvs || tri_mat.empty() || used.empty()) return PT_OK; // not textured: no kernel of §13 runs, nothing is uploaded
+    textured_ = true;
+    if (!c) return PT_OK;                                           // detached scene: host side only
+    std::vector<uint32_t> ids;
+    const pt_status st = tree.ids(c, ids);
+    if (st != PT_OK) return st;
+    // UV rows in blob order, the triangle's material resolved to its descriptor
+    std::vector<float> rows(ids.size() * 8);
+    for (size_t j = 0; j < ids.size(); ++j) {
+        const uint32_t id = ids[j] < tri_mat.size() ? ids[j] : 0u, t = of_material[tri_mat[id]];
+        const uint32_t di = t == PT_NO_TEXTURE ? PT_NO_TEXTURE : desc_of[t];
+        std::memcpy(&rows[j * 8], &uvs[(size_t)id * 6], 6 * sizeof(float));
+        std::memcpy(&rows[j * 8 + 6], &di, 4);
+        rows[j * 8 + 7] = 0.f;
+    }
+    std::vector<uint4> desc(used.size());
+    uint64_t total = 0;
+    for (size_t k = 0; k < used.size(); ++k) {
+        const Texture &T = tex[used[k]];
+        desc[k] = uint4{ (uint32_t)total, T.width, T.height, T.flags };
+        total += (uint64_t)T.width * T.height; // <= 64 * 2^24 texels: the first texel fits 32 bits
+        dev_bytes[used[k]] = (uint64_t)T.width * T.height * sizeof(float4);
+    }
+    HIP_TRY(c, hipSetDevice(context_device(c)));
+    HIP_TRY(c, d_uv.ensure(rows.size() / 4)); HIP_TRY(c, d_desc.ensure(desc.size())); HIP_TRY(c, d_texels.ensure((size_t)total));
+    HIP_TRY(c, hipMemcpy(d_uv.p, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d_desc.p, desc.data(), desc.size() * sizeof(uint4), hipMemcpyHostToDevice));
+    std::vector<float> t4;
+    for (size_t k = 0; k < used.size(); ++k) { // one texture at a time: the staging copy stays one texture large
+        const Texture &T = tex[used[k]];
+        const size_t n = (size_t)T.width * T.height;
+        t4.assign(n * 4, 0.f);
+        for (size_t i = 0; i < n; ++i) { t4[i * 4] = T.rgb[i * 3]; t4[i * 4 + 1] = T.rgb[i * 3 + 1]; t4[i * 4 + 2] = T.rgb[i * 3 + 2]; }
+        HIP_TRY(c, hipMemcpy(d_texels.p + desc[k].x, t4.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+    }
+    n_desc = (uint32_t)used.size();
+    return PT_OK;
+}
+
 uint64_t ptrt::next_scene_serial()
 {
     static std::atomic<uint64_t> last{ 0 };
@@ -366,6 +439,69 @@ pt_status pt_scene_set_materials(pt_scene *s, const pt_material *mats, uint64_t 
     return PT_OK;
 }
 
+pt_status pt_scene_set_triangle_uvs(pt_scene *s, const float *uv6, uint64_t count)
+{
+    if (!s) return fail(nullptr, PT_ERR_INVALID_ARGUMENT, "scene is NULL");
+    if (count && !uv6) return fail(s->ctx, PT_ERR_INVALID_ARGUMENT, "pt_scene_set_triangle_uvs: uv6 is NULL");
+    if (count >= (1ull << 28)) return fail(s->ctx, PT_ERR_UNSUPPORTED, "more than 2^28 triangles");
+    for (uint64_t i = 0; i < count * 6; ++i)
+        if (!(std::fabs(uv6[i]) <= 1048576.0f)) // (a NaN fails the comparison too)
+            return fail(s->ctx, PT_ERR_INVALID_ARGUMENT, "pt_scene_set_triangle_uvs: float %llu is not finite or beyond 2^20", (unsigned long long)i);
+    SceneTextures &T = s->textures;
+    if (count) T.uvs.assign(uv6, uv6 + count * 6); else T.uvs.clear();
+    T.have_uvs = count != 0; // (NULL, 0) and (non-NULL, 0) both leave a scene without UVs
+    s->committed = false;
+    return PT_OK;
+}
+
+pt_status pt_scene_set_texture(pt_scene *s, uint32_t index, const float *rgb, uint32_t width, uint32_t height, uint32_t flags)
+{
+    if (!s) return fail(nullptr, PT_ERR_INVALID_ARGUMENT, "scene is NULL");
+    pt_context *c = s->ctx;
+    if (index >= PT_MAX_TEXTURES) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_scene_set_texture: index %u, the limit is PT_MAX_TEXTURES = %u", index, PT_MAX_TEXTURES);
+    SceneTextures::Texture &T = s->textures.tex[index];
+    if (!rgb && width == 0 && height == 0) {
+        if (flags) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_scene_set_texture: flags 0x%x with nothing to set", flags);
+        T = SceneTextures::Texture{}; s->committed = false;
+        return PT_OK;
+    }
+    if (!rgb) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_scene_set_texture: rgb is NULL");
+    if (width < 1 || width > 4096 || height < 1 || height > 4096) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_scene_set_texture: %u x %u texels, each side must be in [1, 4096]", width, height);
+    if (flags & ~(uint32_t)PT_TEXTURE_NEAREST) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_scene_set_texture: unknown flag bits 0x%x", flags & ~(uint32_t)PT_TEXTURE_NEAREST);
+    const size_t n = (size_t)width * height * 3;
+    for (size_t i = 0; i < n; ++i)
+        if (!(std::isfinite(rgb[i]) && rgb[i] >= 0.f)) return fail(c, PT_ERR_INVALID_ARGUMENT, "pt_scene_set_texture: component %llu is not finite and >= 0", (unsigned long long)i);
+    T.rgb.assign(rgb, rgb + n); T.width = width; T.height = height; T.flags = flags;
+    s->committed = false;
+    return PT_OK;
+}
+
+pt_status pt_scene_set_material_textures(pt_scene *s, const uint32_t *texture_of_material, uint64_t count)
+{
+    if (!s) return fail(nullptr, PT_ERR_INVALID_ARGUMENT, "scene is NULL");
+    if (count && !texture_of_material) return fail(s->ctx, PT_ERR_INVALID_ARGUMENT, "pt_scene_set_material_textures: texture_of_material is NULL");
+    for (uint64_t i = 0; i < count; ++i)
+        if (texture_of_material[i] != PT_NO_TEXTURE && texture_of_material[i] >= PT_MAX_TEXTURES)
+            return fail(s->ctx, PT_ERR_INVALID_ARGUMENT, "pt_scene_set_material_textures: material %llu: texture index %u, the limit is PT_MAX_TEXTURES = %u", (unsigned long long)i, texture_of_material[i], PT_MAX_TEXTURES);
+    SceneTextures &T = s->textures;
+    if (count) T.of_material.assign(texture_of_material, texture_of_material + count); else T.of_material.clear();
+    T.have_binding = count != 0;
+    s->committed = false;
+    return PT_OK;
+}
+
+pt_status pt_scene_texture_info(const pt_scene *s, uint32_t index, pt_texture_info *out)
+{
+    if (!s || !out) return fail(s ? s->ctx : nullptr, PT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (index >= PT_MAX_TEXTURES) return fail(s->ctx, PT_ERR_INVALID_ARGUMENT, "pt_scene_texture_info: index %u, the limit is PT_MAX_TEXTURES = %u", index, PT_MAX_TEXTURES);
+    const SceneTextures::Texture &T = s->textures.tex[index];
+    std::memset(out, 0, sizeof *out);
+    out->width = T.width; out->height = T.height; out->flags = T.flags;
+    out->materials = T.width ? s->textures.bound_materials(index) : 0u;
+    out->device_bytes = s->committed ? s->textures.device_bytes(index) : 0u;
+    return PT_OK;
+}
+
 pt_status pt_scene_set_camera(pt_scene *s, const pt_camera *cam)
 {
     if (!s || !cam) return fail(s ? s->ctx : nullptr, PT_ERR_INVALID_ARGUMENT, "NULL argument");
@@ -426,7 +562,7 @@ static pt_status check_commit(const pt_scene *s, uint32_t &bvh_width, bool &lbvh
     if ((nt || ns) && nm == 0) return fail(c, PT_ERR_INVALID_ARGUMENT, "primitives but no materials");
     for (uint32_t i = 0; i < nt; ++i) if (s->tri_mat[i] >= nm) return fail(c, PT_ERR_INVALID_ARGUMENT, "triangle %u: material id %u >= %u", i, s->tri_mat[i], nm);
     for (uint32_t i = 0; i < ns; ++i) if (s->sph_mat[i] >= nm) return fail(c, PT_ERR_INVALID_ARGUMENT, "sphere %u: material id %u >= %u", i, s->sph_mat[i], nm);
-    return PT_OK;
+    return s->textures.check(c, nt, nm); // docs/SPEC.md §13: the UV count, the binding's count and what it names
 }
 
 // Build tree: the hierarchy and its blob from the scene's current vertices, by one of three builders; the tree owner adopts the blob
@@ -536,8 +672,14 @@ pt_status pt_scene_commit(pt_scene *s, uint32_t bvh_width)
     s->serial = next_scene_serial(); s->updates = 0; // a new tree: nothing recorded from the old one describes it
     s->cache.invalidate(); // level lists, guide index and what earlier frames measured belong to the tree this commit replaces
     if ((st = build_tree(s, bvh_width, lbvh, clock)) != PT_OK) return st;
-    if (!s->ctx) { s->committed = true; return PT_OK; } // detached scene: host-side blob only
+    if (!s->ctx) { // detached scene: host-side blob only
+        if ((st = s->textures.commit(nullptr, s->tri_mat, s->tree)) != PT_OK) return st;
+        s->committed = true; return PT_OK;
+    }
     if ((st = s->tree.upload(s->ctx, clock)) != PT_OK || (st = upload_primitives(s, clock)) != PT_OK || (st = light_table(s, clock)) != PT_OK) return st;
+    // docs/SPEC.md §13: behind the tree, which it reads (the blob order) and does not touch — the same tree and blob with and without textures
+    if ((st = s->textures.commit(s->ctx, s->tri_mat, s->tree)) != PT_OK) return st;
+    clock.lap("textures");
     // the root's boxes as the device holds them, whichever builder made them (frame.cpp scene_pixels)
     HIP_TRY(s->ctx, s->tree.fetch_root(context_stream(s->ctx))); HIP_TRY(s->ctx, hipStreamSynchronize(context_stream(s->ctx)));
     s->tree.root_fetched();

@@ -1,5 +1,5 @@
-// scene.h — pt_scene, and one owner each for the two things a committed scene keeps on both sides of the bus: its tree and its
-// vertices. Which copy is current is private to the owner; nobody else keeps a flag about it. Private to scene.cpp, frame.cpp,
+// scene.h — pt_scene, and one owner each for the things a committed scene keeps on both sides of the bus: its tree, its vertices and its
+// textures. Which copy is current is private to the owner; nobody else keeps a flag about it. Private to scene.cpp, frame.cpp,
 // query.cpp and denoise_host.cpp; the context a scene belongs to and the helpers every public call uses are context.h's.
 #pragma once
 #include "context.h"
@@ -88,6 +88,37 @@ private:
     mutable bool dev_current = false; // dev[cur] holds the scene's vertices (an update's, or device()'s upload of the host vector)
 };
 
+// A scene's albedo textures (docs/SPEC.md §13): the per-triangle UVs, the textures and the per-material binding as the three setters left
+// them (host side, scene content like the triangles: they take effect with pt_scene_commit), and the one device copy of each that a commit
+// of a textured scene makes — the UV rows in blob order with every triangle's material resolved to its texture, the descriptors and the
+// texels. Whether the committed scene is textured is this owner's to say; nobody else keeps a flag about it.
+class SceneTextures {
+public:
+    struct Texture { uint32_t width = 0, height = 0, flags = 0; std::vector<float> rgb; }; // width 0: not set
+    std::vector<float> uvs;                  // 6 floats per triangle; empty with !have_uvs
+    bool have_uvs = false;
+    Texture tex[PT_MAX_TEXTURES];
+    std::vector<uint32_t> of_material;       // a texture index or PT_NO_TEXTURE per material; empty with !have_binding
+    bool have_binding = false;
+
+    // pt_scene_commit's check: the counts against the scene's, every bound index against the textures that are set
+    pt_status check(pt_context *c, size_t n_tris, size_t n_mats) const;
+    // pt_scene_commit: decides textured() for the scene being committed and, with a context, builds and uploads the device copy from the
+    // committed tree's original ids (blob order) and the triangles' materials
+    pt_status commit(pt_context *c, const std::vector<uint32_t> &tri_mat, const CommittedTree &tree);
+    bool textured() const { return textured_; }
+    TexArgs args() const { return TexArgs{ d_uv.p, d_desc.p, d_texels.p, n_desc, 0u }; }
+    uint64_t device_bytes(uint32_t index) const { return dev_bytes[index]; }
+    uint32_t bound_materials(uint32_t index) const;
+
+private:
+    bool textured_ = false;
+    uint32_t n_desc = 0;
+    uint64_t dev_bytes[PT_MAX_TEXTURES] = {};
+    DevBuf<float4> d_uv, d_texels;
+    DevBuf<uint4> d_desc;
+};
+
 struct ExtendChoice {           // what a scene remembers of the extend-kernel probe (frame.cpp ExtendFrame)
     uint32_t kernel = 0;        // the ExtendKernel an earlier frame picked (0 = none yet)
     double rate_simple = 0.0, rate_packed = 0.0; // rays per ms of whole frames run on one kernel (frames too short to probe inside)
@@ -130,6 +161,7 @@ struct pt_scene {
                                          // scene content in the commit's sense: set, replaced and removed at any time, kept by commits and updates
     pt_lens lens{};                      // pt_scene_set_lens (docs/SPEC.md §3.1); radius 0 = none. Like `sky` host values only, read by every pt_render:
                                          // set and removed at any time, kept by commits, updates and pt_scene_set_camera
+    ptrt::SceneTextures textures;        // pt_scene_set_triangle_uvs / _texture / _material_textures (docs/SPEC.md §13)
     bool have_cam = false, committed = false;
     ptrt::CommittedTree tree;
     mutable ptrt::CommitCaches cache;    // (mutable: pt_render and pt_denoise fill it through the const scene they receive)

@@ -49,6 +49,10 @@ class SceneData:
     cam: N.pt_camera = field(default_factory=N.pt_camera)
     sky: np.ndarray = field(default_factory=lambda: np.zeros(3, np.float32))
     environment: np.ndarray = None  # optional n x n x 3 octahedral map (docs/SPEC.md §11); SetScene applies it
+    # Albedo textures (docs/SPEC.md §13), all optional; SetScene passes them on before the commit
+    uvs: np.ndarray = None                # (triangles, 6): (s, t) at v0, v1, v2
+    textures: dict = None                 # index -> H x W x 3 linear RGB, or (H x W x 3, flags) with flags = native.PT_TEXTURE_NEAREST
+    material_textures: np.ndarray = None  # (materials,): a texture index or native.PT_NO_TEXTURE
 
 
 def _octahedral_directions(n, sub):
@@ -91,6 +95,17 @@ def sun_sky_environment(n, sun_dir, sun_rgb, sun_cos, sky_rgb, sub=4):
     d = _octahedral_directions(n, sub)
     inside = ((d @ s) >= sun_cos)[..., None]
     return _octahedral_mean(np.asarray(sky_rgb, np.float64) + inside * np.asarray(sun_rgb, np.float64), n, sub)
+
+
+def texture_from_srgb8(img):
+    """An H x W x 3 (or 4: alpha dropped) uint8 sRGB image as the linear-RGB float32 texels pt_scene_set_texture takes: the sRGB
+    electro-optical transfer function, decoded here on the host (the device never sees an encoded texel)."""
+    a = np.asarray(img)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] not in (3, 4):
+        raise ValueError(f"texture_from_srgb8 takes an H x W x 3 or 4 uint8 image, got {a.dtype} {a.shape}")
+    c = a[..., :3].astype(np.float64) / 255.0
+    lin = np.where(c <= 0.04045, c / 12.92, ((c + 0.055) / 1.055) ** 2.4)
+    return np.ascontiguousarray(lin, np.float32)
 
 
 def make_scene(kind, detail=0, seed=0x5EED0001, width=1920, height=1080):
@@ -220,7 +235,54 @@ class Renderer:
         _check(N.lib.pt_scene_set_sky(s, C.byref(sky)), ctx)
         if getattr(scene, "environment", None) is not None:
             self.SetEnvironment(scene.environment)
+        self._set_textures(scene)
         _check(N.lib.pt_scene_commit(s, bvh_width), ctx)
+
+    def _set_textures(self, scene):
+        """docs/SPEC.md §13: a SceneData's uvs, textures and material_textures, before the commit that makes them take effect."""
+        s, ctx = self._scene, self._ctx
+        if getattr(scene, "uvs", None) is not None:
+            uv = np.ascontiguousarray(scene.uvs, np.float32).reshape(-1, 6)
+            _check(N.lib.pt_scene_set_triangle_uvs(s, _ptr(uv), len(uv)), ctx)
+        for index, t in sorted((getattr(scene, "textures", None) or {}).items()):
+            img, flags = t if isinstance(t, tuple) else (t, 0)
+            a = np.ascontiguousarray(img, np.float32)
+            if a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError(f"texture {index} must be H x W x 3, got {a.shape}")
+            _check(N.lib.pt_scene_set_texture(s, index, _ptr(a), a.shape[1], a.shape[0], flags), ctx)
+        if getattr(scene, "material_textures", None) is not None:
+            mt = np.ascontiguousarray(scene.material_textures, np.uint32)
+            _check(N.lib.pt_scene_set_material_textures(s, _ptr(mt), len(mt)), ctx)
+
+    def SetTriangleUVs(self, uvs):
+        """(triangles, 6) per-triangle UVs of the current scene, or None to remove them; takes effect with the next Commit()."""
+        uv = None if uvs is None else np.ascontiguousarray(uvs, np.float32).reshape(-1, 6)
+        _check(N.lib.pt_scene_set_triangle_uvs(self._scene, _ptr(uv), 0 if uv is None else len(uv)), self._ctx)
+
+    def SetTexture(self, index, img, flags=0):
+        """Texture `index` of the current scene: H x W x 3 linear RGB, or None to remove it; takes effect with the next Commit()."""
+        if img is None:
+            _check(N.lib.pt_scene_set_texture(self._scene, index, None, 0, 0, 0), self._ctx)
+            return
+        a = np.ascontiguousarray(img, np.float32)
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError(f"texture {index} must be H x W x 3, got {a.shape}")
+        _check(N.lib.pt_scene_set_texture(self._scene, index, _ptr(a), a.shape[1], a.shape[0], flags), self._ctx)
+
+    def SetMaterialTextures(self, texture_of_material):
+        """One texture index or native.PT_NO_TEXTURE per material, or None to remove the binding; takes effect with the next Commit()."""
+        mt = None if texture_of_material is None else np.ascontiguousarray(texture_of_material, np.uint32)
+        _check(N.lib.pt_scene_set_material_textures(self._scene, _ptr(mt), 0 if mt is None else len(mt)), self._ctx)
+
+    def Commit(self, bvh_width=0):
+        """pt_scene_commit of the current scene: what the setters above changed takes effect."""
+        _check(N.lib.pt_scene_commit(self._scene, bvh_width), self._ctx)
+
+    def TextureInfo(self, index):
+        """pt_texture_info of texture `index` of the current scene (width 0: not set)."""
+        info = N.pt_texture_info()
+        _check(N.lib.pt_scene_texture_info(self._scene, index, C.byref(info)), self._ctx)
+        return info
 
     def SetEnvironment(self, rgb):
         """Give the current scene an environment map (include/ptrt.h pt_scene_set_environment: n x n x 3 floats, octahedral layout,
