@@ -46,6 +46,8 @@ SYMBOLS = {
     "tr_lookup": (None, [C.POINTER(tr_texture), C.c_float, C.c_float, _f3]),
     "tr_barycentrics": (None, [_f9, _f3, _f3, _f2]),
     "tr_coordinate": (None, [_f6, C.c_float, C.c_float, _f2]),
+    "tr_coordinate_many": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "tr_lookup_many": (None, [C.POINTER(tr_texture), C.c_void_p, C.c_size_t, C.c_void_p]),
     "tr_render": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(tr_textures), C.c_int, C.c_void_p, C.POINTER(tr_stats)]),
 }
 PIPELINE_SYMBOLS = {
@@ -101,6 +103,23 @@ def coordinate(uv6, u, v):
     st = _f2()
     build().tr_coordinate(_f6(*[float(x) for x in uv6]), float(u), float(v), st)
     return np.float32(st[0]), np.float32(st[1])
+
+
+def lookup_many(img, uv6, u, v, flags=0):
+    """(n, 3) texels and (n, 2) coordinates: coordinate() then lookup() for every row of uv6 (n, 6) with barycentrics u, v (n,)."""
+    T, keep = _texture(img, flags)
+    q, u, v = (np.ascontiguousarray(a, np.float32) for a in (uv6, u, v))
+    assert q.shape == (len(u), 6) and u.shape == v.shape
+    st, out = np.empty((len(u), 2), np.float32), np.empty((len(u), 3), np.float32)
+    build().tr_coordinate_many(q.ctypes.data, u.ctypes.data, v.ctypes.data, len(u), st.ctypes.data)
+    build().tr_lookup_many(C.byref(T), st.ctypes.data, len(u), out.ctypes.data)
+    return out, st
+
+
+def barycentrics_many(v9, o, d):
+    """(u, v) float32 arrays of barycentrics() over rows of v9 (n, 9), o and d (n, 3)."""
+    uv = np.array([barycentrics(a, b, c) for a, b, c in zip(v9, o, d)], np.float32).reshape(-1, 2)
+    return uv[:, 0].copy(), uv[:, 1].copy()
 
 
 def split_texture(t):

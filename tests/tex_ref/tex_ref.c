@@ -96,6 +96,18 @@ void tr_coordinate(const float uv6[6], float u, float v, float st[2])
     st[1] = fma_(v, uv6[5], fma_(u, uv6[3], w0 * uv6[1]));
 }
 
+/* tr_coordinate and tr_lookup over n points, for tests that ask a few hundred thousand times: plain loops, no arithmetic of their own.
+ * uv6: 6 floats per point; st: 2 per point; out: 3 per point. */
+void tr_coordinate_many(const float *uv6, const float *u, const float *v, size_t n, float *st)
+{
+    for (size_t i = 0; i < n; ++i) tr_coordinate(uv6 + i * 6, u[i], v[i], st + i * 2);
+}
+
+void tr_lookup_many(const tr_texture *T, const float *st, size_t n, float *out)
+{
+    for (size_t i = 0; i < n; ++i) tr_lookup(T, st[i * 2], st[i * 2 + 1], out + i * 3);
+}
+
 /* the texture a hit of triangle `id` looks up, or NULL */
 static const tr_texture *texture_of(const pto_scene *s, const tr_textures *X, uint32_t id)
 {
